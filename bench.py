@@ -1,22 +1,26 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json's metric.
 
-    python bench.py --gpus 1 --steps K --warmup W [--config c1|c2|c3]
+    python bench.py --gpus 1 --steps K --warmup W [--config c1|c2|c3|c4] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 --config c1 (default, the headline: BASELINE config[1], the configuration `metric` is quoted on).  One step = one pass of
   the hot path over a batch of synthetic rays resident in HBM: PowerSampler bins (S1) + ray ordering pass (one launch)
   -> fused hash-grid lookup + tiny MLPs (fp32 MFMA) + transmittance/alpha compositing (F1+C1+C2, nrhip_render_fwd_ex).
   4096 rays x 128 samples, HashEncoding(16 levels, T=2^19, F=2) + 64-wide MLPs, fp32 table.  Rays shard across ranks
-  with no data-path collective (inference needs none) -> weak scaling.  The same JSON line carries
-  `roofline` (dominant kernel, HIP-event timed inside the timed region), `train` (iters/s of the config-1 field),
-  `train_full` (iters/s of the whole NeuRAD-default training step on BASELINE config[3]'s camera+lidar joint batch,
-  40 960 + 16 384 rays per GPU, incl. losses, gradient exchange and Adam -- the train-iters/sec half of the metric) and,
-  at N=1, `cpu_baseline` = the reference's own torch field eval timed live on this host's cores (kind "reference": the tree
-  is /root/reference in the build container, the byte-compiled oracle/_ref on the GPU box) with `cpu_port_c` (C/OpenMP port
-  of the oracle, the parity checker) beside it; without a reference tree: `cpu_baseline` = the C port (kind "port"),
-  `reference_torch_cpu` = the figure recorded in the build container, `reference_torch_cpu_port_here` = the torch op
-  sequence restated in oracle/torch_cpu_port.py timed on this host.
+  with no data-path collective (inference needs none) -> weak scaling.  A plain run sets up, warms up, times
+  exactly K steps and prints the headline line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`).
+  With --full the same JSON line also carries `device_state`, `roofline` (dominant kernel, HIP-event timed inside the
+  timed region) and the render kernel's labelled variants, `train` (iters/s of the config-1 field), `train_full` (iters/s
+  of the whole NeuRAD-default training step on BASELINE config[3]'s camera+lidar joint batch, 40 960 + 16 384 rays per
+  GPU, incl. losses, gradient exchange and Adam -- the train-iters/sec half of the metric) and, at N=1, `cpu_baseline` =
+  the reference's own torch field eval timed live on this host's cores (kind "reference": the reference's source tree
+  where it is present, else the byte-compiled oracle/_ref) with `cpu_port_c` (C/OpenMP port of the oracle, the parity
+  checker) beside it; without a reference tree: `cpu_baseline` = the C port (kind "port"), `reference_torch_cpu` = the
+  recorded figure, `reference_torch_cpu_port_here` = the torch op sequence restated in oracle/torch_cpu_port.py timed on
+  this host; `parity_rel_l2_vs_oracle` last.
+--dump-outputs DIR (any config but c3 --via-plugin-only): after the timed steps, what the timed step computed in its last
+  step on rank 0 as DIR/<name>.npy (dump_outputs); the inputs are seeded, the same in every run with the same arguments.
 --config c2: BASELINE config[2], 8192 camera rays through the fused proposal sampler (2 rounds) + fused field/compositing
   with NeuRAD's default grids; roofline on the proposal sampler kernel (192 B per proposal evaluation).
 --config c3: the `train_full` step as the timed step.
@@ -129,6 +133,31 @@ def timed(step, steps, warmup, world, device):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     return el
+
+
+DUMP_BUDGET_BYTES = 60 * 2**20  # data of all arrays: under 64 MB with the .npy headers
+DUMP_SAMPLE_SEED = 20251016
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: what the timed path computed in its last step, one DIR/<name>.npy per array -- float64 stays float64,
+    every other floating dtype as float32, integers and booleans as float64 (exact below 2^53).  When the arrays together
+    exceed DUMP_BUDGET_BYTES, each one larger than its share (DUMP_BUDGET_BYTES / number of arrays) is replaced by a fixed
+    sample of its flattened elements: the sorted indices np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False),
+    the same in every run."""
+    os.makedirs(directory, exist_ok=True)
+    out_dtype = {name: torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64
+                 for name, t in arrays.items()}
+    nbytes = {name: t.numel() * (4 if out_dtype[name] == torch.float32 else 8) for name, t in arrays.items()}
+    total = sum(nbytes.values())
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        if total > DUMP_BUDGET_BYTES and nbytes[name] > share:
+            k = share // (nbytes[name] // t.numel())
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(t.numel(), k, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(directory, f"{name}.npy"), t.to(out_dtype[name]).cpu().numpy())
 
 
 def _fused(cls, params, **kw):
@@ -418,7 +447,8 @@ def torch_op_attribution(step_fn, path, n=2):
 
 
 def train_full_section(device, rank, world, steps, warmup, n_cam=C3_CAMERA_RAYS, n_lidar=C3_LIDAR_RAYS, rgb_decoder=True,
-                       cfg_edit=None, sharded_adam=False, sparse_exchange=False, torch_decoder=False, graph=True):
+                       cfg_edit=None, sharded_adam=False, sparse_exchange=False, torch_decoder=False, graph=True,
+                       dump_dir=None):
     """The whole training step at the reference's default sizes (models/neurad.py defaults: static grid L=8, F=4, T=2^22;
     proposal grids L=6, F=1, T=2^20; 128+64 proposal samples, 32 field samples; 32-wide MLPs; 16-d appearance embedding;
     lidar head; RGB CNN decoder) on a camera+lidar joint batch: get_nff_outputs (training mode, jitter, lidar metadata) ->
@@ -520,6 +550,11 @@ def train_full_section(device, rank, world, steps, warmup, n_cam=C3_CAMERA_RAYS,
     allocs1 = _device_allocs()
     host_issue_ms = LAST_ISSUE.get("s_per_step", 0.0) * 1e3
     assert torch.isfinite(state["loss"]), "non-finite loss"
+    if dump_dir and rank == 0:
+        # what the last timed step hands back: its loss and the parameters it updated
+        named = [(f"model.{n}", p) for n, p in m.named_parameters() if p.requires_grad]
+        named += [] if dec is None else [(f"rgb_decoder.{n}", p) for n, p in dec.named_parameters()]
+        dump_outputs(dump_dir, dict([("loss", state["loss"])] + named))
     exchanged_bytes = state["bytes"]
     if os.environ.get("NRHIP_BENCH_TORCH_PROFILE") and rank == 0:
         torch_op_attribution(step, os.environ["NRHIP_BENCH_TORCH_PROFILE"] + ".train_full")
@@ -888,11 +923,11 @@ def bench_c1(args, device, rank, world):
     depth = torch.empty((R_RAYS, 1), device=device)
     acc = torch.empty((R_RAYS, 1), device=device)
     state = {}
-    # HIP events around the render kernel on every 4th timed step (each record is a marker packet in the queue: on every
-    # step they cost ~1.5 % of it)
+    # --full: HIP events around the render kernel on every 4th timed step for the roofline (each record is a marker packet in
+    # the queue: on every step they cost ~1.5 % of it).  A plain run records none.
     ev_every = 4
     events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-              for _ in range((args.steps + ev_every - 1) // ev_every)]
+              for _ in range((args.steps + ev_every - 1) // ev_every)] if args.full else []
 
     def step(i=None):
         # M1 sky stretch (models/neurad.py:451-455) folded into the sampler launch; far == sky_distance here anyway
@@ -902,7 +937,7 @@ def bench_c1(args, device, rank, world):
         # the two event waits cost more than the kernel.)
         sp, eu, order = ops.power_sampler_ordered(None, fars, S, origins, dirs, STATIC_SCALE, lam=-1.0, scaling=0.1,
                                                   last_edge=20000.0)
-        timed_kernel = i is not None and i % ev_every == 0
+        timed_kernel = args.full and i is not None and i % ev_every == 0
         if timed_kernel:
             events[i // ev_every][0].record()
         ops.render_fwd(fs, origins, dirs, area, eu[:, :-1], eu[:, 1:], out=(feats, depth, acc), order=order)
@@ -912,20 +947,12 @@ def bench_c1(args, device, rank, world):
 
     elapsed = timed(step, args.steps, args.warmup, world, device)
     assert torch.isfinite(feats).all() and torch.isfinite(acc).all()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives: the sampler's bin edges and the render kernel's outputs
+        dump_outputs(args.dump_outputs, {"features": feats, "depth": depth, "accumulation": acc, "bin_edges": state["edges"]})
     n_samples = R_RAYS * S
     out = None
     if rank == 0:
-        # Events bracket every 4th launch, starting with the first of the timed region -- and that one is not like the others:
-        # it follows the contract's synchronize (a system-scope release: the table's lines leave the L2) and runs ~170 us
-        # against ~142 us for every later launch.  Sampled 1 in 4 it would weigh 4 x what it does among the K launches; the
-        # average launch duration over the timed region weighs it 1 / K.
-        ts = [a.elapsed_time(b) for a, b in events]
-        kernel_ms = float(ts[0] if len(ts) == 1 else (ts[0] + (args.steps - 1) * np.mean(ts[1:])) / args.steps)
-        if os.environ.get("NRHIP_BENCH_DUMP_EVENTS"):
-            print("kernel us per timed event:", [round(t * 1e3, 1) for t in ts], file=sys.stderr)
-        bytes_per = algorithmic_bytes_per_sample(GRID["num_levels"], GRID["features_per_level"], 4, S)
-        achieved = n_samples * bytes_per / (kernel_ms * 1e-3) / 1e9
-        traffic = recorded_traffic("render_kernel")
         out = {
             "metric": "ray-samples/sec (4096 rays x 128 samples)", "value": world * n_samples * args.steps / elapsed,
             "unit": "ray-samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -937,17 +964,30 @@ def bench_c1(args, device, rank, world):
                        "rays_per_gpu": R_RAYS, "samples_per_ray": S, "parallelism": f"rays sharded x{world}, no collective"},
             "per_gpu_value": n_samples * args.steps / elapsed,
             "target_per_gpu": 2e7,
-            "roofline": {"kernel": "nrhip::render_kernel<16,2,64,fp32,composite,pairs> (software-pipelined gathers, "
-                                   "XCD-coherent ray ranges over the nrhip_ray_order permutation, MLP products as fp16 "
-                                   "pairs with fp32 accumulation)", "bound": "hbm",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "algorithmic_bytes_per_launch": n_samples * bytes_per,
-                         "kernel_ms": kernel_ms, "kernel_ms_plain_mean": float(np.mean(ts)),
-                         "frac_at_the_plain_mean": n_samples * bytes_per / (float(np.mean(ts)) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "kernel_ms_how": f"HIP events around every 4th of the {args.steps} timed launches; the first one (right after "
-                                          f"the synchronize, {ts[0] * 1e3:.1f} us) weighted 1 / {args.steps}, the others' mean "
-                                          f"({float(np.mean(ts[1:]) if len(ts) > 1 else ts[0]) * 1e3:.1f} us) {args.steps - 1} / {args.steps}"},
         }
+    if rank == 0 and args.full:
+        # Events bracket every 4th launch, starting with the first of the timed region -- and that one is not like the others:
+        # it follows the contract's synchronize (a system-scope release: the table's lines leave the L2) and runs ~170 us
+        # against ~142 us for every later launch.  Sampled 1 in 4 it would weigh 4 x what it does among the K launches; the
+        # average launch duration over the timed region weighs it 1 / K.
+        ts = [a.elapsed_time(b) for a, b in events]
+        kernel_ms = float(ts[0] if len(ts) == 1 else (ts[0] + (args.steps - 1) * np.mean(ts[1:])) / args.steps)
+        if os.environ.get("NRHIP_BENCH_DUMP_EVENTS"):
+            print("kernel us per timed event:", [round(t * 1e3, 1) for t in ts], file=sys.stderr)
+        bytes_per = algorithmic_bytes_per_sample(GRID["num_levels"], GRID["features_per_level"], 4, S)
+        achieved = n_samples * bytes_per / (kernel_ms * 1e-3) / 1e9
+        traffic = recorded_traffic("render_kernel")
+        out["roofline"] = {"kernel": "nrhip::render_kernel<16,2,64,fp32,composite,pairs> (software-pipelined gathers, "
+                                     "XCD-coherent ray ranges over the nrhip_ray_order permutation, MLP products as fp16 "
+                                     "pairs with fp32 accumulation)", "bound": "hbm",
+                           "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                           "traffic": traffic, "algorithmic_bytes_per_launch": n_samples * bytes_per,
+                           "kernel_ms": kernel_ms, "kernel_ms_plain_mean": float(np.mean(ts)),
+                           "frac_at_the_plain_mean": n_samples * bytes_per / (float(np.mean(ts)) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                           "kernel_ms_how": f"HIP events around every 4th of the {args.steps} timed launches; the first one (right "
+                                            f"after the synchronize, {ts[0] * 1e3:.1f} us) weighted 1 / {args.steps}, the others' "
+                                            f"mean ({float(np.mean(ts[1:]) if len(ts) > 1 else ts[0]) * 1e3:.1f} us) "
+                                            f"{args.steps - 1} / {args.steps}"}
         # two NON-headline variants of the same kernel on the same batch (labelled; the headline stays fp32 / exact):
         # fp16 table storage (BASELINE config 5's layout) and eval-time early ray termination at transmittance 1e-4
         def kernel_us(fspec, **kw):
@@ -1035,6 +1075,8 @@ def bench_c2(args, device, rank, world):
 
     elapsed = timed(step, args.steps, args.warmup, world, device)
     assert torch.isfinite(state["out"][0]).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("features", "depth", "accumulation"), state["out"])))
     if rank != 0:
         return None
     s = m.config.sampling
@@ -1295,6 +1337,8 @@ def bench_c4(args, device, rank, world):
     finally:
         ops.render_fwd_actors, ops.proposal_sampler_fwd = real_render, real_sampler
     assert torch.isfinite(state["out"]["features"]).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v for k, v in state["out"].items() if torch.is_tensor(v)})
     S = m.config.sampling.num_nerf_samples
     n_field = R * S
     # algorithmic bytes of the render stage: 512 B of fp16 table reads per sample (8 levels x 8 corners x 4 features x 2 B;
@@ -1477,7 +1521,17 @@ def main():
     ap.add_argument("--via-plugin-only", action="store_true", help="c3: time only the --via-plugin step (kernel traces)")
     ap.add_argument("--train-steps", type=int, default=60)
     ap.add_argument("--train-full-steps", type=int, default=30, help="0 skips the train_full section")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the line can carry: the device state under load and, for c1, "
+                         "the roofline and the render kernel's variants, the train / train_full sections, the CPU baselines and "
+                         "the parity check against the oracle (without it a c1 run sets up, warms up, times --steps steps and "
+                         "prints the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed step computed in its last step (rank 0) as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: larger outputs as a fixed, seeded sample)")
     args = ap.parse_args()
+    if args.dump_outputs and args.config == "c3" and args.via_plugin_only:
+        ap.error("--dump-outputs is not supported with --via-plugin-only")
     global WIRE_DTYPE
     WIRE_DTYPE = torch.bfloat16 if args.wire_bf16 else None
 
@@ -1530,14 +1584,14 @@ def main():
             rccl = None
         dist_info = {"backend": backend, "rccl_version": rccl, "devices": [f"{h}:{i}" for h, i, _ in everyone],
                      "env": {k: v for k, v in os.environ.items() if k.startswith(("NCCL_", "RCCL_", "HSA_", "HIP_VISIBLE", "ROCR_VISIBLE"))}}
-    dev_state = device_state(dev_index) if rank == 0 else None
+    dev_state = device_state(dev_index) if rank == 0 and args.full else None
 
     if args.config == "c2":
         out = bench_c2(args, device, rank, world)
     elif args.config == "c4":
         out = bench_c4(args, device, rank, world)
     elif args.config == "c3" and args.via_plugin_only:  # (profiling runs: only the plugin's step in the kernel trace)
-        steps = min(args.steps, 50)
+        steps = args.steps
         vp = train_via_plugin_section(device, rank, world, steps, max(2, min(args.warmup, 5)))
         out = {"metric": "train iters/sec (camera+lidar joint batch), the step as `ns-train neurad-hip` executes it",
                "value": vp.get("rays_per_sec"), "unit": "rays/s", "n_gpus": world, "steps": steps,
@@ -1545,10 +1599,10 @@ def main():
                "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                "config": {"workload": vp.get("what")}, "train_via_plugin": vp}
     elif args.config == "c3":
-        steps = min(args.steps, 50)
+        steps = args.steps
         tf = train_full_section(device, rank, world, steps, max(2, min(args.warmup, 5)), rgb_decoder=not args.no_rgb_decoder,
                                 sharded_adam=args.sharded_adam, sparse_exchange=args.sparse_exchange,
-                                torch_decoder=args.torch_decoder, graph=not args.no_graph)
+                                torch_decoder=args.torch_decoder, graph=not args.no_graph, dump_dir=args.dump_outputs)
         out = {"metric": "train iters/sec (camera+lidar joint batch)", "value": tf["rays_per_sec"], "unit": "rays/s",
                "n_gpus": world, "steps": steps, "warmup": max(2, min(args.warmup, 5)), "ms_per_step": tf["ms_per_iter"],
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -1579,7 +1633,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 return {"error": f"{type(e).__name__}: {e}"[:500]}
 
-        if not args.no_train:
+        if args.full and not args.no_train:
             train = guarded(train_section, device, rank, world, args.train_steps, max(5, args.warmup // 2))
             if isinstance(train, dict) and "error" not in train:
                 soft = guarded(lambda: train_section(device, rank, world, max(args.train_steps // 2, 10), 5, beta=3.0,
@@ -1618,7 +1672,7 @@ def main():
                 if "roofline" in train_full:
                     train_full["field_forward_roofline"] = train_full.pop("roofline")
                 out["train_full"] = train_full
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 cb, (n, ref) = cpu_baseline(fs, origins, dirs, area, edges)
                 rt = reference_torch_cpu()
                 if rt is not None and rt.get("where", "").startswith("this host"):
@@ -1642,7 +1696,8 @@ def main():
                                    "CPU (models/neurad.py:713-715); the oracle restates its dense formulas (DESIGN.md §3)",
                     "field": "oracle pinned to the reference's own outputs (tests/golden/, oracle/make_golden*.py)"}
     if rank == 0:
-        out["device_state"] = dev_state
+        if args.full:
+            out["device_state"] = dev_state
         if dist_info is not None:
             out["dist"] = dist_info
         if rehearsal:

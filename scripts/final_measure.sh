@@ -38,14 +38,14 @@ cat $OUT/${tag}_pmc_traffic.txt
 python $R/scripts/traffic_from_pmc.py $OUT/${tag}_pmc_traffic.txt $tag; cp $R/profiles/traffic_*.json $OUT/
 fi
 cd $R
-timeout 600 python bench.py > $OUT/bench_${tag}_c1.json 2> $OUT/bench_${tag}_c1.err; echo "c1 rc=$?"
-for c in c2 c4; do timeout 600 python bench.py --config $c > $OUT/bench_${tag}_$c.json 2> $OUT/bench_${tag}_$c.err; echo "$c rc=$?"; done
+timeout 600 python bench.py --full > $OUT/bench_${tag}_c1.json 2> $OUT/bench_${tag}_c1.err; echo "c1 rc=$?"
+for c in c2 c4; do timeout 600 python bench.py --full --config $c > $OUT/bench_${tag}_$c.json 2> $OUT/bench_${tag}_$c.err; echo "$c rc=$?"; done
 # c3: the hand-assembled step (eager + HIP-graph replay) and the same step as `ns-train neurad-hip` runs it (--via-plugin)
-timeout 900 python bench.py --config c3 --via-plugin > $OUT/bench_${tag}_c3.json 2> $OUT/bench_${tag}_c3.err; echo "c3 rc=$?"
+timeout 900 python bench.py --full --config c3 --via-plugin > $OUT/bench_${tag}_c3.json 2> $OUT/bench_${tag}_c3.err; echo "c3 rc=$?"
 # `python bench.py --gpus 2` as a plain command (self-launch), over gloo on this box's one GPU: the labelled rehearsal
-NRHIP_DIST_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 10 --warmup 3 --train-steps 20 --train-full-steps 6 > $OUT/${tag}_rehearsal_n2_self_launch_gloo_one_gpu.json 2> $OUT/${tag}_rehearsal_n2_self_launch.err; echo "self-launch rehearsal rc=$?"
-NRHIP_DIST_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 10 --warmup 3 --train-steps 20 --train-full-steps 6 > $OUT/${tag}_rehearsal_n2_gloo_one_gpu.json 2> $OUT/${tag}_rehearsal_n2.err; echo "rehearsal rc=$?"
-NRHIP_DIST_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 10 --warmup 3 --train-steps 20 --train-full-steps 6 --wire-bf16 > $OUT/${tag}_rehearsal_n2_wire_bf16_gloo_one_gpu.json 2> $OUT/${tag}_rehearsal_n2_wire_bf16.err; echo "rehearsal wire-bf16 rc=$?"
+NRHIP_DIST_BACKEND=gloo timeout 600 python bench.py --full --gpus 2 --steps 10 --warmup 3 --train-steps 20 --train-full-steps 6 > $OUT/${tag}_rehearsal_n2_self_launch_gloo_one_gpu.json 2> $OUT/${tag}_rehearsal_n2_self_launch.err; echo "self-launch rehearsal rc=$?"
+NRHIP_DIST_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 2 --steps 10 --warmup 3 --train-steps 20 --train-full-steps 6 > $OUT/${tag}_rehearsal_n2_gloo_one_gpu.json 2> $OUT/${tag}_rehearsal_n2.err; echo "rehearsal rc=$?"
+NRHIP_DIST_BACKEND=gloo timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 10 --warmup 3 --train-steps 20 --train-full-steps 6 --wire-bf16 > $OUT/${tag}_rehearsal_n2_wire_bf16_gloo_one_gpu.json 2> $OUT/${tag}_rehearsal_n2_wire_bf16.err; echo "rehearsal wire-bf16 rc=$?"
 cd /tmp
 prof() { name=$1; shift; timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_${tag}_$name -o t -- "$@" > $OUT/prof_${tag}_$name.log 2>&1
   python $R/scripts/prof_summary.py $(find $OUT/prof_${tag}_$name -name '*.db' | head -1) | head -64 > $OUT/${tag}_${name}_kernel_trace.txt; find $OUT/prof_${tag}_$name -name '*.db' -delete; }
@@ -65,7 +65,7 @@ cd $R
 {
 echo "== MLP products of the headline kernel: fp16 pairs (default, NRHIP_MLP_PAIRS=1) vs the fp32 MFMA (0) vs 3-way bf16 split, alternating"
 for v in 1 0 1 0 bf16; do if [ $v = bf16 ]; then export NRHIP_MLP_SPLIT_BF16=1 NRHIP_MLP_PAIRS=0; else unset NRHIP_MLP_SPLIT_BF16; export NRHIP_MLP_PAIRS=$v; fi
-  timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-train --no-variants 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-train --no-variants 2>/dev/null | python -c "
 import sys, json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('pairs=$v', 'ms_per_step', round(d['ms_per_step'],4), 'value', '%.4g'%d['value'], 'kernel_ms', round(d['roofline']['kernel_ms'],4), 'frac', round(d['roofline']['frac'],4))"; done; unset NRHIP_MLP_SPLIT_BF16 NRHIP_MLP_PAIRS
 echo "== c4 eval: render stage in ray_order (default) vs data-loader order; fused sampler's in-box pass dense (default) vs inline"
