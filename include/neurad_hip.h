@@ -79,7 +79,11 @@ typedef struct {
 
 /* NeuRADField (nerfstudio/fields/neurad_field.py:78-152), static scene part.
  *   geo:  L*F -> hidden -> 1 + geo_feat_dim   (neurad_field.py:98-106)
- *   feat: geo_feat_dim + 16 (SH deg 4) -> hidden ... -> geo_feat_dim  (neurad_field.py:109-117)   */
+ *   feat: geo_feat_dim + 16 (SH deg 4) -> hidden ... -> geo_feat_dim  (neurad_field.py:109-117)
+ * The fused field kernels (nrhip_field_fwd*, nrhip_render_fwd*) are instantiated for hidden width 32 and 64 and the grids
+ * (L, F) = (16, 2), (8, 4), (4, 8) [L*F = 32], (8, 2), (4, 4) [16], (4, 2) [8], (1, 4) [4]; with actors (16, 2) at
+ * H = 64, (8, 4) and (4, 2); anything else is NRHIP_ERR_UNSUPPORTED.  Every encoding-wide tensor is dense [*, L*F]:
+ * geo.weight[0] [H, L*F], save_enc, the override rows.   */
 typedef struct {
   nrhip_grid grid;
   const void* table;        /* [L*T, F] level-major rows (encodings.py:382-384) */
@@ -228,14 +232,14 @@ int nrhip_field_feature_bwd(const nrhip_mlp* m, const float* x, const float* hid
 int nrhip_field_fwd(const nrhip_field* f, const nrhip_rays* rays, float* feature, float* sdf, float* alpha,
                     void* stream);
 /* Training forward: the same kernel, additionally storing what nrhip_mlp_bwd / nrhip_encode_bwd* need, in their
- * layouts (N = R*S, H = hidden width, all 16-byte aligned):  save_enc [N,32] rescaled grid features (geometry MLP
+ * layouts (N = R*S, H = hidden width, all 16-byte aligned):  save_enc [N,L*F] rescaled grid features (geometry MLP
  * input), save_geo_hidden [N,H], save_feat_in [N,48] = geometry embedding | SH(direction) (feature MLP input),
  * save_feat_hidden [N,2H] = layer 0 | layer 1.  Replaces encode_fwd + 2x mlp_fwd + sh4 + concat of the operator path. */
 int nrhip_field_fwd_train(const nrhip_field* f, const nrhip_rays* rays, float* feature, float* sdf, float* alpha,
                           float* save_enc, float* save_geo_hidden, float* save_feat_in, float* save_feat_hidden,
                           void* stream);
 /* The same with ROW OVERRIDES -- the training forward of a scene with dynamic actors (neurad_encoding.py:150-187): a
- * sample with ovr_row[i] = p >= 0 (i = ray * S + sample) takes its encoding row from ovr_rows [P,32] (the actor grid's
+ * sample with ovr_row[i] = p >= 0 (i = ray * S + sample) takes its encoding row from ovr_rows [P,L*F] (the actor grid's
  * rescaled features, zero-padded, computed by the differentiable actor branch for the few samples inside a box) and the
  * view direction of its SH inputs from ovr_dirs [P,3] (box frame, neurad_encoding.py:203-208) instead of the static
  * lookup and the ray direction; ovr_row[i] = -1: the static scene.  save_enc then holds the overriding rows, so the

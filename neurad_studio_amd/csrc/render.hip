@@ -3,7 +3,8 @@
 //
 // Wave layout (tile = 16 consecutive samples of one ray):   lane = 16*g + j
 //     j = lane & 15  : sample inside the tile          g = lane >> 4 : "k-group" (0..3)
-//   * gather: the 4 lanes (j, g=0..3) of a sample each look up L/4 levels  -> 8 features per lane.  Those 8
+//   * gather: the 4 lanes (j, g=0..3) of a sample each look up L/4 levels  -> 8 features per lane (grids with L*F < 32:
+//     ceil(L/4) levels, zero-padded to the same 8 registers -- EncFrame).  Those 8
 //     registers ARE the MFMA B-fragments of geo-layer 1 (v_mfma_f32_16x16x4_f32: B[k = lane>>4][n = lane&15]),
 //     the weight matrix is the A operand with its K axis permuted to match (done once, at LDS staging).
 //   * transposed chaining H^T = W . X^T : the D tile comes out as D[neuron = 4g + r][sample = j]  (r = 0..3),
@@ -46,7 +47,7 @@ struct FieldDev {
   GridDev grid;
   const void* table;
   float scale;
-  const float* gw0; const float* gb0;   // geo layer 0: [H][32], [H]
+  const float* gw0; const float* gb0;   // geo layer 0: [H][L*F], [H]
   const float* gw1; const float* gb1;   // geo layer 1: [33][H], [33]
   const float* fw0; const float* fb0;   // feat layer 0: [H][48]
   const float* fw1; const float* fb1;   // feat layer 1: [H][H]
@@ -59,7 +60,7 @@ struct FieldDev {
 // Training forward (nrhip_field_fwd_train): what the hand-written backward needs, written in the layouts the
 // operator-level kernels read ([N, width] row-major).  All null for inference.
 struct SaveDev {
-  float* enc;  // [N, 32]   rescaled grid features = input of the geometry MLP
+  float* enc;  // [N, L*F]  rescaled grid features = input of the geometry MLP
   float* hg;   // [N, H]    geometry MLP hidden activations (post-ReLU)
   float* xf;   // [N, 48]   feature MLP input: geometry embedding (32) | SH of the ray direction (16)
   float* hf;   // [N, 2H]   feature MLP hidden activations, layer 0 | layer 1
@@ -116,6 +117,36 @@ __device__ __forceinline__ float frag_src(const float* __restrict__ W, int ldw, 
   const int s = 4 * s4 + s3, i = lane & 15, g = lane >> 4;
   const int col = CHAIN ? (16 * (s >> 2) + 4 * g + (s & 3)) : (8 * g + s);
   return W[(size_t)(row_off + 16 * mb + i) * ldw + col];
+}
+
+// The encoding frame.  Geo layer 0 always takes K = 32 inputs: lane group g holds 8 feature slots of its sample, owns
+// levels LPL g .. LPL g + LPL - 1 (LPL = ceil(L / 4) levels per lane) and puts level LPL g + q, feature f in slot F q + f.
+// At L * F == 32 every slot holds a feature.  A smaller grid leaves the slots past LPL F, and the lane groups past L / LPL,
+// as zero padding: those lanes issue no gathers, and the padding meets zero weights.  The frame is private to the kernel:
+// what crosses the ABI (geo.weight[0] [H, L F], save_enc [N, L F], the override rows [P, L F]) is in the dense order.
+template <int L, int F>
+struct EncFrame {
+  static constexpr int LPL = (L + 3) / 4;          // levels per lane group
+  static constexpr int W = LPL * F;                // feature slots of a busy group
+  static constexpr int NG = L / LPL;               // busy lane groups
+  static constexpr int LF = L * F;                 // dense encoding width
+  static constexpr bool FULL = W == 8 && NG == 4;  // no padding (L * F == 32)
+  static_assert(W <= 8 && L % LPL == 0, "encoding frame: at most 8 features per lane group, whole levels per group");
+  static __device__ __forceinline__ bool busy(int g) { return FULL || g < NG; }
+};
+
+// element e of geo layer 0's fragment image (frag_src's order, 8 k-steps): dense column W g + s of the weight, or 0 for
+// a padding slot
+template <int L, int F, int NBLK>
+__device__ __forceinline__ float enc_frag_src(const float* __restrict__ W, int e) {
+  using EF = EncFrame<L, F>;
+  if constexpr (EF::FULL) {
+    return frag_src<false, NBLK, 8>(W, EF::LF, 0, e);
+  } else {
+    const int s3 = e & 3, lane = (e >> 2) & 63, rest = e >> 8;
+    const int s = 4 * (rest & 1) + s3, mb = rest >> 1, i = lane & 15, g = lane >> 4;
+    return (s < EF::W && g < EF::NG) ? W[(size_t)(16 * mb + i) * EF::LF + EF::W * g + s] : 0.f;
+  }
 }
 
 // ---- the matrix work on the matrix cores: 3-way split bf16 ------------------------------------------------------------
@@ -325,9 +356,11 @@ __device__ __forceinline__ void mfma_layer_pairs(const float* __restrict__ wf, c
 // Stage all weights of the field into LDS (256-thread workgroup; caller barriers afterwards).  Every thread first
 // ISSUES all of its global loads (one register each, ~60 in flight), then stores: one memory round trip for the whole
 // 54 KB image instead of one per loop iteration.
-template <int H, int SPLIT = 0>
+template <int L, int F, int H, int SPLIT = 0>
 __device__ __forceinline__ void stage_field_weights(const FieldDev& fd, float* __restrict__ lds) {
   using Ld = Lds<H, SPLIT>;
+  constexpr int LF = EncFrame<L, F>::LF;  // row length of geo layer 0
+  static_assert(!SPLIT || EncFrame<L, F>::FULL, "split / pair products: L * F == 32 only");
   constexpr int NB = H / 16;
   constexpr int T = 256;  // == blockDim.x
   constexpr int N_G0 = H * 32 / T, N_G1 = 32 * H / T, N_F0 = H * 32 / T, N_F1 = H * H / T, N_F2 = 32 * H / T,
@@ -336,7 +369,7 @@ __device__ __forceinline__ void stage_field_weights(const FieldDev& fd, float* _
   const int tid = threadIdx.x;
   float vg0[N_G0], vg1[N_G1], vf0[N_F0], vf1[N_F1], vf2[N_F2], vsh[N_SH], vs[7];
   if constexpr (SPLIT == 1) {
-    stage_split_matrix<false, NB, 2>(lds + Ld::G0, fd.gw0, 32, 0);
+    stage_split_matrix<false, NB, 2>(lds + Ld::G0, fd.gw0, LF, 0);
     stage_split_matrix<true, 2, NB>(lds + Ld::G1, fd.gw1, H, 1);
     stage_split_matrix<true, NB, 2>(lds + Ld::F0, fd.fw0, 48, 0);
     stage_split_matrix<true, NB, NB>(lds + Ld::F1, fd.fw1, H, 0);
@@ -345,7 +378,7 @@ __device__ __forceinline__ void stage_field_weights(const FieldDev& fd, float* _
     if (tid == 0) reinterpret_cast<int*>(lds)[Ld::FLG] = 0;
     __syncthreads();
 #pragma unroll
-    for (int it = 0; it < N_G0; ++it) vg0[it] = pair_src<false, NB, 1>(fd.gw0, 32, 0, it * T + tid);
+    for (int it = 0; it < N_G0; ++it) vg0[it] = pair_src<false, NB, 1>(fd.gw0, LF, 0, it * T + tid);
 #pragma unroll
     for (int it = 0; it < N_G1; ++it) vg1[it] = pair_src<true, 2, H / 32>(fd.gw1, H, 1, it * T + tid);
 #pragma unroll
@@ -354,7 +387,7 @@ __device__ __forceinline__ void stage_field_weights(const FieldDev& fd, float* _
     for (int it = 0; it < N_F1; ++it) vf1[it] = pair_src<true, NB, H / 32>(fd.fw1, H, 0, it * T + tid);
   } else {
 #pragma unroll
-    for (int it = 0; it < N_G0; ++it) vg0[it] = frag_src<false, NB, 8>(fd.gw0, 32, 0, it * T + tid);
+    for (int it = 0; it < N_G0; ++it) vg0[it] = enc_frag_src<L, F, NB>(fd.gw0, it * T + tid);
 #pragma unroll
     for (int it = 0; it < N_G1; ++it) vg1[it] = frag_src<true, 2, H / 4>(fd.gw1, H, 1, it * T + tid);
 #pragma unroll
@@ -518,13 +551,14 @@ __device__ __forceinline__ void layout_corners(float x, float y, float z, float 
 
 template <int L, int F, bool HALF, bool RELAY = false>
 __device__ __forceinline__ void issue_tile(const FieldDev& fd, const PendingTile& pt, int g, uint32_t mask,
-                                           const float* scal_lds, TileFetch<L / 4, F>& tf,
+                                           const float* scal_lds, TileFetch<EncFrame<L, F>::LPL, F>& tf,
                                            const uint32_t* lay_lds = nullptr) {
-  constexpr int LPL = L / 4;
+  constexpr int LPL = EncFrame<L, F>::LPL;
   tf.t0 = pt.t0;
   tf.t1 = pt.t1;
   const SamplePos p = sample_position(pt.ox, pt.oy, pt.oz, pt.dx, pt.dy, pt.dz, pt.area, pt.t0, pt.t1, fd.scale);
   tf.x = p.x, tf.y = p.y, tf.z = p.z, tf.std = p.std;
+  if (!EncFrame<L, F>::busy(g)) return;  // a lane group without levels (L < 4) loads nothing
 #pragma unroll
   for (int q = 0; q < LPL; ++q) {
     if constexpr (RELAY) {
@@ -554,9 +588,10 @@ __device__ __forceinline__ void issue_tile_actors(const FieldDev& fd, const Acto
                                                   uint32_t mask, const float* scal_lds, const float* ascal_lds,
                                                   const int32_t* __restrict__ cand_actor,
                                                   const float* __restrict__ cand_w2b, const float* __restrict__ bounds,
-                                                  const void* const* __restrict__ tables, TileFetch<L / 4, F>& tf,
-                                                  int& slot_out) {
-  constexpr int LPL = L / 4;
+                                                  const void* const* __restrict__ tables,
+                                                  TileFetch<EncFrame<L, F>::LPL, F>& tf, int& slot_out) {
+  constexpr int LPL = EncFrame<L, F>::LPL;
+  const bool busy = EncFrame<L, F>::busy(g);  // lanes of a group without levels load nothing
   const int n = __builtin_amdgcn_readfirstlane(pt.ncand);
   // 32-bit row index, made scalar explicitly: a 64-bit multiply has no scalar form
   const uint32_t row = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)pt.ray * (uint32_t)ad.K));
@@ -591,14 +626,16 @@ __device__ __forceinline__ void issue_tile_actors(const FieldDev& fd, const Acto
       const float bz = w[8] * gs.x + w[9] * gs.y + w[10] * gs.z + w[11];
       const SamplePos p = contract_gaussian(bx, by, bz, gs.std, ad.scale);
       tf.x = p.x, tf.y = p.y, tf.z = p.z, tf.std = p.std;
+      if (busy) {
 #pragma unroll
-      for (int q = 0; q < LPL; ++q) {
-        // levels beyond the actor grid are the zero padding of F.pad (neurad_encoding.py:183): their fetch goes to the
-        // last actor level and is weighted 0 at the blend
-        const int lv = LPL * g + q, alv = lv < ad.La ? lv : ad.La - 1;
-        const Corners cs = hash_corners(p.x, p.y, p.z, ascal_lds[alv], amask);
+        for (int q = 0; q < LPL; ++q) {
+          // levels beyond the actor grid are the zero padding of F.pad (neurad_encoding.py:183): their fetch goes to the
+          // last actor level and is weighted 0 at the blend
+          const int lv = LPL * g + q, alv = lv < ad.La ? lv : ad.La - 1;
+          const Corners cs = hash_corners(p.x, p.y, p.z, ascal_lds[alv], amask);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) Entry<F, HALF>::load(tb, ((uint32_t)alv << ad.log2T) + cs.idx[k], tf.fv[q][k]);
+          for (int k = 0; k < 8; ++k) Entry<F, HALF>::load(tb, ((uint32_t)alv << ad.log2T) + cs.idx[k], tf.fv[q][k]);
+        }
       }
     }
   }
@@ -608,12 +645,14 @@ __device__ __forceinline__ void issue_tile_actors(const FieldDev& fd, const Acto
   if (slot < 0) {
     const SamplePos p = contract_gaussian(gs.x, gs.y, gs.z, gs.std, fd.scale);
     tf.x = p.x, tf.y = p.y, tf.z = p.z, tf.std = p.std;
+    if (busy) {
 #pragma unroll
-    for (int q = 0; q < LPL; ++q) {
-      const Corners cs = hash_corners(p.x, p.y, p.z, scal_lds[q], mask);
+      for (int q = 0; q < LPL; ++q) {
+        const Corners cs = hash_corners(p.x, p.y, p.z, scal_lds[q], mask);
 #pragma unroll
-      for (int k = 0; k < 8; ++k)
-        Entry<F, HALF>::load(fd.table, ((uint32_t)(LPL * g + q) << fd.grid.log2T) + cs.idx[k], tf.fv[q][k]);
+        for (int k = 0; k < 8; ++k)
+          Entry<F, HALF>::load(fd.table, ((uint32_t)(LPL * g + q) << fd.grid.log2T) + cs.idx[k], tf.fv[q][k]);
+      }
     }
   }
 }
@@ -643,9 +682,11 @@ __device__ __forceinline__ void actor_tile_sh(int slot, uint32_t row, int g, flo
     if ((c >> 2) == g) shb[c & 3] = sh[c];
 }
 
-template <int LPL, int F>
-__device__ __forceinline__ void blend_tile_actors(const TileFetch<LPL, F>& tf, int slot, int g, int La,
+template <int L, int F>
+__device__ __forceinline__ void blend_tile_actors(const TileFetch<EncFrame<L, F>::LPL, F>& tf, int slot, int g, int La,
                                                   const float* scal_lds, const float* ascal_lds, float (&feat)[8]) {
+  using EF = EncFrame<L, F>;
+  constexpr int LPL = EF::LPL;
   const bool in_box = slot >= 0;
 #pragma unroll
   for (int q = 0; q < LPL; ++q) {
@@ -658,13 +699,17 @@ __device__ __forceinline__ void blend_tile_actors(const TileFetch<LPL, F>& tf, i
     lerp_corners<F>(c, tf.fv[q], v);
     const float rw = (in_box && lv >= La) ? 0.f : rescale_weight(sc, tf.std);
 #pragma unroll
-    for (int f = 0; f < F; ++f) feat[q * F + f] = v[f] * rw;
+    for (int f = 0; f < F; ++f) feat[q * F + f] = EF::busy(g) ? v[f] * rw : 0.f;
   }
+#pragma unroll
+  for (int k = EF::W; k < 8; ++k) feat[k] = 0.f;  // padding slots of the frame
 }
 
-template <int LPL, int F>
-__device__ __forceinline__ void blend_tile(const TileFetch<LPL, F>& tf, const float* scal_lds, float (&feat)[8]) {
-  static_assert(LPL * F == 8, "8 features per lane");
+template <int L, int F>
+__device__ __forceinline__ void blend_tile(const TileFetch<EncFrame<L, F>::LPL, F>& tf, int g, const float* scal_lds,
+                                           float (&feat)[8]) {
+  using EF = EncFrame<L, F>;
+  constexpr int LPL = EF::LPL;
 #pragma unroll
   for (int q = 0; q < LPL; ++q) {
     const float sc = scal_lds[q];
@@ -675,11 +720,14 @@ __device__ __forceinline__ void blend_tile(const TileFetch<LPL, F>& tf, const fl
     lerp_corners<F>(c, tf.fv[q], v);
     const float rw = rescale_weight(sc, tf.std);
 #pragma unroll
-    for (int f = 0; f < F; ++f) feat[q * F + f] = v[f] * rw;
+    for (int f = 0; f < F; ++f) feat[q * F + f] = EF::busy(g) ? v[f] * rw : 0.f;  // (idle groups fetched nothing)
   }
+#pragma unroll
+  for (int k = EF::W; k < 8; ++k) feat[k] = 0.f;  // padding slots of the frame
 }
 
-// L levels, F features/level (L*F == 32), H hidden width, HALF = fp16 table, COMPOSITE = fuse C1+C2, ACT = dynamic actors.
+// L levels, F features/level (L*F <= 32, see EncFrame), H hidden width, HALF = fp16 table, COMPOSITE = fuse C1+C2,
+// ACT = dynamic actors.
 template <int L, int F, int H, bool HALF, bool COMPOSITE, bool ACT = false, int SPLIT = 0, bool RELAY = false,
           bool OVR = false>
 __global__ __launch_bounds__(256, 2) void render_kernel(
@@ -691,26 +739,27 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     const int32_t* __restrict__ cand_count,
     const int32_t* __restrict__ cand_actor, const float* __restrict__ cand_w2b, const float* __restrict__ bounds,
     const void* const* __restrict__ tables) {
-  static_assert(L * F == 32 && L % 4 == 0, "fused kernel needs L*F == 32, L % 4 == 0");
+  using EF = EncFrame<L, F>;  // (asserts L * F <= 32 in whole levels per lane group)
   static_assert(!ACT || COMPOSITE, "actors: composited eval kernel (static and actor tables share one storage type)");
   static_assert(H % 16 == 0 && H >= 16 && H <= 128, "hidden width");
   // SPLIT = 1 (3-way bf16): the composited static-scene kernel.  SPLIT = 2 (fp16 pairs): also the per-sample kernel of the
   // static scene -- the training forward: the tile runs in units of kPairAct, every store of an activation undoes it
   static_assert(!SPLIT || ((COMPOSITE || SPLIT == 2) && !ACT), "split matrix products: static-scene kernels");
   static_assert(!RELAY || (COMPOSITE && !ACT && !SPLIT), "eval-table layout: the composited static-scene kernel");
+  static_assert(!(SPLIT || RELAY) || EF::FULL, "split / pair products and the eval-table layout: L * F == 32 only");
   // OVR (training forward of a scene with dynamic actors): samples inside an actor box take their encoding row and view
   // direction from the caller (the differentiable actor branch computed them for the few hit samples) instead of the
   // static lookup.  The three ACT-only pointer arguments carry the overrides: cand_count = ovr_row [N] (row index or -1),
-  // cand_w2b = ovr_rows [P,32], bounds = ovr_dirs [P,3].
+  // cand_w2b = ovr_rows [P, L*F], bounds = ovr_dirs [P,3].
   static_assert(!OVR || (!COMPOSITE && !ACT && !SPLIT && !RELAY), "row overrides: the per-sample training forward");
   using Ld = Lds<H, SPLIT>;
   constexpr int NB = H / 16;
-  constexpr int LPL = L / 4;         // levels per lane
+  constexpr int LPL = EF::LPL;       // levels per lane
   constexpr bool DEFER = COMPOSITE;  // last feature layer applied once per ray
   extern __shared__ __attribute__((aligned(16))) float lds[];
 
   // ---- stage weights (once per workgroup; the grid is persistent over rays) ----------------------
-  stage_field_weights<H, SPLIT>(fd, lds);
+  stage_field_weights<L, F, H, SPLIT>(fd, lds);
   if constexpr (ACT || OVR) {
     for (int e = threadIdx.x; e < 16 * H; e += 256) lds[Ld::SHF + e] = frag_src<true, NB, 4>(fd.fw0 + 32, 48, 0, e);
   }
@@ -751,6 +800,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
   //   tf = gathered corners of the CURRENT tile | q = next tile (interval + ray constants loaded, gathers not yet
   //   issued) | the tile after q has its small loads requested at the end of the issue step
   TileFetch<LPL, F> tf;
+  if constexpr (!EF::FULL) tf = TileFetch<LPL, F>{};  // (the idle lane groups never load theirs)
   int ta = -1;  // ACT: candidate slot of the actor containing this lane's sample of the tile in `tf` (-1: none)
   const float* ascal_l = lds + Ld::ASCAL;
   PendingTile q;
@@ -818,13 +868,13 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     bool tile_hit = false;
     float shb[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (ACT) {
-      blend_tile_actors<LPL, F>(tf, ta, g, ad.La, scal_l, ascal_l, feat);
+      blend_tile_actors<L, F>(tf, ta, g, ad.La, scal_l, ascal_l, feat);
       tile_hit = __ballot(ta >= 0) != 0ull;  // wave-uniform
       if (tile_hit)  // here, where few registers are live -- not in the middle of the MLPs
         actor_tile_sh(ta, (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)ray * (uint32_t)ad.K)), g, rd[3 * ray],
                       rd[3 * ray + 1], rd[3 * ray + 2], cand_w2b, shb);
     } else {
-      blend_tile<LPL, F>(tf, scal_l, feat);
+      blend_tile<L, F>(tf, g, scal_l, feat);
       if constexpr (SPLIT == 2) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) feat[k] *= kPairAct;
@@ -834,10 +884,15 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
         if (tile_hit) {
           float bx = rd[3 * ray], by = rd[3 * ray + 1], bz = rd[3 * ray + 2];
           if (ta >= 0) {
-            const float* rp = cand_w2b + (size_t)ta * 32 + 8 * g;  // this lane's 8 columns of the override row
-            const f32x4 r0 = *reinterpret_cast<const f32x4*>(rp), r1 = *reinterpret_cast<const f32x4*>(rp + 4);
+            const float* rp = cand_w2b + (size_t)ta * EF::LF + EF::W * g;  // this lane's columns of the override row
+            if constexpr (EF::FULL) {
+              const f32x4 r0 = *reinterpret_cast<const f32x4*>(rp), r1 = *reinterpret_cast<const f32x4*>(rp + 4);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) feat[k] = r0[k], feat[4 + k] = r1[k];
+              for (int k = 0; k < 4; ++k) feat[k] = r0[k], feat[4 + k] = r1[k];
+            } else if (EF::busy(g)) {  // (the padding slots stay 0)
+#pragma unroll
+              for (int k = 0; k < EF::W; ++k) feat[k] = rp[k];
+            }
             bx = bounds[3 * (size_t)ta], by = bounds[3 * (size_t)ta + 1], bz = bounds[3 * (size_t)ta + 2];
           }
           float sh[16];
@@ -887,17 +942,26 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
       srow = ray * S + s;
       if (saving) {
         constexpr float u = SPLIT == 2 ? 1.f / kPairAct : 1.f;  // (tile units -> true units: a power of two, exact)
-        float* ep = sv.enc + srow * 32 + 8 * g;
-        stream_store(ep, f32x4{feat[0] * u, feat[1] * u, feat[2] * u, feat[3] * u});
-        stream_store(ep + 4, f32x4{feat[4] * u, feat[5] * u, feat[6] * u, feat[7] * u});
+        float* ep = sv.enc + srow * EF::LF + EF::W * g;  // dense [N, L*F]: this lane group's W columns
+        if constexpr (EF::FULL) {
+          stream_store(ep, f32x4{feat[0] * u, feat[1] * u, feat[2] * u, feat[3] * u});
+          stream_store(ep + 4, f32x4{feat[4] * u, feat[5] * u, feat[6] * u, feat[7] * u});
+        } else if (EF::busy(g)) {
+          if constexpr (EF::W == 4) {
+            stream_store(ep, f32x4{feat[0] * u, feat[1] * u, feat[2] * u, feat[3] * u});
+          } else {
+#pragma unroll
+            for (int k = 0; k < EF::W; ++k) __builtin_nontemporal_store(feat[k] * u, ep + k);
+          }
+        }
       }
     }
 
-    // ---- geo MLP layer 0 (32 -> H, ReLU) ---------------------------------------------------------
+    // ---- geo MLP layer 0 (L*F in the 32-slot frame -> H, ReLU) -----------------------------------
     f32x4 h[NB];
 #pragma unroll
     for (int mb = 0; mb < NB; ++mb) h[mb] = *reinterpret_cast<const f32x4*>(lw + Ld::BG0 + 16 * mb + 4 * g);
-    if constexpr (SPLIT == 2) mfma_layer_pairs<false, NB, 1>(lw + Ld::G0, fd.gw0, 32, 0, wbad, lane, feat, h);
+    if constexpr (SPLIT == 2) mfma_layer_pairs<false, NB, 1>(lw + Ld::G0, fd.gw0, EF::LF, 0, wbad, lane, feat, h);
     else if constexpr (SPLIT == 1) mfma_layer_split<NB, 2>(lw + Ld::G0, lane, feat, h);
     else mfma_layer<NB, 8>(lw + Ld::G0, lane, feat, h);
     float hb[H / 4];
@@ -1099,22 +1163,30 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
   }
 }
 
+// The grids the fused kernels are instantiated for: L * F == 32 (L = 16, 8, 4), and the smaller grids that live in the
+// padded frame (EncFrame): BASELINE config[0]'s 1 x 4, NeuRAD tiny's 4 x 2, and the L * F == 16 grids 4 x 4 and 8 x 2.
+static bool fused_grid_shape(int L, int F) {
+  return (L == 16 && F == 2) || (L == 8 && F == 4) || (L == 4 && F == 8) || (L == 1 && F == 4) || (L == 4 && F == 2) ||
+         (L == 4 && F == 4) || (L == 8 && F == 2);
+}
+
 static int validate_field(const nrhip_field* f) {
   NR_REQUIRE(f, NRHIP_ERR_INVALID_ARG, "field descriptor is NULL");
   if (int e = validate_grid(&f->grid)) return e;
   NR_REQUIRE(f->table && f->static_scale > 0.f, NRHIP_ERR_INVALID_ARG, "field: NULL table or non-positive scale");
   const nrhip_mlp& a = f->geo;
   const nrhip_mlp& b = f->feat;
-  const int in = f->grid.num_levels * f->grid.n_features;
-  NR_REQUIRE(in == 32 && f->grid.num_levels % 4 == 0, NRHIP_ERR_UNSUPPORTED,
-             "fused field kernel needs L*F == 32 with L %% 4 == 0 (got L=%d F=%d); use the unfused ops",
-             f->grid.num_levels, f->grid.n_features);
-  NR_REQUIRE(a.num_layers == 2 && b.num_layers == 3 && a.in_dim == 32 && a.out_dim == 33 && b.in_dim == 48 &&
+  const int L = f->grid.num_levels, F = f->grid.n_features, in = L * F;
+  NR_REQUIRE(fused_grid_shape(L, F) && (a.hidden_dim == 32 || a.hidden_dim == 64), NRHIP_ERR_UNSUPPORTED,
+             "fused field kernel: no instantiation for L=%d F=%d H=%d (grids L x F = 16x2, 8x4, 4x8, 8x2, 4x4, 4x2, 1x4; "
+             "hidden width 32 or 64); use the unfused ops",
+             L, F, a.hidden_dim);
+  NR_REQUIRE(a.num_layers == 2 && b.num_layers == 3 && a.in_dim == in && a.out_dim == 33 && b.in_dim == 48 &&
                  b.out_dim == 32 && a.hidden_dim == b.hidden_dim,
              NRHIP_ERR_UNSUPPORTED,
-             "fused field kernel needs geo 32->H->33 (2 layers) and feat 48->H->H->32 (3 layers); use the unfused ops");
-  NR_REQUIRE(a.hidden_dim == 32 || a.hidden_dim == 64, NRHIP_ERR_UNSUPPORTED,
-             "fused field kernel is instantiated for hidden width 32 and 64 (got %d)", a.hidden_dim);
+             "fused field kernel needs geo L*F->H->33 (2 layers, L*F=%d) and feat 48->H->H->32 (3 layers); use the "
+             "unfused ops",
+             in);
   for (int l = 0; l < 2; ++l) NR_REQUIRE(a.weight[l], NRHIP_ERR_INVALID_ARG, "geo weight %d is NULL", l);
   for (int l = 0; l < 3; ++l) NR_REQUIRE(b.weight[l], NRHIP_ERR_INVALID_ARG, "feat weight %d is NULL", l);
   return NRHIP_OK;
@@ -1272,6 +1344,15 @@ static int dispatch_render(const nrhip_field* f, const nrhip_rays* rays, float* 
   CASE(8, 4, 64)
   CASE(4, 8, 32)
   CASE(4, 8, 64)
+  // grids with L*F < 32, in the padded frame (EncFrame): fp32-MFMA products only
+  CASE(1, 4, 32)
+  CASE(1, 4, 64)
+  CASE(4, 2, 32)
+  CASE(4, 2, 64)
+  CASE(4, 4, 32)
+  CASE(4, 4, 64)
+  CASE(8, 2, 32)
+  CASE(8, 2, 64)
 #undef CASE
   set_error("fused field kernel: no instantiation for L=%d F=%d H=%d", L, F, H);
   return NRHIP_ERR_UNSUPPORTED;
@@ -1330,6 +1411,8 @@ static int dispatch_render_actors(const nrhip_field* f, const nrhip_rays* rays, 
   CASE(8, 4, 32)
   CASE(8, 4, 64)
   CASE(16, 2, 64)
+  CASE(4, 2, 32)  // NeuRAD tiny
+  CASE(4, 2, 64)
 #undef CASE
   set_error("fused field kernel with actors: no instantiation for L=%d F=%d H=%d", L, F, H);
   return NRHIP_ERR_UNSUPPORTED;
@@ -1396,6 +1479,8 @@ extern "C" int nrhip_field_fwd_train_ovr(const nrhip_field* f, const nrhip_rays*
   OCASE(8, 4, 32)
   OCASE(8, 4, 64)
   OCASE(16, 2, 64)
+  OCASE(4, 2, 32)  // NeuRAD tiny
+  OCASE(4, 2, 64)
 #undef OCASE
   set_error("field_fwd_train_ovr: no instantiation for L=%d F=%d H=%d", L, F, H);
   return NRHIP_ERR_UNSUPPORTED;

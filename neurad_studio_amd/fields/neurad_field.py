@@ -33,6 +33,13 @@ from ..field_components.neurad_encoding import (ActorSettings, NeuRADHashEncodin
                                                 StaticSettings)
 
 
+# (num_levels, features_per_level) of the static grids the fused field kernels cover
+_FUSED_GRIDS = ((16, 2), (8, 4), (4, 8), (1, 4), (4, 2), (4, 4), (8, 2))
+# (num_levels, features_per_level, hidden width) of the static fields the fused kernels with dynamic actors cover
+# (render.hip: dispatch_render_actors, nrhip_field_fwd_train_ovr)
+_FUSED_ACTOR_FIELDS = ((8, 4, 32), (8, 4, 64), (16, 2, 64), (4, 2, 32), (4, 2, 64))
+
+
 class _TruncExp(torch.autograd.Function):  # field_components/activations.py:28-41
     @staticmethod
     def forward(ctx, x):
@@ -143,9 +150,11 @@ class NeuRADField(nn.Module):
             ag_ = self.hashgrid.actor_grids[0]
             if not (with_actors and ag_.features_per_level == g.features_per_level and ag_.num_levels <= g.num_levels
                     and all(a.hash_table.dtype == g.hash_table.dtype for a in self.hashgrid.actor_grids)
-                    and (g.num_levels, c.geo_hidden_dim) in ((8, 32), (8, 64), (16, 64))):
+                    and (g.num_levels, g.features_per_level, c.geo_hidden_dim) in _FUSED_ACTOR_FIELDS):
                 return False
-        return (g.get_out_dim() == 32 and g.num_levels % 4 == 0 and c.geo_num_layers == 2 and c.nff_num_layers == 3
+        # grids the kernels are instantiated for (render.hip: fused_grid_shape): L * F == 32, and the smaller ones in the
+        # kernel's padded frame -- BASELINE config[0]'s 1 x 4, NeuRAD tiny's 4 x 2, and 4 x 4 / 8 x 2
+        return ((g.num_levels, g.features_per_level) in _FUSED_GRIDS and c.geo_num_layers == 2 and c.nff_num_layers == 3
                 and c.geo_hidden_dim == c.nff_hidden_dim and c.geo_hidden_dim in (32, 64) and c.nff_out_dim == 32)
 
     def train(self, mode: bool = True):
@@ -219,7 +228,7 @@ class NeuRADField(nn.Module):
         gradient, as the reference's index_put does, and the static table nothing for those samples."""
         hg = self.hashgrid
         if not (self.fused_supported(with_actors=True) and self._fused_train_ok()):
-            raise NotImplementedError("render_train: a fused-kernel configuration only (L * F = 32, 32- or 64-wide MLPs)")
+            raise NotImplementedError("render_train: a fused-kernel configuration only (see fused_supported)")
         g = hg.static_grid
         emb, sensor, etimes, emb_cfg = appearance if appearance is not None else (None, None, None, (1.0, 1, False))
         order = ops.ray_order(origins, directions, hg.static_scale) if self.order_rays else None
@@ -237,7 +246,7 @@ class NeuRADField(nn.Module):
             *[t for l in self.mlp_feature.layers for t in (l.weight, l.bias)])
 
     def _actor_overrides(self, origins, directions, pixel_area, edges, times, actor_cand=None):
-        """-> (ovr_row int32 [N]: row of the sample's WINNING actor (highest index containing it) or -1, rows [P,32],
+        """-> (ovr_row int32 [N]: row of the sample's WINNING actor (highest index containing it) or -1, rows [P,L*F],
         box-frame view directions [P,3], pair_idx [P]: flat sample index of every (sample, actor) pair) or four Nones"""
         hg = self.hashgrid
         starts, ends = edges[:, :-1], edges[:, 1:]
