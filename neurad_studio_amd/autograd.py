@@ -111,9 +111,10 @@ class MultiHashGridFn(torch.autograd.Function):
 
 
 class TableBundle:
-    """what the consumers of one ``StackTablesFn`` output share: which grids ANY of their batches touched (a grid none
-    touched gets no gradient at all -- the reference's per-id loop never evaluates it, so torch.optim.Adam leaves its
-    moments alone), and whether the node's backward has run (its graph is gone: build a new one)"""
+    """what the consumers of one ``StackTablesFn`` output share: which grids the batches of the consumers whose BACKWARD ran
+    touched (a grid none touched gets no gradient at all -- the reference's per-id loop never evaluates it, so
+    torch.optim.Adam leaves its moments alone; a consumer whose graph was dropped without a backward adds nothing), and
+    whether the node's backward has run (its graph is gone: build a new one)"""
 
     def __init__(self, n_grids: int) -> None:
         self.present = [False] * n_grids
@@ -144,11 +145,9 @@ class MultiHashGridStackedFn(torch.autograd.Function):
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, x, grid_id, spec, stacked, bundle):
-        ctx.spec = spec
+        ctx.spec, ctx.bundle = spec, bundle
         grid_id = grid_id.to(torch.int32)
         ctx.present = ops.grids_present(grid_id, stacked.shape[0]) if ctx.needs_input_grad[3] else None  # (see MultiHashGridFn)
-        if ctx.present is not None:
-            bundle.present = [bool(a) or bool(b) for a, b in zip(bundle.present, ctx.present)]
         ctx.save_for_backward(x, grid_id, stacked)
         return ops.hashgrid_multi_fwd(spec, list(stacked.unbind(0)), grid_id, x)
 
@@ -157,6 +156,11 @@ class MultiHashGridStackedFn(torch.autograd.Function):
     def backward(ctx, g):
         x, grid_id, stacked = ctx.saved_tensors
         g = g.contiguous()
+        if ctx.present is not None:
+            # presence is recorded HERE, not in the forward: StackTablesFn's backward runs after every consumer of this
+            # step, and a forward whose output was dropped without a backward must not hand its grids a zero gradient
+            b = ctx.bundle
+            b.present = [bool(p) or bool(q) for p, q in zip(b.present, ctx.present)]
         block = ops.hashgrid_multi_bwd(ctx.spec, stacked.shape[0], grid_id, x, g, present=ctx.present, out_dtype=stacked.dtype,
                                        dense_block=True) if ctx.needs_input_grad[3] else None
         gx = ops.hashgrid_multi_bwd_input(ctx.spec, list(stacked.unbind(0)), grid_id, x, g) if ctx.needs_input_grad[0] else None

@@ -12,7 +12,8 @@ per step) and, at world_size > 1, wraps the model in DDP (pipelines/base_pipelin
                        and cameras/raygen.py (rolling-shutter camera rays, lidar rays) -- and merges the two halves with the
                        reference's own ``_merge_img_lidar``.  No worker processes, no queue, no per-step host->device copy.
                        Eval keeps the reference's loaders.
-``ADHipPipeline``      world_size > 1: the model stays bare and ``parallel.data_parallel.GradientSynchronizer`` exchanges the
+``ADHipPipeline``      world_size > 1: rank 0's parameters and buffers are broadcast at construction (as DDP's constructor
+                       does), the model stays bare and ``parallel.data_parallel.GradientSynchronizer`` exchanges the
                        gradients (reduce-scatter + all-gather on the tables' own storage, one coalesced all-reduce for the
                        rest) at the END of every backward pass, so that ``grad_scaler.step`` already sees reduced gradients;
                        ``get_train_loss_dict`` tells the model the batch's [camera; lidar] layout (no boolean-mask gathers).
@@ -32,7 +33,7 @@ from nerfstudio.pipelines.ad_pipeline import ADPipeline, ADPipelineConfig
 
 from ..cameras import raygen
 from ..data import pixel_samplers as hip_samplers
-from ..parallel.data_parallel import GradientSynchronizer
+from ..parallel.data_parallel import GradientSynchronizer, broadcast_module_state
 
 
 @dataclass
@@ -140,6 +141,9 @@ class ADHipPipeline(ADPipeline):
             _ref_base_pipeline.DDP = ddp
         self.grad_sync = None
         if self.world_size > 1:
+            # DDP's constructor broadcast, which _BareModel skips: rank 0's parameters and buffers on every rank.  The
+            # optimizers (and the fp16 tables' master copies) are built afterwards by Trainer.setup, from these values.
+            broadcast_module_state(self.model, src=0)
             params = [p for p in self.model.parameters() if p.requires_grad]
             dynamic = self.model.field.hashgrid.has_actors()  # actor grids receive gradients only when a ray hits them
             self.grad_sync = GradientSynchronizer(

@@ -86,6 +86,17 @@ def scatter_16bit_finish(recv: Tensor, wire_dtype=torch.bfloat16) -> Tensor:
     return acc
 
 
+@torch.no_grad()
+def broadcast_module_state(module: torch.nn.Module, src: int = 0, group=None) -> None:
+    """Every parameter and buffer of ``module`` overwritten in place with rank ``src``'s values: what DDP's constructor does
+    (``_sync_module_states``), which the reference relies on to make replicas seeded with ``seed + rank``
+    (scripts/train.py:104) equal.  Collective: every rank calls it, with the same module structure."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return
+    for t in list(module.parameters()) + list(module.buffers()):
+        dist.broadcast(t.detach(), src, group=group)
+
+
 def all_gather_flat(full: Tensor, shard: Tensor, world: int, group=None) -> None:
     """all_gather_into_tensor, or -- where the backend lacks it for this device -- a list gather + copy"""
     if flat_collectives_supported(group, full.device):

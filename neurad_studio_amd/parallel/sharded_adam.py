@@ -90,10 +90,12 @@ class ShardedTableAdam:
     def step(self) -> int:
         """-> payload bytes this rank exchanged (reduce-scatter + all-gather)"""
         nbytes = 0
+        updated = False
         b1, b2 = self.betas
         for p, st, used in zip(self.tables, self.state, self._used()):
             if not used:
                 continue  # no gradient anywhere: parameters, moments and the step count stay as they are
+            updated = True
             st["step"] += 1
             flat_p = p.data.view(-1)
             grad = p.grad if p.grad is not None else torch.zeros_like(p)
@@ -120,6 +122,12 @@ class ShardedTableAdam:
                 # in place (send buffer = this rank's slot of the receive buffer) where the backend supports it
                 src = p_shard if dist.get_backend(self.group) == "nccl" else p_shard.clone()
                 all_gather_flat(flat_p, src, self.world, self.group)
+        if updated:
+            # the tables were written through ``.data`` and raw kernels: their version counters did not move.  Drop what is
+            # keyed on them (ops.eval_table's re-laid-out tables, the stacked actor tables), as HashGridAdam.step does.
+            from .. import ops
+
+            ops.clear_eval_tables()
         return nbytes
 
     def zero_grad(self, set_to_none: bool = True) -> None:

@@ -495,3 +495,49 @@ def test_auto_sync_reduces_before_the_gradscaler_looks_world2_gloo():
     assert sc0 == sc1 == 4.0 and b0 == b1 > 0
     for a, b in zip(p0, p1):
         assert torch.equal(a, b)  # replicas bit-identical
+
+
+class _Mixed(torch.nn.Module):
+    """every kind of state a NeuRAD replica holds: fp32 and fp16-storage tables, an MLP, float / int / bool buffers"""
+
+    def __init__(self):
+        super().__init__()
+        self.table = torch.nn.Parameter(torch.randn(1024, 4))
+        self.table16 = torch.nn.Parameter(torch.randn(512, 2).half())
+        self.mlp = torch.nn.Sequential(torch.nn.Linear(8, 16), torch.nn.BatchNorm1d(16), torch.nn.Linear(16, 3))
+        self.register_buffer("positions", torch.randn(5, 3))
+        self.register_buffer("ids", torch.randint(0, 100, (7,)))
+        self.register_buffer("present", torch.rand(4, 3) < 0.5)
+
+
+def _broadcast_worker(rank, world, port, ret):
+    from neurad_studio_amd.parallel.data_parallel import broadcast_module_state
+
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    torch.manual_seed(42 + rank)  # scripts/train.py:104: every rank seeded apart
+    m = _Mixed()
+    m.mlp[1].running_mean.normal_()
+    built = {k: v.clone() for k, v in m.state_dict().items()}
+    ptrs = {k: v.data_ptr() for k, v in m.state_dict().items()}
+    broadcast_module_state(m)
+    ret[rank] = (built, {k: v.clone() for k, v in m.state_dict().items()},
+                 all(v.data_ptr() == ptrs[k] for k, v in m.state_dict().items()))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_broadcast_module_state_gives_every_rank_rank0s_parameters_and_buffers_world2_gloo():
+    """what DDP's constructor does for the reference, done by ADHipPipeline at world_size > 1: bit for bit, in place, every
+    dtype"""
+    world = 2
+    with mp.Manager() as mgr:
+        ret = mgr.dict()
+        mp.spawn(_broadcast_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+        (built0, after0, inplace0), (built1, after1, inplace1) = ret[0], ret[1]
+    assert inplace0 and inplace1
+    assert not torch.equal(built0["table"], built1["table"])
+    assert {v.dtype for v in after1.values()} >= {torch.float32, torch.float16, torch.int64, torch.bool}
+    for k, v in built0.items():
+        assert after0[k].dtype == after1[k].dtype == v.dtype, k
+        assert torch.equal(after0[k], v) and torch.equal(after1[k], v), k

@@ -1,0 +1,151 @@
+"""``ns-train neurad-hip`` at world size 2: the replicas must be ONE model.
+
+The reference seeds every rank with ``config.machine.seed + global_rank`` (scripts/train.py:104) and relies on DDP's
+constructor to broadcast rank 0's parameters and buffers.  The method's pipeline keeps its model bare (integration/
+pipeline.py: ``_BareModel`` + ``GradientSynchronizer``), so it must do that broadcast itself -- otherwise every rank
+starts from its own hash tables and MLP weights, applies the same averaged gradient to them, and the replicas never
+converge to one model (only rank 0's copy is checkpointed).
+
+Two ranks share cuda:0 and exchange over gloo; each is seeded as the reference seeds it and built through
+``TrainerConfig.setup`` -> ``trainer.setup()`` on the synthetic drive of tests/test_gpu_plugin_pipeline.py (3 cameras, 2 lidar
+sweeps, 3 actors).  Nothing writes the same values on both ranks: only the pipeline can make them equal.  The parent
+process does not touch the GPU."""
+import os
+import socket
+import sys
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import ref_import  # noqa: E402
+
+pytestmark = [pytest.mark.gpu,
+              pytest.mark.skipif(not ref_import.reference_available(), reason="no reference (oracle/_ref ships with the lease)")]
+
+K = 3
+
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _cpu(t):
+    return t.detach().to("cpu", copy=True)
+
+
+def _worker(rank, world, port, root, table_dtype, ret):
+    import random
+    from pathlib import Path
+
+    import numpy as np
+    import torch.distributed as dist
+
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    os.environ["NERFSTUDIO_METHOD_CONFIGS"] = "neurad-hip=neurad_studio_amd.integration.neurad_hip:neurad_hip"
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    ref_import.install()
+    import nerfstudio.models.neurad as ref_neurad
+    from nerfstudio.pipelines.ad_pipeline import ADPipeline
+
+    import test_gpu_plugin_pipeline as P
+    from neurad_studio_amd.integration.pipeline import ADHipPipeline
+    from neurad_studio_amd.integration.trainer import HipTrainer
+    from neurad_studio_amd.optim import HashGridAdam, TableGradScaler
+
+    ref_neurad.VGGPerceptualLossPix2Pix = torch.nn.Identity  # (loss.vgg_mult = 0 at test size; no weights to load)
+    data = Path(root) / f"rank{rank}"
+    data.mkdir(parents=True)
+    cfg = P._method_config(data)
+    cfg.pipeline.model.table_dtype = table_dtype
+    cfg.output_dir, cfg.experiment_name, cfg.timestamp = data / "outputs", "synthetic-drive", "run"
+    cfg.vis = "none"
+    for group in cfg.optimizers.values():
+        group["scheduler"].warmup_steps = 0
+    cfg.get_base_dir().mkdir(parents=True)
+
+    # what ADPipeline.__init__ built, before ADHipPipeline.__init__ goes on to make the replicas equal
+    built = {}
+    real_init = ADPipeline.__init__
+
+    def spy_init(self, *a, **k):
+        real_init(self, *a, **k)
+        built.update({n: _cpu(t) for n, t in self.model.state_dict().items()})
+
+    ADPipeline.__init__ = spy_init
+    seed = cfg.machine.seed + rank  # scripts/train.py:86-104 (_set_random_seed(config.machine.seed + global_rank))
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    # local_rank is the rank's device on its machine (Trainer.__init__: cuda:{local_rank}; VanillaPipeline.__init__:
+    # dist.barrier(device_ids=[local_rank])): both ranks live on GPU 0 here.  The global rank comes from the process group.
+    trainer = cfg.setup(local_rank=0, world_size=world)
+    assert type(trainer) is HipTrainer and isinstance(trainer.grad_scaler, TableGradScaler) and trainer.device == "cuda:0"
+    trainer.setup()
+    ADPipeline.__init__ = real_init
+    pipe = trainer.pipeline
+    assert isinstance(pipe, ADHipPipeline) and pipe.grad_sync is not None and pipe.model.field.hashgrid.has_actors()
+    ret[f"built{rank}"] = built
+    ret[f"setup{rank}"] = {n: _cpu(t) for n, t in pipe.model.state_dict().items()}
+
+    pipe.train()
+    for step in range(K):
+        trainer.train_iteration(step)
+    trainer._settle_schedulers()
+    torch.cuda.synchronize()
+    opt = trainer.optimizers.optimizers["hashgrids"]
+    assert isinstance(opt, HashGridAdam)
+    names = {id(p): n for n, p in pipe.model.named_parameters()}
+    ret[f"trained{rank}"] = {
+        "params": {n: _cpu(p) for n, p in pipe.model.named_parameters()},
+        "hashgrids": {names[id(p)]: {k: _cpu(v) for k, v in opt.state[p].items() if k in ("exp_avg", "exp_avg_sq", "step")}
+                      for p in opt.param_groups[0]["params"] if p in opt.state},
+        "scale": float(trainer.grad_scaler.get_scale())}
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _same(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b)
+
+
+@pytest.mark.parametrize("table_dtype", ["float32", "float16"], ids=["fp32", "fp16"])
+def test_ranks_seeded_apart_train_one_model(table_dtype, tmp_path):
+    import torch.multiprocessing as mp
+
+    world = 2
+    with mp.Manager() as mgr:
+        ret = mgr.dict()
+        mp.spawn(_worker, args=(world, _free_port(), str(tmp_path), table_dtype, ret), nprocs=world, join=True)
+        res = {k: ret[k] for k in ret.keys()}
+    built0, built1, setup0, setup1 = res["built0"], res["built1"], res["setup0"], res["setup1"]
+    table = "field.hashgrid.static_grid.hash_table"
+    assert built0[table].dtype == getattr(torch, table_dtype)
+    assert not torch.equal(built0[table], built1[table])  # the seeds differ: so did the models the ranks built
+
+    # after trainer.setup(): every entry of the state dict (parameters, fp16 tables, buffers) is rank 0's, on both ranks
+    assert setup0.keys() == setup1.keys() == built0.keys()
+    for n in setup0:
+        assert _same(setup1[n], setup0[n]), n
+        assert _same(setup0[n], built0[n]), n
+
+    # K iterations later (HipTrainer + TableGradScaler + GradientSynchronizer as built, each rank on its own batches): the
+    # parameters and the tables' Adam state are still bit-identical.  (BatchNorm running statistics follow each rank's own
+    # batch, as under DDP: not compared.)
+    t0, t1 = res["trained0"], res["trained1"]
+    assert t0["scale"] == t1["scale"]
+    assert t0["params"].keys() == t1["params"].keys()
+    moved = 0
+    for n, p in t0["params"].items():
+        assert _same(t1["params"][n], p), n
+        moved += int(not torch.equal(p, setup0[n]))
+    assert moved > 0  # (it trained)
+    assert t0["hashgrids"].keys() == t1["hashgrids"].keys() and table in t0["hashgrids"]
+    for n, st in t0["hashgrids"].items():
+        assert st.keys() == t1["hashgrids"][n].keys() == {"exp_avg", "exp_avg_sq", "step"}, n
+        for k, v in st.items():
+            assert _same(t1["hashgrids"][n][k], v), (n, k)
