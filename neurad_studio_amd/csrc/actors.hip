@@ -504,8 +504,7 @@ __global__ __launch_bounds__(256) void actor_pair_positions_bwd_kernel(
   // ---- contraction backward (spatial_distortions.py:126-141, order = inf): (g_x01, g_cstd) -> g_pos ----------------
   float m[3] = {pos[0] / a.scale, pos[1] / a.scale, pos[2] / a.scale};
   const float am[3] = {fabsf(m[0]), fabsf(m[1]), fabsf(m[2])};
-  const int kmax = am[0] >= am[1] ? (am[0] >= am[2] ? 0 : 2) : (am[1] >= am[2] ? 1 : 2);
-  const float mag = am[kmax];
+  const float mag = fmaxf(fmaxf(am[0], am[1]), am[2]);
   float gm[3] = {g_x01[3 * p] / 4.f, g_x01[3 * p + 1] / 4.f, g_x01[3 * p + 2] / 4.f};  // x01 = (m' + 2) / 4
   if (!(mag < 1.f)) {
     // m' = k m, k = 2/mag - 1/mag^2;   cstd = (std/scale) q / 4, q = ((2 mag - 1)^(1/3) / mag)^2
@@ -513,8 +512,7 @@ __global__ __launch_bounds__(256) void actor_pair_positions_bwd_kernel(
     const float cr = cbrtf(2.f * mag - 1.f), rr = cr / mag;
     const float dq = 2.f * rr * ((2.f / 3.f) / (cr * cr * mag) - cr / (mag * mag));
     const float g_mag = (gm[0] * m[0] + gm[1] * m[1] + gm[2] * m[2]) * dk + g_cstd[p] * (g.std / a.scale) * dq / 4.f;
-    for (int c = 0; c < 3; ++c) gm[c] *= k;
-    gm[kmax] += g_mag * (m[kmax] < 0.f ? -1.f : 1.f);
+    inf_norm_bwd(m, am, mag, k, g_mag, gm);
   }
   float gpos[3] = {gm[0] / a.scale * flip, gm[1] / a.scale, gm[2] / a.scale};
   // ---- pos_i = b1_i v_0 + b2_i v_1 + b3_i v_2,  v = mean - t ---------------------------------------------------------

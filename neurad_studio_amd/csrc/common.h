@@ -308,6 +308,14 @@ __device__ __forceinline__ SamplePos contract_gaussian(float mx, float my, float
   return p;
 }
 
+// Backward of the contraction's m' = k(mag) m past the scalar chain: gm <- k gm + d|m|_inf/dm g_mag.  torch's inf-norm
+// backward splits g_mag evenly over the axes tied for the maximum, each with its sign (linalg_vector_norm_backward).
+__device__ __forceinline__ void inf_norm_bwd(const float* m, const float* am, float mag, float k, float g_mag, float* gm) {
+  const float share = g_mag / (float)((am[0] == mag) + (am[1] == mag) + (am[2] == mag));
+#pragma unroll
+  for (int c = 0; c < 3; ++c) gm[c] = gm[c] * k + (am[c] == mag ? (m[c] < 0.f ? -share : share) : 0.f);
+}
+
 __device__ __forceinline__ SamplePos sample_position(float ox, float oy, float oz, float dx, float dy, float dz,
                                                      float area, float t0, float t1, float scale) {
   // Position arithmetic mirrors torch op for op (separately rounded mul/add/div, no fma): one ulp of the

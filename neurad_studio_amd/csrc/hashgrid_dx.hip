@@ -118,21 +118,19 @@ __global__ __launch_bounds__(256) void encode_bwd_rays_kernel(GridDev g, const v
         const float a2 = sc * 2.f * p.std;
         const float w = 1.f / fmaxf(a2, 1.f);
         gx += (sc * w) * dx, gy += (sc * w) * dy, gz += (sc * w) * dz;
-        if (a2 > 1.f) gstd -= dv * (2.f * sc) * (w * w);
+        if (a2 >= 1.f) gstd -= dv * (2.f * sc) * (w * w);  // clamp_min passes the gradient at equality
       }
       // contraction backward: (gx, gy, gz) = dL/dx01, gstd = dL/d cstd  ->  dL/d mean
       const float u[3] = {gs.x / scale, gs.y / scale, gs.z / scale};
       const float au[3] = {fabsf(u[0]), fabsf(u[1]), fabsf(u[2])};
-      const int kmax = au[0] >= au[1] ? (au[0] >= au[2] ? 0 : 2) : (au[1] >= au[2] ? 1 : 2);
-      const float mag = au[kmax];
+      const float mag = fmaxf(fmaxf(au[0], au[1]), au[2]);
       float gm[3] = {gx / 4.f, gy / 4.f, gz / 4.f};
       if (!(mag < 1.f)) {
         const float k = 2.f / mag - 1.f / (mag * mag), dk = -2.f / (mag * mag) + 2.f / (mag * mag * mag);
         const float cr = cbrtf(2.f * mag - 1.f), rr = cr / mag;
         const float dq = 2.f * rr * ((2.f / 3.f) / (cr * cr * mag) - cr / (mag * mag));
         const float g_mag = (gm[0] * u[0] + gm[1] * u[1] + gm[2] * u[2]) * dk + gstd * (gs.std / scale) * dq / 4.f;
-        for (int c = 0; c < 3; ++c) gm[c] *= k;
-        gm[kmax] += g_mag * (u[kmax] < 0.f ? -1.f : 1.f);
+        inf_norm_bwd(u, au, mag, k, g_mag, gm);
       }
       const float dist = (t1 - t0) / 2.f, t = t0 + dist;
       for (int c = 0; c < 3; ++c) {

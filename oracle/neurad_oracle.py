@@ -289,7 +289,44 @@ def encode_static(grid: GridParams, static_scale, origins, directions, pixel_are
     return rescale_grid_features(feat, cstd.reshape(-1), grid.scalings, grid.n_feat)
 
 
-def encode_static_ray_grads(grid: GridParams, static_scale, origins, directions, pixel_area, starts, ends, grad_enc):
+def _lerp_derivs(tab, idx, off, absolute=False):
+    """value and d/d(offset) of the trilinear lerp (encodings.py:425-464) at corner rows ``idx`` [N,L,8] with fp32 offsets
+    [N,L,3], float64.  absolute: every difference taken as a sum of absolute values (tab holds |table|)."""
+    fc = [tab[idx[..., k]] for k in range(8)]  # [N,L,F]; corner order 0 ccc 1 cfc 2 ffc 3 fcc 4 ccf 5 cff 6 fff 7 fcf
+    ox, oy, oz = (off[..., k:k + 1].astype(np.float64) for k in range(3))
+    mx, my, mz = 1 - ox, 1 - oy, 1 - oz
+    sub = (lambda a, b: a + b) if absolute else (lambda a, b: a - b)
+    f03, f12 = fc[0] * ox + fc[3] * mx, fc[1] * ox + fc[2] * mx
+    f56, f47 = fc[5] * ox + fc[6] * mx, fc[4] * ox + fc[7] * mx
+    val = (f03 * oy + f12 * my) * oz + (f47 * oy + f56 * my) * mz
+    d03, d12, d56, d47 = sub(fc[0], fc[3]), sub(fc[1], fc[2]), sub(fc[5], fc[6]), sub(fc[4], fc[7])
+    dvx = (d03 * oy + d12 * my) * oz + (d47 * oy + d56 * my) * mz
+    dvy = sub(f03, f12) * oz + sub(f47, f56) * mz
+    dvz = sub(f03 * oy + f12 * my, f47 * oy + f56 * my)
+    return val, dvx, dvy, dvz
+
+
+def hashgrid_input_grads(x, table, scalings, table_size: int, grad_out, with_abs: bool = False):
+    """dL/dx [N,3] of :func:`hashgrid_fwd` (autograd w.r.t. in_tensor, encodings.py:425-464: floor / ceil carry no
+    gradient, d enc_l / dx = scal_l d lerp / d offset), float64 from the fp32 cells and offsets.  with_abs: also the sum
+    of |terms| per element -> (gx, gx_abs)."""
+    sc = np.asarray(scalings, f32)
+    L = sc.shape[0]
+    idx, off = hashgrid_corner_indices(np.asarray(x, f32), sc, table_size)
+    F = np.asarray(table).shape[1]
+    g = np.asarray(grad_out, np.float64).reshape(-1, L, F)
+    scl = sc.astype(np.float64)[None, :, None]
+    outs = []
+    for absolute in ((False, True) if with_abs else (False,)):
+        _, dvx, dvy, dvz = _lerp_derivs(np.abs(np.asarray(table, np.float64)) if absolute else np.asarray(table, np.float64),
+                                        idx, off, absolute)
+        gg = np.abs(g) if absolute else g
+        outs.append(np.stack([(gg * dv * scl).sum((1, 2)) for dv in (dvx, dvy, dvz)], -1))
+    return tuple(outs) if with_abs else outs[0]
+
+
+def encode_static_ray_grads(grid: GridParams, static_scale, origins, directions, pixel_area, starts, ends, grad_enc,
+                            with_abs: bool = False, ties: str = "split", clamp_at_one: bool = True):
     """dL/d(origins), dL/d(directions) [R,3] of :func:`encode_static` (M = 1) given dL/d(rescaled features) [R*S, L*F]:
     what autograd does for a camera optimizer that moves the rays (cameras/camera_optimizers.py:173-182).  The chain, every
     link the derivative of the reference line it names (sample midpoints t are constants: bins are detached,
@@ -299,7 +336,14 @@ def encode_static_ray_grads(grid: GridParams, static_scale, origins, directions,
       x = (c + 2) / 4, s = std' / 4;  |u|_inf >= 1: c = (2 - 1/m) u / m, std' = (std/scale) ((2m - 1)^(1/3) / m)^2, m = |u|_inf
                                                                         spatial_distortions.py:126-141,  u = mean / scale
       mean = o + d t                                                    cameras/rays.py:119
-    Primal quantities (cells, offsets, masks) in fp32 exactly as the forward restatement, derivative arithmetic in fp64."""
+    Primal quantities (cells, offsets, masks) in fp32 exactly as the forward restatement, derivative arithmetic in fp64.
+    At the edges the subgradient is torch's: clamp_min passes the gradient where 2 scal_l s == 1, and the inf-norm's
+    backward splits dL/dm evenly over the axes tied for the maximum, each with its sign.
+
+    with_abs: also return, per output element, the sum of the absolute values of the terms that make it up (every
+    difference and product of the chain taken in absolute value) -> (go, gd, go_abs, gd_abs), float64.
+    ties="first", clamp_at_one=False: the wrong subgradients (whole dL/dm to the first maximal axis, no clamp gradient at
+    equality) -- a negative control for tests that must tell the two apart."""
     f64 = np.float64
     mean, std = fast_isotropic_gaussian(origins, directions, pixel_area, starts, ends)
     R, S = np.asarray(starts).shape
@@ -310,44 +354,49 @@ def encode_static_ray_grads(grid: GridParams, static_scale, origins, directions,
     L, F = sc.shape[0], grid.n_feat
     idx, off = hashgrid_corner_indices(x, sc, grid.table_size)
     t = np.asarray(grid.table, f64)
-    fc = [t[idx[..., k]] for k in range(8)]  # [N,L,F]; corner order 0 ccc 1 cfc 2 ffc 3 fcc 4 ccf 5 cff 6 fff 7 fcf
-    ox, oy, oz = (off[..., k:k + 1].astype(f64) for k in range(3))
-    mx, my, mz = 1 - ox, 1 - oy, 1 - oz
-    f03, f12 = fc[0] * ox + fc[3] * mx, fc[1] * ox + fc[2] * mx
-    f56, f47 = fc[5] * ox + fc[6] * mx, fc[4] * ox + fc[7] * mx
-    val = (f03 * oy + f12 * my) * oz + (f47 * oy + f56 * my) * mz
-    d03, d12, d56, d47 = fc[0] - fc[3], fc[1] - fc[2], fc[5] - fc[6], fc[4] - fc[7]
-    dvx = (d03 * oy + d12 * my) * oz + (d47 * oy + d56 * my) * mz
-    dvy = (f03 - f12) * oz + (f47 - f56) * mz
-    dvz = (f03 * oy + f12 * my) - (f47 * oy + f56 * my)
-    g = np.asarray(grad_enc, f64).reshape(N, L, F)
     s = cstd.reshape(-1, 1).astype(f64)
     a = sc[None, :].astype(f64) * 2.0 * s                     # [N,L]
+    a32 = (sc[None, :] * f32(2)) * cstd.reshape(-1, 1).astype(f32)  # the fp32 primal torch compares with 1
     w = 1.0 / np.maximum(a, 1.0)
-    dw = np.where(a > 1.0, -2.0 * sc[None, :].astype(f64) * w * w, 0.0)
+    dw = np.where((a32 >= 1.0) if clamp_at_one else (a32 > 1.0), -2.0 * sc[None, :].astype(f64) * w * w, 0.0)
     scw = (sc[None, :].astype(f64) * w)[..., None]
-    gx = np.stack([(g * dvx * scw).sum((1, 2)), (g * dvy * scw).sum((1, 2)), (g * dvz * scw).sum((1, 2))], -1)  # dL/dx01
-    gs = ((g * val).sum(-1) * dw).sum(-1)                    # dL/d cstd
     # contraction backward
     u = (mean.reshape(-1, 3) / f32(static_scale)).astype(f32).astype(f64)
     sd = (std.reshape(-1) / f32(static_scale)).astype(f32).astype(f64)
     au = np.abs(u)
-    kmax = np.argmax(au, -1)
-    m = au[np.arange(N), kmax]
-    gc = gx / 4.0
+    m = au.max(-1)
+    if ties == "split":
+        tied = au == m[:, None]
+    else:
+        tied = np.arange(3)[None, :] == np.argmax(au, -1)[:, None]
+    share = tied / tied.sum(-1, keepdims=True)
     outside = ~(m < 1.0)
     mm = np.where(outside, m, 1.0)
-    k = 2.0 / mm - 1.0 / mm**2
-    dk = -2.0 / mm**2 + 2.0 / mm**3
     cr = np.cbrt(2.0 * mm - 1.0)
-    dq = 2.0 * (cr / mm) * ((2.0 / 3.0) / (cr * cr * mm) - cr / mm**2)      # d/dm of ((2m-1)^(1/3)/m)^2
-    g_mag = (gc * u).sum(-1) * dk + (gs / 4.0) * sd * dq
-    gu = np.where(outside[:, None], gc * k[:, None], gc)
-    gu[np.arange(N), kmax] += np.where(outside, g_mag * np.sign(u[np.arange(N), kmax]), 0.0)
-    gmean = (gu / f64(static_scale)).reshape(R, S, 3)
     st, en = np.asarray(starts, f32), np.asarray(ends, f32)
     tm = (st + f32(1) * ((en - st) / f32(2))).astype(f64)
-    return gmean.sum(1).astype(f32), (gmean * tm[..., None]).sum(1).astype(f32)
+
+    def chain(tab, g, absolute):
+        val, dvx, dvy, dvz = _lerp_derivs(tab, idx, off, absolute)
+        gx = np.stack([(g * dvx * scw).sum((1, 2)), (g * dvy * scw).sum((1, 2)), (g * dvz * scw).sum((1, 2))], -1)
+        gs = ((g * val).sum(-1) * (np.abs(dw) if absolute else dw)).sum(-1)   # dL/d cstd
+        gc = gx / 4.0
+        sgn = (lambda v: v) if absolute else (lambda v: -v)
+        k = 2.0 / mm + sgn(1.0 / mm**2)
+        dk = sgn(2.0 / mm**2) + 2.0 / mm**3
+        dq = 2.0 * (cr / mm) * ((2.0 / 3.0) / (cr * cr * mm) + sgn(cr / mm**2))  # d/dm of ((2m-1)^(1/3)/m)^2
+        g_mag = (gc * (au if absolute else u)).sum(-1) * dk + (gs / 4.0) * sd * dq
+        gu = np.where(outside[:, None], gc * k[:, None], gc)
+        gu += np.where(outside[:, None], share * (g_mag[:, None] * (1.0 if absolute else np.sign(u))), 0.0)
+        gmean = (gu / f64(static_scale)).reshape(R, S, 3)
+        return gmean.sum(1), (gmean * (np.abs(tm) if absolute else tm)[..., None]).sum(1)
+
+    g = np.asarray(grad_enc, f64).reshape(N, L, F)
+    go, gd = chain(t, g, False)
+    if not with_abs:
+        return go.astype(f32), gd.astype(f32)
+    goa, gda = chain(np.abs(t), np.abs(g), True)
+    return go, gd, goa, gda
 
 
 def proposal_density_ray_grads(p: "ProposalParams", origins, directions, pixel_area, starts, ends, grad_density):
