@@ -80,10 +80,10 @@ typedef struct {
 /* NeuRADField (nerfstudio/fields/neurad_field.py:78-152), static scene part.
  *   geo:  L*F -> hidden -> 1 + geo_feat_dim   (neurad_field.py:98-106)
  *   feat: geo_feat_dim + 16 (SH deg 4) -> hidden ... -> geo_feat_dim  (neurad_field.py:109-117)
- * The fused field kernels (nrhip_field_fwd*, nrhip_render_fwd*) are instantiated for hidden width 32 and 64 and the grids
- * (L, F) = (16, 2), (8, 4), (4, 8) [L*F = 32], (8, 2), (4, 4) [16], (4, 2) [8], (1, 4) [4]; with actors (16, 2) at
- * H = 64, (8, 4) and (4, 2); anything else is NRHIP_ERR_UNSUPPORTED.  Every encoding-wide tensor is dense [*, L*F]:
- * geo.weight[0] [H, L*F], save_enc, the override rows.   */
+ * The fused field kernels (nrhip_field_fwd*, nrhip_render_fwd*) are instantiated for the (L, F, hidden width) listed in
+ * csrc/render_variants.h (static scene: its Static rows; with actors: its Actors / Overrides rows); anything else is
+ * NRHIP_ERR_UNSUPPORTED.  Every encoding-wide tensor is dense [*, L*F]: geo.weight[0] [H, L*F], save_enc, the override
+ * rows.   */
 typedef struct {
   nrhip_grid grid;
   const void* table;        /* [L*T, F] level-major rows (encodings.py:382-384) */

@@ -40,6 +40,7 @@
 // The sky residual (models/neurad.py:381: w_{S-1} += 1 - sum w) is folded into the last tile -- the accumulated weight is
 // complete there, so no copy of the last sample's features has to be kept.
 #include "common.h"
+#include "render_variants.h"
 
 namespace nrhip {
 
@@ -54,7 +55,7 @@ struct FieldDev {
   const float* fw2; const float* fb2;   // feat layer 2: [32][H]
   int use_sdf;
   float beta;
-  uint32_t lay[NRHIP_MAX_LEVELS * 4];  // RELAY kernels: {mulY, mulZ, mask, row0} per level of the eval table (eval_layout.hip)
+  uint32_t lay[NRHIP_MAX_LEVELS * 4];  // Src::EvalTable kernels: {mulY, mulZ, mask, row0} per level of the eval table (eval_layout.hip)
 };
 
 // Training forward (nrhip_field_fwd_train): what the hand-written backward needs, written in the layouts the
@@ -68,12 +69,12 @@ struct SaveDev {
 
 // LDS carve (floats), H = hidden width.  Fragment-ordered weights use [mb][s/4][lane][s%4] so that one
 // ds_read_b128 fetches the A fragments of 4 consecutive k-steps.
-// SPLIT = 1: the four per-tile matrices are stored as 3-way bf16 splits (6 bytes per weight instead of 4, see
-// mfma_layer_split); SPLIT = 2: as fp16 pairs (hi image | lo image, 4 bytes per weight, see mfma_layer_pairs).
-template <int H, int SPLIT = 0>
+// Prod::Bf16Split: the four per-tile matrices are stored as 3-way bf16 splits (6 bytes per weight instead of 4, see
+// mfma_layer_split); Prod::F16Pairs: as fp16 pairs (hi image | lo image, 4 bytes per weight, see mfma_layer_pairs).
+template <int H, Prod PROD = Prod::F32>
 struct Lds {
   static constexpr int NB = H / 16;        // 16-neuron blocks of a hidden layer
-  static constexpr int WS(int n) { return SPLIT == 1 ? n + n / 2 : n; }
+  static constexpr int WS(int n) { return PROD == Prod::Bf16Split ? n + n / 2 : n; }
   static constexpr int G0 = 0;             // geo L0 : NB blocks x 8 steps
   static constexpr int G1 = G0 + WS(H * 32);   // geo L1 (rows 1..32): 2 blocks x H/4 steps
   static constexpr int F0 = G1 + WS(32 * H);   // feat L0 (geo part): NB blocks x 8 steps
@@ -88,10 +89,10 @@ struct Lds {
   static constexpr int BF2 = BF1 + H;
   static constexpr int SCAL = BF2 + 32;    // per-level scalings
   static constexpr int RB = SCAL + NRHIP_MAX_LEVELS;  // per wave: this ray's bias of feat L0 (fb0 + SH part), 4 x H
-  static constexpr int LAY = RB + 4 * H;   // RELAY: per-level {mulY, mulZ, mask, row0} (uint32), 16-byte aligned
-  static constexpr int FLG = LAY + 4 * NRHIP_MAX_LEVELS;  // SPLIT = 2: a weight does not fit the fp16 pair (int, 0 / 1)
+  static constexpr int LAY = RB + 4 * H;   // Src::EvalTable: per-level {mulY, mulZ, mask, row0} (uint32), 16-byte aligned
+  static constexpr int FLG = LAY + 4 * NRHIP_MAX_LEVELS;  // Prod::F16Pairs: a weight does not fit the fp16 pair (int, 0 / 1)
   static constexpr int TOTAL = FLG + 4;
-  // ACT instantiations only:
+  // Src::Actors / Src::Overrides instantiations only:
   static constexpr int SHF = TOTAL;             // feat L0 SH part in fragment order: NB blocks x 4 steps
   static constexpr int ASCAL = SHF + 16 * H;    // actor grid: per-level scalings
   static constexpr int TOTAL_ACT = ASCAL + NRHIP_MAX_LEVELS;
@@ -353,14 +354,24 @@ __device__ __forceinline__ void mfma_layer_pairs(const float* __restrict__ wf, c
   for (int mb = 0; mb < NBLK; ++mb) acc[mb] *= 1.f / kPairW;
 }
 
+// One per-tile layer on the variant's products: acc (+)= W . b, K inputs per lane in the layer's own order (CHAIN: the
+// previous layer's D tiles, else the gathered features).  W / ldw / row_off / wbad: the pair form's fp32 way out.
+template <Prod PROD, bool CHAIN, int NBLK, int K>
+__device__ __forceinline__ void tile_layer(const float* __restrict__ wf, const float* __restrict__ W, int ldw, int row_off,
+                                           bool wbad, int lane, const float (&b)[K], f32x4 (&acc)[NBLK]) {
+  if constexpr (PROD == Prod::F16Pairs) mfma_layer_pairs<CHAIN, NBLK, K / 8>(wf, W, ldw, row_off, wbad, lane, b, acc);
+  else if constexpr (PROD == Prod::Bf16Split) mfma_layer_split<NBLK, K / 4>(wf, lane, b, acc);
+  else mfma_layer<NBLK, K>(wf, lane, b, acc);
+}
+
 // Stage all weights of the field into LDS (256-thread workgroup; caller barriers afterwards).  Every thread first
 // ISSUES all of its global loads (one register each, ~60 in flight), then stores: one memory round trip for the whole
 // 54 KB image instead of one per loop iteration.
-template <int L, int F, int H, int SPLIT = 0>
+template <int L, int F, int H, Prod PROD = Prod::F32>
 __device__ __forceinline__ void stage_field_weights(const FieldDev& fd, float* __restrict__ lds) {
-  using Ld = Lds<H, SPLIT>;
+  using Ld = Lds<H, PROD>;
   constexpr int LF = EncFrame<L, F>::LF;  // row length of geo layer 0
-  static_assert(!SPLIT || EncFrame<L, F>::FULL, "split / pair products: L * F == 32 only");
+  static_assert(PROD == Prod::F32 || EncFrame<L, F>::FULL, "split / pair products: L * F == 32 only");
   constexpr int NB = H / 16;
   constexpr int T = 256;  // == blockDim.x
   constexpr int N_G0 = H * 32 / T, N_G1 = 32 * H / T, N_F0 = H * 32 / T, N_F1 = H * H / T, N_F2 = 32 * H / T,
@@ -368,12 +379,12 @@ __device__ __forceinline__ void stage_field_weights(const FieldDev& fd, float* _
   static_assert((H * 32) % T == 0 && (H * H) % T == 0 && (16 * H) % T == 0, "regions are whole passes of the block");
   const int tid = threadIdx.x;
   float vg0[N_G0], vg1[N_G1], vf0[N_F0], vf1[N_F1], vf2[N_F2], vsh[N_SH], vs[7];
-  if constexpr (SPLIT == 1) {
+  if constexpr (PROD == Prod::Bf16Split) {
     stage_split_matrix<false, NB, 2>(lds + Ld::G0, fd.gw0, LF, 0);
     stage_split_matrix<true, 2, NB>(lds + Ld::G1, fd.gw1, H, 1);
     stage_split_matrix<true, NB, 2>(lds + Ld::F0, fd.fw0, 48, 0);
     stage_split_matrix<true, NB, NB>(lds + Ld::F1, fd.fw1, H, 0);
-  } else if constexpr (SPLIT == 2) {
+  } else if constexpr (PROD == Prod::F16Pairs) {
     static_assert(H % 32 == 0, "fp16 pairs: K = 32 steps");
     if (tid == 0) reinterpret_cast<int*>(lds)[Ld::FLG] = 0;
     __syncthreads();
@@ -410,7 +421,7 @@ __device__ __forceinline__ void stage_field_weights(const FieldDev& fd, float* _
   vs[4] = fd.gb1 ? fd.gb1[t33] : 0.f;
   vs[5] = fd.fb2 ? fd.fb2[t32] : 0.f;
   vs[6] = fd.grid.scal[t32];
-  if constexpr (SPLIT == 2) {
+  if constexpr (PROD == Prod::F16Pairs) {
     // the tile runs in units of kPairAct (see mfma_layer_pairs): biases in, the three exits out -- all powers of two
     // ... and the biases of the four pair layers x kPairW on top (mfma_layer_pairs accumulates onto them in place)
     constexpr float kB = kPairAct * kPairW;
@@ -431,7 +442,7 @@ __device__ __forceinline__ void stage_field_weights(const FieldDev& fd, float* _
     for (int it = 0; it < N_F1; ++it) bad |= pair_store(lds + Ld::F1, H * H, it * T + tid, vf1[it]);
     if (bad) reinterpret_cast<int*>(lds)[Ld::FLG] = 1;
   }
-  if constexpr (SPLIT == 0) {
+  if constexpr (PROD == Prod::F32) {
 #pragma unroll
     for (int it = 0; it < N_G0; ++it) lds[Ld::G0 + it * T + tid] = vg0[it];
 #pragma unroll
@@ -726,10 +737,9 @@ __device__ __forceinline__ void blend_tile(const TileFetch<EncFrame<L, F>::LPL, 
   for (int k = EF::W; k < 8; ++k) feat[k] = 0.f;  // padding slots of the frame
 }
 
-// L levels, F features/level (L*F <= 32, see EncFrame), H hidden width, HALF = fp16 table, COMPOSITE = fuse C1+C2,
-// ACT = dynamic actors.
-template <int L, int F, int H, bool HALF, bool COMPOSITE, bool ACT = false, int SPLIT = 0, bool RELAY = false,
-          bool OVR = false>
+// L levels, F features/level (L*F <= 32, see EncFrame), H hidden width, HALF = fp16 table; OUT / SRC / PROD: the variant
+// (render_variants.h).
+template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD>
 __global__ __launch_bounds__(256, 2) void render_kernel(
     FieldDev fd, int64_t n_rays, int S, int stride, const int32_t* __restrict__ order, const float* __restrict__ ro,
     const float* __restrict__ rd, const float* __restrict__ rarea, const float* __restrict__ rstarts,
@@ -740,26 +750,25 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     const int32_t* __restrict__ cand_actor, const float* __restrict__ cand_w2b, const float* __restrict__ bounds,
     const void* const* __restrict__ tables) {
   using EF = EncFrame<L, F>;  // (asserts L * F <= 32 in whole levels per lane group)
-  static_assert(!ACT || COMPOSITE, "actors: composited eval kernel (static and actor tables share one storage type)");
+  static_assert(render_variant_ok(L, F, OUT, SRC, PROD), "not a legal variant: see render_variant_ok");
   static_assert(H % 16 == 0 && H >= 16 && H <= 128, "hidden width");
-  // SPLIT = 1 (3-way bf16): the composited static-scene kernel.  SPLIT = 2 (fp16 pairs): also the per-sample kernel of the
-  // static scene -- the training forward: the tile runs in units of kPairAct, every store of an activation undoes it
-  static_assert(!SPLIT || ((COMPOSITE || SPLIT == 2) && !ACT), "split matrix products: static-scene kernels");
-  static_assert(!RELAY || (COMPOSITE && !ACT && !SPLIT), "eval-table layout: the composited static-scene kernel");
-  static_assert(!(SPLIT || RELAY) || EF::FULL, "split / pair products and the eval-table layout: L * F == 32 only");
+  constexpr bool COMPOSITE = OUT == Out::Composite;
+  constexpr bool ACT = SRC == Src::Actors, RELAY = SRC == Src::EvalTable, OVR = SRC == Src::Overrides;
+  constexpr bool PAIRS = PROD == Prod::F16Pairs;
   // OVR (training forward of a scene with dynamic actors): samples inside an actor box take their encoding row and view
   // direction from the caller (the differentiable actor branch computed them for the few hit samples) instead of the
-  // static lookup.  The three ACT-only pointer arguments carry the overrides: cand_count = ovr_row [N] (row index or -1),
-  // cand_w2b = ovr_rows [P, L*F], bounds = ovr_dirs [P,3].
-  static_assert(!OVR || (!COMPOSITE && !ACT && !SPLIT && !RELAY), "row overrides: the per-sample training forward");
-  using Ld = Lds<H, SPLIT>;
+  // static lookup.  The three actor-only pointer arguments carry the overrides:
+  const int32_t* const ovr_row = cand_count;  // [N] row index or -1
+  const float* const ovr_rows = cand_w2b;     // [P, L*F]
+  const float* const ovr_dirs = bounds;       // [P, 3]
+  using Ld = Lds<H, PROD>;
   constexpr int NB = H / 16;
   constexpr int LPL = EF::LPL;       // levels per lane
   constexpr bool DEFER = COMPOSITE;  // last feature layer applied once per ray
   extern __shared__ __attribute__((aligned(16))) float lds[];
 
   // ---- stage weights (once per workgroup; the grid is persistent over rays) ----------------------
-  stage_field_weights<L, F, H, SPLIT>(fd, lds);
+  stage_field_weights<L, F, H, PROD>(fd, lds);
   if constexpr (ACT || OVR) {
     for (int e = threadIdx.x; e < 16 * H; e += 256) lds[Ld::SHF + e] = frag_src<true, NB, 4>(fd.fw0 + 32, 48, 0, e);
   }
@@ -770,8 +779,8 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     if (threadIdx.x < 4 * L) reinterpret_cast<uint32_t*>(lds + Ld::LAY)[threadIdx.x] = fd.lay[threadIdx.x];
   }
   __syncthreads();
-  bool wbad = false;  // SPLIT = 2: some weight does not fit its fp16 pair -> every tile takes the fp32 products
-  if constexpr (SPLIT == 2) wbad = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(lds)[Ld::FLG]) != 0;
+  bool wbad = false;  // PAIRS: some weight does not fit its fp16 pair -> every tile takes the fp32 products
+  if constexpr (PAIRS) wbad = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(lds)[Ld::FLG]) != 0;
 
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -808,7 +817,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
   int64_t ray = q.ray;
   if constexpr (ACT) issue_tile_actors<L, F, HALF>(fd, ad, q, g, mask, scal_l, ascal_l, cand_actor, cand_w2b, bounds, tables, tf, ta);
   else issue_tile<L, F, HALF, RELAY>(fd, q, g, mask, scal_l, tf, lay_l);
-  if constexpr (OVR) ta = (q.valid && j < S) ? cand_count[q.ray * S + j] : -1;  // override row of this lane's sample of `tf`
+  if constexpr (OVR) ta = (q.valid && j < S) ? ovr_row[q.ray * S + j] : -1;  // override row of this lane's sample of `tf`
   {
     const bool wrap = ntile == 1;
     load_pending(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
@@ -875,7 +884,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
                       rd[3 * ray + 1], rd[3 * ray + 2], cand_w2b, shb);
     } else {
       blend_tile<L, F>(tf, g, scal_l, feat);
-      if constexpr (SPLIT == 2) {
+      if constexpr (PAIRS) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) feat[k] *= kPairAct;
       }
@@ -884,7 +893,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
         if (tile_hit) {
           float bx = rd[3 * ray], by = rd[3 * ray + 1], bz = rd[3 * ray + 2];
           if (ta >= 0) {
-            const float* rp = cand_w2b + (size_t)ta * EF::LF + EF::W * g;  // this lane's columns of the override row
+            const float* rp = ovr_rows + (size_t)ta * EF::LF + EF::W * g;  // this lane's columns of the override row
             if constexpr (EF::FULL) {
               const f32x4 r0 = *reinterpret_cast<const f32x4*>(rp), r1 = *reinterpret_cast<const f32x4*>(rp + 4);
 #pragma unroll
@@ -893,7 +902,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
 #pragma unroll
               for (int k = 0; k < EF::W; ++k) feat[k] = rp[k];
             }
-            bx = bounds[3 * (size_t)ta], by = bounds[3 * (size_t)ta + 1], bz = bounds[3 * (size_t)ta + 2];
+            bx = ovr_dirs[3 * (size_t)ta], by = ovr_dirs[3 * (size_t)ta + 1], bz = ovr_dirs[3 * (size_t)ta + 2];
           }
           float sh[16];
           sh4((bx + 1.f) / 2.f, (by + 1.f) / 2.f, (bz + 1.f) / 2.f, sh);
@@ -927,7 +936,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     // unconditional (see load_pending)
     if constexpr (ACT) issue_tile_actors<L, F, HALF>(fd, ad, q, g, mask, scal_l, ascal_l, cand_actor, cand_w2b, bounds, tables, tf, ta);
     else issue_tile<L, F, HALF, RELAY>(fd, q, g, mask, scal_l, tf, lay_l);
-    if constexpr (OVR) ta = (q.valid && 16 * q.t + j < S) ? cand_count[q.ray * S + 16 * q.t + j] : -1;
+    if constexpr (OVR) ta = (q.valid && 16 * q.t + j < S) ? ovr_row[q.ray * S + 16 * q.t + j] : -1;
     {
       const bool wrap = nt + 1 == ntile;  // request the small loads of the tile after it
       load_pending(q, wrap ? npos + pos_step : npos, wrap ? 0 : nt + 1, rr, j, order, ro, rd, rarea, rstarts, rends,
@@ -941,7 +950,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
       saving = sv.enc != nullptr && live;
       srow = ray * S + s;
       if (saving) {
-        constexpr float u = SPLIT == 2 ? 1.f / kPairAct : 1.f;  // (tile units -> true units: a power of two, exact)
+        constexpr float u = PAIRS ? 1.f / kPairAct : 1.f;  // (tile units -> true units: a power of two, exact)
         float* ep = sv.enc + srow * EF::LF + EF::W * g;  // dense [N, L*F]: this lane group's W columns
         if constexpr (EF::FULL) {
           stream_store(ep, f32x4{feat[0] * u, feat[1] * u, feat[2] * u, feat[3] * u});
@@ -961,9 +970,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     f32x4 h[NB];
 #pragma unroll
     for (int mb = 0; mb < NB; ++mb) h[mb] = *reinterpret_cast<const f32x4*>(lw + Ld::BG0 + 16 * mb + 4 * g);
-    if constexpr (SPLIT == 2) mfma_layer_pairs<false, NB, 1>(lw + Ld::G0, fd.gw0, EF::LF, 0, wbad, lane, feat, h);
-    else if constexpr (SPLIT == 1) mfma_layer_split<NB, 2>(lw + Ld::G0, lane, feat, h);
-    else mfma_layer<NB, 8>(lw + Ld::G0, lane, feat, h);
+    tile_layer<PROD, false>(lw + Ld::G0, fd.gw0, EF::LF, 0, wbad, lane, feat, h);
     float hb[H / 4];
 #pragma unroll
     for (int mb = 0; mb < NB; ++mb)
@@ -972,7 +979,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
 
     if constexpr (!COMPOSITE) {
       if (saving) {
-        constexpr float u = SPLIT == 2 ? 1.f / kPairAct : 1.f;
+        constexpr float u = PAIRS ? 1.f / kPairAct : 1.f;
 #pragma unroll
         for (int mb = 0; mb < NB; ++mb)
           stream_store(sv.hg + srow * H + 16 * mb + 4 * g,
@@ -997,9 +1004,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
       const float* bp = lw + Ld::BG1 + 1 + 16 * mb + 4 * g;
       e[mb] = f32x4{bp[0], bp[1], bp[2], bp[3]};
     }
-    if constexpr (SPLIT == 2) mfma_layer_pairs<true, 2, H / 32>(lw + Ld::G1, fd.gw1, H, 1, wbad, lane, hb, e);
-    else if constexpr (SPLIT == 1) mfma_layer_split<2, NB>(lw + Ld::G1, lane, hb, e);
-    else mfma_layer<2, H / 4>(lw + Ld::G1, lane, hb, e);
+    tile_layer<PROD, true>(lw + Ld::G1, fd.gw1, H, 1, wbad, lane, hb, e);
     float eb[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) eb[k] = e[k >> 2][k & 3];
@@ -1007,7 +1012,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     // ---- feature MLP (32 [+16 SH folded into the per-ray bias] -> H -> H -> 32), residual add ------
     if constexpr (!COMPOSITE) {
       if (saving) {
-        constexpr float u = SPLIT == 2 ? 1.f / kPairAct : 1.f;
+        constexpr float u = PAIRS ? 1.f / kPairAct : 1.f;
         float* xp = sv.xf + srow * 48;
         stream_store(xp + 4 * g, e[0] * u);
         stream_store(xp + 16 + 4 * g, e[1] * u);
@@ -1023,16 +1028,14 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
       for (int mb = 0; mb < NB; ++mb) h[mb] = *reinterpret_cast<const f32x4*>(lw + Ld::BF0 + 16 * mb + 4 * g);
       mfma_layer<NB, 4>(lw + Ld::SHF, lane, shb, h);
     }
-    if constexpr (SPLIT == 2) mfma_layer_pairs<true, NB, 1>(lw + Ld::F0, fd.fw0, 48, 0, wbad, lane, eb, h);
-    else if constexpr (SPLIT == 1) mfma_layer_split<NB, 2>(lw + Ld::F0, lane, eb, h);
-    else mfma_layer<NB, 8>(lw + Ld::F0, lane, eb, h);
+    tile_layer<PROD, true>(lw + Ld::F0, fd.fw0, 48, 0, wbad, lane, eb, h);
 #pragma unroll
     for (int mb = 0; mb < NB; ++mb)
 #pragma unroll
       for (int r = 0; r < 4; ++r) hb[4 * mb + r] = fmaxf(h[mb][r], 0.f);
     if constexpr (!COMPOSITE) {
       if (saving) {
-        constexpr float u = SPLIT == 2 ? 1.f / kPairAct : 1.f;
+        constexpr float u = PAIRS ? 1.f / kPairAct : 1.f;
 #pragma unroll
         for (int mb = 0; mb < NB; ++mb)
           stream_store(sv.hf + srow * (2 * H) + 16 * mb + 4 * g,
@@ -1041,16 +1044,14 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     }
 #pragma unroll
     for (int mb = 0; mb < NB; ++mb) h[mb] = *reinterpret_cast<const f32x4*>(lw + Ld::BF1 + 16 * mb + 4 * g);
-    if constexpr (SPLIT == 2) mfma_layer_pairs<true, NB, H / 32>(lw + Ld::F1, fd.fw1, H, 0, wbad, lane, hb, h);
-    else if constexpr (SPLIT == 1) mfma_layer_split<NB, NB>(lw + Ld::F1, lane, hb, h);
-    else mfma_layer<NB, H / 4>(lw + Ld::F1, lane, hb, h);
+    tile_layer<PROD, true>(lw + Ld::F1, fd.fw1, H, 0, wbad, lane, hb, h);
 #pragma unroll
     for (int mb = 0; mb < NB; ++mb)
 #pragma unroll
       for (int r = 0; r < 4; ++r) hb[4 * mb + r] = fmaxf(h[mb][r], 0.f);
     if constexpr (!COMPOSITE) {
       if (saving) {
-        constexpr float u = SPLIT == 2 ? 1.f / kPairAct : 1.f;
+        constexpr float u = PAIRS ? 1.f / kPairAct : 1.f;
 #pragma unroll
         for (int mb = 0; mb < NB; ++mb)
           stream_store(sv.hf + srow * (2 * H) + H + 16 * mb + 4 * g,
@@ -1068,8 +1069,8 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
       f32x4 o[2];
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb) o[mb] = *reinterpret_cast<const f32x4*>(lw + Ld::BF2 + 16 * mb + 4 * g);
-      mfma_layer<2, H / 4>(lw + Ld::F2, lane, hb, o);  // (SPLIT = 2: fw2 is staged x 1 / kPairAct -- true units)
-      if constexpr (SPLIT == 2) {
+      mfma_layer<2, H / 4>(lw + Ld::F2, lane, hb, o);  // (PAIRS: fw2 is staged x 1 / kPairAct -- true units)
+      if constexpr (PAIRS) {
         o[0] += e[0] * (1.f / kPairAct);
         o[1] += e[1] * (1.f / kPairAct);
       } else {
@@ -1142,7 +1143,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
           const f32x4 b2 = *reinterpret_cast<const f32x4*>(lw + Ld::BF2 + 16 * mb + 4 * g);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float es = SPLIT == 2 ? fa[mb][r] * (1.f / kPairAct) : fa[mb][r];  // (the embedding sum ran in tile units)
+            const float es = PAIRS ? fa[mb][r] * (1.f / kPairAct) : fa[mb][r];  // (the embedding sum ran in tile units)
             of2[mb][r] = fmaf(b2[r], wsum, row_sum16(of2[mb][r] + es));
           }
         }
@@ -1163,11 +1164,26 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
   }
 }
 
-// The grids the fused kernels are instantiated for: L * F == 32 (L = 16, 8, 4), and the smaller grids that live in the
-// padded frame (EncFrame): BASELINE config[0]'s 1 x 4, NeuRAD tiny's 4 x 2, and the L * F == 16 grids 4 x 4 and 8 x 2.
-static bool fused_grid_shape(int L, int F) {
-  return (L == 16 && F == 2) || (L == 8 && F == 4) || (L == 4 && F == 8) || (L == 1 && F == 4) || (L == 4 && F == 2) ||
-         (L == 4 && F == 4) || (L == 8 && F == 2);
+// ---- host side: which variant, and its launch -----------------------------------------------------------------------
+struct Variant {  // one row of render_variants.h
+  int L, F, H;
+  Out out;
+  Src src;
+  Prod prod;
+};
+constexpr Variant kVariants[] = {
+#define X(L_, F_, H_, O_, S_, P_) {L_, F_, H_, Out::O_, Src::S_, Prod::P_},
+    NRHIP_RENDER_VARIANTS(X)
+#undef X
+};
+
+static bool same(const Variant& a, const Variant& b) {
+  return a.L == b.L && a.F == b.F && a.H == b.H && a.out == b.out && a.src == b.src && a.prod == b.prod;
+}
+static bool has_variant(const Variant& v) {
+  for (const Variant& r : kVariants)
+    if (same(r, v)) return true;
+  return false;
 }
 
 static int validate_field(const nrhip_field* f) {
@@ -1177,9 +1193,10 @@ static int validate_field(const nrhip_field* f) {
   const nrhip_mlp& a = f->geo;
   const nrhip_mlp& b = f->feat;
   const int L = f->grid.num_levels, F = f->grid.n_features, in = L * F;
-  NR_REQUIRE(fused_grid_shape(L, F) && (a.hidden_dim == 32 || a.hidden_dim == 64), NRHIP_ERR_UNSUPPORTED,
-             "fused field kernel: no instantiation for L=%d F=%d H=%d (grids L x F = 16x2, 8x4, 4x8, 8x2, 4x4, 4x2, 1x4; "
-             "hidden width 32 or 64); use the unfused ops",
+  // (the table holds every static fp32 shape for both outputs: tests/test_fused_shapes_gate.py)
+  NR_REQUIRE(has_variant({L, F, a.hidden_dim, Out::Composite, Src::Static, Prod::F32}), NRHIP_ERR_UNSUPPORTED,
+             "fused field kernel: no instantiation for L=%d F=%d H=%d (the grids and hidden widths: csrc/render_variants.h); "
+             "use the unfused ops",
              L, F, a.hidden_dim);
   NR_REQUIRE(a.num_layers == 2 && b.num_layers == 3 && a.in_dim == in && a.out_dim == 33 && b.in_dim == 48 &&
                  b.out_dim == 32 && a.hidden_dim == b.hidden_dim,
@@ -1209,9 +1226,8 @@ static FieldDev to_dev(const nrhip_field& f) {
   return d;
 }
 
-// the candidate lists + actor tables an ACT launch reads (all device pointers)
+// the candidate lists + actor tables a Src::Actors launch reads (all device pointers)
 struct ActorLaunch {
-  const int32_t* range;  // [2] device: slice of the processing order (NULL = all rays)
   ActorFieldDev ad;
   const int32_t* cand_count;
   const int32_t* cand_actor;
@@ -1219,14 +1235,29 @@ struct ActorLaunch {
   const float* bounds;
   const void* const* tables;
 };
+// the caller's rows a Src::Overrides launch reads (device pointers)
+struct OverrideLaunch {
+  const int32_t* row;  // [N] row index of the sample, or -1
+  const float* rows;   // [P, L*F]
+  const float* dirs;   // [P, 3]
+};
+// What a launch hands to the kernel beside the field and the rays, whatever the variant (value-initialise: all off)
+struct RenderArgs {
+  float *feat, *depth, *acc, *w;  // composited: w optional | per-sample: feat, sdf, alpha
+  float *sdf, *alpha;
+  SaveDev sv;
+  float stop_eps;
+  const int32_t* range;  // [2] device: slice of the processing order (NULL = all rays)
+  ActorLaunch actors;
+  OverrideLaunch ovr;
+  hipStream_t stream;
+};
 
-template <int L, int F, int H, bool HALF, bool COMPOSITE, bool ACT = false, int SPLIT = 0, bool RELAY = false,
-          bool OVR = false>
-static int launch_render(const FieldDev& fd, const RaysDev& rd, float* of, float* od, float* oa, float* ow, float* os,
-                         float* oal, const SaveDev& sv, float stop_eps, hipStream_t st,
-                         const ActorLaunch& al = ActorLaunch()) {
-  constexpr size_t lds = ((ACT || OVR) ? Lds<H, SPLIT>::TOTAL_ACT : Lds<H, SPLIT>::TOTAL) * sizeof(float);
-  auto kern = render_kernel<L, F, H, HALF, COMPOSITE, ACT, SPLIT, RELAY, OVR>;
+template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD>
+static int launch_render(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
+  constexpr bool OVR = SRC == Src::Overrides;
+  constexpr size_t lds = ((SRC == Src::Actors || OVR) ? Lds<H, PROD>::TOTAL_ACT : Lds<H, PROD>::TOTAL) * sizeof(float);
+  auto kern = render_kernel<L, F, H, HALF, OUT, SRC, PROD>;
   static int cap = 0;  // persistent grid: CUs x resident workgroups per CU, queried once per instantiation
   if (!cap) {
     if (lds > 64 * 1024)
@@ -1239,122 +1270,67 @@ static int launch_render(const FieldDev& fd, const RaysDev& rd, float* of, float
   }
   const int64_t want = (rd.R + 3) / 4;
   const int blocks = (int)(want < cap ? want : cap);
-  kern<<<blocks, 256, lds, st>>>(fd, rd.R, rd.S, rd.stride, rd.order, rd.o, rd.d, rd.area, rd.starts, rd.ends, of, od, oa,
-                                 ow, os, oal, sv, stop_eps, al.range, al.ad, al.cand_count, al.cand_actor, al.cand_w2b,
-                                 al.bounds, al.tables);
+  const ActorLaunch& al = a.actors;
+  // (the override kernel reads its three arrays through the actor kernel's pointer arguments: see render_kernel)
+  kern<<<blocks, 256, lds, a.stream>>>(fd, rd.R, rd.S, rd.stride, rd.order, rd.o, rd.d, rd.area, rd.starts, rd.ends, a.feat,
+                                       a.depth, a.acc, a.w, a.sdf, a.alpha, a.sv, a.stop_eps, a.range, al.ad,
+                                       OVR ? a.ovr.row : al.cand_count, al.cand_actor, OVR ? a.ovr.rows : al.cand_w2b,
+                                       OVR ? a.ovr.dirs : al.bounds, al.tables);
   return check_launch("render/field fused kernel");
 }
 
-template <bool COMPOSITE>
-static int dispatch_render(const nrhip_field* f, const nrhip_rays* rays, float* of, float* od, float* oa, float* ow,
-                           float* os, float* oal, void* stream, const SaveDev& sv = SaveDev{}, float stop_eps = 0.f,
-                           const int32_t* range = nullptr) {
-  ActorLaunch al = ActorLaunch();
-  al.range = range;
-  const FieldDev fd = to_dev(*f);
-  const RaysDev rd = to_dev(*rays);
-  const hipStream_t st = (hipStream_t)stream;
+// THE preference order among the variants of one (L, F, H, output).  Actors and overrides are the caller's choice (fp32
+// products only); for the static scene the first of these that has a row in the table wins:
+static Variant choose_variant(const nrhip_field* f, Out out, Src src) {
   const int L = f->grid.num_levels, F = f->grid.n_features, H = f->geo.hidden_dim;
-  const bool half = f->grid.param_dtype == 1;
-  // NRHIP_MLP_SPLIT_BF16=1 (64-wide MLPs, composited output): the per-tile matrix products run as 3-way
-  // split bf16 on the matrix cores (mfma_layer_split) instead of the fp32 MFMA.  Same results to fp32 accuracy; NOT the
-  // default because it measured no faster (163 vs 163 us on config[1]: the splitting costs the vector ALU what the matrix
-  // pipe saves -- DESIGN.md §9).
+  if (src != Src::Static) return {L, F, H, out, src, Prod::F32};
+  const bool composite = out == Out::Composite;
   const bool split_bf16 = tuning().mlp_split_bf16;
-  // NRHIP_MLP_PAIRS (default 1): the same products as fp16 pairs (mfma_layer_pairs; composited output)
   const bool pairs = tuning().mlp_pairs >= 0 ? tuning().mlp_pairs == 1 : kPairsDefault;
-  if constexpr (COMPOSITE) {
-    // eval table given (nrhip_field.eval_table / eval_layout): the coarse levels are read from their shadow copies.  Decided
-    // FIRST: a caller that hands the table over asked for this kernel; it exists with fp32-MFMA products only (the
-    // static_assert above: the relayout and the split / pair products do not combine), so it wins over the pair default.
-    if (f->eval_table && f->eval_layout) {
-      FieldDev fe = fd;
-      fe.table = f->eval_table;
-#define RCASE(L_, F_, H_)                                                                                              \
-  if (L == L_ && F == F_ && H == H_)                                                                                   \
-    return half ? launch_render<L_, F_, H_, true, true, false, false, true>(fe, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al)  \
-                : launch_render<L_, F_, H_, false, true, false, false, true>(fe, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al);
-      RCASE(16, 2, 64)
-      RCASE(8, 4, 32)
-      RCASE(8, 4, 64)
-#undef RCASE
-    }
-  }
-  if constexpr (COMPOSITE) {
-    if (H == 64 && pairs && !split_bf16) {
-#define PCASE(L_, F_)                                                                                                  \
-  if (L == L_ && F == F_)                                                                                              \
-    return half ? launch_render<L_, F_, 64, true, true, false, 2>(fd, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al)      \
-                : launch_render<L_, F_, 64, false, true, false, 2>(fd, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al);
-      PCASE(16, 2)
-      PCASE(8, 4)
-      PCASE(4, 8)
-#undef PCASE
-    }
-    // ... and at NeuRAD's own width, where the arithmetic mostly hid under the memory time already (c2's render stage
-    // 72 -> 60-67 us)
-    if (H == 32 && pairs && !split_bf16) {
-#define PCASE(L_, F_)                                                                                                  \
-  if (L == L_ && F == F_)                                                                                              \
-    return half ? launch_render<L_, F_, 32, true, true, false, 2>(fd, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al)      \
-                : launch_render<L_, F_, 32, false, true, false, 2>(fd, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al);
-      PCASE(16, 2)
-      PCASE(8, 4)
-      PCASE(4, 8)
-#undef PCASE
-    }
-  }
-  if constexpr (!COMPOSITE) {
-    // the per-sample kernel (field forward / training forward with saved activations): the same pair products, OPT-IN
-    // (NRHIP_MLP_PAIRS_TRAIN=1).  Round 6 measured no gain: the kernel stores 516 B of activations per sample beside its
-    // gathers and is bound by them -- 1.03-1.09 ms with pairs against 1.01-1.03 ms with the fp32 MFMA on the c3 batch,
-    // the step unchanged (profiles/r06_ab_pairs_train.txt)
-    if (pairs && tuning().mlp_pairs_train && !split_bf16) {
-#define TCASE(L_, F_, H_)                                                                                              \
-  if (L == L_ && F == F_ && H == H_)                                                                                   \
-    return half ? launch_render<L_, F_, H_, true, false, false, 2>(fd, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al)     \
-                : launch_render<L_, F_, H_, false, false, false, 2>(fd, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al);
-      TCASE(8, 4, 32)
-      TCASE(16, 2, 64)
-      TCASE(8, 4, 64)
-      TCASE(16, 2, 32)
-#undef TCASE
-    }
-  }
-  if constexpr (COMPOSITE) {
-    if (H == 64 && split_bf16) {
-#define SCASE(L_, F_)                                                                                                  \
-  if (L == L_ && F == F_)                                                                                              \
-    return half ? launch_render<L_, F_, 64, true, true, false, 1>(fd, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al)      \
-                : launch_render<L_, F_, 64, false, true, false, 1>(fd, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al);
-      SCASE(16, 2)
-      SCASE(8, 4)
-      SCASE(4, 8)
-#undef SCASE
-    }
-  }
-#define CASE(L_, F_, H_)                                                                                          \
-  if (L == L_ && F == F_ && H == H_) {                                                                            \
-    return half ? launch_render<L_, F_, H_, true, COMPOSITE>(fd, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al)   \
-                : launch_render<L_, F_, H_, false, COMPOSITE>(fd, rd, of, od, oa, ow, os, oal, sv, stop_eps, st, al); \
-  }
-  CASE(16, 2, 64)
-  CASE(16, 2, 32)
-  CASE(8, 4, 32)
-  CASE(8, 4, 64)
-  CASE(4, 8, 32)
-  CASE(4, 8, 64)
-  // grids with L*F < 32, in the padded frame (EncFrame): fp32-MFMA products only
-  CASE(1, 4, 32)
-  CASE(1, 4, 64)
-  CASE(4, 2, 32)
-  CASE(4, 2, 64)
-  CASE(4, 4, 32)
-  CASE(4, 4, 64)
-  CASE(8, 2, 32)
-  CASE(8, 2, 64)
-#undef CASE
-  set_error("fused field kernel: no instantiation for L=%d F=%d H=%d", L, F, H);
+  const struct {
+    bool on;
+    Src src;
+    Prod prod;
+  } order[] = {
+      // 1. eval table given (nrhip_field.eval_table / eval_layout): the coarse levels are read from their shadow copies.
+      // Decided FIRST: a caller that hands the table over asked for this kernel; it exists with fp32-MFMA products only
+      // (render_variant_ok: the relayout and the split / pair products do not combine), so it wins over the pair default.
+      {composite && f->eval_table && f->eval_layout, Src::EvalTable, Prod::F32},
+      // 2. NRHIP_MLP_PAIRS (default 1): the products as fp16 pairs (mfma_layer_pairs) in the composited kernels -- at H = 64,
+      // and at NeuRAD's own width, where the arithmetic mostly hid under the memory time already (c2's render stage
+      // 72 -> 60-67 us).  In the per-sample kernel (field forward / training forward with saved activations) the same pair
+      // products are OPT-IN (NRHIP_MLP_PAIRS_TRAIN=1).  Round 6 measured no gain: the kernel stores 516 B of activations per
+      // sample beside its gathers and is bound by them -- 1.03-1.09 ms with pairs against 1.01-1.03 ms with the fp32 MFMA on
+      // the c3 batch, the step unchanged (profiles/r06_ab_pairs_train.txt)
+      {pairs && !split_bf16 && (composite || tuning().mlp_pairs_train), Src::Static, Prod::F16Pairs},
+      // 3. NRHIP_MLP_SPLIT_BF16=1 (64-wide MLPs, composited output): the per-tile matrix products run as 3-way split bf16
+      // on the matrix cores (mfma_layer_split) instead of the fp32 MFMA.  Same results to fp32 accuracy; NOT the default
+      // because it measured no faster (163 vs 163 us on config[1]: the splitting costs the vector ALU what the matrix pipe
+      // saves -- DESIGN.md §9).
+      {split_bf16 && composite, Src::Static, Prod::Bf16Split},
+  };
+  for (const auto& c : order)
+    if (c.on && has_variant({L, F, H, out, c.src, c.prod})) return {L, F, H, out, c.src, c.prod};
+  return {L, F, H, out, Src::Static, Prod::F32};  // 4. the fp32 MFMA
+}
+
+// Looks the chosen variant up in the table and launches it (fp32 or fp16 table by the grid's storage type).
+static int dispatch_render(const nrhip_field* f, const nrhip_rays* rays, Out out, Src src, const RenderArgs& a) {
+  const Variant v = choose_variant(f, out, src);
+  FieldDev fd = to_dev(*f);
+  if (v.src == Src::EvalTable) fd.table = f->eval_table;
+  const RaysDev rd = to_dev(*rays);
+  const bool half = f->grid.param_dtype == 1;
+#define X(L_, F_, H_, O_, S_, P_)                                                             \
+  if (same(v, {L_, F_, H_, Out::O_, Src::S_, Prod::P_}))                                      \
+    return half ? launch_render<L_, F_, H_, true, Out::O_, Src::S_, Prod::P_>(fd, rd, a)      \
+                : launch_render<L_, F_, H_, false, Out::O_, Src::S_, Prod::P_>(fd, rd, a);
+  NRHIP_RENDER_VARIANTS(X)
+#undef X
+  set_error("%s: no instantiation for L=%d F=%d H=%d",
+            src == Src::Actors ? "fused field kernel with actors" : src == Src::Overrides ? "field_fwd_train_ovr"
+                                                                                          : "fused field kernel",
+            v.L, v.F, v.H);
   return NRHIP_ERR_UNSUPPORTED;
 }
 
@@ -1394,30 +1370,6 @@ __global__ __launch_bounds__(kPartThreads) void actor_partition_kernel(const int
   if (tid == 0) ranges[0] = 0, ranges[1] = (int32_t)total, ranges[2] = (int32_t)total, ranges[3] = (int32_t)n;
 }
 
-// composited eval with dynamic actors: the static shapes NeuRAD uses with actors, fp32 or fp16 tables
-static int dispatch_render_actors(const nrhip_field* f, const nrhip_rays* rays, const ActorLaunch& al, float* of, float* od,
-                                  float* oa, float* ow, float stop_eps, void* stream) {
-  const FieldDev fd = to_dev(*f);
-  const RaysDev rd = to_dev(*rays);
-  const hipStream_t st = (hipStream_t)stream;
-  const int L = f->grid.num_levels, F = f->grid.n_features, H = f->geo.hidden_dim;
-  const bool half = f->grid.param_dtype == 1;
-#define CASE(L_, F_, H_)                                                                                                     \
-  if (L == L_ && F == F_ && H == H_)                                                                                         \
-    return half ? launch_render<L_, F_, H_, true, true, true>(fd, rd, of, od, oa, ow, nullptr, nullptr, SaveDev{}, stop_eps, \
-                                                              st, al)                                                        \
-                : launch_render<L_, F_, H_, false, true, true>(fd, rd, of, od, oa, ow, nullptr, nullptr, SaveDev{},          \
-                                                               stop_eps, st, al);
-  CASE(8, 4, 32)
-  CASE(8, 4, 64)
-  CASE(16, 2, 64)
-  CASE(4, 2, 32)  // NeuRAD tiny
-  CASE(4, 2, 64)
-#undef CASE
-  set_error("fused field kernel with actors: no instantiation for L=%d F=%d H=%d", L, F, H);
-  return NRHIP_ERR_UNSUPPORTED;
-}
-
 }  // namespace nrhip
 
 using namespace nrhip;
@@ -1428,7 +1380,19 @@ extern "C" int nrhip_field_fwd(const nrhip_field* f, const nrhip_rays* rays, flo
   if (int e = validate_rays(rays)) return e;
   if (rays->n_rays == 0 || rays->n_samples == 0) return NRHIP_OK;
   NR_REQUIRE(feature && sdf && alpha, NRHIP_ERR_INVALID_ARG, "field_fwd: NULL output");
-  return dispatch_render<false>(f, rays, feature, nullptr, nullptr, nullptr, sdf, alpha, stream);
+  RenderArgs a{};
+  a.feat = feature, a.sdf = sdf, a.alpha = alpha, a.stream = (hipStream_t)stream;
+  return dispatch_render(f, rays, Out::PerSample, Src::Static, a);
+}
+
+// the two training forwards: every output and save buffer present, the save buffers aligned for 16-byte stores
+static int check_train_buffers(const char* who, const float* feature, const float* sdf, const float* alpha,
+                               const SaveDev& sv) {
+  NR_REQUIRE(feature && sdf && alpha && sv.enc && sv.hg && sv.xf && sv.hf, NRHIP_ERR_INVALID_ARG, "%s: NULL output", who);
+  NR_REQUIRE(((reinterpret_cast<uintptr_t>(sv.enc) | reinterpret_cast<uintptr_t>(sv.hg) |
+               reinterpret_cast<uintptr_t>(sv.xf) | reinterpret_cast<uintptr_t>(sv.hf)) & 15) == 0,
+             NRHIP_ERR_INVALID_ARG, "%s: save buffers must be 16-byte aligned", who);
+  return NRHIP_OK;
 }
 
 extern "C" int nrhip_field_fwd_train(const nrhip_field* f, const nrhip_rays* rays, float* feature, float* sdf,
@@ -1437,13 +1401,11 @@ extern "C" int nrhip_field_fwd_train(const nrhip_field* f, const nrhip_rays* ray
   if (int e = validate_field(f)) return e;
   if (int e = validate_rays(rays)) return e;
   if (rays->n_rays == 0 || rays->n_samples == 0) return NRHIP_OK;
-  NR_REQUIRE(feature && sdf && alpha && save_enc && save_geo_hidden && save_feat_in && save_feat_hidden,
-             NRHIP_ERR_INVALID_ARG, "field_fwd_train: NULL output");
-  NR_REQUIRE(((reinterpret_cast<uintptr_t>(save_enc) | reinterpret_cast<uintptr_t>(save_geo_hidden) |
-               reinterpret_cast<uintptr_t>(save_feat_in) | reinterpret_cast<uintptr_t>(save_feat_hidden)) & 15) == 0,
-             NRHIP_ERR_INVALID_ARG, "field_fwd_train: save buffers must be 16-byte aligned");
-  const SaveDev sv{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
-  return dispatch_render<false>(f, rays, feature, nullptr, nullptr, nullptr, sdf, alpha, stream, sv);
+  RenderArgs a{};
+  a.feat = feature, a.sdf = sdf, a.alpha = alpha, a.stream = (hipStream_t)stream;
+  a.sv = SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
+  if (int e = check_train_buffers("field_fwd_train", feature, sdf, alpha, a.sv)) return e;
+  return dispatch_render(f, rays, Out::PerSample, Src::Static, a);
 }
 
 extern "C" int nrhip_field_fwd_train_ovr(const nrhip_field* f, const nrhip_rays* rays, const int32_t* ovr_row,
@@ -1453,37 +1415,17 @@ extern "C" int nrhip_field_fwd_train_ovr(const nrhip_field* f, const nrhip_rays*
   if (int e = validate_field(f)) return e;
   if (int e = validate_rays(rays)) return e;
   if (rays->n_rays == 0 || rays->n_samples == 0) return NRHIP_OK;
-  NR_REQUIRE(feature && sdf && alpha && save_enc && save_geo_hidden && save_feat_in && save_feat_hidden && ovr_row &&
-                 ovr_rows && ovr_dirs,
-             NRHIP_ERR_INVALID_ARG, "field_fwd_train_ovr: NULL pointer");
-  NR_REQUIRE(((reinterpret_cast<uintptr_t>(save_enc) | reinterpret_cast<uintptr_t>(save_geo_hidden) |
-               reinterpret_cast<uintptr_t>(save_feat_in) | reinterpret_cast<uintptr_t>(save_feat_hidden) |
-               reinterpret_cast<uintptr_t>(ovr_rows)) & 15) == 0,
-             NRHIP_ERR_INVALID_ARG, "field_fwd_train_ovr: save buffers and override rows must be 16-byte aligned");
+  RenderArgs a{};
+  a.feat = feature, a.sdf = sdf, a.alpha = alpha, a.stream = (hipStream_t)stream;
+  a.sv = SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
+  a.ovr = OverrideLaunch{ovr_row, ovr_rows, ovr_dirs};
+  if (int e = check_train_buffers("field_fwd_train_ovr", feature, sdf, alpha, a.sv)) return e;
+  NR_REQUIRE(ovr_row && ovr_rows && ovr_dirs, NRHIP_ERR_INVALID_ARG, "field_fwd_train_ovr: NULL pointer");
+  NR_REQUIRE((reinterpret_cast<uintptr_t>(ovr_rows) & 15) == 0, NRHIP_ERR_INVALID_ARG,
+             "field_fwd_train_ovr: override rows must be 16-byte aligned");
   NR_REQUIRE(rays->n_rays * rays->n_samples < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "field_fwd_train_ovr: N >= 2^31");
-  const SaveDev sv{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
-  ActorLaunch al = ActorLaunch();
-  al.cand_count = ovr_row, al.cand_w2b = ovr_rows, al.bounds = ovr_dirs;
-  const FieldDev fd = to_dev(*f);
-  const RaysDev rd = to_dev(*rays);
-  const int L = f->grid.num_levels, F = f->grid.n_features, H = f->geo.hidden_dim;
   NR_REQUIRE(f->grid.param_dtype == 0 || f->grid.param_dtype == 1, NRHIP_ERR_INVALID_ARG, "field_fwd_train_ovr: dtype");
-  const bool half = f->grid.param_dtype == 1;
-#define OCASE(L_, F_, H_)                                                                                                   \
-  if (L == L_ && F == F_ && H == H_)                                                                                        \
-    return half ? launch_render<L_, F_, H_, true, false, false, false, false, true>(fd, rd, feature, nullptr, nullptr, nullptr, \
-                                                                                    sdf, alpha, sv, 0.f, (hipStream_t)stream, al) \
-                : launch_render<L_, F_, H_, false, false, false, false, false, true>(fd, rd, feature, nullptr, nullptr,     \
-                                                                                     nullptr, sdf, alpha, sv, 0.f,          \
-                                                                                     (hipStream_t)stream, al);
-  OCASE(8, 4, 32)
-  OCASE(8, 4, 64)
-  OCASE(16, 2, 64)
-  OCASE(4, 2, 32)  // NeuRAD tiny
-  OCASE(4, 2, 64)
-#undef OCASE
-  set_error("field_fwd_train_ovr: no instantiation for L=%d F=%d H=%d", L, F, H);
-  return NRHIP_ERR_UNSUPPORTED;
+  return dispatch_render(f, rays, Out::PerSample, Src::Overrides, a);
 }
 
 extern "C" int nrhip_render_fwd_ex(const nrhip_field* f, const nrhip_rays* rays, float* out_features, float* out_depth,
@@ -1495,8 +1437,10 @@ extern "C" int nrhip_render_fwd_ex(const nrhip_field* f, const nrhip_rays* rays,
   NR_REQUIRE(rays->n_samples >= 1, NRHIP_ERR_INVALID_ARG, "render_fwd: needs >= 1 sample per ray");
   NR_REQUIRE(early_stop_eps >= 0.f && early_stop_eps < 1.f, NRHIP_ERR_INVALID_ARG,
              "render_fwd: early_stop_eps %g not in [0,1)", (double)early_stop_eps);
-  return dispatch_render<true>(f, rays, out_features, out_depth, out_acc, out_weights, nullptr, nullptr, stream,
-                               SaveDev{}, early_stop_eps);
+  RenderArgs a{};
+  a.feat = out_features, a.depth = out_depth, a.acc = out_acc, a.w = out_weights;
+  a.stop_eps = early_stop_eps, a.stream = (hipStream_t)stream;
+  return dispatch_render(f, rays, Out::Composite, Src::Static, a);
 }
 
 extern "C" int nrhip_render_fwd(const nrhip_field* f, const nrhip_rays* rays, float* out_features, float* out_depth,
@@ -1526,6 +1470,9 @@ extern "C" int nrhip_render_fwd_actors(const nrhip_field* f, const nrhip_actors*
              "render_fwd_actors: actor grid (L=%d F=%d) must have the static grid's features per level (F=%d) and at most "
              "its levels (L=%d); use the unfused ops",
              a->grid.num_levels, a->grid.n_features, f->grid.n_features, f->grid.num_levels);
+  RenderArgs ra{};
+  ra.feat = out_features, ra.depth = out_depth, ra.acc = out_acc, ra.w = out_weights;
+  ra.stop_eps = early_stop_eps, ra.stream = (hipStream_t)stream;
   ActorLaunch al;
   al.ad.K = a->max_candidates > 0 ? a->max_candidates : NRHIP_DEFAULT_ACTOR_CANDIDATES;
   al.ad.La = a->grid.num_levels, al.ad.log2T = a->grid.log2_table_size, al.ad.scale = a->actor_scale;
@@ -1540,9 +1487,8 @@ extern "C" int nrhip_render_fwd_actors(const nrhip_field* f, const nrhip_actors*
   if (int e = check_launch("actor_partition")) return e;
   nrhip_rays split = *rays;
   split.order = order2;
-  if (int e = dispatch_render<true>(f, &split, out_features, out_depth, out_acc, out_weights, nullptr, nullptr, stream,
-                                    SaveDev{}, early_stop_eps, ranges))
-    return e;
-  al.range = ranges + 2;
-  return dispatch_render_actors(f, &split, al, out_features, out_depth, out_acc, out_weights, early_stop_eps, stream);
+  ra.range = ranges;
+  if (int e = dispatch_render(f, &split, Out::Composite, Src::Static, ra)) return e;
+  ra.range = ranges + 2, ra.actors = al;
+  return dispatch_render(f, &split, Out::Composite, Src::Actors, ra);
 }

@@ -33,10 +33,12 @@ from ..field_components.neurad_encoding import (ActorSettings, NeuRADHashEncodin
                                                 StaticSettings)
 
 
+# The fields the fused kernels cover: host-side copies of csrc/render_variants.h (the gate works with no library loaded),
+# pinned to that table by tests/test_fused_shapes_gate.py.
 # (num_levels, features_per_level) of the static grids the fused field kernels cover
 _FUSED_GRIDS = ((16, 2), (8, 4), (4, 8), (1, 4), (4, 2), (4, 4), (8, 2))
 # (num_levels, features_per_level, hidden width) of the static fields the fused kernels with dynamic actors cover
-# (render.hip: dispatch_render_actors, nrhip_field_fwd_train_ovr)
+# (the table's Actors and Overrides rows)
 _FUSED_ACTOR_FIELDS = ((8, 4, 32), (8, 4, 64), (16, 2, 64), (4, 2, 32), (4, 2, 64))
 
 
@@ -152,7 +154,7 @@ class NeuRADField(nn.Module):
                     and all(a.hash_table.dtype == g.hash_table.dtype for a in self.hashgrid.actor_grids)
                     and (g.num_levels, g.features_per_level, c.geo_hidden_dim) in _FUSED_ACTOR_FIELDS):
                 return False
-        # grids the kernels are instantiated for (render.hip: fused_grid_shape): L * F == 32, and the smaller ones in the
+        # grids the kernels are instantiated for (csrc/render_variants.h): L * F == 32, and the smaller ones in the
         # kernel's padded frame -- BASELINE config[0]'s 1 x 4, NeuRAD tiny's 4 x 2, and 4 x 4 / 8 x 2
         return ((g.num_levels, g.features_per_level) in _FUSED_GRIDS and c.geo_num_layers == 2 and c.nff_num_layers == 3
                 and c.geo_hidden_dim == c.nff_hidden_dim and c.geo_hidden_dim in (32, 64) and c.nff_out_dim == 32)

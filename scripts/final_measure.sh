@@ -21,18 +21,19 @@ pmc c1_mfma render_kernel "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCL
 C2="python $R/bench.py --config c2 --steps 10 --warmup 2 --no-cpu-baseline"
 pmc c2_fetch proposal_sampler_kernel FETCH_SIZE $C2
 pmc c2_write proposal_sampler_kernel WRITE_SIZE $C2
+# render_kernel<L, F, H, fp16 table, Out (0 per sample, 1 composite), Src (0 static, 1 eval table, 2 actors, 3 overrides), Prod (0 fp32, 1 bf16 split, 2 fp16 pairs)>
 C3="python $R/bench.py --config c3 --steps 3 --warmup 1 --no-rgb-decoder"
-pmc c3_fetch "render_kernel<8, 4, 32, false, false" FETCH_SIZE $C3
-pmc c3_write "render_kernel<8, 4, 32, false, false" WRITE_SIZE $C3
+pmc c3_fetch "render_kernel<8, 4, 32, false, (nrhip::Out)0, (nrhip::Src)0, (nrhip::Prod)0>" FETCH_SIZE $C3
+pmc c3_write "render_kernel<8, 4, 32, false, (nrhip::Out)0, (nrhip::Src)0, (nrhip::Prod)0>" WRITE_SIZE $C3
 C4="python $R/bench.py --config c4 --steps 5 --warmup 2 --train-steps 0"
-pmc c4_fetch "render_kernel<8, 4, 32, true, true, true" FETCH_SIZE $C4
-pmc c4_write "render_kernel<8, 4, 32, true, true, true" WRITE_SIZE $C4
-pmc c4static_fetch "render_kernel<8, 4, 32, true, true, false" FETCH_SIZE $C4
+pmc c4_fetch "render_kernel<8, 4, 32, true, (nrhip::Out)1, (nrhip::Src)2, (nrhip::Prod)0>" FETCH_SIZE $C4
+pmc c4_write "render_kernel<8, 4, 32, true, (nrhip::Out)1, (nrhip::Src)2, (nrhip::Prod)0>" WRITE_SIZE $C4
+pmc c4static_fetch "render_kernel<8, 4, 32, true, (nrhip::Out)1, (nrhip::Src)0, (nrhip::Prod)2>" FETCH_SIZE $C4
 pmc c4s_fetch "proposal_sampler_kernel" FETCH_SIZE $C4
 pmc c4s_write "proposal_sampler_kernel" WRITE_SIZE $C4
 C4T="python $R/bench.py --config c4 --steps 2 --warmup 1 --train-steps 36"
-pmc c4t_fetch "render_kernel<8, 4, 32, true, false, false, 0, false, true" FETCH_SIZE $C4T
-pmc c4t_write "render_kernel<8, 4, 32, true, false, false, 0, false, true" WRITE_SIZE $C4T
+pmc c4t_fetch "render_kernel<8, 4, 32, true, (nrhip::Out)0, (nrhip::Src)3, (nrhip::Prod)0>" FETCH_SIZE $C4T
+pmc c4t_write "render_kernel<8, 4, 32, true, (nrhip::Out)0, (nrhip::Src)3, (nrhip::Prod)0>" WRITE_SIZE $C4T
 } > $OUT/${tag}_pmc_traffic.txt 2>&1
 cat $OUT/${tag}_pmc_traffic.txt
 python $R/scripts/traffic_from_pmc.py $OUT/${tag}_pmc_traffic.txt $tag; cp $R/profiles/traffic_*.json $OUT/

@@ -4,8 +4,10 @@ exist for.  Host logic only: no GPU.
 
 The checks run in a child process: importing the field module binds FieldHeadNames for the whole process (the
 reference's own enum when nerfstudio is importable, field_components/field_heads.py), which other tests pin."""
+import ast
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -68,7 +70,7 @@ def gate(cases):
 STATIC = [(1, 4, 32), (1, 4, 64), (4, 2, 32), (4, 2, 64), (4, 4, 32), (4, 4, 64), (8, 2, 32), (8, 2, 64), (8, 4, 32),
           (16, 2, 64), (4, 8, 32)]
 OTHER = [(3, 8, 32), (2, 2, 32), (4, 2, 48), (8, 8, 32)]
-WITH_ACTORS = [(4, 2, 32), (4, 2, 64), (8, 4, 32), (8, 4, 64), (16, 2, 64)]  # dispatch_render_actors / the ovr kernel
+WITH_ACTORS = [(4, 2, 32), (4, 2, 64), (8, 4, 32), (8, 4, 64), (16, 2, 64)]  # the actor and override kernels
 
 
 def test_static_grids_take_the_fused_kernels_where_they_are_instantiated():
@@ -94,3 +96,65 @@ def test_model_fused_paths_with_actors(L, F):
     res = gate([["model", L, F, 32]])
     want = (L, F) == (4, 2)
     assert res[f"model {L} {F} 32"] == [want, want]
+
+
+# ---- the gate's constants against the kernels' variant table -------------------------------------------------------------
+VARIANTS = os.path.join(ROOT, "neurad_studio_amd", "csrc", "render_variants.h")
+FIELD_PY = os.path.join(ROOT, "neurad_studio_amd", "fields", "neurad_field.py")
+
+
+def variant_rows(path=VARIANTS):
+    """-> [(L, F, H, output, source, products)] of the X-macro, comments dropped"""
+    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    table = src[src.index("#define NRHIP_RENDER_VARIANTS(X)"):]
+    return [(int(L), int(F), int(H), o, s, p)
+            for L, F, H, o, s, p in re.findall(r"\bX\(\s*(\d+),\s*(\d+),\s*(\d+),\s*(\w+),\s*(\w+),\s*(\w+)\s*\)", table)]
+
+
+def gate_constants():
+    """_FUSED_GRIDS / _FUSED_ACTOR_FIELDS read from the module's source (importing it binds FieldHeadNames: see the top)"""
+    out = {}
+    for node in ast.parse(open(FIELD_PY).read()).body:
+        if isinstance(node, ast.Assign) and getattr(node.targets[0], "id", "") in ("_FUSED_GRIDS", "_FUSED_ACTOR_FIELDS"):
+            out[node.targets[0].id] = set(ast.literal_eval(node.value))
+    return out
+
+
+def check_gate_against_table(rows, consts):
+    assert len(rows) == len(set(rows)) > 0, "duplicate or no rows"
+    assert {r[3] for r in rows} <= {"PerSample", "Composite"} and {r[4] for r in rows} <= {"Static", "EvalTable", "Actors", "Overrides"}
+    assert {r[5] for r in rows} <= {"F32", "Bf16Split", "F16Pairs"}
+    have = set(rows)
+    plain = {(L, F) for L, F, H, o, s, p in rows if (s, p) == ("Static", "F32")}
+    # a static grid is fused when the plain kernel exists for both outputs at both hidden widths -- and no plain row is a stray
+    whole = {(L, F) for L, F in plain
+             if all((L, F, H, o, "Static", "F32") in have for H in (32, 64) for o in ("PerSample", "Composite"))}
+    assert whole == plain == consts["_FUSED_GRIDS"], (whole ^ consts["_FUSED_GRIDS"], plain ^ whole)
+    assert {H for L, F, H, o, s, p in rows if (s, p) == ("Static", "F32")} == {32, 64}
+    actors = {(L, F, H) for L, F, H, o, s, p in rows if s == "Actors"}
+    overrides = {(L, F, H) for L, F, H, o, s, p in rows if s == "Overrides"}
+    assert actors == overrides == consts["_FUSED_ACTOR_FIELDS"], (actors ^ overrides, actors ^ consts["_FUSED_ACTOR_FIELDS"])
+    # the dispatcher's last candidate: every row has the plain kernel of its (L, F, H, output) behind it
+    for L, F, H, o, s, p in rows:
+        assert (L, F, H, o, "Static", "F32") in have, (L, F, H, o, s, p)
+
+
+def test_gate_constants_follow_the_variant_table():
+    rows = variant_rows()
+    assert len(rows) == 54  # one launch case per row, fp32 and fp16 tables each: render.hip's 108 render_kernel instantiations
+    check_gate_against_table(rows, gate_constants())
+
+
+def test_gate_check_notices_a_missing_row():
+    """the check above has teeth: any single row taken out of the table breaks it, unless that row is an optional variant
+    (eval table, pair / split products) the dispatcher merely prefers"""
+    rows, consts = variant_rows(), gate_constants()
+    for i, r in enumerate(rows):
+        optional = r[4] == "EvalTable" or r[5] != "F32"
+        try:
+            check_gate_against_table(rows[:i] + rows[i + 1:], consts)
+            noticed = False
+        except AssertionError:
+            noticed = True
+        assert noticed != optional, r
