@@ -650,6 +650,54 @@ int nrhip_occgrid_march(const nrhip_occgrid* grid, const float* origins, const f
 int nrhip_packed_visibility_from_alpha(const float* alphas, const int64_t* segments, int64_t r, float early_stop_eps,
                                        float alpha_thre, uint8_t* mask, void* stream);
 
+/* ---- C1 packed: compositing of the march's packed samples (nerfacc's packed render_weight_from_alpha /
+ *      render_weight_from_density / accumulate_along_rays, renderers.py:83-90,126-135,343-347,402-409) and their fusion.
+ *      segments int64 [R+1]: ray r owns the samples [segments[r], segments[r+1]) of the [M]-shaped arrays -- the fourth
+ *      output of the march's Python wrapper, or nrhip_packed_segments of ray_indices.  One wavefront walks one ray in
+ *      chunks of 64 with a carried prefix, the arithmetic of the dense kernels; no atomics (bitwise reproducible), no
+ *      allocation, no host synchronisation (graph-capturable).  r == 0 is a no-op that reads no pointer; a batch without
+ *      samples (every segment empty) reads no sample pointer and still zeroes the per-ray outputs.  Parity with nerfacc
+ *      itself is unpinned (un-vendored); what is pinned is listed in DESIGN.md.                                      */
+/* segments[q] = number of i with ray_indices[i] < q, q in [0, R].  PRECONDITION: ray_indices [M] is non-decreasing with
+ * values in [0, R) -- what the march and nerfacc both guarantee; it is not checked.                                  */
+int nrhip_packed_segments(const int64_t* ray_indices, int64_t m, int64_t r, int64_t* segments, void* stream);
+/* alpha_i = 1 - exp(-sigma_i (t_end_i - t_start_i)), T_i = exp(-sum_{j<i, same ray} sigma_j delta_j), w_i = T_i alpha_i;
+ * trans / alphas may be NULL.  Backward: gradient w.r.t. sigmas from grad_w.                                          */
+int nrhip_packed_weight_from_density(const float* t_starts, const float* t_ends, const float* sigmas,
+                                     const int64_t* segments, int64_t r, float* weights, float* trans /*or NULL*/,
+                                     float* alphas /*or NULL*/, void* stream);
+int nrhip_packed_weight_from_density_bwd(const float* t_starts, const float* t_ends, const float* sigmas,
+                                         const int64_t* segments, const float* grad_w, int64_t r, float* grad_sigmas,
+                                         void* stream);
+/* T_i = prod_{j<i, same ray} (1 - alpha_j), w_i = T_i alpha_i; trans may be NULL */
+int nrhip_packed_weight_from_alpha(const float* alphas, const int64_t* segments, int64_t r, float* weights,
+                                   float* trans /*or NULL*/, void* stream);
+int nrhip_packed_weight_from_alpha_bwd(const float* alphas, const int64_t* segments, const float* grad_w,
+                                       const float* grad_t /*may be NULL*/, int64_t r, float* grad_alphas, void* stream);
+/* out[r,c] = sum over ray r's samples of weights[i] values[i,c]  (values NULL: c must be 1, a plain sum of the weights).
+ * Every row of out is written, zeros for an empty segment: the caller does not pre-zero it.  C % 4 == 0 with 16-byte
+ * aligned rows reads values in 16-byte pieces (C = 32: 8 lanes a sample, C = 48: 4 lanes x 3), any other C >= 1 takes
+ * a generic path.                                                                                                     */
+int nrhip_packed_accumulate(const float* weights, const float* values /*[M,C] or NULL*/, const int64_t* segments,
+                            int64_t r, int32_t c, float* out /*[R,C]*/, void* stream);
+int nrhip_packed_accumulate_bwd(const float* weights, const float* values, const float* g_out /*[R,C]*/,
+                                const int64_t* segments, int64_t r, int32_t c, float* grad_weights /*[M], may be NULL*/,
+                                float* grad_values /*[M,C], may be NULL*/, void* stream);
+/* fused: weights (mode 1: from sigmas, mode 0: from alphas), sum w f, sum w (t_start + t_end) / 2 (render_depth_simple:
+ * no normalisation) and sum w in one pass over a ray's segment; no sky-residual sample.  The backward recomputes the
+ * transmittance and runs the sums over the later samples as a suffix scan; g_weights is the upstream gradient of
+ * out_weights.                                                                                                        */
+int nrhip_packed_composite_fwd(const float* t_starts, const float* t_ends, const float* sigmas_or_alphas,
+                               const float* features /*[M,C]*/, const int64_t* segments, int64_t r, int32_t c,
+                               int32_t mode, float* out_features /*[R,C]*/, float* out_depth /*[R,1]*/,
+                               float* out_accumulation /*[R,1]*/, float* out_weights /*[M], may be NULL*/, void* stream);
+int nrhip_packed_composite_bwd(const float* t_starts, const float* t_ends, const float* sigmas_or_alphas,
+                               const float* features, const int64_t* segments, const float* g_features /*[R,C]*/,
+                               const float* g_depth /*[R], may be NULL*/, const float* g_accumulation /*[R], may be NULL*/,
+                               const float* g_weights /*[M], may be NULL*/, int64_t r, int32_t c, int32_t mode,
+                               float* grad_sigmas_or_alphas /*[M], may be NULL*/, float* grad_features /*[M,C], may be NULL*/,
+                               void* stream);
+
 /* ---- S5+M1 fused: ProposalNetworkSampler as driven by NeuRADModel._get_ray_samples
  *      (ray_samplers.py:623-666, models/neurad.py:443-459).  One wave marches one ray through
  *      power bins -> (density -> weights -> pdf resample) x n_rounds, entirely on chip.

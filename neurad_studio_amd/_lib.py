@@ -212,6 +212,15 @@ PROTOTYPES = {
     "nrhip_render_fwd_actors": [C.POINTER(Field), C.POINTER(Actors), C.POINTER(Rays), P, P, P, P, P, P, P, F32, P, P],
     "nrhip_occgrid_march": [C.POINTER(OccGrid), P, P, P, P, P, I64, F32, F32, F32, F32, I32, P, P, P, P, P, P],
     "nrhip_packed_visibility_from_alpha": [P, P, I64, F32, F32, P, P],
+    "nrhip_packed_segments": [P, I64, I64, P, P],
+    "nrhip_packed_weight_from_density": [P, P, P, P, I64, P, P, P, P],
+    "nrhip_packed_weight_from_density_bwd": [P, P, P, P, P, I64, P, P],
+    "nrhip_packed_weight_from_alpha": [P, P, I64, P, P, P],
+    "nrhip_packed_weight_from_alpha_bwd": [P, P, P, P, I64, P, P],
+    "nrhip_packed_accumulate": [P, P, P, I64, I32, P, P],
+    "nrhip_packed_accumulate_bwd": [P, P, P, P, I64, I32, P, P, P],
+    "nrhip_packed_composite_fwd": [P, P, P, P, P, I64, I32, I32, P, P, P, P, P],
+    "nrhip_packed_composite_bwd": [P, P, P, P, P, P, P, P, P, I64, I32, I32, P, P, P],
     "nrhip_proposal_sampler_fwd": [C.POINTER(SamplerCfg), C.POINTER(Proposal), P, P, P, P, P, I64, C.POINTER(P),
                                    C.POINTER(P), C.POINTER(P), P],
     "nrhip_proposal_sampler_fwd_actors": [C.POINTER(SamplerCfg), C.POINTER(Proposal), C.POINTER(Actors), P, P, P, P, P, P, P,

@@ -396,6 +396,82 @@ class AccumulateFn(torch.autograd.Function):
         return ops.accumulate_along_rays_bwd(w, v, g.contiguous(), ctx.needs_input_grad[0], ctx.needs_input_grad[1])
 
 
+class PackedWeightFromDensityFn(torch.autograd.Function):
+    """nerfacc.render_weight_from_density, packed mode: [M] samples, ``segments`` [R+1].  Gradient w.r.t. sigmas."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, t_starts, t_ends, sigmas, segments):
+        ctx.save_for_backward(t_starts, t_ends, sigmas, segments)
+        w, t, a = ops.packed_weight_from_density(t_starts, t_ends, sigmas, segments)
+        ctx.mark_non_differentiable(t, a)
+        return w, t, a
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, gw, gt, ga):
+        s, e, sg, seg = ctx.saved_tensors
+        return None, None, ops.packed_weight_from_density_bwd(s, e, sg, seg, gw.contiguous()).view_as(sg), None
+
+
+class PackedWeightFromAlphaFn(torch.autograd.Function):
+    """nerfacc.render_weight_from_alpha, packed mode.  Gradients from the weights and the transmittance."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, alphas, segments):
+        ctx.save_for_backward(alphas, segments)
+        return ops.packed_weight_from_alpha(alphas, segments)
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, gw, gt):
+        a, seg = ctx.saved_tensors
+        ga = ops.packed_weight_from_alpha_bwd(a, seg, gw.contiguous(), None if gt is None else gt.contiguous())
+        return ga.view_as(a), None
+
+
+class PackedAccumulateFn(torch.autograd.Function):
+    """nerfacc.accumulate_along_rays, packed mode: weights [M], values [M,C] or None -> [R,C] / [R,1]."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, weights, values, segments):
+        ctx.save_for_backward(weights, values, segments)
+        return ops.packed_accumulate(weights, values, segments)
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, g):
+        w, v, seg = ctx.saved_tensors
+        need_v = v is not None and ctx.needs_input_grad[1]
+        gw, gv = ops.packed_accumulate_bwd(w, v, g.contiguous(), seg, ctx.needs_input_grad[0], need_v)
+        return (None if gw is None else gw.view_as(w)), gv, None
+
+
+class PackedCompositeFn(torch.autograd.Function):
+    """Fused packed compositing: weights from sigmas (density_mode) or alphas, then features [R,C], depth [R,1] (sum w mid,
+    render_depth_simple), accumulation [R,1] and the weights [M] in one pass.  Gradients to sigmas / alphas and features."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, t_starts, t_ends, x, features, segments, density_mode):
+        ctx.save_for_backward(t_starts, t_ends, x, features, segments)
+        ctx.density_mode = bool(density_mode)
+        ctx.set_materialize_grads(False)  # an output nobody used arrives as None, not as a tensor of zeros
+        return ops.packed_composite_fwd(t_starts, t_ends, x, features, segments, ctx.density_mode)
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, gf, gd, ga, gw):
+        s, e, x, f, seg = ctx.saved_tensors
+        if gf is None:
+            gf = torch.zeros((seg.shape[0] - 1, f.shape[1]), device=f.device, dtype=torch.float32)
+        gx, gfe = ops.packed_composite_bwd(s, e, x, f, seg, ctx.density_mode, gf.contiguous(), gd, ga, gw,
+                                           need_grad_x=ctx.needs_input_grad[2], need_grad_features=ctx.needs_input_grad[3])
+        return None, None, (None if gx is None else gx.view_as(x)), gfe, None, None
+
+
 class CarvingLossFn(torch.autograd.Function):
     """sum((w * (is_lidar & ~is_close))^2) over a level (models/neurad.py:399-408) -- value and gradient from ONE pass that
     recomputes the mask from the sample edges.  args: weights [R,S], starts, ends [R,S], is_lidar, did_return, distance

@@ -90,7 +90,9 @@ extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
 // 510: nrhip_encode_bwd_binned / nrhip_hashgrid_bwd_binned write fp32 gradients whatever g->param_dtype says (the fp16 form
 // is nrhip_encode_bwd_binned_f16); nrhip_adam_step_many_dev (+ _workspace), nrhip_tuning_reload.
 // 511: nrhip_nonfinite_check_many.
-extern "C" int nrhip_version(void) { return 511; }
+// 512: packed compositing: nrhip_packed_segments, nrhip_packed_weight_from_density / _alpha (+ _bwd),
+// nrhip_packed_accumulate (+ _bwd), nrhip_packed_composite_fwd / _bwd.
+extern "C" int nrhip_version(void) { return 512; }
 
 extern "C" int nrhip_tuning_reload(void) {
   nrhip::g_tuning = nrhip::read_tuning();

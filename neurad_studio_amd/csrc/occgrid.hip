@@ -8,6 +8,7 @@
 //     packed (ray_index, t_start, t_end).
 // One wavefront marches one ray 64 candidates at a time: ballot(occupied) -> popcount prefix -> compacted store.
 #include "common.h"
+#include "packed_composite.h"
 
 namespace nrhip {
 
@@ -188,4 +189,134 @@ extern "C" int nrhip_packed_visibility_from_alpha(const float* alphas, const int
   nrhip::packed_visibility_kernel<<<(int)((r + 3) / 4), 256, 0, (hipStream_t)stream>>>(alphas, segments, r,
                                                                                        early_stop_eps, alpha_thre, mask);
   return nrhip::check_launch("packed_visibility_from_alpha");
+}
+
+// ---- packed compositing (packed_composite.h): nerfacc's packed render_weight_from_* / accumulate_along_rays and their
+// fusion.  Validation on the host; r == 0 is a no-op that reads no pointer; a batch whose segments are all empty launches
+// (the per-ray outputs are zeroed) and touches no sample pointer.
+#define PACKED_COMMON(NAME, r_, segments_, c_)                                                       \
+  NR_REQUIRE((r_) >= 0, NRHIP_ERR_INVALID_ARG, NAME ": negative ray count");                          \
+  NR_REQUIRE((c_) >= 1, NRHIP_ERR_INVALID_ARG, NAME ": channel count %d < 1", (int)(c_));             \
+  if ((r_) == 0) return NRHIP_OK;                                                                    \
+  NR_REQUIRE((segments_), NRHIP_ERR_INVALID_ARG, NAME ": segments is NULL")
+
+#define PACKED_LAUNCH(KERNEL, r_, stream, ...) \
+  nrhip::packed::KERNEL<<<nrhip::packed::blocks_for(r_), 64 * nrhip::packed::kWaves, 0, (hipStream_t)stream>>>(__VA_ARGS__)
+
+extern "C" int nrhip_packed_segments(const int64_t* ray_indices, int64_t m, int64_t r, int64_t* segments, void* stream) {
+  NR_REQUIRE(r >= 0 && m >= 0, NRHIP_ERR_INVALID_ARG, "packed_segments: negative ray or sample count");
+  NR_REQUIRE(segments, NRHIP_ERR_INVALID_ARG, "packed_segments: segments is NULL");
+  NR_REQUIRE(m == 0 || ray_indices, NRHIP_ERR_INVALID_ARG, "packed_segments: ray_indices is NULL");
+  int blocks = grid_for(r + 1, 256);
+  blocks = blocks > 4096 ? 4096 : blocks;
+  nrhip::packed::segments_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(ray_indices, m, r, segments);
+  return check_launch("packed_segments");
+}
+
+extern "C" int nrhip_packed_weight_from_density(const float* t_starts, const float* t_ends, const float* sigmas,
+                                                const int64_t* segments, int64_t r, float* weights, float* trans,
+                                                float* alphas, void* stream) {
+  PACKED_COMMON("packed_weight_from_density", r, segments, 1);
+  PACKED_LAUNCH(fwd_kernel<nrhip::packed::kDensity>, r, stream, t_starts, t_ends, sigmas, nullptr, segments, r, 1, 1, 0,
+                nullptr, nullptr, nullptr, weights, trans, alphas);
+  return check_launch("packed_weight_from_density");
+}
+
+extern "C" int nrhip_packed_weight_from_density_bwd(const float* t_starts, const float* t_ends, const float* sigmas,
+                                                    const int64_t* segments, const float* grad_w, int64_t r,
+                                                    float* grad_sigmas, void* stream) {
+  PACKED_COMMON("packed_weight_from_density_bwd", r, segments, 1);
+  PACKED_LAUNCH(bwd_kernel<nrhip::packed::kDensity>, r, stream, t_starts, t_ends, sigmas, nullptr, segments, nullptr,
+                nullptr, nullptr, grad_w, nullptr, r, 1, 1, 0, grad_sigmas, nullptr);
+  return check_launch("packed_weight_from_density_bwd");
+}
+
+extern "C" int nrhip_packed_weight_from_alpha(const float* alphas, const int64_t* segments, int64_t r, float* weights,
+                                              float* trans, void* stream) {
+  PACKED_COMMON("packed_weight_from_alpha", r, segments, 1);
+  PACKED_LAUNCH(fwd_kernel<nrhip::packed::kAlpha>, r, stream, nullptr, nullptr, alphas, nullptr, segments, r, 1, 1, 0,
+                nullptr, nullptr, nullptr, weights, trans, nullptr);
+  return check_launch("packed_weight_from_alpha");
+}
+
+extern "C" int nrhip_packed_weight_from_alpha_bwd(const float* alphas, const int64_t* segments, const float* grad_w,
+                                                  const float* grad_t, int64_t r, float* grad_alphas, void* stream) {
+  PACKED_COMMON("packed_weight_from_alpha_bwd", r, segments, 1);
+  PACKED_LAUNCH(bwd_kernel<nrhip::packed::kAlpha>, r, stream, nullptr, nullptr, alphas, nullptr, segments, nullptr, nullptr,
+                nullptr, grad_w, grad_t, r, 1, 1, 0, grad_alphas, nullptr);
+  return check_launch("packed_weight_from_alpha_bwd");
+}
+
+extern "C" int nrhip_packed_accumulate(const float* weights, const float* values, const int64_t* segments, int64_t r,
+                                       int32_t c, float* out, void* stream) {
+  PACKED_COMMON("packed_accumulate", r, segments, c);
+  NR_REQUIRE(out, NRHIP_ERR_INVALID_ARG, "packed_accumulate: out is NULL");
+  NR_REQUIRE(values || c == 1, NRHIP_ERR_INVALID_ARG, "packed_accumulate: values is NULL (a plain sum) but c = %d", c);
+  const nrhip::packed::Plan p = nrhip::packed::plan_for(c, values, out, nullptr);
+  if (values)
+    PACKED_LAUNCH(fwd_kernel<nrhip::packed::kWeights>, r, stream, nullptr, nullptr, weights, values, segments, r, c, p.lp,
+                  p.k, out, nullptr, nullptr, nullptr, nullptr, nullptr);
+  else
+    PACKED_LAUNCH(fwd_kernel<nrhip::packed::kWeights>, r, stream, nullptr, nullptr, weights, nullptr, segments, r, 1, 1, 0,
+                  nullptr, nullptr, out, nullptr, nullptr, nullptr);
+  return check_launch("packed_accumulate");
+}
+
+extern "C" int nrhip_packed_accumulate_bwd(const float* weights, const float* values, const float* g_out,
+                                           const int64_t* segments, int64_t r, int32_t c, float* grad_weights,
+                                           float* grad_values, void* stream) {
+  PACKED_COMMON("packed_accumulate_bwd", r, segments, c);
+  NR_REQUIRE(g_out, NRHIP_ERR_INVALID_ARG, "packed_accumulate_bwd: g_out is NULL");
+  NR_REQUIRE(values || (c == 1 && !grad_values), NRHIP_ERR_INVALID_ARG,
+             "packed_accumulate_bwd: values is NULL (a plain sum) but c != 1 or grad_values is asked for");
+  if (!grad_weights && !grad_values) return NRHIP_OK;
+  const nrhip::packed::Plan p = nrhip::packed::plan_for(c, values, g_out, grad_values);
+  if (values)
+    PACKED_LAUNCH(bwd_kernel<nrhip::packed::kWeights>, r, stream, nullptr, nullptr, weights, values, segments, g_out,
+                  nullptr, nullptr, nullptr, nullptr, r, c, p.lp, p.k, grad_weights, grad_values);
+  else
+    PACKED_LAUNCH(bwd_kernel<nrhip::packed::kWeights>, r, stream, nullptr, nullptr, weights, nullptr, segments, nullptr,
+                  nullptr, g_out, nullptr, nullptr, r, 1, 1, 0, grad_weights, nullptr);
+  return check_launch("packed_accumulate_bwd");
+}
+
+extern "C" int nrhip_packed_composite_fwd(const float* t_starts, const float* t_ends, const float* sigmas_or_alphas,
+                                          const float* features, const int64_t* segments, int64_t r, int32_t c,
+                                          int32_t mode, float* out_features, float* out_depth, float* out_accumulation,
+                                          float* out_weights, void* stream) {
+  PACKED_COMMON("packed_composite_fwd", r, segments, c);
+  NR_REQUIRE(mode == 0 || mode == 1, NRHIP_ERR_INVALID_ARG, "packed_composite_fwd: mode %d not 0 (alphas) or 1 (sigmas)",
+             mode);
+  NR_REQUIRE(out_features && out_depth && out_accumulation, NRHIP_ERR_INVALID_ARG,
+             "packed_composite_fwd: a per-ray output is NULL");
+  const nrhip::packed::Plan p = nrhip::packed::plan_for(c, features, out_features, nullptr);
+  if (mode == 1)
+    PACKED_LAUNCH(fwd_kernel<nrhip::packed::kDensity>, r, stream, t_starts, t_ends, sigmas_or_alphas, features, segments,
+                  r, c, p.lp, p.k, out_features, out_depth, out_accumulation, out_weights, nullptr, nullptr);
+  else
+    PACKED_LAUNCH(fwd_kernel<nrhip::packed::kAlpha>, r, stream, t_starts, t_ends, sigmas_or_alphas, features, segments, r,
+                  c, p.lp, p.k, out_features, out_depth, out_accumulation, out_weights, nullptr, nullptr);
+  return check_launch("packed_composite_fwd");
+}
+
+extern "C" int nrhip_packed_composite_bwd(const float* t_starts, const float* t_ends, const float* sigmas_or_alphas,
+                                          const float* features, const int64_t* segments, const float* g_features,
+                                          const float* g_depth, const float* g_accumulation, const float* g_weights,
+                                          int64_t r, int32_t c, int32_t mode, float* grad_sigmas_or_alphas,
+                                          float* grad_features, void* stream) {
+  PACKED_COMMON("packed_composite_bwd", r, segments, c);
+  NR_REQUIRE(mode == 0 || mode == 1, NRHIP_ERR_INVALID_ARG, "packed_composite_bwd: mode %d not 0 (alphas) or 1 (sigmas)",
+             mode);
+  NR_REQUIRE(g_features, NRHIP_ERR_INVALID_ARG, "packed_composite_bwd: g_features is NULL");
+  if (!grad_sigmas_or_alphas && !grad_features) return NRHIP_OK;
+  const nrhip::packed::Plan p = nrhip::packed::plan_for(c, features, g_features, grad_features);
+  if (mode == 1)
+    PACKED_LAUNCH(bwd_kernel<nrhip::packed::kDensity>, r, stream, t_starts, t_ends, sigmas_or_alphas, features, segments,
+                  g_features, g_depth, g_accumulation, g_weights, nullptr, r, c, p.lp, p.k, grad_sigmas_or_alphas,
+                  grad_features);
+  else
+    PACKED_LAUNCH(bwd_kernel<nrhip::packed::kAlpha>, r, stream, t_starts, t_ends, sigmas_or_alphas, features, segments,
+                  g_features, g_depth, g_accumulation, g_weights, nullptr, r, c, p.lp, p.k, grad_sigmas_or_alphas,
+                  grad_features);
+  return check_launch("packed_composite_bwd");
 }

@@ -25,7 +25,7 @@ from torch import Tensor, nn
 
 from .. import autograd as ag
 from .. import ops
-from ..cameras.rays import RaySamples, per_ray, sample_times
+from ..cameras.rays import Frustums, RaySamples, per_ray, sample_times
 from ..field_components.encodings import SHEncoding
 from ..field_components.field_heads import FieldHeadNames
 from ..field_components.mlp import MLP
@@ -276,6 +276,15 @@ class NeuRADField(nn.Module):
     # ---- Field.forward (neurad_field.py:128-152) ------------------------------------------------
     def forward(self, ray_samples: RaySamples, compute_normals: bool = False) -> Dict[FieldHeadNames, Tensor]:
         fr = ray_samples.frustums  # this package's RaySamples or the reference's (cameras/rays.py:142-187)
+        if fr.starts.dim() == 2:
+            # packed samples [M,1] with their own origins [M,3] (VolumetricSampler): M rays of one sample each through the
+            # same kernels; the heads come back with the packed batch shape, [M,C]
+            up = lambda t: None if t is None else t[:, None]  # noqa: E731
+            dense = RaySamples(frustums=Frustums(origins=fr.origins[:, None], directions=fr.directions[:, None],
+                                                 starts=fr.starts[:, None], ends=fr.ends[:, None],
+                                                 pixel_area=fr.pixel_area[:, None], offsets=up(fr.offsets)),
+                               camera_indices=ray_samples.camera_indices, times=ray_samples.times)
+            return {k: v[:, 0] for k, v in self.forward(dense, compute_normals).items()}
         o, d, a = per_ray(fr)
         starts, ends = fr.starts[..., 0], fr.ends[..., 0]
         R, S = starts.shape

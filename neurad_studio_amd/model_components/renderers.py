@@ -1,5 +1,6 @@
 """Renderers with the reference's signatures (model_components/renderers.py:59-90,322-350,353-418) and
-render_depth_simple (models/neurad.py:727-734), dense mode, on the HIP compositing kernels."""
+render_depth_simple (models/neurad.py:727-734) on the HIP compositing kernels: dense, and -- with ``ray_indices`` and
+``num_rays`` -- over the packed samples of VolumetricSampler; ``render_packed`` is the fused packed form."""
 from __future__ import annotations
 
 from typing import Optional
@@ -37,8 +38,12 @@ class DepthRenderer(nn.Module):
     def forward(self, weights: Tensor, ray_samples: RaySamples, ray_indices=None, num_rays=None) -> Tensor:
         eps = 1e-10
         steps = (ray_samples.frustums.starts + ray_samples.frustums.ends) / 2
-        depth = nerfacc.accumulate_along_rays(weights[..., 0], values=steps)
-        acc = nerfacc.accumulate_along_rays(weights[..., 0], values=None)
+        if ray_indices is not None and num_rays is not None:  # packed samples of the volumetric sampler
+            depth = nerfacc.accumulate_along_rays(weights[..., 0], values=steps, ray_indices=ray_indices, n_rays=num_rays)
+            acc = nerfacc.accumulate_along_rays(weights[..., 0], values=None, ray_indices=ray_indices, n_rays=num_rays)
+        else:
+            depth = nerfacc.accumulate_along_rays(weights[..., 0], values=steps)
+            acc = nerfacc.accumulate_along_rays(weights[..., 0], values=None)
         depth = depth / (acc + eps)
         return torch.clip(depth, steps.min(), steps.max())
 
@@ -53,3 +58,19 @@ class NormalsRenderer(nn.Module):
         if normalize:
             n = n / (torch.linalg.norm(n, dim=-1, keepdim=True) + 1e-10)
         return n
+
+
+def render_packed(features: Tensor, ray_samples: RaySamples, ray_indices: Tensor, num_rays: int, *,
+                  density: Optional[Tensor] = None, alpha: Optional[Tensor] = None) -> dict:
+    """Fused compositing of the packed samples ``VolumetricSampler.forward`` returns: features [M,C] and exactly one of
+    density / alpha ([M] or [M,1]) -> ``features`` [R,C], ``depth`` [R,1] (render_depth_simple: sum w mid, not normalised),
+    ``accumulation`` [R,1] and the per-sample ``weights`` [M,1], one kernel forward and one backward."""
+    from .. import autograd as ag
+
+    if (density is None) == (alpha is None):
+        raise ValueError("render_packed: give exactly one of density / alpha")
+    x = density if density is not None else alpha
+    seg = ag.ops.packed_segments(ray_indices, int(num_rays))
+    f, d, a, w = ag.PackedCompositeFn.apply(ray_samples.frustums.starts.reshape(-1), ray_samples.frustums.ends.reshape(-1),
+                                            x.reshape(-1), features, seg, density is not None)
+    return {"features": f, "depth": d, "accumulation": a, "weights": w[..., None]}

@@ -1158,6 +1158,144 @@ def packed_visibility_from_alpha(alphas: Tensor, segments: Tensor, early_stop_ep
     return mask.bool()
 
 
+# ---- packed compositing (csrc/packed_composite.h): every op takes `segments` int64 [R+1], the march's fourth output ----
+def _seg(segments: Tensor) -> Tuple[Tensor, int]:
+    s = _chk(segments, "segments", torch.int64)
+    if s.dim() != 1 or s.shape[0] < 1:
+        raise ValueError("segments must be int64 [R+1]")
+    return s, s.shape[0] - 1
+
+
+def _flat(t: Tensor, name: str, m: Optional[int] = None) -> Tensor:
+    t = _chk(t, name)
+    t = t.reshape(-1)
+    if m is not None and t.shape[0] != m:
+        raise ValueError(f"{name}: {t.shape[0]} samples, expected {m}")
+    return t
+
+
+def packed_segments(ray_indices: Tensor, n_rays: int) -> Tensor:
+    """sorted ray_indices int64 [M] with values in [0, n_rays) -> segments int64 [n_rays + 1]"""
+    ri = _chk(ray_indices, "ray_indices", torch.int64).reshape(-1)
+    seg = torch.empty((int(n_rays) + 1,), dtype=torch.int64, device=ri.device)
+    call("nrhip_packed_segments", _ptr(ri), ri.shape[0], int(n_rays), _ptr(seg), _stream())
+    return seg
+
+
+def packed_weight_from_density(t_starts, t_ends, sigmas, segments):
+    """-> weights, trans, alphas [M]"""
+    sg = _flat(sigmas, "sigmas")
+    s, e = _flat(t_starts, "t_starts", sg.shape[0]), _flat(t_ends, "t_ends", sg.shape[0])
+    seg, R = _seg(segments)
+    w, t, a = torch.empty_like(sg), torch.empty_like(sg), torch.empty_like(sg)
+    call("nrhip_packed_weight_from_density", _ptr(s), _ptr(e), _ptr(sg), _ptr(seg), R, _ptr(w), _ptr(t), _ptr(a), _stream())
+    return w, t, a
+
+
+def packed_weight_from_density_bwd(t_starts, t_ends, sigmas, segments, grad_w):
+    sg = _flat(sigmas, "sigmas")
+    s, e, gw = (_flat(v, n, sg.shape[0]) for v, n in ((t_starts, "t_starts"), (t_ends, "t_ends"), (grad_w, "grad_w")))
+    seg, R = _seg(segments)
+    gs = torch.empty_like(sg)
+    call("nrhip_packed_weight_from_density_bwd", _ptr(s), _ptr(e), _ptr(sg), _ptr(seg), _ptr(gw), R, _ptr(gs), _stream())
+    return gs
+
+
+def packed_weight_from_alpha(alphas, segments):
+    """-> weights, trans [M]"""
+    a = _flat(alphas, "alphas")
+    seg, R = _seg(segments)
+    w, t = torch.empty_like(a), torch.empty_like(a)
+    call("nrhip_packed_weight_from_alpha", _ptr(a), _ptr(seg), R, _ptr(w), _ptr(t), _stream())
+    return w, t
+
+
+def packed_weight_from_alpha_bwd(alphas, segments, grad_w, grad_t=None):
+    a = _flat(alphas, "alphas")
+    gw = _flat(grad_w, "grad_w", a.shape[0])
+    gt = None if grad_t is None else _flat(grad_t, "grad_t", a.shape[0])
+    seg, R = _seg(segments)
+    ga = torch.empty_like(a)
+    call("nrhip_packed_weight_from_alpha_bwd", _ptr(a), _ptr(seg), _ptr(gw), _ptr(gt), R, _ptr(ga), _stream())
+    return ga
+
+
+def packed_accumulate(weights, values, segments):
+    """weights [M], values [M,C] or None -> [R,C] ([R,1] without values); rays without samples get zeros"""
+    w = _flat(weights, "weights")
+    seg, R = _seg(segments)
+    v = None
+    if values is not None:
+        v = _chk(values, "values")
+        if v.dim() != 2 or v.shape[0] != w.shape[0] or v.shape[1] < 1:
+            raise ValueError("values must be [M,C] with one row per weight")
+    Cc = 1 if v is None else v.shape[1]
+    out = torch.empty((R, Cc), device=w.device, dtype=torch.float32)
+    # an empty [0,C] tensor has no address, and NULL values mean "the plain sum": any non-null address stands in (no sample,
+    # nothing is read through it; the rows of out are still zeroed by the kernel)
+    vp = _ptr(out) if (v is not None and v.numel() == 0) else _ptr(v)
+    call("nrhip_packed_accumulate", _ptr(w), vp, _ptr(seg), R, Cc, _ptr(out), _stream())
+    return out
+
+
+def packed_accumulate_bwd(weights, values, g_out, segments, need_grad_weights=True, need_grad_values=True):
+    """-> (grad weights [M] or None, grad values [M,C] or None)"""
+    w = _flat(weights, "weights")
+    seg, R = _seg(segments)
+    v = None if values is None else _chk(values, "values")
+    Cc = 1 if v is None else v.shape[1]
+    g = _chk(g_out, "g_out")
+    if g.shape != (R, Cc):
+        raise ValueError(f"g_out must be [{R},{Cc}]")
+    gw = torch.empty_like(w) if need_grad_weights else None
+    gv = torch.empty_like(v) if (need_grad_values and v is not None) else None
+    if w.numel():  # (no samples: nothing to write, and an empty values tensor has no address to tell it from "plain sum")
+        call("nrhip_packed_accumulate_bwd", _ptr(w), _ptr(v), _ptr(g), _ptr(seg), R, Cc, _ptr(gw), _ptr(gv), _stream())
+    return gw, gv
+
+
+def packed_composite_fwd(t_starts, t_ends, sigmas_or_alphas, features, segments, density_mode: bool,
+                         return_weights: bool = True):
+    """fused packed compositing -> features [R,C], depth [R,1] (sum w mid), accumulation [R,1], weights [M] or None"""
+    x = _flat(sigmas_or_alphas, "sigmas" if density_mode else "alphas")
+    M = x.shape[0]
+    s, e = _flat(t_starts, "t_starts", M), _flat(t_ends, "t_ends", M)
+    f = _chk(features, "features")
+    if f.dim() != 2 or f.shape[0] != M or f.shape[1] < 1:
+        raise ValueError("features must be [M,C] with one row per sample")
+    seg, R = _seg(segments)
+    Cc = f.shape[1]
+    of = torch.empty((R, Cc), device=x.device, dtype=torch.float32)
+    od = torch.empty((R, 1), device=x.device, dtype=torch.float32)
+    oa = torch.empty((R, 1), device=x.device, dtype=torch.float32)
+    ow = torch.empty_like(x) if return_weights else None
+    call("nrhip_packed_composite_fwd", _ptr(s), _ptr(e), _ptr(x), _ptr(f), _ptr(seg), R, Cc, 1 if density_mode else 0,
+         _ptr(of), _ptr(od), _ptr(oa), _ptr(ow), _stream())
+    return of, od, oa, ow
+
+
+def packed_composite_bwd(t_starts, t_ends, sigmas_or_alphas, features, segments, density_mode: bool, g_features,
+                         g_depth=None, g_accumulation=None, g_weights=None, need_grad_x=True, need_grad_features=True):
+    """-> (grad sigmas / alphas [M] or None, grad features [M,C] or None)"""
+    x = _flat(sigmas_or_alphas, "sigmas" if density_mode else "alphas")
+    M = x.shape[0]
+    s, e = _flat(t_starts, "t_starts", M), _flat(t_ends, "t_ends", M)
+    f = _chk(features, "features")
+    seg, R = _seg(segments)
+    Cc = f.shape[1]
+    gF = _chk(g_features, "g_features")
+    if gF.shape != (R, Cc):
+        raise ValueError(f"g_features must be [{R},{Cc}]")
+    gd = None if g_depth is None else _flat(g_depth, "g_depth", R)
+    ga = None if g_accumulation is None else _flat(g_accumulation, "g_accumulation", R)
+    gw = None if g_weights is None else _flat(g_weights, "g_weights", M)
+    gx = torch.empty_like(x) if need_grad_x else None
+    gf = torch.empty_like(f) if need_grad_features else None
+    call("nrhip_packed_composite_bwd", _ptr(s), _ptr(e), _ptr(x), _ptr(f), _ptr(seg), _ptr(gF), _ptr(gd), _ptr(ga), _ptr(gw),
+         R, Cc, 1 if density_mode else 0, _ptr(gx), _ptr(gf), _stream())
+    return gx, gf
+
+
 def adam_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, step: int, lr: float, beta1: float = 0.9,
               beta2: float = 0.999, eps: float = 1e-15, weight_decay: float = 0.0, grad_scale: float = 1.0) -> None:
     """torch.optim.Adam / AdamW update of one fp32 tensor, in place (csrc/adam.hip)"""

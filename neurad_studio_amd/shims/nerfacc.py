@@ -1,5 +1,6 @@
-"""nerfacc-shaped module (dense mode) on HIP kernels: the three functions neurad-studio calls
-(models/neurad.py:716-723,734; model_components/renderers.py:88,130,133,345,404,407,455,486).
+"""nerfacc-shaped module on HIP kernels: the three functions neurad-studio calls
+(models/neurad.py:716-723,734; model_components/renderers.py:88,130,133,345,404,407,455,486), dense and -- with
+``ray_indices`` + ``n_rays`` or ``packed_info`` -- packed (csrc/packed_composite.h), and ``pack_info``.
 Put this directory on sys.path as ``nerfacc`` or import it directly."""
 from __future__ import annotations
 
@@ -10,24 +11,52 @@ from torch import Tensor
 from .. import autograd as ag
 
 
+def _segments(packed_info, ray_indices, n_rays, prefix_trans=None) -> Tensor:
+    """segments int64 [R+1] of a packed call: from packed_info [R,2] (start, count) or sorted ray_indices + n_rays"""
+    import torch
+
+    if prefix_trans is not None:
+        raise NotImplementedError("prefix_trans")
+    if packed_info is not None:
+        info = packed_info.to(torch.int64)
+        seg = torch.empty((info.shape[0] + 1,), dtype=torch.int64, device=info.device)
+        seg[:-1] = info[:, 0]
+        seg[-1:] = (info[-1:, 0] + info[-1:, 1]) if info.shape[0] else 0
+        return seg
+    if n_rays is None:
+        raise ValueError("packed mode: ray_indices needs n_rays")
+    return ag.ops.packed_segments(ray_indices, int(n_rays))
+
+
+def pack_info(ray_indices: Tensor, n_rays: Optional[int] = None) -> Tensor:
+    """nerfacc.pack_info: sorted ray_indices [M] -> packed_info [n_rays, 2] (start, count) per ray"""
+    import torch
+
+    if n_rays is None:
+        raise ValueError("pack_info: n_rays is needed (no host synchronisation to find it)")
+    seg = ag.ops.packed_segments(ray_indices, int(n_rays))
+    return torch.stack([seg[:-1], seg[1:] - seg[:-1]], -1)
+
+
 def render_weight_from_alpha(alphas: Tensor, packed_info=None, ray_indices=None, n_rays=None,
                              prefix_trans=None) -> Tuple[Tensor, Tensor]:
     if packed_info is not None or ray_indices is not None:
-        raise NotImplementedError("packed mode has no caller in neurad-studio (SURVEY §2.1)")
+        return ag.PackedWeightFromAlphaFn.apply(alphas, _segments(packed_info, ray_indices, n_rays, prefix_trans))
     return ag.WeightFromAlphaFn.apply(alphas.contiguous())
 
 
 def render_weight_from_density(t_starts: Tensor, t_ends: Tensor, sigmas: Tensor, packed_info=None, ray_indices=None,
                                n_rays=None, prefix_trans=None) -> Tuple[Tensor, Tensor, Tensor]:
     if packed_info is not None or ray_indices is not None:
-        raise NotImplementedError("packed mode has no caller in neurad-studio (SURVEY §2.1)")
+        return ag.PackedWeightFromDensityFn.apply(t_starts, t_ends, sigmas,
+                                                  _segments(packed_info, ray_indices, n_rays, prefix_trans))
     return ag.WeightFromDensityFn.apply(t_starts.contiguous(), t_ends.contiguous(), sigmas.contiguous())
 
 
 def accumulate_along_rays(weights: Tensor, values: Optional[Tensor] = None, ray_indices: Optional[Tensor] = None,
                           n_rays: Optional[int] = None) -> Tensor:
     if ray_indices is not None:
-        raise NotImplementedError("packed mode has no caller in neurad-studio (SURVEY §2.1)")
+        return ag.PackedAccumulateFn.apply(weights, values, _segments(None, ray_indices, n_rays))
     if values is None:
         return weights.sum(-1, keepdim=True) if weights.requires_grad else ag.ops.accumulate_along_rays(weights.contiguous())
     return ag.AccumulateFn.apply(weights.contiguous(), values.contiguous())
