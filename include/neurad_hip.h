@@ -646,6 +646,48 @@ int nrhip_occgrid_march(const nrhip_occgrid* grid, const float* origins, const f
                         int32_t max_candidates, int32_t* counts /*[R], counting pass*/,
                         const int64_t* offsets /*[R], write pass*/, int64_t* ray_indices, float* t_starts,
                         float* t_ends, void* stream);
+/* Multi-level grid: level l is the level-0 box scaled by 2^l about its centre (the caller passes every box, nested and in
+ * that order).  The march clips the ray to the outermost box; a candidate's level is the first whose box contains its
+ * midpoint, and it is kept iff that level's cell (same floor-and-clamp rule) is set.  Same two passes and outputs as
+ * nrhip_occgrid_march; with levels == 1 the outputs are those of nrhip_occgrid_march bit for bit.                      */
+#define NRHIP_OCCGRID_MAX_LEVELS 8
+typedef struct {
+  int32_t levels, resolution;                 /* res^3 cells per level, cell index = (ix*res + iy)*res + iz */
+  float aabbs[NRHIP_OCCGRID_MAX_LEVELS][6];   /* per level: min xyz, max xyz */
+  uint8_t* binaries;                          /* [levels,res,res,res] occupancy (written by the update entry points) */
+} nrhip_occgrid_levels;
+int nrhip_occgrid_march_levels(const nrhip_occgrid_levels* grid, const float* origins, const float* directions,
+                               const float* t_min /*[R] or NULL*/, const float* t_max /*[R] or NULL*/,
+                               const float* t_rand /*[R] or NULL*/, int64_t r, float render_step_size, float near_plane,
+                               float far_plane, float cone_angle, int32_t max_candidates, int32_t* counts,
+                               const int64_t* offsets, int64_t* ray_indices, float* t_starts, float* t_ends,
+                               void* stream);
+/* ---- occupancy-grid maintenance (modelled on nerfacc 0.5 OccGridEstimator._update / mark_invisible_cells; the rule is
+ *      stated in csrc/occgrid_update.h and restated in tests/occgrid_update_restatement.py -- parity with nerfacc itself is
+ *      unpinned, like the march).  occs fp32 [levels*res^3]; occs < 0 marks an invisible cell.  No entry point allocates,
+ *      synchronises with the host or sizes anything by data; results are bitwise reproducible.
+ *      workspace: device scratch of nrhip_occgrid_update_workspace bytes, ZERO-FILLED once by the caller and then owned by
+ *      the grid (the entry points keep the parts they rely on zeroed).                                               */
+int nrhip_occgrid_update_workspace(int32_t levels, int32_t resolution, int64_t* bytes);
+/* Candidate cells and their jittered positions.  warmup != 0: every visible cell of every level, capacity res^3 per level.
+ * warmup == 0: per level the visible ones of the n draws cell_draws int64 [levels,n], then its occupied cells in ascending
+ * order (more than n: n draws with replacement through sel_draws fp32 [levels,n] in [0,1)), capacity 2 n per level.
+ * jitter fp32 [levels,capacity,3] in [0,1).  Outputs: cell_ids int32 [levels,capacity] (-1 behind the level's count),
+ * counts int32 [levels], positions fp32 [levels*capacity,3].  capacity == 0 is a no-op that reads no pointer.          */
+int nrhip_occgrid_update_candidates(const nrhip_occgrid_levels* grid, const float* occs, int32_t warmup, int32_t n,
+                                    const int64_t* cell_draws, const float* sel_draws, const float* jitter,
+                                    int32_t* cell_ids, int32_t* counts, float* positions, void* workspace,
+                                    int64_t workspace_bytes, void* stream);
+/* occ_values fp32 [levels*capacity]: what was evaluated at the positions.  occs[c] = max(occs[c] * ema_decay, max of the
+ * cell's candidates) on touched cells; then binaries = occs > min(mean of the visible occs, occ_thre).                */
+int nrhip_occgrid_update_apply(const nrhip_occgrid_levels* grid, float* occs, int64_t capacity, const int32_t* cell_ids,
+                               const int32_t* counts, const float* occ_values, float ema_decay, float occ_thre,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+/* K fp32 [n_k,3,3] with n_k == n_cams or 1, c2w fp32 [n_cams,3,4] (OpenCV convention).  Visible cells: occs = 0;
+ * invisible ones: occs = -1 and their binary cleared.                                                               */
+int nrhip_occgrid_mark_invisible(const nrhip_occgrid_levels* grid, const float* K, int32_t n_k, const float* c2w,
+                                 int32_t n_cams, int32_t width, int32_t height, float near_plane, float* occs,
+                                 void* stream);
 /* nerfacc render_visibility_from_alpha, packed: segments [R+1] delimit each ray's samples */
 int nrhip_packed_visibility_from_alpha(const float* alphas, const int64_t* segments, int64_t r, float early_stop_eps,
                                        float alpha_thre, uint8_t* mask, void* stream);

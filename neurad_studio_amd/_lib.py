@@ -89,6 +89,14 @@ class OccGrid(C.Structure):
     _fields_ = [("aabb", C.c_float * 6), ("resolution", C.c_int32), ("binaries", C.c_void_p)]
 
 
+OCCGRID_MAX_LEVELS = 8  # NRHIP_OCCGRID_MAX_LEVELS
+
+
+class OccGridLevels(C.Structure):  # nrhip_occgrid_levels
+    _fields_ = [("levels", C.c_int32), ("resolution", C.c_int32), ("aabbs", (C.c_float * 6) * OCCGRID_MAX_LEVELS),
+                ("binaries", C.c_void_p)]
+
+
 class CameraTable(C.Structure):
     _fields_ = [("camera_to_worlds", C.c_void_p), ("fx", C.c_void_p), ("fy", C.c_void_p), ("cx", C.c_void_p),
                 ("cy", C.c_void_p), ("times", C.c_void_p), ("rolling_shutter", C.c_int32),
@@ -211,6 +219,11 @@ PROTOTYPES = {
     "nrhip_actor_density_splice_bwd": [P, I32, P, P, P, P, P, P, I64, P, P, P, P],
     "nrhip_render_fwd_actors": [C.POINTER(Field), C.POINTER(Actors), C.POINTER(Rays), P, P, P, P, P, P, P, F32, P, P],
     "nrhip_occgrid_march": [C.POINTER(OccGrid), P, P, P, P, P, I64, F32, F32, F32, F32, I32, P, P, P, P, P, P],
+    "nrhip_occgrid_march_levels": [C.POINTER(OccGridLevels), P, P, P, P, P, I64, F32, F32, F32, F32, I32, P, P, P, P, P, P],
+    "nrhip_occgrid_update_workspace": [I32, I32, C.POINTER(I64)],
+    "nrhip_occgrid_update_candidates": [C.POINTER(OccGridLevels), P, I32, I32, P, P, P, P, P, P, P, I64, P],
+    "nrhip_occgrid_update_apply": [C.POINTER(OccGridLevels), P, I64, P, P, P, F32, F32, P, I64, P],
+    "nrhip_occgrid_mark_invisible": [C.POINTER(OccGridLevels), P, I32, P, I32, I32, I32, F32, P, P],
     "nrhip_packed_visibility_from_alpha": [P, P, I64, F32, F32, P, P],
     "nrhip_packed_segments": [P, I64, I64, P, P],
     "nrhip_packed_weight_from_density": [P, P, P, P, I64, P, P, P, P],

@@ -92,7 +92,9 @@ extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
 // 511: nrhip_nonfinite_check_many.
 // 512: packed compositing: nrhip_packed_segments, nrhip_packed_weight_from_density / _alpha (+ _bwd),
 // nrhip_packed_accumulate (+ _bwd), nrhip_packed_composite_fwd / _bwd.
-extern "C" int nrhip_version(void) { return 512; }
+// 513: occupancy-grid maintenance: nrhip_occgrid_march_levels, nrhip_occgrid_update_workspace / _candidates / _apply,
+//      nrhip_occgrid_mark_invisible
+extern "C" int nrhip_version(void) { return 513; }
 
 extern "C" int nrhip_tuning_reload(void) {
   nrhip::g_tuning = nrhip::read_tuning();

@@ -6,17 +6,18 @@
 //   * candidate intervals tile that range back to back: dt = max(t * cone_angle, step)  (uniform when cone_angle = 0);
 //   * a candidate is kept iff the cell containing its midpoint is occupied; kept intervals are emitted in order as
 //     packed (ray_index, t_start, t_end).
+// Multi-level grids (nrhip_occgrid_march_levels; the state and its update rule: occgrid_update.h): the ray is clipped to the
+// outermost box; a candidate's level is the first l whose (closed) box contains its midpoint -- the outermost level when
+// rounding puts it outside all of them -- and it is kept iff binaries[l] is set at the cell the same floor-and-clamp rule
+// gives in that level; step sizes do not depend on the level.  One level: exactly the single-grid march.
 // One wavefront marches one ray 64 candidates at a time: ballot(occupied) -> popcount prefix -> compacted store.
 #include "common.h"
+#include "occgrid_update.h"
 #include "packed_composite.h"
 
 namespace nrhip {
 
-struct OccDev {
-  float lo[3], hi[3];
-  int res;
-  const uint8_t* bin;
-};
+using OccDev = occ::LevelsDev;
 
 struct March {
   float t0, t_far, step, c, t1;
@@ -30,12 +31,14 @@ struct March {
 __device__ __forceinline__ bool setup_march(const OccDev& g, const float* o, const float* d, float near, float far,
                                             float step, float cone, March& m) {
   float tn = near, tf = far;
+  const float* lo = g.lo[g.L - 1];
+  const float* hi = g.hi[g.L - 1];
 #pragma unroll
-  for (int a = 0; a < 3; ++a) {  // slab test against the grid AABB
+  for (int a = 0; a < 3; ++a) {  // slab test against the (outermost) grid AABB
     const float inv = 1.f / d[a];
-    float ta = (g.lo[a] - o[a]) * inv, tb = (g.hi[a] - o[a]) * inv;
+    float ta = (lo[a] - o[a]) * inv, tb = (hi[a] - o[a]) * inv;
     if (d[a] == 0.f) {
-      if (o[a] < g.lo[a] || o[a] > g.hi[a]) return false;
+      if (o[a] < lo[a] || o[a] > hi[a]) return false;
       continue;
     }
     if (ta > tb) { const float s = ta; ta = tb; tb = s; }
@@ -51,14 +54,22 @@ __device__ __forceinline__ bool setup_march(const OccDev& g, const float* o, con
 }
 
 __device__ __forceinline__ bool occupied(const OccDev& g, const float* o, const float* d, float tm) {
+  const float p[3] = {o[0] + d[0] * tm, o[1] + d[1] * tm, o[2] + d[2] * tm};
+  int lvl = g.L - 1;
+  for (int l = g.L - 2; l >= 0; --l) {  // boxes are nested: the last hit going inwards is the first level containing p
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) in = in && p[a] >= g.lo[l][a] && p[a] <= g.hi[l][a];
+    lvl = in ? l : lvl;
+  }
   int idx = 0;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const float u = (o[a] + d[a] * tm - g.lo[a]) / (g.hi[a] - g.lo[a]);
+    const float u = (p[a] - g.lo[lvl][a]) / (g.hi[lvl][a] - g.lo[lvl][a]);
     const int i = min(max((int)floorf(u * (float)g.res), 0), g.res - 1);
     idx = idx * g.res + i;
   }
-  return g.bin[idx] != 0;
+  return g.bin[(int64_t)lvl * g.res * g.res * g.res + idx] != 0;
 }
 
 // WRITE=false: counts[ray] ; WRITE=true: packed outputs at offsets[ray]
@@ -107,25 +118,36 @@ __global__ __launch_bounds__(256) void occgrid_march_kernel(OccDev g, const floa
 static int to_dev(const nrhip_occgrid* g, OccDev& d) {
   NR_REQUIRE(g && g->binaries && g->resolution >= 1 && g->resolution <= 1024, NRHIP_ERR_INVALID_ARG,
              "occgrid: NULL grid or resolution outside [1,1024]");
+  d = OccDev{};
   for (int a = 0; a < 3; ++a) {
-    d.lo[a] = g->aabb[a], d.hi[a] = g->aabb[3 + a];
-    NR_REQUIRE(d.hi[a] > d.lo[a], NRHIP_ERR_INVALID_ARG, "occgrid: empty AABB");
+    d.lo[0][a] = g->aabb[a], d.hi[0][a] = g->aabb[3 + a];
+    NR_REQUIRE(d.hi[0][a] > d.lo[0][a], NRHIP_ERR_INVALID_ARG, "occgrid: empty AABB");
   }
-  d.res = g->resolution, d.bin = g->binaries;
+  d.L = 1, d.res = g->resolution, d.bin = const_cast<uint8_t*>(g->binaries);
   return NRHIP_OK;
 }
 
-}  // namespace nrhip
+static int to_dev(const nrhip_occgrid_levels* g, OccDev& d) {
+  NR_REQUIRE(g && g->binaries, NRHIP_ERR_INVALID_ARG, "occgrid: NULL grid or NULL binaries");
+  NR_REQUIRE(g->levels >= 1 && g->levels <= NRHIP_OCCGRID_MAX_LEVELS, NRHIP_ERR_INVALID_ARG,
+             "occgrid: %d levels outside [1,%d]", g->levels, NRHIP_OCCGRID_MAX_LEVELS);
+  NR_REQUIRE(g->resolution >= 1 && g->resolution <= 1024, NRHIP_ERR_INVALID_ARG, "occgrid: resolution outside [1,1024]");
+  d = OccDev{};
+  for (int l = 0; l < g->levels; ++l)
+    for (int a = 0; a < 3; ++a) {
+      d.lo[l][a] = g->aabbs[l][a], d.hi[l][a] = g->aabbs[l][3 + a];
+      NR_REQUIRE(d.hi[l][a] > d.lo[l][a], NRHIP_ERR_INVALID_ARG, "occgrid: empty AABB at level %d", l);
+      NR_REQUIRE(l == 0 || (d.lo[l][a] <= d.lo[l - 1][a] && d.hi[l][a] >= d.hi[l - 1][a]), NRHIP_ERR_INVALID_ARG,
+                 "occgrid: the box of level %d does not contain that of level %d", l, l - 1);
+    }
+  d.L = g->levels, d.res = g->resolution, d.bin = g->binaries;
+  return NRHIP_OK;
+}
 
-using namespace nrhip;
-
-extern "C" int nrhip_occgrid_march(const nrhip_occgrid* grid, const float* origins, const float* directions,
-                                   const float* t_min, const float* t_max, const float* t_rand, int64_t r,
-                                   float render_step_size, float near_plane, float far_plane, float cone_angle,
-                                   int32_t max_candidates, int32_t* counts, const int64_t* offsets,
-                                   int64_t* ray_indices, float* t_starts, float* t_ends, void* stream) {
-  OccDev d;
-  if (int e = to_dev(grid, d)) return e;
+static int march(const OccDev& d, const float* origins, const float* directions, const float* t_min, const float* t_max,
+                 const float* t_rand, int64_t r, float render_step_size, float near_plane, float far_plane,
+                 float cone_angle, int32_t max_candidates, int32_t* counts, const int64_t* offsets, int64_t* ray_indices,
+                 float* t_starts, float* t_ends, void* stream) {
   NR_REQUIRE(r >= 0 && render_step_size > 0.f && cone_angle >= 0.f && max_candidates >= 1, NRHIP_ERR_INVALID_ARG,
              "occgrid_march: bad argument");
   if (r == 0) return NRHIP_OK;
@@ -144,6 +166,124 @@ extern "C" int nrhip_occgrid_march(const nrhip_occgrid* grid, const float* origi
                                                        max_candidates, nullptr, offsets, ray_indices, t_starts, t_ends);
   }
   return check_launch("occgrid_march");
+}
+
+}  // namespace nrhip
+
+using namespace nrhip;
+
+extern "C" int nrhip_occgrid_march(const nrhip_occgrid* grid, const float* origins, const float* directions,
+                                   const float* t_min, const float* t_max, const float* t_rand, int64_t r,
+                                   float render_step_size, float near_plane, float far_plane, float cone_angle,
+                                   int32_t max_candidates, int32_t* counts, const int64_t* offsets,
+                                   int64_t* ray_indices, float* t_starts, float* t_ends, void* stream) {
+  OccDev d;
+  if (int e = to_dev(grid, d)) return e;
+  return march(d, origins, directions, t_min, t_max, t_rand, r, render_step_size, near_plane, far_plane, cone_angle,
+               max_candidates, counts, offsets, ray_indices, t_starts, t_ends, stream);
+}
+
+extern "C" int nrhip_occgrid_march_levels(const nrhip_occgrid_levels* grid, const float* origins, const float* directions,
+                                          const float* t_min, const float* t_max, const float* t_rand, int64_t r,
+                                          float render_step_size, float near_plane, float far_plane, float cone_angle,
+                                          int32_t max_candidates, int32_t* counts, const int64_t* offsets,
+                                          int64_t* ray_indices, float* t_starts, float* t_ends, void* stream) {
+  OccDev d;
+  if (int e = to_dev(grid, d)) return e;
+  return march(d, origins, directions, t_min, t_max, t_rand, r, render_step_size, near_plane, far_plane, cone_angle,
+               max_candidates, counts, offsets, ray_indices, t_starts, t_ends, stream);
+}
+
+// ---- grid maintenance (occgrid_update.h) ---------------------------------------------------------------------------------
+extern "C" int nrhip_occgrid_update_workspace(int32_t levels, int32_t resolution, int64_t* bytes) {
+  NR_REQUIRE(bytes, NRHIP_ERR_INVALID_ARG, "occgrid_update_workspace: bytes is NULL");
+  NR_REQUIRE(levels >= 1 && levels <= NRHIP_OCCGRID_MAX_LEVELS && resolution >= 1 && resolution <= 1024,
+             NRHIP_ERR_INVALID_ARG, "occgrid_update_workspace: levels outside [1,%d] or resolution outside [1,1024]",
+             NRHIP_OCCGRID_MAX_LEVELS);
+  *bytes = occ::scratch_layout(levels, resolution).bytes;
+  return NRHIP_OK;
+}
+
+#define OCC_WS(NAME)                                                                                              \
+  const occ::Scratch ws = occ::scratch_layout(d.L, d.res);                                                        \
+  NR_REQUIRE(workspace && workspace_bytes >= ws.bytes, NRHIP_ERR_INVALID_ARG,                                    \
+             NAME ": workspace is NULL or smaller than nrhip_occgrid_update_workspace asks for (%lld < %lld)",    \
+             (long long)workspace_bytes, (long long)ws.bytes);                                                    \
+  char* const wsp = (char*)workspace
+
+extern "C" int nrhip_occgrid_update_candidates(const nrhip_occgrid_levels* grid, const float* occs, int32_t warmup,
+                                               int32_t n, const int64_t* cell_draws, const float* sel_draws,
+                                               const float* jitter, int32_t* cell_ids, int32_t* counts, float* positions,
+                                               void* workspace, int64_t workspace_bytes, void* stream) {
+  OccDev d;
+  if (int e = to_dev(grid, d)) return e;
+  const int64_t n_cells = (int64_t)d.res * d.res * d.res;
+  NR_REQUIRE(n >= 0 && n <= n_cells, NRHIP_ERR_INVALID_ARG, "occgrid_update_candidates: n = %d outside [0, res^3]", n);
+  const int64_t cap = warmup ? n_cells : 2 * (int64_t)n;
+  if (cap == 0) return NRHIP_OK;  // nothing to do: no pointer is read, the workspace included
+  OCC_WS("occgrid_update_candidates");
+  NR_REQUIRE(occs && jitter && cell_ids && counts && positions, NRHIP_ERR_INVALID_ARG,
+             "occgrid_update_candidates: NULL occs, jitter or output");
+  NR_REQUIRE(warmup || (cell_draws && sel_draws), NRHIP_ERR_INVALID_ARG,
+             "occgrid_update_candidates: the draws are NULL after warm-up");
+  const hipStream_t st = (hipStream_t)stream;
+  occ::CompactArgs a{};
+  const int parts = warmup ? 1 : 2;
+  a.mode[0] = warmup ? occ::kVisibleCells : occ::kVisibleDraws, a.mode[1] = occ::kOccupiedCells;
+  a.n_src[0] = warmup ? ws.cells : n, a.n_src[1] = ws.cells;
+  a.dst[0] = cell_ids, a.dst_stride[0] = cap;
+  a.dst[1] = (int32_t*)(wsp + ws.off_list), a.dst_stride[1] = ws.cells;
+  a.block_counts = (int32_t*)(wsp + ws.off_bcnt), a.totals = (int32_t*)(wsp + ws.off_tot);
+  a.occs = occs, a.bin = d.bin, a.draws = cell_draws, a.cells = ws.cells, a.n = n, a.n_blk = (int)ws.n_blk, a.L = d.L;
+  const dim3 cg((unsigned)ws.n_blk, d.L, parts);
+  occ::compact_kernel<false><<<cg, 256, 0, st>>>(a);
+  occ::compact_scan_kernel<<<dim3(d.L, parts), 256, 0, st>>>(a.block_counts, a.totals, a.n_blk, d.L);
+  occ::compact_kernel<true><<<cg, 256, 0, st>>>(a);
+  occ::candidates_finalize_kernel<<<dim3((unsigned)grid_for(cap, 256), d.L), 256, 0, st>>>(
+      d, warmup, n, cap, a.totals, a.dst[1], ws.cells, sel_draws, jitter, cell_ids, counts, positions);
+  return check_launch("occgrid_update_candidates");
+}
+
+extern "C" int nrhip_occgrid_update_apply(const nrhip_occgrid_levels* grid, float* occs, int64_t capacity,
+                                          const int32_t* cell_ids, const int32_t* counts, const float* occ_values,
+                                          float ema_decay, float occ_thre, void* workspace, int64_t workspace_bytes,
+                                          void* stream) {
+  OccDev d;
+  if (int e = to_dev(grid, d)) return e;
+  OCC_WS("occgrid_update_apply");
+  NR_REQUIRE(capacity >= 0 && capacity <= ws.cells, NRHIP_ERR_INVALID_ARG,
+             "occgrid_update_apply: capacity %lld outside [0, res^3]", (long long)capacity);
+  NR_REQUIRE(occs, NRHIP_ERR_INVALID_ARG, "occgrid_update_apply: occs is NULL");
+  NR_REQUIRE(capacity == 0 || (cell_ids && counts && occ_values), NRHIP_ERR_INVALID_ARG,
+             "occgrid_update_apply: NULL candidates or values");
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t total = (int64_t)d.L * ws.cells;
+  uint32_t* keys = (uint32_t*)(wsp + ws.off_keys);
+  double* psum = (double*)(wsp + ws.off_psum);
+  long long* pcnt = (long long*)(wsp + ws.off_pcnt);
+  float* thre = (float*)(wsp + ws.off_thre);
+  if (capacity)
+    occ::ema_max_kernel<<<dim3((unsigned)grid_for(capacity, 256), d.L), 256, 0, st>>>(capacity, ws.cells, cell_ids, counts,
+                                                                                      occ_values, keys);
+  occ::ema_apply_sum_kernel<<<(unsigned)ws.n_part, 256, 0, st>>>(total, ema_decay, occs, keys, psum, pcnt);
+  occ::mean_final_kernel<<<1, 256, 0, st>>>(psum, pcnt, ws.n_part, occ_thre, thre);
+  occ::threshold_kernel<<<(unsigned)grid_for(total, 256), 256, 0, st>>>(total, occs, thre, d.bin);
+  return check_launch("occgrid_update_apply");
+}
+
+extern "C" int nrhip_occgrid_mark_invisible(const nrhip_occgrid_levels* grid, const float* K, int32_t n_k,
+                                            const float* c2w, int32_t n_cams, int32_t width, int32_t height,
+                                            float near_plane, float* occs, void* stream) {
+  OccDev d;
+  if (int e = to_dev(grid, d)) return e;
+  NR_REQUIRE(n_cams >= 0 && (n_k == 1 || n_k == n_cams), NRHIP_ERR_INVALID_ARG,
+             "occgrid_mark_invisible: %d intrinsics for %d cameras (one each, or one for all)", n_k, n_cams);
+  NR_REQUIRE(width >= 1 && height >= 1, NRHIP_ERR_INVALID_ARG, "occgrid_mark_invisible: empty image");
+  NR_REQUIRE(occs && (n_cams == 0 || (K && c2w)), NRHIP_ERR_INVALID_ARG, "occgrid_mark_invisible: NULL pointer");
+  const int64_t cells = (int64_t)d.res * d.res * d.res;
+  occ::mark_invisible_kernel<<<dim3((unsigned)grid_for(cells, 256), d.L), 256, 0, (hipStream_t)stream>>>(
+      d, K, n_k == 1 ? 0 : 9, c2w, n_cams, (float)width, (float)height, near_plane, occs);
+  return check_launch("occgrid_mark_invisible");
 }
 
 namespace nrhip {

@@ -393,6 +393,20 @@ class NeuRADProposalField(nn.Module):
         return ops.ProposalSpec(g.spec, g.hash_table.detach(), self.hashgrid.static_scale,
                                 self.density_decoder.weight.detach())
 
+    def density_fn(self, positions: Tensor, times: Optional[Tensor] = None) -> Tensor:
+        """fields/base_field.py:48-68: the density alone at ``positions`` [*bs,3] -> [*bs,1], through ``get_density`` on
+        zero-length samples (origin = position, direction one, start = end = 0, pixel area one); ``times`` is dropped, as
+        in the reference.  What a model hands to the occupancy grid:
+        ``est.update_every_n_steps(step, occ_eval_fn=field.density_fn)``."""
+        del times
+        bs = positions.shape[:-1]
+        p = positions.reshape(-1, 1, 3)  # one sample per "ray"
+        zero = torch.zeros_like(p[..., :1])
+        rs = RaySamples(frustums=Frustums(origins=p, directions=torch.ones_like(p), starts=zero, ends=zero,
+                                          pixel_area=torch.ones_like(zero)))
+        density, _ = self.get_density(rs)
+        return density.reshape(*bs, 1)
+
     def get_density(self, ray_samples: RaySamples, actor_cand=None) -> Tuple[Tensor, None]:
         """neurad_field.py:208-213, one kernel: gaussian -> contraction -> 6-level lookup -> rescale -> dot -> exp.
         actor_cand: candidate lists already computed for these rays (they depend on the ray's line only)."""

@@ -1079,20 +1079,61 @@ def actor_density(spec: ActorSpec, cand, origins, directions, pixel_area, starts
     return hit if return_actor else hit >= 0
 
 
+def occgrid_level_aabbs(roi_aabb, levels: int) -> Tensor:
+    """CPU fp32 [L,6]: level l is the level-0 box scaled by 2^l about its centre (centre and half extent in fp32)"""
+    a = torch.as_tensor(roi_aabb, dtype=torch.float32).reshape(6).cpu()
+    centre, half = (a[:3] + a[3:]) * 0.5, (a[3:] - a[:3]) * 0.5
+    return torch.stack([torch.cat([centre - half * float(2 ** l), centre + half * float(2 ** l)]) for l in range(levels)])
+
+
 @dataclass
 class OccGridSpec:
-    aabb: Tensor       # [6] min xyz, max xyz (any device; read on the host)
-    binaries: Tensor   # [res,res,res] bool / uint8 on the GPU
+    aabb: Tensor       # [6] min xyz, max xyz -- or [L,6], one box per level (any device; read on the host)
+    binaries: Tensor   # [res,res,res] -- or [L,res,res,res] -- bool / uint8 on the GPU
+
+    def _bytes(self, in_place: bool = False) -> Tensor:
+        b = self.binaries
+        if not b.is_cuda or b.dim() not in (3, 4) or b.shape[-3] != b.shape[-2] or b.shape[-2] != b.shape[-1]:
+            raise ValueError("binaries must be a cubic [res,res,res] or [L,res,res,res] GPU tensor")
+        if b.is_contiguous() and b.dtype in (torch.bool, torch.uint8):
+            return b.view(torch.uint8)  # a bool is one byte, 0 or 1: no copy
+        if in_place:
+            raise ValueError("binaries must be a contiguous bool / uint8 tensor to be updated in place")
+        return b.to(torch.uint8).contiguous()
 
     def c_grid(self):
-        b = self.binaries
-        if not b.is_cuda or b.dim() != 3 or b.shape[0] != b.shape[1] or b.shape[1] != b.shape[2]:
+        b8 = self._bytes()
+        if b8.dim() != 3:
             raise ValueError("binaries must be a cubic [res,res,res] GPU tensor")
-        b8 = b.to(torch.uint8).contiguous()
         g = _lib.OccGrid()
         for i, v in enumerate(self.aabb.reshape(-1).tolist()):
             g.aabb[i] = v
-        g.resolution, g.binaries = b.shape[0], b8.data_ptr()
+        g.resolution, g.binaries = b8.shape[0], b8.data_ptr()
+        return g, b8
+
+    @property
+    def levels(self) -> int:
+        return 1 if self.binaries.dim() == 3 else self.binaries.shape[0]
+
+    @property
+    def resolution(self) -> int:
+        return self.binaries.shape[-1]
+
+    def c_levels(self, in_place: bool = False):
+        """nrhip_occgrid_levels of a [L,res,res,res] (or [res,res,res]) grid; aabb [6] is expanded to the L nested boxes"""
+        b8 = self._bytes(in_place)
+        L = self.levels
+        if not 1 <= L <= _lib.OCCGRID_MAX_LEVELS:
+            raise ValueError(f"occupancy grid with {L} levels (1..{_lib.OCCGRID_MAX_LEVELS})")
+        boxes = torch.as_tensor(self.aabb, dtype=torch.float32)
+        boxes = occgrid_level_aabbs(boxes, L) if boxes.numel() == 6 and L > 1 else boxes.reshape(-1, 6)
+        if boxes.shape[0] != L:
+            raise ValueError(f"{boxes.shape[0]} boxes for {L} levels")
+        g = _lib.OccGridLevels()
+        g.levels, g.resolution, g.binaries = L, b8.shape[-1], b8.data_ptr()
+        for l, box in enumerate(boxes.tolist()):
+            for i, v in enumerate(box):
+                g.aabbs[l][i] = v
         return g, b8
 
 
@@ -1130,14 +1171,19 @@ def occgrid_march(grid: OccGridSpec, origins, directions, render_step_size, near
     -> (ray_indices int64 [M], t_starts [M], t_ends [M], segments int64 [R+1])"""
     o, d = _chk(origins, "origins"), _chk(directions, "directions")
     R, dev = o.shape[0], o.device
-    g, keep = grid.c_grid()
+    if grid.binaries.dim() == 4:  # [L,res,res,res]: the levels-aware entry point (L = 1: the same samples bit for bit)
+        g, keep = grid.c_levels()
+        entry = "nrhip_occgrid_march_levels"
+    else:
+        g, keep = grid.c_grid()
+        entry = "nrhip_occgrid_march"
     tmn = None if t_min is None else _chk(t_min.reshape(-1), "t_min")
     tmx = None if t_max is None else _chk(t_max.reshape(-1), "t_max")
     tr = None if t_rand is None else _chk(t_rand.reshape(-1), "t_rand")
     counts = torch.zeros((R,), dtype=torch.int32, device=dev)
     args = (C.byref(g), _ptr(o), _ptr(d), _ptr(tmn), _ptr(tmx), _ptr(tr), R, float(render_step_size), float(near_plane),
             float(far_plane), float(cone_angle), int(max_candidates))
-    call("nrhip_occgrid_march", *args, _ptr(counts), _ptr(None), _ptr(None), _ptr(None), _ptr(None), _stream())
+    call(entry, *args, _ptr(counts), _ptr(None), _ptr(None), _ptr(None), _ptr(None), _stream())
     seg = torch.zeros((R + 1,), dtype=torch.int64, device=dev)
     torch.cumsum(counts, 0, out=seg[1:])
     M = int(seg[-1].item()) if R else 0
@@ -1145,8 +1191,119 @@ def occgrid_march(grid: OccGridSpec, origins, directions, render_step_size, near
     ts = torch.empty((M,), dtype=torch.float32, device=dev)
     te = torch.empty((M,), dtype=torch.float32, device=dev)
     if M:
-        call("nrhip_occgrid_march", *args, _ptr(None), _ptr(seg), _ptr(ri), _ptr(ts), _ptr(te), _stream())
+        call(entry, *args, _ptr(None), _ptr(seg), _ptr(ri), _ptr(ts), _ptr(te), _stream())
     return ri, ts, te, seg
+
+
+# ---- occupancy-grid maintenance (csrc/occgrid_update.h states the rule; parity with nerfacc itself is unpinned) ----------
+def occgrid_update_scratch(levels: int, resolution: int, device) -> dict:
+    """The device scratch of a grid, allocated (zero-filled) once and kept by its owner -- shims.nerfacc.OccGridEstimator
+    caches it: the kernels' workspace plus the fixed-capacity candidate buffers of both regimes, filled on first use."""
+    need = C.c_int64(0)
+    call("nrhip_occgrid_update_workspace", int(levels), int(resolution), C.byref(need))
+    return {"levels": int(levels), "resolution": int(resolution),
+            "workspace": torch.zeros((need.value,), dtype=torch.uint8, device=device)}
+
+
+def _occ_scratch(grid: OccGridSpec, scratch: Optional[dict], device) -> dict:
+    if scratch is None:
+        return occgrid_update_scratch(grid.levels, grid.resolution, device)
+    if scratch["levels"] != grid.levels or scratch["resolution"] != grid.resolution or scratch["workspace"].device != device:
+        raise ValueError("occgrid scratch belongs to a grid of another shape or device")
+    return scratch
+
+
+def occgrid_update_capacity(resolution: int, warmup: bool, n: Optional[int] = None) -> Tuple[int, int]:
+    """(n, capacity per level): n = res^3 // 4 draws; res^3 slots during warm-up, 2 n after it"""
+    n = resolution ** 3 // 4 if n is None else int(n)
+    return n, (resolution ** 3 if warmup else 2 * n)
+
+
+def occgrid_update_candidates(grid: OccGridSpec, occs: Tensor, warmup: bool, n: Optional[int] = None,
+                              cell_draws: Optional[Tensor] = None, sel_draws: Optional[Tensor] = None,
+                              jitter: Optional[Tensor] = None, scratch: Optional[dict] = None):
+    """-> cell_ids int32 [L,cap] (-1 behind the level's count), counts int32 [L], positions fp32 [L*cap,3].
+    The draws (cell_draws int64 [L,n], sel_draws fp32 [L,n], jitter fp32 [L,cap,3]) are made on the device when not given.
+    The outputs live in ``scratch`` when one is passed: the next call of the same regime overwrites them."""
+    occs = _chk(occs, "occs")
+    L, res, dev = grid.levels, grid.resolution, occs.device
+    if occs.numel() != L * res ** 3:
+        raise ValueError(f"occs has {occs.numel()} elements for {L} x {res}^3 cells")
+    n, cap = occgrid_update_capacity(res, warmup, n)
+    sc = _occ_scratch(grid, scratch, dev)
+    if not warmup:
+        if cell_draws is None:
+            cell_draws = torch.randint(0, res ** 3, (L, n), dtype=torch.int64, device=dev)
+        if sel_draws is None:
+            sel_draws = torch.rand((L, n), dtype=torch.float32, device=dev)
+        cell_draws, sel_draws = _chk(cell_draws, "cell_draws", torch.int64), _chk(sel_draws, "sel_draws")
+        if tuple(cell_draws.shape) != (L, n) or tuple(sel_draws.shape) != (L, n):
+            raise ValueError(f"cell_draws / sel_draws must be [{L},{n}]")
+    if jitter is None:
+        jitter = torch.rand((L, cap, 3), dtype=torch.float32, device=dev)
+    jitter = _chk(jitter, "jitter")
+    if tuple(jitter.shape) != (L, cap, 3):
+        raise ValueError(f"jitter must be [{L},{cap},3], got {tuple(jitter.shape)}")
+    key = ("cand", bool(warmup), n)
+    if key not in sc:
+        sc[key] = (torch.empty((L, cap), dtype=torch.int32, device=dev), torch.zeros((L,), dtype=torch.int32, device=dev),
+                   torch.empty((L * cap, 3), dtype=torch.float32, device=dev))
+    ids, counts, pos = sc[key]
+    g, keep = grid.c_levels()
+    ws = sc["workspace"]
+    call("nrhip_occgrid_update_candidates", C.byref(g), _ptr(occs), int(bool(warmup)), n, _ptr(cell_draws if not warmup else None),
+         _ptr(sel_draws if not warmup else None), _ptr(jitter), _ptr(ids), _ptr(counts), _ptr(pos), _ptr(ws), ws.numel(),
+         _stream())
+    return ids, counts, pos
+
+
+def occgrid_update_apply(grid: OccGridSpec, occs: Tensor, cell_ids: Tensor, counts: Tensor, occ_values: Tensor,
+                         ema_decay: float = 0.95, occ_thre: float = 1e-2, scratch: Optional[dict] = None) -> None:
+    """In place: the EMA of ``occs`` at the candidates' cells (max over a cell's candidates, decay once), then
+    ``grid.binaries = occs > min(mean of the visible occs, occ_thre)``."""
+    occs = _chk(occs, "occs")
+    if not occs.is_contiguous():
+        raise ValueError("occs must be contiguous (updated in place)")
+    ids, counts = _chk(cell_ids, "cell_ids", torch.int32), _chk(counts, "counts", torch.int32)
+    L, res = grid.levels, grid.resolution
+    if ids.dim() != 2 or ids.shape[0] != L or counts.numel() != L or occs.numel() != L * res ** 3:
+        raise ValueError("occgrid_update_apply: cell_ids [L,cap], counts [L], occs [L*res^3]")
+    vals = _chk(occ_values.reshape(-1), "occ_values")
+    if vals.numel() != ids.numel():
+        raise ValueError(f"occ_values has {vals.numel()} elements for {ids.numel()} candidate slots")
+    sc = _occ_scratch(grid, scratch, occs.device)
+    g, keep = grid.c_levels(in_place=True)
+    ws = sc["workspace"]
+    call("nrhip_occgrid_update_apply", C.byref(g), _ptr(occs), ids.shape[1], _ptr(ids), _ptr(counts), _ptr(vals),
+         float(ema_decay), float(occ_thre), _ptr(ws), ws.numel(), _stream())
+
+
+def occgrid_update(grid: OccGridSpec, occs: Tensor, occ_eval_fn, step: int, occ_thre: float = 1e-2, ema_decay: float = 0.95,
+                   warmup_steps: int = 256, n: Optional[int] = None, cell_draws=None, sel_draws=None, jitter=None,
+                   scratch: Optional[dict] = None):
+    """One update of (occs, grid.binaries), in place: candidates -> ``occ_eval_fn(positions [L*cap,3])`` once -> EMA ->
+    threshold.  No host synchronisation and no allocation sized by data.  -> (cell_ids, counts, positions)"""
+    ids, counts, pos = occgrid_update_candidates(grid, occs, step < warmup_steps, n, cell_draws, sel_draws, jitter, scratch)
+    vals = occ_eval_fn(pos).reshape(-1).float() if pos.shape[0] else pos.new_empty((0,))
+    occgrid_update_apply(grid, occs, ids, counts, vals, ema_decay, occ_thre, scratch)
+    return ids, counts, pos
+
+
+def occgrid_mark_invisible(grid: OccGridSpec, occs: Tensor, K: Tensor, c2w: Tensor, width: int, height: int,
+                           near_plane: float = 0.0) -> None:
+    """In place: occs = 0 on the cells some camera sees (and none sees closer than near_plane), -1 -- and the binary
+    cleared -- on the others.  K [N,3,3] or [1,3,3], c2w [N,3,4] or [N,4,4], OpenCV convention."""
+    occs = _chk(occs, "occs")
+    if not occs.is_contiguous() or occs.numel() != grid.levels * grid.resolution ** 3:
+        raise ValueError("occs must be a contiguous fp32 [L*res^3] tensor")
+    if K.dim() != 3 or tuple(K.shape[1:]) != (3, 3) or c2w.dim() != 3 or tuple(c2w.shape[1:]) not in ((3, 4), (4, 4)):
+        raise ValueError("K must be [N,3,3] or [1,3,3] and c2w [N,3,4] or [N,4,4]")
+    if K.shape[0] not in (1, c2w.shape[0]):
+        raise ValueError(f"{K.shape[0]} intrinsics for {c2w.shape[0]} cameras")
+    Kc, Mc = _chk(K, "K"), _chk(c2w[:, :3, :4], "c2w")
+    g, keep = grid.c_levels(in_place=True)
+    call("nrhip_occgrid_mark_invisible", C.byref(g), _ptr(Kc), Kc.shape[0], _ptr(Mc), Mc.shape[0], int(width), int(height),
+         float(near_plane), _ptr(occs), _stream())
 
 
 def packed_visibility_from_alpha(alphas: Tensor, segments: Tensor, early_stop_eps: float, alpha_thre: float) -> Tensor:

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
+import torch
 from torch import Tensor
 
 from .. import autograd as ag
@@ -13,8 +14,6 @@ from .. import autograd as ag
 
 def _segments(packed_info, ray_indices, n_rays, prefix_trans=None) -> Tensor:
     """segments int64 [R+1] of a packed call: from packed_info [R,2] (start, count) or sorted ray_indices + n_rays"""
-    import torch
-
     if prefix_trans is not None:
         raise NotImplementedError("prefix_trans")
     if packed_info is not None:
@@ -30,8 +29,6 @@ def _segments(packed_info, ray_indices, n_rays, prefix_trans=None) -> Tensor:
 
 def pack_info(ray_indices: Tensor, n_rays: Optional[int] = None) -> Tensor:
     """nerfacc.pack_info: sorted ray_indices [M] -> packed_info [n_rays, 2] (start, count) per ray"""
-    import torch
-
     if n_rays is None:
         raise ValueError("pack_info: n_rays is needed (no host synchronisation to find it)")
     seg = ag.ops.packed_segments(ray_indices, int(n_rays))
@@ -62,32 +59,107 @@ def accumulate_along_rays(weights: Tensor, values: Optional[Tensor] = None, ray_
     return ag.AccumulateFn.apply(weights.contiguous(), values.contiguous())
 
 
-class OccGridEstimator:
-    """nerfacc.OccGridEstimator-shaped holder of a single-level binary occupancy grid with ``sampling`` as
-    VolumetricSampler calls it (model_components/ray_samplers.py:527-540).  Marching rule: csrc/occgrid.hip."""
+class OccGridEstimator(torch.nn.Module):
+    """nerfacc.OccGridEstimator-shaped module: a multi-level occupancy grid with ``sampling`` as VolumetricSampler calls it
+    (model_components/ray_samplers.py:527-540), ``update_every_n_steps`` and ``mark_invisible_cells``.  Marching rule:
+    csrc/occgrid.hip; update rule: csrc/occgrid_update.h (modelled on nerfacc 0.5, parity with nerfacc itself unpinned --
+    its own ``state_dict`` is not loadable here).
+
+    Buffers: ``aabbs`` [L,6] (level l: the level-0 box scaled by 2^l about its centre), ``occs`` fp32 [L*res^3],
+    ``binaries`` bool [L,res,res,res], ``resolution`` int32 [3] and ``fresh``.  A fresh estimator has every binary set and
+    every occ one -- "nothing known, march everything"; the first update or ``mark_invisible_cells`` ends that state by
+    zeroing ``occs`` first, so the EMA starts from zero.  ``binaries`` may be edited in place."""
 
     def __init__(self, roi_aabb, resolution: int = 128, levels: int = 1, device="cuda"):
-        import torch
+        super().__init__()
+        from .. import ops
 
-        if levels != 1:
-            raise NotImplementedError("multi-level occupancy grids")
-        self.aabbs = torch.as_tensor(roi_aabb, dtype=torch.float32).reshape(1, 6)
-        self.binaries = torch.ones((1, resolution, resolution, resolution), dtype=torch.bool, device=device)
-        self.occs = self.binaries.float().reshape(-1)
+        if levels < 1:
+            raise ValueError("levels must be >= 1")
+        boxes = ops.occgrid_level_aabbs(roi_aabb, levels)
+        self.levels, self.cells_per_lvl = int(levels), int(resolution) ** 3
+        self.register_buffer("aabbs", boxes.to(device))
+        self.register_buffer("binaries", torch.ones((levels, resolution, resolution, resolution), dtype=torch.bool,
+                                                    device=device))
+        self.register_buffer("occs", torch.ones((levels * self.cells_per_lvl,), dtype=torch.float32, device=device))
+        self.register_buffer("resolution", torch.tensor([resolution] * 3, dtype=torch.int32))
+        self.register_buffer("fresh", torch.ones((), dtype=torch.bool))
+        # host mirrors: the march and the update read the boxes and the flag without a device read
+        self._aabbs_host, self._fresh_host, self._scratch = boxes.clone(), True, None
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self._aabbs_host = self._fresh_host = None  # re-read once, at the next use
+
+    def _spec(self):
+        from .. import ops
+
+        if self._aabbs_host is None:
+            self._aabbs_host = self.aabbs.detach().cpu().clone()
+        return ops.OccGridSpec(self._aabbs_host, self.binaries)
+
+    def _end_fresh(self) -> None:
+        if self._fresh_host is None:
+            self._fresh_host = bool(self.fresh.item())
+        if self._fresh_host:
+            self.occs.zero_()
+            self.fresh.fill_(False)
+            self._fresh_host = False
+
+    def _get_scratch(self) -> dict:
+        from .. import ops
+
+        sc = self._scratch
+        if sc is None or sc["workspace"].device != self.occs.device:
+            sc = self._scratch = ops.occgrid_update_scratch(self.levels, self.binaries.shape[-1], self.occs.device)
+        return sc
+
+    @torch.no_grad()
+    def update_every_n_steps(self, step: int, occ_eval_fn, occ_thre: float = 1e-2, ema_decay: float = 0.95,
+                             warmup_steps: int = 256, n: int = 16) -> None:
+        """nerfacc's training-loop call: every ``n`` steps, evaluate ``occ_eval_fn`` ([N,3] positions -> [N,1] or [N]
+        density x step size) at the candidate cells and fold it into the grid.  Training mode only."""
+        if not self.training:
+            raise RuntimeError("You should only call this function only during training. Please call _update() directly "
+                               "if you want to update the field during inference.")
+        if step % n == 0:
+            self._update(step=step, occ_eval_fn=occ_eval_fn, occ_thre=occ_thre, ema_decay=ema_decay,
+                         warmup_steps=warmup_steps)
+
+    @torch.no_grad()
+    def _update(self, step: int, occ_eval_fn, occ_thre: float = 1e-2, ema_decay: float = 0.95, warmup_steps: int = 256,
+                cell_draws=None, sel_draws=None, jitter=None):
+        """One update (csrc/occgrid_update.h).  The three draw tensors are injected by tests; by default they are made on
+        the device.  From the second call on: no host synchronisation, no allocation sized by data.
+        -> (cell_ids, counts, positions) of the candidates, views of the cached scratch."""
+        from .. import ops
+
+        self._end_fresh()
+        return ops.occgrid_update(self._spec(), self.occs, occ_eval_fn, step, occ_thre, ema_decay, warmup_steps,
+                                  cell_draws=cell_draws, sel_draws=sel_draws, jitter=jitter, scratch=self._get_scratch())
+
+    @torch.no_grad()
+    def mark_invisible_cells(self, K, c2w, width: int, height: int, near_plane: float = 0.0) -> None:
+        """Cells no camera sees -- or one sees closer than ``near_plane`` -- get occs = -1 and are never evaluated or
+        occupied again; the others get occs = 0.  K [N,3,3] or [1,3,3], c2w [N,3,4] or [N,4,4] (OpenCV)."""
+        from .. import ops
+
+        self._end_fresh()
+        dev = self.occs.device
+        ops.occgrid_mark_invisible(self._spec(), self.occs, K.to(dev, torch.float32), c2w.to(dev, torch.float32), width,
+                                   height, near_plane)
 
     def sampling(self, rays_o, rays_d, sigma_fn=None, alpha_fn=None, near_plane: float = 0.0, far_plane: float = 1e10,
                  t_min=None, t_max=None, render_step_size: float = 1e-3, early_stop_eps: float = 1e-4,
                  alpha_thre: float = 0.0, stratified: bool = False, cone_angle: float = 0.0):
-        import torch
-
         from .. import ops
 
         t_rand = torch.rand((rays_o.shape[0],), device=rays_o.device) if stratified else None
-        grid = ops.OccGridSpec(self.aabbs[0], self.binaries[0])
-        ri, ts, te, seg = ops.occgrid_march(grid, rays_o, rays_d, render_step_size, near_plane, far_plane, t_min, t_max,
-                                            cone_angle, t_rand)
+        ri, ts, te, seg = ops.occgrid_march(self._spec(), rays_o, rays_d, render_step_size, near_plane, far_plane, t_min,
+                                            t_max, cone_angle, t_rand)
         if (alpha_thre > 0.0 or early_stop_eps > 0.0) and (sigma_fn is not None or alpha_fn is not None) and ri.numel():
-            alpha_thre = min(alpha_thre, float(self.occs.mean().item()))
+            if alpha_thre > 0.0:  # (the one host read of this route: out of scope to move it to the device)
+                alpha_thre = min(alpha_thre, float(self.occs.mean().item()))
             if sigma_fn is not None:
                 alphas = 1.0 - torch.exp(-sigma_fn(ts, te, ri) * (te - ts))
             else:
