@@ -332,20 +332,10 @@ extern "C" int nrhip_actor_encode(const nrhip_actors* a, const nrhip_rays* rays,
   const RaysDev rd = to_dev(*rays);
   const int blocks = grid_for(n, 256);
   const hipStream_t st = (hipStream_t)stream;
-#define CALL(F)                                                                                                              \
-  do {                                                                                                                       \
-    if (a->grid.param_dtype == 1)                                                                                            \
-      actor_encode_kernel<F, true><<<blocks, 256, 0, st>>>(d, rd, cand_count, cand_actor, cand_w2b, out_dim, features, directions, hit);  \
-    else                                                                                                                     \
-      actor_encode_kernel<F, false><<<blocks, 256, 0, st>>>(d, rd, cand_count, cand_actor, cand_w2b, out_dim, features, directions, hit); \
-  } while (0)
-  switch (a->grid.n_features) {
-    case 1: CALL(1); break;
-    case 2: CALL(2); break;
-    case 4: CALL(4); break;
-    default: CALL(8); break;
-  }
-#undef CALL
+  dispatch_f(a->grid.n_features, a->grid.param_dtype == 1, [&](auto F, auto H) {
+    actor_encode_kernel<F, H><<<blocks, 256, 0, st>>>(d, rd, cand_count, cand_actor, cand_w2b, out_dim, features,
+                                                      directions, hit);
+  });
   return check_launch("actor_encode");
 }
 
@@ -565,19 +555,7 @@ __global__ __launch_bounds__(256) void actor_pair_positions_bwd_kernel(
     const unsigned long long hm = __ballot(head);
     if (hm != __ballot(live)) {
       const uint32_t run = (uint32_t)__popcll(hm & ((2ull << lane) - 1ull));
-#define NR_SEG_STEP(OFF)                                                   \
-  {                                                                        \
-    const bool same = dpp_row_shl<OFF>(run, 0xffffffffu) == run;           \
-    _Pragma("unroll") for (int j = 0; j < 9; ++j) {                        \
-      const float t = dpp_row_shl<OFF>(v[j], 0.f);                         \
-      if (same) v[j] += t;                                                 \
-    }                                                                      \
-  }
-      NR_SEG_STEP(1)
-      NR_SEG_STEP(2)
-      NR_SEG_STEP(4)
-      NR_SEG_STEP(8)
-#undef NR_SEG_STEP
+      NR_SUM_RUNS_ONTO_HEADS(v, 9, run)
     }
     if (head) {
       float* gr = g_rot6 + ((size_t)tix[e] * a.A + act) * 6;

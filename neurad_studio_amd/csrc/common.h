@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/neurad_hip.h"
 
 namespace nrhip {
@@ -316,29 +318,12 @@ __device__ __forceinline__ void inf_norm_bwd(const float* m, const float* am, fl
   for (int c = 0; c < 3; ++c) gm[c] = gm[c] * k + (am[c] == mag ? (m[c] < 0.f ? -share : share) : 0.f);
 }
 
+// H2 then H3.  Position arithmetic mirrors torch op for op (separately rounded mul/add/div, no fma): one ulp of the
+// contracted coordinate is 8192 * 6e-8 = 5e-4 of a cell at the finest level, so rounding-order matters.
 __device__ __forceinline__ SamplePos sample_position(float ox, float oy, float oz, float dx, float dy, float dz,
                                                      float area, float t0, float t1, float scale) {
-  // Position arithmetic mirrors torch op for op (separately rounded mul/add/div, no fma): one ulp of the
-  // contracted coordinate is 8192 * 6e-8 = 5e-4 of a cell at the finest level, so rounding-order matters.
-#pragma clang fp contract(off)
-  const float dist = (t1 - t0) / 2.f;
-  const float t = t0 + 1.f * dist;
-  float mx = ox + dx * t, my = oy + dy * t, mz = oz + dz * t;
-  float std = fast_cbrt((area * (t * t)) * dist);
-  // ScaledSceneContraction: divide by scale, contract (inf-norm), map [-2,2] -> [0,1]
-  mx /= scale, my /= scale, mz /= scale, std /= scale;
-  const float mag = fmaxf(fabsf(mx), fmaxf(fabsf(my), fabsf(mz)));
-  if (!(mag < 1.f)) {
-    const float cm = fmaxf(mag, 1.f);
-    const float k = 2.f - (1.f / cm);
-    mx = k * (mx / cm), my = k * (my / cm), mz = k * (mz / cm);
-    const float sc = fast_cbrt(2.f * cm - 1.f) / cm;
-    std = std * (sc * sc);
-  }
-  SamplePos p;
-  p.x = (mx + 2.f) / 4.f, p.y = (my + 2.f) / 4.f, p.z = (mz + 2.f) / 4.f;
-  p.std = std / 4.f;
-  return p;
+  const SamplePos g = sample_gaussian(ox, oy, oz, dx, dy, dz, area, t0, t1);
+  return contract_gaussian(g.x, g.y, g.z, g.std, scale);
 }
 
 // H4: 1 / max(1, 2*scalings_l*std)   (neurad_encoding.py:302)
@@ -370,29 +355,78 @@ __device__ __forceinline__ void sh4(float x, float y, float z, float (&c)[16]) {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 
-// DPP helpers over rows of 16 lanes -------------------------------------------------------------
-// row_shr:n  = 0x110+n ; bound_ctrl=false keeps `old` for lanes shifted in from outside the row.
-template <int N>
-__device__ __forceinline__ float dpp_row_shr(float v, float fill) {
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x110 + N, 0xf,
-                                         0xf, false));
+// DPP: v_mov_b32_dpp with control CTRL, all rows and banks, bound_ctrl = false: lanes without a source keep `old` -----
+template <int CTRL>
+__device__ __forceinline__ int dpp(int old, int v) {
+  return __builtin_amdgcn_update_dpp(old, v, CTRL, 0xf, 0xf, false);
+}
+template <int CTRL>
+__device__ __forceinline__ float dpp(float old, float v) {
+  return __builtin_bit_cast(float, dpp<CTRL>(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v)));
+}
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp(uint32_t old, uint32_t v) {
+  return (uint32_t)dpp<CTRL>((int)old, (int)v);
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp(double old, double v) {
+  const long long o = __builtin_bit_cast(long long, old), x = __builtin_bit_cast(long long, v);
+  const uint32_t lo = (uint32_t)dpp<CTRL>((int)(uint32_t)o, (int)(uint32_t)x);
+  const uint32_t hi = (uint32_t)dpp<CTRL>((int)(uint32_t)(o >> 32), (int)(uint32_t)(x >> 32));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+// Rows of 16 lanes.  row_shr:n = 0x110+n: lane i reads lane i-n of its row; row_shl:n = 0x100+n: lane i reads lane i+n.
+// Lanes whose source is outside the row get `fill`.
+template <int N, class T>
+__device__ __forceinline__ T dpp_row_shr(T v, T fill) {
+  return dpp<0x110 + N>(fill, v);
+}
+template <int N, class T>
+__device__ __forceinline__ T dpp_row_shl(T v, T fill) {
+  return dpp<0x100 + N>(fill, v);
 }
 
-// row_shl:n = 0x100+n : lane i reads lane i+n of its row; lanes whose source is outside the row get `fill`.
-template <int N>
-__device__ __forceinline__ float dpp_row_shl(float v, float fill) {
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), 0x100 + N, 0xf,
-                                         0xf, false));
+// Run combining before atomics: equal keys in adjacent lanes form a run, `run` numbers the runs of the wave (the count
+// of run heads up to and including the lane).  Segmented suffix sum of v[0..N) onto each run's head lane, inside the
+// 16-lane rows.  A macro, not a function template: the function form changes the code of the kernels around it (more
+// VGPRs and instructions in the binned emit kernels).  v, N and run are pasted as they are: pass a plain array variable,
+// a constant and a plain uint32_t variable, no expressions.  (NR_SEG_STEP_ is the macro's own helper and has to stay
+// defined for it.)
+#define NR_SEG_STEP_(v, N, run, OFF)                                       \
+  {                                                                        \
+    const bool same = dpp_row_shl<OFF>(run, 0xffffffffu) == run;           \
+    _Pragma("unroll") for (int j = 0; j < N; ++j) {                        \
+      const float t = dpp_row_shl<OFF>(v[j], 0.f);                         \
+      if (same) v[j] += t;                                                 \
+    }                                                                      \
+  }
+#define NR_SUM_RUNS_ONTO_HEADS(v, N, run) \
+  NR_SEG_STEP_(v, N, run, 1) NR_SEG_STEP_(v, N, run, 2) NR_SEG_STEP_(v, N, run, 4) NR_SEG_STEP_(v, N, run, 8)
+
+// Orders one wave's LDS traffic (the one-wave-per-ray kernels exchange through LDS without a workgroup barrier).
+__device__ __forceinline__ void wave_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
 }
-template <int N>
-__device__ __forceinline__ uint32_t dpp_row_shl(uint32_t v, uint32_t fill) {
-  return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x100 + N, 0xf, 0xf, false);
+
+// Host-side dispatch on features-per-level: fn(std::integral_constant<int, F>) -- the argument converts to a constant
+// expression, so `kernel<F>` works inside a generic lambda.  f must be validated (validate_grid): anything but 1, 2, 4
+// goes to 8.  The second form also carries a flag (fp16 storage, x-pair records) as std::bool_constant.
+template <class Fn>
+inline void dispatch_f(int f, Fn&& fn) {
+  switch (f) {
+    case 1: fn(std::integral_constant<int, 1>{}); break;
+    case 2: fn(std::integral_constant<int, 2>{}); break;
+    case 4: fn(std::integral_constant<int, 4>{}); break;
+    default: fn(std::integral_constant<int, 8>{}); break;
+  }
 }
-template <int N>
-__device__ __forceinline__ uint32_t dpp_row_shr(uint32_t v, uint32_t fill) {
-  return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x110 + N, 0xf, 0xf, false);
+template <class Fn>
+inline void dispatch_f(int f, bool flag, Fn&& fn) {
+  dispatch_f(f, [&](auto F) {
+    if (flag) fn(F, std::true_type{});
+    else fn(F, std::false_type{});
+  });
 }
 
 inline int grid_for(int64_t threads, int block) { return (int)((threads + block - 1) / block); }
@@ -420,6 +454,5 @@ __device__ __forceinline__ void mfma_layer(const float* __restrict__ wf, int lan
         acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mb][s3], b[4 * s4 + s3], acc[mb], 0, 0, 0);
   }
 }
-
 
 }  // namespace nrhip

@@ -578,19 +578,7 @@ __global__ __launch_bounds__(1024) void bin_emit_kernel(GridDev g, Src src, int 
           // some run is longer than 1: segmented suffix sum onto the run heads, inside each 16-lane row, on DPP
           // row shifts (VALU rate; a 64-lane __shfl version goes through the LDS crossbar 18x per corner)
           const uint32_t run = (uint32_t)__popcll(hm & ((2ull << lane) - 1ull));
-#define NR_SEG_STEP(OFF)                                                   \
-  {                                                                        \
-    const bool same = dpp_row_shl<OFF>(run, 0xffffffffu) == run;           \
-    _Pragma("unroll") for (int j = 0; j < NV; ++j) {                       \
-      const float t = dpp_row_shl<OFF>(v[j], 0.f);                         \
-      if (same) v[j] += t;                                                 \
-    }                                                                      \
-  }
-          NR_SEG_STEP(1)
-          NR_SEG_STEP(2)
-          NR_SEG_STEP(4)
-          NR_SEG_STEP(8)
-#undef NR_SEG_STEP
+          NR_SUM_RUNS_ONTO_HEADS(v, NV, run)
         }
         if (head && live) {
           const uint32_t b = kf >> log2TS;
@@ -755,15 +743,6 @@ __global__ __launch_bounds__(1024) void bin_reduce_kernel(const uint32_t* __rest
   }
 }
 
-#define NR_DISPATCH_F(F_, CALL)      \
-  do {                               \
-    const int f__ = (F_);            \
-    if (f__ == 1) { CALL(1); }       \
-    else if (f__ == 2) { CALL(2); }  \
-    else if (f__ == 4) { CALL(4); }  \
-    else { CALL(8); }                \
-  } while (0)
-
 }  // namespace
 }  // namespace nrhip
 
@@ -861,31 +840,22 @@ int run_binned(const char* what, const GridDev& gd, const Src& src, int64_t n, f
                 sum ? (double)mx * p.nb / sum : 0.0);
       }
     }
-#define CALL2(F, P)                                                                                                 \
-  do {                                                                                                              \
-    static thread_local bool configured = false;                                                                    \
-    if (!configured) {                                                                                              \
-      (void)hipFuncSetAttribute((const void*)bin_emit_kernel<F, P, Src>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                lds_a_max);                                                                         \
-      (void)hipFuncSetAttribute((const void*)bin_reduce_kernel<F, P>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                kTileBytes + 4096);                                                                 \
-      configured = true;                                                                                            \
-    }                                                                                                               \
-    bin_emit_kernel<F, P, Src><<<grid_a, 1024, lds_a, st>>>(gd, src, p.log2TS, p.nb, i_off, cnt, counts,             \
-                                                            nseg > 1 ? segtot : nullptr, offsets, gpos, gidx,       \
-                                                            nlive, qrec, qmax, p.nmax);                             \
-    bin_reduce_kernel<F, P><<<cols, 1024, lds_b, st>>>(offsets, qrec, qmax, grad_table, gd.log2T, p.log2TS, p.nb,   \
-                                                       p.nmax, (overwrite && i_off == 0) ? 1 : 0, out_half ? 1 : 0, \
-                                                       nbg);                                                        \
-  } while (0)
-#define CALL(F)              \
-  do {                       \
-    if (p.pair) CALL2(F, true);  \
-    else CALL2(F, false);    \
-  } while (0)
-    NR_DISPATCH_F(gd.F, CALL);
-#undef CALL
-#undef CALL2
+    dispatch_f(gd.F, p.pair, [&](auto F, auto P) {
+      static thread_local bool configured = false;  // one flag per instantiation of this body: per (F, PAIR, Src)
+      if (!configured) {
+        (void)hipFuncSetAttribute((const void*)bin_emit_kernel<F, P, Src>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  lds_a_max);
+        (void)hipFuncSetAttribute((const void*)bin_reduce_kernel<F, P>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  kTileBytes + 4096);
+        configured = true;
+      }
+      bin_emit_kernel<F, P, Src><<<grid_a, 1024, lds_a, st>>>(gd, src, p.log2TS, p.nb, i_off, cnt, counts,
+                                                              nseg > 1 ? segtot : nullptr, offsets, gpos, gidx, nlive,
+                                                              qrec, qmax, p.nmax);
+      bin_reduce_kernel<F, P><<<cols, 1024, lds_b, st>>>(offsets, qrec, qmax, grad_table, gd.log2T, p.log2TS, p.nb,
+                                                         p.nmax, (overwrite && i_off == 0) ? 1 : 0, out_half ? 1 : 0,
+                                                         nbg);
+    });
     if (int e = check_launch(what)) return e;
   }
   return NRHIP_OK;

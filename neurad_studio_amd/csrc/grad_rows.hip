@@ -146,14 +146,12 @@ int fill_levels(const int32_t* levels, const int64_t* caps, int32_t n, int32_t n
 
 using namespace nrhip;
 
-#define NR_ROWS_F(F, CALL)                                                                                  \
-  switch (F) {                                                                                              \
-    case 1: CALL(1); break;                                                                                 \
-    case 2: CALL(2); break;                                                                                 \
-    case 4: CALL(4); break;                                                                                 \
-    case 8: CALL(8); break;                                                                                 \
-    default: NR_REQUIRE(false, NRHIP_ERR_UNSUPPORTED, "grad_rows: features_per_level %d not in {1,2,4,8}", (int)F); \
-  }
+// f arrives as a bare int here, not in a validated nrhip_grid: checked before every dispatch_f
+static int check_rows_f(int f) {
+  NR_REQUIRE(f == 1 || f == 2 || f == 4 || f == 8, NRHIP_ERR_UNSUPPORTED,
+             "grad_rows: features_per_level %d not in {1,2,4,8}", f);
+  return NRHIP_OK;
+}
 
 static int64_t rows_blocks(int64_t rows_per_level) { return (rows_per_level + kRowsPerBlock - 1) / kRowsPerBlock; }
 
@@ -165,11 +163,11 @@ extern "C" int nrhip_grad_rows_count(const float* grad, int32_t n_levels, int64_
   const int nblk = (int)rows_blocks(rows_per_level);
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(level_counts, 0, (size_t)n_levels * sizeof(int64_t), st) != hipSuccess) return check_launch("grad_rows_count");
-#define CALL(F)                                                                                                       \
-  rows_count_kernel<F><<<dim3((unsigned)nblk, (unsigned)n_levels), kRowsPerBlock, 0, st>>>(                           \
-      grad, rows_per_level, nblk, block_counts, reinterpret_cast<unsigned long long*>(level_counts))
-  NR_ROWS_F(f, CALL);
-#undef CALL
+  if (int e = check_rows_f(f)) return e;
+  dispatch_f(f, [&](auto F) {
+    rows_count_kernel<F><<<dim3((unsigned)nblk, (unsigned)n_levels), kRowsPerBlock, 0, st>>>(
+        grad, rows_per_level, nblk, block_counts, reinterpret_cast<unsigned long long*>(level_counts));
+  });
   rows_scan_kernel<<<n_levels, 1024, 0, st>>>(block_counts, nblk);
   return check_launch("grad_rows_count");
 }
@@ -183,11 +181,11 @@ extern "C" int nrhip_grad_rows_compact(const float* grad, int32_t n_levels, int6
   if (int e = fill_levels(levels, caps, n_list_levels, n_levels, &ll, "grad_rows_compact")) return e;
   if (ll.start[ll.n] == 0) return NRHIP_OK;
   const int nblk = (int)rows_blocks(rows_per_level);
-#define CALL(F)                                                                                                           \
-  rows_compact_kernel<F><<<dim3((unsigned)nblk, (unsigned)ll.n), kRowsPerBlock, 0, (hipStream_t)stream>>>(                \
-      grad, rows_per_level, nblk, block_offsets, ll, scale, rows, vals)
-  NR_ROWS_F(f, CALL);
-#undef CALL
+  if (int e = check_rows_f(f)) return e;
+  dispatch_f(f, [&](auto F) {
+    rows_compact_kernel<F><<<dim3((unsigned)nblk, (unsigned)ll.n), kRowsPerBlock, 0, (hipStream_t)stream>>>(
+        grad, rows_per_level, nblk, block_offsets, ll, scale, rows, vals);
+  });
   return check_launch("grad_rows_compact");
 }
 
@@ -200,10 +198,10 @@ extern "C" int nrhip_grad_rows_apply(float* grad, int32_t n_levels, int64_t rows
   if (int e = fill_levels(levels, caps, n_list_levels, n_levels, &ll, "grad_rows_apply")) return e;
   const int64_t total = ll.start[ll.n];
   if (total == 0) return NRHIP_OK;
-#define CALL(F)                                                                                                      \
-  rows_apply_kernel<F><<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(grad, rows_per_level, ll, rows, \
-                                                                                          vals, mode)
-  NR_ROWS_F(f, CALL);
-#undef CALL
+  if (int e = check_rows_f(f)) return e;
+  dispatch_f(f, [&](auto F) {
+    rows_apply_kernel<F><<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(grad, rows_per_level, ll,
+                                                                                            rows, vals, mode);
+  });
   return check_launch("grad_rows_apply");
 }

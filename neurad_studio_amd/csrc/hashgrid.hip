@@ -130,19 +130,7 @@ __global__ __launch_bounds__(256) void hashgrid_multi_bwd_runs_kernel(GridDev g,
       for (int j = 0; j < F; ++j) v[j] = w[k] * gv[j];
       if (hm != __ballot(live)) {  // some run is longer than 1: segmented suffix sum onto the run heads, inside each row
         const uint32_t run = (uint32_t)__popcll(hm & ((2ull << lane) - 1ull));
-#define NR_SEG_STEP(OFF)                                                   \
-  {                                                                        \
-    const bool same = dpp_row_shl<OFF>(run, 0xffffffffu) == run;           \
-    _Pragma("unroll") for (int j = 0; j < F; ++j) {                        \
-      const float t = dpp_row_shl<OFF>(v[j], 0.f);                         \
-      if (same) v[j] += t;                                                 \
-    }                                                                      \
-  }
-        NR_SEG_STEP(1)
-        NR_SEG_STEP(2)
-        NR_SEG_STEP(4)
-        NR_SEG_STEP(8)
-#undef NR_SEG_STEP
+        NR_SUM_RUNS_ONTO_HEADS(v, F, run)
       }
       if (head) {
         float* e = table + (((size_t)l << g.log2T) + c.idx[k]) * F;
@@ -390,26 +378,6 @@ __global__ __launch_bounds__(256) void proposal_density_bwd_kernel(GridDev g, co
   }
 }
 
-// --------------------------------------------------------------------------------------------
-#define DISPATCH_F_HALF(F_, HALF_, CALL)                                   \
-  do {                                                                     \
-    const int f__ = (F_);                                                  \
-    const bool h__ = (HALF_);                                              \
-    if (f__ == 1) { if (h__) { CALL(1, true); } else { CALL(1, false); } } \
-    else if (f__ == 2) { if (h__) { CALL(2, true); } else { CALL(2, false); } } \
-    else if (f__ == 4) { if (h__) { CALL(4, true); } else { CALL(4, false); } } \
-    else { if (h__) { CALL(8, true); } else { CALL(8, false); } }          \
-  } while (0)
-
-#define DISPATCH_F(F_, CALL)         \
-  do {                               \
-    const int f__ = (F_);            \
-    if (f__ == 1) { CALL(1); }       \
-    else if (f__ == 2) { CALL(2); }  \
-    else if (f__ == 4) { CALL(4); }  \
-    else { CALL(8); }                \
-  } while (0)
-
 }  // namespace nrhip
 
 using namespace nrhip;
@@ -422,9 +390,9 @@ extern "C" int nrhip_hashgrid_fwd(const nrhip_grid* g, const void* table, const 
   NR_REQUIRE(table && x && out, NRHIP_ERR_INVALID_ARG, "hashgrid_fwd: null pointer");
   const GridDev gd = to_dev(*g);
   const int blocks = grid_for(n * gd.L, 256);
-#define CALL(F, H) hashgrid_fwd_kernel<F, H><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, table, x, n, out)
-  DISPATCH_F_HALF(gd.F, gd.dtype == 1, CALL);
-#undef CALL
+  dispatch_f(gd.F, gd.dtype == 1, [&](auto F, auto H) {
+    hashgrid_fwd_kernel<F, H><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, table, x, n, out);
+  });
   return check_launch("hashgrid_fwd");
 }
 
@@ -435,9 +403,9 @@ extern "C" int nrhip_hashgrid_bwd(const nrhip_grid* g, const float* x, const flo
   if (n == 0) return NRHIP_OK;
   const GridDev gd = to_dev(*g);
   const int blocks = grid_for(n * gd.L, 256);
-#define CALL(F) hashgrid_bwd_kernel<F><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, x, grad_out, n, grad_table)
-  DISPATCH_F(gd.F, CALL);
-#undef CALL
+  dispatch_f(gd.F, [&](auto F) {
+    hashgrid_bwd_kernel<F><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, x, grad_out, n, grad_table);
+  });
   return check_launch("hashgrid_bwd");
 }
 
@@ -451,9 +419,9 @@ extern "C" int nrhip_encode_fwd(const nrhip_grid* g, const void* table, float st
   const GridDev gd = to_dev(*g);
   const RaysDev rd = to_dev(*rays);
   const int blocks = grid_for(n * gd.L, 256);
-#define CALL(F, H) encode_fwd_kernel<F, H><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, table, static_scale, rd, out)
-  DISPATCH_F_HALF(gd.F, gd.dtype == 1, CALL);
-#undef CALL
+  dispatch_f(gd.F, gd.dtype == 1, [&](auto F, auto H) {
+    encode_fwd_kernel<F, H><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, table, static_scale, rd, out);
+  });
   return check_launch("encode_fwd");
 }
 
@@ -467,9 +435,9 @@ extern "C" int nrhip_encode_bwd(const nrhip_grid* g, float static_scale, const n
   const GridDev gd = to_dev(*g);
   const RaysDev rd = to_dev(*rays);
   const int blocks = grid_for(n, 256);
-#define CALL(F) encode_bwd_runs_kernel<F><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, static_scale, rd, grad_out, grad_table)
-  DISPATCH_F(gd.F, CALL);
-#undef CALL
+  dispatch_f(gd.F, [&](auto F) {
+    encode_bwd_runs_kernel<F><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, static_scale, rd, grad_out, grad_table);
+  });
   return check_launch("encode_bwd");
 }
 
@@ -640,15 +608,10 @@ extern "C" int nrhip_hashgrid_multi_fwd(const nrhip_grid* g, const void* const* 
   NR_REQUIRE(tables && grid_id && x && out, NRHIP_ERR_INVALID_ARG, "hashgrid_multi_fwd: null pointer");
   const GridDev gd = to_dev(*g);
   const int blocks = grid_for(n * gd.L, 256);
-  if (g->param_dtype == 1) {  // fp16-storage grids (all grids of one call share the dtype)
-#define CALL(F) hashgrid_multi_fwd_kernel<F, true><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, tables, grid_id, x, n, out)
-    DISPATCH_F(gd.F, CALL);
-#undef CALL
-  } else {
-#define CALL(F) hashgrid_multi_fwd_kernel<F, false><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, tables, grid_id, x, n, out)
-    DISPATCH_F(gd.F, CALL);
-#undef CALL
-  }
+  // H: fp16-storage grids (all grids of one call share the dtype)
+  dispatch_f(gd.F, g->param_dtype == 1, [&](auto F, auto H) {
+    hashgrid_multi_fwd_kernel<F, H><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, tables, grid_id, x, n, out);
+  });
   return check_launch("hashgrid_multi_fwd");
 }
 
@@ -661,14 +624,16 @@ extern "C" int nrhip_hashgrid_multi_bwd(const nrhip_grid* g, int32_t n_grids, co
   const GridDev gd = to_dev(*g);
   if (!tuning().multi_bwd_runs) {  // NRHIP_MULTI_BWD_RUNS=0: one thread per (row, level), every corner term its own atomic (A/B)
     const int blocks = grid_for(n * gd.L, 256);
-#define CALL(F) hashgrid_multi_bwd_kernel<F><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, grid_id, x, grad_out, n, grad_tables, n_grids)
-    DISPATCH_F(gd.F, CALL);
-#undef CALL
+    dispatch_f(gd.F, [&](auto F) {
+      hashgrid_multi_bwd_kernel<F><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, grid_id, x, grad_out, n, grad_tables,
+                                                                            n_grids);
+    });
   } else {
     const int blocks = grid_for(n, 256);
-#define CALL(F) hashgrid_multi_bwd_runs_kernel<F><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, grid_id, x, grad_out, n, grad_tables, n_grids)
-    DISPATCH_F(gd.F, CALL);
-#undef CALL
+    dispatch_f(gd.F, [&](auto F) {
+      hashgrid_multi_bwd_runs_kernel<F><<<blocks, 256, 0, (hipStream_t)stream>>>(gd, grid_id, x, grad_out, n,
+                                                                                 grad_tables, n_grids);
+    });
   }
   return check_launch("hashgrid_multi_bwd");
 }

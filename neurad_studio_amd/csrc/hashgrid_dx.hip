@@ -161,18 +161,9 @@ extern "C" int nrhip_hashgrid_bwd_input(const nrhip_grid* g, const void* table, 
   const GridDev gd = to_dev(*g);
   const int blocks = grid_for(n, 256);
   const hipStream_t st = (hipStream_t)stream;
-#define CALL(F)                                                                        \
-  do {                                                                                 \
-    if (g->param_dtype == 1) hashgrid_bwd_input_kernel<F, true><<<blocks, 256, 0, st>>>(gd, table, x, grad_out, n, grad_x);   \
-    else hashgrid_bwd_input_kernel<F, false><<<blocks, 256, 0, st>>>(gd, table, x, grad_out, n, grad_x);                      \
-  } while (0)
-  switch (gd.F) {
-    case 1: CALL(1); break;
-    case 2: CALL(2); break;
-    case 4: CALL(4); break;
-    default: CALL(8); break;
-  }
-#undef CALL
+  dispatch_f(gd.F, g->param_dtype == 1, [&](auto F, auto H) {
+    hashgrid_bwd_input_kernel<F, H><<<blocks, 256, 0, st>>>(gd, table, x, grad_out, n, grad_x);
+  });
   return check_launch("hashgrid_bwd_input");
 }
 
@@ -186,18 +177,9 @@ extern "C" int nrhip_hashgrid_multi_bwd_input(const nrhip_grid* g, const void* c
   const GridDev gd = to_dev(*g);
   const int blocks = grid_for(n, 256);
   const hipStream_t st = (hipStream_t)stream;
-#define CALL(F)                                                                        \
-  do {                                                                                 \
-    if (g->param_dtype == 1) hashgrid_multi_bwd_input_kernel<F, true><<<blocks, 256, 0, st>>>(gd, tables, grid_id, x, grad_out, n, grad_x);   \
-    else hashgrid_multi_bwd_input_kernel<F, false><<<blocks, 256, 0, st>>>(gd, tables, grid_id, x, grad_out, n, grad_x);                      \
-  } while (0)
-  switch (gd.F) {
-    case 1: CALL(1); break;
-    case 2: CALL(2); break;
-    case 4: CALL(4); break;
-    default: CALL(8); break;
-  }
-#undef CALL
+  dispatch_f(gd.F, g->param_dtype == 1, [&](auto F, auto H) {
+    hashgrid_multi_bwd_input_kernel<F, H><<<blocks, 256, 0, st>>>(gd, tables, grid_id, x, grad_out, n, grad_x);
+  });
   return check_launch("hashgrid_multi_bwd_input");
 }
 
@@ -213,21 +195,9 @@ extern "C" int nrhip_encode_bwd_rays(const nrhip_grid* g, const void* table, flo
   const int G = rd.S > 32 ? 64 : (rd.S > 16 ? 32 : 16);
   const int blocks = grid_for(rd.R * G, 256);
   const hipStream_t st = (hipStream_t)stream;
-#define CALL(F)                                                                                                        \
-  do {                                                                                                                 \
-    if (g->param_dtype == 1)                                                                                           \
-      encode_bwd_rays_kernel<F, true><<<blocks, 256, 0, st>>>(gd, table, static_scale, rd, grad_out, G, grad_origins, \
-                                                              grad_directions);                                        \
-    else                                                                                                               \
-      encode_bwd_rays_kernel<F, false><<<blocks, 256, 0, st>>>(gd, table, static_scale, rd, grad_out, G, grad_origins, \
-                                                               grad_directions);                                       \
-  } while (0)
-  switch (gd.F) {
-    case 1: CALL(1); break;
-    case 2: CALL(2); break;
-    case 4: CALL(4); break;
-    default: CALL(8); break;
-  }
-#undef CALL
+  dispatch_f(gd.F, g->param_dtype == 1, [&](auto F, auto H) {
+    encode_bwd_rays_kernel<F, H><<<blocks, 256, 0, st>>>(gd, table, static_scale, rd, grad_out, G, grad_origins,
+                                                         grad_directions);
+  });
   return check_launch("encode_bwd_rays");
 }

@@ -46,10 +46,6 @@ __device__ __forceinline__ void scan_inplace(float* arr, int n, int lane) {
     carry = wscan::last(v);
   }
 }
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 __global__ __launch_bounds__(64 * kRaysPerBlock) void interlevel_loss_kernel(
     const float* __restrict__ c_all, const float* __restrict__ w_all, int sf, const float* __restrict__ cp_all,

@@ -43,19 +43,19 @@ inline int blocks_for(int64_t r) {
 
 // total over each aligned group of lp in {1,2,4,8} lanes, in every lane of the group (DPP quad_perm / row_half_mirror)
 __device__ __forceinline__ float group_sum(float q, int lp) {
-  if (lp >= 2) q += wscan::dpp<0xB1>(0.f, q);  // quad_perm [1,0,3,2]
-  if (lp >= 4) q += wscan::dpp<0x4E>(0.f, q);  // quad_perm [2,3,0,1]
-  if (lp >= 8) q += wscan::dpp<0x141>(0.f, q);  // row_half_mirror: the other quad of the 8 (quads are uniform by now)
+  if (lp >= 2) q += dpp<0xB1>(0.f, q);  // quad_perm [1,0,3,2]
+  if (lp >= 4) q += dpp<0x4E>(0.f, q);  // quad_perm [2,3,0,1]
+  if (lp >= 8) q += dpp<0x141>(0.f, q);  // row_half_mirror: the other quad of the 8 (quads are uniform by now)
   return q;
 }
 
 // total over the lanes of the wave with the same lane % lp, lp in {1,2,4,8}: row rotations inside the 16-lane rows, then the
 // four rows
 __device__ __forceinline__ float class_sum(float v, int lp) {
-  if (lp <= 1) v += wscan::dpp<0x121>(0.f, v);  // row_ror:1
-  if (lp <= 2) v += wscan::dpp<0x122>(0.f, v);  // row_ror:2
-  if (lp <= 4) v += wscan::dpp<0x124>(0.f, v);  // row_ror:4
-  v += wscan::dpp<0x128>(0.f, v);               // row_ror:8
+  if (lp <= 1) v += dpp<0x121>(0.f, v);  // row_ror:1
+  if (lp <= 2) v += dpp<0x122>(0.f, v);  // row_ror:2
+  if (lp <= 4) v += dpp<0x124>(0.f, v);  // row_ror:4
+  v += dpp<0x128>(0.f, v);               // row_ror:8
   v += __shfl_xor(v, 16, 64);
   v += __shfl_xor(v, 32, 64);
   return v;

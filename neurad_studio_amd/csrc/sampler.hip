@@ -143,10 +143,6 @@ __global__ __launch_bounds__(kOrderThreads) void power_sampler_order_kernel(
 // wave-wide sum / scan on DPP row shifts + readlane (wave_scan.h), not on ds_bpermute shuffles
 __device__ __forceinline__ float wsum(float v) { return wscan::reduce<wscan::Add>(v); }
 __device__ __forceinline__ float wscan_add(float v, int lane) { return wscan::incl<wscan::Add>(v, lane); }
-__device__ __forceinline__ void wave_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // S4 for one ray (ray_samplers.py:306-366).  w_lds[Sp] raw weights, bins_lds[Sp+1] existing spacing bins,
 // cdf_lds[Sp+1] scratch.  Writes the Sn+1 new spacing bins to new_bins (LDS or global) and, if eu_out, the

@@ -324,10 +324,10 @@ namespace half {
 template <class Op>
 __device__ __forceinline__ float incl(float v, int lane) {
   const float e = Op::template id<float>();
-  v = Op::op(wscan::dpp<0x111>(e, v), v);
-  v = Op::op(wscan::dpp<0x112>(e, v), v);
-  v = Op::op(wscan::dpp<0x114>(e, v), v);
-  v = Op::op(wscan::dpp<0x118>(e, v), v);
+  v = Op::op(dpp<0x111>(e, v), v);
+  v = Op::op(dpp<0x112>(e, v), v);
+  v = Op::op(dpp<0x114>(e, v), v);
+  v = Op::op(dpp<0x118>(e, v), v);
   const float t0 = wscan::lane_of(v, 15), t2 = wscan::lane_of(v, 47);
   const int row = lane >> 4;
   return Op::op(row == 1 ? t0 : (row == 3 ? t2 : e), v);
@@ -335,17 +335,17 @@ __device__ __forceinline__ float incl(float v, int lane) {
 template <class Op>
 __device__ __forceinline__ float rincl(float v, int lane) {
   const float e = Op::template id<float>();
-  v = Op::op(v, wscan::dpp<0x101>(e, v));
-  v = Op::op(v, wscan::dpp<0x102>(e, v));
-  v = Op::op(v, wscan::dpp<0x104>(e, v));
-  v = Op::op(v, wscan::dpp<0x108>(e, v));
+  v = Op::op(v, dpp<0x101>(e, v));
+  v = Op::op(v, dpp<0x102>(e, v));
+  v = Op::op(v, dpp<0x104>(e, v));
+  v = Op::op(v, dpp<0x108>(e, v));
   const float s1 = wscan::lane_of(v, 16), s3 = wscan::lane_of(v, 48);
   const int row = lane >> 4;
   return Op::op(v, row == 0 ? s1 : (row == 2 ? s3 : e));
 }
 // the value of lane - 1 inside the half (lanes 0 and 32: `first`)
 __device__ __forceinline__ float shift_up1(float v, float first, int lane) {
-  float x = wscan::dpp<0x111>(first, v);
+  float x = dpp<0x111>(first, v);
   const float a = wscan::lane_of(v, 15), c = wscan::lane_of(v, 47);
   x = lane == 16 ? a : x;
   x = lane == 48 ? c : x;
@@ -353,10 +353,10 @@ __device__ __forceinline__ float shift_up1(float v, float first, int lane) {
 }
 // sum over the half, the same value in each of its lanes
 __device__ __forceinline__ float sum(float v, int lane) {
-  v += wscan::dpp<0x111>(0.f, v);
-  v += wscan::dpp<0x112>(0.f, v);
-  v += wscan::dpp<0x114>(0.f, v);
-  v += wscan::dpp<0x118>(0.f, v);
+  v += dpp<0x111>(0.f, v);
+  v += dpp<0x112>(0.f, v);
+  v += dpp<0x114>(0.f, v);
+  v += dpp<0x118>(0.f, v);
   const float lo = wscan::lane_of(v, 15) + wscan::lane_of(v, 31), hi = wscan::lane_of(v, 47) + wscan::lane_of(v, 63);
   return lane < 32 ? lo : hi;
 }

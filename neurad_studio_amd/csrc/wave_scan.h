@@ -1,34 +1,17 @@
 // Wave-wide (64-lane) prefix scans and reductions for the one-wave-per-ray kernels (losses.hip, train_fused.hip,
-// composite.hip, the PDF sampler): DPP row shifts inside the four 16-lane rows -- VALU rate -- and three v_readlane for the
-// row totals, instead of six dependent ds_bpermute per scan (what __shfl_up compiles to: each a round trip through the LDS
-// crossbar, and these kernels are chains of such scans: the interlevel loss runs six fp64 ones per ray).
+// composite.hip, packed_composite.h, the PDF sampler in sampler.hip) and for the ray ordering (rayorder.h) and the
+// gradient row lists (grad_rows.hip): DPP row shifts (dpp<CTRL> of common.h) inside the four 16-lane rows -- VALU rate
+// -- and three v_readlane for the row totals, instead of six dependent ds_bpermute per scan (what __shfl_up compiles to:
+// each a round trip through the LDS crossbar, and these kernels are chains of such scans: the interlevel loss runs six
+// fp64 ones per ray).
 // The association of the sums differs from a Hillis-Steele scan only across rows (prefix = total of the rows below + in-row
 // prefix); every caller is an fp32 / fp64 sum or product with tolerances, none needs a particular association.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "common.h"  // dpp<CTRL>
 
 namespace nrhip {
 namespace wscan {
 
-template <int CTRL>
-__device__ __forceinline__ int dpp(int old, int v) {
-  return __builtin_amdgcn_update_dpp(old, v, CTRL, 0xf, 0xf, false);  // lanes without a source keep `old`
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp(float old, float v) {
-  return __builtin_bit_cast(float, dpp<CTRL>(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v)));
-}
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp(uint32_t old, uint32_t v) {
-  return (uint32_t)dpp<CTRL>((int)old, (int)v);
-}
-template <int CTRL>
-__device__ __forceinline__ double dpp(double old, double v) {
-  const long long o = __builtin_bit_cast(long long, old), x = __builtin_bit_cast(long long, v);
-  const uint32_t lo = (uint32_t)dpp<CTRL>((int)(uint32_t)o, (int)(uint32_t)x);
-  const uint32_t hi = (uint32_t)dpp<CTRL>((int)(uint32_t)(o >> 32), (int)(uint32_t)(x >> 32));
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
 __device__ __forceinline__ float lane_of(float v, int l) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
 }

@@ -161,6 +161,36 @@ def ray_order(origins: Tensor, directions: Tensor, static_scale: float, t_ref: O
 
 
 # ------------------------------------------------------------------------------------------------
+# Table gradients: the atomics-free radix partition (csrc/encode_bwd_binned.hip) or memory-side atomics.
+# A/B switch for profiling and for the parity test of the atomic path
+_FORCE_ATOMIC_SCATTER = os.environ.get("NRHIP_ENCODE_BWD_ATOMIC") is not None
+_MULTI_BWD_BINNED = os.environ.get("NRHIP_MULTI_BWD_BINNED", "1") != "0"  # 0: the actor grids' gradients by atomics (A/B)
+_BINNED_MIN_SAMPLES = 1 << 15
+_BINNED_ROUND_SAMPLES = 1 << 23  # round_samples() of csrc/encode_bwd_binned.hip
+
+
+def _binned_table_grad(n_samples: int, out_dtype=torch.float32, enabled: bool = True) -> Tuple[bool, bool]:
+    """-> (binned, half).  binned: the partition computes this gradient (unless the library then reports no workspace: a
+    table too large to cut into LDS slices) -- not for small batches (one actor's hits), where four launches + scratch cost
+    more than the few atomics.  half: it also writes the fp16 gradient of an fp16-storage table itself, which takes one round
+    of the library's default length; otherwise fp32 comes back and the caller casts."""
+    binned = enabled and n_samples >= _BINNED_MIN_SAMPLES and not _FORCE_ATOMIC_SCATTER
+    half = (binned and out_dtype == torch.float16 and n_samples <= _BINNED_ROUND_SAMPLES
+            and "NRHIP_BIN_ROUND_LOG2" not in os.environ)
+    return binned, half
+
+
+def _table_grad_workspace(c_grid, n_samples: int, device) -> Optional[Tensor]:
+    """Scratch for the atomics-free table gradients; None -> use the atomic entry point."""
+    if not _binned_table_grad(n_samples)[0]:
+        return None
+    need = C.c_int64(0)
+    call("nrhip_encode_bwd_binned_workspace", C.byref(c_grid), int(n_samples), C.byref(need))
+    if need.value <= 0:
+        return None
+    return torch.empty((need.value,), device=device, dtype=torch.uint8)
+
+
 def hashgrid_fwd(spec: GridSpec, table: Tensor, x: Tensor) -> Tensor:
     x = _chk(x, "x")
     if x.dim() != 2 or x.shape[1] != 3:
@@ -250,10 +280,10 @@ def _multi_bwd_block(spec: GridSpec, n_grids: int, grid_id: Tensor, x: Tensor, g
                      n_slots: int, out_dtype) -> Tensor:
     """-> [n_slots, rows, F] of ``out_dtype``: slot slots[a] holds grid a's gradient (slots[a] < 0: grid a sends nothing)"""
     n = x.shape[0]
-    if n >= _BINNED_MIN_SAMPLES and not _FORCE_ATOMIC_SCATTER and _MULTI_BWD_BINNED:
+    binned, half = _binned_table_grad(n, out_dtype, enabled=_MULTI_BWD_BINNED)
+    if binned:
         # the radix partition over (slot, level, slice) (csrc/encode_bwd_binned.hip, MultiSrc): no memory-side atomics, every
         # element of the block written by the partition (no zero-fill), fp16-storage grids get their fp16 gradient directly
-        half = out_dtype == torch.float16 and n <= _BINNED_ROUND_SAMPLES and "NRHIP_BIN_ROUND_LOG2" not in os.environ
         g = spec.c_grid(torch.empty((spec.table_rows, spec.features_per_level), device="meta"))  # (the shape only)
         need = C.c_int64(0)
         call("nrhip_hashgrid_multi_bwd_binned_workspace", C.byref(g), n_slots, n, C.byref(need))
@@ -312,32 +342,12 @@ def hashgrid_bwd_input(spec: GridSpec, table: Tensor, x: Tensor, grad_out: Tenso
     return gx
 
 
-# A/B switch for profiling and for the parity test of the atomic path
-_FORCE_ATOMIC_SCATTER = os.environ.get("NRHIP_ENCODE_BWD_ATOMIC") is not None
-_BINNED_MIN_SAMPLES = 1 << 15
-_MULTI_BWD_BINNED = os.environ.get("NRHIP_MULTI_BWD_BINNED", "1") != "0"  # 0: the actor grids' gradients by atomics (A/B)
-
-
-def _table_grad_workspace(c_grid, n_samples: int, device) -> Optional[Tensor]:
-    """Scratch for the atomics-free table gradients (csrc/encode_bwd_binned.hip); None -> use the atomic entry point."""
-    if _FORCE_ATOMIC_SCATTER or n_samples < _BINNED_MIN_SAMPLES:
-        return None  # small batches (one actor's hits): four launches + scratch cost more than the few atomics
-    need = C.c_int64(0)
-    call("nrhip_encode_bwd_binned_workspace", C.byref(c_grid), int(n_samples), C.byref(need))
-    if need.value <= 0:
-        return None
-    return torch.empty((need.value,), device=device, dtype=torch.uint8)
-
-
 def encode_fwd(spec: GridSpec, table: Tensor, static_scale: float, origins, directions, pixel_area, starts, ends):
     r, keep = _c_rays(origins, directions, pixel_area, starts, ends)
     out = torch.empty((r.n_rays * r.n_samples, spec.out_dim), device=origins.device, dtype=torch.float32)
     g = spec.c_grid(table)
     call("nrhip_encode_fwd", C.byref(g), _ptr(table), float(static_scale), C.byref(r), _ptr(out), _stream())
     return out
-
-
-_BINNED_ROUND_SAMPLES = 1 << 23  # round_samples() of csrc/encode_bwd_binned.hip
 
 
 def encode_bwd(spec: GridSpec, static_scale: float, origins, directions, pixel_area, starts, ends, grad_out,
@@ -347,8 +357,7 @@ def encode_bwd(spec: GridSpec, static_scale: float, origins, directions, pixel_a
     r, keep = _c_rays(origins, directions, pixel_area, starts, ends)
     grad_out = _chk(grad_out, "grad_out")
     n = r.n_rays * r.n_samples
-    half = (out_dtype == torch.float16 and n <= _BINNED_ROUND_SAMPLES and not _FORCE_ATOMIC_SCATTER and n >= _BINNED_MIN_SAMPLES
-            and "NRHIP_BIN_ROUND_LOG2" not in os.environ)
+    half = _binned_table_grad(n, out_dtype)[1]
     gt = torch.empty((spec.table_rows, spec.features_per_level), device=origins.device,
                      dtype=torch.float16 if half else torch.float32)
     g = spec.c_grid(gt)

@@ -71,3 +71,12 @@ def test_empty_lists_and_argument_checks():
         ops.grad_rows_compact(grad, 2, blocks, [2], [4])  # level out of range
     with pytest.raises(_lib.NeuradHipError):
         ops.grad_rows_count(torch.zeros(2 * 512, 3, device="cuda"), 2)  # features_per_level not in {1, 2, 4, 8}
+    # ... in each of the three entry points, as NRHIP_ERR_UNSUPPORTED (2) with this message
+    bad = torch.zeros(2 * 512, 3, device="cuda")
+    message = r"failed \(code 2\): grad_rows: features_per_level 3 not in \{1,2,4,8\}"
+    with pytest.raises(_lib.NeuradHipError, match="nrhip_grad_rows_count " + message):
+        ops.grad_rows_count(bad, 2)
+    with pytest.raises(_lib.NeuradHipError, match="nrhip_grad_rows_compact " + message):
+        ops.grad_rows_compact(bad, 2, blocks, [0], [4])
+    with pytest.raises(_lib.NeuradHipError, match="nrhip_grad_rows_apply " + message):
+        ops.grad_rows_apply(bad, 2, [0], [4], torch.zeros(4, dtype=torch.int32, device="cuda"), None, add=False)

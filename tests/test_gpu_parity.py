@@ -799,3 +799,95 @@ def test_binned_table_gradient_is_fp32_whatever_the_tables_storage_type(ops, mon
     _lib.call("nrhip_hashgrid_bwd_binned", C.byref(g), ops._ptr(x), ops._ptr(g2), 500, ops._ptr(gt2), 1, ops._ptr(ws2),
               ws2.numel(), ops._stream())
     assert torch.equal(gt2, want2)
+
+
+# ------------------------------------------------------------------------------------------------
+# Every entry point that picks its kernel by features-per-level (csrc/common.h: dispatch_f), at every F and both table
+# storage types.  The smallest shape that separates the instantiations: 257 rows (no multiple of 64 or 256), 2 levels,
+# 2^8 entries.  A call that lands in another width's kernel reads and writes rows of another length and misses at any
+# tolerance; the tolerances are those of the tests of the same entry points above and in test_gpu_multi_grid_binned.py.
+DISPATCH_L, DISPATCH_LG, DISPATCH_N, DISPATCH_GRIDS = 2, 8, 257, 3
+
+
+def _dispatch_tables(F, half):
+    tabs = [synth.hash_table(DISPATCH_L * 2**DISPATCH_LG, F, seed=600 + 10 * F + i, scale=0.7) for i in range(DISPATCH_GRIDS)]
+    if half:  # the oracle sees the values the fp16 storage holds
+        tabs = [t.astype(np.float16).astype(np.float32) for t in tabs]
+    return tabs
+
+
+@pytest.fixture
+def library_calls(ops, monkeypatch):
+    """names of the C entry points the wrappers reach, in order"""
+    names, real = [], ops.call
+
+    def call(name, *args):
+        names.append(name)
+        return real(name, *args)
+
+    monkeypatch.setattr(ops, "call", call)
+    return names
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["fp32", "fp16"])
+@pytest.mark.parametrize("F", [1, 2, 4, 8])
+def test_forward_lookups_at_every_feature_width_and_storage_type(ops, F, half):
+    L, lg, n = DISPATCH_L, DISPATCH_LG, DISPATCH_N
+    tdt = torch.float16 if half else torch.float32
+    tabs = _dispatch_tables(F, half)
+    spec = ops.GridSpec(L, F, lg, 16, 64)
+    scal = O.hash_scalings(L, 16, 64)
+    x = synth.uniform((n, 3), 0.0, 1.0, 40 + F)
+    # nrhip_hashgrid_fwd
+    y = host(ops.hashgrid_fwd(spec, dev(tabs[0], tdt), dev(x)))
+    assert y.shape == (n, L * F) and rel_l2(y, O.hashgrid_fwd(x, tabs[0], scal, 2**lg)) < TIGHT
+    # nrhip_hashgrid_multi_fwd: row i looks up tables[ids[i]]
+    ids = (np.arange(n) % DISPATCH_GRIDS).astype(np.int32)
+    ym = host(ops.hashgrid_multi_fwd(spec, [dev(t, tdt) for t in tabs], dev(ids, torch.int32), dev(x)))
+    ref = np.zeros_like(ym)
+    for a in range(DISPATCH_GRIDS):
+        ref[ids == a] = O.hashgrid_fwd(x[ids == a], tabs[a], scal, 2**lg)
+    assert rel_l2(ym, ref) < TOL
+    # nrhip_encode_fwd: one sample on each of 257 rays
+    o, d, area, st, en, _ = _sample_rays(n, 1, seed=60 + F)
+    enc = host(ops.encode_fwd(spec, dev(tabs[0], tdt), 100.0, dev(o), dev(d), dev(area), dev(st), dev(en)))
+    assert rel_l2(enc, O.encode_static(O.GridParams(tabs[0], L, 16, 64, lg), 100.0, o, d, area, st, en)) < TIGHT
+
+
+@pytest.mark.parametrize("F", [1, 2, 4, 8])
+def test_table_gradients_at_every_feature_width(ops, F, monkeypatch, switches, library_calls):
+    """atomics and partition, the partition with and without x-pair records (its second template flag), one grid and several"""
+    L, lg, n, G = DISPATCH_L, DISPATCH_LG, DISPATCH_N, DISPATCH_GRIDS
+    spec = ops.GridSpec(L, F, lg, 16, 64)
+    scal = O.hash_scalings(L, 16, 64)
+    x = synth.uniform((n, 3), 0.0, 1.0, 40 + F)
+    x[64:128] = x[64] + 1e-4 * x[64:128]  # one cell: runs of equal entries in neighbouring lanes
+    x = np.clip(x, 0.0, 1.0)
+    go = synth.normal((n, L * F), 50 + F)
+    ids = np.sort(np.arange(n) % G).astype(np.int32)
+    dx, dgo, dids = dev(x), dev(go), dev(ids, torch.int32)
+    ref = O.hashgrid_bwd(x, go, scal, 2**lg, L * 2**lg, F)
+    monkeypatch.setattr(ops, "_BINNED_MIN_SAMPLES", 1)
+
+    def check(atomic):
+        monkeypatch.setattr(ops, "_FORCE_ATOMIC_SCATTER", atomic)
+        del library_calls[:]
+        one = ops.hashgrid_bwd(spec, None, dx, dgo)
+        assert one.shape == (L * 2**lg, F) and rel_l2(host(one), ref) < TIGHT
+        many = ops.hashgrid_multi_bwd(spec, G, dids, dx, dgo, present=[True] * G)
+        assert ("nrhip_hashgrid_bwd" in library_calls) == atomic and ("nrhip_hashgrid_bwd_binned" in library_calls) != atomic
+        assert ("nrhip_hashgrid_multi_bwd" in library_calls) == atomic
+        assert ("nrhip_hashgrid_multi_bwd_binned" in library_calls) != atomic
+        for a in range(G):
+            monkeypatch.setattr(ops, "_FORCE_ATOMIC_SCATTER", True)
+            single = ops.hashgrid_bwd(spec, None, dx[dids == a].contiguous(), dgo[dids == a].contiguous())
+            assert many[a].shape == single.shape
+            assert float((many[a] - single).abs().max()) <= 2e-6 * float(single.abs().max()) + 1e-12, a
+
+    check(atomic=True)  # (the multi-grid atomics with run combining)
+    switches.set("NRHIP_MULTI_BWD_RUNS", "0")
+    check(atomic=True)
+    switches.unset("NRHIP_MULTI_BWD_RUNS")
+    for pairs in ("all", "none"):
+        switches.set("NRHIP_BIN_PAIRS", pairs)
+        check(atomic=False)

@@ -204,6 +204,28 @@ def test_hashgrid_multi_bwd_input_per_element(ops, order):
         assert excess(got, ref, A).max() <= 12 + F + L, (sc, excess(got, ref, A).max())
 
 
+@pytest.mark.parametrize("F", [1, 2, 4, 8])
+@pytest.mark.parametrize("half", [False, True], ids=["fp32", "fp16"])
+def test_hashgrid_multi_bwd_input_every_feature_width_and_storage_type(ops, F, half):
+    """the kernel is picked by (F, storage type): the smallest shape that separates the instantiations, same bound"""
+    L, lg, n, G = 2, 8, 257, 3
+    tabs = [synth.hash_table(L * 2**lg, F, seed=520 + 10 * F + i, scale=0.7) for i in range(G)]
+    if half:
+        tabs = [t.astype(np.float16).astype(np.float32) for t in tabs]
+    ids = (np.arange(n) % G).astype(np.int32)
+    x = synth.uniform((n, 3), 0.0, 1.0, 13 + F)
+    spec = ops.GridSpec(L, F, lg, 16, 64)
+    scal = O.hash_scalings(L, 16, 64)
+    go = sharp_gradients(n, L * F, 450 + F, 1.0)
+    ref, A = np.zeros((n, 3)), np.zeros((n, 3))
+    for i in range(G):
+        m = ids == i
+        ref[m], A[m] = O.hashgrid_input_grads(x[m], tabs[i], scal, 2**lg, go[m], with_abs=True)
+    dtabs = [dev(t).to(torch.float16 if half else torch.float32) for t in tabs]
+    got = host(ops.hashgrid_multi_bwd_input(spec, dtabs, dev(ids, torch.int32), dev(x), dev(go)))
+    assert excess(got, ref, A).max() <= 12 + F + L, excess(got, ref, A).max()
+
+
 def _actor_spec(ops, a, A):
     tabs = [torch.zeros((4 * 2**9, 4), device="cuda") for _ in range(A)]
     return ops.ActorSpec(timestamps=dev(a["timestamps"]), positions=dev(a["positions"]),
