@@ -9,14 +9,13 @@ result is a RayBundle of the class passed as ``bundle_cls`` (default: this packa
 inside nerfstudio types)."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
 from torch import Tensor
 
 from .. import _lib
-from ..ops import _chk, _ptr, _stream
+from ..ops import _chk, launch
 from .rays import RayBundle
 
 PERSPECTIVE = 1  # CameraType.PERSPECTIVE.value (cameras/cameras.py:43-55)
@@ -73,8 +72,7 @@ def camera_rays(cameras, camera_indices: Tensor, coords: Tensor, bundle_cls=RayB
     area = torch.empty((R, 1), device=dev)
     norm = torch.empty((R, 1), device=dev)
     times = None if times_tab is None else torch.empty((R, 1), device=dev)
-    _lib.call("nrhip_camera_rays", C.byref(t), _ptr(idx), _ptr(xy), R, _ptr(o), _ptr(d), _ptr(area), _ptr(norm), _ptr(times),
-              _stream())
+    launch("nrhip_camera_rays", t, idx, xy, R, o, d, area, norm, times)
     skip = ("rolling_shutter_time", "time_to_center_pixel", "rs_direction") if rs else ()
     metadata = {k: v[idx] for k, v in md.items() if isinstance(v, Tensor) and k not in skip}
     metadata["directions_norm"] = norm
@@ -103,8 +101,7 @@ def lidar_rays(lidars, lidar_indices: Tensor, points: Tensor, bundle_cls=RayBund
     dist = torch.empty((R, 1), device=dev)
     ret = torch.empty((R, 1), device=dev, dtype=torch.uint8)
     times = None if times_tab is None else torch.empty((R, 1), device=dev)
-    _lib.call("nrhip_lidar_rays", C.byref(t), _ptr(idx), _ptr(pts), pts.shape[1], R, _ptr(o), _ptr(d), _ptr(area), _ptr(dist),
-              _ptr(ret), _ptr(times), _stream())
+    launch("nrhip_lidar_rays", t, idx, pts, pts.shape[1], R, o, d, area, dist, ret, times)
     metadata = {k: v[idx] for k, v in md.items() if isinstance(v, Tensor)}
     metadata.update(directions_norm=dist, is_lidar=torch.ones((R, 1), dtype=torch.bool, device=dev), did_return=ret.bool())
     return bundle_cls(origins=o, directions=d, pixel_area=area, camera_indices=idx[:, None], times=times, metadata=metadata,

@@ -17,8 +17,7 @@ from typing import Dict, Optional
 import torch
 from torch import Tensor
 
-from .. import _lib
-from ..ops import _ptr, _stream
+from ..ops import launch
 
 
 def patch_sample(images: Optional[Tensor], patch_size: int, patch_scale: int, *, uniforms: Optional[Tensor] = None,
@@ -51,9 +50,9 @@ def patch_sample(images: Optional[Tensor], patch_size: int, patch_scale: int, *,
     rays = torch.empty((P * patch_size * patch_size, 3), device=dev, dtype=torch.int64)
     coords = torch.empty((P * patch_size * patch_size, 2), device=dev) if want_coords else None
     patches = None if images is None else torch.empty((P, K, K, c), device=dev, dtype=images.dtype)
-    _lib.call("nrhip_patch_sample", _ptr(src if uniforms is not None else None), _ptr(src if centers is not None else None), P,
-              n, h, w, c, patch_size, patch_scale, _ptr(image_idx), _ptr(images),
-              0 if images is None or images.dtype == torch.float32 else 1, _ptr(rays), _ptr(coords), _ptr(patches), _stream())
+    launch("nrhip_patch_sample", src if uniforms is not None else None, src if centers is not None else None, P, n, h, w, c,
+           patch_size, patch_scale, image_idx, images, 0 if images is None or images.dtype == torch.float32 else 1, rays,
+           coords, patches)
     return rays, coords, patches
 
 
@@ -185,8 +184,8 @@ def lidar_point_sample(lidar: Tensor, points_per_lidar: Tensor, num_rays: int, *
         lidar_idx = lidar_idx.to(device=dev, dtype=torch.int64).contiguous()
     indices = torch.empty((num_rays, 2), device=dev, dtype=torch.int64)
     points = torch.empty((num_rays, lidar.shape[1]), device=dev)
-    _lib.call("nrhip_lidar_point_sample", _ptr(shuffle.contiguous()), _ptr(draws.contiguous()), _ptr(npl), _ptr(lidar_idx),
-              _ptr(lidar), n, rpl, lidar.shape[1], num_rays, _ptr(indices), _ptr(points), _stream())
+    launch("nrhip_lidar_point_sample", shuffle.contiguous(), draws.contiguous(), npl, lidar_idx, lidar, n, rpl,
+           lidar.shape[1], num_rays, indices, points)
     return indices, points
 
 

@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import call
 
 
-def _stream() -> C.c_void_p:
+def _stream() -> C.c_void_p:  # (_stream / _ptr: for tests and scripts that call the library directly; wrappers use launch)
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
@@ -35,6 +35,41 @@ def _chk(t: Tensor, name: str, dtype=torch.float32) -> Tensor:
     if t.dtype != dtype:
         raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _opt(t: Optional[Tensor], name: str, dtype=torch.float32) -> Optional[Tensor]:
+    """an optional per-ray / per-sample argument: None, or the tensor flattened and checked"""
+    return None if t is None else _chk(t.reshape(-1), name, dtype)
+
+
+def _c_args(args: tuple) -> Tuple[list, tuple]:
+    """-> (what the C entry point receives, the arguments themselves).  A tensor (parameters included) goes as its address,
+    None as NULL, a ctypes structure by reference; ints, floats, ctypes arrays and byref objects go as they are.  Nothing is
+    checked here -- ``_chk`` and the wrappers do that.  Whoever holds the pair holds every tensor the addresses point to."""
+    return [a.data_ptr() if isinstance(a, Tensor) else C.byref(a) if isinstance(a, C.Structure) else a for a in args], args
+
+
+def launch(name: str, *args) -> None:
+    """Enqueue entry point ``name`` on the current stream (which it appends to ``args``).  ``args`` holds every tensor until
+    the entry point has returned, a contiguous copy made in the argument list included.  Host-only entry points (workspace
+    and size queries, plans) take no stream: they go through ``call`` with the same conversion."""
+    c_args, keep = _c_args(args)
+    call(name, *c_args, torch.cuda.current_stream().cuda_stream)
+
+
+def _workspace(entry: str, *args, device, dtype) -> Tuple[Tensor, int]:
+    """Ask ``entry`` (a ``*_workspace`` query: args..., int64* out) for its scratch size and allocate it -> (scratch of
+    max(size, 1) elements of ``dtype``: never a NULL address, the size the library asked for)"""
+    need = C.c_int64(0)
+    c_args, keep = _c_args(args)
+    call(entry, *c_args, C.byref(need))
+    return torch.empty((max(need.value, 1),), device=device, dtype=dtype), need.value
+
+
+def _host_ptrs(tensors: Sequence[Optional[Tensor]], n: Optional[int] = None):
+    """host array of ``n`` (default: as many as tensors) data pointers for a ``void* const*`` argument; None -> NULL.  The
+    caller keeps the tensors."""
+    return (C.c_void_p * (len(tensors) if n is None else n))(*[0 if t is None else t.data_ptr() for t in tensors])
 
 
 def hash_scalings(num_levels: int, min_res: int, max_res: int) -> Tensor:
@@ -67,15 +102,17 @@ class GridSpec:
     def table_rows(self) -> int:
         return self.num_levels << self.log2_hashmap_size
 
-    def c_grid(self, table: Tensor) -> _lib.Grid:
-        if table.dtype not in (torch.float32, torch.float16):
-            raise TypeError(f"hash table must be fp32 or fp16, got {table.dtype}")
-        if tuple(table.shape) != (self.table_rows, self.features_per_level):
+    def c_grid(self, table) -> _lib.Grid:
+        """table: the hash table (its shape is checked), or its storage dtype alone"""
+        dtype = table.dtype if isinstance(table, Tensor) else table
+        if dtype not in (torch.float32, torch.float16):
+            raise TypeError(f"hash table must be fp32 or fp16, got {dtype}")
+        if isinstance(table, Tensor) and tuple(table.shape) != (self.table_rows, self.features_per_level):
             raise ValueError(f"hash table shape {tuple(table.shape)} != {(self.table_rows, self.features_per_level)}")
         g = _lib.Grid()
         g.num_levels, g.n_features = self.num_levels, self.features_per_level
         g.log2_table_size = self.log2_hashmap_size
-        g.param_dtype = 1 if table.dtype == torch.float16 else 0
+        g.param_dtype = 1 if dtype == torch.float16 else 0
         sc = self.scalings.tolist()
         for i, v in enumerate(sc):
             g.scalings[i] = v
@@ -149,14 +186,10 @@ def ray_order(origins: Tensor, directions: Tensor, static_scale: float, t_ref: O
     o, d = _chk(origins, "origins"), _chk(directions, "directions")
     out = torch.empty((o.shape[0],), device=o.device, dtype=torch.int32)
     if o.shape[0] > _RAY_ORDER_LARGE:  # many workgroups: the one-workgroup pass costs ~2 us per 1024 rays
-        need = C.c_int64(0)
-        call("nrhip_ray_order_workspace", o.shape[0], int(key_bits), C.byref(need))
-        ws = torch.empty((need.value,), device=o.device, dtype=torch.uint8)
-        call("nrhip_ray_order_large", _ptr(o), _ptr(d), o.shape[0], float(t_ref), float(static_scale), int(key_bits),
-             _ptr(ws), ws.numel(), _ptr(out), _stream())
+        ws, need = _workspace("nrhip_ray_order_workspace", o.shape[0], int(key_bits), device=o.device, dtype=torch.uint8)
+        launch("nrhip_ray_order_large", o, d, o.shape[0], float(t_ref), float(static_scale), int(key_bits), ws, need, out)
         return out
-    call("nrhip_ray_order", _ptr(o), _ptr(d), o.shape[0], float(t_ref), float(static_scale), int(key_bits), _ptr(out),
-         _stream())
+    launch("nrhip_ray_order", o, d, o.shape[0], float(t_ref), float(static_scale), int(key_bits), out)
     return out
 
 
@@ -184,11 +217,8 @@ def _table_grad_workspace(c_grid, n_samples: int, device) -> Optional[Tensor]:
     """Scratch for the atomics-free table gradients; None -> use the atomic entry point."""
     if not _binned_table_grad(n_samples)[0]:
         return None
-    need = C.c_int64(0)
-    call("nrhip_encode_bwd_binned_workspace", C.byref(c_grid), int(n_samples), C.byref(need))
-    if need.value <= 0:
-        return None
-    return torch.empty((need.value,), device=device, dtype=torch.uint8)
+    ws, need = _workspace("nrhip_encode_bwd_binned_workspace", c_grid, int(n_samples), device=device, dtype=torch.uint8)
+    return ws if need > 0 else None
 
 
 def hashgrid_fwd(spec: GridSpec, table: Tensor, x: Tensor) -> Tensor:
@@ -197,8 +227,7 @@ def hashgrid_fwd(spec: GridSpec, table: Tensor, x: Tensor) -> Tensor:
         raise ValueError(f"x must be [N,3], got {tuple(x.shape)}")  # encodings.py:428
     table = table if table.is_contiguous() else table.contiguous()
     out = torch.empty((x.shape[0], spec.out_dim), device=x.device, dtype=torch.float32)
-    g = spec.c_grid(table)
-    call("nrhip_hashgrid_fwd", C.byref(g), _ptr(table), _ptr(x), x.shape[0], _ptr(out), _stream())
+    launch("nrhip_hashgrid_fwd", spec.c_grid(table), table, x, x.shape[0], out)
     return out
 
 
@@ -208,10 +237,9 @@ def hashgrid_bwd(spec: GridSpec, table_like: Tensor, x: Tensor, grad_out: Tensor
     g = spec.c_grid(gt)
     ws = _table_grad_workspace(g, x.shape[0], x.device)
     if ws is not None:  # overwrite = 1: the partition writes every element of the gradient, no zero-fill
-        call("nrhip_hashgrid_bwd_binned", C.byref(g), _ptr(x), _ptr(grad_out), x.shape[0], _ptr(gt), 1, _ptr(ws),
-             ws.numel(), _stream())
+        launch("nrhip_hashgrid_bwd_binned", g, x, grad_out, x.shape[0], gt, 1, ws, ws.numel())
     else:
-        call("nrhip_hashgrid_bwd", C.byref(g), _ptr(x), _ptr(grad_out), x.shape[0], _ptr(gt.zero_()), _stream())
+        launch("nrhip_hashgrid_bwd", g, x, grad_out, x.shape[0], gt.zero_())
     return gt
 
 
@@ -235,10 +263,7 @@ def hashgrid_multi_fwd(spec: GridSpec, tables: Sequence[Tensor], grid_id: Tensor
     x, grid_id = _chk(x, "x"), _chk(grid_id, "grid_id", torch.int32)
     tables = [_chk(t, "table", tables[0].dtype) for t in tables]  # fp32 or fp16 storage, one dtype per call
     out = torch.empty((x.shape[0], spec.out_dim), device=x.device, dtype=torch.float32)
-    g = spec.c_grid(tables[0])
-    ptrs = _ptr_array(tables)
-    call("nrhip_hashgrid_multi_fwd", C.byref(g), _ptr(ptrs), len(tables), _ptr(grid_id), _ptr(x), x.shape[0], _ptr(out),
-         _stream())
+    launch("nrhip_hashgrid_multi_fwd", spec.c_grid(tables[0]), _ptr_array(tables), len(tables), grid_id, x, x.shape[0], out)
     return out
 
 
@@ -284,16 +309,14 @@ def _multi_bwd_block(spec: GridSpec, n_grids: int, grid_id: Tensor, x: Tensor, g
     if binned:
         # the radix partition over (slot, level, slice) (csrc/encode_bwd_binned.hip, MultiSrc): no memory-side atomics, every
         # element of the block written by the partition (no zero-fill), fp16-storage grids get their fp16 gradient directly
-        g = spec.c_grid(torch.empty((spec.table_rows, spec.features_per_level), device="meta"))  # (the shape only)
-        need = C.c_int64(0)
-        call("nrhip_hashgrid_multi_bwd_binned_workspace", C.byref(g), n_slots, n, C.byref(need))
-        if need.value > 0:
+        g = spec.c_grid(torch.float32)  # (levels and sizes only: the gradient's type is the `half` flag of the call)
+        ws, need = _workspace("nrhip_hashgrid_multi_bwd_binned_workspace", g, n_slots, n, device=x.device, dtype=torch.uint8)
+        if need > 0:
             block = torch.empty((n_slots, spec.table_rows, spec.features_per_level), device=x.device,
                                 dtype=torch.float16 if half else torch.float32)
-            ws = torch.empty((need.value,), device=x.device, dtype=torch.uint8)
             slot32 = _slot_table(slots, x.device, torch.int32)
-            call("nrhip_hashgrid_multi_bwd_binned", C.byref(g), n_grids, _ptr(grid_id), _ptr(slot32), n_slots, _ptr(x),
-                 _ptr(grad_out), n, _ptr(block), 1 if half else 0, _ptr(ws), ws.numel(), _stream())
+            launch("nrhip_hashgrid_multi_bwd_binned", g, n_grids, grid_id, slot32, n_slots, x, grad_out, n, block,
+                   1 if half else 0, ws, need)
             return block if block.dtype == out_dtype else block.to(out_dtype)
     # one zero-filled block for all touched grids (a scene has ~100 actor grids: one fill, not one per grid)
     flat = torch.zeros((n_slots, spec.table_rows, spec.features_per_level), device=x.device, dtype=torch.float32)
@@ -302,8 +325,7 @@ def _multi_bwd_block(spec: GridSpec, n_grids: int, grid_id: Tensor, x: Tensor, g
     # a torch.tensor(list, device=...) here is a pageable host->device copy, i.e. a stream synchronisation per backward
     slot = _slot_table(slots, x.device, torch.int64)
     ptrs = torch.where(slot >= 0, slot * (flat[0].numel() * 4) + flat.data_ptr(), torch.zeros_like(slot))
-    call("nrhip_hashgrid_multi_bwd", C.byref(g), n_grids, _ptr(grid_id), _ptr(x), _ptr(grad_out), x.shape[0], _ptr(ptrs),
-         _stream())
+    launch("nrhip_hashgrid_multi_bwd", g, n_grids, grid_id, x, grad_out, x.shape[0], ptrs)
     # fp16-storage grids: autograd wants the parameter's dtype -- ONE cast of the block
     return flat if out_dtype == torch.float32 else flat.to(out_dtype)
 
@@ -327,26 +349,22 @@ def hashgrid_multi_bwd_input(spec: GridSpec, tables: Sequence[Tensor], grid_id: 
     x, grid_id, grad_out = _chk(x, "x"), _chk(grid_id, "grid_id", torch.int32), _chk(grad_out, "grad_out")
     tables = [_chk(t, "table", tables[0].dtype) for t in tables]
     gx = torch.empty_like(x)
-    g = spec.c_grid(tables[0])
-    ptrs = _ptr_array(tables)
-    call("nrhip_hashgrid_multi_bwd_input", C.byref(g), _ptr(ptrs), len(tables), _ptr(grid_id), _ptr(x), _ptr(grad_out),
-         x.shape[0], _ptr(gx), _stream())
+    launch("nrhip_hashgrid_multi_bwd_input", spec.c_grid(tables[0]), _ptr_array(tables), len(tables), grid_id, x, grad_out,
+           x.shape[0], gx)
     return gx
 
 
 def hashgrid_bwd_input(spec: GridSpec, table: Tensor, x: Tensor, grad_out: Tensor) -> Tensor:
     x, grad_out = _chk(x, "x"), _chk(grad_out, "grad_out")
     gx = torch.empty_like(x)
-    g = spec.c_grid(table)
-    call("nrhip_hashgrid_bwd_input", C.byref(g), _ptr(table), _ptr(x), _ptr(grad_out), x.shape[0], _ptr(gx), _stream())
+    launch("nrhip_hashgrid_bwd_input", spec.c_grid(table), table, x, grad_out, x.shape[0], gx)
     return gx
 
 
 def encode_fwd(spec: GridSpec, table: Tensor, static_scale: float, origins, directions, pixel_area, starts, ends):
     r, keep = _c_rays(origins, directions, pixel_area, starts, ends)
     out = torch.empty((r.n_rays * r.n_samples, spec.out_dim), device=origins.device, dtype=torch.float32)
-    g = spec.c_grid(table)
-    call("nrhip_encode_fwd", C.byref(g), _ptr(table), float(static_scale), C.byref(r), _ptr(out), _stream())
+    launch("nrhip_encode_fwd", spec.c_grid(table), table, float(static_scale), r, out)
     return out
 
 
@@ -363,17 +381,14 @@ def encode_bwd(spec: GridSpec, static_scale: float, origins, directions, pixel_a
     g = spec.c_grid(gt)
     ws = _table_grad_workspace(g, n, origins.device)
     if ws is not None and half:  # the fp16 gradient of an fp16-storage table, written by the partition itself
-        call("nrhip_encode_bwd_binned_f16", C.byref(g), float(static_scale), C.byref(r), _ptr(grad_out), _ptr(gt), _ptr(ws),
-             ws.numel(), _stream())
+        launch("nrhip_encode_bwd_binned_f16", g, float(static_scale), r, grad_out, gt, ws, ws.numel())
     elif ws is not None:  # overwrite = 1: the partition writes every element of the gradient, no zero-fill
-        call("nrhip_encode_bwd_binned", C.byref(g), float(static_scale), C.byref(r), _ptr(grad_out), _ptr(gt), 1,
-             _ptr(ws), ws.numel(), _stream())
+        launch("nrhip_encode_bwd_binned", g, float(static_scale), r, grad_out, gt, 1, ws, ws.numel())
     else:  # tables too large to cut into LDS slices, or a tiny batch: memory-side atomics (fp32 only)
         if gt.dtype != torch.float32:
             gt = torch.empty((spec.table_rows, spec.features_per_level), device=origins.device, dtype=torch.float32)
             g = spec.c_grid(gt)
-        call("nrhip_encode_bwd", C.byref(g), float(static_scale), C.byref(r), _ptr(grad_out), _ptr(gt.zero_()),
-             _stream())
+        launch("nrhip_encode_bwd", g, float(static_scale), r, grad_out, gt.zero_())
     return gt
 
 
@@ -388,15 +403,14 @@ def encode_bwd_rays(spec: GridSpec, table: Tensor, static_scale: float, origins,
         raise ValueError(f"grad_out has {grad_out.numel()} elements, expected {r.n_rays * r.n_samples * spec.out_dim}")
     g = spec.c_grid(table)
     out = torch.empty((2, r.n_rays, 3), device=origins.device, dtype=torch.float32)
-    call("nrhip_encode_bwd_rays", C.byref(g), _ptr(_chk(table, "table", table.dtype)), float(static_scale), C.byref(r),
-         _ptr(grad_out), _ptr(out[0]), _ptr(out[1]), _stream())
+    launch("nrhip_encode_bwd_rays", g, _chk(table, "table", table.dtype), float(static_scale), r, grad_out, out[0], out[1])
     return out[0], out[1]
 
 
 def sh4_fwd(dirs01: Tensor) -> Tensor:
     d = _chk(dirs01, "dirs")
     out = torch.empty((d.shape[0], 16), device=d.device, dtype=torch.float32)
-    call("nrhip_sh4_fwd", _ptr(d), d.shape[0], _ptr(out), _stream())
+    launch("nrhip_sh4_fwd", d, d.shape[0], out)
     return out
 
 
@@ -410,8 +424,20 @@ def mlp_fwd(x: Tensor, weights, biases, save_hidden: bool = False):
     hidden = None
     if save_hidden and m.num_layers > 1:
         hidden = torch.empty((n, (m.num_layers - 1) * m.hidden_dim), device=x.device, dtype=torch.float32)
-    call("nrhip_mlp_fwd", C.byref(m), _ptr(x), n, _ptr(y), _ptr(hidden), _stream())
+    launch("nrhip_mlp_fwd", m, x, n, y, hidden)
     return (y, hidden) if save_hidden else y
+
+
+def _mlp_grads(m: _lib.Mlp, n: int, weights, biases, device):
+    """what both MLP backward entry points write into: -> (weight gradients, bias gradients (None where there is no bias),
+    the C arguments behind them: the two host pointer arrays, the workspace and its size)"""
+    # one zero-filled buffer for every weight / bias gradient of the MLP (one fill launch instead of 2 per layer)
+    sizes = [w.numel() for w in weights] + [0 if b is None else b.numel() for b in biases]
+    views = torch.split(torch.zeros((sum(sizes),), device=device, dtype=torch.float32), sizes)
+    gws = [v.view_as(w) for v, w in zip(views[:len(weights)], weights)]
+    gbs = [None if b is None else v.view_as(b) for v, b in zip(views[len(weights):], biases)]
+    ws, need = _workspace("nrhip_mlp_bwd_workspace", m, n, device=device, dtype=torch.float32)
+    return gws, gbs, (_host_ptrs(gws, _lib.MAX_LAYERS), _host_ptrs(gbs, _lib.MAX_LAYERS), ws, need)
 
 
 def mlp_bwd(x: Tensor, hidden: Optional[Tensor], grad_y: Tensor, weights, biases, need_grad_x: bool = True):
@@ -419,19 +445,8 @@ def mlp_bwd(x: Tensor, hidden: Optional[Tensor], grad_y: Tensor, weights, biases
     m, keep = _c_mlp(weights, biases)
     n = x.shape[0]
     gx = torch.empty_like(x) if need_grad_x else None
-    # one zero-filled buffer for every weight / bias gradient of the MLP (one fill launch instead of 2 per layer)
-    sizes = [w.numel() for w in weights] + [0 if b is None else b.numel() for b in biases]
-    flat = torch.zeros((sum(sizes),), device=x.device, dtype=torch.float32)
-    views = torch.split(flat, sizes)
-    gws = [v.view_as(w) for v, w in zip(views[:len(weights)], weights)]
-    gbs = [None if b is None else v.view_as(b) for v, b in zip(views[len(weights):], biases)]
-    need = C.c_int64(0)
-    call("nrhip_mlp_bwd_workspace", C.byref(m), n, C.byref(need))
-    ws = torch.empty((max(need.value, 1),), device=x.device, dtype=torch.float32)
-    pw = (C.c_void_p * _lib.MAX_LAYERS)(*[g.data_ptr() for g in gws])
-    pb = (C.c_void_p * _lib.MAX_LAYERS)(*[(0 if g is None else g.data_ptr()) for g in gbs])
-    call("nrhip_mlp_bwd", C.byref(m), _ptr(x), _ptr(hidden), _ptr(grad_y), n, _ptr(gx),
-         C.cast(pw, C.POINTER(C.c_void_p)), C.cast(pb, C.POINTER(C.c_void_p)), _ptr(ws), need.value, _stream())
+    gws, gbs, out = _mlp_grads(m, n, weights, biases, x.device)
+    launch("nrhip_mlp_bwd", m, x, hidden, grad_y, n, gx, *out)
     return gx, gws, gbs
 
 
@@ -450,18 +465,8 @@ def field_feature_bwd(x: Tensor, hidden: Tensor, grad_feature: Tensor, grad_geo0
     if grad_geo0.shape[0] != n or grad_feature.shape != (n, 32):
         raise ValueError("field_feature_bwd: grad_feature [N,32] and grad_geo0 [N] expected")
     g_geo = torch.empty((n, 33), device=x.device, dtype=torch.float32)
-    sizes = [w.numel() for w in weights] + [b.numel() for b in biases]
-    flat = torch.zeros((sum(sizes),), device=x.device, dtype=torch.float32)
-    views = torch.split(flat, sizes)
-    gws = [v.view_as(w) for v, w in zip(views[:len(weights)], weights)]
-    gbs = [v.view_as(b) for v, b in zip(views[len(weights):], biases)]
-    need = C.c_int64(0)
-    call("nrhip_mlp_bwd_workspace", C.byref(m), n, C.byref(need))
-    ws = torch.empty((max(need.value, 1),), device=x.device, dtype=torch.float32)
-    pw = (C.c_void_p * _lib.MAX_LAYERS)(*[g.data_ptr() for g in gws])
-    pb = (C.c_void_p * _lib.MAX_LAYERS)(*[g.data_ptr() for g in gbs])
-    call("nrhip_field_feature_bwd", C.byref(m), _ptr(x), _ptr(hidden), _ptr(grad_feature), _ptr(grad_geo0), n, _ptr(g_geo),
-         C.cast(pw, C.POINTER(C.c_void_p)), C.cast(pb, C.POINTER(C.c_void_p)), _ptr(ws), need.value, _stream())
+    gws, gbs, out = _mlp_grads(m, n, weights, biases, x.device)
+    launch("nrhip_field_feature_bwd", m, x, hidden, grad_feature, grad_geo0, n, g_geo, *out)
     return g_geo, gws, gbs
 
 
@@ -509,14 +514,9 @@ _EVAL_TABLES: dict = {}  # (data_ptr, version, dtype, shape, grid key) -> (eval 
 def eval_layout_plan(spec: GridSpec, table_dtype=torch.float32):
     """host logic: -> (layout ctypes array [L*4] = {mulY, mulZ, mask, row0} per level, rows of the eval table, number of
     levels that get a shadow copy)"""
-    g = _lib.Grid()
-    g.num_levels, g.n_features, g.log2_table_size = spec.num_levels, spec.features_per_level, spec.log2_hashmap_size
-    g.param_dtype = 1 if table_dtype == torch.float16 else 0
-    for i, v in enumerate(spec.scalings.tolist()):
-        g.scalings[i] = v
     lay = (C.c_uint32 * (4 * spec.num_levels))()
     rows = C.c_int64(0)
-    call("nrhip_eval_layout_plan", C.byref(g), lay, C.byref(rows))
+    call("nrhip_eval_layout_plan", C.byref(spec.c_grid(table_dtype)), lay, C.byref(rows))
     n_shadow = sum(1 for l in range(spec.num_levels) if lay[4 * l] != 2654435761)
     return lay, rows.value, n_shadow
 
@@ -535,8 +535,7 @@ def eval_table(spec: GridSpec, table: Tensor):
             hit = (None, None)
         else:
             out = torch.empty((rows, spec.features_per_level), device=table.device, dtype=table.dtype)
-            g = spec.c_grid(table)
-            call("nrhip_eval_layout_build", C.byref(g), _ptr(table), lay, _ptr(out), _stream())
+            launch("nrhip_eval_layout_build", spec.c_grid(table), table, lay, out)
             hit = (out, lay)
         for k in [k for k in _EVAL_TABLES if k[0] == key[0] and k != key]:  # older versions of the same parameter
             del _EVAL_TABLES[k]
@@ -564,7 +563,7 @@ def field_fwd(fs: FieldSpec, origins, directions, pixel_area, starts, ends, orde
     feature = torch.empty((R, S, 32), device=dev, dtype=torch.float32)
     sdf = torch.empty((R, S), device=dev, dtype=torch.float32)
     alpha = torch.empty((R, S), device=dev, dtype=torch.float32)
-    call("nrhip_field_fwd", C.byref(f), C.byref(r), _ptr(feature), _ptr(sdf), _ptr(alpha), _stream())
+    launch("nrhip_field_fwd", f, r, feature, sdf, alpha)
     return feature, sdf, alpha
 
 
@@ -587,12 +586,17 @@ def field_fwd_train(fs: FieldSpec, origins, directions, pixel_area, starts, ends
         ov, rows, dirs = _chk(ov.reshape(-1), "ovr_row", torch.int32), _chk(rows, "ovr_rows"), _chk(dirs, "ovr_dirs")
         if ov.shape[0] != n or rows.dim() != 2 or rows.shape[1] != LF or dirs.shape != (rows.shape[0], 3):
             raise ValueError(f"field_fwd_train: override = (int32 [N], [P,{LF}], [P,3])")
-        call("nrhip_field_fwd_train_ovr", C.byref(f), C.byref(r), _ptr(ov), _ptr(rows), _ptr(dirs), _ptr(feature), _ptr(sdf),
-             _ptr(head), _ptr(enc), _ptr(hg), _ptr(xf), _ptr(hf), _stream())
+        launch("nrhip_field_fwd_train_ovr", f, r, ov, rows, dirs, feature, sdf, head, enc, hg, xf, hf)
     else:
-        call("nrhip_field_fwd_train", C.byref(f), C.byref(r), _ptr(feature), _ptr(sdf), _ptr(head), _ptr(enc), _ptr(hg),
-             _ptr(xf), _ptr(hf), _stream())
+        launch("nrhip_field_fwd_train", f, r, feature, sdf, head, enc, hg, xf, hf)
     return (feature, sdf, head), (enc, hg, xf, hf)
+
+
+def _render_outputs(R: int, S: int, device, return_weights: bool, out=None):
+    """-> features [R,32], depth [R,1], accumulation [R,1] (the caller's ``out`` when given), weights [R,S] or None"""
+    mk = lambda c: torch.empty((R, c), device=device, dtype=torch.float32)  # noqa: E731
+    feats, depth, acc = (mk(32), mk(1), mk(1)) if out is None else out
+    return feats, depth, acc, (mk(S) if return_weights else None)
 
 
 def render_fwd(fs: FieldSpec, origins, directions, pixel_area, starts, ends, return_weights: bool = False,
@@ -603,17 +607,8 @@ def render_fwd(fs: FieldSpec, origins, directions, pixel_area, starts, ends, ret
     order: processing order from ``ray_order`` (locality hint; outputs stay in batch order)."""
     r, keep = _c_rays(origins, directions, pixel_area, starts, ends, order)
     f, keep2 = fs.c_field(eval_layout=not fs.table.requires_grad)
-    R, S = r.n_rays, r.n_samples
-    dev = origins.device
-    if out is None:
-        feats = torch.empty((R, 32), device=dev, dtype=torch.float32)
-        depth = torch.empty((R, 1), device=dev, dtype=torch.float32)
-        acc = torch.empty((R, 1), device=dev, dtype=torch.float32)
-    else:
-        feats, depth, acc = out
-    w = torch.empty((R, S), device=dev, dtype=torch.float32) if return_weights else None
-    call("nrhip_render_fwd_ex", C.byref(f), C.byref(r), _ptr(feats), _ptr(depth), _ptr(acc), _ptr(w),
-         float(early_stop_eps), _stream())
+    feats, depth, acc, w = _render_outputs(r.n_rays, r.n_samples, origins.device, return_weights, out)
+    launch("nrhip_render_fwd_ex", f, r, feats, depth, acc, w, float(early_stop_eps))
     return (feats, depth, acc, w) if return_weights else (feats, depth, acc)
 
 
@@ -626,15 +621,9 @@ def render_fwd_actors(fs: FieldSpec, spec: "ActorSpec", cand, origins, direction
     f, keep2 = fs.c_field()
     a, keep3 = spec.c_actors()
     cnt, act, w2b, _ = cand
-    R, S = r.n_rays, r.n_samples
-    dev = origins.device
-    feats = torch.empty((R, 32), device=dev, dtype=torch.float32)
-    depth = torch.empty((R, 1), device=dev, dtype=torch.float32)
-    acc = torch.empty((R, 1), device=dev, dtype=torch.float32)
-    w = torch.empty((R, S), device=dev, dtype=torch.float32) if return_weights else None
-    work = torch.empty((R + 4,), device=dev, dtype=torch.int32)
-    call("nrhip_render_fwd_actors", C.byref(f), C.byref(a), C.byref(r), _ptr(cnt), _ptr(act), _ptr(w2b), _ptr(feats),
-         _ptr(depth), _ptr(acc), _ptr(w), float(early_stop_eps), _ptr(work), _stream())
+    feats, depth, acc, w = _render_outputs(r.n_rays, r.n_samples, origins.device, return_weights)
+    work = torch.empty((r.n_rays + 4,), device=origins.device, dtype=torch.int32)
+    launch("nrhip_render_fwd_actors", f, a, r, cnt, act, w2b, feats, depth, acc, w, float(early_stop_eps), work)
     return (feats, depth, acc, w) if return_weights else (feats, depth, acc)
 
 
@@ -643,7 +632,7 @@ def render_weight_from_alpha(alphas: Tensor):
     a = _chk(alphas, "alphas")
     R, S = a.shape
     w, t = torch.empty_like(a), torch.empty_like(a)
-    call("nrhip_render_weight_from_alpha", _ptr(a), R, S, _ptr(w), _ptr(t), _stream())
+    launch("nrhip_render_weight_from_alpha", a, R, S, w, t)
     return w, t
 
 
@@ -651,7 +640,7 @@ def render_weight_from_alpha_bwd(alphas, grad_w, grad_t=None):
     a, gw = _chk(alphas, "alphas"), _chk(grad_w, "grad_w")
     gt = None if grad_t is None else _chk(grad_t, "grad_t")
     ga = torch.empty_like(a)
-    call("nrhip_render_weight_from_alpha_bwd", _ptr(a), _ptr(gw), _ptr(gt), a.shape[0], a.shape[1], _ptr(ga), _stream())
+    launch("nrhip_render_weight_from_alpha_bwd", a, gw, gt, a.shape[0], a.shape[1], ga)
     return ga
 
 
@@ -659,7 +648,7 @@ def render_weight_from_density(t_starts, t_ends, sigmas):
     s, e, sg = _chk(t_starts, "t_starts"), _chk(t_ends, "t_ends"), _chk(sigmas, "sigmas")
     R, S = sg.shape
     w, t, a = torch.empty_like(sg), torch.empty_like(sg), torch.empty_like(sg)
-    call("nrhip_render_weight_from_density", _ptr(s), _ptr(e), _ptr(sg), R, S, _ptr(w), _ptr(t), _ptr(a), _stream())
+    launch("nrhip_render_weight_from_density", s, e, sg, R, S, w, t, a)
     return w, t, a
 
 
@@ -667,8 +656,7 @@ def render_weight_from_density_bwd(t_starts, t_ends, sigmas, grad_w):
     s, e, sg, gw = (_chk(v, n) for v, n in ((t_starts, "t_starts"), (t_ends, "t_ends"), (sigmas, "sigmas"),
                                             (grad_w, "grad_w")))
     gs = torch.empty_like(sg)
-    call("nrhip_render_weight_from_density_bwd", _ptr(s), _ptr(e), _ptr(sg), _ptr(gw), sg.shape[0], sg.shape[1],
-         _ptr(gs), _stream())
+    launch("nrhip_render_weight_from_density_bwd", s, e, sg, gw, sg.shape[0], sg.shape[1], gs)
     return gs
 
 
@@ -677,12 +665,12 @@ def accumulate_along_rays(weights, values=None):
     R, S = w.shape
     if values is None:
         out = torch.empty((R, 1), device=w.device, dtype=torch.float32)
-        call("nrhip_accumulate_along_rays", _ptr(w), _ptr(None), R, S, 1, _ptr(out), _stream())
+        launch("nrhip_accumulate_along_rays", w, None, R, S, 1, out)
         return out
     v = _chk(values, "values")
     Cc = v.shape[-1]
     out = torch.empty((R, Cc), device=w.device, dtype=torch.float32)
-    call("nrhip_accumulate_along_rays", _ptr(w), _ptr(v), R, S, Cc, _ptr(out), _stream())
+    launch("nrhip_accumulate_along_rays", w, v, R, S, Cc, out)
     return out
 
 
@@ -693,7 +681,7 @@ def composite_fwd(weights, features, starts, ends):
     of = torch.empty((R, Cc), device=w.device, dtype=torch.float32)
     od = torch.empty((R, 1), device=w.device, dtype=torch.float32)
     oa = torch.empty((R, 1), device=w.device, dtype=torch.float32)
-    call("nrhip_composite_fwd", _ptr(w), _ptr(f), _ptr(s), _ptr(e), R, S, Cc, _ptr(of), _ptr(od), _ptr(oa), _stream())
+    launch("nrhip_composite_fwd", w, f, s, e, R, S, Cc, of, od, oa)
     return of, od, oa
 
 
@@ -715,29 +703,27 @@ def lidar_carving(starts: Tensor, ends: Tensor, is_lidar: Tensor, did_return: Op
     close = torch.empty((R, S), dtype=torch.bool, device=dev) if want_mask else None
     loss = torch.empty((R,), dtype=torch.float32, device=dev) if w is not None else None
     gw = torch.empty((R, S), dtype=torch.float32, device=dev) if (w is not None and want_grad) else None
-    call("nrhip_lidar_carving", _ptr(starts), _ptr(ends), starts.stride(0), _ptr(w), _ptr(lid), _ptr(ret), _ptr(dist),
-         float(carving_epsilon), float(non_return_lidar_distance), R, S, _ptr(close), _ptr(loss), _ptr(gw), _stream())
+    launch("nrhip_lidar_carving", starts, ends, starts.stride(0), w, lid, ret, dist, float(carving_epsilon),
+           float(non_return_lidar_distance), R, S, close, loss, gw)
     return close, loss, gw
 
 
 def embedding_lerp(weight: Tensor, idx_lo: Tensor, idx_hi: Optional[Tensor] = None, frac: Optional[Tensor] = None) -> Tensor:
     """out[r] = weight[idx_lo[r]] * (1 - frac[r]) + weight[idx_hi[r]] * frac[r]   (idx_hi None: weight[idx_lo])"""
     w, lo = _chk(weight, "weight"), _chk(idx_lo.reshape(-1), "idx_lo", torch.int64)
-    hi = None if idx_hi is None else _chk(idx_hi.reshape(-1), "idx_hi", torch.int64)
-    fr = None if frac is None else _chk(frac.reshape(-1), "frac")
+    hi = _opt(idx_hi, "idx_hi", torch.int64)
+    fr = _opt(frac, "frac")
     out = torch.empty((lo.shape[0], w.shape[1]), dtype=torch.float32, device=w.device)
-    call("nrhip_embedding_lerp_fwd", _ptr(w), _ptr(lo), _ptr(hi), _ptr(fr), lo.shape[0], w.shape[0], w.shape[1], _ptr(out),
-         _stream())
+    launch("nrhip_embedding_lerp_fwd", w, lo, hi, fr, lo.shape[0], w.shape[0], w.shape[1], out)
     return out
 
 
 def embedding_lerp_bwd(g_out: Tensor, idx_lo, idx_hi, frac, n_embed: int) -> Tensor:
     g, lo = _chk(g_out, "g_out"), _chk(idx_lo.reshape(-1), "idx_lo", torch.int64)
-    hi = None if idx_hi is None else _chk(idx_hi.reshape(-1), "idx_hi", torch.int64)
-    fr = None if frac is None else _chk(frac.reshape(-1), "frac")
+    hi = _opt(idx_hi, "idx_hi", torch.int64)
+    fr = _opt(frac, "frac")
     gw = torch.zeros((n_embed, g.shape[1]), dtype=torch.float32, device=g.device)
-    call("nrhip_embedding_lerp_bwd", _ptr(g), _ptr(lo), _ptr(hi), _ptr(fr), lo.shape[0], n_embed, g.shape[1], _ptr(gw),
-         _stream())
+    launch("nrhip_embedding_lerp_bwd", g, lo, hi, fr, lo.shape[0], n_embed, g.shape[1], gw)
     return gw
 
 
@@ -747,20 +733,19 @@ def accumulate_along_rays_bwd(weights, values, g_out, need_grad_weights=True, ne
     R, S, Cc = v.shape
     gw = torch.empty_like(w) if need_grad_weights else None
     gv = torch.empty_like(v) if need_grad_values else None
-    call("nrhip_accumulate_along_rays_bwd", _ptr(w), _ptr(v), _ptr(g), R, S, Cc, _ptr(gw), _ptr(gv), _stream())
+    launch("nrhip_accumulate_along_rays_bwd", w, v, g, R, S, Cc, gw, gv)
     return gw, gv
 
 
 def composite_bwd(weights, features, starts, ends, g_feat, g_depth=None, g_acc=None, need_grad_features=True):
     w, f, s, e, gf = (_chk(v, n) for v, n in ((weights, "weights"), (features, "features"), (starts, "starts"),
                                               (ends, "ends"), (g_feat, "g_feat")))
-    gd = None if g_depth is None else _chk(g_depth.reshape(-1), "g_depth")
-    ga = None if g_acc is None else _chk(g_acc.reshape(-1), "g_acc")
+    gd = _opt(g_depth, "g_depth")
+    ga = _opt(g_acc, "g_acc")
     R, S, Cc = f.shape
     gw = torch.empty_like(w)
     gfe = torch.empty_like(f) if need_grad_features else None
-    call("nrhip_composite_bwd", _ptr(w), _ptr(f), _ptr(s), _ptr(e), _ptr(gf), _ptr(gd), _ptr(ga), R, S, Cc, _ptr(gw),
-         _ptr(gfe), _stream())
+    launch("nrhip_composite_bwd", w, f, s, e, gf, gd, ga, R, S, Cc, gw, gfe)
     return gw, gfe
 
 
@@ -789,7 +774,7 @@ def proposal_density_fwd(ps: ProposalSpec, origins, directions, pixel_area, star
     dens = torch.empty((r.n_rays, r.n_samples), device=origins.device, dtype=torch.float32)
     lf = (torch.empty((ps.grid.num_levels, r.n_rays * r.n_samples), device=origins.device, dtype=torch.float32)
           if save_features else None)
-    call("nrhip_proposal_density_fwd", C.byref(p), C.byref(r), _ptr(dens), _ptr(lf), _stream())
+    launch("nrhip_proposal_density_fwd", p, r, dens, lf)
     return (dens, lf) if save_features else dens
 
 
@@ -801,30 +786,28 @@ def proposal_density_bwd(ps: ProposalSpec, origins, directions, pixel_area, star
     ws = _table_grad_workspace(p.grid, r.n_rays * r.n_samples, origins.device)
     if ws is not None:
         gt = torch.empty((ps.grid.table_rows, 1), device=origins.device, dtype=torch.float32)
-        call("nrhip_proposal_density_bwd_binned", C.byref(p), C.byref(r), _ptr(_chk(density, "density")),
-             _ptr(level_features), _ptr(_chk(grad_density, "grad_density")), _ptr(gt), _ptr(gdec), 1, _ptr(ws),
-             ws.numel(), _stream())
+        launch("nrhip_proposal_density_bwd_binned", p, r, _chk(density, "density"), level_features,
+               _chk(grad_density, "grad_density"), gt, gdec, 1, ws, ws.numel())
     else:
         if ps.table.dtype != torch.float32:  # the atomic kernel recomputes the features from an fp32 table: small batches only
             ps32 = ProposalSpec(ps.grid, ps.table.float(), ps.static_scale, ps.decoder_weight)  # (alive until the launch)
             p, keep2 = ps32.c_prop()
         gt = torch.zeros((ps.grid.table_rows, 1), device=origins.device, dtype=torch.float32)
-        call("nrhip_proposal_density_bwd", C.byref(p), C.byref(r), _ptr(_chk(density, "density")),
-             _ptr(_chk(grad_density, "grad_density")), _ptr(gt), _ptr(gdec), _stream())
+        launch("nrhip_proposal_density_bwd", p, r, _chk(density, "density"), _chk(grad_density, "grad_density"), gt, gdec)
     return gt, gdec
 
 
 def weights_from_density(deltas, densities) -> Tensor:
     d, s = _chk(deltas, "deltas"), _chk(densities, "densities")
     w = torch.empty_like(s)
-    call("nrhip_weights_from_density", _ptr(d), _ptr(s), s.shape[0], s.shape[1], _ptr(w), _stream())
+    launch("nrhip_weights_from_density", d, s, s.shape[0], s.shape[1], w)
     return w
 
 
 def weights_from_density_bwd(deltas, densities, grad_w) -> Tensor:
     d, s, g = _chk(deltas, "deltas"), _chk(densities, "densities"), _chk(grad_w, "grad_w")
     gs = torch.empty_like(s)
-    call("nrhip_weights_from_density_bwd", _ptr(d), _ptr(s), _ptr(g), s.shape[0], s.shape[1], _ptr(gs), _stream())
+    launch("nrhip_weights_from_density_bwd", d, s, g, s.shape[0], s.shape[1], gs)
     return gs
 
 
@@ -832,13 +815,12 @@ def power_sampler(nears: Optional[Tensor], fars: Tensor, num_samples: int, lam: 
                   t_rand: Optional[Tensor] = None, last_edge: float = 0.0):
     """-> spacing bins, euclidean bins [R,S+1]; last_edge > 0 sets the last euclidean edge (the model's sky stretch)"""
     f = _chk(fars.reshape(-1), "fars")
-    n = None if nears is None else _chk(nears.reshape(-1), "nears")
+    n = _opt(nears, "nears")
     R = f.shape[0]
     tr = None if t_rand is None else _chk(t_rand, "t_rand")
     sp = torch.empty((R, num_samples + 1), device=f.device, dtype=torch.float32)
     eu = torch.empty_like(sp)
-    call("nrhip_power_sampler", _ptr(n), _ptr(f), R, num_samples, float(lam), float(scaling), _ptr(tr),
-         float(last_edge), _ptr(sp), _ptr(eu), _stream())
+    launch("nrhip_power_sampler", n, f, R, num_samples, float(lam), float(scaling), tr, float(last_edge), sp, eu)
     return sp, eu
 
 
@@ -847,7 +829,7 @@ def power_sampler_ordered(nears: Optional[Tensor], fars: Tensor, num_samples: in
                           last_edge: float = 0.0, t_ref: Optional[float] = None, key_bits: int = 0):
     """``power_sampler`` and ``ray_order`` as one launch -> (spacing bins, euclidean bins [R,S+1], order int32 [R])"""
     f = _chk(fars.reshape(-1), "fars")
-    n = None if nears is None else _chk(nears.reshape(-1), "nears")
+    n = _opt(nears, "nears")
     o, d = _chk(origins, "origins"), _chk(directions, "directions")
     R = f.shape[0]
     if o.shape != (R, 3) or d.shape != (R, 3):
@@ -856,9 +838,8 @@ def power_sampler_ordered(nears: Optional[Tensor], fars: Tensor, num_samples: in
     sp = torch.empty((R, num_samples + 1), device=f.device, dtype=torch.float32)
     eu = torch.empty_like(sp)
     order = torch.empty((R,), device=f.device, dtype=torch.int32)
-    call("nrhip_power_sampler_ordered", _ptr(n), _ptr(f), R, num_samples, float(lam), float(scaling), _ptr(tr),
-         float(last_edge), _ptr(sp), _ptr(eu), _ptr(o), _ptr(d), float(static_scale if t_ref is None else t_ref),
-         float(static_scale), int(key_bits), _ptr(order), _stream())
+    launch("nrhip_power_sampler_ordered", n, f, R, num_samples, float(lam), float(scaling), tr, float(last_edge), sp, eu, o,
+           d, float(static_scale if t_ref is None else t_ref), float(static_scale), int(key_bits), order)
     return sp, eu, order
 
 
@@ -866,7 +847,7 @@ def pdf_sample(weights, spacing_bins, nears, fars, num_samples, lam=-1.0, scalin
                rand: Optional[Tensor] = None):
     w, b = _chk(weights, "weights"), _chk(spacing_bins, "spacing_bins")
     f = _chk(fars.reshape(-1), "fars")
-    n = None if nears is None else _chk(nears.reshape(-1), "nears")
+    n = _opt(nears, "nears")
     R, Sp = w.shape
     stride = 0
     if rand is not None:
@@ -874,8 +855,8 @@ def pdf_sample(weights, spacing_bins, nears, fars, num_samples, lam=-1.0, scalin
         stride = 0 if rand.numel() == R else num_samples + 1
     sp = torch.empty((R, num_samples + 1), device=w.device, dtype=torch.float32)
     eu = torch.empty_like(sp)
-    call("nrhip_pdf_sample", _ptr(w), _ptr(b), _ptr(n), _ptr(f), R, Sp, num_samples, float(lam), float(scaling),
-         float(histogram_padding), _ptr(rand), stride, _ptr(sp), _ptr(eu), _stream())
+    launch("nrhip_pdf_sample", w, b, n, f, R, Sp, num_samples, float(lam), float(scaling), float(histogram_padding), rand,
+           stride, sp, eu)
     return sp, eu
 
 
@@ -890,8 +871,8 @@ def proposal_sampler_fwd(props: Sequence[ProposalSpec], origins, directions, pix
         raise ValueError("num_samples needs one entry per proposal round plus the final count")
     o, d = _chk(origins, "origins"), _chk(directions, "directions")
     a = _chk(pixel_area.reshape(-1), "pixel_area")
-    f = None if fars is None else _chk(fars.reshape(-1), "fars")
-    n = None if nears is None else _chk(nears.reshape(-1), "nears")
+    f = _opt(fars, "fars")
+    n = _opt(nears, "nears")
     R = o.shape[0]
     cfg = _lib.SamplerCfg()
     cfg.n_rounds = n_rounds
@@ -907,23 +888,15 @@ def proposal_sampler_fwd(props: Sequence[ProposalSpec], origins, directions, pix
     ws = [torch.empty((R, num_samples[i]), device=o.device, dtype=torch.float32) for i in range(n_rounds)]
     sps = [torch.empty((R, num_samples[i] + 1), device=o.device, dtype=torch.float32) for i in range(n_rounds + 1)]
     eus = [torch.empty((R, num_samples[i] + 1), device=o.device, dtype=torch.float32) for i in range(n_rounds + 1)]
-    pw = (C.c_void_p * n_rounds)(*[t.data_ptr() for t in ws])
-    psp = (C.c_void_p * (n_rounds + 1))(*[t.data_ptr() for t in sps])
-    peu = (C.c_void_p * (n_rounds + 1))(*[t.data_ptr() for t in eus])
+    entry, actor_part = "nrhip_proposal_sampler_fwd", ()
     if actor_specs is not None:
         cacts = (_lib.Actors * n_rounds)()
         for i, s in enumerate(actor_specs):
             ca, k = s.c_actors()
             cacts[i] = ca
             keep.append(k)
-        cnt, act, w2b, _ = cand
-        call("nrhip_proposal_sampler_fwd_actors", C.byref(cfg), cprops, cacts, _ptr(cnt), _ptr(act), _ptr(w2b), _ptr(o),
-             _ptr(d), _ptr(a), _ptr(n), _ptr(f), R, C.cast(pw, C.POINTER(C.c_void_p)), C.cast(psp, C.POINTER(C.c_void_p)),
-             C.cast(peu, C.POINTER(C.c_void_p)), _stream())
-        return ws, sps, eus
-    call("nrhip_proposal_sampler_fwd", C.byref(cfg), cprops, _ptr(o), _ptr(d), _ptr(a), _ptr(n), _ptr(f), R,
-         C.cast(pw, C.POINTER(C.c_void_p)), C.cast(psp, C.POINTER(C.c_void_p)), C.cast(peu, C.POINTER(C.c_void_p)),
-         _stream())
+        entry, actor_part = "nrhip_proposal_sampler_fwd_actors", (cacts, *cand[:3])  # (cand_count, cand_actor, cand_w2b)
+    launch(entry, cfg, cprops, *actor_part, o, d, a, n, f, R, _host_ptrs(ws), _host_ptrs(sps), _host_ptrs(eus))
     return ws, sps, eus
 
 
@@ -981,12 +954,11 @@ def actor_prepare(spec: ActorSpec, origins, directions, pixel_area, starts, ends
     act = torch.empty((R, K), dtype=torch.int32, device=dev)  # only the first cnt[r] entries of a row are ever read
     w2b = torch.empty((R, K, 12), dtype=torch.float32, device=dev)
     if edit is None:
-        call("nrhip_actor_prepare", C.byref(a), C.byref(r), _ptr(t), _ptr(cnt), _ptr(act), _ptr(w2b), _ptr(None), _stream())
+        launch("nrhip_actor_prepare", a, r, t, cnt, act, w2b, None)
     else:
         e = _lib.ActorEdit(float(edit.get("lateral", 0.0)), float(edit.get("longitudinal", 0.0)),
                            float(edit.get("height", 0.0)), float(edit.get("rotation", 0.0)), int(edit.get("index", -1)))
-        call("nrhip_actor_prepare_edited", C.byref(a), C.byref(r), _ptr(t), C.byref(e), _ptr(cnt), _ptr(act), _ptr(w2b),
-             _ptr(None), _stream())
+        launch("nrhip_actor_prepare_edited", a, r, t, e, cnt, act, w2b, None)
     return cnt, act, w2b, None
 
 
@@ -1002,8 +974,7 @@ def actor_encode(spec: ActorSpec, cand, origins, directions, pixel_area, starts,
     assert feats.data_ptr() == features.data_ptr(), "features must be contiguous (updated in place)"
     dirs = torch.empty((n, 3), dtype=torch.float32, device=feats.device)
     hit = torch.empty((n,), dtype=torch.int32, device=feats.device)
-    call("nrhip_actor_encode", C.byref(a), C.byref(r), _ptr(cnt), _ptr(act), _ptr(w2b), feats.shape[1], _ptr(feats),
-         _ptr(dirs), _ptr(hit), _ptr(None if ray_flip is None else _chk(ray_flip.reshape(-1), "ray_flip")), _stream())
+    launch("nrhip_actor_encode", a, r, cnt, act, w2b, feats.shape[1], feats, dirs, hit, _opt(ray_flip, "ray_flip"))
     return dirs, hit  # int32: actor index or -1
 
 
@@ -1017,9 +988,8 @@ def actor_pair_positions(spec: ActorSpec, origins, directions, pixel_area, start
     P_ = si.shape[0]
     x01 = torch.empty((P_, 3), dtype=torch.float32, device=si.device)
     cstd = torch.empty((P_,), dtype=torch.float32, device=si.device)
-    call("nrhip_actor_pair_positions_fwd", C.byref(a), C.byref(r), _ptr(_chk(times.reshape(-1), "times")), _ptr(si),
-         _ptr(ai), _ptr(None if ray_flip is None else _chk(ray_flip.reshape(-1), "ray_flip")), P_, _ptr(x01), _ptr(cstd),
-         _stream())
+    launch("nrhip_actor_pair_positions_fwd", a, r, _chk(times.reshape(-1), "times"), si, ai, _opt(ray_flip, "ray_flip"), P_,
+           x01, cstd)
     return x01, cstd
 
 
@@ -1033,14 +1003,13 @@ def actor_pair_positions_bwd(spec: ActorSpec, origins, directions, pixel_area, s
     flat = torch.zeros((a.n_times * a.n_actors * 9,), dtype=torch.float32, device=si.device)
     gp = flat[: a.n_times * a.n_actors * 3].view(a.n_times, a.n_actors, 3)
     gr = flat[a.n_times * a.n_actors * 3:].view(a.n_times, a.n_actors, 6)
-    common = (C.byref(a), C.byref(r), _ptr(_chk(times.reshape(-1), "times")), _ptr(si), _ptr(ai),
-              _ptr(None if ray_flip is None else _chk(ray_flip.reshape(-1), "ray_flip")), si.shape[0],
-              _ptr(_chk(grad_x01, "grad_x01")), _ptr(_chk(grad_cstd, "grad_cstd")), _ptr(gp), _ptr(gr))
+    common = (a, r, _chk(times.reshape(-1), "times"), si, ai, _opt(ray_flip, "ray_flip"), si.shape[0],
+              _chk(grad_x01, "grad_x01"), _chk(grad_cstd, "grad_cstd"), gp, gr)
     if not ray_grads:
-        call("nrhip_actor_pair_positions_bwd", *common, _stream())
+        launch("nrhip_actor_pair_positions_bwd", *common)
         return gp, gr
     god = torch.zeros((2, r.n_rays, 3), dtype=torch.float32, device=si.device)
-    call("nrhip_actor_pair_positions_bwd_rays", *common, _ptr(god[0]), _ptr(god[1]), _stream())
+    launch("nrhip_actor_pair_positions_bwd_rays", *common, god[0], god[1])
     return gp, gr, god[0], god[1]
 
 
@@ -1050,7 +1019,7 @@ def actor_hits(spec: ActorSpec, cand, origins, directions, pixel_area, starts, e
     a, keep2 = spec.c_actors()
     cnt, act, w2b, _ = cand
     hits = torch.empty((r.n_rays * r.n_samples, _lib.MAX_SAMPLE_CONTAINMENTS), dtype=torch.int32, device=origins.device)
-    call("nrhip_actor_hits", C.byref(a), C.byref(r), _ptr(cnt), _ptr(act), _ptr(w2b), _ptr(hits), _stream())
+    launch("nrhip_actor_hits", a, r, cnt, act, w2b, hits)
     return hits
 
 
@@ -1063,12 +1032,12 @@ def actor_pairs(hits: Tensor) -> Tuple[Tensor, Tensor]:
     nblk = (n + 1023) // 1024
     off = torch.empty((max(nblk, 1),), dtype=torch.int32, device=h.device)
     total = torch.empty((1,), dtype=torch.int64, device=h.device)
-    call("nrhip_actor_pairs_count", _ptr(h), n, _ptr(off), _ptr(total), _stream())
+    launch("nrhip_actor_pairs_count", h, n, off, total)
     P_ = int(total.item())
     si = torch.empty((P_,), dtype=torch.int64, device=h.device)
     ai = torch.empty((P_,), dtype=torch.int32, device=h.device)
     if P_:
-        call("nrhip_actor_pairs_write", _ptr(h), n, _ptr(off), _ptr(total), _ptr(si), _ptr(ai), _stream())
+        launch("nrhip_actor_pairs_write", h, n, off, total, si, ai)
     return si, ai
 
 
@@ -1083,8 +1052,7 @@ def actor_density(spec: ActorSpec, cand, origins, directions, pixel_area, starts
     dens = _chk(density, "density")
     assert dens.data_ptr() == density.data_ptr(), "density must be contiguous (updated in place)"
     hit = torch.empty((r.n_rays, r.n_samples), dtype=torch.int32, device=dens.device)
-    call("nrhip_actor_density", C.byref(a), C.byref(r), _ptr(cnt), _ptr(act), _ptr(w2b), _ptr(dw), dw.numel(),
-         _ptr(dens), _ptr(hit), _ptr(None if ray_flip is None else _chk(ray_flip.reshape(-1), "ray_flip")), _stream())
+    launch("nrhip_actor_density", a, r, cnt, act, w2b, dw, dw.numel(), dens, hit, _opt(ray_flip, "ray_flip"))
     return hit if return_actor else hit >= 0
 
 
@@ -1154,8 +1122,7 @@ def actor_density_splice_fwd(density: Tensor, rows: Tensor, weight: Tensor, samp
     if weight.numel() != la or idx.shape[0] != P or win.shape[0] != P or density.dtype != torch.float32 or not density.is_contiguous():
         raise ValueError("actor_density_splice_fwd: shapes")
     logit = torch.empty((P,), device=rows.device, dtype=torch.float32)
-    call("nrhip_actor_density_splice_fwd", _ptr(rows), la, _ptr(weight), _ptr(idx), _ptr(win), P, _ptr(density), _ptr(logit),
-         _stream())
+    launch("nrhip_actor_density_splice_fwd", rows, la, weight, idx, win, P, density, logit)
     return logit
 
 
@@ -1169,8 +1136,8 @@ def actor_density_splice_bwd(rows, weight, sample_idx, winner, logit, density_ou
     g_dens = g.clone()
     g_rows = torch.empty_like(rows)
     g_w = torch.zeros((la,), device=rows.device, dtype=torch.float32)
-    call("nrhip_actor_density_splice_bwd", _ptr(rows), la, _ptr(weight), _ptr(idx), _ptr(win), _ptr(_chk(logit, "logit")),
-         _ptr(_chk(density_out.reshape(-1), "density_out")), _ptr(g), P, _ptr(g_dens), _ptr(g_rows), _ptr(g_w), _stream())
+    launch("nrhip_actor_density_splice_bwd", rows, la, weight, idx, win, _chk(logit, "logit"),
+           _chk(density_out.reshape(-1), "density_out"), g, P, g_dens, g_rows, g_w)
     return g_dens, g_rows, g_w
 
 
@@ -1186,13 +1153,10 @@ def occgrid_march(grid: OccGridSpec, origins, directions, render_step_size, near
     else:
         g, keep = grid.c_grid()
         entry = "nrhip_occgrid_march"
-    tmn = None if t_min is None else _chk(t_min.reshape(-1), "t_min")
-    tmx = None if t_max is None else _chk(t_max.reshape(-1), "t_max")
-    tr = None if t_rand is None else _chk(t_rand.reshape(-1), "t_rand")
     counts = torch.zeros((R,), dtype=torch.int32, device=dev)
-    args = (C.byref(g), _ptr(o), _ptr(d), _ptr(tmn), _ptr(tmx), _ptr(tr), R, float(render_step_size), float(near_plane),
-            float(far_plane), float(cone_angle), int(max_candidates))
-    call(entry, *args, _ptr(counts), _ptr(None), _ptr(None), _ptr(None), _ptr(None), _stream())
+    args = (g, o, d, _opt(t_min, "t_min"), _opt(t_max, "t_max"), _opt(t_rand, "t_rand"), R, float(render_step_size),
+            float(near_plane), float(far_plane), float(cone_angle), int(max_candidates))
+    launch(entry, *args, counts, None, None, None, None)
     seg = torch.zeros((R + 1,), dtype=torch.int64, device=dev)
     torch.cumsum(counts, 0, out=seg[1:])
     M = int(seg[-1].item()) if R else 0
@@ -1200,7 +1164,7 @@ def occgrid_march(grid: OccGridSpec, origins, directions, render_step_size, near
     ts = torch.empty((M,), dtype=torch.float32, device=dev)
     te = torch.empty((M,), dtype=torch.float32, device=dev)
     if M:
-        call(entry, *args, _ptr(None), _ptr(seg), _ptr(ri), _ptr(ts), _ptr(te), _stream())
+        launch(entry, *args, None, seg, ri, ts, te)
     return ri, ts, te, seg
 
 
@@ -1208,10 +1172,8 @@ def occgrid_march(grid: OccGridSpec, origins, directions, render_step_size, near
 def occgrid_update_scratch(levels: int, resolution: int, device) -> dict:
     """The device scratch of a grid, allocated (zero-filled) once and kept by its owner -- shims.nerfacc.OccGridEstimator
     caches it: the kernels' workspace plus the fixed-capacity candidate buffers of both regimes, filled on first use."""
-    need = C.c_int64(0)
-    call("nrhip_occgrid_update_workspace", int(levels), int(resolution), C.byref(need))
-    return {"levels": int(levels), "resolution": int(resolution),
-            "workspace": torch.zeros((need.value,), dtype=torch.uint8, device=device)}
+    ws, _ = _workspace("nrhip_occgrid_update_workspace", int(levels), int(resolution), device=device, dtype=torch.uint8)
+    return {"levels": int(levels), "resolution": int(resolution), "workspace": ws.zero_()}
 
 
 def _occ_scratch(grid: OccGridSpec, scratch: Optional[dict], device) -> dict:
@@ -1260,9 +1222,8 @@ def occgrid_update_candidates(grid: OccGridSpec, occs: Tensor, warmup: bool, n: 
     ids, counts, pos = sc[key]
     g, keep = grid.c_levels()
     ws = sc["workspace"]
-    call("nrhip_occgrid_update_candidates", C.byref(g), _ptr(occs), int(bool(warmup)), n, _ptr(cell_draws if not warmup else None),
-         _ptr(sel_draws if not warmup else None), _ptr(jitter), _ptr(ids), _ptr(counts), _ptr(pos), _ptr(ws), ws.numel(),
-         _stream())
+    launch("nrhip_occgrid_update_candidates", g, occs, int(bool(warmup)), n, cell_draws if not warmup else None,
+           sel_draws if not warmup else None, jitter, ids, counts, pos, ws, ws.numel())
     return ids, counts, pos
 
 
@@ -1283,8 +1244,8 @@ def occgrid_update_apply(grid: OccGridSpec, occs: Tensor, cell_ids: Tensor, coun
     sc = _occ_scratch(grid, scratch, occs.device)
     g, keep = grid.c_levels(in_place=True)
     ws = sc["workspace"]
-    call("nrhip_occgrid_update_apply", C.byref(g), _ptr(occs), ids.shape[1], _ptr(ids), _ptr(counts), _ptr(vals),
-         float(ema_decay), float(occ_thre), _ptr(ws), ws.numel(), _stream())
+    launch("nrhip_occgrid_update_apply", g, occs, ids.shape[1], ids, counts, vals, float(ema_decay), float(occ_thre), ws,
+           ws.numel())
 
 
 def occgrid_update(grid: OccGridSpec, occs: Tensor, occ_eval_fn, step: int, occ_thre: float = 1e-2, ema_decay: float = 0.95,
@@ -1311,16 +1272,16 @@ def occgrid_mark_invisible(grid: OccGridSpec, occs: Tensor, K: Tensor, c2w: Tens
         raise ValueError(f"{K.shape[0]} intrinsics for {c2w.shape[0]} cameras")
     Kc, Mc = _chk(K, "K"), _chk(c2w[:, :3, :4], "c2w")
     g, keep = grid.c_levels(in_place=True)
-    call("nrhip_occgrid_mark_invisible", C.byref(g), _ptr(Kc), Kc.shape[0], _ptr(Mc), Mc.shape[0], int(width), int(height),
-         float(near_plane), _ptr(occs), _stream())
+    launch("nrhip_occgrid_mark_invisible", g, Kc, Kc.shape[0], Mc, Mc.shape[0], int(width), int(height), float(near_plane),
+           occs)
 
 
 def packed_visibility_from_alpha(alphas: Tensor, segments: Tensor, early_stop_eps: float, alpha_thre: float) -> Tensor:
     a = _chk(alphas.reshape(-1), "alphas")
     mask = torch.empty((a.shape[0],), dtype=torch.uint8, device=a.device)
     if a.shape[0]:
-        call("nrhip_packed_visibility_from_alpha", _ptr(a), _ptr(segments), segments.shape[0] - 1, float(early_stop_eps),
-             float(alpha_thre), _ptr(mask), _stream())
+        launch("nrhip_packed_visibility_from_alpha", a, segments, segments.shape[0] - 1, float(early_stop_eps),
+               float(alpha_thre), mask)
     return mask.bool()
 
 
@@ -1344,7 +1305,7 @@ def packed_segments(ray_indices: Tensor, n_rays: int) -> Tensor:
     """sorted ray_indices int64 [M] with values in [0, n_rays) -> segments int64 [n_rays + 1]"""
     ri = _chk(ray_indices, "ray_indices", torch.int64).reshape(-1)
     seg = torch.empty((int(n_rays) + 1,), dtype=torch.int64, device=ri.device)
-    call("nrhip_packed_segments", _ptr(ri), ri.shape[0], int(n_rays), _ptr(seg), _stream())
+    launch("nrhip_packed_segments", ri, ri.shape[0], int(n_rays), seg)
     return seg
 
 
@@ -1354,7 +1315,7 @@ def packed_weight_from_density(t_starts, t_ends, sigmas, segments):
     s, e = _flat(t_starts, "t_starts", sg.shape[0]), _flat(t_ends, "t_ends", sg.shape[0])
     seg, R = _seg(segments)
     w, t, a = torch.empty_like(sg), torch.empty_like(sg), torch.empty_like(sg)
-    call("nrhip_packed_weight_from_density", _ptr(s), _ptr(e), _ptr(sg), _ptr(seg), R, _ptr(w), _ptr(t), _ptr(a), _stream())
+    launch("nrhip_packed_weight_from_density", s, e, sg, seg, R, w, t, a)
     return w, t, a
 
 
@@ -1363,7 +1324,7 @@ def packed_weight_from_density_bwd(t_starts, t_ends, sigmas, segments, grad_w):
     s, e, gw = (_flat(v, n, sg.shape[0]) for v, n in ((t_starts, "t_starts"), (t_ends, "t_ends"), (grad_w, "grad_w")))
     seg, R = _seg(segments)
     gs = torch.empty_like(sg)
-    call("nrhip_packed_weight_from_density_bwd", _ptr(s), _ptr(e), _ptr(sg), _ptr(seg), _ptr(gw), R, _ptr(gs), _stream())
+    launch("nrhip_packed_weight_from_density_bwd", s, e, sg, seg, gw, R, gs)
     return gs
 
 
@@ -1372,7 +1333,7 @@ def packed_weight_from_alpha(alphas, segments):
     a = _flat(alphas, "alphas")
     seg, R = _seg(segments)
     w, t = torch.empty_like(a), torch.empty_like(a)
-    call("nrhip_packed_weight_from_alpha", _ptr(a), _ptr(seg), R, _ptr(w), _ptr(t), _stream())
+    launch("nrhip_packed_weight_from_alpha", a, seg, R, w, t)
     return w, t
 
 
@@ -1382,7 +1343,7 @@ def packed_weight_from_alpha_bwd(alphas, segments, grad_w, grad_t=None):
     gt = None if grad_t is None else _flat(grad_t, "grad_t", a.shape[0])
     seg, R = _seg(segments)
     ga = torch.empty_like(a)
-    call("nrhip_packed_weight_from_alpha_bwd", _ptr(a), _ptr(seg), _ptr(gw), _ptr(gt), R, _ptr(ga), _stream())
+    launch("nrhip_packed_weight_from_alpha_bwd", a, seg, gw, gt, R, ga)
     return ga
 
 
@@ -1399,8 +1360,7 @@ def packed_accumulate(weights, values, segments):
     out = torch.empty((R, Cc), device=w.device, dtype=torch.float32)
     # an empty [0,C] tensor has no address, and NULL values mean "the plain sum": any non-null address stands in (no sample,
     # nothing is read through it; the rows of out are still zeroed by the kernel)
-    vp = _ptr(out) if (v is not None and v.numel() == 0) else _ptr(v)
-    call("nrhip_packed_accumulate", _ptr(w), vp, _ptr(seg), R, Cc, _ptr(out), _stream())
+    launch("nrhip_packed_accumulate", w, out if (v is not None and v.numel() == 0) else v, seg, R, Cc, out)
     return out
 
 
@@ -1416,7 +1376,7 @@ def packed_accumulate_bwd(weights, values, g_out, segments, need_grad_weights=Tr
     gw = torch.empty_like(w) if need_grad_weights else None
     gv = torch.empty_like(v) if (need_grad_values and v is not None) else None
     if w.numel():  # (no samples: nothing to write, and an empty values tensor has no address to tell it from "plain sum")
-        call("nrhip_packed_accumulate_bwd", _ptr(w), _ptr(v), _ptr(g), _ptr(seg), R, Cc, _ptr(gw), _ptr(gv), _stream())
+        launch("nrhip_packed_accumulate_bwd", w, v, g, seg, R, Cc, gw, gv)
     return gw, gv
 
 
@@ -1435,8 +1395,7 @@ def packed_composite_fwd(t_starts, t_ends, sigmas_or_alphas, features, segments,
     od = torch.empty((R, 1), device=x.device, dtype=torch.float32)
     oa = torch.empty((R, 1), device=x.device, dtype=torch.float32)
     ow = torch.empty_like(x) if return_weights else None
-    call("nrhip_packed_composite_fwd", _ptr(s), _ptr(e), _ptr(x), _ptr(f), _ptr(seg), R, Cc, 1 if density_mode else 0,
-         _ptr(of), _ptr(od), _ptr(oa), _ptr(ow), _stream())
+    launch("nrhip_packed_composite_fwd", s, e, x, f, seg, R, Cc, 1 if density_mode else 0, of, od, oa, ow)
     return of, od, oa, ow
 
 
@@ -1457,8 +1416,7 @@ def packed_composite_bwd(t_starts, t_ends, sigmas_or_alphas, features, segments,
     gw = None if g_weights is None else _flat(g_weights, "g_weights", M)
     gx = torch.empty_like(x) if need_grad_x else None
     gf = torch.empty_like(f) if need_grad_features else None
-    call("nrhip_packed_composite_bwd", _ptr(s), _ptr(e), _ptr(x), _ptr(f), _ptr(seg), _ptr(gF), _ptr(gd), _ptr(ga), _ptr(gw),
-         R, Cc, 1 if density_mode else 0, _ptr(gx), _ptr(gf), _stream())
+    launch("nrhip_packed_composite_bwd", s, e, x, f, seg, gF, gd, ga, gw, R, Cc, 1 if density_mode else 0, gx, gf)
     return gx, gf
 
 
@@ -1468,8 +1426,28 @@ def adam_step(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tensor, 
     for t, n in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
         if _chk(t, n).data_ptr() != t.data_ptr() or t.shape != param.shape:
             raise ValueError(f"adam_step: {n} must be a contiguous fp32 GPU tensor of the parameter's shape")
-    call("nrhip_adam_step", _ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), int(step), float(lr),
-         float(beta1), float(beta2), float(eps), float(weight_decay), float(grad_scale), _stream())
+    launch("nrhip_adam_step", param, grad, exp_avg, exp_avg_sq, param.numel(), int(step), float(lr), float(beta1),
+           float(beta2), float(eps), float(weight_decay), float(grad_scale))
+
+
+def _adam_item(a, who: str, param: Tensor, grad: Tensor, m: Tensor, v: Tensor, image: Optional[Tensor]) -> None:
+    """check one item of ``who`` and fill what nrhip_adam_tensor and nrhip_adam_tensor_dev share (all but ``step``)"""
+    for t, n in ((param, "param"), (m, "exp_avg"), (v, "exp_avg_sq")):
+        if _chk(t, n).data_ptr() != t.data_ptr() or t.shape != param.shape:
+            raise ValueError(f"{who}: {n} must be a contiguous fp32 GPU tensor of the parameter's shape")
+    if grad.dtype not in (torch.float32, torch.float16) or not grad.is_contiguous() or not grad.is_cuda or grad.shape != param.shape:
+        raise ValueError(f"{who}: grad must be a contiguous fp32 / fp16 GPU tensor of the parameter's shape")
+    if image is not None and (image.dtype != torch.float16 or not image.is_contiguous() or image.shape != param.shape):
+        raise ValueError(f"{who}: image must be a contiguous fp16 tensor of the parameter's shape")
+    a.param, a.grad, a.exp_avg, a.exp_avg_sq = param.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr()
+    a.image_fp16 = image.data_ptr() if image is not None else None
+    a.n, a.grad_dtype = param.numel(), 1 if grad.dtype == torch.float16 else 0
+
+
+def _f32_scalar(t, what: str) -> Tensor:
+    if not (isinstance(t, Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
+        raise ValueError(f"{what} must be an fp32 GPU scalar")
+    return t
 
 
 def adam_step_many(items, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-15, weight_decay: float = 0.0,
@@ -1482,19 +1460,10 @@ def adam_step_many(items, lr: float, beta1: float = 0.9, beta2: float = 0.999, e
         return
     arr = (_lib.AdamTensor * len(items))()
     for k, (param, grad, m, v, step, image) in enumerate(items):
-        for t, n in ((param, "param"), (m, "exp_avg"), (v, "exp_avg_sq")):
-            if _chk(t, n).data_ptr() != t.data_ptr() or t.shape != param.shape:
-                raise ValueError(f"adam_step_many: {n} must be a contiguous fp32 GPU tensor of the parameter's shape")
-        if grad.dtype not in (torch.float32, torch.float16) or not grad.is_contiguous() or not grad.is_cuda or grad.shape != param.shape:
-            raise ValueError("adam_step_many: grad must be a contiguous fp32 / fp16 GPU tensor of the parameter's shape")
-        if image is not None and (image.dtype != torch.float16 or not image.is_contiguous() or image.shape != param.shape):
-            raise ValueError("adam_step_many: image must be a contiguous fp16 tensor of the parameter's shape")
-        a = arr[k]
-        a.param, a.grad, a.exp_avg, a.exp_avg_sq = param.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr()
-        a.image_fp16 = image.data_ptr() if image is not None else None
-        a.n, a.step, a.grad_dtype = param.numel(), int(step), 1 if grad.dtype == torch.float16 else 0
-    call("nrhip_adam_step_many", arr, len(items), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
-         float(grad_scale), _stream())
+        _adam_item(arr[k], "adam_step_many", param, grad, m, v, image)
+        arr[k].step = int(step)
+    launch("nrhip_adam_step_many", arr, len(items), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+           float(grad_scale))
 
 
 _ADAM_CTL_BYTES = None
@@ -1529,35 +1498,17 @@ def adam_step_many_dev(items, lr, beta1: float = 0.9, beta2: float = 0.999, eps:
     dev = items[0][0].device
     arr = (_lib.AdamTensorDev * len(items))()
     for k, (param, grad, m, v, step, image) in enumerate(items):
-        for t, n in ((param, "param"), (m, "exp_avg"), (v, "exp_avg_sq")):
-            if _chk(t, n).data_ptr() != t.data_ptr() or t.shape != param.shape:
-                raise ValueError(f"adam_step_many_dev: {n} must be a contiguous fp32 GPU tensor of the parameter's shape")
-        if grad.dtype not in (torch.float32, torch.float16) or not grad.is_contiguous() or not grad.is_cuda or grad.shape != param.shape:
-            raise ValueError("adam_step_many_dev: grad must be a contiguous fp32 / fp16 GPU tensor of the parameter's shape")
-        if image is not None and (image.dtype != torch.float16 or not image.is_contiguous() or image.shape != param.shape):
-            raise ValueError("adam_step_many_dev: image must be a contiguous fp16 tensor of the parameter's shape")
-        if not (isinstance(step, Tensor) and step.is_cuda and step.dtype == torch.float32 and step.numel() == 1):
-            raise ValueError("adam_step_many_dev: step must be an fp32 GPU scalar")
-        a = arr[k]
-        a.param, a.grad, a.exp_avg, a.exp_avg_sq = param.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr()
-        a.image_fp16 = image.data_ptr() if image is not None else None
-        a.n, a.step, a.grad_dtype = param.numel(), step.data_ptr(), 1 if grad.dtype == torch.float16 else 0
-
-    def scalar(t, what):
-        if t is None:
-            return None
-        if not (isinstance(t, Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
-            raise ValueError(f"adam_step_many_dev: {what} must be an fp32 GPU scalar")
-        return t.data_ptr()
-
+        _adam_item(arr[k], "adam_step_many_dev", param, grad, m, v, image)
+        arr[k].step = _f32_scalar(step, "adam_step_many_dev: step").data_ptr()
+    scalar = lambda t, what: None if t is None else _f32_scalar(t, f"adam_step_many_dev: {what}")  # noqa: E731
     lr_dev = scalar(lr, "lr") if isinstance(lr, Tensor) else None
     if workspace is None:
         workspace = adam_workspace(len(items), dev)
     if workspace.numel() < adam_workspace_floats(len(items)) or not workspace.is_cuda or workspace.dtype != torch.float32:
         raise ValueError("adam_step_many_dev: workspace too small (ops.adam_workspace)")
-    call("nrhip_adam_step_many_dev", arr, len(items), 0.0 if lr_dev is not None else float(lr), lr_dev, float(beta1),
-         float(beta2), float(eps), float(weight_decay), float(host_grad_scale), scalar(grad_scale, "grad_scale"),
-         scalar(found_inf, "found_inf"), workspace.data_ptr(), _stream())
+    launch("nrhip_adam_step_many_dev", arr, len(items), 0.0 if lr_dev is not None else float(lr), lr_dev, float(beta1),
+           float(beta2), float(eps), float(weight_decay), float(host_grad_scale), scalar(grad_scale, "grad_scale"),
+           scalar(found_inf, "found_inf"), workspace)
 
 
 def nonfinite_check(tensors, found_inf: Tensor) -> Tensor:
@@ -1566,8 +1517,7 @@ def nonfinite_check(tensors, found_inf: Tensor) -> Tensor:
     cleared here.  Same flag semantics as ``torch._amp_foreach_non_finite_check_and_unscale_`` at a scale of 1, without the
     write-back."""
     tensors = [t for t in tensors if t.numel()]
-    if not (found_inf.is_cuda and found_inf.dtype == torch.float32 and found_inf.numel() == 1):
-        raise ValueError("nonfinite_check: found_inf must be an fp32 GPU scalar")
+    _f32_scalar(found_inf, "nonfinite_check: found_inf")
     if not tensors:
         return found_inf
     arr = (_lib.CheckTensor * len(tensors))()
@@ -1576,7 +1526,7 @@ def nonfinite_check(tensors, found_inf: Tensor) -> Tensor:
                 or t.device != found_inf.device):
             raise ValueError("nonfinite_check: tensors must be contiguous, 16-byte aligned fp32 / fp16 tensors on found_inf's GPU")
         arr[k].data, arr[k].n, arr[k].dtype = t.data_ptr(), t.numel(), 1 if t.dtype == torch.float16 else 0
-    call("nrhip_nonfinite_check_many", arr, len(tensors), found_inf.data_ptr(), _stream())
+    launch("nrhip_nonfinite_check_many", arr, len(tensors), found_inf)
     return found_inf
 
 
@@ -1601,8 +1551,7 @@ def interlevel_loss_level(c: Tensor, w: Tensor, cp: Tensor, wp: Tensor, pulse_wi
         raise ValueError(f"interlevel_loss: shapes c {tuple(c.shape)} w {tuple(w.shape)} cp {tuple(cp.shape)} wp {tuple(wp.shape)}")
     loss = torch.empty((R,), device=w.device, dtype=torch.float32)
     g = torch.empty_like(wp) if need_grad else None
-    call("nrhip_interlevel_loss", _ptr(c), _ptr(w), sf, _ptr(cp), _ptr(wp), sp, float(pulse_width), R, _ptr(loss), _ptr(g),
-         _stream())
+    launch("nrhip_interlevel_loss", c, w, sf, cp, wp, sp, float(pulse_width), R, loss, g)
     return loss, g
 
 
@@ -1614,7 +1563,7 @@ def distortion_loss_rays(c: Tensor, w: Tensor, need_grad: bool = True):
         raise ValueError(f"distortion_loss: c {tuple(c.shape)} does not match w {tuple(w.shape)}")
     loss = torch.empty((R,), device=w.device, dtype=torch.float32)
     g = torch.empty_like(w) if need_grad else None
-    call("nrhip_distortion_loss", _ptr(c), _ptr(w), s, R, _ptr(loss), _ptr(g), _stream())
+    launch("nrhip_distortion_loss", c, w, s, R, loss, g)
     return loss, g
 
 
@@ -1637,7 +1586,7 @@ def prop_weights_fwd(edges: Tensor, densities: Tensor, want_depth: bool = True):
     e, es = _edges(edges, S)
     w = torch.empty_like(dens)
     depth = torch.empty((R, 1), device=dens.device, dtype=torch.float32) if want_depth else None
-    call("nrhip_prop_weights_fwd", _ptr(e), es, _ptr(dens), R, S, _ptr(w), _ptr(depth), _stream())
+    launch("nrhip_prop_weights_fwd", e, es, dens, R, S, w, depth)
     return w, depth
 
 
@@ -1646,9 +1595,9 @@ def prop_weights_bwd(edges: Tensor, densities: Tensor, grad_w: Optional[Tensor],
     R, S = dens.shape
     e, es = _edges(edges, S)
     gw = None if grad_w is None else _chk(grad_w, "grad_w")
-    gd = None if grad_depth is None else _chk(grad_depth.reshape(-1), "grad_depth")
+    gd = _opt(grad_depth, "grad_depth")
     gdens = torch.empty_like(dens)
-    call("nrhip_prop_weights_bwd", _ptr(e), es, _ptr(dens), _ptr(gw), _ptr(gd), R, S, _ptr(gdens), _stream())
+    launch("nrhip_prop_weights_bwd", e, es, dens, gw, gd, R, S, gdens)
     return gdens
 
 
@@ -1658,7 +1607,7 @@ def sdf_render_fwd(sdf: Tensor, beta: Tensor, beta_min: float, features: Tensor,
     first C columns written), depth [R,1], acc [R,1].  beta = None: the density head (use_sdf = False) -- ``sdf`` is the
     raw geometry output x, sigma = trunc_exp(x), alpha = 1 - exp(-sigma (end - start)) (render_weight_from_density)."""
     sdf, feat = _chk(sdf, "sdf"), _chk(features, "features")
-    b = None if beta is None else _chk(beta.reshape(-1), "beta")
+    b = _opt(beta, "beta")
     R, S = sdf.shape
     C_ = feat.shape[-1]
     if feat.numel() != R * S * C_ or (b is not None and b.numel() != 1):
@@ -1670,8 +1619,8 @@ def sdf_render_fwd(sdf: Tensor, beta: Tensor, beta_min: float, features: Tensor,
     out = torch.empty((R, C_ + extra_cols), device=dev, dtype=torch.float32)
     depth = torch.empty((R, 1), device=dev, dtype=torch.float32)
     acc = torch.empty((R, 1), device=dev, dtype=torch.float32)
-    call("nrhip_sdf_render_fwd", _ptr(sdf), _ptr(b), float(beta_min), _ptr(feat), _ptr(e), es, R, S, C_, _ptr(alpha),
-         _ptr(w_ns), _ptr(out), C_ + extra_cols, _ptr(depth), _ptr(acc), _stream())
+    launch("nrhip_sdf_render_fwd", sdf, b, float(beta_min), feat, e, es, R, S, C_, alpha, w_ns, out, C_ + extra_cols, depth,
+           acc)
     return alpha, w_ns, out, depth, acc
 
 
@@ -1689,7 +1638,7 @@ def sdf_render_bwd(sdf, beta, beta_min, alpha, features, edges, g_out: Tensor, g
     """-> grad_features [R,S,C], grad_sdf [R,S], grad_beta [1] (None for the density head, beta = None).  g_out: [R,C] view
     (row stride free) of the gradient of the composited features."""
     sdf, feat, alpha = _chk(sdf, "sdf"), _chk(features, "features"), _chk(alpha, "alpha")
-    b = None if beta is None else _chk(beta.reshape(-1), "beta")
+    b = _opt(beta, "beta")
     R, S = sdf.shape
     C_ = feat.shape[-1]
     e, es = _edges(edges, S)
@@ -1698,18 +1647,16 @@ def sdf_render_bwd(sdf, beta, beta_min, alpha, features, edges, g_out: Tensor, g
         raise ValueError(f"sdf_render_bwd: g_out {tuple(g.shape)} != {(R, C_)}")
     if g.data_ptr() % 16 or (gs * 4) % 16:
         g, gs = g.contiguous(), C_
-    gd = None if g_depth is None else _chk(g_depth.reshape(-1), "g_depth")
-    ga = None if g_acc is None else _chk(g_acc.reshape(-1), "g_acc")
+    gd = _opt(g_depth, "g_depth")
+    ga = _opt(g_acc, "g_acc")
     gw = None if g_weights_ns is None else _chk(g_weights_ns.reshape(R, S - 1), "g_weights_ns")
     dev = sdf.device
     gfeat = torch.empty_like(feat)
     gsdf = torch.empty_like(sdf)
     gbeta = None if b is None else torch.empty((1,), device=dev, dtype=torch.float32)
-    need = C.c_int64(0)
-    call("nrhip_sdf_render_bwd_workspace", R, C.byref(need))
-    ws = torch.empty((max(need.value, 1),), device=dev, dtype=torch.float32)
-    call("nrhip_sdf_render_bwd", _ptr(sdf), _ptr(b), float(beta_min), _ptr(alpha), _ptr(feat), _ptr(e), es, _ptr(g), gs,
-         _ptr(gd), _ptr(ga), _ptr(gw), R, S, C_, _ptr(gfeat), _ptr(gsdf), _ptr(gbeta), _ptr(ws), _stream())
+    ws, _ = _workspace("nrhip_sdf_render_bwd_workspace", R, device=dev, dtype=torch.float32)
+    launch("nrhip_sdf_render_bwd", sdf, b, float(beta_min), alpha, feat, e, es, g, gs, gd, ga, gw, R, S, C_, gfeat, gsdf,
+           gbeta, ws)
     return gfeat, gsdf, gbeta
 
 
@@ -1718,14 +1665,14 @@ def appearance_fwd(weight: Tensor, sensor_idx: Optional[Tensor], times: Optional
     """appearance embedding rows (models/neurad.py:423-441) written into ``out`` ([R,D] view, row stride free)"""
     w = _chk(weight, "weight")
     E, D = w.shape
-    s = None if sensor_idx is None else _chk(sensor_idx.reshape(-1), "sensor_idx", torch.int64)
-    t = None if times is None else _chk(times.reshape(-1), "times")
+    s = _opt(sensor_idx, "sensor_idx", torch.int64)
+    t = _opt(times, "times")
     if out is None:
         out = torch.empty((n_rays, D), device=w.device, dtype=torch.float32)
     if not (out.is_cuda and out.dtype == torch.float32 and out.shape == (n_rays, D) and out.stride(1) == 1):
         raise ValueError("appearance_fwd: out must be a float32 [R,D] GPU view with unit inner stride")
-    call("nrhip_appearance_fwd", _ptr(w), _ptr(s), _ptr(t), float(duration), int(n_per_sensor), 1 if temporal else 0,
-         n_rays, E, D, _ptr(out), out.stride(0) if n_rays > 1 else D, _stream())
+    launch("nrhip_appearance_fwd", w, s, t, float(duration), int(n_per_sensor), 1 if temporal else 0, n_rays, E, D, out,
+           out.stride(0) if n_rays > 1 else D)
     return out
 
 
@@ -1733,11 +1680,10 @@ def appearance_bwd(g_out: Tensor, sensor_idx, times, duration: float, n_per_sens
                    n_embed: int) -> Tensor:
     g, gs = _strided_rows(g_out, "g_out")
     R, D = g.shape
-    s = None if sensor_idx is None else _chk(sensor_idx.reshape(-1), "sensor_idx", torch.int64)
-    t = None if times is None else _chk(times.reshape(-1), "times")
+    s = _opt(sensor_idx, "sensor_idx", torch.int64)
+    t = _opt(times, "times")
     gw = torch.empty((n_embed, D), device=g.device, dtype=torch.float32)  # the entry point zero-fills it
-    call("nrhip_appearance_bwd", _ptr(g), gs, _ptr(s), _ptr(t), float(duration), int(n_per_sensor), 1 if temporal else 0,
-         R, n_embed, D, _ptr(gw), _stream())
+    launch("nrhip_appearance_bwd", g, gs, s, t, float(duration), int(n_per_sensor), 1 if temporal else 0, R, n_embed, D, gw)
     return gw
 
 
@@ -1753,7 +1699,7 @@ def mask_compact(mask: Tensor, n_out: int):
     # gather index) instead of uninitialised memory
     rows = torch.zeros((n_out,), device=m.device, dtype=torch.int64)
     inverse = torch.empty((m.shape[0],), device=m.device, dtype=torch.int32)
-    call("nrhip_mask_compact", _ptr(m), m.shape[0], _ptr(rows), n_out, _ptr(inverse), _ptr(None), _stream())
+    launch("nrhip_mask_compact", m, m.shape[0], rows, n_out, inverse, None)
     return rows, inverse
 
 
@@ -1776,13 +1722,9 @@ def lidar_losses(depths: Sequence[Tensor], lidar_rows: Tensor, distance: Tensor,
     dev = rows.device
     metrics = torch.empty((2 + nl,), device=dev, dtype=torch.float32)
     unit = torch.empty((nl + 2, n), device=dev, dtype=torch.float32)
-    need = C.c_int64(0)
-    call("nrhip_lidar_losses_workspace", n, C.byref(need))
-    scratch = torch.empty((need.value,), device=dev, dtype=torch.float32)
-    pd = (C.c_void_p * nl)(*[d.data_ptr() for d in ds])
-    call("nrhip_lidar_losses", C.cast(pd, C.POINTER(C.c_void_p)), nl, _ptr(rows), _ptr(dist), _ptr(ret), _ptr(inten),
-         _ptr(tgt), _ptr(lg), n, float(non_return_distance), float(non_return_mult), float(quantile), _ptr(metrics),
-         _ptr(unit), _ptr(scratch), _stream())
+    scratch, _ = _workspace("nrhip_lidar_losses_workspace", n, device=dev, dtype=torch.float32)
+    launch("nrhip_lidar_losses", _host_ptrs(ds), nl, rows, dist, ret, inten, tgt, lg, n, float(non_return_distance),
+           float(non_return_mult), float(quantile), metrics, unit, scratch)
     return metrics, (unit, scratch, ret)
 
 
@@ -1796,9 +1738,7 @@ def lidar_losses_bwd(saved, inverse: Tensor, upstream: Tensor, n_levels: int, n_
     gds = [torch.empty((n_rays, 1), device=dev, dtype=torch.float32) if nd else None for nd in need_depth]
     gi = torch.empty((n, 1), device=dev, dtype=torch.float32) if need_intensity else None
     gl = torch.empty((n, 1), device=dev, dtype=torch.float32) if need_logits else None
-    pg = (C.c_void_p * n_levels)(*[(0 if g is None else g.data_ptr()) for g in gds])
-    call("nrhip_lidar_losses_bwd", _ptr(unit), _ptr(scratch), _ptr(ret), _ptr(inv), _ptr(up), n_levels, n_rays, n,
-         C.cast(pg, C.POINTER(C.c_void_p)), _ptr(gi), _ptr(gl), _stream())
+    launch("nrhip_lidar_losses_bwd", unit, scratch, ret, inv, up, n_levels, n_rays, n, _host_ptrs(gds, n_levels), gi, gl)
     return gds, gi, gl
 
 
@@ -1811,7 +1751,7 @@ def grad_rows_count(grad: Tensor, n_levels: int):
     nblk = (T + _lib.GRAD_ROWS_PER_BLOCK - 1) // _lib.GRAD_ROWS_PER_BLOCK
     blocks = torch.empty((n_levels, nblk), dtype=torch.int32, device=g.device)
     counts = torch.empty((n_levels,), dtype=torch.int64, device=g.device)
-    call("nrhip_grad_rows_count", _ptr(g), n_levels, T, F, _ptr(blocks), _ptr(counts), _stream())
+    launch("nrhip_grad_rows_count", g, n_levels, T, F, blocks, counts)
     return counts, blocks
 
 
@@ -1839,8 +1779,7 @@ def grad_rows_compact(grad: Tensor, n_levels: int, block_offsets: Tensor, levels
         tk = int(sum(cpk))
         if tk:
             lv, cp, n = _list_args(lvk, cpk)
-            call("nrhip_grad_rows_compact", _ptr(g), n_levels, T, F, _ptr(bo), lv, cp, n, float(scale), _ptr(rows[off:]),
-                 _ptr(vals[off:]), _stream())
+            launch("nrhip_grad_rows_compact", g, n_levels, T, F, bo, lv, cp, n, float(scale), rows[off:], vals[off:])
         off += tk
     return rows, vals
 
@@ -1862,6 +1801,6 @@ def grad_rows_apply(grad: Tensor, n_levels: int, levels: Sequence[int], caps: Se
         tk = int(sum(cpk))
         if tk:
             lv, cp, n = _list_args(lvk, cpk)
-            call("nrhip_grad_rows_apply", _ptr(g), n_levels, T, F, lv, cp, n, _ptr(rows[off:]),
-                 _ptr(None if vals is None else vals[off:]), 1 if add else 0, _stream())
+            launch("nrhip_grad_rows_apply", g, n_levels, T, F, lv, cp, n, rows[off:], None if vals is None else vals[off:],
+                   1 if add else 0)
         off += tk

@@ -9,7 +9,7 @@ import torch
 from torch import Tensor
 
 from ._lib import call
-from .ops import _chk, _ptr, _stream
+from .ops import _chk, _host_ptrs, _workspace, launch
 
 _WFRAG_BYTES = 49 * 2 * 64 * 16
 
@@ -20,7 +20,7 @@ def conv7x7_pack(weight: Tensor, mode: int = 0) -> Tensor:
     if tuple(w.shape) != (32, 32, 7, 7):
         raise ValueError(f"conv7x7_pack: weight {tuple(w.shape)}, expected (32, 32, 7, 7)")
     out = torch.empty((_WFRAG_BYTES // 2,), device=w.device, dtype=torch.float16)
-    call("nrhip_conv7x7_pack", _ptr(w), mode, _ptr(out), _stream())
+    launch("nrhip_conv7x7_pack", w, mode, out)
     return out
 
 
@@ -31,8 +31,7 @@ def conv7x7_pack_many(weights) -> Tensor:
         if tuple(w.shape) != (32, 32, 7, 7):
             raise ValueError(f"conv7x7_pack_many: weight {tuple(w.shape)}, expected (32, 32, 7, 7)")
     out = torch.empty((len(ws), 2, _WFRAG_BYTES // 2), device=ws[0].device, dtype=torch.float16)
-    ptrs = (C.c_void_p * len(ws))(*[w.data_ptr() for w in ws])
-    call("nrhip_conv7x7_pack_many", ptrs, len(ws), _ptr(out), _stream())
+    launch("nrhip_conv7x7_pack_many", _host_ptrs(ws), len(ws), out)
     return out
 
 
@@ -58,7 +57,7 @@ def conv7x7(x: Tensor, wfrag: Tensor, bias: Optional[Tensor] = None, stats: bool
         call("nrhip_conv7x7_tiles", h, w, r, C.byref(tiles))
         part = torch.empty((b * tiles.value, 64), device=x.device, dtype=torch.float32)
     bias_f = None if bias is None else _chk(bias.detach().to(torch.float32), "bias")
-    call("nrhip_conv7x7", _ptr(x), _ptr(wfrag), _ptr(bias_f), _ptr(out), _ptr(part), b, h, w, r, _stream())
+    launch("nrhip_conv7x7", x, wfrag, bias_f, out, part, b, h, w, r)
     return out, part
 
 
@@ -74,22 +73,13 @@ def conv7x7_wgrad(x: Tensor, grad_out: Tensor, grad_weight: Tensor, grad_bias: O
     gw = _chk(grad_weight, "grad_weight")
     if gw.data_ptr() != grad_weight.data_ptr() or tuple(gw.shape) != (32, 32, 7, 7):
         raise ValueError("conv7x7_wgrad: grad_weight must be a contiguous fp32 [32, 32, 7, 7] tensor")
-    n = C.c_int64(0)
-    call("nrhip_conv7x7_wgrad_workspace", b, h, w, C.byref(n))
-    ws = torch.empty((n.value,), device=x.device, dtype=torch.float32)
-    call("nrhip_conv7x7_wgrad", _ptr(x), _ptr(grad_out), _ptr(ws), _ptr(gw), _ptr(grad_bias), _ptr(grad_scale), b, h, w,
-         _stream())
+    ws, _ = _workspace("nrhip_conv7x7_wgrad_workspace", b, h, w, device=x.device, dtype=torch.float32)
+    launch("nrhip_conv7x7_wgrad", x, grad_out, ws, gw, grad_bias, grad_scale, b, h, w)
 
 
 # ---- the other layers ------------------------------------------------------------------------------------------------
 def _f32(t: Tensor, name: str) -> Tensor:
     return _chk(t.detach() if t.requires_grad else t, name)
-
-
-def _ws(entry: str, *dims, device) -> Tensor:
-    n = C.c_int64(0)
-    call(entry, *dims, C.byref(n))
-    return torch.empty((max(n.value, 1),), device=device, dtype=torch.float32)
 
 
 def _act16(t: Tensor, name: str, like: Optional[Tensor] = None) -> Tensor:
@@ -112,8 +102,8 @@ def bn_finalize(part: Tensor, count: int, gamma: Tensor, beta: Tensor, eps: floa
                 running_mean: Optional[Tensor], running_var: Optional[Tensor]) -> Tensor:
     """-> coef [4, 32] = scale, shift, mean, rstd; running statistics updated in place like torch's batch_norm"""
     coef = torch.empty((4, 32), device=part.device, dtype=torch.float32)
-    call("nrhip_dec_bn_finalize", _ptr(part), part.shape[0], count, _ptr(_f32(gamma, "gamma")), _ptr(_f32(beta, "beta")),
-         float(eps), float(momentum), _ptr(running_mean), _ptr(running_var), _ptr(coef), _stream())
+    launch("nrhip_dec_bn_finalize", part, part.shape[0], count, _f32(gamma, "gamma"), _f32(beta, "beta"), float(eps),
+           float(momentum), running_mean, running_var, coef)
     return coef
 
 
@@ -122,7 +112,7 @@ def bn_act(c: Tensor, coef: Tensor, skip: Optional[Tensor] = None) -> Tensor:
     if skip is not None:
         _act16(skip, "skip", c)
     out = torch.empty_like(c)
-    call("nrhip_dec_bn_act", _ptr(c), _ptr(coef), _ptr(skip), _ptr(out), c.numel() // 32, _stream())
+    launch("nrhip_dec_bn_act", c, coef, skip, out, c.numel() // 32)
     return out
 
 
@@ -131,7 +121,7 @@ def grad_scale(grad: Tensor) -> Tensor:
     working scale: its fp16 gradient tensors carry S, every fp32 result is multiplied by 1/S)"""
     g = _chk(grad, "grad")
     scale = torch.empty((3,), device=g.device, dtype=torch.float32)
-    call("nrhip_dec_grad_scale", _ptr(g), g.numel(), _ptr(scale), _stream())
+    launch("nrhip_dec_grad_scale", g, g.numel(), scale)
     return scale
 
 
@@ -139,17 +129,17 @@ def bn_bwd(grad_out: Tensor, act: Tensor, c: Tensor, gamma: Tensor, coef: Tensor
            grad_beta: Tensor, grad_scale: Optional[Tensor] = None) -> Tensor:
     _act16(c, "c"), _act16(grad_out, "grad_out", c), _act16(act, "act", c), _coef(coef, "coef", 4)
     npix = c.numel() // 32
-    ws = _ws("nrhip_dec_bn_bwd_workspace", npix, device=c.device)
+    ws, _ = _workspace("nrhip_dec_bn_bwd_workspace", npix, device=c.device, dtype=torch.float32)
     out = torch.empty_like(c)
-    call("nrhip_dec_bn_bwd", _ptr(grad_out), _ptr(act), _ptr(c), _ptr(_f32(gamma, "gamma")), _ptr(coef), _ptr(ws),
-         _ptr(grad_gamma), _ptr(grad_beta), _ptr(grad_scale), _ptr(out), npix, _stream())
+    launch("nrhip_dec_bn_bwd", grad_out, act, c, _f32(gamma, "gamma"), coef, ws, grad_gamma, grad_beta, grad_scale, out,
+           npix)
     return out
 
 
 def add_masked(a: Tensor, grad_out: Tensor, act: Tensor) -> Tensor:
     _act16(a, "a"), _act16(grad_out, "grad_out", a), _act16(act, "act", a)
     out = torch.empty_like(a)
-    call("nrhip_dec_add_masked", _ptr(a), _ptr(grad_out), _ptr(act), _ptr(out), a.numel() // 32, _stream())
+    launch("nrhip_dec_add_masked", a, grad_out, act, out, a.numel() // 32)
     return out
 
 
@@ -157,8 +147,7 @@ def conv1x1_in_fwd(features: Tensor, weight: Tensor, bias: Tensor) -> Tensor:
     f = _chk(features, "features")
     n, cin = f.shape
     out = torch.empty((n, 32), device=f.device, dtype=torch.float16)
-    call("nrhip_dec_conv1x1_in_fwd", _ptr(f), _ptr(_f32(weight, "weight").reshape(32, cin)), _ptr(_f32(bias, "bias")),
-         _ptr(out), n, cin, _stream())
+    launch("nrhip_dec_conv1x1_in_fwd", f, _f32(weight, "weight").reshape(32, cin), _f32(bias, "bias"), out, n, cin)
     return out
 
 
@@ -166,10 +155,10 @@ def conv1x1_in_bwd(features: Tensor, h: Tensor, grad_h: Tensor, weight: Tensor, 
                    grad_scale: Optional[Tensor] = None):
     f = _chk(features, "features")
     n, cin = f.shape
-    ws = _ws("nrhip_dec_conv1x1_in_bwd_workspace", n, cin, device=f.device)
+    ws, _ = _workspace("nrhip_dec_conv1x1_in_bwd_workspace", n, cin, device=f.device, dtype=torch.float32)
     gf = torch.empty_like(f)
-    call("nrhip_dec_conv1x1_in_bwd", _ptr(f), _ptr(h), _ptr(grad_h), _ptr(_f32(weight, "weight")), _ptr(ws), _ptr(gf),
-         _ptr(grad_weight), _ptr(grad_bias), _ptr(grad_scale), n, cin, _stream())
+    launch("nrhip_dec_conv1x1_in_bwd", f, h, grad_h, _f32(weight, "weight"), ws, gf, grad_weight, grad_bias, grad_scale, n,
+           cin)
     return gf
 
 
@@ -179,7 +168,7 @@ def upsample_pack(weight: Tensor) -> Tensor:
     if tuple(w.shape) != (32, 32, 3, 3):
         raise ValueError(f"upsample_pack: weight {tuple(w.shape)}, expected (32, 32, 3, 3)")
     out = torch.empty((2, 9 * 2 * 64 * 8), device=w.device, dtype=torch.float16)
-    call("nrhip_dec_upsample_pack", _ptr(w), _ptr(out), _stream())
+    launch("nrhip_dec_upsample_pack", w, out)
     return out
 
 
@@ -189,7 +178,7 @@ def upsample_fwd(h: Tensor, wup: Tensor, bias: Tensor) -> Tensor:
         raise ValueError("upsample_fwd: h must be [B, H, W, 32] and wup the output of upsample_pack")
     b, hh, w, _ = h.shape
     out = torch.empty((b, 3 * hh, 3 * w, 32), device=h.device, dtype=torch.float16)
-    call("nrhip_dec_upsample_fwd", _ptr(h), _ptr(wup), _ptr(_f32(bias, "bias")), _ptr(out), b, hh, w, _stream())
+    launch("nrhip_dec_upsample_fwd", h, wup, _f32(bias, "bias"), out, b, hh, w)
     return out
 
 
@@ -199,10 +188,9 @@ def upsample_bwd(h: Tensor, grad_out: Tensor, wup: Tensor, grad_weight: Tensor, 
     if h.dim() != 4 or grad_out.shape != (h.shape[0], 3 * h.shape[1], 3 * h.shape[2], 32) or wup.numel() != 2 * 9 * 2 * 64 * 8:
         raise ValueError("upsample_bwd: h [B, H, W, 32], grad_out [B, 3H, 3W, 32], wup from upsample_pack")
     b, hh, w, _ = h.shape
-    ws = _ws("nrhip_dec_upsample_bwd_workspace", b, hh, w, device=h.device)
+    ws, _ = _workspace("nrhip_dec_upsample_bwd_workspace", b, hh, w, device=h.device, dtype=torch.float32)
     gh = torch.empty_like(h)
-    call("nrhip_dec_upsample_bwd", _ptr(h), _ptr(grad_out), _ptr(wup), _ptr(ws), _ptr(gh), _ptr(grad_weight),
-         _ptr(grad_bias), _ptr(grad_scale), b, hh, w, _stream())
+    launch("nrhip_dec_upsample_bwd", h, grad_out, wup, ws, gh, grad_weight, grad_bias, grad_scale, b, hh, w)
     return gh
 
 
@@ -212,8 +200,7 @@ def rgb_fwd(h: Tensor, weight: Tensor, bias: Tensor) -> Tensor:
         raise ValueError("rgb_fwd: h must be [B, H, W, 32], weight [3, 32(, 1, 1)], bias [3]")
     b, hh, w, _ = h.shape
     rgb = torch.empty((b, hh, w, 3), device=h.device, dtype=torch.float32)
-    call("nrhip_dec_rgb_fwd", _ptr(h), _ptr(_f32(weight, "weight")), _ptr(_f32(bias, "bias")), _ptr(rgb), b * hh * w,
-         _stream())
+    launch("nrhip_dec_rgb_fwd", h, _f32(weight, "weight"), _f32(bias, "bias"), rgb, b * hh * w)
     return rgb
 
 
@@ -223,10 +210,10 @@ def rgb_bwd(h: Tensor, rgb: Tensor, grad_rgb: Tensor, weight: Tensor, grad_weigh
     npix = h.numel() // 32
     if rgb.numel() != 3 * npix or grad_rgb.numel() != 3 * npix or grad_weight.numel() != 96 or grad_bias.numel() != 3:
         raise ValueError("rgb_bwd: rgb / grad_rgb must hold 3 values per pixel of h, grad_weight 96, grad_bias 3")
-    ws = _ws("nrhip_dec_rgb_bwd_workspace", npix, device=h.device)
+    ws, _ = _workspace("nrhip_dec_rgb_bwd_workspace", npix, device=h.device, dtype=torch.float32)
     gh = torch.empty_like(h)
-    call("nrhip_dec_rgb_bwd", _ptr(h), _ptr(rgb), _ptr(_chk(grad_rgb, "grad_rgb")), _ptr(_f32(weight, "weight")), _ptr(ws),
-         _ptr(gh), _ptr(grad_weight), _ptr(grad_bias), _ptr(grad_scale), npix, _stream())
+    launch("nrhip_dec_rgb_bwd", h, rgb, _chk(grad_rgb, "grad_rgb"), _f32(weight, "weight"), ws, gh, grad_weight, grad_bias,
+           grad_scale, npix)
     return gh
 
 
@@ -281,7 +268,7 @@ class RgbDecoderFn(torch.autograd.Function):
         saved = torch.empty((sizes[0].value,), device=feats.device, dtype=torch.uint8)
         work = torch.empty((sizes[1].value,), device=feats.device, dtype=torch.uint8)
         rgb = torch.empty((b, 3 * ph, 3 * pw, 3), device=feats.device, dtype=torch.float32)
-        call("nrhip_rgb_decoder_fwd", C.byref(d), _ptr(feats), _ptr(saved), _ptr(work), _ptr(rgb), _stream())
+        launch("nrhip_rgb_decoder_fwd", d, feats, saved, work, rgb)
         ctx.training, ctx.dec, ctx.keep = training, d, keep
         # through save_for_backward, not as attributes: `rgb` is this node's own output (an attribute would close the cycle
         # rgb -> grad_fn -> ctx -> rgb that only the cyclic GC breaks, holding the activation buffer until then), the
@@ -299,8 +286,7 @@ class RgbDecoderFn(torch.autograd.Function):
         work = torch.empty((ctx.sizes[1].value,), device=feats.device, dtype=torch.uint8)
         gf = torch.empty_like(feats)
         flat = torch.empty((ctx.sizes[2].value,), device=feats.device, dtype=torch.float32)
-        call("nrhip_rgb_decoder_bwd", C.byref(ctx.dec), _ptr(feats), _ptr(saved), _ptr(rgb), _ptr(grad_rgb), _ptr(work),
-             _ptr(gf), _ptr(flat), _stream())
+        launch("nrhip_rgb_decoder_bwd", ctx.dec, feats, saved, rgb, grad_rgb, work, gf, flat)
         grads, off = [], 0
         for shape, need in zip(ctx.shapes, ctx.need[1:]):
             k = 1

@@ -891,3 +891,77 @@ def test_table_gradients_at_every_feature_width(ops, F, monkeypatch, switches, l
     for pairs in ("all", "none"):
         switches.set("NRHIP_BIN_PAIRS", pairs)
         check(atomic=False)
+
+
+# ------------------------------------------------------------------------------------------------
+# Inputs that make a wrapper copy: `_chk` (or the `reshape(-1)` in front of it) returns a contiguous copy that only the
+# wrapper's argument list refers to.  The launch path holds it until the entry point has returned; a copy freed earlier
+# could be handed to the next allocation.  These kernels use no atomics: the result must equal, bit for bit, the same call
+# on `.contiguous()` inputs.
+def _poisoned(like):
+    """an unrelated tensor of the copy's size, allocated and filled right before the call under test"""
+    if like.dtype.is_floating_point:
+        return torch.full((like.numel(),), float("nan"), device="cuda", dtype=like.dtype)
+    return torch.full((like.numel(),), 2**40, device="cuda", dtype=like.dtype)
+
+
+def _same_on_strided_and_contiguous_inputs(fn, strided, fixed=()):
+    """fn(*strided inputs, *fixed) == fn(*their contiguous copies, *fixed), every output bit for bit"""
+    assert all(t is None or not t.is_contiguous() for t in strided)
+    dense = [None if t is None else t.contiguous() for t in strided]
+    first = next(t for t in strided if t is not None)
+    junk = [_poisoned(first)]
+    got = fn(*strided, *fixed)
+    junk.append(_poisoned(first))
+    want = fn(*dense, *fixed)
+    junk.append(_poisoned(first))
+    torch.cuda.synchronize()
+    got, want = (got, want) if isinstance(got, tuple) else ((got,), (want,))
+    assert len(got) == len(want) and len(got) >= 1
+    for a, b in zip(got, want):
+        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b)
+        assert not a.is_floating_point() or bool(torch.isfinite(a).all())
+
+
+def test_inline_copies_embedding_lerp(ops):
+    E, D, R = 64, 8, 257
+    torch.manual_seed(11)
+    w = torch.randn(E, D, device="cuda")
+    lo = torch.randint(0, E, (R,), device="cuda")
+    hi = torch.randint(0, E, (2 * R,), device="cuda")[::2]
+    frac = torch.rand(R, 3, device="cuda")[:, 1]
+    _same_on_strided_and_contiguous_inputs(lambda h, f: ops.embedding_lerp(w, lo, h, f), (hi, frac))
+    ref = w[lo] * (1 - frac[:, None]) + w[hi] * frac[:, None]
+    assert torch.equal(ops.embedding_lerp(w, lo, hi, frac), ref)  # (bit for bit, as in the test above)
+
+
+def test_inline_copies_render_weight_from_density(ops):
+    R, S = 257, 33
+    _, _, _, st, en, _ = _sample_rays(R, S, seed=31)
+    starts, ends = dev(st.T).t(), dev(en.T).t()                       # [R,S] views of [S,R] storage
+    sigmas = dev(synth.uniform((S, R), 0.0, 3.0, seed=32)).t()
+    _same_on_strided_and_contiguous_inputs(ops.render_weight_from_density, (starts, ends, sigmas))
+
+
+def test_inline_copies_power_sampler(ops):
+    R, S = 257, 33
+    fars = dev(synth.uniform((R, 2), 10.0, 300.0, seed=33))[:, 0]
+    nears = dev(synth.uniform((2 * R,), 0.0, 2.0, seed=34))[::2]
+    _same_on_strided_and_contiguous_inputs(lambda n, f: ops.power_sampler(n, f, S), (nears, fars))
+    _same_on_strided_and_contiguous_inputs(lambda n, f: ops.power_sampler(n, f, S), (None, fars))
+
+
+def test_inline_copies_actor_pair_positions(ops):
+    from test_gpu_actors import make_field
+
+    R, S, P = 257, 8, 1025
+    spec = make_field().hashgrid.actor_spec()
+    o, d, area, st, en, _ = _sample_rays(R, S, seed=35, fars=60.0)
+    rays = tuple(dev(v) for v in (o, d, area, st, en))
+    torch.manual_seed(12)
+    times = (1.0 + torch.rand(R, 2, device="cuda"))[:, 0]  # within every actor's trajectory
+    flip = (torch.randint(0, 2, (2 * R,), device="cuda") * 2 - 1).float()[::2]
+    si = torch.randint(0, R * S, (P,), device="cuda")
+    ai = torch.randint(0, 3, (P,), device="cuda", dtype=torch.int32)
+    _same_on_strided_and_contiguous_inputs(lambda t, f: ops.actor_pair_positions(spec, *rays, t, si, ai, f), (times, flip))
+    _same_on_strided_and_contiguous_inputs(lambda t, f: ops.actor_pair_positions(spec, *rays, t, si, ai, f), (times, None))

@@ -107,3 +107,39 @@ def test_binned_table_gradient_choice_matches_the_four_call_sites_it_replaced(mo
     # a table the library cannot cut into slices (workspace 0): atomics, whatever the batch
     monkeypatch.setattr(ops, "call", lambda name, *args: None)
     assert ops._table_grad_workspace(C.c_int(0), 1 << 20, "cpu") is None
+
+
+def test_launch_marshalling_passes_addresses_null_scalars_and_structs_and_keeps_the_tensors():
+    """ops._c_args is the conversion ``launch`` and the workspace queries apply to their arguments: a tensor (an
+    nn.Parameter too) goes as its address, None as NULL, a ctypes structure by reference, everything else as it is; the
+    pair it returns holds the tensors, so they outlive the call that receives the addresses."""
+    import ctypes as C
+    import gc
+    import weakref
+
+    import torch
+
+    from neurad_studio_amd import _lib, ops
+
+    t = torch.arange(6, dtype=torch.float32)[::2].contiguous()  # (a copy nobody else holds, like _chk's)
+    p = torch.nn.Parameter(torch.ones(4))
+    g = _lib.Grid()
+    g.num_levels = 7
+    arr = (C.c_void_p * 2)(1, 2)
+    addr_t, addr_p, alive = t.data_ptr(), p.data_ptr(), (weakref.ref(t), weakref.ref(p))
+    held = ops._c_args((t, p, None, 5, 2.5, g, arr))
+    del t, p
+    gc.collect()
+    c_args, kept = held
+    assert c_args[0] == addr_t and c_args[1] == addr_p and type(c_args[0]) is int and type(c_args[1]) is int
+    assert c_args[2] is None                       # ctypes passes None as a NULL pointer
+    assert c_args[3] == 5 and type(c_args[3]) is int and c_args[4] == 2.5 and type(c_args[4]) is float
+    assert type(c_args[5]) is type(C.byref(g)) and c_args[5]._obj is g
+    assert C.cast(c_args[5], C.POINTER(_lib.Grid)).contents.num_levels == 7
+    assert c_args[6] is arr
+    assert len(c_args) == 7
+    # the tensors live as long as the returned pair does, and no longer
+    assert alive[0]() is kept[0] and alive[1]() is kept[1] and kept[0].data_ptr() == addr_t
+    del held, c_args, kept
+    gc.collect()
+    assert alive[0]() is None and alive[1]() is None
