@@ -740,6 +740,32 @@ int nrhip_packed_composite_bwd(const float* t_starts, const float* t_ends, const
                                float* grad_sigmas_or_alphas /*[M], may be NULL*/, float* grad_features /*[M,C], may be NULL*/,
                                void* stream);
 
+/* ---- F1+C1 packed, fused: nrhip_render_fwd_ex for the march's packed samples -- the field evaluated on every sample and
+ *      composited as nrhip_packed_composite_fwd does (no sky-residual sample, depth = sum w (t_start + t_end) / 2 over all
+ *      samples, an empty segment writes zeros to its three output rows: the caller does not pre-zero), in ONE kernel:
+ *      one wavefront per ray in tiles of 16 samples, origins / directions / pixel area read PER RAY (no per-sample copy
+ *      exists on this path), no per-sample feature ever written.  Static scene, inference; instantiated for every
+ *      `Composite, Static` row of csrc/render_variants.h with fp32 or fp16-pair products (NRHIP_MLP_PAIRS as for
+ *      nrhip_render_fwd_ex), fp32 and fp16 tables.  early_stop_eps as nrhip_render_fwd_ex (tile-granular; weights of the
+ *      skipped samples are written as 0; 0 = exact).  n_rays == 0 is a no-op that reads no pointer; n_samples == 0 reads
+ *      no sample pointer and no segment and still zeroes the per-ray outputs; n_samples >= 2^31 is NRHIP_ERR_UNSUPPORTED.
+ *      No allocation, no host synchronisation (graph-capturable).  PRECONDITION (not checked): segments is
+ *      non-decreasing from 0 to n_samples.                                                                              */
+typedef struct {
+  int64_t n_rays;            /* R */
+  int64_t n_samples;         /* M = segments[R]; < 2^31 */
+  const float* origins;      /* [R,3] */
+  const float* directions;   /* [R,3] */
+  const float* pixel_area;   /* [R]   */
+  const float* t_starts;     /* [M]   */
+  const float* t_ends;       /* [M]   */
+  const int64_t* segments;   /* [R+1], as nrhip_packed_segments / the march produce */
+  const int32_t* order;      /* optional [R]: processing order (see nrhip_rays.order) */
+} nrhip_packed_rays;
+int nrhip_render_fwd_packed(const nrhip_field* f, const nrhip_packed_rays* rays, float* out_features /*[R,32]*/,
+                            float* out_depth /*[R]*/, float* out_acc /*[R]*/, float* out_weights /*[M] or NULL*/,
+                            float early_stop_eps, void* stream);
+
 /* ---- S5+M1 fused: ProposalNetworkSampler as driven by NeuRADModel._get_ray_samples
  *      (ray_samplers.py:623-666, models/neurad.py:443-459).  One wave marches one ray through
  *      power bins -> (density -> weights -> pdf resample) x n_rounds, entirely on chip.

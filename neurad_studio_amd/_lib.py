@@ -34,6 +34,12 @@ class Rays(C.Structure):
                 ("ends", C.c_void_p), ("sample_stride", C.c_int32), ("order", C.c_void_p)]
 
 
+class PackedRays(C.Structure):  # nrhip_packed_rays
+    _fields_ = [("n_rays", C.c_int64), ("n_samples", C.c_int64), ("origins", C.c_void_p), ("directions", C.c_void_p),
+                ("pixel_area", C.c_void_p), ("t_starts", C.c_void_p), ("t_ends", C.c_void_p), ("segments", C.c_void_p),
+                ("order", C.c_void_p)]
+
+
 class Field(C.Structure):
     _fields_ = [("grid", Grid), ("table", C.c_void_p), ("static_scale", C.c_float), ("geo", Mlp), ("feat", Mlp),
                 ("use_sdf", C.c_int32), ("beta", C.c_float), ("eval_table", C.c_void_p),
@@ -182,6 +188,7 @@ PROTOTYPES = {
     "nrhip_composite_bwd": [P, P, P, P, P, P, P, I64, I32, I32, P, P, P],
     "nrhip_render_fwd": [C.POINTER(Field), C.POINTER(Rays), P, P, P, P, P],
     "nrhip_render_fwd_ex": [C.POINTER(Field), C.POINTER(Rays), P, P, P, P, F32, P],
+    "nrhip_render_fwd_packed": [C.POINTER(Field), C.POINTER(PackedRays), P, P, P, P, F32, P],
     "nrhip_ray_order": [P, P, I64, F32, F32, I32, P, P],
     "nrhip_ray_order_workspace": [I64, I32, C.POINTER(I64)],
     "nrhip_ray_order_large": [P, P, I64, F32, F32, I32, P, I64, P, P],

@@ -94,7 +94,8 @@ extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
 // nrhip_packed_accumulate (+ _bwd), nrhip_packed_composite_fwd / _bwd.
 // 513: occupancy-grid maintenance: nrhip_occgrid_march_levels, nrhip_occgrid_update_workspace / _candidates / _apply,
 //      nrhip_occgrid_mark_invisible
-extern "C" int nrhip_version(void) { return 513; }
+// 514: nrhip_render_fwd_packed (+ nrhip_packed_rays): the fused render kernel on packed samples
+extern "C" int nrhip_version(void) { return 514; }
 
 extern "C" int nrhip_tuning_reload(void) {
   nrhip::g_tuning = nrhip::read_tuning();

@@ -37,6 +37,11 @@
 //     index wins, features zero-padded to 32) and feeds its box-frame direction to the SH encoding.  The ray's candidate
 //     list (nrhip_actor_prepare) is walked with scalar loads -- empty for most rays -- and only tiles that contain a hit
 //     replace the per-ray SH bias row by four extra k-steps with per-sample SH values.
+//   * PACKED SAMPLES (Lay::Packed instantiations, eval: nrhip_render_fwd_packed): the occupancy march's ragged output.  A
+//     ray's base and sample count are two scalar loads of `segments`; the pipeline's "wrap to the next ray" decisions use the
+//     PENDING ray's own tile count; the ray constants stay per ray, so no per-sample copy of them and no per-sample feature
+//     exists anywhere on the route.  Compositing is nrhip_packed_composite_fwd's: no sky residual, depth over all samples,
+//     zeros for a ray without samples (which costs one dead tile's gathers and no MLP).
 // The sky residual (models/neurad.py:381: w_{S-1} += 1 - sum w) is folded into the last tile -- the accumulated weight is
 // complete there, so no copy of the last sample's features has to be kept.
 #include "common.h"
@@ -540,6 +545,33 @@ __device__ __forceinline__ void load_pending(PendingTile& p, int64_t pos, int t,
   p.ncand = cand_count ? cand_count[ray] : 0;
 }
 
+// Lay::Packed: ray r owns the samples [segs[r], segs[r + 1]) of the [M]-shaped interval arrays, M = rr.S >= 1 (a batch
+// without samples never reaches the kernel).  The index of every load stays inside [0, M): a lane past the ray's end reads
+// the ray's last sample; an empty segment gives b - 1 <= M - 1, which is -1 only for b == 0, where sample 0 stands in.
+// The last clamp holds the reads inside the arrays even for segments that break their precondition.
+__device__ __forceinline__ void load_pending_packed(PendingTile& p, int64_t pos, int t, const RayRange& rr, int j,
+                                                    const int32_t* __restrict__ order, const float* __restrict__ ro,
+                                                    const float* __restrict__ rd, const float* __restrict__ rarea,
+                                                    const float* __restrict__ rstarts, const float* __restrict__ rends,
+                                                    const int64_t* __restrict__ segs, int& first, int& count) {
+  p.pos = pos, p.t = t, p.valid = pos < rr.end;
+  const int64_t pc = p.valid ? pos : rr.end - 1;
+  const int64_t ray = order ? (int64_t)order[pc] : pc;
+  p.ray = ray;
+  const int b = (int)segs[ray], n = (int)segs[ray + 1] - b;  // (M < 2^31)
+  first = b, count = n;
+  const int s = p.valid ? 16 * t + j : j;
+  int si = b + (s < n ? s : n - 1);
+  si = si < 0 ? 0 : si;
+  si = si < rr.S ? si : rr.S - 1;
+  p.t0 = rstarts[si];
+  p.t1 = rends[si];
+  p.ox = ro[3 * ray], p.oy = ro[3 * ray + 1], p.oz = ro[3 * ray + 2];
+  p.dx = rd[3 * ray], p.dy = rd[3 * ray + 1], p.dz = rd[3 * ray + 2];
+  p.area = rarea[ray];
+  p.ncand = 0;
+}
+
 // H2 + H3 + the hash of H1 for one pending tile, then all gathers issued back to back (no waits in here beyond the
 // pending tile's own small loads, which were issued a whole tile earlier).
 // hash_corners with the level's own multipliers and mask (eval_layout.hip): the reference hash for the levels that keep it,
@@ -737,9 +769,11 @@ __device__ __forceinline__ void blend_tile(const TileFetch<EncFrame<L, F>::LPL, 
   for (int k = EF::W; k < 8; ++k) feat[k] = 0.f;  // padding slots of the frame
 }
 
-// L levels, F features/level (L*F <= 32, see EncFrame), H hidden width, HALF = fp16 table; OUT / SRC / PROD: the variant
-// (render_variants.h).
-template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD>
+// L levels, F features/level (L*F <= 32, see EncFrame), H hidden width, HALF = fp16 table; OUT / SRC / PROD / LAY: the
+// variant (render_variants.h).  Lay::Packed takes the sample count M in `S` and the segments [R + 1] through `tables`
+// (no new argument: the existing kernels keep their argument block), and composites as nrhip_packed_composite_fwd does:
+// no sky-residual sample, depth over all samples, zeros for a ray without samples.
+template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD, Lay LAY = Lay::Dense>
 __global__ __launch_bounds__(256, 2) void render_kernel(
     FieldDev fd, int64_t n_rays, int S, int stride, const int32_t* __restrict__ order, const float* __restrict__ ro,
     const float* __restrict__ rd, const float* __restrict__ rarea, const float* __restrict__ rstarts,
@@ -750,11 +784,13 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     const int32_t* __restrict__ cand_actor, const float* __restrict__ cand_w2b, const float* __restrict__ bounds,
     const void* const* __restrict__ tables) {
   using EF = EncFrame<L, F>;  // (asserts L * F <= 32 in whole levels per lane group)
-  static_assert(render_variant_ok(L, F, OUT, SRC, PROD), "not a legal variant: see render_variant_ok");
+  static_assert(render_variant_ok(L, F, OUT, SRC, PROD, LAY), "not a legal variant: see render_variant_ok");
   static_assert(H % 16 == 0 && H >= 16 && H <= 128, "hidden width");
   constexpr bool COMPOSITE = OUT == Out::Composite;
   constexpr bool ACT = SRC == Src::Actors, RELAY = SRC == Src::EvalTable, OVR = SRC == Src::Overrides;
   constexpr bool PAIRS = PROD == Prod::F16Pairs;
+  constexpr bool PACKED = LAY == Lay::Packed;
+  const int64_t* const segs = reinterpret_cast<const int64_t*>(tables);  // PACKED: [R + 1]
   // OVR (training forward of a scene with dynamic actors): samples inside an actor box take their encoding row and view
   // direction from the caller (the differentiable actor branch computed them for the few hit samples) instead of the
   // static lookup.  The three actor-only pointer arguments carry the overrides:
@@ -813,14 +849,20 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
   int ta = -1;  // ACT: candidate slot of the actor containing this lane's sample of the tile in `tf` (-1: none)
   const float* ascal_l = lds + Ld::ASCAL;
   PendingTile q;
-  load_pending(q, pos, 0, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
+  int qb = 0, qn = 0;  // PACKED: first sample and sample count of q's ray (wave-uniform)
+  auto tiles_of = [](int n) { return n > 16 ? (n + 15) >> 4 : 1; };  // PACKED: a ray without samples walks one dead tile
+  if constexpr (PACKED) load_pending_packed(q, pos, 0, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn);
+  else load_pending(q, pos, 0, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
   int64_t ray = q.ray;
+  int cb = 0, cn = 0;  // PACKED: first sample and sample count of the ray in `tf`
+  if constexpr (PACKED) cb = qb, cn = qn;
   if constexpr (ACT) issue_tile_actors<L, F, HALF>(fd, ad, q, g, mask, scal_l, ascal_l, cand_actor, cand_w2b, bounds, tables, tf, ta);
   else issue_tile<L, F, HALF, RELAY>(fd, q, g, mask, scal_l, tf, lay_l);
   if constexpr (OVR) ta = (q.valid && j < S) ? ovr_row[q.ray * S + j] : -1;  // override row of this lane's sample of `tf`
   {
-    const bool wrap = ntile == 1;
-    load_pending(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
+    const bool wrap = (PACKED ? tiles_of(cn) : ntile) == 1;
+    if constexpr (PACKED) load_pending_packed(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn);
+    else load_pending(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
   }
 
   // per-ray state
@@ -869,7 +911,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     asm volatile("" : "+v"(opaque));
     const float* lw = lds + opaque;
     const int s = 16 * t + j;
-    const bool live = s < S;
+    const bool live = s < (PACKED ? cn : S);
     const float t0 = tf.t0, t1 = tf.t1;
 
     // ---- blend the fetched corners (H1 + H4): the only wait on the gathers ---------------------------
@@ -924,25 +966,50 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
         stop_here = fd.use_sdf ? (c < stop_eps) : (c > -__logf(stop_eps));  // wave-uniform -> scalar branch
       }
     }
-    const bool last_tile = t == ntile - 1;
+    const bool last_tile = t == (PACKED ? tiles_of(cn) : ntile) - 1;
     const bool ray_done = last_tile || stop_here;
 
     // ---- issue the next tile's gathers: they fly while this tile runs through the MLPs ---------------
-    if (ray_done && q.valid && q.pos == pos)  // terminated early: q still points into this ray -> skip to the next ray
-      load_pending(q, pos + pos_step, 0, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);  // (one exposed round trip)
+    if (ray_done && q.valid && q.pos == pos) {  // terminated early: q still points into this ray -> skip to the next ray
+      // (one exposed round trip)
+      if constexpr (PACKED) load_pending_packed(q, pos + pos_step, 0, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn);
+      else load_pending(q, pos + pos_step, 0, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
+    }
     const bool have_next = q.valid;
     const int64_t npos = q.pos, nray = q.ray;
     const int nt = q.t;
+    int nb = 0, nn = 0;
+    if constexpr (PACKED) nb = qb, nn = qn;
     // unconditional (see load_pending)
     if constexpr (ACT) issue_tile_actors<L, F, HALF>(fd, ad, q, g, mask, scal_l, ascal_l, cand_actor, cand_w2b, bounds, tables, tf, ta);
     else issue_tile<L, F, HALF, RELAY>(fd, q, g, mask, scal_l, tf, lay_l);
     if constexpr (OVR) ta = (q.valid && 16 * q.t + j < S) ? ovr_row[q.ray * S + 16 * q.t + j] : -1;
     {
-      const bool wrap = nt + 1 == ntile;  // request the small loads of the tile after it
-      load_pending(q, wrap ? npos + pos_step : npos, wrap ? 0 : nt + 1, rr, j, order, ro, rd, rarea, rstarts, rends,
-                   cand_count);
+      const bool wrap = nt + 1 == (PACKED ? tiles_of(nn) : ntile);  // request the small loads of the tile after it
+      if constexpr (PACKED)
+        load_pending_packed(q, wrap ? npos + pos_step : npos, wrap ? 0 : nt + 1, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn);
+      else
+        load_pending(q, wrap ? npos + pos_step : npos, wrap ? 0 : nt + 1, rr, j, order, ro, rd, rarea, rstarts, rends,
+                     cand_count);
     }
     __builtin_amdgcn_sched_barrier(0);
+
+    if constexpr (PACKED) {
+      if (cn <= 0) {  // wave-uniform: a ray without samples writes its zeros and runs no MLP on the dead tile
+        if (j == 0) {
+          float* fp = out_feat + ray * 32;
+          *reinterpret_cast<f32x4*>(fp + 4 * g) = f32x4{0.f, 0.f, 0.f, 0.f};
+          *reinterpret_cast<f32x4*>(fp + 16 + 4 * g) = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (g == 0) {
+            out_acc[ray] = 0.f;
+            out_depth[ray] = 0.f;
+          }
+        }
+        if (!have_next) break;
+        pos = npos, ray = nray, t = nt, cb = nb, cn = nn;
+        continue;
+      }
+    }
 
     bool saving = false;
     int64_t srow = 0;
@@ -1112,15 +1179,17 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
         w = T * (1.f - expf(-sd));
         carry += __shfl(incl, (lane & 48) | 15, 64);
       }
-      if (out_w && live && g == 0) out_w[ray * S + s] = w;
+      if (out_w && live && g == 0) out_w[PACKED ? (int64_t)cb + s : ray * S + s] = w;
       // ---- C2 accumulation ------------------------------------------------------------------------
       acc_w += w;
-      if (s < S - 1) acc_d += w * ((t0 + t1) / 2.f);
-      float wf = w;  // weight of this sample's FEATURES: the sky residual 1 - sum w goes on sample S-1
+      if (PACKED || s < S - 1) acc_d += w * ((t0 + t1) / 2.f);  // (PACKED: every sample; a dead lane has w = 0)
+      float wf = w;  // weight of this sample's FEATURES: the sky residual 1 - sum w goes on sample S-1 (not PACKED)
       float acc = 0.f;
       if (ray_done) {
         acc = row_sum16(acc_w);
-        if (last_tile && s == S - 1) wf += 1.f - acc;
+        if constexpr (!PACKED) {
+          if (last_tile && s == S - 1) wf += 1.f - acc;
+        }
       }
 #pragma unroll
       for (int k = 0; k < H / 4; ++k) ha[k] = fmaf(hb[k], wf, ha[k]);
@@ -1133,9 +1202,10 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
       if (ray_done) {
         const float dep = row_sum16(acc_d);
         if (!last_tile && out_w)  // terminated early: the rest of the ray contributes nothing
-          for (int s2 = 16 * (t + 1) + lane; s2 < S; s2 += 64) out_w[ray * S + s2] = 0.f;
-        // features = fw2 . (sum w h2) + fb2 * sum w' + sum w' e ;  sum w' = acc + (1 - acc) on a completed ray
-        const float wsum = last_tile ? acc + (1.f - acc) : acc;
+          for (int s2 = 16 * (t + 1) + lane; s2 < (PACKED ? cn : S); s2 += 64)
+            out_w[(PACKED ? (int64_t)cb : ray * S) + s2] = 0.f;
+        // features = fw2 . (sum w h2) + fb2 * sum w' + sum w' e ;  sum w' = acc + (1 - acc) on a completed ray (PACKED: acc)
+        const float wsum = (!PACKED && last_tile) ? acc + (1.f - acc) : acc;
         f32x4 of2[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
         mfma_layer<2, H / 4>(lw + Ld::F2, lane, ha, of2);
 #pragma unroll
@@ -1161,6 +1231,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
 
     if (!have_next) break;
     pos = npos, ray = nray, t = nt;
+    if constexpr (PACKED) cb = nb, cn = nn;
   }
 }
 
@@ -1248,16 +1319,17 @@ struct RenderArgs {
   SaveDev sv;
   float stop_eps;
   const int32_t* range;  // [2] device: slice of the processing order (NULL = all rays)
+  const int64_t* segments;  // Lay::Packed: [R + 1] device
   ActorLaunch actors;
   OverrideLaunch ovr;
   hipStream_t stream;
 };
 
-template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD>
+template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD, Lay LAY = Lay::Dense>
 static int launch_render(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
-  constexpr bool OVR = SRC == Src::Overrides;
+  constexpr bool OVR = SRC == Src::Overrides, PACKED = LAY == Lay::Packed;
   constexpr size_t lds = ((SRC == Src::Actors || OVR) ? Lds<H, PROD>::TOTAL_ACT : Lds<H, PROD>::TOTAL) * sizeof(float);
-  auto kern = render_kernel<L, F, H, HALF, OUT, SRC, PROD>;
+  auto kern = render_kernel<L, F, H, HALF, OUT, SRC, PROD, LAY>;
   static int cap = 0;  // persistent grid: CUs x resident workgroups per CU, queried once per instantiation
   if (!cap) {
     if (lds > 64 * 1024)
@@ -1271,11 +1343,13 @@ static int launch_render(const FieldDev& fd, const RaysDev& rd, const RenderArgs
   const int64_t want = (rd.R + 3) / 4;
   const int blocks = (int)(want < cap ? want : cap);
   const ActorLaunch& al = a.actors;
-  // (the override kernel reads its three arrays through the actor kernel's pointer arguments: see render_kernel)
+  // (the override kernel reads its three arrays through the actor kernel's pointer arguments, the packed kernel its
+  // segments through the last of them and M = rd.S: see render_kernel)
   kern<<<blocks, 256, lds, a.stream>>>(fd, rd.R, rd.S, rd.stride, rd.order, rd.o, rd.d, rd.area, rd.starts, rd.ends, a.feat,
                                        a.depth, a.acc, a.w, a.sdf, a.alpha, a.sv, a.stop_eps, a.range, al.ad,
                                        OVR ? a.ovr.row : al.cand_count, al.cand_actor, OVR ? a.ovr.rows : al.cand_w2b,
-                                       OVR ? a.ovr.dirs : al.bounds, al.tables);
+                                       OVR ? a.ovr.dirs : al.bounds,
+                                       PACKED ? reinterpret_cast<const void* const*>(a.segments) : al.tables);
   return check_launch("render/field fused kernel");
 }
 
@@ -1331,6 +1405,34 @@ static int dispatch_render(const nrhip_field* f, const nrhip_rays* rays, Out out
             src == Src::Actors ? "fused field kernel with actors" : src == Src::Overrides ? "field_fwd_train_ovr"
                                                                                           : "fused field kernel",
             v.L, v.F, v.H);
+  return NRHIP_ERR_UNSUPPORTED;
+}
+
+// A row of the table in the packed layout, where render_variant_ok admits it (the packed kernels have no rows of their own)
+template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD>
+static int launch_packed_row(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
+  if constexpr (render_variant_ok(L, F, OUT, SRC, PROD, Lay::Packed)) {
+    return launch_render<L, F, H, HALF, OUT, SRC, PROD, Lay::Packed>(fd, rd, a);
+  } else {
+    set_error("fused field kernel: no packed form of this variant");
+    return NRHIP_ERR_UNSUPPORTED;
+  }
+}
+
+// dispatch_render for packed samples: choose_variant's preference among the rows that have a packed form (the fp16
+// pairs where the table has them, else the fp32 MFMA).  rd.S carries M, a.segments the segments.
+static int dispatch_render_packed(const nrhip_field* f, const RaysDev& rd, const RenderArgs& a) {
+  Variant v = choose_variant(f, Out::Composite, Src::Static);
+  if (!render_variant_ok(v.L, v.F, v.out, v.src, v.prod, Lay::Packed)) v.src = Src::Static, v.prod = Prod::F32;
+  const FieldDev fd = to_dev(*f);
+  const bool half = f->grid.param_dtype == 1;
+#define X(L_, F_, H_, O_, S_, P_)                                                                \
+  if (same(v, {L_, F_, H_, Out::O_, Src::S_, Prod::P_}))                                         \
+    return half ? launch_packed_row<L_, F_, H_, true, Out::O_, Src::S_, Prod::P_>(fd, rd, a)     \
+                : launch_packed_row<L_, F_, H_, false, Out::O_, Src::S_, Prod::P_>(fd, rd, a);
+  NRHIP_RENDER_VARIANTS(X)
+#undef X
+  set_error("fused field kernel: no instantiation for L=%d F=%d H=%d", v.L, v.F, v.H);
   return NRHIP_ERR_UNSUPPORTED;
 }
 
@@ -1446,6 +1548,37 @@ extern "C" int nrhip_render_fwd_ex(const nrhip_field* f, const nrhip_rays* rays,
 extern "C" int nrhip_render_fwd(const nrhip_field* f, const nrhip_rays* rays, float* out_features, float* out_depth,
                                 float* out_acc, float* out_weights, void* stream) {
   return nrhip_render_fwd_ex(f, rays, out_features, out_depth, out_acc, out_weights, 0.f, stream);
+}
+
+extern "C" int nrhip_render_fwd_packed(const nrhip_field* f, const nrhip_packed_rays* rays, float* out_features,
+                                       float* out_depth, float* out_acc, float* out_weights, float early_stop_eps,
+                                       void* stream) {
+  if (int e = validate_field(f)) return e;
+  NR_REQUIRE(rays, NRHIP_ERR_INVALID_ARG, "render_fwd_packed: rays descriptor is NULL");
+  const int64_t R = rays->n_rays, M = rays->n_samples;
+  NR_REQUIRE(R >= 0 && M >= 0, NRHIP_ERR_INVALID_ARG, "render_fwd_packed: negative ray/sample count");
+  if (R == 0) return NRHIP_OK;
+  NR_REQUIRE(out_features && out_depth && out_acc, NRHIP_ERR_INVALID_ARG, "render_fwd_packed: NULL output");
+  NR_REQUIRE(early_stop_eps >= 0.f && early_stop_eps < 1.f, NRHIP_ERR_INVALID_ARG,
+             "render_fwd_packed: early_stop_eps %g not in [0,1)", (double)early_stop_eps);
+  NR_REQUIRE(M < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "render_fwd_packed: M >= 2^31");
+  hipStream_t st = (hipStream_t)stream;
+  if (M == 0) {  // every segment is empty: no sample pointer (and no segment) is read, the per-ray outputs are zeroed
+    if (hipMemsetAsync(out_features, 0, (size_t)R * 32 * sizeof(float), st) != hipSuccess ||
+        hipMemsetAsync(out_depth, 0, (size_t)R * sizeof(float), st) != hipSuccess ||
+        hipMemsetAsync(out_acc, 0, (size_t)R * sizeof(float), st) != hipSuccess) {
+      set_error("render_fwd_packed: zeroing the outputs failed");
+      return NRHIP_ERR_LAUNCH;
+    }
+    return NRHIP_OK;
+  }
+  NR_REQUIRE(rays->origins && rays->directions && rays->pixel_area && rays->t_starts && rays->t_ends && rays->segments,
+             NRHIP_ERR_INVALID_ARG, "render_fwd_packed: rays descriptor has a NULL pointer");
+  RenderArgs a{};
+  a.feat = out_features, a.depth = out_depth, a.acc = out_acc, a.w = out_weights;
+  a.stop_eps = early_stop_eps, a.stream = st, a.segments = rays->segments;
+  const RaysDev rd{R, (int)M, 0, rays->origins, rays->directions, rays->pixel_area, rays->t_starts, rays->t_ends, rays->order};
+  return dispatch_render_packed(f, rd, a);
 }
 
 extern "C" int nrhip_render_fwd_actors(const nrhip_field* f, const nrhip_actors* a, const nrhip_rays* rays,

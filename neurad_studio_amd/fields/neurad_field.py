@@ -159,6 +159,12 @@ class NeuRADField(nn.Module):
         return ((g.num_levels, g.features_per_level) in _FUSED_GRIDS and c.geo_num_layers == 2 and c.nff_num_layers == 3
                 and c.geo_hidden_dim == c.nff_hidden_dim and c.geo_hidden_dim in (32, 64) and c.nff_out_dim == 32)
 
+    def fused_packed_supported(self) -> bool:
+        """Can the fused render kernel composite this field's PACKED samples (``render_packed``)?  The static scene of every
+        field ``fused_supported`` covers: the packed kernels are the table's composited static rows (csrc/render_variants.h:
+        render_variant_ok); scenes with dynamic actors take the operator path."""
+        return not self.hashgrid.has_actors() and self.fused_supported()
+
     def train(self, mode: bool = True):
         """a mode switch drops the cached host copy of beta: writes through ``beta.data`` (EMA / weight averaging, some
         optimizers) do not bump the version counter the cache is keyed on, and they happen between training and eval"""
@@ -214,6 +220,31 @@ class NeuRADField(nn.Module):
                                          return_weights, early_stop_eps=early_stop_eps, order=order)
         return ops.render_fwd(self.field_spec(), origins, directions, pixel_area, starts, ends, return_weights,
                               early_stop_eps=early_stop_eps, order=order)
+
+    def render_packed(self, origins, directions, pixel_area, t_starts, t_ends, *, segments: Optional[Tensor] = None,
+                      ray_indices: Optional[Tensor] = None, num_rays: Optional[int] = None, return_weights=False,
+                      early_stop_eps: float = 0.0, order: Optional[Tensor] = None):
+        """``render`` for the packed samples of an occupancy march, one kernel: per-RAY origins / directions [R,3] and
+        pixel_area [R] (or [R,1]), per-sample t_starts / t_ends [M], and exactly one of ``segments`` int64 [R+1] or
+        ``ray_indices`` int64 [M] (sorted) + ``num_rays``.  -> features [R,32], depth [R,1] (sum w mid), accumulation [R,1]
+        (, weights [M]), composited as renderers.render_packed does (no sky residual; a ray without samples gets zeros).
+        Inference only: training goes through forward() + renderers.render_packed."""
+        if (segments is None) == (ray_indices is None):
+            raise ValueError("render_packed: give exactly one of segments / ray_indices (+ num_rays)")
+        if ray_indices is not None and num_rays is None:
+            raise ValueError("render_packed: ray_indices needs num_rays")
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or any(
+                isinstance(t, Tensor) and t.requires_grad for t in (origins, directions, t_starts, t_ends))):
+            raise RuntimeError("render_packed has no backward: call it under torch.no_grad(); a grad-enabled call goes "
+                               "through forward() on the packed RaySamples + renderers.render_packed")
+        if not self.fused_packed_supported():
+            raise NotImplementedError("fused packed render kernel: static scenes of the fused configurations only; use the "
+                                      "operator path, forward() on the packed RaySamples + renderers.render_packed")
+        with torch.no_grad():
+            if segments is None:
+                segments = ops.packed_segments(ray_indices, int(num_rays))
+            return ops.render_fwd_packed(self.field_spec(), origins, directions, pixel_area, t_starts, t_ends, segments,
+                                         return_weights, early_stop_eps=early_stop_eps, order=order)
 
     def render_train(self, origins, directions, pixel_area, edges, appearance=None, times: Optional[Tensor] = None,
                      actor_cand=None):

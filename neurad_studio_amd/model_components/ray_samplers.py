@@ -211,10 +211,8 @@ class VolumetricSampler(Sampler):
         raise RuntimeError("The VolumetricSampler fuses sample generation and density check together. "
                            "Please call forward() directly.")
 
-    def forward(self, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0,
-                far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0):
-        from ..cameras.rays import Frustums
-
+    def _march(self, ray_bundle: RayBundle, render_step_size, near_plane, far_plane, alpha_thre, cone_angle):
+        """-> contiguous origins, directions and the march's packed (ray_indices, starts, ends)"""
         rays_o, rays_d = ray_bundle.origins.contiguous(), ray_bundle.directions.contiguous()
         t_min = t_max = None
         if ray_bundle.nears is not None and ray_bundle.fars is not None:
@@ -225,10 +223,23 @@ class VolumetricSampler(Sampler):
             alpha_fn=self._wrap(self.alpha_fn, rays_o, rays_d, ray_bundle.times), render_step_size=render_step_size,
             near_plane=near_plane, far_plane=1e10 if far_plane is None else far_plane, stratified=self.training,
             cone_angle=cone_angle, alpha_thre=alpha_thre)
+        return rays_o, rays_d, ray_indices, starts, ends
+
+    def forward(self, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0,
+                far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0):
+        rays_o, rays_d, ray_indices, starts, ends = self._march(ray_bundle, render_step_size, near_plane, far_plane,
+                                                                alpha_thre, cone_angle)
         if starts.shape[0] == 0:  # single fake sample (ray_samplers.py:541-547)
             ray_indices = torch.zeros((1,), dtype=torch.long, device=rays_o.device)
             starts = torch.ones((1,), dtype=torch.float32, device=rays_o.device)
             ends = torch.ones((1,), dtype=torch.float32, device=rays_o.device)
+        return self._gather(ray_bundle, rays_o, rays_d, ray_indices, starts, ends), ray_indices
+
+    @staticmethod
+    def _gather(ray_bundle: RayBundle, rays_o, rays_d, ray_indices, starts, ends) -> RaySamples:
+        """the packed RaySamples [M,1]: per-sample copies of the bundle's per-ray tensors"""
+        from ..cameras.rays import Frustums
+
         ray_samples = RaySamples(frustums=Frustums(origins=rays_o[ray_indices], directions=rays_d[ray_indices],
                                                    starts=starts[..., None], ends=ends[..., None],
                                                    pixel_area=ray_bundle.pixel_area[ray_indices]),
@@ -236,4 +247,37 @@ class VolumetricSampler(Sampler):
                                  else ray_bundle.camera_indices[ray_indices])
         if ray_bundle.times is not None:
             ray_samples.times = ray_bundle.times[ray_indices]
-        return ray_samples, ray_indices
+        return ray_samples
+
+    @torch.no_grad()
+    def render(self, field, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0,
+               far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0,
+               early_stop_eps: float = 0.0) -> dict:
+        """Eval: march + field + compositing -> ``features`` [R,32], ``depth`` [R,1] (sum w mid), ``accumulation`` [R,1],
+        ``weights`` [M,1] and the march's ``ray_indices`` / ``t_starts`` / ``t_ends`` [M].  A field with a packed fused
+        kernel (``fused_packed_supported``) gets the BUNDLE'S per-ray tensors and the packed intervals in one kernel: no
+        per-sample copy of origins / directions / pixel area, no per-sample feature.  Any other field takes forward() on
+        the gathered RaySamples + renderers.render_packed: the same keys.  A march without samples returns zero rows (the
+        single fake sample of forward() serves its callers' shapes and is not needed here).  early_stop_eps: the fused
+        route's ray termination (see ops.render_fwd); the operator route is exact."""
+        if self.training:
+            raise RuntimeError("VolumetricSampler.render is the eval route; training calls forward() + renderers.render_packed")
+        R = ray_bundle.origins.shape[0]
+        rays_o, rays_d, ri, starts, ends = self._march(ray_bundle, render_step_size, near_plane, far_plane, alpha_thre,
+                                                       cone_angle)
+        marched = {"ray_indices": ri, "t_starts": starts, "t_ends": ends}
+        if getattr(field, "fused_packed_supported", lambda: False)():
+            f, d, a, w = field.render_packed(rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri, num_rays=R,
+                                             return_weights=True, early_stop_eps=early_stop_eps)
+            return {"features": f, "depth": d, "accumulation": a, "weights": w[:, None], **marched}
+        from ..field_components.field_heads import FieldHeadNames
+        from .renderers import render_packed
+
+        if starts.shape[0] == 0:
+            z = lambda c: torch.zeros((R, c), device=rays_o.device, dtype=torch.float32)  # noqa: E731
+            return {"features": z(field.config.nff_out_dim), "depth": z(1), "accumulation": z(1),
+                    "weights": starts.new_zeros((0, 1)), **marched}
+        rs = self._gather(ray_bundle, rays_o, rays_d, ri, starts, ends)
+        out = field(rs)
+        kw = {"alpha": out[FieldHeadNames.ALPHA]} if FieldHeadNames.ALPHA in out else {"density": out[FieldHeadNames.DENSITY]}
+        return {**render_packed(out[FieldHeadNames.FEATURE], rs, ri, R, **kw), **marched}

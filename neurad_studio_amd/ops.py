@@ -1399,6 +1399,35 @@ def packed_composite_fwd(t_starts, t_ends, sigmas_or_alphas, features, segments,
     return of, od, oa, ow
 
 
+def render_fwd_packed(fs: FieldSpec, origins, directions, pixel_area, t_starts, t_ends, segments,
+                      return_weights: bool = False, early_stop_eps: float = 0.0, order: Optional[Tensor] = None):
+    """The fused render kernel on the march's packed samples: per-RAY origins [R,3] / directions [R,3] / pixel_area [R],
+    per-sample t_starts / t_ends [M], segments int64 [R+1] -> features [R,32], depth [R,1] (sum w mid, not normalised),
+    accumulation [R,1] (, weights [M]); compositing as ``packed_composite_fwd`` (no sky residual, zeros for a ray without
+    samples).  early_stop_eps / order: see ``render_fwd``."""
+    o, d = _chk(origins, "origins"), _chk(directions, "directions")
+    a = _chk(pixel_area.reshape(-1), "pixel_area")
+    seg, R = _seg(segments)
+    if o.shape != (R, 3) or d.shape != (R, 3) or a.shape != (R,):
+        raise ValueError(f"render_fwd_packed: origins / directions [R,3] and pixel_area [R] with R = {R} = len(segments) - 1")
+    s = _flat(t_starts, "t_starts")
+    e = _flat(t_ends, "t_ends", s.shape[0])
+    r = _lib.PackedRays()
+    r.n_rays, r.n_samples = R, s.shape[0]
+    r.origins, r.directions, r.pixel_area = o.data_ptr(), d.data_ptr(), a.data_ptr()
+    r.t_starts, r.t_ends, r.segments = s.data_ptr(), e.data_ptr(), seg.data_ptr()
+    if order is not None:
+        order = _chk(order, "order", torch.int32)
+        if order.shape != (R,):
+            raise ValueError(f"order must be int32 [R={R}], got {tuple(order.shape)}")
+        r.order = order.data_ptr()
+    f, keep = fs.c_field()
+    feats, depth, acc, _ = _render_outputs(R, 0, o.device, False)
+    w = torch.empty_like(s) if return_weights else None
+    launch("nrhip_render_fwd_packed", f, r, feats, depth, acc, w, float(early_stop_eps))
+    return (feats, depth, acc, w) if return_weights else (feats, depth, acc)
+
+
 def packed_composite_bwd(t_starts, t_ends, sigmas_or_alphas, features, segments, density_mode: bool, g_features,
                          g_depth=None, g_accumulation=None, g_weights=None, need_grad_x=True, need_grad_features=True):
     """-> (grad sigmas / alphas [M] or None, grad features [M,C] or None)"""
