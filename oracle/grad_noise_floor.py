@@ -28,7 +28,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), HERE]
 import numpy as np
 import torch
 
-import test_gpu_reference_plugin as t
+import plugin_harness as t
 
 PERTURBED_TRIALS = int(os.environ.get("NRHIP_FLOOR_TRIALS", "8"))
 t.ref_import.install()
@@ -36,13 +36,13 @@ os.environ["NERFSTUDIO_METHOD_CONFIGS"] = "neurad-hip=neurad_studio_amd.integrat
 import nerfstudio.models.neurad as ref_neurad
 
 ref_neurad.VGGPerceptualLossPix2Pix = torch.nn.Identity
-torch.nn.Module.to = lambda self, *a, **k: self  # (_build_pair moves the plugin to cuda: not here)
+torch.nn.Module.to = lambda self, *a, **k: self  # (build_pair moves the plugin to cuda: not here)
 
 
 def step(m, b, dt, origin_noise=None):
     m.zero_grad(set_to_none=True)
-    rb = t._bundle(b, "cpu")
-    lab = t._labels(b, "cpu")
+    rb = t.bundle(b, "cpu")
+    lab = t.labels(b, "cpu")
     if origin_noise is not None:
         rb.origins = rb.origins * origin_noise
     if dt == torch.float64:
@@ -76,11 +76,11 @@ def main():
             continue
         if True:
             kw = dict(pose_opt=pose, n_actors=na, fp16_tables=na == 32)  # (actors32: tables hold fp16-representable values)
-            _, m32 = t._build_pair(ref_neurad, wa, **kw)
-            _, m64 = t._build_pair(ref_neurad, wa, **kw)
+            _, m32 = t.build_pair(ref_neurad, wa, **kw)
+            _, m64 = t.build_pair(ref_neurad, wa, **kw)
             m64 = m64.double()
-            b = t._batch(wa, n_actors=na)
-            t._deterministic(m32, True), t._deterministic(m64, True)
+            b = t.batch(wa, n_actors=na)
+            t.deterministic(m32, True), t.deterministic(m64, True)
             rb32, l32 = step(m32, b, torch.float32)
             rb64, l64 = step(m64, b, torch.float64)
             f64 = t.per_loss_gradient_errors(m32, l32, m64, l64, detail=True)
@@ -88,8 +88,8 @@ def main():
                 f64["__ray_grads__"] = [t.rel_l2(t.N(a), t.N(c)) for a, c in zip(ray_grads(rb32, l32), ray_grads(rb64, l64))]
             pert = {}
             for trial in range(PERTURBED_TRIALS):
-                _, mp = t._build_pair(ref_neurad, wa, **kw)
-                t._deterministic(mp, True)
+                _, mp = t.build_pair(ref_neurad, wa, **kw)
+                t.deterministic(mp, True)
                 g = torch.Generator().manual_seed(1000 + trial)
                 with torch.no_grad():
                     for n, p in mp.named_parameters():

@@ -1,5 +1,5 @@
 """Which half of mixed precision moves the plugin's K-iteration loop away from the reference's fp32 loop (static scene, full
-learning rates, tests/test_gpu_plugin_train_loop.py's harness): autocast alone, GradScaler alone, both, neither.
+learning rates, tests/plugin_harness.py): autocast alone, GradScaler alone, both, neither.
 usage (GPU box): python scripts/amp_drift_probe.py > gpurun_out/amp_drift_probe.txt"""
 import os
 import sys
@@ -13,25 +13,24 @@ import ref_import
 
 ref_import.install()
 os.environ.setdefault("NERFSTUDIO_METHOD_CONFIGS", "neurad-hip=neurad_studio_amd.integration.neurad_hip:neurad_hip")
-import test_gpu_plugin_train_loop as L
-import test_gpu_reference_plugin as t
+import plugin_harness as t
 from torch.cuda.amp.grad_scaler import GradScaler
 
 import nerfstudio.models.neurad as ref_neurad
 
 ref_neurad.VGGPerceptualLossPix2Pix = torch.nn.Identity
-methods = L._methods()
-K = L.K
+methods = t.methods()
+K = t.K
 
 
 def run(who, autocast, scaler, device="cuda:0"):
-    hip, ref32 = t._build_pair(ref_neurad, False)
+    hip, ref32 = t.build_pair(ref_neurad, False)
     m = hip if who == "hip" else (ref32.to(device) if device != "cpu" else ref32)
     if who != "hip" and device != "cpu":
         m.camera_optimizer.to(device)
-    t._deterministic(m, True)
-    loop = L._Loop(methods["neurad-hip" if who == "hip" else "neurad"], m, L._Pipeline(m, False, device.split(":")[0], torch.float32),
-                   device, True, warmup=False)
+    t.deterministic(m, True)
+    loop = t.Loop(methods["neurad-hip" if who == "hip" else "neurad"], m, t.Pipeline(m, False, device.split(":")[0], torch.float32),
+                  device, True, warmup=False)
     loop.mixed_precision = bool(autocast)                       # what Trainer.train_iteration hands torch.autocast
     loop.grad_scaler = GradScaler(enabled=bool(scaler))         # and what scales the loss
     return loop.run(K)

@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 import torch
 
-import test_gpu_reference_plugin as t
+import plugin_harness as t
 
 t.ref_import.install()
 os.environ["NERFSTUDIO_METHOD_CONFIGS"] = "neurad-hip=neurad_studio_amd.integration.neurad_hip:neurad_hip"
@@ -18,15 +18,15 @@ wa = "actors" in sys.argv
 fused_dec = "fdec" in sys.argv
 torch.backends.cudnn.allow_tf32 = False
 torch.backends.cuda.matmul.allow_tf32 = False
-hip, refm = t._build_pair(ref_neurad, wa, fused_decoder=fused_dec)
-b = t._batch(wa)
-t._deterministic(hip, True), t._deterministic(refm, True)
+hip, refm = t.build_pair(ref_neurad, wa, fused_decoder=fused_dec)
+b = t.batch(wa)
+t.deterministic(hip, True), t.deterministic(refm, True)
 
 
 def run(m, dev):
     m.zero_grad(set_to_none=True)
-    out = m.get_outputs(t._bundle(b, dev), patch_size=(b["patch"], b["patch"]), calc_lidar_losses=True)
-    lab = t._labels(b, dev)
+    out = m.get_outputs(t.bundle(b, dev), patch_size=(b["patch"], b["patch"]), calc_lidar_losses=True)
+    lab = t.labels(b, dev)
     met = m.get_metrics_dict(out, lab)
     return out, m.get_loss_dict(out, lab, met)
 

@@ -6,14 +6,7 @@ import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "neurad_hip.h")
-
-
-def header_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(?:int|const char\*)\s+(nrhip_\w+)\s*\(", src)))
+from host_gate import HEADER, header_functions
 
 
 @pytest.fixture(scope="module")

@@ -1,13 +1,13 @@
 """world_size-2 gloo tests (CPU) of the N>1 path: ray sharding and the flat-buffer gradient exchange
 (SURVEY §8e).  The collective logic is device-agnostic; on the GPU box the same code runs over RCCL."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from gpu_util import free_port
 from neurad_studio_amd.parallel.data_parallel import GradientSynchronizer, shard_range
 
 
@@ -19,12 +19,6 @@ def test_shard_range_covers_everything_and_keeps_patches_whole():
             assert s % gran == 0 or s == n
             seen += list(range(s, e))
         assert seen == list(range(n))
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _worker(rank, world, port, ret):
@@ -63,7 +57,7 @@ def test_gradient_synchronizer_world2_gloo():
     world = 2
     with mp.Manager() as mgr:
         ret = mgr.dict()
-        mp.spawn(_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+        mp.spawn(_worker, args=(world, free_port(), ret), nprocs=world, join=True)
         assert all(ret[r] for r in range(world)), dict(ret)
 
 
@@ -130,7 +124,7 @@ def test_model_replicas_stay_identical_world2_gloo(overlap):
     world = 2
     with mp.Manager() as mgr:
         ret = mgr.dict()
-        mp.spawn(_worker_model, args=(world, _free_port(), ret, overlap), nprocs=world, join=True)
+        mp.spawn(_worker_model, args=(world, free_port(), ret, overlap), nprocs=world, join=True)
         assert all(ret[r] for r in range(world)), dict(ret)
 
 
@@ -199,7 +193,7 @@ def _sharded_adam_worker(rank, world, port, ret):
 def test_sharded_table_adam_world2_matches_one_process_on_the_mean_gradient():
     world = 2
     ret = mp.get_context("spawn").Manager().dict()
-    mp.spawn(_sharded_adam_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+    mp.spawn(_sharded_adam_worker, args=(world, free_port(), ret), nprocs=world, join=True)
     assert all(ret[r] for r in range(world)), dict(ret)
 
 
@@ -240,7 +234,7 @@ def test_overlap_hook_only_for_gradients_every_rank_holds_world2_gloo():
     world = 2
     with mp.Manager() as mgr:
         ret = mgr.dict()
-        mp.spawn(_uneven_overlap_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+        mp.spawn(_uneven_overlap_worker, args=(world, free_port(), ret), nprocs=world, join=True)
         assert all(ret[r] for r in range(world)), dict(ret)
 
 
@@ -281,7 +275,7 @@ def _sharded_adam_skip_worker(rank, world, port, ret):
 def test_sharded_table_adam_skips_tables_without_any_gradient_world2_gloo():
     world = 2
     ret = mp.get_context("spawn").Manager().dict()
-    mp.spawn(_sharded_adam_skip_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+    mp.spawn(_sharded_adam_skip_worker, args=(world, free_port(), ret), nprocs=world, join=True)
     assert all(ret[r] for r in range(world)), dict(ret)
 
 
@@ -331,7 +325,7 @@ def test_level_sparse_exchange_equals_the_dense_exchange_world2_gloo():
     world = 2
     with mp.Manager() as mgr:
         ret = mgr.dict()
-        mp.spawn(_worker_levels, args=(world, _free_port(), ret), nprocs=world, join=True)
+        mp.spawn(_worker_levels, args=(world, free_port(), ret), nprocs=world, join=True)
         assert all(ret[r][0] for r in range(world)), dict(ret)
 
 
@@ -384,7 +378,7 @@ def test_level_sparse_exchange_with_hook_started_overlap_world2_gloo():
     world = 2
     with mp.Manager() as mgr:
         ret = mgr.dict()
-        mp.spawn(_worker_levels_overlap, args=(world, _free_port(), ret), nprocs=world, join=True)
+        mp.spawn(_worker_levels_overlap, args=(world, free_port(), ret), nprocs=world, join=True)
         assert all(ret[r][0] for r in range(world)), dict(ret)
 
 
@@ -451,7 +445,7 @@ def _wire16_worker(rank, world, port, ret):
 def test_bf16_wire_format_keeps_replicas_identical_world2_gloo():
     world = 2
     ret = mp.get_context("spawn").Manager().dict()
-    mp.spawn(_wire16_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+    mp.spawn(_wire16_worker, args=(world, free_port(), ret), nprocs=world, join=True)
     assert all(ret[r] for r in range(world)), dict(ret)
 
 
@@ -489,7 +483,7 @@ def test_auto_sync_reduces_before_the_gradscaler_looks_world2_gloo():
     world = 2
     with mp.Manager() as mgr:
         ret = mgr.dict()
-        mp.spawn(_auto_sync_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+        mp.spawn(_auto_sync_worker, args=(world, free_port(), ret), nprocs=world, join=True)
         (s0, p0, sc0, b0), (s1, p1, sc1, b1) = ret[0], ret[1]
     assert s0 == s1 == [False, True, False], (s0, s1)  # the overflow on rank 1 skipped the step on BOTH ranks
     assert sc0 == sc1 == 4.0 and b0 == b1 > 0
@@ -533,7 +527,7 @@ def test_broadcast_module_state_gives_every_rank_rank0s_parameters_and_buffers_w
     world = 2
     with mp.Manager() as mgr:
         ret = mgr.dict()
-        mp.spawn(_broadcast_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+        mp.spawn(_broadcast_worker, args=(world, free_port(), ret), nprocs=world, join=True)
         (built0, after0, inplace0), (built1, after1, inplace1) = ret[0], ret[1]
     assert inplace0 and inplace1
     assert not torch.equal(built0["table"], built1["table"])

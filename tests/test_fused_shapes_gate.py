@@ -4,40 +4,14 @@ exist for.  Host logic only: no GPU.
 
 The checks run in a child process: importing the field module binds FieldHeadNames for the whole process (the
 reference's own enum when nerfstudio is importable, field_components/field_heads.py), which other tests pin."""
-import ast
 import json
-import os
-import re
-import subprocess
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_gate import gate_constants, run_child, variant_rows
 
 CHILD = r'''
-import json, sys
-import torch
-from neurad_studio_amd.fields.neurad_field import NeuRADField, NeuRADFieldConfig
-from neurad_studio_amd.model_components.dynamic_actors import DynamicActors, DynamicActorsConfig
 from neurad_studio_amd.models.neurad import NeuRADHotPath, NeuRADHotPathConfig
-
-
-def field_config(L, F, H):
-    cfg = NeuRADFieldConfig(geo_hidden_dim=H, nff_hidden_dim=H)
-    st, ac = cfg.grid.static, cfg.grid.actor
-    st.num_levels, st.hashgrid_dim, st.log2_hashmap_size = L, F, 10
-    ac.num_levels, ac.hashgrid_dim, ac.log2_hashmap_size = min(2, L), F, 8  # the actor grids share F (the default)
-    return cfg
-
-
-def make_actors():
-    p = torch.eye(4).repeat(2, 1, 1)
-    p[:, :3, 3] = torch.tensor([10.0, 0.0, 0.5])
-    traj = {"timestamps": torch.tensor([0.0, 1.0]), "poses": p, "dims": torch.tensor([2.0, 4.5, 1.6]),
-            "symmetric": torch.tensor(True), "deformable": torch.tensor(False)}
-    return DynamicActors(DynamicActorsConfig(), trajectories=[traj])
-
 
 out = {}
 for kind, L, F, H in json.loads(sys.argv[1]):
@@ -60,11 +34,7 @@ print(json.dumps(out))
 
 def gate(cases):
     """-> {"kind L F H": [..]} from a fresh interpreter"""
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT] + [p for p in [os.environ.get("PYTHONPATH")] if p]))
-    r = subprocess.run([sys.executable, "-c", CHILD, json.dumps(cases)], capture_output=True, text=True, env=env,
-                       cwd=ROOT, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return json.loads(r.stdout.strip().splitlines()[-1])
+    return run_child(CHILD, json.dumps(cases))
 
 
 STATIC = [(1, 4, 32), (1, 4, 64), (4, 2, 32), (4, 2, 64), (4, 4, 32), (4, 4, 64), (8, 2, 32), (8, 2, 64), (8, 4, 32),
@@ -99,28 +69,6 @@ def test_model_fused_paths_with_actors(L, F):
 
 
 # ---- the gate's constants against the kernels' variant table -------------------------------------------------------------
-VARIANTS = os.path.join(ROOT, "neurad_studio_amd", "csrc", "render_variants.h")
-FIELD_PY = os.path.join(ROOT, "neurad_studio_amd", "fields", "neurad_field.py")
-
-
-def variant_rows(path=VARIANTS):
-    """-> [(L, F, H, output, source, products)] of the X-macro, comments dropped"""
-    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    src = re.sub(r"//[^\n]*", "", src)
-    table = src[src.index("#define NRHIP_RENDER_VARIANTS(X)"):]
-    return [(int(L), int(F), int(H), o, s, p)
-            for L, F, H, o, s, p in re.findall(r"\bX\(\s*(\d+),\s*(\d+),\s*(\d+),\s*(\w+),\s*(\w+),\s*(\w+)\s*\)", table)]
-
-
-def gate_constants():
-    """_FUSED_GRIDS / _FUSED_ACTOR_FIELDS read from the module's source (importing it binds FieldHeadNames: see the top)"""
-    out = {}
-    for node in ast.parse(open(FIELD_PY).read()).body:
-        if isinstance(node, ast.Assign) and getattr(node.targets[0], "id", "") in ("_FUSED_GRIDS", "_FUSED_ACTOR_FIELDS"):
-            out[node.targets[0].id] = set(ast.literal_eval(node.value))
-    return out
-
-
 def check_gate_against_table(rows, consts):
     assert len(rows) == len(set(rows)) > 0, "duplicate or no rows"
     assert {r[3] for r in rows} <= {"PerSample", "Composite"} and {r[4] for r in rows} <= {"Static", "EvalTable", "Actors", "Overrides"}

@@ -7,63 +7,16 @@ import torch
 import neurad_oracle as O
 import synth
 from conftest import load_golden, rel_l2
-from test_oracle_actors import actor_params, field_params
+from builders import actor_params, field_params, trajectories
+from gpu_util import cuda, host, make_actor_field
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def trajectories():
-    """same synthetic trajectories as oracle/make_golden_actors.py"""
-    ts_all = torch.tensor([0.0, 1.0, 2.0, 3.0, 4.0])
-    out = []
-    for a, (y0, yaw, dims, ts) in enumerate([(8.0, 0.3, (2.0, 4.5, 1.6), ts_all[:3]), (-6.0, -0.2, (2.1, 4.8, 1.7), ts_all),
-                                             (-5.0, 0.1, (1.9, 4.2, 1.5), ts_all[1:])]):
-        poses = []
-        for t in ts:
-            c, s = np.cos(yaw + 0.05 * float(t)), np.sin(yaw + 0.05 * float(t))
-            p = torch.eye(4)
-            p[:3, :3] = torch.tensor([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
-            p[:3, 3] = torch.tensor([12.0 + 2.0 * float(t) + a, y0, 0.5])
-            poses.append(p)
-        out.append({"timestamps": ts.clone(), "poses": torch.stack(poses), "dims": torch.tensor(dims),
-                    "symmetric": torch.tensor(True), "deformable": torch.tensor(False)})
-    return out
-
-
-def make_field():
-    from neurad_studio_amd.fields.neurad_field import NeuRADField, NeuRADFieldConfig
-    from neurad_studio_amd.model_components.dynamic_actors import DynamicActors, DynamicActorsConfig
-
-    actors = DynamicActors(DynamicActorsConfig(), trajectories=trajectories())
-    cfg = NeuRADFieldConfig()
-    cfg.grid.static.log2_hashmap_size = 11
-    cfg.grid.actor.log2_hashmap_size = 9
-    fld = NeuRADField(cfg, actors=actors, static_scale=100.0).cuda().eval()
-    with torch.no_grad():
-        fld.hashgrid.static_grid.hash_table.copy_(dev(synth.hash_table(8 * 2**11, 4, seed=51, scale=0.5)))
-        for i, g in enumerate(fld.hashgrid.actor_grids):
-            g.hash_table.copy_(dev(synth.hash_table(4 * 2**9, 4, seed=400 + i, scale=0.7)))
-        for k, l in enumerate(fld.mlp_geo.layers):
-            w, b = synth.linear(l.out_features, l.in_features, 200 + 10 * k)
-            l.weight.copy_(dev(w)), l.bias.copy_(dev(b))
-        for k, l in enumerate(fld.mlp_feature.layers):
-            w, b = synth.linear(l.out_features, l.in_features, 300 + 10 * k)
-            l.weight.copy_(dev(w)), l.bias.copy_(dev(b))
-    return fld
-
-
 def test_actor_state_matches_reference_buffers():
     g = load_golden("field_actors")
-    fld = make_field()
+    fld = make_actor_field()
     act = fld.hashgrid.actors
     np.testing.assert_array_equal(host(act.actor_present_at_time), g["present"])
     assert rel_l2(host(act.actor_positions), g["positions"]) < 1e-7
@@ -76,18 +29,18 @@ def test_field_with_actors_vs_reference_golden():
     from neurad_studio_amd.field_components.field_heads import FieldHeadNames
 
     g = load_golden("field_actors")
-    fld = make_field()
+    fld = make_actor_field()
     R = g["o"].shape[0]
-    rb = RayBundle(origins=dev(g["o"]), directions=dev(g["d"]), pixel_area=dev(g["area"])[:, None],
-                   times=dev(g["times"])[:, None], nears=torch.zeros(R, 1, device="cuda"),
+    rb = RayBundle(origins=cuda(g["o"]), directions=cuda(g["d"]), pixel_area=cuda(g["area"])[:, None],
+                   times=cuda(g["times"])[:, None], nears=torch.zeros(R, 1, device="cuda"),
                    fars=torch.full((R, 1), 60.0, device="cuda"))
-    rs = rb.get_ray_samples(dev(g["starts"])[..., None], dev(g["ends"])[..., None])
+    rs = rb.get_ray_samples(cuda(g["starts"])[..., None], cuda(g["ends"])[..., None])
     # hit set == the reference's (ray, sample) pairs
     o, d, a = rs.frustums.per_ray()
-    spec, cand = fld.hashgrid.prepare_actors(o, d, a, dev(g["starts"]), dev(g["ends"]), dev(g["times"]))
+    spec, cand = fld.hashgrid.prepare_actors(o, d, a, cuda(g["starts"]), cuda(g["ends"]), cuda(g["times"]))
     feats = torch.zeros((R * g["starts"].shape[1], 32), device="cuda")
     from neurad_studio_amd import ops
-    dirs, hit = ops.actor_encode(spec, cand, o, d, a, dev(g["starts"]), dev(g["ends"]), feats)
+    dirs, hit = ops.actor_encode(spec, cand, o, d, a, cuda(g["starts"]), cuda(g["ends"]), feats)
     want = np.zeros(g["starts"].shape, bool)
     want[g["hit_ray"], g["hit_sample"]] = True
     np.testing.assert_array_equal(host(hit).reshape(want.shape) >= 0, want)
@@ -111,17 +64,17 @@ def test_actor_training_flip_injected():
     from neurad_studio_amd import ops
 
     g = load_golden("field_actors")
-    fld = make_field()
+    fld = make_actor_field()
     R, S = g["starts"].shape
-    o, d, a = dev(g["o"]), dev(g["d"]), dev(g["area"])
-    spec, cand = fld.hashgrid.prepare_actors(o, d, a, dev(g["starts"]), dev(g["ends"]), dev(g["times"]))
+    o, d, a = cuda(g["o"]), cuda(g["d"]), cuda(g["area"])
+    spec, cand = fld.hashgrid.prepare_actors(o, d, a, cuda(g["starts"]), cuda(g["ends"]), cuda(g["times"]))
     flip = np.where(np.arange(R) % 3 == 0, -1.0, 1.0).astype(np.float32)
     grid = O.GridParams(synth.hash_table(8 * 2**11, 4, seed=51, scale=0.5), 8, 32, 8192, 11)
     ref, rdirs = O.encode_with_actors(grid, 100.0, actor_params(g), g["o"], g["d"], g["area"], g["starts"], g["ends"],
                                       g["times"], ray_flip=flip)
     feats = ops.encode_fwd(fld.hashgrid.static_grid.spec, fld.hashgrid.static_grid.hash_table.detach(), 100.0, o, d, a,
-                           dev(g["starts"]), dev(g["ends"]))
-    dirs, hit = ops.actor_encode(spec, cand, o, d, a, dev(g["starts"]), dev(g["ends"]), feats, dev(flip))
+                           cuda(g["starts"]), cuda(g["ends"]))
+    dirs, hit = ops.actor_encode(spec, cand, o, d, a, cuda(g["starts"]), cuda(g["ends"]), feats, cuda(flip))
     assert rel_l2(host(feats), ref) < TOL
     assert rel_l2(host(dirs).reshape(R, S, 3), rdirs) < 1e-6
 
@@ -142,12 +95,12 @@ def test_actor_encode_every_feature_width_and_storage_type(F, half):
     ap.grids = [O.GridParams(stored(synth.hash_table(L * 2**lg, F, seed=430 + 10 * F + i, scale=0.7)), L, 64, 1024, lg)
                 for i in range(3)]
     ref, rdirs = O.encode_with_actors(static, 100.0, ap, g["o"], g["d"], g["area"], g["starts"], g["ends"], g["times"])
-    spec = ops.ActorSpec(timestamps=dev(g["timestamps"]), positions=dev(g["positions"]), rotations_6d=dev(g["rotations_6d"]),
-                         present=dev(g["present"]), bounds=dev(ap.bounds), grid=ops.GridSpec(L, F, lg, 64, 1024),
-                         tables=[dev(t.table).to(tdt) for t in ap.grids], actor_scale=10.0)
-    o, d, a, st, en = dev(g["o"]), dev(g["d"]), dev(g["area"]), dev(g["starts"]), dev(g["ends"])
-    cand = ops.actor_prepare(spec, o, d, a, st, en, dev(g["times"]))
-    feats = ops.encode_fwd(ops.GridSpec(L, 8, lg, 16, 64), dev(static.table), 100.0, o, d, a, st, en)
+    spec = ops.ActorSpec(timestamps=cuda(g["timestamps"]), positions=cuda(g["positions"]), rotations_6d=cuda(g["rotations_6d"]),
+                         present=cuda(g["present"]), bounds=cuda(ap.bounds), grid=ops.GridSpec(L, F, lg, 64, 1024),
+                         tables=[cuda(t.table).to(tdt) for t in ap.grids], actor_scale=10.0)
+    o, d, a, st, en = cuda(g["o"]), cuda(g["d"]), cuda(g["area"]), cuda(g["starts"]), cuda(g["ends"])
+    cand = ops.actor_prepare(spec, o, d, a, st, en, cuda(g["times"]))
+    feats = ops.encode_fwd(ops.GridSpec(L, 8, lg, 16, 64), cuda(static.table), 100.0, o, d, a, st, en)
     dirs, hit = ops.actor_encode(spec, cand, o, d, a, st, en, feats)
     want = np.zeros(g["starts"].shape, bool)
     want[g["hit_ray"], g["hit_sample"]] = True
@@ -169,15 +122,15 @@ def test_proposal_density_with_actors_vs_oracle():
     p = NeuRADProposalField(c, actors=actors, static_scale=100.0).cuda().eval()
     w, _ = synth.linear(1, 6, 77, bias=False)
     with torch.no_grad():
-        p.hashgrid.static_grid.hash_table.copy_(dev(synth.hash_table(6 * 2**11, 1, seed=91, scale=2.0)))
+        p.hashgrid.static_grid.hash_table.copy_(cuda(synth.hash_table(6 * 2**11, 1, seed=91, scale=2.0)))
         for i, gr in enumerate(p.hashgrid.actor_grids):
-            gr.hash_table.copy_(dev(synth.hash_table(4 * 2**8, 1, seed=500 + i, scale=1.5)))
-        p.density_decoder.weight.copy_(dev(w + np.float32(0.3)))
+            gr.hash_table.copy_(cuda(synth.hash_table(4 * 2**8, 1, seed=500 + i, scale=1.5)))
+        p.density_decoder.weight.copy_(cuda(w + np.float32(0.3)))
     R = g["o"].shape[0]
-    rb = RayBundle(origins=dev(g["o"]), directions=dev(g["d"]), pixel_area=dev(g["area"])[:, None],
-                   times=dev(g["times"])[:, None], nears=torch.zeros(R, 1, device="cuda"),
+    rb = RayBundle(origins=cuda(g["o"]), directions=cuda(g["d"]), pixel_area=cuda(g["area"])[:, None],
+                   times=cuda(g["times"])[:, None], nears=torch.zeros(R, 1, device="cuda"),
                    fars=torch.full((R, 1), 60.0, device="cuda"))
-    rs = rb.get_ray_samples(dev(g["starts"])[..., None], dev(g["ends"])[..., None])
+    rs = rb.get_ray_samples(cuda(g["starts"])[..., None], cuda(g["ends"])[..., None])
     with torch.no_grad():
         dens = host(p.get_density(rs)[0][..., 0])
     # oracle: static proposal density, then exp(decoder . padded actor feats) on the hit samples
@@ -195,8 +148,8 @@ def test_hashgrid_dx_vs_reference_autograd():
 
     g = load_golden("field_actors_grads")
     spec = ops.GridSpec(4, 4, 9, 64, 1024)
-    table = dev(synth.hash_table(4 * 2**9, 4, seed=400, scale=0.7))
-    gx = ops.hashgrid_bwd_input(spec, table, dev(g["hx"]), dev(g["hgy"]))
+    table = cuda(synth.hash_table(4 * 2**9, 4, seed=400, scale=0.7))
+    gx = ops.hashgrid_bwd_input(spec, table, cuda(g["hx"]), cuda(g["hgy"]))
     assert rel_l2(host(gx), g["hdx"]) < TOL
 
 
@@ -206,16 +159,16 @@ def test_actor_gradients_vs_reference_autograd():
     from neurad_studio_amd.field_components.field_heads import FieldHeadNames
 
     g, gg = load_golden("field_actors"), load_golden("field_actors_grads")
-    fld = make_field()
+    fld = make_actor_field()
     R = g["o"].shape[0]
-    rb = RayBundle(origins=dev(g["o"]), directions=dev(g["d"]), pixel_area=dev(g["area"])[:, None],
-                   times=dev(g["times"])[:, None], nears=torch.zeros(R, 1, device="cuda"),
+    rb = RayBundle(origins=cuda(g["o"]), directions=cuda(g["d"]), pixel_area=cuda(g["area"])[:, None],
+                   times=cuda(g["times"])[:, None], nears=torch.zeros(R, 1, device="cuda"),
                    fars=torch.full((R, 1), 60.0, device="cuda"))
-    rs = rb.get_ray_samples(dev(g["starts"])[..., None], dev(g["ends"])[..., None])
+    rs = rb.get_ray_samples(cuda(g["starts"])[..., None], cuda(g["ends"])[..., None])
     out = fld(rs)
     assert rel_l2(host(out[FieldHeadNames.FEATURE]), g["feature"]) < TOL
-    ((out[FieldHeadNames.FEATURE] * dev(gg["g_feature"])).sum()
-     + (out[FieldHeadNames.ALPHA][..., 0] * dev(gg["g_alpha"])).sum()).backward()
+    ((out[FieldHeadNames.FEATURE] * cuda(gg["g_feature"])).sum()
+     + (out[FieldHeadNames.ALPHA][..., 0] * cuda(gg["g_alpha"])).sum()).backward()
     tg = np.zeros((8 * 2**11, 4), np.float32)
     tg[gg["tg_idx"]] = gg["tg_val"]
     assert rel_l2(host(fld.hashgrid.static_grid.hash_table.grad), tg) < TOL
@@ -250,13 +203,13 @@ def test_many_actors_along_a_ray_no_candidate_cap():
     fld = NeuRADField(cfg, actors=actors, static_scale=100.0).cuda().eval()
     fp = field_params()
     with torch.no_grad():
-        fld.hashgrid.static_grid.hash_table.copy_(dev(fp.grid.table))
+        fld.hashgrid.static_grid.hash_table.copy_(cuda(fp.grid.table))
         tabs = [synth.hash_table(4 * 2**9, 4, seed=900 + i, scale=0.7) for i in range(A)]
         for gr, t in zip(fld.hashgrid.actor_grids, tabs):
-            gr.hash_table.copy_(dev(t))
+            gr.hash_table.copy_(cuda(t))
         for layers, ws, bs in ((fld.mlp_geo.layers, fp.geo_w, fp.geo_b), (fld.mlp_feature.layers, fp.feat_w, fp.feat_b)):
             for l, w, b in zip(layers, ws, bs):
-                l.weight.copy_(dev(w)), l.bias.copy_(dev(b))
+                l.weight.copy_(cuda(w)), l.bias.copy_(cuda(b))
     R, S = 32, 64
     o = (synth.normal((R, 3), 3) * np.array([0.5, 0.3, 0.1], np.float32)).astype(np.float32)
     tgt = np.stack([np.full(R, 110.0), synth.uniform((R,), -0.6, 0.6, 4), synth.uniform((R,), 0.2, 0.6, 5)], -1)
@@ -270,9 +223,9 @@ def test_many_actors_along_a_ray_no_candidate_cap():
                        host(actors.actor_present_at_time), host(actors.actor_sizes), host(actors.actor_padding),
                        [O.GridParams(t, 4, 64, 1024, 9) for t in tabs], actor_scale=10.0)
     ref = O.field_fwd_actors(fp, ap, o, d, area, st, en, times)
-    rb = RayBundle(origins=dev(o), directions=dev(d), pixel_area=dev(area)[:, None], times=dev(times)[:, None])
-    rs = rb.get_ray_samples(dev(st)[..., None], dev(en)[..., None])
-    spec, cand = fld.hashgrid.prepare_actors(dev(o), dev(d), dev(area), dev(st), dev(en), dev(times))
+    rb = RayBundle(origins=cuda(o), directions=cuda(d), pixel_area=cuda(area)[:, None], times=cuda(times)[:, None])
+    rs = rb.get_ray_samples(cuda(st)[..., None], cuda(en)[..., None])
+    spec, cand = fld.hashgrid.prepare_actors(cuda(o), cuda(d), cuda(area), cuda(st), cuda(en), cuda(times))
     assert cand[1].shape == (R, A) and int(cand[0].max()) > 8, "the scene must exceed the old per-ray cap"
     with torch.no_grad():
         out = fld(rs)
@@ -296,11 +249,11 @@ def test_fused_render_with_actors_vs_reference_golden():
     """nrhip_render_fwd_actors (device-side ray split + static kernel + per-sample table select kernel) against the
     REFERENCE's per-sample field outputs for the actor scene (golden field_actors: feature, alpha), composited."""
     g = load_golden("field_actors")
-    fld = make_field()
+    fld = make_actor_field()
     starts, ends = g["starts"], g["ends"]
     with torch.no_grad():
-        feats, depth, acc, w = fld.render(dev(g["o"]), dev(g["d"]), dev(g["area"]), dev(starts), dev(ends), return_weights=True,
-                                          times=dev(g["times"]))
+        feats, depth, acc, w = fld.render(cuda(g["o"]), cuda(g["d"]), cuda(g["area"]), cuda(starts), cuda(ends), return_weights=True,
+                                          times=cuda(g["times"]))
     want_f, want_d, want_a = _composite_reference(g["feature"], g["alpha"], starts, ends)
     assert want_f.shape == feats.shape
     assert rel_l2(host(feats), want_f) < TOL
@@ -308,7 +261,7 @@ def test_fused_render_with_actors_vs_reference_golden():
     assert rel_l2(host(depth), want_d) < TOL
     assert rel_l2(host(w), O.render_weight_from_alpha(g["alpha"])[0]) < TOL
     # the scene really exercises both kernels: some rays have candidates, some do not
-    cnt = fld.hashgrid.prepare_actors(dev(g["o"]), dev(g["d"]), dev(g["area"]), dev(starts), dev(ends), dev(g["times"]))[1][0]
+    cnt = fld.hashgrid.prepare_actors(cuda(g["o"]), cuda(g["d"]), cuda(g["area"]), cuda(starts), cuda(ends), cuda(g["times"]))[1][0]
     assert 0 < int((cnt > 0).sum()) and len(g["hit_ray"]) > 0
 
 
@@ -335,13 +288,13 @@ def test_fused_render_many_actors_vs_oracle_and_operator_path(with_order):
     fld = NeuRADField(cfg, actors=actors, static_scale=100.0).cuda().eval()
     fp = field_params()
     with torch.no_grad():
-        fld.hashgrid.static_grid.hash_table.copy_(dev(fp.grid.table))
+        fld.hashgrid.static_grid.hash_table.copy_(cuda(fp.grid.table))
         tabs = [synth.hash_table(4 * 2**9, 4, seed=900 + i, scale=0.7) for i in range(A)]
         for gr, t in zip(fld.hashgrid.actor_grids, tabs):
-            gr.hash_table.copy_(dev(t))
+            gr.hash_table.copy_(cuda(t))
         for layers, ws, bs in ((fld.mlp_geo.layers, fp.geo_w, fp.geo_b), (fld.mlp_feature.layers, fp.feat_w, fp.feat_b)):
             for l, w, b in zip(layers, ws, bs):
-                l.weight.copy_(dev(w)), l.bias.copy_(dev(b))
+                l.weight.copy_(cuda(w)), l.bias.copy_(cuda(b))
         fld.sdf_to_density.beta.fill_(fp.beta)
     R, S = 301, 72  # ragged: not a multiple of the 4 rays per workgroup, last tile half full
     o = (synth.normal((R, 3), 3) * np.array([0.5, 0.3, 0.1], np.float32)).astype(np.float32)
@@ -358,17 +311,17 @@ def test_fused_render_many_actors_vs_oracle_and_operator_path(with_order):
                        [O.GridParams(t, 4, 64, 1024, 9) for t in tabs], actor_scale=10.0)
     ref = O.field_fwd_actors(fp, ap, o, d, area, st, en, times)
     want_f, want_d, want_a = _composite_reference(ref["feature"], ref["alpha"], st, en)
-    order = ops.ray_order(dev(o), dev(d), 100.0) if with_order else None
+    order = ops.ray_order(cuda(o), cuda(d), 100.0) if with_order else None
     with torch.no_grad():
-        feats, depth, acc = fld.render(dev(o), dev(d), dev(area), dev(st), dev(en), times=dev(times), order=order)
-    cnt = fld.hashgrid.prepare_actors(dev(o), dev(d), dev(area), dev(st), dev(en), dev(times))[1][0]
+        feats, depth, acc = fld.render(cuda(o), cuda(d), cuda(area), cuda(st), cuda(en), times=cuda(times), order=order)
+    cnt = fld.hashgrid.prepare_actors(cuda(o), cuda(d), cuda(area), cuda(st), cuda(en), cuda(times))[1][0]
     assert int(cnt.max()) > 8 and int((cnt == 0).sum()) > 50
     assert rel_l2(host(feats), want_f) < TOL
     assert rel_l2(host(acc), want_a) < TOL
     assert rel_l2(host(depth), want_d) < TOL
     # early termination stays within its bound on the actor kernel too
     with torch.no_grad():
-        f2, _, a2 = fld.render(dev(o), dev(d), dev(area), dev(st), dev(en), times=dev(times), early_stop_eps=1e-3)
+        f2, _, a2 = fld.render(cuda(o), cuda(d), cuda(area), cuda(st), cuda(en), times=cuda(times), early_stop_eps=1e-3)
     assert float((a2 - acc).abs().max()) <= 1e-3 + 1e-6 and float((f2 - feats).abs().max()) < 5e-2
 
 
@@ -378,18 +331,18 @@ def test_fused_render_with_actors_fp16_tables_equal_rounded_fp32_tables():
     g = load_golden("field_actors")
     outs = []
     for half in (False, True):
-        fld = make_field()
+        fld = make_actor_field()
         for grid in [fld.hashgrid.static_grid, *fld.hashgrid.actor_grids]:
             rounded = grid.hash_table.data.half()
             grid.hash_table.data = rounded if half else rounded.float()
         assert fld.fused_supported(with_actors=True)
         with torch.no_grad():
-            outs.append(fld.render(dev(g["o"]), dev(g["d"]), dev(g["area"]), dev(g["starts"]), dev(g["ends"]),
-                                   times=dev(g["times"])))
+            outs.append(fld.render(cuda(g["o"]), cuda(g["d"]), cuda(g["area"]), cuda(g["starts"]), cuda(g["ends"]),
+                                   times=cuda(g["times"])))
     for a, b in zip(*outs):
         assert torch.equal(a, b)
     # mixed storage is refused, not silently converted
-    fld = make_field()
+    fld = make_actor_field()
     fld.hashgrid.static_grid.hash_table.data = fld.hashgrid.static_grid.hash_table.data.half()
     assert not fld.fused_supported(with_actors=True)
 
@@ -404,11 +357,11 @@ def test_actor_pair_positions_kernel_vs_torch_autograd(scale):
     from neurad_studio_amd.model_components.dynamic_actors import world2box_pairs
 
     g = load_golden("field_actors")
-    fld = make_field()
+    fld = make_actor_field()
     fld.hashgrid.config.actor.actor_scale = scale
     act = fld.hashgrid.actors
-    o, d, a = dev(g["o"]), dev(g["d"]), dev(g["area"])
-    st, en, times = dev(g["starts"]), dev(g["ends"]), dev(g["times"])
+    o, d, a = cuda(g["o"]), cuda(g["d"]), cuda(g["area"])
+    st, en, times = cuda(g["starts"]), cuda(g["ends"]), cuda(g["times"])
     R, S = st.shape
     torch.manual_seed(0)
     P = 4000
@@ -461,25 +414,25 @@ def test_actor_edits_vs_reference_golden():
     from neurad_studio_amd.field_components.field_heads import FieldHeadNames
 
     g, ge = load_golden("field_actors"), load_golden("field_actors_edit")
-    fld = make_field()
+    fld = make_actor_field()
     R, S = g["starts"].shape
-    rb = RayBundle(origins=dev(g["o"]), directions=dev(g["d"]), pixel_area=dev(g["area"])[:, None],
-                   times=dev(g["times"])[:, None], nears=torch.zeros(R, 1, device="cuda"),
+    rb = RayBundle(origins=cuda(g["o"]), directions=cuda(g["d"]), pixel_area=cuda(g["area"])[:, None],
+                   times=cuda(g["times"])[:, None], nears=torch.zeros(R, 1, device="cuda"),
                    fars=torch.full((R, 1), 60.0, device="cuda"))
-    rs = rb.get_ray_samples(dev(g["starts"])[..., None], dev(g["ends"])[..., None])
+    rs = rb.get_ray_samples(cuda(g["starts"])[..., None], cuda(g["ends"])[..., None])
     o, d, a = rs.frustums.per_ray()
     act = fld.hashgrid.actors
     for e, (lat, lon, hgt, rot, idx) in enumerate(ge["edits"].tolist()):
         act.actor_editing.update(lateral=lat, longitudinal=lon, height=hgt, rotation=rot, index=idx)
-        spec, cand = fld.hashgrid.prepare_actors(o, d, a, dev(g["starts"]), dev(g["ends"]), dev(g["times"]))
-        _, hit = ops.actor_encode(spec, cand, o, d, a, dev(g["starts"]), dev(g["ends"]), torch.zeros((R * S, 32), device="cuda"))
+        spec, cand = fld.hashgrid.prepare_actors(o, d, a, cuda(g["starts"]), cuda(g["ends"]), cuda(g["times"]))
+        _, hit = ops.actor_encode(spec, cand, o, d, a, cuda(g["starts"]), cuda(g["ends"]), torch.zeros((R * S, 32), device="cuda"))
         want = np.zeros((R, S), bool)
         want[ge[f"e{e}_hit_ray"], ge[f"e{e}_hit_sample"]] = True
         np.testing.assert_array_equal(host(hit).reshape(R, S) >= 0, want)
         with torch.no_grad():
             out = fld(rs)
-            feats, depth, acc = fld.render(dev(g["o"]), dev(g["d"]), dev(g["area"]), dev(g["starts"]), dev(g["ends"]),
-                                           times=dev(g["times"]))
+            feats, depth, acc = fld.render(cuda(g["o"]), cuda(g["d"]), cuda(g["area"]), cuda(g["starts"]), cuda(g["ends"]),
+                                           times=cuda(g["times"]))
         assert rel_l2(host(out[FieldHeadNames.ALPHA][..., 0]), ge[f"e{e}_alpha"]) < TOL
         has_f = f"e{e}_feature" in ge
         want_f, want_d, want_a = _composite_reference(ge[f"e{e}_feature"] if has_f else np.zeros((R, S, 32), np.float32),

@@ -16,25 +16,9 @@ import torch
 
 import synth
 from conftest import rel_l2
+from builders import trajectories
 
 pytestmark = pytest.mark.gpu
-
-
-def trajectories():
-    ts_all = torch.tensor([0.0, 1.0, 2.0, 3.0, 4.0])
-    out = []
-    for a, (y0, yaw, dims, ts) in enumerate([(8.0, 0.3, (2.0, 4.5, 1.6), ts_all[:3]), (-6.0, -0.2, (2.1, 4.8, 1.7), ts_all),
-                                             (-5.0, 0.1, (1.9, 4.2, 1.5), ts_all[1:])]):
-        poses = []
-        for t in ts:
-            c, s = np.cos(yaw + 0.05 * float(t)), np.sin(yaw + 0.05 * float(t))
-            p = torch.eye(4)
-            p[:3, :3] = torch.tensor([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
-            p[:3, 3] = torch.tensor([12.0 + 2.0 * float(t) + a, y0, 0.5])
-            poses.append(p)
-        out.append({"timestamps": ts.clone(), "poses": torch.stack(poses), "dims": torch.tensor(dims),
-                    "symmetric": torch.tensor(True), "deformable": torch.tensor(False)})
-    return out
 
 
 def build():

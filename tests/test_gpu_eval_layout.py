@@ -1,22 +1,16 @@
 """Eval-time layout of the coarse hash-grid levels (csrc/eval_layout.hip): the fused render kernel reading the shadow copies
 must produce the SAME BITS as the plain table -- with processing orders, early termination, fp16 storage -- and the eval
 table must be rebuilt when the parameter changes."""
-import numpy as np
 import pytest
 import torch
 
 import neurad_oracle as O
 from conftest import rel_l2
-from test_gpu_parity import TOL, _sample_rays, dev, field_params, host, to_spec
+from builders import field_params, sample_rays
+from gpu_util import TOL, dev, host, to_spec
+from gpu_util import ops  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ops():
-    from neurad_studio_amd import ops as _ops
-
-    return _ops
 
 
 CFGS = [  # (L, F, lg, min_res, max_res, H, n shadow levels expected)
@@ -40,7 +34,7 @@ def test_render_with_eval_layout_is_bit_identical(ops, cfg, half, monkeypatch, s
     lay, rows, ns = ops.eval_layout_plan(fs.grid, fs.table.dtype)
     assert ns == n_shadow and rows <= fs.grid.table_rows
     R, S = 3000, 48
-    o, d, area, s, e, eu = _sample_rays(R, S, seed=9)
+    o, d, area, s, e, eu = sample_rays(R, S, seed=9)
     do, dd, da, edges = dev(o), dev(d), dev(area), dev(eu)
     order = ops.ray_order(do, dd, 100.0)
     outs = {}

@@ -8,62 +8,13 @@ import torch
 import neurad_oracle as O
 import synth
 from conftest import load_golden, rel_l2
-from test_gpu_parity import TIGHT, TOL
-from test_oracle_field_shapes import SHAPES, actor_params, field_params
+from builders import SHAPES, actor_params, field_params, sample_rays, shape_params, tagged_field_params, trajectories
+from gpu_util import TIGHT, TOL, actor_rays, bundle, dev, host, load_field_weights, to_spec, torch_sdf_render
+from gpu_util import ops  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
 SMALL = [(1, 4), (4, 2), (4, 4), (8, 2)]  # (L, F) of the padded-frame instantiations
-
-
-@pytest.fixture(scope="module")
-def ops():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from neurad_studio_amd import ops as _ops
-
-    return _ops
-
-
-def dev(a, dtype=torch.float32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def shape_params(L, F, H, use_sdf, half=False):
-    """an (L, F) grid with O(1) features and H-wide MLPs; fp16 storage: the oracle sees the rounded table"""
-    lg, mn, mx = (10, 32, 32) if L == 1 else (10, 32, 2048)
-    LF = L * F
-    table = synth.hash_table(L * 2**lg, F, seed=60 + L + F, scale=2.0 if use_sdf else 0.5)
-    if half:
-        table = table.astype(np.float16).astype(np.float32)
-    gw, gb, fw, fb = [], [], [], []
-    for k, (o, i) in enumerate([(H, LF), (33, H)]):
-        w, b = synth.linear(o, i, 200 + 10 * k)
-        gw.append(w), gb.append(b)
-    for k, (o, i) in enumerate([(H, 48), (H, H), (32, H)]):
-        w, b = synth.linear(o, i, 300 + 10 * k)
-        fw.append(w), fb.append(b)
-    p = O.FieldParams(O.GridParams(table, L, mn, mx, lg), 100.0, gw, gb, fw, fb, use_sdf=use_sdf)
-    if use_sdf:
-        p.beta = 3.0  # alphas away from saturation: the compositing is exercised
-    return p
-
-
-def to_spec(ops, p, half=False):
-    g = p.grid
-    spec = ops.GridSpec(g.num_levels, g.n_feat, g.log2_hashmap_size, g.min_res, g.max_res)
-    return ops.FieldSpec(spec, dev(g.table, torch.float16 if half else torch.float32), p.static_scale,
-                         [dev(w) for w in p.geo_w], [dev(b) for b in p.geo_b], [dev(w) for w in p.feat_w],
-                         [dev(b) for b in p.feat_b], use_sdf=p.use_sdf, beta=abs(p.beta) + p.beta_min)
-
-
-def sample_rays(R, S, seed):
-    o, d, area, _ = synth.rays(R, seed)
-    _, eu, _ = O.power_sampler(np.zeros(R), np.full(R, 200.0, np.float32), S)
-    return o, d, area, np.ascontiguousarray(eu[:, :-1]), np.ascontiguousarray(eu[:, 1:])
 
 
 # ---- 1. the kernels against the oracle ---------------------------------------------------------------------------------
@@ -76,7 +27,7 @@ def test_small_grid_render_and_field_fwd_vs_oracle(ops, LF, H, use_sdf, half):
     p = shape_params(L, F, H, use_sdf, half)
     fs = to_spec(ops, p, half)
     for R, S in ((37, 40), (9, 7), (5, 1)):  # ragged last tile, S < 16, one sample per ray
-        o, d, area, s, e = sample_rays(R, S, seed=R + S)
+        o, d, area, s, e = sample_rays(R, S, seed=R + S)[:5]
         ref = O.render_rays(p, o, d, area, s, e)
         feats, depth, acc, w = ops.render_fwd(fs, dev(o), dev(d), dev(area), dev(s), dev(e), return_weights=True)
         assert rel_l2(host(feats), ref["features"]) < TIGHT, (R, S)
@@ -104,7 +55,7 @@ def test_small_grid_training_forward_saves_the_dense_encoding(ops):
     for L, F in SMALL:
         p = shape_params(L, F, 32, True)
         fs = to_spec(ops, p)
-        o, d, area, s, e = sample_rays(11, 21, seed=3)
+        o, d, area, s, e = sample_rays(11, 21, seed=3)[:5]
         (feat, sdf, head), (enc, hg, xf, hf) = ops.field_fwd_train(fs, dev(o), dev(d), dev(area), dev(s), dev(e))
         assert enc.shape == (11 * 21, L * F)
         ref = O.encode_static(p.grid, 100.0, o, d, area, s, e)
@@ -121,20 +72,11 @@ def make_field(tag, half=False, actors=None):
     st = cfg.grid.static
     st.num_levels, st.hashgrid_dim, st.base_res, st.max_res, st.log2_hashmap_size = L, F, mn, mx, lg
     cfg.grid.actor.hashgrid_dim, cfg.grid.actor.num_levels, cfg.grid.actor.log2_hashmap_size = 2, 2, 9
-    fld = NeuRADField(cfg, actors=actors, static_scale=100.0).cuda()
-    p = field_params(tag)
-    with torch.no_grad():
-        table = dev(p.grid.table)
-        fld.hashgrid.static_grid.hash_table.data = table.half() if half else table
-        for layers, ws, bs in ((fld.mlp_geo.layers, p.geo_w, p.geo_b), (fld.mlp_feature.layers, p.feat_w, p.feat_b)):
-            for l, w, b in zip(layers, ws, bs):
-                l.weight.copy_(dev(w)), l.bias.copy_(dev(b))
-    return fld
+    return load_field_weights(NeuRADField(cfg, actors=actors, static_scale=100.0).cuda(), tagged_field_params(tag), half)
 
 
 def samples(g):
     from neurad_studio_amd.model_components.ray_samplers import PowerSampler
-    from test_gpu_modules import bundle
 
     rs = PowerSampler(num_samples=g["starts"].shape[1], lambda_=-1.0, scaling=0.1).eval()(bundle(g["o"], g["d"], g["area"]))
     assert rel_l2(host(rs.frustums.starts[..., 0]), g["starts"]) < 1e-5
@@ -187,7 +129,6 @@ def test_small_grid_fused_training_vs_operator_path(tag):
     parameter gradient, and the ray gradients when the rays require grad"""
     from neurad_studio_amd.field_components.field_heads import FieldHeadNames as FH
     from neurad_studio_amd.model_components.ray_samplers import PowerSampler
-    from test_gpu_modules import bundle
 
     g = load_golden(f"field_{tag}")
     res = {}
@@ -215,7 +156,6 @@ def test_small_grid_render_train_vs_operator_path(tag):
     """render_train (the model's fused node: field -> learnable-beta SDF head -> weights -> compositing) against the
     operator-level field (fused_training = False) composited by torch ops in fp64: outputs and every parameter gradient"""
     from neurad_studio_amd.field_components.field_heads import FieldHeadNames as FH
-    from test_gpu_train_fused import _torch_sdf_render
 
     g = load_golden(f"field_{tag}")
     rs = samples(g)
@@ -232,8 +172,8 @@ def test_small_grid_render_train_vs_operator_path(tag):
             fld.fused_training = False
             out = fld(rs)
             sd = fld.sdf_to_density
-            _, w, feats, depth, acc = _torch_sdf_render(out[FH.SDF][..., 0].double(), sd.beta.double(), sd.beta_min_value,
-                                                        out[FH.FEATURE].double(), edges.double())
+            _, w, feats, depth, acc = torch_sdf_render(out[FH.SDF][..., 0].double(), sd.beta.double(), sd.beta_min_value,
+                                                       out[FH.FEATURE].double(), edges.double())
         ((feats * gF).sum() + (depth * gD).sum() + (acc * gA).sum() + (w * gW).sum()).backward()
         res[mode] = ([host(t).astype(np.float64) for t in (feats, depth, acc, w)], field_grads(fld))
     for a, b in zip(res["fused"][0], res["operator"][0]):
@@ -268,7 +208,6 @@ def test_small_grid_fp16_tables_equal_rounded_fp32_tables(tag):
 # ---- 4. NeuRAD tiny with dynamic actors --------------------------------------------------------------------------------
 def make_actor_field():
     from neurad_studio_amd.model_components.dynamic_actors import DynamicActors, DynamicActorsConfig
-    from test_gpu_actors import trajectories
 
     actors = DynamicActors(DynamicActorsConfig(), trajectories=trajectories())
     fld = make_field("neurad_tiny", actors=actors)
@@ -292,7 +231,7 @@ def test_neurad_tiny_render_with_actors_vs_reference_golden():
     assert rel_l2(host(depth), want_d) < TOL
     assert rel_l2(host(w), wr) < TOL
     # the oracle agrees (pinned by test_oracle_field_shapes), and the scene has rays with and without candidates
-    ref = O.field_fwd_actors(field_params("neurad_tiny"), actor_params(g), g["o"], g["d"], g["area"], g["starts"],
+    ref = O.field_fwd_actors(tagged_field_params("neurad_tiny"), actor_params(g, 2, 2), g["o"], g["d"], g["area"], g["starts"],
                              g["ends"], g["times"])
     assert rel_l2(ref["feature"], g["feature"]) < 1e-5
     cnt = fld.hashgrid.prepare_actors(dev(g["o"]), dev(g["d"]), dev(g["area"]), dev(g["starts"]), dev(g["ends"]),
@@ -304,7 +243,6 @@ def tiny_model(actors=False, appearance_dim=0):
     """NeuRADHotPath with the "NeuRAD tiny" field: static grid 4 x 2, actor grids 2 x 2 (small tables)"""
     from neurad_studio_amd.model_components.dynamic_actors import DynamicActors, DynamicActorsConfig
     from neurad_studio_amd.models.neurad import NeuRADHotPath, NeuRADHotPathConfig
-    from test_gpu_actors import trajectories
 
     torch.manual_seed(1)
     c = NeuRADHotPathConfig(appearance_dim=appearance_dim)
@@ -335,7 +273,6 @@ def _grads(m):
 def test_neurad_tiny_model_with_actors_training_matches_operator_path():
     """the model's fused training node with dynamic actors (nrhip_field_fwd_train_ovr, override rows [P, 8]) against the
     operator-level path of the same model: outputs and every gradient (static and actor tables, trajectories, MLPs, beta)"""
-    from test_gpu_train_fused import _actor_rays
 
     res = {}
     for mode in ("fused", "operator"):
@@ -344,7 +281,7 @@ def test_neurad_tiny_model_with_actors_training_matches_operator_path():
         m.fused_training = mode == "fused"
         assert m.fused_training_possible() == (mode == "fused")
         torch.manual_seed(77)
-        out = m.get_nff_outputs(_actor_rays())
+        out = m.get_nff_outputs(actor_rays())
         (out["features"].square().mean() + 1e-3 * out["depth"].mean() + out["accumulation"].mean()).backward()
         res[mode] = (out, _grads(m))
     for k in ("features", "depth", "accumulation"):
@@ -364,8 +301,6 @@ def test_four_level_grids_without_actor_kernels_render_through_the_operator_path
     from neurad_studio_amd.fields.neurad_field import NeuRADField, NeuRADFieldConfig
     from neurad_studio_amd.model_components.dynamic_actors import DynamicActors, DynamicActorsConfig
     from neurad_studio_amd.model_components.ray_samplers import PowerSampler
-    from test_gpu_actors import trajectories
-    from test_gpu_train_fused import _actor_rays
 
     L, F = LF
     cfg = NeuRADFieldConfig()
@@ -378,7 +313,7 @@ def test_four_level_grids_without_actor_kernels_render_through_the_operator_path
         for gr in fld.hashgrid.actor_grids:
             gr.hash_table.mul_(3000.0)
     assert not fld.fused_supported(with_actors=True)
-    rb = _actor_rays(64)
+    rb = actor_rays(64)
     rb.nears, rb.fars = torch.zeros(64, 1, device="cuda"), torch.full((64, 1), 60.0, device="cuda")
     rs = PowerSampler(num_samples=24, lambda_=-1.0, scaling=0.1).eval()(rb)
     with torch.no_grad():
@@ -406,8 +341,6 @@ def test_four_level_grids_without_actor_kernels_render_through_the_operator_path
 
 # ---- 5. model level ----------------------------------------------------------------------------------------------------
 def test_neurad_tiny_model_fused_eval_and_training_match_operator_path():
-    from test_gpu_modules import bundle
-
     m = tiny_model().eval()
     R = 64
     o, d, area, _ = synth.rays(R, 9)
@@ -441,22 +374,13 @@ def test_uninstantiated_shapes_stay_unsupported_and_the_field_falls_back(ops):
     from neurad_studio_amd import _lib
     from neurad_studio_amd.field_components.field_heads import FieldHeadNames as FH
     from neurad_studio_amd.fields.neurad_field import NeuRADField, NeuRADFieldConfig
-    from test_gpu_modules import bundle
 
     for L, F, H in ((3, 8, 32), (4, 2, 48), (2, 2, 32)):
         p = shape_params(4, 2, H, True) if (L, F) == (4, 2) else None
         if p is None:
-            lg = 10
-            gw, gb, fw, fb = [], [], [], []
-            for k, (o_, i) in enumerate([(H, L * F), (33, H)]):
-                w, b = synth.linear(o_, i, 200 + 10 * k)
-                gw.append(w), gb.append(b)
-            for k, (o_, i) in enumerate([(H, 48), (H, H), (32, H)]):
-                w, b = synth.linear(o_, i, 300 + 10 * k)
-                fw.append(w), fb.append(b)
-            p = O.FieldParams(O.GridParams(synth.hash_table(L * 2**lg, F, seed=5), L, 32, 2048, lg), 100.0, gw, gb, fw, fb)
+            p = field_params(True, L, F, 10, H, 32, 2048, scale=1e-3, seed=5)
         fs = to_spec(ops, p)
-        o, d, area, s, e = sample_rays(4, 8, seed=1)
+        o, d, area, s, e = sample_rays(4, 8, seed=1)[:5]
         # NRHIP_ERR_UNSUPPORTED (2) from the C entry points, with a message that names the shape
         with pytest.raises(_lib.NeuradHipError, match=rf"code 2\).*L={L} F={F} H={H}"):
             ops.render_fwd(fs, dev(o), dev(d), dev(area), dev(s), dev(e))

@@ -4,15 +4,15 @@ Replays must walk the trajectory of the eagerly launched step (bench.py's train_
 import pytest
 import torch
 
+from gpu_util import rehearsal_loss, rehearsal_model, shard
+
 pytestmark = pytest.mark.gpu
 
 
 def _setup(capturable):
-    from test_gpu_dist_rehearsal import _loss, _model, _shard
-
     from neurad_studio_amd.optim import HashGridAdam
 
-    m = _model()  # (sampler in eval mode: no jitter, so that graph and eager runs see the same samples)
+    m = rehearsal_model()  # (sampler in eval mode: no jitter, so that graph and eager runs see the same samples)
     params = [p for p in m.parameters() if p.requires_grad]
     tables = [p for p in params if p.numel() >= 1 << 14]
     small = [p for p in params if p.numel() < 1 << 14]
@@ -20,7 +20,7 @@ def _setup(capturable):
     opts = [HashGridAdam(tables, lr=1e-2, eps=1e-3, **kw), torch.optim.Adam(small, lr=1e-2, eps=1e-3, fused=True, **kw)]
     from neurad_studio_amd.cameras.rays import RayBundle
 
-    src = _shard(0, 0)  # the batch's tensors live on the device; every step builds its own bundle from them (the model
+    src = shard(0, 0)  # the batch's tensors live on the device; every step builds its own bundle from them (the model
     state = {}          # scales pixel_area and clamps fars IN the bundle it is given: models/neurad.py:443-449,702-709)
 
     def step():
@@ -28,7 +28,7 @@ def _setup(capturable):
             o.zero_grad(set_to_none=True)
         rb = RayBundle(origins=src.origins, directions=src.directions, pixel_area=src.pixel_area.clone(),
                        nears=src.nears.clone(), fars=None, times=src.times, metadata=dict(src.metadata))
-        loss = _loss(m, rb)
+        loss = rehearsal_loss(m, rb)
         loss.backward()
         for o in opts:
             o.step()

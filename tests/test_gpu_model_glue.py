@@ -7,55 +7,23 @@ import pytest
 import torch
 
 from conftest import load_golden, rel_l2
+from builders import trajectories
+from gpu_util import cuda, glue_bundle, glue_model, host
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
-
-
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    return t if dtype is None else t.to(dtype)
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def build_model(g):
-    from neurad_studio_amd.models.neurad import NeuRADHotPath, NeuRADHotPathConfig
-
-    c = NeuRADHotPathConfig(appearance_dim=16)
-    c.field.grid.static.log2_hashmap_size = 10
-    c.field.sdf_beta = 3.0
-    for pf in (c.sampling.proposal_field_1, c.sampling.proposal_field_2):
-        pf.grid.static.log2_hashmap_size = 9
-    m = NeuRADHotPath(c, static_scale=100.0, num_sensors=3, duration=float(g["duration"])).cuda()
-    sd = {k[3:]: dev(v) for k, v in g.items() if k.startswith("sd/") and ".actors." not in k}
-    missing, unexpected = m.load_state_dict(sd, strict=False)
-    assert not missing and not unexpected, (missing, unexpected)  # the reference checkpoint's names, one to one
-    return m
-
-
-def bundle(g):
-    from neurad_studio_amd.cameras.rays import RayBundle
-
-    return RayBundle(origins=dev(g["o"]), directions=dev(g["d"]), pixel_area=dev(g["area"])[:, None],
-                     times=dev(g["times"])[:, None],
-                     metadata={"is_lidar": dev(g["is_lidar"])[:, None], "did_return": dev(g["did_return"])[:, None],
-                               "directions_norm": dev(g["directions_norm"])[:, None],
-                               "sensor_idxs": dev(g["sensor_idxs"])[:, None]})
 
 
 def test_training_outputs_with_lidar_metadata_and_appearance_vs_reference():
     """the OPERATOR-level training path (the reference's orchestration over this package's fields / sampler / renderers);
     the fused training nodes are held against the same golden in tests/test_gpu_train_fused.py"""
     g = load_golden("model_train_glue")
-    m = build_model(g).train()
+    m = glue_model(g).train()
     m.fused_training = False
     m.sampler.eval(), m.field.eval()  # deterministic sampling, as in the generator
     for p in m.proposal_fields:
         p.eval()
-    out = m.get_nff_outputs(bundle(g), calc_lidar_losses=True)
+    out = m.get_nff_outputs(glue_bundle(g), calc_lidar_losses=True)
     assert out["features"].shape == (80, 48)
     for k in ("features", "depth", "accumulation", "prop_depth_0", "prop_depth_1"):
         assert rel_l2(host(out[k]), g[k]) < TOL, k
@@ -74,7 +42,7 @@ def test_training_outputs_with_lidar_metadata_and_appearance_vs_reference():
     from neurad_studio_amd.model_components.lidar_losses import LidarLossSettings, lidar_loss_dict, lidar_metrics
     from neurad_studio_amd.model_components.losses import distortion_loss, zipnerf_interlevel_loss
 
-    is_lidar = dev(g["is_lidar"])
+    is_lidar = cuda(g["is_lidar"])
     intensity, logits = m.decode_lidar(out["features"], is_lidar)
     assert rel_l2(host(intensity), g["intensity"]) < TOL and rel_l2(host(logits), g["ray_drop_logits"]) < TOL
     outputs = dict(out, intensity=intensity, ray_drop_logits=logits)
@@ -82,9 +50,9 @@ def test_training_outputs_with_lidar_metadata_and_appearance_vs_reference():
     lc = g["loss_cfg"]
     assert (cfg.depth_mult, cfg.intensity_mult, cfg.carving_mult, cfg.ray_drop_loss_mult, cfg.prop_lidar_loss_mult,
             cfg.non_return_loss_mult, cfg.non_return_lidar_distance, cfg.quantile_threshold) == tuple(lc[:8])
-    did_return = dev(g["did_return"])[is_lidar]
-    metrics = lidar_metrics(outputs, is_lidar, did_return, dev(g["directions_norm"])[is_lidar][:, None],
-                            dev(g["lidar_points"])[:, 3:4], cfg, fused=False)
+    did_return = cuda(g["did_return"])[is_lidar]
+    metrics = lidar_metrics(outputs, is_lidar, did_return, cuda(g["directions_norm"])[is_lidar][:, None],
+                            cuda(g["lidar_points"])[:, 3:4], cfg, fused=False)
     for k in ("depth_loss", "intensity_loss", "ray_drop_loss", "carving_loss", "depth_loss_0", "depth_loss_1",
               "carving_loss_0", "carving_loss_1"):
         assert abs(float(metrics[k]) / float(g["metric_" + k]) - 1) < 2e-3, (k, float(metrics[k]), float(g["metric_" + k]))
@@ -118,10 +86,10 @@ def test_eval_fused_path_with_appearance_and_normalized_depth():
     """C3 through the fused eval path, and normalize_depth (DepthRenderer('expected'), renderers.py:398-416) against
     the operator-level path of the same model."""
     g = load_golden("model_train_glue")
-    m = build_model(g).eval()
+    m = glue_model(g).eval()
     with torch.no_grad():
-        fused = m.get_nff_outputs(bundle(g))
-    op = m.get_nff_outputs(bundle(g))  # grad enabled -> operator-level path, eval mode (no jitter)
+        fused = m.get_nff_outputs(glue_bundle(g))
+    op = m.get_nff_outputs(glue_bundle(g))  # grad enabled -> operator-level path, eval mode (no jitter)
     assert fused["features"].shape == (80, 48)
     for k in ("features", "depth", "accumulation", "prop_depth_0", "prop_depth_1"):
         assert rel_l2(host(fused[k]), host(op[k])) < 5e-5, k
@@ -130,8 +98,8 @@ def test_eval_fused_path_with_appearance_and_normalized_depth():
 
     m.config.normalize_depth, m.renderer_depth = True, DepthRenderer(method="expected")
     with torch.no_grad():
-        fused_n = m.get_nff_outputs(bundle(g))
-    op_n = m.get_nff_outputs(bundle(g))
+        fused_n = m.get_nff_outputs(glue_bundle(g))
+    op_n = m.get_nff_outputs(glue_bundle(g))
     assert rel_l2(host(fused_n["depth"]), host(op_n["depth"])) < 5e-5
     assert bool((fused_n["depth"] >= fused["depth"] - 1e-6).all())  # dividing by sum w <= 1 never shortens a depth
     # early termination and ray ordering are eval options of the same path: bounded / no change
@@ -141,11 +109,11 @@ def test_eval_fused_path_with_appearance_and_normalized_depth():
     m.config.normalize_depth, m.renderer_depth = False, render_depth_simple
     m.order_rays = True
     with torch.no_grad():
-        ordered = m.get_nff_outputs(bundle(g))
+        ordered = m.get_nff_outputs(glue_bundle(g))
     assert torch.equal(ordered["features"], fused["features"]) and torch.equal(ordered["depth"], fused["depth"])
     m.early_stop_eps = 1e-3
     with torch.no_grad():
-        cut = m.get_nff_outputs(bundle(g))
+        cut = m.get_nff_outputs(glue_bundle(g))
     assert float((cut["accumulation"] - fused["accumulation"]).abs().max()) <= 1.01e-3
 
 
@@ -156,7 +124,6 @@ def test_proposal_field_with_actors_density_and_gradients_vs_reference():
     from neurad_studio_amd.fields.neurad_field import NeuRADProposalField, NeuRADProposalFieldConfig
     from neurad_studio_amd.model_components.dynamic_actors import DynamicActors, DynamicActorsConfig
     from neurad_studio_amd.model_components.ray_samplers import PowerSampler
-    from test_gpu_actors import trajectories
     import synth
 
     g = load_golden("proposal_actors")
@@ -166,13 +133,13 @@ def test_proposal_field_with_actors_density_and_gradients_vs_reference():
     cfg.grid.actor.log2_hashmap_size = 8
     fld = NeuRADProposalField(cfg, actors=actors, static_scale=100.0).cuda().eval()
     with torch.no_grad():
-        fld.hashgrid.static_grid.hash_table.copy_(dev(synth.hash_table(6 * 2**10, 1, seed=61, scale=2.0)))
+        fld.hashgrid.static_grid.hash_table.copy_(cuda(synth.hash_table(6 * 2**10, 1, seed=61, scale=2.0)))
         for i, gr in enumerate(fld.hashgrid.actor_grids):
-            gr.hash_table.copy_(dev(synth.hash_table(4 * 2**8, 1, seed=500 + i, scale=2.5)))
-        fld.density_decoder.weight.copy_(dev(synth.uniform((1, 6), -0.6, 0.6, seed=62)))
+            gr.hash_table.copy_(cuda(synth.hash_table(4 * 2**8, 1, seed=500 + i, scale=2.5)))
+        fld.density_decoder.weight.copy_(cuda(synth.uniform((1, 6), -0.6, 0.6, seed=62)))
     R = g["o"].shape[0]
-    rb = RayBundle(origins=dev(g["o"]), directions=dev(g["d"]), pixel_area=torch.full((R, 1), 2.43e-6, device="cuda"),
-                   times=dev(g["times"])[:, None], nears=torch.zeros(R, 1, device="cuda"),
+    rb = RayBundle(origins=cuda(g["o"]), directions=cuda(g["d"]), pixel_area=torch.full((R, 1), 2.43e-6, device="cuda"),
+                   times=cuda(g["times"])[:, None], nears=torch.zeros(R, 1, device="cuda"),
                    fars=torch.full((R, 1), 60.0, device="cuda"))
     rs = PowerSampler(num_samples=40, lambda_=-1.0, scaling=0.1).eval()(rb)
     with torch.no_grad():
@@ -180,7 +147,7 @@ def test_proposal_field_with_actors_density_and_gradients_vs_reference():
     assert rel_l2(host(d0[..., 0]), g["density"]) < TOL
     dens, _ = fld.get_density(rs)
     assert rel_l2(host(dens[..., 0]), g["density"]) < TOL
-    (dens[..., 0] * dev(g["g_density"])).sum().backward()
+    (dens[..., 0] * cuda(g["g_density"])).sum().backward()
     tg = host(fld.hashgrid.static_grid.hash_table.grad)
     ref_tg = np.zeros_like(tg)
     ref_tg[g["tg_idx"]] = g["tg_val"]
@@ -210,8 +177,8 @@ def test_rgb_cnn_decoder_vs_reference():
             w = (synth.normal(tuple(p.shape), 600 + k) * (1.0 / np.sqrt(fan_in) if p.dim() > 1 else 0.1)).astype(np.float32)
             if name.endswith(("1.weight", "4.weight")) and p.dim() == 1:
                 w = w + 1.0
-            p.copy_(dev(w))
-    feats = dev(g["features"])
+            p.copy_(cuda(w))
+    feats = cuda(g["features"])
     import copy
 
     # (1) the torch modules in fp32: the golden's own arithmetic
@@ -244,10 +211,10 @@ def test_chunked_eval_entry_and_lidar_head():
     """get_outputs_for_ray_bundle (the chunked entry of models/neurad.py:623-675): chunks of any size give the outputs of
     one call, the lidar head runs on the rendered features; also through the reference's own slicing protocol."""
     g = load_golden("model_train_glue")
-    m = build_model(g).eval()
+    m = glue_model(g).eval()
     with torch.no_grad():
-        whole = m.get_nff_outputs(bundle(g))
-    out = m.get_outputs_for_ray_bundle(bundle(g), num_rays_per_chunk=32, is_lidar=True)  # 80 rays -> 32 + 32 + 16
+        whole = m.get_nff_outputs(glue_bundle(g))
+    out = m.get_outputs_for_ray_bundle(glue_bundle(g), num_rays_per_chunk=32, is_lidar=True)  # 80 rays -> 32 + 32 + 16
     for k in ("features", "depth", "accumulation", "prop_depth_0", "prop_depth_1"):
         assert torch.equal(out[k], whole[k]), k  # per-ray kernels: chunking changes nothing, bit for bit
     intensity, logit = m.decode_lidar(whole["features"])
@@ -265,7 +232,7 @@ def test_chunked_eval_entry_and_lidar_head():
             from neurad_studio_amd.models.neurad import _slice_bundle
             return _slice_bundle(self.rb, a, b)
 
-    out2 = m.get_outputs_for_ray_bundle(RefLikeBundle(bundle(g)), num_rays_per_chunk=50)
+    out2 = m.get_outputs_for_ray_bundle(RefLikeBundle(glue_bundle(g)), num_rays_per_chunk=50)
     assert torch.equal(out2["features"], whole["features"]) and "intensity" not in out2
 
 
@@ -288,7 +255,6 @@ def test_model_eval_with_actors_fused_render_matches_operator_path():
     from neurad_studio_amd.cameras.rays import RayBundle
     from neurad_studio_amd.model_components.dynamic_actors import DynamicActors, DynamicActorsConfig
     from neurad_studio_amd.models.neurad import NeuRADHotPath, NeuRADHotPathConfig
-    from test_gpu_actors import trajectories
 
     torch.manual_seed(1)
     c = NeuRADHotPathConfig(appearance_dim=0)
@@ -311,7 +277,7 @@ def test_model_eval_with_actors_fused_render_matches_operator_path():
     R = 256
     gen = torch.Generator().manual_seed(5)
     times = 1.0 + torch.rand(R, 1, generator=gen)  # all three trajectories exist in [1, 2]
-    a = torch.arange(R) % 3  # look at actor a, where it is at the ray's time (test_gpu_actors.trajectories), from ~4 m:
+    a = torch.arange(R) % 3  # look at actor a, where it is at the ray's time (builders.trajectories), from ~4 m:
     tgt = torch.stack([12.0 + 2.0 * times[:, 0] + a, torch.tensor([8.0, -6.0, -5.0])[a], torch.full((R,), 0.5)], -1)
     side = torch.nn.functional.normalize(torch.randn(R, 3, generator=gen) * torch.tensor([1.0, 1.0, 0.15]), dim=-1)
     o = tgt + 4.0 * side  # the box fills the first metres of the ray, where the samplers put their samples

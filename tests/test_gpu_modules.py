@@ -7,43 +7,11 @@ import torch
 import neurad_oracle as O
 import synth
 from conftest import load_golden, rel_l2
+from builders import trajectories
+from gpu_util import bundle, cuda, host, make_field, make_prop, small_model
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def make_field(use_sdf, lg=11, num_multisamples=1):
-    from neurad_studio_amd.fields.neurad_field import NeuRADField, NeuRADFieldConfig
-
-    cfg = NeuRADFieldConfig(use_sdf=use_sdf, num_multisamples=num_multisamples)
-    cfg.grid.static.log2_hashmap_size = lg
-    f = NeuRADField(cfg, actors=None, static_scale=100.0).cuda()
-    with torch.no_grad():
-        f.hashgrid.static_grid.hash_table.copy_(dev(synth.hash_table(8 * 2**lg, 4, seed=51, scale=0.5)))
-        for k, l in enumerate(f.mlp_geo.layers):
-            w, b = synth.linear(l.out_features, l.in_features, 200 + 10 * k)
-            l.weight.copy_(dev(w)), l.bias.copy_(dev(b))
-        for k, l in enumerate(f.mlp_feature.layers):
-            w, b = synth.linear(l.out_features, l.in_features, 300 + 10 * k)
-            l.weight.copy_(dev(w)), l.bias.copy_(dev(b))
-    return f
-
-
-def bundle(o, d, area, fars=None):
-    from neurad_studio_amd.cameras.rays import RayBundle
-
-    R = o.shape[0]
-    return RayBundle(origins=dev(o), directions=dev(d), pixel_area=dev(area)[:, None],
-                     nears=torch.zeros(R, 1, device="cuda"),
-                     fars=torch.full((R, 1), 20000.0, device="cuda") if fars is None else dev(fars)[:, None])
 
 
 @pytest.mark.parametrize("fused_training", [True, False], ids=["fused-train", "operator-train"])
@@ -69,7 +37,7 @@ def test_field_forward_backward_vs_reference_autograd(tag, fused_training):
     assert rel_l2(host(out_f[FieldHeadNames.FEATURE]), g["feature"]) < TOL
     assert rel_l2(host(out[key][..., 0]), g["alpha" if tag == "sdf" else "density"]) < TOL
     assert rel_l2(host(out_f[key][..., 0]), host(out[key][..., 0])) < 1e-5
-    ((out[FieldHeadNames.FEATURE] * dev(g["g_feature"])).sum() + (out[key][..., 0] * dev(g["g_head"])).sum()).backward()
+    ((out[FieldHeadNames.FEATURE] * cuda(g["g_feature"])).sum() + (out[key][..., 0] * cuda(g["g_head"])).sum()).backward()
     tg = np.zeros((8 * 2**11, 4), np.float32)
     tg[g["tg_idx"]] = g["tg_val"]
     assert rel_l2(host(fld.hashgrid.static_grid.hash_table.grad), tg) < TOL
@@ -98,7 +66,7 @@ def test_field_multisampled_vs_reference_golden():
         assert rel_l2(host(o_[FieldHeadNames.FEATURE]), gm["feature"]) < TOL
         assert rel_l2(host(o_[FieldHeadNames.ALPHA][..., 0]), gm["alpha"]) < TOL
         assert rel_l2(host(o_[FieldHeadNames.SDF][..., 0]), gm["sdf"]) < TOL
-    ((out[FieldHeadNames.FEATURE] * dev(g["g_feature"])).sum() + (out[FieldHeadNames.ALPHA][..., 0] * dev(g["g_head"])).sum()).backward()
+    ((out[FieldHeadNames.FEATURE] * cuda(g["g_feature"])).sum() + (out[FieldHeadNames.ALPHA][..., 0] * cuda(g["g_head"])).sum()).backward()
     tg = np.zeros((8 * 2**11, 4), np.float32)
     tg[gm["tg_idx"]] = gm["tg_val"]
     assert rel_l2(host(fld.hashgrid.static_grid.hash_table.grad), tg) < TOL
@@ -106,24 +74,10 @@ def test_field_multisampled_vs_reference_golden():
     # dynamic actors + multisampling is refused at construction
     from neurad_studio_amd.fields.neurad_field import NeuRADField, NeuRADFieldConfig
     from neurad_studio_amd.model_components.dynamic_actors import DynamicActors, DynamicActorsConfig
-    from test_gpu_actors import trajectories
 
     with pytest.raises(NotImplementedError, match="num_multisamples"):
         NeuRADField(NeuRADFieldConfig(num_multisamples=2), actors=DynamicActors(DynamicActorsConfig(), trajectories=trajectories()),
                     static_scale=100.0)
-
-
-def make_prop(seed, lg=11):
-    from neurad_studio_amd.fields.neurad_field import NeuRADProposalField, NeuRADProposalFieldConfig
-
-    c = NeuRADProposalFieldConfig()
-    c.grid.static.log2_hashmap_size = lg
-    p = NeuRADProposalField(c, actors=None, static_scale=100.0).cuda()
-    w, _ = synth.linear(1, 6, seed + 1, bias=False)
-    with torch.no_grad():
-        p.hashgrid.static_grid.hash_table.copy_(dev(synth.hash_table(6 * 2**lg, 1, seed=seed, scale=2.0)))
-        p.density_decoder.weight.copy_(dev(w + np.float32(0.3)))
-    return p
 
 
 def test_proposal_sampler_module_vs_reference_golden():
@@ -147,24 +101,6 @@ def test_proposal_sampler_module_vs_reference_golden():
         assert rel_l2(host(r.frustums.starts[..., 0]), g["starts"]) < TOL
         assert rel_l2(host(r.frustums.ends[..., 0]), g["ends"]) < TOL
         assert rel_l2(host(r.spacing_ends[..., 0]), g["spe"]) < TOL
-
-
-def small_model(use_sdf=True):
-    from neurad_studio_amd.models.neurad import NeuRADHotPath, NeuRADHotPathConfig
-
-    c = NeuRADHotPathConfig(appearance_dim=0)
-    c.field.use_sdf = use_sdf
-    c.field.sdf_beta = 3.0
-    c.field.grid.static.log2_hashmap_size = 12
-    c.sampling.proposal_field_1.grid.static.log2_hashmap_size = 11
-    c.sampling.proposal_field_2.grid.static.log2_hashmap_size = 11
-    torch.manual_seed(0)
-    m = NeuRADHotPath(c, static_scale=100.0).cuda()
-    with torch.no_grad():
-        m.field.hashgrid.static_grid.hash_table.mul_(1000.0)  # O(1) features so alphas vary
-        for p in m.proposal_fields:
-            p.hashgrid.static_grid.hash_table.mul_(2000.0)
-    return m
 
 
 @pytest.mark.parametrize("use_sdf", [True, False])
@@ -216,9 +152,9 @@ def test_nerfacc_shaped_shim_and_renderers():
     from neurad_studio_amd.model_components.renderers import AccumulationRenderer, FeatureRenderer
     from neurad_studio_amd.shims import nerfacc
 
-    a = dev(synth.uniform((9, 40), 0, 0.3, 1)).requires_grad_(True)
+    a = cuda(synth.uniform((9, 40), 0, 0.3, 1)).requires_grad_(True)
     w, t = nerfacc.render_weight_from_alpha(a)
-    feats = dev(synth.normal((9, 40, 32), 2))
+    feats = cuda(synth.normal((9, 40, 32), 2))
     out = FeatureRenderer()(features=feats, weights=w[..., None])
     acc = AccumulationRenderer()(weights=w[..., None])
     (out.sum() + acc.sum()).backward()
@@ -238,7 +174,7 @@ def test_tinycudann_shaped_shim_matches_torch_path_oracle():
                "n_hidden_layers": 1}
     m = tcnn.NetworkWithInputEncoding(3, 16, enc_cfg, net_cfg).cuda()
     x = synth.uniform((777, 3), 0, 1, 4)
-    y = m(dev(x))
+    y = m(cuda(x))
     table = host(m.encoding.params).reshape(-1, 2)
     sc = O.hash_scalings(16, 16, 1024)
     np.testing.assert_array_equal(m.encoding.spec.scalings.numpy(), sc)
@@ -249,7 +185,7 @@ def test_tinycudann_shaped_shim_matches_torch_path_oracle():
     assert m.encoding.params.grad.abs().sum() > 0 and m.network.layers[0].weight.grad.abs().sum() > 0
     sh = tcnn.Encoding(3, {"otype": "SphericalHarmonics", "degree": 4}).cuda()
     d = synth.uniform((50, 3), 0, 1, 5)
-    assert rel_l2(host(sh(dev(d))), O.sh_deg4(d)) < 1e-6
+    assert rel_l2(host(sh(cuda(d))), O.sh_deg4(d)) < 1e-6
 
 
 def test_full_size_neurad_default_chain_properties():

@@ -6,12 +6,9 @@ import torch
 
 import occgrid_oracle as OO
 import synth
+from gpu_util import cuda
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @pytest.mark.parametrize("cone", [0.0, 0.01])
@@ -27,8 +24,8 @@ def test_occgrid_march_vs_restatement(cone):
     d[:5, 0] = 0.0  # axis-parallel components
     d = (d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32)
     t_max = synth.uniform((R,), 5.0, 60.0, 3)
-    ri, ts, te, seg = ops.occgrid_march(ops.OccGridSpec(torch.from_numpy(aabb), dev(binaries)), dev(o), dev(d), 0.25,
-                                        near_plane=0.1, far_plane=40.0, t_max=dev(t_max), cone_angle=cone)
+    ri, ts, te, seg = ops.occgrid_march(ops.OccGridSpec(torch.from_numpy(aabb), cuda(binaries)), cuda(o), cuda(d), 0.25,
+                                        near_plane=0.1, far_plane=40.0, t_max=cuda(t_max), cone_angle=cone)
     rri, rts, rte = OO.occgrid_march(aabb, binaries, o, d, 0.25, 0.1, 40.0, None, t_max, cone)
     ri, ts, te = ri.cpu().numpy(), ts.cpu().numpy(), te.cpu().numpy()
     # midpoint cell tests are discrete: allow a handful of boundary flips, compare the rest exactly
@@ -54,9 +51,9 @@ def test_estimator_sampling_with_alpha_pruning_and_empty_grid():
 
     est = OccGridEstimator([-5, -5, -5, 5, 5, 5], resolution=16)
     R = 64
-    o = dev(np.zeros((R, 3), np.float32))
+    o = cuda(np.zeros((R, 3), np.float32))
     d = synth.normal((R, 3), 5)
-    d = dev((d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32))
+    d = cuda((d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32))
     ri, ts, te = est.sampling(o, d, render_step_size=0.5, far_plane=100.0)
     assert ri.numel() > 0 and float(te.max()) <= 5 * np.sqrt(3) + 1e-3
     alpha_fn = lambda ts, te, ri: torch.full_like(ts, 0.5)  # noqa: E731
@@ -82,7 +79,7 @@ def test_volumetric_sampler_module():
     R = 32
     d = synth.normal((R, 3), 6)
     rb = RayBundle(origins=torch.zeros(R, 3, device="cuda"),
-                   directions=dev((d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32)),
+                   directions=cuda((d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32)),
                    pixel_area=torch.full((R, 1), 1e-6, device="cuda"), nears=torch.zeros(R, 1, device="cuda"),
                    fars=torch.full((R, 1), 3.0, device="cuda"))
     s = VolumetricSampler(est).eval()

@@ -11,6 +11,7 @@ import torch
 import occgrid_update_restatement as UR
 import synth
 from conftest import rel_l2
+from gpu_util import cuda, host
 
 pytestmark = pytest.mark.gpu
 
@@ -18,22 +19,13 @@ TIGHT = 2e-5  # tests/test_gpu_packed.py
 UNIT = [-1.0, -1.0, -1.0, 1.0, 1.0, 1.0]
 
 
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    return t if dtype is None else t.to(dtype)
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def dev_draws(d, warmup):
-    return dict(cell_draws=None if warmup else dev(d["cell_draws"]), sel_draws=None if warmup else dev(d["sel_draws"]),
-                jitter=dev(d["jitter"]))
+    return dict(cell_draws=None if warmup else cuda(d["cell_draws"]), sel_draws=None if warmup else cuda(d["sel_draws"]),
+                jitter=cuda(d["jitter"]))
 
 
 def shell_occ_torch(p):
@@ -70,8 +62,8 @@ def test_candidates_equal_the_restatement(case):
         assert n_occ[0] > n
     if case == "two_levels":
         assert n_occ[0] > n >= n_occ[1] > 0
-    grid = ops.OccGridSpec(torch.tensor(UNIT), dev(binaries))
-    ids, counts, pos = ops.occgrid_update_candidates(grid, dev(occs), warmup, **dev_draws(d, warmup))
+    grid = ops.OccGridSpec(torch.tensor(UNIT), cuda(binaries))
+    ids, counts, pos = ops.occgrid_update_candidates(grid, cuda(occs), warmup, **dev_draws(d, warmup))
     assert ids.shape == (L, cap) and pos.shape == (L * cap, 3)
     np.testing.assert_array_equal(host(counts), want_counts)
     np.testing.assert_array_equal(host(ids), want_ids)
@@ -93,8 +85,8 @@ def test_positions_lie_in_their_cells(box):
     d["jitter"][0, :8] = np.float32(1.0 - 2.0 ** -24)  # the largest jitter there is
     d["jitter"][0, 8:16] = 0.0
     aabbs = UR.level_aabbs(box, L)
-    grid = ops.OccGridSpec(torch.from_numpy(aabbs), dev(binaries))
-    ids, counts, pos = ops.occgrid_update_candidates(grid, dev(occs), False, **dev_draws(d, False))
+    grid = ops.OccGridSpec(torch.from_numpy(aabbs), cuda(binaries))
+    ids, counts, pos = ops.occgrid_update_candidates(grid, cuda(occs), False, **dev_draws(d, False))
     ids, pos = host(ids), host(pos).reshape(L, -1, 3)
     want32, want64 = UR.positions(aabbs, res, ids, d["jitter"]), UR.positions(aabbs, res, ids, d["jitter"], np.float64)
     lo, hi = UR.cell_boxes(aabbs, res, ids)
@@ -139,9 +131,9 @@ def test_ema_takes_the_max_over_duplicates_and_decays_once():
     occs[[10, 11]] = [0.5, 0.5]
     ids[0, 210:214] = [5, 6, 7, 9]  # behind the count: ignored whatever they hold
     vals[0, 210:214] = 100.0
-    grid = ops.OccGridSpec(torch.tensor(UNIT), dev(binaries))
-    got = dev(occs)
-    ops.occgrid_update_apply(grid, got, dev(ids), dev(counts), dev(vals), decay, 1e-2)
+    grid = ops.OccGridSpec(torch.tensor(UNIT), cuda(binaries))
+    got = cuda(occs)
+    ops.occgrid_update_apply(grid, got, cuda(ids), cuda(counts), cuda(vals), decay, 1e-2)
     got = host(got)
     want = occs.copy()
     for l in range(L):  # written out cell by cell
@@ -226,7 +218,7 @@ def test_gating_first_update_and_state_dict_round_trip():
     # in-place edits of the binaries are what the march sees
     est.binaries[:] = False
     o = torch.zeros(8, 3, device="cuda")
-    dirs = torch.nn.functional.normalize(dev(synth.normal((8, 3), 5)), dim=-1)
+    dirs = torch.nn.functional.normalize(cuda(synth.normal((8, 3), 5)), dim=-1)
     assert est.sampling(o, dirs, render_step_size=0.1)[0].numel() == 0
 
 
@@ -274,11 +266,11 @@ def test_one_level_is_the_single_grid_march(cone):
     binaries = np.random.default_rng(0).random((res, res, res)) < 0.3
     aabb = torch.tensor([-10.0, -10, -2, 10, 10, 6])
     o, d = march_inputs(R, 1, [6.0, 6.0, 2.0])
-    t_max = dev(synth.uniform((R,), 5.0, 60.0, 3))
-    args = (dev(o), dev(d), 0.25)
+    t_max = cuda(synth.uniform((R,), 5.0, 60.0, 3))
+    args = (cuda(o), cuda(d), 0.25)
     kw = dict(near_plane=0.1, far_plane=40.0, t_max=t_max, cone_angle=cone)
-    single = ops.occgrid_march(ops.OccGridSpec(aabb, dev(binaries)), *args, **kw)
-    levels = ops.occgrid_march(ops.OccGridSpec(aabb[None], dev(binaries[None])), *args, **kw)
+    single = ops.occgrid_march(ops.OccGridSpec(aabb, cuda(binaries)), *args, **kw)
+    levels = ops.occgrid_march(ops.OccGridSpec(aabb[None], cuda(binaries[None])), *args, **kw)
     assert single[0].numel() > 1000
     for a, b in zip(single, levels):
         assert torch.equal(a, b) if a.dtype == torch.int64 else torch.equal(a.view(torch.int32), b.view(torch.int32))
@@ -296,7 +288,7 @@ def test_three_level_march_vs_restatement(cone):
     aabbs = UR.level_aabbs(UNIT, L)
     o, d = march_inputs(R, 8, [0.9, 0.9, 0.9])
     o[:20] *= 4.0  # some origins in the outer levels and outside the grid
-    ri, ts, te, seg = ops.occgrid_march(ops.OccGridSpec(torch.from_numpy(aabbs), dev(binaries)), dev(o), dev(d), step,
+    ri, ts, te, seg = ops.occgrid_march(ops.OccGridSpec(torch.from_numpy(aabbs), cuda(binaries)), cuda(o), cuda(d), step,
                                         near_plane=0.05, far_plane=30.0, cone_angle=cone)
     ri, ts, te = host(ri), host(ts), host(te)
     m = UR.march_levels(aabbs, binaries, o, d, step, 0.05, 30.0, cone_angle=cone)
@@ -370,7 +362,7 @@ def test_pruned_route_end_to_end():
     res, R, step = 16, 96, 0.07
     rng = np.random.default_rng(3)
     inside = rng.random((res, res, res)) < 0.25
-    inside_t = dev(inside)
+    inside_t = cuda(inside)
 
     def cell_of(p):
         i = torch.clamp(torch.floor((p + 1.0) / 2.0 * res).long(), 0, res - 1)
@@ -378,11 +370,11 @@ def test_pruned_route_end_to_end():
 
     sigma = lambda p: cell_of(p).float()[:, None] * 6.0  # noqa: E731
     o, d = march_inputs(R, 60, [0.5, 0.5, 0.5])
-    o_t, d_t = dev(o), dev(d)
+    o_t, d_t = cuda(o), cuda(d)
     est = OccGridEstimator(UNIT, resolution=res)
     before = est.sampling(o_t, d_t, render_step_size=step)
     jitter = np.random.default_rng(4).random((1, res ** 3, 3), dtype=np.float32) * np.float32(0.999)  # strictly inside
-    est._update(0, lambda p: sigma(p) * step, jitter=dev(jitter))
+    est._update(0, lambda p: sigma(p) * step, jitter=cuda(jitter))
     np.testing.assert_array_equal(host(est.binaries[0]), inside)
     after = est.sampling(o_t, d_t, render_step_size=step, stratified=False)
     m = UR.march_levels(np.asarray([UNIT], np.float32), inside[None], o, d, step)
@@ -419,9 +411,9 @@ def test_density_fn_equals_get_density_and_feeds_the_update():
     fld = NeuRADProposalField(c, actors=None, static_scale=10.0).cuda()
     w, _ = synth.linear(1, 6, 72, bias=False)
     with torch.no_grad():
-        fld.hashgrid.static_grid.hash_table.copy_(dev(synth.hash_table(6 * 2 ** lg, 1, seed=71, scale=2.0)))
-        fld.density_decoder.weight.copy_(dev(w + np.float32(0.3)))
-    p = dev(synth.normal((500, 3), 73) * 8.0)
+        fld.hashgrid.static_grid.hash_table.copy_(cuda(synth.hash_table(6 * 2 ** lg, 1, seed=71, scale=2.0)))
+        fld.density_decoder.weight.copy_(cuda(w + np.float32(0.3)))
+    p = cuda(synth.normal((500, 3), 73) * 8.0)
     zero = torch.zeros_like(p[:, None, :1])
     rs = RaySamples(frustums=Frustums(origins=p[:, None], directions=torch.ones_like(p[:, None]), starts=zero, ends=zero,
                                       pixel_area=torch.ones_like(zero)))
@@ -434,7 +426,7 @@ def test_density_fn_equals_get_density_and_feeds_the_update():
     assert float(got.std()) > 0 and torch.isfinite(got).all()
     est = OccGridEstimator([-8, -8, -8, 8, 8, 8], resolution=16, levels=2)
     fld.train()
-    jitter = dev(np.random.default_rng(5).random((2, 16 ** 3, 3), dtype=np.float32))
+    jitter = cuda(np.random.default_rng(5).random((2, 16 ** 3, 3), dtype=np.float32))
     est.update_every_n_steps(0, occ_eval_fn=fld.density_fn)
     prev = est.occs.clone()
     ids, counts, pos = est._update(16, fld.density_fn, occ_thre=1e9, jitter=jitter)  # thre = the mean of the densities

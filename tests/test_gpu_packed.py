@@ -1,7 +1,7 @@
 """Packed (ragged) compositing of the occupancy-marched samples, forward and backward, from the kernels to the renderers.
 What is pinned: the reference's RaySamples.get_weights golden on truncated rays (1), a float64 restatement written from
 the formulas (tests/packed_restatement.py) for every op's forward and -- through float64 torch autograd -- backward (2, 3),
-the dense kernels on uniform segments (4), the saturated input families of test_gpu_saturation.py per element (5),
+the dense kernels on uniform segments (4), the saturated input families of tests/sharp_refs.py per element (5),
 bitwise reproducibility (6), the segment search (7), the module-level sequence VolumetricSampler -> field -> packed
 renderers (8), the dense operator path end to end (9) and graph capture (10).  Parity with nerfacc itself stays unpinned.
 Tolerances are those of tests/test_gpu_parity.py for the dense kernels this mirrors."""
@@ -12,31 +12,14 @@ import torch
 import packed_restatement as PR
 import synth
 from conftest import load_golden, rel_l2
+from gpu_util import cuda, host64, make_field, ray_bundle
+from gpu_util import ops  # noqa: F401  (fixture)
+from sharp_refs import SAMPLES, TINY, U, check, ref_alpha, ref_density, sharp_alphas, sharp_bins
 
 pytestmark = pytest.mark.gpu
 
 TIGHT, TOL = 2e-5, 1e-4
-U = 2.0 ** -24  # fp32 unit roundoff
-TINY = 2.0 ** -126  # fp32's smallest normal number
-ONE_BELOW = np.float32(1.0 - 2.0 ** -24)
 CHANNELS = [1, 3, 32, 48]
-
-
-@pytest.fixture(scope="module")
-def ops():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from neurad_studio_amd import ops as _ops
-
-    return _ops
-
-
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    return t if dtype is None else t.to(dtype)
-
-
-def host(t):
-    return t.detach().cpu().numpy().astype(np.float64)
 
 
 def ragged_counts(R, seed):
@@ -70,7 +53,7 @@ def ragged_inputs(seed, C, R=200):
 
 
 def on_device(p):
-    return {k: (dev(v) if isinstance(v, np.ndarray) and k != "counts" else v) for k, v in p.items()}
+    return {k: (cuda(v) if isinstance(v, np.ndarray) and k != "counts" else v) for k, v in p.items()}
 
 
 # ---- 1. reference anchor ---------------------------------------------------------------------------------------------
@@ -85,12 +68,12 @@ def test_packed_weights_against_the_reference_golden(ops):
     seg = PR.segments_from_counts(n)
     pick = np.concatenate([np.arange(r * S, r * S + n[r]) for r in range(R)])
     ts, te = eu[:, :-1].reshape(-1)[pick], eu[:, 1:].reshape(-1)[pick]
-    w, _, _ = ops.packed_weight_from_density(dev(ts), dev(te), dev(dens.reshape(-1)[pick]), dev(seg))
+    w, _, _ = ops.packed_weight_from_density(cuda(ts), cuda(te), cuda(dens.reshape(-1)[pick]), cuda(seg))
     want = w0.reshape(-1)[pick]
     ref = PR.weight_from_density(PR.f64(ts), PR.f64(te), PR.f64(dens.reshape(-1)[pick]), seg)[0].numpy()
-    print(f"restatement vs golden {rel_l2(ref, want):.3g}, kernel vs golden {rel_l2(host(w), want):.3g}")
+    print(f"restatement vs golden {rel_l2(ref, want):.3g}, kernel vs golden {rel_l2(host64(w), want):.3g}")
     assert rel_l2(ref, want) < TIGHT
-    assert rel_l2(host(w), want) < TIGHT
+    assert rel_l2(host64(w), want) < TIGHT
 
 
 # ---- 2. forward against the float64 restatement -------------------------------------------------------------------------
@@ -101,15 +84,15 @@ def test_weight_ops_forward(ops):
     w, t, a = ops.packed_weight_from_density(d["ts"], d["te"], d["sig"], d["seg"])
     rw, rt, ra = PR.weight_from_density(ts, te, sig, p["seg"])
     for got, want, what in ((w, rw, "weights"), (t, rt, "trans"), (a, ra, "alphas")):
-        err = rel_l2(host(got), want.numpy())
+        err = rel_l2(host64(got), want.numpy())
         print(f"density {what}: {err:.3g}")
-        assert np.isfinite(host(got)).all() and err < TIGHT, what
+        assert np.isfinite(host64(got)).all() and err < TIGHT, what
     w, t = ops.packed_weight_from_alpha(d["alpha"], d["seg"])
     rw, rt = PR.weight_from_alpha(al, p["seg"])
     for got, want, what in ((w, rw, "weights"), (t, rt, "trans")):
-        err = rel_l2(host(got), want.numpy())
+        err = rel_l2(host64(got), want.numpy())
         print(f"alpha {what}: {err:.3g}")
-        assert np.isfinite(host(got)).all() and err < TIGHT, what
+        assert np.isfinite(host64(got)).all() and err < TIGHT, what
 
 
 @pytest.mark.parametrize("C", CHANNELS)
@@ -119,23 +102,23 @@ def test_accumulate_and_composite_forward(ops, C):
     empty = p["counts"] == 0
     ts, te, sig, al, feat = (PR.f64(p[k]) for k in ("ts", "te", "sig", "alpha", "feat"))
     w64 = PR.weight_from_alpha(al, p["seg"])[0]
-    w32 = dev(w64.numpy().astype(np.float32))
+    w32 = cuda(w64.numpy().astype(np.float32))
     out = ops.packed_accumulate(w32, d["feat"], d["seg"])
     want = PR.accumulate(PR.f64(w32), feat, p["seg"]).numpy()
-    assert out.shape == (p["R"], C) and rel_l2(host(out), want) < TIGHT
-    assert (host(out)[empty] == 0).all() and np.isfinite(host(out)).all()
+    assert out.shape == (p["R"], C) and rel_l2(host64(out), want) < TIGHT
+    assert (host64(out)[empty] == 0).all() and np.isfinite(host64(out)).all()
     out1 = ops.packed_accumulate(w32, None, d["seg"])
-    assert out1.shape == (p["R"], 1) and rel_l2(host(out1), PR.accumulate(PR.f64(w32), None, p["seg"]).numpy()) < TIGHT
-    assert (host(out1)[empty] == 0).all()
+    assert out1.shape == (p["R"], 1) and rel_l2(host64(out1), PR.accumulate(PR.f64(w32), None, p["seg"]).numpy()) < TIGHT
+    assert (host64(out1)[empty] == 0).all()
     for density_mode, x64, x in ((True, sig, d["sig"]), (False, al, d["alpha"])):
         of, od, oa, ow = ops.packed_composite_fwd(d["ts"], d["te"], x, d["feat"], d["seg"], density_mode)
         rf, rd, ra, rw = PR.composite(ts, te, x64, feat, p["seg"], density_mode)
         for got, want, what in ((of, rf, "features"), (od, rd, "depth"), (oa, ra, "accumulation"), (ow, rw, "weights")):
-            err = rel_l2(host(got), want.numpy())
+            err = rel_l2(host64(got), want.numpy())
             print(f"C={C} density_mode={density_mode} {what}: {err:.3g}")
-            assert got.shape == want.shape and np.isfinite(host(got)).all() and err < TIGHT, (what, density_mode)
+            assert got.shape == want.shape and np.isfinite(host64(got)).all() and err < TIGHT, (what, density_mode)
         for got in (of, od, oa):
-            assert (host(got)[empty] == 0).all()
+            assert (host64(got)[empty] == 0).all()
         # the unfused chain gives the same numbers as the fused kernel
         w_unf = (ops.packed_weight_from_density(d["ts"], d["te"], x, d["seg"]) if density_mode
                  else ops.packed_weight_from_alpha(x, d["seg"]))[0]
@@ -170,18 +153,18 @@ def test_weight_ops_backward(ops):
     gw, gt = synth.normal((M,), 32), synth.normal((M,), 33)
     sig = PR.f64(p["sig"], grad=True)
     (PR.weight_from_density(PR.f64(p["ts"]), PR.f64(p["te"]), sig, p["seg"])[0] * PR.f64(gw)).sum().backward()
-    gs = ops.packed_weight_from_density_bwd(d["ts"], d["te"], d["sig"], d["seg"], dev(gw))
-    err = rel_l2(host(gs), sig.grad.numpy())
+    gs = ops.packed_weight_from_density_bwd(d["ts"], d["te"], d["sig"], d["seg"], cuda(gw))
+    err = rel_l2(host64(gs), sig.grad.numpy())
     print(f"grad_sigmas: {err:.3g}")
-    assert np.isfinite(host(gs)).all() and err < TOL
+    assert np.isfinite(host64(gs)).all() and err < TOL
     for with_gt in (True, False):
         al = PR.f64(p["alpha"], grad=True)
         w, t = PR.weight_from_alpha(al, p["seg"])
         ((w * PR.f64(gw)).sum() + ((t * PR.f64(gt)).sum() if with_gt else 0)).backward()
-        ga = ops.packed_weight_from_alpha_bwd(d["alpha"], d["seg"], dev(gw), dev(gt) if with_gt else None)
-        err = rel_l2(host(ga), al.grad.numpy())
+        ga = ops.packed_weight_from_alpha_bwd(d["alpha"], d["seg"], cuda(gw), cuda(gt) if with_gt else None)
+        err = rel_l2(host64(ga), al.grad.numpy())
         print(f"grad_alphas (grad_t {with_gt}): {err:.3g}")
-        assert np.isfinite(host(ga)).all() and err < TOL
+        assert np.isfinite(host64(ga)).all() and err < TOL
 
 
 def test_weight_autograd_nodes(ops):
@@ -190,7 +173,7 @@ def test_weight_autograd_nodes(ops):
 
     p = ragged_inputs(35, 1)
     d = on_device(p)
-    gw, gt = dev(synth.normal((p["M"],), 36)), dev(synth.normal((p["M"],), 37))
+    gw, gt = cuda(synth.normal((p["M"],), 36)), cuda(synth.normal((p["M"],), 37))
     sig = d["sig"].clone().requires_grad_(True)
     w, t, a = ag.PackedWeightFromDensityFn.apply(d["ts"], d["te"], sig, d["seg"])
     assert w.requires_grad and not t.requires_grad and not a.requires_grad
@@ -212,25 +195,25 @@ def test_accumulate_backward(ops, C):
     g = synth.normal((p["R"], C), 42)
     w, v = PR.f64(w32, grad=True), PR.f64(p["feat"], grad=True)
     (PR.accumulate(w, v, p["seg"]) * PR.f64(g)).sum().backward()
-    gw, gv = ops.packed_accumulate_bwd(dev(w32), d["feat"], dev(g), d["seg"])
-    print(f"C={C} grad_weights {rel_l2(host(gw), w.grad.numpy()):.3g} grad_values {rel_l2(host(gv), v.grad.numpy()):.3g}")
-    assert rel_l2(host(gw), w.grad.numpy()) < TIGHT and rel_l2(host(gv), v.grad.numpy()) < TIGHT
+    gw, gv = ops.packed_accumulate_bwd(cuda(w32), d["feat"], cuda(g), d["seg"])
+    print(f"C={C} grad_weights {rel_l2(host64(gw), w.grad.numpy()):.3g} grad_values {rel_l2(host64(gv), v.grad.numpy()):.3g}")
+    assert rel_l2(host64(gw), w.grad.numpy()) < TIGHT and rel_l2(host64(gv), v.grad.numpy()) < TIGHT
     # each gradient only when it is needed
-    only_w = ops.packed_accumulate_bwd(dev(w32), d["feat"], dev(g), d["seg"], need_grad_values=False)
-    only_v = ops.packed_accumulate_bwd(dev(w32), d["feat"], dev(g), d["seg"], need_grad_weights=False)
+    only_w = ops.packed_accumulate_bwd(cuda(w32), d["feat"], cuda(g), d["seg"], need_grad_values=False)
+    only_v = ops.packed_accumulate_bwd(cuda(w32), d["feat"], cuda(g), d["seg"], need_grad_weights=False)
     assert only_w[1] is None and torch.equal(only_w[0], gw) and only_v[0] is None and torch.equal(only_v[1], gv)
-    wt, vt = dev(w32).requires_grad_(True), d["feat"].clone().requires_grad_(True)
-    (ag.PackedAccumulateFn.apply(wt, vt.detach(), d["seg"]) * dev(g)).sum().backward()
+    wt, vt = cuda(w32).requires_grad_(True), d["feat"].clone().requires_grad_(True)
+    (ag.PackedAccumulateFn.apply(wt, vt.detach(), d["seg"]) * cuda(g)).sum().backward()
     assert torch.equal(wt.grad, gw) and vt.grad is None
-    (ag.PackedAccumulateFn.apply(wt.detach(), vt, d["seg"]) * dev(g)).sum().backward()
+    (ag.PackedAccumulateFn.apply(wt.detach(), vt, d["seg"]) * cuda(g)).sum().backward()
     assert torch.equal(vt.grad, gv)
     # without values: the plain sum
     g1 = synth.normal((p["R"], 1), 43)
     w1 = PR.f64(w32, grad=True)
     (PR.accumulate(w1, None, p["seg"]) * PR.f64(g1)).sum().backward()
-    wt = dev(w32).requires_grad_(True)
-    (ag.PackedAccumulateFn.apply(wt, None, d["seg"]) * dev(g1)).sum().backward()
-    assert rel_l2(host(wt.grad), w1.grad.numpy()) < TIGHT
+    wt = cuda(w32).requires_grad_(True)
+    (ag.PackedAccumulateFn.apply(wt, None, d["seg"]) * cuda(g1)).sum().backward()
+    assert rel_l2(host64(wt.grad), w1.grad.numpy()) < TIGHT
 
 
 @pytest.mark.parametrize("density_mode", [True, False], ids=["density", "alpha"])
@@ -258,22 +241,22 @@ def test_composite_backward(ops, C, density_mode):
             of = ag.PackedAccumulateFn.apply(ow, f, d["seg"])
             od = ag.PackedAccumulateFn.apply(ow, ((d["ts"] + d["te"]) / 2)[:, None], d["seg"])
             oa = ag.PackedAccumulateFn.apply(ow, None, d["seg"])
-        ((of * dev(gF)).sum() + (od * dev(gD)).sum() + (oa * dev(gA)).sum() + (ow * dev(gW)).sum()).backward()
+        ((of * cuda(gF)).sum() + (od * cuda(gD)).sum() + (oa * cuda(gA)).sum() + (ow * cuda(gW)).sum()).backward()
         return x.grad, f.grad
 
     gx, gf = run(True)
     ux, uf = run(False)
-    e_x, e_f = rel_l2(host(gx), x64.grad.numpy()), rel_l2(host(gf), f64.grad.numpy())
-    e_ux, e_uf = rel_l2(host(gx), host(ux)), rel_l2(host(gf), host(uf))
+    e_x, e_f = rel_l2(host64(gx), x64.grad.numpy()), rel_l2(host64(gf), f64.grad.numpy())
+    e_ux, e_uf = rel_l2(host64(gx), host64(ux)), rel_l2(host64(gf), host64(uf))
     print(f"C={C} {key}: grad_x {e_x:.3g} grad_features {e_f:.3g}; fused vs unfused {e_ux:.3g} {e_uf:.3g}")
-    assert np.isfinite(host(gx)).all() and np.isfinite(host(gf)).all()
+    assert np.isfinite(host64(gx)).all() and np.isfinite(host64(gf)).all()
     assert e_x < TOL and e_f < TIGHT
     assert e_ux < TIGHT and e_uf < TIGHT
     # only the outputs that were used send a gradient; only the inputs that need one get it
     x = d[key].clone().requires_grad_(True)
     of = ag.PackedCompositeFn.apply(d["ts"], d["te"], x, d["feat"], d["seg"], density_mode)[0]
-    (of * dev(gF)).sum().backward()
-    want, none = ops.packed_composite_bwd(d["ts"], d["te"], d[key], d["feat"], d["seg"], density_mode, dev(gF),
+    (of * cuda(gF)).sum().backward()
+    want, none = ops.packed_composite_bwd(d["ts"], d["te"], d[key], d["feat"], d["seg"], density_mode, cuda(gF),
                                           need_grad_features=False)
     assert none is None and torch.equal(x.grad, want)
 
@@ -285,21 +268,21 @@ def test_uniform_segments_agree_with_the_dense_kernels(ops):
 
     R, S, C = 37, 70, 32
     e = np.cumsum(synth.uniform((R, S + 1), 0.01, 0.4, 60), -1).astype(np.float32)
-    ts, te = dev(e[:, :-1]), dev(e[:, 1:])
-    sig = dev(np.exp(synth.uniform((R, S), -5.0, 1.5, 61)))
-    al = dev(synth.uniform((R, S), 0.0, 1.0, 62) ** 3)
-    feat = dev(synth.normal((R, S, C), 63))
+    ts, te = cuda(e[:, :-1]), cuda(e[:, 1:])
+    sig = cuda(np.exp(synth.uniform((R, S), -5.0, 1.5, 61)))
+    al = cuda(synth.uniform((R, S), 0.0, 1.0, 62) ** 3)
+    feat = cuda(synth.normal((R, S, C), 63))
     before = nerfacc.render_weight_from_density(ts, te, sig), nerfacc.render_weight_from_alpha(al)
     seg = torch.arange(R + 1, device="cuda") * S
     pw, pt, pa = ops.packed_weight_from_density(ts, te, sig, seg)
     dw, dt, da = ops.render_weight_from_density(ts, te, sig)
     for got, want, what in ((pw, dw, "w"), (pt, dt, "T"), (pa, da, "alpha")):
-        assert rel_l2(host(got), host(want).reshape(-1)) < 2 * TIGHT, what
+        assert rel_l2(host64(got), host64(want).reshape(-1)) < 2 * TIGHT, what
     pw, pt = ops.packed_weight_from_alpha(al, seg)
     dw, dt = ops.render_weight_from_alpha(al)
-    assert rel_l2(host(pw), host(dw).reshape(-1)) < 2 * TIGHT and rel_l2(host(pt), host(dt).reshape(-1)) < 2 * TIGHT
-    assert rel_l2(host(ops.packed_accumulate(dw, feat.reshape(-1, C), seg)), host(ops.accumulate_along_rays(dw, feat))) < 2 * TIGHT
-    assert rel_l2(host(ops.packed_accumulate(dw, None, seg)), host(ops.accumulate_along_rays(dw))) < 2 * TIGHT
+    assert rel_l2(host64(pw), host64(dw).reshape(-1)) < 2 * TIGHT and rel_l2(host64(pt), host64(dt).reshape(-1)) < 2 * TIGHT
+    assert rel_l2(host64(ops.packed_accumulate(dw, feat.reshape(-1, C), seg)), host64(ops.accumulate_along_rays(dw, feat))) < 2 * TIGHT
+    assert rel_l2(host64(ops.packed_accumulate(dw, None, seg)), host64(ops.accumulate_along_rays(dw))) < 2 * TIGHT
     # the packed call through the shim is the same kernel
     ri = torch.arange(R, device="cuda").repeat_interleave(S)
     assert torch.equal(nerfacc.render_weight_from_alpha(al.reshape(-1), ray_indices=ri, n_rays=R)[0], pw)
@@ -315,104 +298,6 @@ def test_uniform_segments_agree_with_the_dense_kernels(ops):
 
 
 # ---- 5. saturation -------------------------------------------------------------------------------------------------------
-SAT_R = 13
-SAT_SAMPLES = [1, 16, 63, 64, 65, 130]
-
-
-def check(got, ref, bound, what):
-    """per element: finite wherever the reference is, and |got - ref| <= bound"""
-    got, ref, bound = (np.broadcast_to(np.asarray(v, np.float64), np.shape(got)) for v in (got, ref, bound))
-    fin = np.isfinite(ref)
-    bad = fin & ~np.isfinite(got)
-    assert not bad.any(), f"{what}: non-finite where the reference is finite at {np.argwhere(bad)[:5].tolist()}"
-    err = np.where(fin, np.abs(got - ref), 0.0)
-    over = err > bound
-    if over.any():
-        k = tuple(np.argwhere(over)[0])
-        raise AssertionError(f"{what}: {int(over.sum())} elements off, first {k}: got {got[k]!r} want {ref[k]!r} "
-                             f"bound {bound[k]!r} (max err/bound {float((err / np.maximum(bound, 1e-300)).max()):.3g})")
-
-
-def sharp_alphas(S, seed):
-    """the alpha family of test_gpu_saturation.py: exact 1, 1 - 2^-24 and exact 0 sprinkled in and in runs, a ray without
-    special values, a ray opaque from its first sample on"""
-    R = SAT_R
-    a = synth.uniform((R, S), 0.0, 1.0, seed)
-    pick = synth.uniform((R, S), 0.0, 1.0, seed + 1)
-    a = np.where(pick < 0.06, np.float32(1.0), a)
-    a = np.where((pick >= 0.06) & (pick < 0.14), ONE_BELOW, a)
-    a = np.where((pick >= 0.14) & (pick < 0.24), np.float32(0.0), a)
-    a = np.where((pick >= 0.24) & (pick < 0.5), a * np.float32(1e-3), a)
-    lo, hi = S // 3, S // 3 + max(1, S // 4)
-    a[1, lo:hi] = 1.0
-    a[2, lo:hi] = ONE_BELOW
-    a[3, lo:hi] = 0.0
-    a[4, lo:] = ONE_BELOW
-    a[5] = synth.uniform((S,), 0.0, 0.2, seed + 2)
-    a[6, 0] = 1.0
-    a[7, -1] = 1.0
-    a[8, : S // 2] = 0.0
-    a[8, S // 2] = 1.0
-    return np.ascontiguousarray(a, np.float32)
-
-
-def sharp_bins(S, seed):
-    """the bin family of test_gpu_saturation.py: sigma * delta from 1e-4 past 88, zero-length bins, a sky bin at 1e10"""
-    R = SAT_R
-    e = np.cumsum(synth.uniform((R, S + 1), 0.0, 2.0, seed), -1).astype(np.float32)
-    zero = synth.uniform((R, S), 0, 1, seed + 1) < 0.15
-    for s in range(S):
-        e[:, s + 1] = np.where(zero[:, s], e[:, s], np.maximum(e[:, s + 1], e[:, s]))
-    e[::3, -1] = 1e10
-    sig = np.exp(synth.uniform((R, S), -9.0, 5.0, seed + 2)).astype(np.float32)
-    big = synth.uniform((R, S), 0, 1, seed + 3) < 0.1
-    sig = np.where(big, np.float32(200.0), sig)
-    sig[1] = 1e-3
-    return np.ascontiguousarray(e[:, :-1]), np.ascontiguousarray(e[:, 1:]), np.ascontiguousarray(sig)
-
-
-def excl_trans(a):
-    return torch.cumprod(torch.cat([torch.ones_like(a[:, :1]), 1 - a[:, :-1]], -1), -1)
-
-
-def ref_alpha(a32, gw, gt):
-    """float64 cumprod autograd -> w, T, dL/dalpha, and the magnitude sum of dL/dalpha's terms (test_gpu_saturation.py)"""
-    a = PR.f64(a32, grad=True)
-    T = excl_trans(a)
-    w = a * T
-    (w * PR.f64(gw) + T * PR.f64(gt)).sum().backward()
-    b = PR.f64(a32, grad=True)
-    Tb = excl_trans(b)
-    (b * Tb * PR.f64(np.abs(gw)) + Tb * PR.f64(np.abs(gt))).sum().backward()
-    mag = 2 * np.abs(gw) * T.detach().numpy() - b.grad.numpy()
-    return w.detach().numpy(), T.detach().numpy(), a.grad.numpy(), mag
-
-
-def suffix_excl(v):
-    return np.concatenate([np.flip(np.cumsum(np.flip(v[:, 1:], -1), -1), -1), np.zeros_like(v[:, :1])], -1)
-
-
-def ref_density(delta32, sig32, gw):
-    """float64 density-mode weights, their gradient written out, and the per-element error scales of an fp32 evaluation
-    (test_gpu_saturation.py: ref_density)"""
-    S = sig32.shape[1]
-    dl = np.asarray(delta32, np.float64)
-    sd = np.asarray(sig32, np.float64) * dl
-    cinn = np.cumsum(sd, -1)
-    cexn = np.concatenate([np.zeros_like(sd[:, :1]), cinn[:, :-1]], -1)
-    Tn = np.exp(-cexn)
-    an = -np.expm1(-sd)
-    w = an * Tn
-    g = np.asarray(gw, np.float64)
-    grad = dl * (g * Tn * np.exp(-sd) - suffix_excl(g * w))
-    ag_ = np.abs(g)
-    e_head = ag_ * Tn * np.exp(-sd) * (1 + cinn)
-    e_term = ag_ * Tn * (an * (1 + cexn) + 1.0 / (S + 4))
-    gscale = 4 * (S + 4) * U * dl * (e_head + suffix_excl(e_term))
-    fscale = 4 * (S + 4) * U * Tn * (1 + cexn)
-    return w, Tn, an, grad, fscale, gscale
-
-
 def packed_blocks(blocks):
     """dense [R,S] blocks of different S -> one ragged batch with an empty ray between the blocks; -> seg, and a function
     that packs a list of per-block arrays (trailing dims kept) the same way"""
@@ -423,14 +308,14 @@ def packed_blocks(blocks):
 
 
 def test_alpha_mode_saturated(ops):
-    blocks = [sharp_alphas(S, 10 + S) for S in SAT_SAMPLES]
+    blocks = [sharp_alphas(S, 10 + S) for S in SAMPLES]
     seg, pack = packed_blocks(blocks)
     gws = [synth.normal(b.shape, 20 + b.shape[1]) for b in blocks]
     gts = [synth.normal(b.shape, 30 + b.shape[1]) for b in blocks]
     a = pack(blocks)
-    w, t = ops.packed_weight_from_alpha(dev(a), dev(seg))
-    ga = host(ops.packed_weight_from_alpha_bwd(dev(a), dev(seg), dev(pack(gws)), dev(pack(gts))))
-    ga0 = host(ops.packed_weight_from_alpha_bwd(dev(a), dev(seg), dev(pack(gws))))
+    w, t = ops.packed_weight_from_alpha(cuda(a), cuda(seg))
+    ga = host64(ops.packed_weight_from_alpha_bwd(cuda(a), cuda(seg), cuda(pack(gws)), cuda(pack(gts))))
+    ga0 = host64(ops.packed_weight_from_alpha_bwd(cuda(a), cuda(seg), cuda(pack(gws))))
     refs = [ref_alpha(b, gw, gt) for b, gw, gt in zip(blocks, gws, gts)]
     refs0 = [ref_alpha(b, gw, np.zeros_like(gt)) for b, gw, gt in zip(blocks, gws, gts)]
     rtol = pack([np.full(b.shape, 2 * (b.shape[1] + 2) * U) for b in blocks])
@@ -438,25 +323,25 @@ def test_alpha_mode_saturated(ops):
     gscale = pack([np.broadcast_to(np.abs(gw).max(-1, keepdims=True) + np.abs(gt).max(-1, keepdims=True), gw.shape)
                    for gw, gt in zip(gws, gts)])
     rw, rt, rga, mag = (pack([r[k] for r in refs]) for k in range(4))
-    check(host(w), rw, TINY + rtol * rw, "weights")
-    check(host(t), rt, TINY + rtol * rt, "trans")
-    assert (host(w)[a == 0] == 0).all()
+    check(host64(w), rw, TINY + rtol * rw, "weights")
+    check(host64(t), rt, TINY + rtol * rt, "trans")
+    assert (host64(w)[a == 0] == 0).all()
     check(ga, rga, 2.0 ** -100 * gscale + gtol * mag, "dL/dalpha")
     check(ga0, pack([r[2] for r in refs0]), 2.0 ** -100 * gscale + gtol * pack([r[3] for r in refs0]), "dL/dalpha (no grad_t)")
 
 
 def test_density_mode_saturated(ops):
-    bins = [sharp_bins(S, 40 + S) for S in SAT_SAMPLES]
+    bins = [sharp_bins(S, 40 + S) for S in SAMPLES]
     seg, pack = packed_blocks([b[2] for b in bins])
     gws = [synth.normal(b[2].shape, 50 + b[2].shape[1]) for b in bins]
     st, en, sig = (pack([b[k] for b in bins]) for k in range(3))
     refs = [ref_density(b[1] - b[0], b[2], gw) for b, gw in zip(bins, gws)]
     rw, rt, ra, rgs, fscale, gscale = (pack([r[k] for r in refs]) for k in range(6))
-    w, t, a = ops.packed_weight_from_density(dev(st), dev(en), dev(sig), dev(seg))
-    check(host(w), rw, TINY + fscale, "weights")
-    check(host(t), rt, TINY + fscale, "trans")
-    check(host(a), ra, TINY + 4 * U, "alphas")
-    gs = host(ops.packed_weight_from_density_bwd(dev(st), dev(en), dev(sig), dev(seg), dev(pack(gws))))
+    w, t, a = ops.packed_weight_from_density(cuda(st), cuda(en), cuda(sig), cuda(seg))
+    check(host64(w), rw, TINY + fscale, "weights")
+    check(host64(t), rt, TINY + fscale, "trans")
+    check(host64(a), ra, TINY + 4 * U, "alphas")
+    gs = host64(ops.packed_weight_from_density_bwd(cuda(st), cuda(en), cuda(sig), cuda(seg), cuda(pack(gws))))
     atol = pack([TINY * ((b[1] - b[0]).astype(np.float64) + 1) * np.abs(gw).max(-1, keepdims=True) for b, gw in zip(bins, gws)])
     check(gs, rgs, atol + gscale, "dL/dsigma")
 
@@ -468,8 +353,8 @@ def test_fused_composite_saturated(ops, C):
     test_sdf_render_saturated does (4 (S + C + 8) u of the magnitude sum under |G|'s own magnitude sum), density mode as
     test_prop_weights_saturated does (gscale(G) + gscale(|G| terms)), the latter widened by (C + 4) / (4 (S + 4)): G's own
     C + 3 roundings enter the gradient through the very terms gscale adds up, each weighted 4 (S + 4) u there."""
-    ablocks = [sharp_alphas(S, 110 + S) for S in SAT_SAMPLES]
-    bins = [sharp_bins(S, 140 + S) for S in SAT_SAMPLES]
+    ablocks = [sharp_alphas(S, 110 + S) for S in SAMPLES]
+    bins = [sharp_bins(S, 140 + S) for S in SAMPLES]
     for b in bins:  # (a sky edge of 1e10 would make the depth's midpoints the whole story)
         b[1][:, -1] = np.where(b[1][:, -1] > 1e9, np.maximum(np.float32(1e4), b[0][:, -1]), b[1][:, -1])
     seg, pack = packed_blocks(ablocks)
@@ -488,32 +373,32 @@ def test_fused_composite_saturated(ops, C):
     unpack = lambda v: np.split(v, np.cumsum([b.size for b in ablocks])[:-1])  # noqa: E731
     Gb = [g.reshape(b.shape) for g, b in zip(unpack(G), ablocks)]
     Gmb = [g.reshape(b.shape) for g, b in zip(unpack(Gm), ablocks)]
-    d = dict(ts=dev(st), te=dev(en), seg=dev(seg), feat=dev(feat))
+    d = dict(ts=cuda(st), te=cuda(en), seg=cuda(seg), feat=cuda(feat))
     for density_mode, x in ((False, al), (True, sig)):
-        of, od, oa, ow = ops.packed_composite_fwd(d["ts"], d["te"], dev(x), d["feat"], d["seg"], density_mode)
-        gx, gf = ops.packed_composite_bwd(d["ts"], d["te"], dev(x), d["feat"], d["seg"], density_mode, dev(gF), dev(gD),
-                                          dev(gA), dev(gW))
+        of, od, oa, ow = ops.packed_composite_fwd(d["ts"], d["te"], cuda(x), d["feat"], d["seg"], density_mode)
+        gx, gf = ops.packed_composite_bwd(d["ts"], d["te"], cuda(x), d["feat"], d["seg"], density_mode, cuda(gF), cuda(gD),
+                                          cuda(gA), cuda(gW))
         for v in (of, od, oa, ow, gx, gf):
             assert torch.isfinite(v).all()
-        w_unf = (ops.packed_weight_from_density(d["ts"], d["te"], dev(x), d["seg"]) if density_mode
-                 else ops.packed_weight_from_alpha(dev(x), d["seg"]))[0]
+        w_unf = (ops.packed_weight_from_density(d["ts"], d["te"], cuda(x), d["seg"]) if density_mode
+                 else ops.packed_weight_from_alpha(cuda(x), d["seg"]))[0]
         assert torch.equal(ow, w_unf)  # (held per element by the two tests above)
-        w64 = host(ow)
+        w64 = host64(ow)
         rgf = w64[:, None] * gF[rows].astype(np.float64)
-        check(host(gf), rgf, TINY + 2 * U * np.abs(rgf), "d features")
+        check(host64(gf), rgf, TINY + 2 * U * np.abs(rgf), "d features")
         if density_mode:
             refs = [ref_density(b[1] - b[0], b[2], g) for b, g in zip(bins, Gb)]
             refs_m = [ref_density(b[1] - b[0], b[2], g) for b, g in zip(bins, Gmb)]
             widen = pack([np.full(b.shape, 1 + (C + 4) / (4 * (b.shape[1] + 4))) for b in ablocks])
             atol = pack([TINY * ((b[1] - b[0]).astype(np.float64) + 1) * g.max(-1, keepdims=True) for b, g in zip(bins, Gmb)])
-            check(host(gx), pack([r[3] for r in refs]), atol + pack([r[5] for r in refs]) + widen * pack([r[5] for r in refs_m]),
+            check(host64(gx), pack([r[3] for r in refs]), atol + pack([r[5] for r in refs]) + widen * pack([r[5] for r in refs_m]),
                   "dL/dsigma")
         else:
             refs = [ref_alpha(b, g, np.zeros_like(g)) for b, g in zip(ablocks, Gb)]
             refs_m = [ref_alpha(b, g, np.zeros_like(g)) for b, g in zip(ablocks, Gmb)]
             gtol = pack([np.full(b.shape, 4 * (b.shape[1] + C + 8) * U) for b in ablocks])
             gscale = pack([np.broadcast_to(g.max(-1, keepdims=True), g.shape) for g in Gmb])
-            check(host(gx), pack([r[2] for r in refs]), 2.0 ** -100 * gscale + gtol * pack([r[3] for r in refs_m]), "dL/dalpha")
+            check(host64(gx), pack([r[2] for r in refs]), 2.0 ** -100 * gscale + gtol * pack([r[3] for r in refs_m]), "dL/dalpha")
 
 
 # ---- 6. reproducibility --------------------------------------------------------------------------------------------------
@@ -521,7 +406,7 @@ def test_fused_composite_saturated(ops, C):
 def test_fused_forward_and_backward_are_bitwise_reproducible(ops, C):
     p = ragged_inputs(70 + C, C)
     d = on_device(p)
-    gF, gD, gA = dev(synth.normal((p["R"], C), 71)), dev(synth.normal((p["R"], 1), 72)), dev(synth.normal((p["R"], 1), 73))
+    gF, gD, gA = cuda(synth.normal((p["R"], C), 71)), cuda(synth.normal((p["R"], 1), 72)), cuda(synth.normal((p["R"], 1), 73))
     for mode, key in ((True, "sig"), (False, "alpha")):
         runs = []
         for _ in range(2):
@@ -541,47 +426,18 @@ def test_packed_segments_and_pack_info(ops):
     for counts in cases:
         R = len(counts)
         seg = PR.segments_from_counts(counts)
-        ri = dev(PR.ray_indices_from_segments(seg))
+        ri = cuda(PR.ray_indices_from_segments(seg))
         got = ops.packed_segments(ri, R)
         want = torch.searchsorted(ri, torch.arange(R + 1, device="cuda"))
-        assert got.dtype == torch.int64 and torch.equal(got, want) and torch.equal(got, dev(seg))
+        assert got.dtype == torch.int64 and torch.equal(got, want) and torch.equal(got, cuda(seg))
         info = nerfacc.pack_info(ri, R)
-        assert info.shape == (R, 2) and torch.equal(info[:, 1], dev(np.asarray(counts, np.int64)))
-        assert torch.equal(info[:, 0], dev(seg[:-1]))
+        assert info.shape == (R, 2) and torch.equal(info[:, 1], cuda(np.asarray(counts, np.int64)))
+        assert torch.equal(info[:, 0], cuda(seg[:-1]))
         if ri.numel():
             assert torch.equal(torch.repeat_interleave(torch.arange(R, device="cuda"), info[:, 1]), ri)
 
 
 # ---- 8. module level -------------------------------------------------------------------------------------------------------
-def make_field(use_sdf, lg=11):
-    from neurad_studio_amd.fields.neurad_field import NeuRADField, NeuRADFieldConfig
-
-    cfg = NeuRADFieldConfig(use_sdf=use_sdf)
-    cfg.grid.static.log2_hashmap_size = lg
-    f = NeuRADField(cfg, actors=None, static_scale=100.0).cuda()
-    with torch.no_grad():
-        f.hashgrid.static_grid.hash_table.copy_(dev(synth.hash_table(8 * 2**lg, 4, seed=51, scale=0.5)))
-        for k, l in enumerate(f.mlp_geo.layers):
-            w, b = synth.linear(l.out_features, l.in_features, 200 + 10 * k)
-            l.weight.copy_(dev(w)), l.bias.copy_(dev(b))
-        for k, l in enumerate(f.mlp_feature.layers):
-            w, b = synth.linear(l.out_features, l.in_features, 300 + 10 * k)
-            l.weight.copy_(dev(w)), l.bias.copy_(dev(b))
-    return f
-
-
-def ray_bundle(R, seed, far):
-    from neurad_studio_amd.cameras.rays import RayBundle
-
-    o = synth.uniform((R, 3), -4.0, 4.0, seed)
-    d = synth.normal((R, 3), seed + 1)
-    d = (d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32)
-    for r in (0, R // 2, R // 2 + 1, R - 1):  # rays that start outside the grid and point away from it: no samples
-        o[r], d[r] = (8.0, 8.0, 8.0), (1.0, 0.0, 0.0)
-    return RayBundle(origins=dev(o), directions=dev(d), pixel_area=torch.full((R, 1), 1e-6, device="cuda"),
-                     nears=torch.zeros(R, 1, device="cuda"), fars=torch.full((R, 1), float(far), device="cuda"))
-
-
 @pytest.mark.parametrize("use_sdf", [True, False], ids=["sdf", "density"])
 def test_volumetric_sampler_field_packed_renderers(ops, use_sdf):
     from neurad_studio_amd.field_components.field_heads import FieldHeadNames
@@ -593,7 +449,7 @@ def test_volumetric_sampler_field_packed_renderers(ops, use_sdf):
 
     R = 96
     est = OccGridEstimator([-5, -5, -5, 5, 5, 5], resolution=16)
-    est.binaries[0] = dev(np.random.default_rng(3).random((16, 16, 16)) < 0.3)
+    est.binaries[0] = cuda(np.random.default_rng(3).random((16, 16, 16)) < 0.3)
     rb = ray_bundle(R, 90, far=9.0)
     rs, ri = VolumetricSampler(est).eval()(rb, render_step_size=0.2, cone_angle=0.05)
     M = ri.shape[0]
@@ -622,21 +478,21 @@ def test_volumetric_sampler_field_packed_renderers(ops, use_sdf):
     want_a = PR.accumulate(w64, None, seg).numpy()
     want_d = PR.accumulate(w64, PR.f64(mid), seg).numpy()
     want_n = PR.accumulate(w64, PR.f64(normals), seg).numpy()
-    assert rel_l2(host(weights[:, 0]), w64.numpy()) < TIGHT
-    assert rel_l2(host(FeatureRenderer()(feat, weights, ray_indices=ri, num_rays=R)), want_f) < TIGHT
-    assert rel_l2(host(AccumulationRenderer()(weights, ray_indices=ri, num_rays=R)), want_a) < TIGHT
-    assert rel_l2(host(render_depth_simple(weights, rs, ray_indices=ri, num_rays=R)), want_d) < TIGHT
-    assert rel_l2(host(NormalsRenderer()(normals, weights, normalize=False, ray_indices=ri, num_rays=R)), want_n) < TIGHT
+    assert rel_l2(host64(weights[:, 0]), w64.numpy()) < TIGHT
+    assert rel_l2(host64(FeatureRenderer()(feat, weights, ray_indices=ri, num_rays=R)), want_f) < TIGHT
+    assert rel_l2(host64(AccumulationRenderer()(weights, ray_indices=ri, num_rays=R)), want_a) < TIGHT
+    assert rel_l2(host64(render_depth_simple(weights, rs, ray_indices=ri, num_rays=R)), want_d) < TIGHT
+    assert rel_l2(host64(NormalsRenderer()(normals, weights, normalize=False, ray_indices=ri, num_rays=R)), want_n) < TIGHT
     n_norm = want_n / (np.linalg.norm(want_n, axis=-1, keepdims=True) + 1e-10)
-    assert rel_l2(host(NormalsRenderer()(normals, weights, ray_indices=ri, num_rays=R)), n_norm) < TIGHT
+    assert rel_l2(host64(NormalsRenderer()(normals, weights, ray_indices=ri, num_rays=R)), n_norm) < TIGHT
     want_depth = np.clip(want_d / (want_a + 1e-10), float(mid.min()), float(mid.max()))
     got_depth = DepthRenderer()(weights, rs, ray_indices=ri, num_rays=R)
-    assert got_depth.shape == (R, 1) and rel_l2(host(got_depth), want_depth) < TIGHT
+    assert got_depth.shape == (R, 1) and rel_l2(host64(got_depth), want_depth) < TIGHT
     kw = {"alpha": head} if use_sdf else {"density": head}
     fused = render_packed(feat, rs, ri, R, **kw)
     assert fused["weights"].shape == (M, 1)
     for key, want in (("features", want_f), ("depth", want_d), ("accumulation", want_a), ("weights", w64.numpy()[:, None])):
-        assert rel_l2(host(fused[key]), want) < TIGHT, key
+        assert rel_l2(host64(fused[key]), want) < TIGHT, key
     # training: the loss reaches the hash table and the MLPs through the fused node
     fld.train()
     out = fld(rs)
@@ -666,7 +522,7 @@ def test_packed_path_agrees_with_the_dense_operator_path(ops, use_sdf):
 
     d = synth.normal((R, 3), 6)
     rb = RayBundle(origins=torch.zeros(R, 3, device="cuda"),
-                   directions=dev((d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32)),
+                   directions=cuda((d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32)),
                    pixel_area=torch.full((R, 1), 1e-6, device="cuda"), nears=torch.zeros(R, 1, device="cuda"),
                    fars=torch.full((R, 1), 3.0, device="cuda"))
     rs, ri = VolumetricSampler(est).eval()(rb, render_step_size=0.25)
@@ -688,7 +544,7 @@ def test_packed_path_agrees_with_the_dense_operator_path(ops, use_sdf):
     fused = render_packed(out_p[FieldHeadNames.FEATURE], rs, ri, R, **({"alpha": out_p[key]} if use_sdf else {"density": out_p[key]}))
     for name, got, want in (("features", fused["features"], feats), ("accumulation", fused["accumulation"], acc),
                             ("depth", fused["depth"], depth)):
-        err = rel_l2(host(got), host(want))
+        err = rel_l2(host64(got), host64(want))
         print(f"{name}: packed vs dense {err:.3g}")
         assert err < TOL, name
 
@@ -698,7 +554,7 @@ def test_fused_forward_and_backward_replay_in_a_graph(ops):
     C = 32
     p = ragged_inputs(95, C)
     d = on_device(p)
-    gF, gD, gA = dev(synth.normal((p["R"], C), 96)), dev(synth.normal((p["R"], 1), 97)), dev(synth.normal((p["R"], 1), 98))
+    gF, gD, gA = cuda(synth.normal((p["R"], C), 96)), cuda(synth.normal((p["R"], 1), 97)), cuda(synth.normal((p["R"], 1), 98))
 
     def step():
         fwd = ops.packed_composite_fwd(d["ts"], d["te"], d["sig"], d["feat"], d["seg"], True)

@@ -8,32 +8,11 @@ import torch
 import neurad_oracle as O
 import synth
 from conftest import load_golden, rel_l2
+from builders import HASH_CFGS, RENDER_CFGS, field_params, mlp_params, prop_params, sample_rays
+from gpu_util import TIGHT, TOL, dev, host, make_actor_field, to_pspec, to_spec
+from gpu_util import ops  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-4  # north_star tolerance (rel-L2 vs the reference's fp32 torch path)
-TIGHT = 2e-5
-
-
-@pytest.fixture(scope="module")
-def ops():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from neurad_studio_amd import ops as _ops
-
-    return _ops
-
-
-def dev(a, dtype=torch.float32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-HASH_CFGS = {"c2small": (16, 16, 1024, 12, 2), "neurad": (8, 32, 8192, 12, 4), "prop": (6, 128, 4096, 11, 1),
-             "tiny": (1, 32, 32, 10, 4), "actor": (4, 64, 1024, 10, 4)}
-
 
 @pytest.mark.parametrize("tag", list(HASH_CFGS))
 def test_hashgrid_fwd_vs_reference_golden(ops, tag):
@@ -90,20 +69,10 @@ def test_sh4(ops):
     assert rel_l2(host(ops.sh4_fwd(dev(g["d01"]))), g["y"]) < 1e-6
 
 
-def _mlp_params(cfg):
-    i, n, w, o = (int(v) for v in cfg)
-    dims = [i] + [w] * (n - 1) + [o]
-    ws, bs = [], []
-    for k in range(n):
-        wk, bk = synth.linear(dims[k + 1], dims[k], 100 + 10 * k)
-        ws.append(wk), bs.append(bk)
-    return ws, bs
-
-
 @pytest.mark.parametrize("tag", ["geo64", "feat64", "geo32", "lidar"])
 def test_mlp_fwd_bwd_vs_reference_golden(ops, tag):
     g = load_golden(f"mlp_{tag}")
-    ws, bs = _mlp_params(g["cfg"])
+    ws, bs = mlp_params(g["cfg"])
     dws, dbs = [dev(w) for w in ws], [dev(b) for b in bs]
     x = dev(g["x"])
     y, hidden = ops.mlp_fwd(x, dws, dbs, save_hidden=True)
@@ -132,27 +101,6 @@ def test_mlp_odd_shapes_and_ragged_batches(ops, dims):
                        [None if b is None else dev(b) for b in bs]).shape == (0, o)
 
 
-def field_params(use_sdf=True, L=8, F=4, lg=11, H=32, mn=32, mx=8192, scale=0.5):
-    grid = O.GridParams(synth.hash_table(L * 2**lg, F, seed=51, scale=scale), L, mn, mx, lg)
-    gw, gb, fw, fb = [], [], [], []
-    for k, (o, i) in enumerate([(H, 32), (33, H)]):
-        w, b = synth.linear(o, i, 200 + 10 * k)
-        gw.append(w), gb.append(b)
-    for k, (o, i) in enumerate([(H, 48), (H, H), (32, H)]):
-        w, b = synth.linear(o, i, 300 + 10 * k)
-        fw.append(w), fb.append(b)
-    return O.FieldParams(grid, 100.0, gw, gb, fw, fb, use_sdf=use_sdf)
-
-
-def to_spec(ops, p: O.FieldParams, half=False):
-    g = p.grid
-    spec = ops.GridSpec(g.num_levels, g.n_feat, g.log2_hashmap_size, g.min_res, g.max_res)
-    table = dev(g.table, torch.float16 if half else torch.float32)
-    return ops.FieldSpec(spec, table, p.static_scale, [dev(w) for w in p.geo_w], [dev(b) for b in p.geo_b],
-                         [dev(w) for w in p.feat_w], [dev(b) for b in p.feat_b], use_sdf=p.use_sdf,
-                         beta=abs(p.beta) + p.beta_min)
-
-
 @pytest.mark.parametrize("tag", ["sdf", "density"])
 def test_field_fwd_vs_reference_golden(ops, tag):
     g = load_golden(f"field_{tag}")
@@ -172,22 +120,6 @@ def test_field_fwd_vs_reference_golden(ops, tag):
     assert rel_l2(enc, ref) < TIGHT
 
 
-def _sample_rays(R, S, seed, fars=200.0):
-    o, d, area, _ = synth.rays(R, seed)
-    bins, eu, _ = O.power_sampler(np.zeros(R), np.full(R, fars, np.float32), S)
-    return o, d, area, np.ascontiguousarray(eu[:, :-1]), np.ascontiguousarray(eu[:, 1:]), eu
-
-
-RENDER_CFGS = [  # (L, F, lg, min_res, max_res, H, use_sdf, R, S)
-    (16, 2, 12, 16, 1024, 64, True, 37, 128),   # BASELINE config 2 shape (small table)
-    (8, 4, 11, 32, 8192, 32, True, 50, 32),     # NeuRAD defaults
-    (8, 4, 11, 32, 8192, 32, False, 21, 33),    # density head, ragged S (not a multiple of 16)
-    (16, 2, 12, 16, 1024, 32, True, 5, 7),      # S < 16
-    (8, 4, 11, 32, 8192, 64, False, 9, 1),      # single sample per ray
-    (4, 8, 10, 64, 1024, 64, True, 13, 48),
-]
-
-
 @pytest.mark.parametrize("cfg", RENDER_CFGS)
 def test_render_fused_vs_oracle(ops, cfg):
     L, F, lg, mn, mx, H, use_sdf, R, S = cfg
@@ -195,7 +127,7 @@ def test_render_fused_vs_oracle(ops, cfg):
     if use_sdf:
         p.beta = 3.0  # keep alphas away from saturation so the compositing is exercised
     fs = to_spec(ops, p)
-    o, d, area, s, e, eu = _sample_rays(R, S, seed=R + S)
+    o, d, area, s, e, eu = sample_rays(R, S, seed=R + S)
     ref = O.render_rays(p, o, d, area, s, e)
     edges = dev(eu)
     # bin EDGES passed as strided views: starts = edges[:, :-1], ends = edges[:, 1:]  (no copies)
@@ -221,7 +153,7 @@ def test_render_fp16_table(ops):
     p.beta = 3.0
     p.grid.table = p.grid.table.astype(np.float16).astype(np.float32)  # oracle sees the rounded values
     fs = to_spec(ops, p, half=True)
-    o, d, area, s, e, _ = _sample_rays(33, 32, seed=5)
+    o, d, area, s, e, _ = sample_rays(33, 32, seed=5)
     ref = O.render_rays(p, o, d, area, s, e)
     feats, depth, acc = ops.render_fwd(fs, dev(o), dev(d), dev(area), dev(s), dev(e))
     assert rel_l2(host(feats), ref["features"]) < TOL and rel_l2(host(acc), ref["accumulation"]) < TOL
@@ -278,18 +210,6 @@ def test_compositing_ops_fwd_bwd(ops):
     assert rel_l2(host(gs2), tsig.grad.numpy()) < TOL
 
 
-def prop_params(seed, lg=11):
-    w, _ = synth.linear(1, 6, seed + 1, bias=False)
-    return O.ProposalParams(O.GridParams(synth.hash_table(6 * 2**lg, 1, seed=seed, scale=2.0), 6, 128, 4096, lg),
-                            100.0, w + np.float32(0.3))
-
-
-def to_pspec(ops, p):
-    g = p.grid
-    return ops.ProposalSpec(ops.GridSpec(g.num_levels, 1, g.log2_hashmap_size, g.min_res, g.max_res), dev(g.table),
-                            p.static_scale, dev(p.decoder_w))
-
-
 def test_sampler_pieces_vs_reference_golden(ops):
     g = load_golden("sampler_parts")
     R = g["o"].shape[0]
@@ -333,7 +253,7 @@ def test_proposal_density_bwd(ops, atomic, monkeypatch):
     p = prop_params(95)
     ps = to_pspec(ops, p)
     R, S = 11, 40
-    o, d, area, s, e, _ = _sample_rays(R, S, seed=3)
+    o, d, area, s, e, _ = sample_rays(R, S, seed=3)
     dens = ops.proposal_density_fwd(ps, dev(o), dev(d), dev(area), dev(s), dev(e))
     gd = synth.normal((R, S), 12)
     gt, gdec = ops.proposal_density_bwd(ps, dev(o), dev(d), dev(area), dev(s), dev(e), dens, dev(gd))
@@ -375,7 +295,7 @@ def test_full_size_properties_config2(ops):
     p = field_params(use_sdf=True, L=L, F=F, lg=lg, H=H, mn=16, mx=1024, scale=1.0)
     p.beta = 2.0
     fs = to_spec(ops, p)
-    o, d, area, s, e, eu = _sample_rays(R, S, seed=77)
+    o, d, area, s, e, eu = sample_rays(R, S, seed=77)
     do, dd, da, edges = dev(o), dev(d), dev(area), dev(eu)
     feats, depth, acc, w = ops.render_fwd(fs, do, dd, da, edges[:, :-1], edges[:, 1:], return_weights=True)
     f2, sdf2, alpha2 = ops.field_fwd(fs, do, dd, da, edges[:, :-1], edges[:, 1:])
@@ -407,7 +327,7 @@ def test_encode_bwd_binned_equals_atomic_scatter(ops, cfg, monkeypatch, switches
         switches.set("NRHIP_BIN_ROUND_LOG2", str(cfg[5]))
     L, F, lg, R, S = cfg[:5]
     spec = ops.GridSpec(L, F, lg, 16, 2048)
-    o, d, area, s, e, eu = _sample_rays(R, S, seed=5)
+    o, d, area, s, e, eu = sample_rays(R, S, seed=5)
     do, dd, da, edges = dev(o), dev(d), dev(area), dev(eu)
     go = dev(synth.normal((R * S, L * F), 11))
     st, en = edges[:, :-1], edges[:, 1:]
@@ -518,7 +438,7 @@ def test_table_gradient_skips_exactly_zero_samples_exactly(ops, cfg, monkeypatch
     silent samples sit between two samples of the same cell (they split a merged run, nothing else)."""
     L, F, lg, R, S = cfg
     spec = ops.GridSpec(L, F, lg, 16, 2048)
-    o, d, area, s, e, eu = _sample_rays(R, S, seed=7)
+    o, d, area, s, e, eu = sample_rays(R, S, seed=7)
     do, dd, da, edges = dev(o), dev(d), dev(area), dev(eu)
     st, en = edges[:, :-1], edges[:, 1:]
     g = synth.normal((R, S, L * F), 13)
@@ -626,7 +546,7 @@ def test_encode_bwd_binned_degenerate_distribution(ops, monkeypatch):
     almost all records.  The radix partition sizes its queues exactly, so this is slow-ish but exact."""
     L, F, lg, R, S = 8, 4, 18, 2048, 64
     spec = ops.GridSpec(L, F, lg, 32, 4096)
-    o, d, area, s, e, eu = _sample_rays(1, S, seed=9)
+    o, d, area, s, e, eu = sample_rays(1, S, seed=9)
     do, dd, da = dev(np.repeat(o, R, 0)), dev(np.repeat(d, R, 0)), dev(np.repeat(area, R, 0))
     edges = dev(np.repeat(eu, R, 0)).clone()
     edges[: R // 2] = torch.linspace(5.0, 5.0001, S + 1, device="cuda")  # half of the rays: all samples in one cell
@@ -749,7 +669,7 @@ def test_encode_bwd_binned_writes_the_fp16_gradient_of_an_fp16_storage_table(ops
     of the fp32 result -- identical integer accumulation, one rounding at the store"""
     L, F, lg, R, S = 8, 4, 15, 1100, 32
     spec = ops.GridSpec(L, F, lg, 16, 2048)
-    o, d, area, s, e, eu = _sample_rays(R, S, seed=9)
+    o, d, area, s, e, eu = sample_rays(R, S, seed=9)
     do, dd, da, edges = dev(o), dev(d), dev(area), dev(eu)
     go = dev(synth.normal((R * S, L * F), 19))
     go[::5] = 0  # silent samples; some slices stay empty at this size
@@ -775,7 +695,7 @@ def test_binned_table_gradient_is_fp32_whatever_the_tables_storage_type(ops, mon
 
     L, F, lg, R, S = 8, 4, 14, 300, 32
     spec = ops.GridSpec(L, F, lg, 16, 2048)
-    o, d, area, s, e, eu = _sample_rays(R, S, seed=4)
+    o, d, area, s, e, eu = sample_rays(R, S, seed=4)
     do, dd, da, edges = dev(o), dev(d), dev(area), dev(eu)
     go = dev(synth.normal((R * S, L * F), 23))
     st, en = edges[:, :-1], edges[:, 1:]
@@ -849,7 +769,7 @@ def test_forward_lookups_at_every_feature_width_and_storage_type(ops, F, half):
         ref[ids == a] = O.hashgrid_fwd(x[ids == a], tabs[a], scal, 2**lg)
     assert rel_l2(ym, ref) < TOL
     # nrhip_encode_fwd: one sample on each of 257 rays
-    o, d, area, st, en, _ = _sample_rays(n, 1, seed=60 + F)
+    o, d, area, st, en, _ = sample_rays(n, 1, seed=60 + F)
     enc = host(ops.encode_fwd(spec, dev(tabs[0], tdt), 100.0, dev(o), dev(d), dev(area), dev(st), dev(en)))
     assert rel_l2(enc, O.encode_static(O.GridParams(tabs[0], L, 16, 64, lg), 100.0, o, d, area, st, en)) < TIGHT
 
@@ -937,7 +857,7 @@ def test_inline_copies_embedding_lerp(ops):
 
 def test_inline_copies_render_weight_from_density(ops):
     R, S = 257, 33
-    _, _, _, st, en, _ = _sample_rays(R, S, seed=31)
+    _, _, _, st, en, _ = sample_rays(R, S, seed=31)
     starts, ends = dev(st.T).t(), dev(en.T).t()                       # [R,S] views of [S,R] storage
     sigmas = dev(synth.uniform((S, R), 0.0, 3.0, seed=32)).t()
     _same_on_strided_and_contiguous_inputs(ops.render_weight_from_density, (starts, ends, sigmas))
@@ -952,11 +872,9 @@ def test_inline_copies_power_sampler(ops):
 
 
 def test_inline_copies_actor_pair_positions(ops):
-    from test_gpu_actors import make_field
-
     R, S, P = 257, 8, 1025
-    spec = make_field().hashgrid.actor_spec()
-    o, d, area, st, en, _ = _sample_rays(R, S, seed=35, fars=60.0)
+    spec = make_actor_field().hashgrid.actor_spec()
+    o, d, area, st, en, _ = sample_rays(R, S, seed=35, fars=60.0)
     rays = tuple(dev(v) for v in (o, d, area, st, en))
     torch.manual_seed(12)
     times = (1.0 + torch.rand(R, 2, device="cuda"))[:, 0]  # within every actor's trajectory

@@ -7,16 +7,9 @@ import torch
 
 import neurad_oracle as O
 from conftest import load_golden
+from gpu_util import cuda, host
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 @pytest.mark.parametrize("tag", ["neurad", "odd", "even", "single"])
@@ -25,8 +18,8 @@ def test_patch_sample_vs_reference(tag):
 
     g = load_golden("patch_sampler")
     n, h, w, ps, sc = (int(v) for v in g[f"{tag}_shape"])
-    rays, coords, patches = patch_sample(dev(g[f"{tag}_image"]), ps, sc, uniforms=dev(g[f"{tag}_uniforms"]),
-                                         image_idx=dev(g[f"{tag}_image_idx"]))
+    rays, coords, patches = patch_sample(cuda(g[f"{tag}_image"]), ps, sc, uniforms=cuda(g[f"{tag}_uniforms"]),
+                                         image_idx=cuda(g[f"{tag}_image_idx"]))
     np.testing.assert_array_equal(host(rays), g[f"{tag}_indices"])
     np.testing.assert_array_equal(host(patches), g[f"{tag}_patches"])
     np.testing.assert_array_equal(host(coords), g[f"{tag}_coords"])
@@ -37,7 +30,7 @@ def test_patch_sample_given_centers_vs_reference():
 
     g = load_golden("patch_sampler")
     n, h, w, ps, sc = (int(v) for v in g["centers_shape"])
-    rays, coords, patches = patch_sample(dev(g["centers_image"]), ps, sc, centers=dev(g["centers_centers"]), want_coords=False)
+    rays, coords, patches = patch_sample(cuda(g["centers_image"]), ps, sc, centers=cuda(g["centers_centers"]), want_coords=False)
     assert coords is None
     np.testing.assert_array_equal(host(rays), g["centers_indices"])
     np.testing.assert_array_equal(host(patches), g["centers_patches"])
@@ -120,9 +113,9 @@ def test_lidar_point_sample_vs_reference(tag, rays):
     from neurad_studio_amd.data.pixel_samplers import lidar_point_sample
 
     g = load_golden("patch_sampler")
-    idx, pts = lidar_point_sample(dev(g[f"{tag}_cloud"]), dev(g[f"{tag}_points_per_lidar"]), rays,
-                                  shuffle=dev(g[f"{tag}_shuffle"]), draws=dev(g[f"{tag}_draws"]),
-                                  lidar_idx=dev(g[f"{tag}_lidar_idx"]))
+    idx, pts = lidar_point_sample(cuda(g[f"{tag}_cloud"]), cuda(g[f"{tag}_points_per_lidar"]), rays,
+                                  shuffle=cuda(g[f"{tag}_shuffle"]), draws=cuda(g[f"{tag}_draws"]),
+                                  lidar_idx=cuda(g[f"{tag}_lidar_idx"]))
     np.testing.assert_array_equal(host(idx), g[f"{tag}_indices"])
     np.testing.assert_array_equal(host(pts), g[f"{tag}_points"])
 

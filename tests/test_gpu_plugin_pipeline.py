@@ -13,9 +13,6 @@ import sys
 import types
 from collections import defaultdict
 from copy import deepcopy
-from dataclasses import dataclass, field
-from pathlib import Path
-from typing import Type
 
 import numpy as np
 import pytest
@@ -25,109 +22,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ref_import  # noqa: E402
-import synth  # noqa: E402
-import test_gpu_reference_plugin as t  # noqa: E402
-from test_gpu_reference_plugin import ref  # noqa: E402,F401
+import plugin_harness as t  # noqa: E402
+from plugin_harness import ref  # noqa: E402,F401
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not ref_import.reference_available(), reason="no reference (oracle/_ref ships with the lease)")]
-
-H, W, N_CAM, N_LIDAR, PTS = 48, 72, 3, 2, 700
-
-
-def _poses(n, seed):
-    out = []
-    for i in range(n):
-        yaw = 0.2 * i + 0.05 * float(synth.normal((1,), seed + i)[0])
-        c, s = np.cos(yaw), np.sin(yaw)
-        # camera looking along +x of the world: columns = (right, up, back)
-        rot = np.array([[s, 0.0, -c], [-c, 0.0, -s], [0.0, 1.0, 0.0]], np.float32)
-        out.append(np.concatenate([rot, np.array([[2.0 * i], [0.3 * i], [1.6]], np.float32)], 1))
-    return np.stack(out).astype(np.float32)
-
-
-def make_parser_classes(root: Path):
-    from nerfstudio.cameras.cameras import Cameras, CameraType
-    from nerfstudio.cameras.lidars import Lidars, LidarType
-    from nerfstudio.data.dataparsers.base_dataparser import DataParser, DataParserConfig, DataparserOutputs
-    from nerfstudio.data.scene_box import SceneBox
-    from PIL import Image
-
-    files = []
-    for i in range(N_CAM):
-        img = (synth.uniform((H, W, 3), 0, 1, 300 + i) * 255).astype(np.uint8)
-        f = root / f"cam{i}.png"
-        Image.fromarray(img).save(f)
-        files.append(f)
-
-    @dataclass
-    class SynthParserConfig(DataParserConfig):
-        _target: Type = field(default_factory=lambda: SynthParser)
-        data: Path = root
-        add_missing_points: bool = True  # (read by ADPipeline.__init__, pipelines/ad_pipeline.py:71-73)
-
-    class SynthParser(DataParser):
-        includes_time = True
-
-        def _generate_dataparser_outputs(self, split="train", **kwargs):
-            T = t.T
-            md = {"rolling_shutter_time": T(synth.uniform((N_CAM, 1), 0.01, 0.03, 6)),
-                  "time_to_center_pixel": T(synth.uniform((N_CAM, 1), -0.01, 0.01, 7)),
-                  "velocities": T(synth.normal((N_CAM, 3), 8) * 3), "sensor_idxs": torch.arange(N_CAM)[:, None] % 2}
-            cams = Cameras(camera_to_worlds=T(_poses(N_CAM, 10)), fx=T(synth.uniform((N_CAM, 1), 60, 70, 1)),
-                           fy=T(synth.uniform((N_CAM, 1), 60, 70, 2)), cx=float(W / 2), cy=float(H / 2), width=W, height=H,
-                           camera_type=CameraType.PERSPECTIVE, times=T(synth.uniform((N_CAM, 1), 0.3, 3.5, 5)), metadata=md)
-            l2w = _poses(N_LIDAR, 40)
-            lid = Lidars(lidar_to_worlds=T(l2w), lidar_type=LidarType.VELODYNE64E, assume_ego_compensated=True,
-                         times=T(synth.uniform((N_LIDAR, 1), 0.3, 3.5, 41)),
-                         metadata={"velocities": T(synth.normal((N_LIDAR, 3), 42) * 3),
-                                   "sensor_idxs": torch.full((N_LIDAR, 1), 2)}, valid_lidar_distance_threshold=1000.0)
-            clouds = []
-            for i in range(N_LIDAR):
-                p = np.concatenate([synth.normal((PTS, 3), 44 + i) * np.array([15.0, 15.0, 1.0], np.float32),
-                                    synth.uniform((PTS, 1), 0, 1, 46 + i), synth.uniform((PTS, 1), -0.05, 0.05, 48 + i)], -1)
-                p[:40, :3] *= 200.0  # beams without a return
-                clouds.append(T(p))
-            return DataparserOutputs(
-                image_filenames=list(files), cameras=cams,
-                scene_box=SceneBox(aabb=torch.tensor([[-100.0] * 3, [100.0] * 3])),
-                metadata={"lidars": lid, "point_clouds": clouds, "trajectories": t._trajectories(), "duration": 5.0,
-                          "sensor_idx_to_name": {0: "cam0", 1: "cam1", 2: "lidar"}})
-
-    return SynthParserConfig
-
-
-def _method_config(tmp_path):
-    """the ``neurad-hip`` method's trainer config, pointed at the synthetic drive and shrunk to test size"""
-    methods = dict(__import__("nerfstudio.configs.method_configs", fromlist=["all_methods"]).all_methods)
-    if "neurad-hip" not in methods:
-        from nerfstudio.plugins.registry import discover_methods
-
-        methods.update(discover_methods()[0])
-    cfg = deepcopy(methods["neurad-hip"])
-    pc = cfg.pipeline
-    pc.ray_patch_size = (4, 4)
-    pc.datamanager.dataparser = make_parser_classes(tmp_path)()
-    pc.datamanager.train_num_rays_per_batch = 5 * 16
-    pc.datamanager.train_num_lidar_rays_per_batch = 48
-    pc.datamanager.eval_num_rays_per_batch = 16
-    pc.datamanager.eval_num_lidar_rays_per_batch = 16
-    pc.datamanager.pixel_sampler.patch_size, pc.datamanager.pixel_sampler.patch_scale = 4, pc.model.rgb_upsample_factor
-    t._shrink(pc.model)
-    pc.__post_init__()
-    return cfg
-
 
 @pytest.fixture()
 def pipeline(ref, tmp_path):
     from neurad_studio_amd.integration.pipeline import ADHipDataManager, ADHipPipeline
 
-    cfg = _method_config(tmp_path)
+    cfg = t.method_config(tmp_path)
     pc = cfg.pipeline
     torch.manual_seed(0)
     pipe = pc.setup(device="cuda:0", test_mode="val", world_size=1, local_rank=0, grad_scaler=None)
     assert isinstance(pipe, ADHipPipeline) and isinstance(pipe.datamanager, ADHipDataManager)
-    t._fill(pipe.model)
+    t.fill(pipe.model)
     return cfg, pipe
 
 
@@ -234,7 +144,7 @@ def test_fused_metrics_equal_the_references_get_metrics_dict(pipeline):
     get_metrics_dict (models/neurad.py:461-529) on the same outputs: same keys, same values"""
     cfg, pipe = pipeline
     pipe.train()
-    t._deterministic(pipe.model, True)
+    t.deterministic(pipe.model, True)
     torch.manual_seed(5)
     rb, batch = pipe.datamanager.next_train(0)
     m = pipe.model
@@ -266,7 +176,7 @@ def test_ns_train_neurad_hip_from_config_setup_to_checkpoint(ref, tmp_path):
     from neurad_studio_amd.optim import HashGridAdam, TableGradScaler
 
     n_iter = 8
-    cfg = _method_config(tmp_path)
+    cfg = t.method_config(tmp_path)
     cfg.output_dir, cfg.experiment_name, cfg.timestamp = tmp_path / "outputs", "synthetic-drive", "run"
     cfg.vis = "none"  # no viewer, no event writer (neither viser nor tensorboard is installed here); the local writer stays
     cfg.max_num_iterations, cfg.steps_per_save = n_iter, 4
@@ -283,7 +193,7 @@ def test_ns_train_neurad_hip_from_config_setup_to_checkpoint(ref, tmp_path):
     assert isinstance(trainer.pipeline, ADHipPipeline) and isinstance(trainer.pipeline.datamanager, ADHipDataManager)
     assert isinstance(trainer.optimizers.optimizers["hashgrids"], HashGridAdam)
     assert len(trainer.callbacks) >= 1  # the model's own (sampler anneal / step callbacks, models/neurad.py:291-300)
-    t._fill(trainer.pipeline.model)
+    t.fill(trainer.pipeline.model)
     table = trainer.pipeline.model.field.hashgrid.static_grid.hash_table
     before = table.detach().clone()
     trainer.train()

@@ -16,9 +16,6 @@ iterations: every parameter.  The yardsticks are the reference's own: fp32 vs fp
 1e-15) and its AMP loop vs its fp32 loop (what mixed precision itself costs)."""
 import os
 import sys
-import types
-from collections import defaultdict
-from copy import deepcopy
 
 import numpy as np
 import pytest
@@ -28,104 +25,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ref_import  # noqa: E402
-import test_gpu_reference_plugin as t  # noqa: E402
-from test_gpu_reference_plugin import ref  # noqa: E402,F401  (module-scoped fixture: stubs + registry variable)
+import plugin_harness as t  # noqa: E402
+from plugin_harness import ref  # noqa: E402,F401  (module-scoped fixture: stubs + registry variable)
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not ref_import.reference_available(), reason="no reference (oracle/_ref ships with the lease)")]
 
-K = 10
-
-
-def _batch_k(with_actors, k, n_actors=3):
-    """iteration k's batch: the test scene's rays moved a little further along each iteration, labels rolled"""
-    b = t._batch(with_actors, n_actors=n_actors)
-    b = dict(b)
-    b["o"] = (b["o"] + np.float32(0.15 * k) * np.array([1.0, -0.5, 0.02], np.float32)).astype(np.float32)
-    b["times"] = (0.2 + (b["times"] - 0.2 + 0.31 * k) % 3.6).astype(np.float32)
-    b["image"] = np.roll(b["image"], k, axis=1)
-    b["lidar"] = np.roll(b["lidar"], k, axis=0)
-    b["dist"] = (6.0 + (b["dist"] - 6.0 + 1.7 * k) % 34.0).astype(np.float32)
-    return b
-
-
-class _Pipeline:
-    """what ``ADPipeline.get_train_loss_dict`` (pipelines/ad_pipeline.py:78-100 -- the reference's method, called unbound)
-    reads from its pipeline: a datamanager that hands out (ray_bundle, batch), the model, config.ray_patch_size"""
-
-    def __init__(self, model, with_actors, device, dtype, n_actors=3):
-        self._model = self.model = model
-        self.config = types.SimpleNamespace(ray_patch_size=None)
-        self.datamanager = types.SimpleNamespace(next_train=self._next_train)
-        self._args = (with_actors, device, dtype, n_actors)
-
-    def _next_train(self, step):
-        with_actors, device, dtype, n_actors = self._args
-        b = _batch_k(with_actors, step, n_actors)
-        self.config.ray_patch_size = (b["patch"], b["patch"])
-        rb, lab = t._bundle(b, device), t._labels(b, device)
-        if dtype == torch.float64:
-            for k in ("origins", "directions", "pixel_area", "times"):
-                setattr(rb, k, getattr(rb, k).double())
-            rb.metadata["directions_norm"] = rb.metadata["directions_norm"].double()
-            lab = {k: (v.double() if v.is_floating_point() else v) for k, v in lab.items()}
-        return rb, lab
-
-    def get_train_loss_dict(self, step):
-        from nerfstudio.pipelines.ad_pipeline import ADPipeline
-
-        return ADPipeline.get_train_loss_dict(self, step)
-
-
-class _Loop:
-    """the attributes ``Trainer.train_iteration`` reads (engine/trainer.py:176-189,535-579), set as ``Trainer.__init__`` /
-    ``Trainer.setup`` set them; the iteration itself is the reference's own function"""
-
-    def __init__(self, method_config, model, pipeline, device, mixed_precision, warmup=True):
-        from nerfstudio.engine.optimizers import Optimizers
-        from torch.cuda.amp.grad_scaler import GradScaler  # engine/trainer.py:40
-
-        self.config = types.SimpleNamespace(log_gradients=False)
-        self.device = device
-        self.mixed_precision = bool(mixed_precision) and not device.startswith("cpu")
-        self.grad_scaler = GradScaler(enabled=self.mixed_precision)
-        self.gradient_accumulation_steps = defaultdict(lambda: 1)
-        self.pipeline = pipeline
-        # Trainer.setup_optimizers (engine/trainer.py:264-275): the method's optimizer table x the model's parameter groups
-        groups = {k: v for k, v in model.get_param_groups().items() if len(v)}
-        table = deepcopy({k: method_config.optimizers[k] for k in groups})
-        if not warmup:  # full learning rates from the first iteration (the shipped schedules ramp up over 500 - 2500 steps:
-            for v in table.values():  # ten iterations of those move the parameters by 1e-4 only)
-                v["scheduler"].warmup_steps = 0
-        self.optimizers = Optimizers(table, groups)
-
-    def run(self, n):
-        from nerfstudio.engine.trainer import Trainer
-
-        losses = []
-        for step in range(n):
-            _, loss_dict, _ = Trainer.train_iteration(self, step)
-            losses.append({k: float(v) for k, v in loss_dict.items()})
-            self.pipeline.model.sampler.step_cb(step)  # the model's AFTER_TRAIN_ITERATION callback (models/neurad.py:291-300)
-        return losses
-
-
-def _methods():
-    import nerfstudio.configs.method_configs as ref_methods
-    from nerfstudio.plugins.registry import discover_methods
-
-    methods = dict(ref_methods.all_methods)
-    if "neurad-hip" not in methods:
-        methods.update(discover_methods()[0])
-    return methods
-
+K = t.K
 
 def _param_report(models, init):
     """{name: {pair: ||a - b|| / ||update of the fp32 reference||}} for the parameter tensors that moved"""
     ref32 = dict(models["ref32"].named_parameters())
     rep = {}
     for n, p0 in init.items():
-        if t._analytically_zero(n):  # (gradient = rounding noise, which Adam at eps = 1e-15 turns into +-lr steps)
+        if t.analytically_zero(n):  # (gradient = rounding noise, which Adam at eps = 1e-15 turns into +-lr steps)
             continue
         r = ref32[n].detach().double().cpu()
         upd = float((r - p0.double()).norm())
@@ -141,15 +54,15 @@ def _param_report(models, init):
 
 
 def _run_all(ref, with_actors, fp16_tables=False, n_actors=3, with_amp_reference=True, warmup=True):
-    methods = _methods()
-    hip, ref32 = t._build_pair(ref, with_actors, n_actors=n_actors, fp16_tables=fp16_tables)
+    methods = t.methods()
+    hip, ref32 = t.build_pair(ref, with_actors, n_actors=n_actors, fp16_tables=fp16_tables)
     init = {n: p.detach().float().cpu().clone() for n, p in ref32.named_parameters()}
-    _, ref64 = t._build_pair(ref, with_actors, n_actors=n_actors, fp16_tables=fp16_tables)
+    _, ref64 = t.build_pair(ref, with_actors, n_actors=n_actors, fp16_tables=fp16_tables)
     ref64 = ref64.double()
-    hip32, _ = t._build_pair(ref, with_actors, n_actors=n_actors, fp16_tables=fp16_tables)
+    hip32, _ = t.build_pair(ref, with_actors, n_actors=n_actors, fp16_tables=fp16_tables)
     models = {"hip": hip, "hip32": hip32, "ref32": ref32, "ref64": ref64}
     if with_amp_reference:  # the reference's torch model on the GPU, under the reference's AMP loop
-        _, refamp = t._build_pair(ref, with_actors, n_actors=n_actors, fp16_tables=fp16_tables)
+        _, refamp = t.build_pair(ref, with_actors, n_actors=n_actors, fp16_tables=fp16_tables)
         models["refamp"] = refamp.to("cuda")
         models["refamp"].camera_optimizer.to("cuda")
     spec = {"hip": ("neurad-hip", "cuda:0", torch.float32, True), "hip32": ("neurad-hip", "cuda:0", torch.float32, False),
@@ -158,9 +71,9 @@ def _run_all(ref, with_actors, fp16_tables=False, n_actors=3, with_amp_reference
     losses = {}
     for who, m in models.items():
         method, device, dtype, mp = spec[who]
-        t._deterministic(m, True)
-        pipe = _Pipeline(m, with_actors, device.split(":")[0], dtype, n_actors)
-        loop = _Loop(methods[method], m, pipe, device, mp, warmup=warmup)
+        t.deterministic(m, True)
+        pipe = t.Pipeline(m, with_actors, device.split(":")[0], dtype, n_actors)
+        loop = t.Loop(methods[method], m, pipe, device, mp, warmup=warmup)
         if who == "hip":
             from neurad_studio_amd.optim import HashGridAdam
 
@@ -222,7 +135,7 @@ def _check(models, init, losses, tag):
     # parameters after K iterations, relative to the size of the update the reference made
     worst = {}
     for n, e in prep.items():
-        kind = t._kind(n)
+        kind = t.kind(n)
         w = worst.setdefault(kind, {"hip": 0.0, "hip32": 0.0, "ref64": 0.0, "refamp": 0.0})
         for who in w:
             w[who] = max(w[who], e.get(who, 0.0))
@@ -251,13 +164,13 @@ def test_fp16_storage_tables_train_under_mixed_precision(ref):
     """BASELINE config[4]'s storage mode through the reference's loop: ``GradScaler.step`` refuses fp16 gradients for ordinary
     optimizers ("Attempting to unscale FP16 gradients"); HashGridAdam takes scale and found-inf on the device.  32 actors,
     ``table_dtype="float16"`` selected through the model config."""
-    methods = _methods()
-    hip, ref32 = t._build_pair(ref, True, n_actors=32, fp16_tables=True)
+    methods = t.methods()
+    hip, ref32 = t.build_pair(ref, True, n_actors=32, fp16_tables=True)
     assert hip.field.hashgrid.static_grid.hash_table.dtype == torch.float16
     init = {n: p.detach().float().cpu().clone() for n, p in ref32.named_parameters()}
-    t._deterministic(hip, True), t._deterministic(ref32, True)
-    loops = {"hip": _Loop(methods["neurad-hip"], hip, _Pipeline(hip, True, "cuda", torch.float32, 32), "cuda:0", True),
-             "ref32": _Loop(methods["neurad"], ref32, _Pipeline(ref32, True, "cpu", torch.float32, 32), "cpu", True)}
+    t.deterministic(hip, True), t.deterministic(ref32, True)
+    loops = {"hip": t.Loop(methods["neurad-hip"], hip, t.Pipeline(hip, True, "cuda", torch.float32, 32), "cuda:0", True),
+             "ref32": t.Loop(methods["neurad"], ref32, t.Pipeline(ref32, True, "cpu", torch.float32, 32), "cpu", True)}
     losses = {who: lp.run(6) for who, lp in loops.items()}
     for k in range(6):
         for term, want in losses["ref32"][k].items():

@@ -20,9 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ref_import  # noqa: E402
-import test_gpu_plugin_train_loop as L  # noqa: E402
-import test_gpu_reference_plugin as t  # noqa: E402
-from test_gpu_reference_plugin import ref  # noqa: E402,F401
+import plugin_harness as t  # noqa: E402
+from plugin_harness import ref  # noqa: E402,F401
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not ref_import.reference_available(), reason="no reference (oracle/_ref ships with the lease)")]
@@ -31,14 +30,14 @@ K = 12
 NON_FINITE_AT = (2, 3, 7)
 
 
-class _PoisonedPipeline(L._Pipeline):
+class _PoisonedPipeline(t.Pipeline):
     """the test pipeline with one loss term made infinite in the chosen iterations; the K batches are built up front (their
     host -> device copies would trip the sync-debug mode the deferred iteration runs under)"""
 
     def prefetch(self, n):
         self._cache = {}
         for step in range(n):
-            rb, lab = L._Pipeline._next_train(self, step)
+            rb, lab = t.Pipeline._next_train(self, step)
             self._cache[step] = (rb, lab, self.config.ray_patch_size)
         self.datamanager = types.SimpleNamespace(next_train=self._cached_next_train)
 
@@ -89,16 +88,16 @@ def test_deferred_scheduler_step_is_the_reference_iteration(ref):
 
     from neurad_studio_amd.integration.trainer import HipTrainer, HipTrainerConfig
 
-    methods = L._methods()
+    methods = t.methods()
     method = methods["neurad-hip"]
     assert isinstance(method, HipTrainerConfig) and method._target is HipTrainer  # what `ns-train neurad-hip` instantiates
-    a, _ = t._build_pair(ref, False)
-    twins = {"reference": a, "reference again": t._build_pair(ref, False)[0], "deferred": t._build_pair(ref, False)[0]}
+    a, _ = t.build_pair(ref, False)
+    twins = {"reference": a, "reference again": t.build_pair(ref, False)[0], "deferred": t.build_pair(ref, False)[0]}
     init = {n: p.detach().float().clone() for n, p in a.named_parameters()}
     loops = {}
     for who, m in twins.items():
         m.load_state_dict(a.state_dict())
-        t._deterministic(m, True)
+        t.deterministic(m, True)
         cls = HipTrainer if who == "deferred" else Trainer
         loops[who] = (_make_loop(cls, method, m), cls.train_iteration)
     sync_free = 0

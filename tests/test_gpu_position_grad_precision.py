@@ -35,28 +35,14 @@ import torch
 import neurad_oracle as O
 import synth
 from conftest import load_golden
-from test_oracle_grad_edges import actor_case, actor_pair_grads64, edge_g_enc, edge_grid, excess
+from gpu_util import dev, host64_via32
+from gpu_util import ops  # noqa: F401  (fixture)
+from grad_edge_refs import actor_case, actor_pair_grads64, edge_g_enc, edge_grid, excess
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
 SCALES = (1.0, 2.0 ** 16, 2.0 ** 24)
-
-
-@pytest.fixture(scope="module")
-def ops():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from neurad_studio_amd import ops as _ops
-
-    return _ops
-
-
-def dev(a, dtype=torch.float32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
-
-
-def host(t):
-    return t.detach().float().cpu().numpy().astype(np.float64)
 
 
 def sharp_gradients(n, width, seed, scale):
@@ -87,7 +73,7 @@ def run_rays(ops, grid, scale, o, d, area, st, en, ge, tdt):
     spec = ops.GridSpec(grid.num_levels, grid.n_feat, grid.log2_hashmap_size, grid.min_res, grid.max_res)
     go, gd = ops.encode_bwd_rays(spec, dev(grid.table).to(tdt), scale, dev(o), dev(d), dev(area), dev(st), dev(en),
                                  dev(ge))
-    return host(go), host(gd)
+    return host64_via32(go), host64_via32(gd)
 
 
 @pytest.mark.parametrize("F", [1, 2, 4, 8])
@@ -175,7 +161,7 @@ def test_hashgrid_bwd_input_per_element(ops, F, half):
     for k, sc in enumerate(SCALES):
         go = sharp_gradients(n, L * F, 300 + k, sc)
         ref, A = O.hashgrid_input_grads(x, grid.table, grid.scalings, 2**11, go, with_abs=True)
-        got = host(ops.hashgrid_bwd_input(spec, tab, dev(x), dev(go)))
+        got = host64_via32(ops.hashgrid_bwd_input(spec, tab, dev(x), dev(go)))
         assert excess(got, ref, A).max() <= 12 + F + L, (sc, excess(got, ref, A).max())
 
 
@@ -200,7 +186,7 @@ def test_hashgrid_multi_bwd_input_per_element(ops, order):
             m = ids == i
             if m.any():
                 ref[m], A[m] = O.hashgrid_input_grads(x[m], tabs[i], scal, 2**lg, go[m], with_abs=True)
-        got = host(ops.hashgrid_multi_bwd_input(spec, [dev(t) for t in tabs], dev(ids, torch.int32), dev(x), dev(go)))
+        got = host64_via32(ops.hashgrid_multi_bwd_input(spec, [dev(t) for t in tabs], dev(ids, torch.int32), dev(x), dev(go)))
         assert excess(got, ref, A).max() <= 12 + F + L, (sc, excess(got, ref, A).max())
 
 
@@ -222,7 +208,7 @@ def test_hashgrid_multi_bwd_input_every_feature_width_and_storage_type(ops, F, h
         m = ids == i
         ref[m], A[m] = O.hashgrid_input_grads(x[m], tabs[i], scal, 2**lg, go[m], with_abs=True)
     dtabs = [dev(t).to(torch.float16 if half else torch.float32) for t in tabs]
-    got = host(ops.hashgrid_multi_bwd_input(spec, dtabs, dev(ids, torch.int32), dev(x), dev(go)))
+    got = host64_via32(ops.hashgrid_multi_bwd_input(spec, dtabs, dev(ids, torch.int32), dev(x), dev(go)))
     assert excess(got, ref, A).max() <= 12 + F + L, excess(got, ref, A).max()
 
 
@@ -243,7 +229,8 @@ def _run_pairs(ops, a, A, o, d, area, st, en, times, sidx, aidx, flip, gx, gs):
     gp2, gr2 = ops.actor_pair_positions_bwd(spec, dev(o), dev(d), dev(area), dev(st), dev(en), dev(times),
                                             dev(sidx, torch.int64), dev(aidx, torch.int32),
                                             None if flip is None else dev(flip), dev(gx), dev(gs))
-    return dict(dpos=host(gp), drot=host(gr), go=host(go), gd=host(gd), dpos2=host(gp2), drot2=host(gr2))
+    return dict(dpos=host64_via32(gp), drot=host64_via32(gr), go=host64_via32(go), gd=host64_via32(gd),
+                dpos2=host64_via32(gp2), drot2=host64_via32(gr2))
 
 
 @pytest.mark.parametrize("n_pairs", [1, 15, 16, 17, 1023, 1025])

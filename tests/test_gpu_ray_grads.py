@@ -8,7 +8,7 @@ import torch
 import neurad_oracle as O
 import synth
 from conftest import load_golden, rel_l2
-from test_gpu_modules import bundle, dev, host, make_field, make_prop
+from gpu_util import bundle, cuda, host, make_field, make_prop
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -24,17 +24,17 @@ def test_encode_bwd_rays_vs_reference_autograd():
     g = load_golden("ray_grads")
     grid = _field_grid()
     spec = ops.GridSpec(8, 4, 11, 32, 8192)
-    args = [dev(g[k]) for k in ("o", "d", "area", "starts", "ends")]
-    go, gd = ops.encode_bwd_rays(spec, dev(grid.table), 100.0, *args, dev(g["g_enc"]))
+    args = [cuda(g[k]) for k in ("o", "d", "area", "starts", "ends")]
+    go, gd = ops.encode_bwd_rays(spec, cuda(grid.table), 100.0, *args, cuda(g["g_enc"]))
     assert rel_l2(host(go), g["enc_go"]) < TOL and rel_l2(host(gd), g["enc_gd"]) < TOL
     # run to run: no atomics -> bit-identical
-    go2, gd2 = ops.encode_bwd_rays(spec, dev(grid.table), 100.0, *args, dev(g["g_enc"]))
+    go2, gd2 = ops.encode_bwd_rays(spec, cuda(grid.table), 100.0, *args, cuda(g["g_enc"]))
     assert torch.equal(go, go2) and torch.equal(gd, gd2)
     # rows that are exactly zero (samples behind an opaque surface / overridden by an actor) contribute nothing
     ge = g["g_enc"].copy()
     ge[::3] = 0
     want = O.encode_static_ray_grads(grid, 100.0, g["o"], g["d"], g["area"], g["starts"], g["ends"], ge)
-    go, gd = ops.encode_bwd_rays(spec, dev(grid.table), 100.0, *args, dev(ge))
+    go, gd = ops.encode_bwd_rays(spec, cuda(grid.table), 100.0, *args, cuda(ge))
     assert rel_l2(host(go), want[0]) < TOL and rel_l2(host(gd), want[1]) < TOL
 
 
@@ -48,12 +48,12 @@ def test_encode_bwd_rays_group_sizes_and_fp16_table_vs_oracle(S):
     _, eu, _ = O.power_sampler(np.zeros(R), np.full(R, 3000.0, np.float32), S)
     ge = synth.normal((R * S, 32), seed=9)
     spec = ops.GridSpec(8, 4, 11, 32, 8192)
-    edges = dev(eu)
+    edges = cuda(eu)
     for dtype, tdt in ((np.float32, torch.float32), (np.float16, torch.float16)):
         grid = _field_grid(dtype=dtype)
         want = O.encode_static_ray_grads(grid, 100.0, o, d, area, eu[:, :-1], eu[:, 1:], ge)
-        go, gd = ops.encode_bwd_rays(spec, dev(grid.table).to(tdt), 100.0, dev(o), dev(d), dev(area), edges[:, :-1],
-                                     edges[:, 1:], dev(ge))
+        go, gd = ops.encode_bwd_rays(spec, cuda(grid.table).to(tdt), 100.0, cuda(o), cuda(d), cuda(area), edges[:, :-1],
+                                     edges[:, 1:], cuda(ge))
         assert rel_l2(host(go), want[0]) < TOL and rel_l2(host(gd), want[1]) < TOL, (S, dtype)
 
 
@@ -63,25 +63,25 @@ def test_proposal_density_ray_gradients_vs_reference_autograd():
     g = load_golden("ray_grads")
     p = make_prop(91)
     hg = p.hashgrid
-    o, d = dev(g["o"]).requires_grad_(True), dev(g["d"]).requires_grad_(True)
+    o, d = cuda(g["o"]).requires_grad_(True), cuda(g["d"]).requires_grad_(True)
     dens = ag.ProposalDensityFn.apply(hg.static_grid.hash_table, p.density_decoder.weight, hg.static_grid.spec, hg.static_scale,
-                                      o, d, dev(g["area"]), dev(g["starts"]), dev(g["ends"]))
+                                      o, d, cuda(g["area"]), cuda(g["starts"]), cuda(g["ends"]))
     assert rel_l2(host(dens), g["prop_dens"]) < TOL
-    (dens * dev(g["prop_g_dens"])).sum().backward()
+    (dens * cuda(g["prop_g_dens"])).sum().backward()
     assert rel_l2(host(o.grad), g["prop_go"]) < TOL and rel_l2(host(d.grad), g["prop_gd"]) < TOL
     # the fused sampler round (weights + depth from the edges): ray gradients against torch autograd through the
     # operator-level nodes on the same inputs
-    edges = torch.cat([dev(g["starts"]), dev(g["ends"])[:, -1:]], -1).contiguous()
-    gw = dev(synth.normal(g["starts"].shape, seed=3))
+    edges = torch.cat([cuda(g["starts"]), cuda(g["ends"])[:, -1:]], -1).contiguous()
+    gw = cuda(synth.normal(g["starts"].shape, seed=3))
 
     def run(fused):
-        o_, d_ = dev(g["o"]).requires_grad_(True), dev(g["d"]).requires_grad_(True)
+        o_, d_ = cuda(g["o"]).requires_grad_(True), cuda(g["d"]).requires_grad_(True)
         if fused:
             w, dep = ag.ProposalRoundFn.apply(hg.static_grid.hash_table, p.density_decoder.weight, hg.static_grid.spec,
-                                              hg.static_scale, o_, d_, dev(g["area"]), edges)
+                                              hg.static_scale, o_, d_, cuda(g["area"]), edges)
         else:
             dn = ag.ProposalDensityFn.apply(hg.static_grid.hash_table, p.density_decoder.weight, hg.static_grid.spec,
-                                            hg.static_scale, o_, d_, dev(g["area"]), edges[:, :-1], edges[:, 1:])
+                                            hg.static_scale, o_, d_, cuda(g["area"]), edges[:, :-1], edges[:, 1:])
             w, dep = ag.PropWeightsFn.apply(edges, dn)
         ((w * gw).sum() + dep.sum()).backward()
         return host(o_.grad), host(d_.grad)
@@ -105,8 +105,8 @@ def test_field_ray_gradients_vs_reference_autograd(fused_training):
     rs = PowerSampler(num_samples=g["starts"].shape[1], lambda_=-1.0, scaling=0.1).eval()(rb)
     out = fld(rs)
     assert rel_l2(host(out[FieldHeadNames.FEATURE]), g["field_feature"]) < TOL
-    ((out[FieldHeadNames.FEATURE] * dev(g["field_g_feature"])).sum()
-     + (out[FieldHeadNames.ALPHA][..., 0] * dev(g["field_g_alpha"])).sum()).backward()
+    ((out[FieldHeadNames.FEATURE] * cuda(g["field_g_feature"])).sum()
+     + (out[FieldHeadNames.ALPHA][..., 0] * cuda(g["field_g_alpha"])).sum()).backward()
     # Through the MLPs the bound is the reference's own: its fp32 model against itself in fp64 differs by 2.4e-2 / 3.5e-2 on
     # these gradients, on EVERY ray (golden field_floor: d lerp / dx is bilinear in the other two offsets, which fp32
     # positions resolve to 5e-4 of a finest-level cell; the per-ray sums cancel heavily, the direction gradient weighs every
@@ -124,7 +124,7 @@ def test_field_ray_gradients_vs_reference_autograd(fused_training):
     rb2 = bundle(g["o"], g["d"], g["area"])
     rs2 = PowerSampler(num_samples=g["starts"].shape[1], lambda_=-1.0, scaling=0.1).eval()(rb2)
     out2 = fld(rs2)
-    ((out2[FieldHeadNames.FEATURE] * dev(g["field_g_feature"])).sum()
-     + (out2[FieldHeadNames.ALPHA][..., 0] * dev(g["field_g_alpha"])).sum()).backward()
+    ((out2[FieldHeadNames.FEATURE] * cuda(g["field_g_feature"])).sum()
+     + (out2[FieldHeadNames.ALPHA][..., 0] * cuda(g["field_g_alpha"])).sum()).backward()
     assert rel_l2(host(fld.hashgrid.static_grid.hash_table.grad), tg) < 1e-6  # (a batch this small takes the atomic scatter)
     assert rb2.origins.grad is None

@@ -18,17 +18,16 @@ place of the CPU placeholder (models/neurad.py:713-715 returns 0.5 on CPU), no V
 """
 import os
 import sys
-from copy import deepcopy
 
-import numpy as np
 import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import plugin_harness as t  # noqa: E402
 import ref_import  # noqa: E402
-import synth  # noqa: E402
 from conftest import rel_l2  # noqa: E402
+from plugin_harness import N, T, check_gradients_against_floor, per_loss_gradient_errors, ref  # noqa: E402,F401
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not ref_import.reference_available(),
@@ -36,263 +35,14 @@ pytestmark = [pytest.mark.gpu,
                                         "(oracle/_ref ships with the lease)")]
 
 
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32)))
-
-
-def N(t):
-    return t.detach().float().cpu().numpy()
-
-
-def _dense_nerfacc():
-    import types
-
-    m = types.ModuleType("nerfacc")
-
-    def render_weight_from_alpha(alphas, **kw):
-        trans = torch.cumprod(torch.cat([torch.ones_like(alphas[..., :1]), 1 - alphas[..., :-1]], -1), -1)
-        return trans * alphas, trans
-
-    def accumulate_along_rays(weights, values=None, ray_indices=None, n_rays=None):
-        return weights.sum(-1, keepdim=True) if values is None else (weights[..., None] * values).sum(-2)
-
-    def render_weight_from_density(t_starts, t_ends, sigmas, **kw):
-        sd = sigmas * (t_ends - t_starts)
-        trans = torch.exp(-(torch.cumsum(sd, -1) - sd))
-        alphas = 1 - torch.exp(-sd)
-        return trans * alphas, trans, alphas
-
-    m.render_weight_from_alpha, m.accumulate_along_rays = render_weight_from_alpha, accumulate_along_rays
-    m.render_weight_from_density = render_weight_from_density
-    return m
-
-
-def _trajectories():
-    """3 actors moving along +x (the scene of oracle/make_golden_actors.py): actor 2 overlaps actor 1's box, actor 0 is
-    present early only"""
-    ts_all = torch.tensor([0.0, 1.0, 2.0, 3.0, 4.0])
-    out = []
-    for a, (y0, yaw, dims, ts) in enumerate([(8.0, 0.3, (2.0, 4.5, 1.6), ts_all[:3]), (-6.0, -0.2, (2.1, 4.8, 1.7), ts_all),
-                                             (-5.0, 0.1, (1.9, 4.2, 1.5), ts_all[1:])]):
-        poses = []
-        for t in ts:
-            c, s = np.cos(yaw + 0.05 * float(t)), np.sin(yaw + 0.05 * float(t))
-            p = torch.eye(4)
-            p[:3, :3] = torch.tensor([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
-            p[:3, 3] = torch.tensor([12.0 + 2.0 * float(t) + a, y0, 0.5])
-            poses.append(p)
-        out.append({"timestamps": ts.clone(), "poses": torch.stack(poses), "dims": torch.tensor(dims),
-                    "symmetric": torch.tensor(True), "deformable": torch.tensor(False)})
-    return out
-
-
-def _many_trajectories(n):
-    """n actors in two lanes along +x, staggered every 3 m, each present over its own part of the scene's 4 s (config[4]'s 32
-    actors at test size: several boxes along every ray, neighbours overlapping at the lane changes)"""
-    ts_all = torch.tensor([0.0, 1.0, 2.0, 3.0, 4.0])
-    out = []
-    for a in range(n):
-        ts = ts_all[a % 2:] if a % 3 else ts_all[:4]
-        yaw = 0.25 * ((a * 7) % 5 - 2) / 2
-        poses = []
-        for t in ts:
-            c, s = np.cos(yaw + 0.04 * float(t)), np.sin(yaw + 0.04 * float(t))
-            p = torch.eye(4)
-            p[:3, :3] = torch.tensor([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
-            p[:3, 3] = torch.tensor([8.0 + 3.0 * a + 1.5 * float(t), 6.5 if a % 2 == 0 else -5.5, 0.5])
-            poses.append(p)
-        out.append({"timestamps": ts.clone(), "poses": torch.stack(poses),
-                    "dims": torch.tensor([1.9 + 0.01 * a, 4.2 + 0.02 * a, 1.5 + 0.01 * a]),
-                    "symmetric": torch.tensor(True), "deformable": torch.tensor(False)})
-    return out
-
-
-def _fill(model):
-    """deterministic O(1)-feature parameters (tests/synth.py) so that densities, weights and every loss term are far from
-    their trivial values"""
-    for k, (name, p) in enumerate(model.named_parameters()):
-        if name.endswith("hash_table"):
-            scale = 1.0 if p.shape[1] == 4 else 2.5
-            p.data = T(synth.hash_table(p.shape[0], p.shape[1], seed=100 + k, scale=scale)).to(p.device, p.dtype)
-        elif name.startswith(("field.mlp", "proposal_fields", "lidar_decoder")) and name.endswith("weight") and p.dim() == 2:
-            w, _ = synth.linear(p.shape[0], p.shape[1], 100 + k)
-            p.data = T(w).to(p.device)
-        elif name.startswith(("field.mlp", "lidar_decoder")) and name.endswith("bias"):
-            p.data = T(synth.uniform(tuple(p.shape), -0.2, 0.2, 100 + k)).to(p.device)
-    # a translucent static scene (positive SDF offset): the rays reach the actors' corridor 10-25 m out, so that the actor
-    # grids and the trajectories receive gradients of the same order as the static table's
-    with torch.no_grad():
-        model.field.mlp_geo.layers[-1].bias[0] = 1.2
-    model.appearance_embedding.weight.data = T(synth.normal(tuple(model.appearance_embedding.weight.shape), seed=77)).to(
-        model.appearance_embedding.weight.device)
-
-
-@pytest.fixture(scope="module")
-def ref():
-    ref_import.install()
-    import nerfstudio.model_components.renderers as ref_renderers
-    import nerfstudio.models.neurad as ref_neurad
-
-    saved = (ref_neurad.VGGPerceptualLossPix2Pix, ref_neurad.nerfacc, ref_renderers.nerfacc,
-             os.environ.get("NERFSTUDIO_METHOD_CONFIGS"))
-    ref_neurad.VGGPerceptualLossPix2Pix = torch.nn.Identity
-    os.environ["NERFSTUDIO_METHOD_CONFIGS"] = "neurad-hip=neurad_studio_amd.integration.neurad_hip:neurad_hip"
-    yield ref_neurad
-    ref_neurad.VGGPerceptualLossPix2Pix, ref_neurad.nerfacc, ref_renderers.nerfacc = saved[:3]
-    if saved[3] is None:
-        os.environ.pop("NERFSTUDIO_METHOD_CONFIGS", None)
-    else:
-        os.environ["NERFSTUDIO_METHOD_CONFIGS"] = saved[3]
-
-
-def _shrink(c):
-    c.field.grid.static.log2_hashmap_size = 12
-    c.field.grid.actor.log2_hashmap_size = 9
-    c.field.sdf_beta = 3.0
-    for pf in (c.sampling.proposal_field_1, c.sampling.proposal_field_2):
-        pf.grid.static.log2_hashmap_size = 10
-        pf.grid.actor.log2_hashmap_size = 8
-    c.loss.vgg_mult = 0.0
-    return c
-
-
-def _build_pair(ref_neurad, with_actors, fused_decoder=False, pose_opt=False, n_actors=3, fp16_tables=False, use_sdf=True,
-                normalize_depth=False):
-    """(the plugin on cuda:0, resolved through the registry; the reference's torch model on the CPU; same weights).
-    pose_opt: camera_optimizer.mode = "SO3xR3" on both (the `*-scaleopt` methods, configs/method_configs.py:438-447), with
-    non-zero pose adjustments so that the rays really move.  n_actors > 3: `_many_trajectories`.  fp16_tables: the plugin's
-    main-field static table and actor grids in fp16 STORAGE (BASELINE config[4]); the reference's fp32 tables then hold exactly
-    those rounded values"""
-    import nerfstudio.model_components.renderers as ref_renderers
-    from nerfstudio.data.scene_box import SceneBox
-    from nerfstudio.plugins.registry import discover_methods
-
-    # what ns-train does: importing the method table runs the plugin discovery (configs/method_configs.py ->
-    # plugins/registry.py:56-73, the NERFSTUDIO_METHOD_CONFIGS form)
-    import nerfstudio.configs.method_configs as ref_methods
-
-    methods = ref_methods.all_methods
-    if "neurad-hip" not in methods:  # the table was imported earlier in this process, before the variable was set
-        methods, _ = discover_methods()
-    mcfg = _shrink(deepcopy(methods["neurad-hip"].pipeline.model))
-    mcfg.fused_decoder = fused_decoder
-    if fp16_tables:  # the plugin's own switch (integration/neurad_hip.py: NeuRADHipModelConfig.table_dtype)
-        mcfg.table_dtype = "float16"
-    mcfg.field.use_sdf, mcfg.normalize_depth = use_sdf, normalize_depth
-    if pose_opt:
-        mcfg.camera_optimizer = deepcopy(mcfg.camera_optimizer)
-        mcfg.camera_optimizer.mode = "SO3xR3"
-    from neurad_studio_amd.integration.neurad_hip import NeuRADHipModel
-
-
-    def kw():
-        return dict(scene_box=SceneBox(aabb=torch.tensor([[-100.0] * 3, [100.0] * 3])), num_train_data=2,
-                    metadata={"duration": 5.0, "sensor_idx_to_name": {0: "cam0", 1: "cam1", 2: "lidar"},
-                              "trajectories": (_trajectories() if n_actors == 3 else _many_trajectories(n_actors))
-                              if with_actors else []})
-
-    torch.manual_seed(0)
-    hip = mcfg.setup(**kw())
-    assert isinstance(hip, NeuRADHipModel) and isinstance(hip, ref_neurad.NeuRADModel)
-    ref_cfg = _shrink(ref_neurad.NeuRADModelConfig(implementation="torch"))
-    for c in (ref_cfg.field, ref_cfg.sampling.proposal_field_1, ref_cfg.sampling.proposal_field_2):
-        c.grid.actor.use_4d_hashgrid = False
-    if pose_opt:  # (the method table's camera optimizer carries its own penalties: the same object on both sides)
-        ref_cfg.camera_optimizer = deepcopy(mcfg.camera_optimizer)
-    ref_cfg.field.use_sdf, ref_cfg.normalize_depth = use_sdf, normalize_depth
-    refm = ref_cfg.setup(**kw())
-    assert sorted(hip.state_dict()) == sorted(refm.state_dict())
-    _fill(hip)
-    if pose_opt:
-        pa = hip.camera_optimizer.pose_adjustment
-        pa.data = T(synth.normal(tuple(pa.shape), seed=55) * np.float32(0.02)).to(pa.device)
-    if fp16_tables:
-        assert all(gr.hash_table.dtype == torch.float16
-                   for gr in [hip.field.hashgrid.static_grid, *hip.field.hashgrid.actor_grids])
-    refm.load_state_dict({k: (v.float() if v.dtype == torch.float16 else v) for k, v in hip.state_dict().items()})
-    hip = hip.to("cuda")
-    # the reference on the CPU: dense nerfacc formulas instead of its 0.5 placeholder (models/neurad.py:713-715)
-    na = _dense_nerfacc()
-    ref_neurad.nerfacc = na
-    ref_renderers.nerfacc = na
-    # (on the INSTANCE: the plugin class inherits from NeuRADModel and must keep the reference's method)
-    if use_sdf:
-        refm._render_weights = lambda outputs, rs: na.render_weight_from_alpha(
-            outputs[ref_neurad.FieldHeadNames.ALPHA].squeeze(-1))[0]
-    else:  # models/neurad.py:718-723
-        refm._render_weights = lambda outputs, rs: na.render_weight_from_density(
-            t_starts=rs.frustums.starts.squeeze(-1), t_ends=rs.frustums.ends.squeeze(-1),
-            sigmas=outputs[ref_neurad.FieldHeadNames.DENSITY].squeeze(-1))[0]
-    return hip, refm
-
-
-def _batch(with_actors, patch=4, n_patches=3, n_lidar=40, n_actors=3):
-    """camera rays in ``patch`` x ``patch`` patches (the CNN decoder's unit) then lidar rays; with actors the rays are
-    aimed down the actors' corridor so that many samples fall inside boxes"""
-    Rc = n_patches * patch * patch
-    R = Rc + n_lidar
-    o = synth.normal((R, 3), 5) * np.array([1.5, 1.5, 0.3], np.float32)
-    if with_actors:
-        if n_actors == 3:
-            tgt = np.stack([synth.uniform((R,), 10, 24, 8),
-                            np.where(np.arange(R) % 2 == 0, 8.0, -5.5) + synth.uniform((R,), -1.5, 1.5, 9),
-                            synth.uniform((R,), 0.0, 1.0, 10)], -1).astype(np.float32)
-        else:  # down the two lanes of `_many_trajectories`: shallow angles, several boxes along a ray
-            tgt = np.stack([synth.uniform((R,), 12, 8.0 + 3.0 * n_actors, 28),
-                            np.where(np.arange(R) % 2 == 0, 6.5, -5.5) + synth.uniform((R,), -1.0, 1.0, 9),
-                            synth.uniform((R,), 0.1, 0.9, 10)], -1).astype(np.float32)
-        d = tgt - o
-    else:
-        d = synth.normal((R, 3), 6)
-    d = (d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32)
-    is_lidar = np.arange(R) >= Rc
-    did_return = np.where(is_lidar, synth.uniform((R,), 0, 1, 7) < 0.75, True)
-    dist = synth.uniform((R,), 6.0, 40.0, 8)
-    area = np.where(is_lidar, 4.5e-6, 2.7e-7).astype(np.float32)
-    times = synth.uniform((R,), 0.2, 3.8, 9)
-    sensor = np.where(is_lidar, 2, (np.arange(R) // (patch * patch)) % 2).astype(np.int64)
-    up = 3 * patch
-    image = synth.uniform((n_patches, up, up, 3), 0.0, 1.0, 31)
-    lidar = np.concatenate([synth.normal((n_lidar, 3), 21), synth.uniform((n_lidar, 1), 0, 1, 22)], -1)
-    return dict(o=o, d=d, is_lidar=is_lidar, did_return=did_return, dist=dist, area=area, times=times, sensor=sensor,
-                image=image, lidar=lidar, patch=patch, Rc=Rc)
-
-
-def _bundle(b, device):
-    from nerfstudio.cameras.rays import RayBundle
-
-    t = lambda a: T(a).to(device)  # noqa: E731
-    return RayBundle(origins=t(b["o"]), directions=t(b["d"]), pixel_area=t(b["area"])[:, None], times=t(b["times"])[:, None],
-                     camera_indices=(torch.arange(len(b["o"]), device=device) % 2)[:, None],
-                     metadata={"is_lidar": torch.from_numpy(b["is_lidar"])[:, None].to(device),
-                               "did_return": torch.from_numpy(b["did_return"])[:, None].to(device),
-                               "directions_norm": t(b["dist"])[:, None],
-                               "sensor_idxs": torch.from_numpy(b["sensor"])[:, None].to(device)})
-
-
-def _labels(b, device):
-    return {"image": T(b["image"]).to(device), "lidar": T(b["lidar"]).to(device),
-            "is_lidar": torch.from_numpy(b["is_lidar"])[:, None].to(device),
-            "did_return": torch.from_numpy(b["did_return"])[:, None].to(device),
-            "distance": T(b["dist"][b["is_lidar"]])[:, None].to(device)}
-
-
-def _deterministic(m, train):
-    m.train(train)
-    m.sampler.eval(), m.field.eval()
-    for p in m.proposal_fields:
-        p.eval()
-    return m
-
-
 @pytest.mark.parametrize("with_actors", [False, True], ids=["static", "actors3"])
 def test_plugin_eval_outputs_match_the_reference_torch_model(ref, with_actors):
-    hip, refm = _build_pair(ref, with_actors)
-    b = _batch(with_actors)
-    _deterministic(hip, False), _deterministic(refm, False)
+    hip, refm = t.build_pair(ref, with_actors)
+    b = t.batch(with_actors)
+    t.deterministic(hip, False), t.deterministic(refm, False)
     with torch.no_grad():
-        got = hip.get_nff_outputs(_bundle(b, "cuda"))
-        want = refm.get_nff_outputs(_bundle(b, "cpu"))
+        got = hip.get_nff_outputs(t.bundle(b, "cuda"))
+        want = refm.get_nff_outputs(t.bundle(b, "cpu"))
     assert set(got) == set(want)
     for k in ("features", "depth", "accumulation", "prop_depth_0", "prop_depth_1"):
         assert got[k].shape == want[k].shape and got[k].is_cuda, k
@@ -305,159 +55,22 @@ def test_plugin_eval_with_actor_edits_matches_the_reference_torch_model(ref):
     """the viewer's actor sliders / the actor-shift FID evaluation (pipelines/ad_pipeline.py:476-480) write
     ``model.dynamic_actors.actor_editing``; the reference applies it in get_boxes2world outside training
     (model_components/dynamic_actors.py:181-249,261-265), the plugin in nrhip_actor_prepare_edited"""
-    hip, refm = _build_pair(ref, True)
-    b = _batch(True)
-    _deterministic(hip, False), _deterministic(refm, False)
+    hip, refm = t.build_pair(ref, True)
+    b = t.batch(True)
+    t.deterministic(hip, False), t.deterministic(refm, False)
     with torch.no_grad():
-        base = hip.get_nff_outputs(_bundle(b, "cuda"))["features"].clone()
+        base = hip.get_nff_outputs(t.bundle(b, "cuda"))["features"].clone()
     for edit in (dict(lateral=1.0, longitudinal=-1.5, height=0.2, rotation=0.0, index=-1.0),
                  dict(lateral=0.0, longitudinal=0.0, height=0.0, rotation=0.5, index=1.0),
                  dict(lateral=-0.7, longitudinal=0.0, height=0.0, rotation=-0.3, index=9.0)):
         hip.dynamic_actors.actor_editing.update(edit), refm.dynamic_actors.actor_editing.update(edit)
         with torch.no_grad():
-            got = hip.get_nff_outputs(_bundle(b, "cuda"))
-            want = refm.get_nff_outputs(_bundle(b, "cpu"))
+            got = hip.get_nff_outputs(t.bundle(b, "cuda"))
+            want = refm.get_nff_outputs(t.bundle(b, "cpu"))
         for k in ("features", "depth", "accumulation", "prop_depth_0", "prop_depth_1"):
             assert rel_l2(N(got[k]), N(want[k])) < 1e-4, (edit, k, rel_l2(N(got[k]), N(want[k])))
         # the edit really moved something: the unedited output is much farther from the edited reference than the plugin is
         assert rel_l2(N(base), N(want["features"])) > 10 * rel_l2(N(got["features"]), N(want["features"])) + 1e-5, edit
-
-
-def _losses(m, b, device):
-    m.zero_grad(set_to_none=True)
-    outputs = m.get_outputs(_bundle(b, device), patch_size=(b["patch"], b["patch"]), calc_lidar_losses=True)
-    labels = _labels(b, device)
-    metrics = m.get_metrics_dict(outputs, labels)
-    return outputs, m.get_loss_dict(outputs, labels, metrics)
-
-
-def _kind(name):
-    if name.endswith("hash_table"):
-        return "actor_grid" if "actor_grids" in name else "table"
-    if name.startswith("dynamic_actors"):
-        return "trajectory"
-    if name.startswith("camera_optimizer"):
-        return "pose"
-    if name.startswith("rgb_decoder"):
-        return "decoder"
-    if name.startswith("lidar_decoder"):
-        return "lidar_head"
-    if name.startswith("appearance_embedding"):
-        return "embedding"
-    if name.endswith("sdf_to_density.beta"):
-        return "beta"
-    return "mlp"
-
-
-def _analytically_zero(name):
-    """convolution biases that feed a BatchNorm: their gradient is zero in exact arithmetic (rounding noise in fp32)"""
-    return name.startswith("rgb_decoder") and name.endswith((".main_branch.0.bias", ".main_branch.3.bias"))
-
-
-OUTLIER_REL = 1e-4
-
-
-def _outlier_stats(a, c, by_rows):
-    """(# units of ``a`` further than OUTLIER_REL x the largest unit of ``c`` from ``c``, # units ``c`` reaches, squared error
-    and squared norm over the REST).  Unit = a table row (hash tables: a ReLU-kink flip switches one sample's 8 corners x L
-    levels on or off) or an element (everything else)."""
-    a, c = a.detach().double().cpu(), c.detach().double().cpu()
-    if by_rows:
-        diff, mag = (a - c).norm(dim=-1), c.norm(dim=-1)
-    else:
-        diff, mag = (a - c).abs().reshape(-1), c.abs().reshape(-1)
-    out = diff > OUTLIER_REL * float(mag.max())
-    reached = mag > 0
-    rest = ~out
-    return int(out.sum()), int(reached.sum()), float((diff[rest] ** 2).sum()), float((mag[rest] ** 2).sum())
-
-
-def per_loss_gradient_errors(got_model, got_losses, want_model, want_losses, detail=False):
-    """{loss term: {parameter kind: worst rel-L2 over the kind's tensors of d loss / d parameter}} of ``got`` against
-    ``want``, one backward per term of get_loss_dict on either side (also used by oracle/grad_noise_floor.py: the
-    reference in fp32 against itself in fp64).  detail=True: {term: {kind: {"rel_l2", "outlier_frac" (units further than
-    1e-4 of the tensor's largest unit from the reference / units the reference reaches), "rest_rel_l2" (over the other
-    units, pooled over the kind's tensors)}}} -- what separates "a few ReLU-kink flips" from "a wrong gradient"."""
-    names = [n for n, p in want_model.named_parameters() if p.requires_grad and not _analytically_zero(n)]
-    gp, wp = dict(got_model.named_parameters()), dict(want_model.named_parameters())
-    res = {}
-    for term in want_losses:
-        gg = torch.autograd.grad(got_losses[term], [gp[n] for n in names], retain_graph=True, allow_unused=True)
-        wg = torch.autograd.grad(want_losses[term], [wp[n] for n in names], retain_graph=True, allow_unused=True)
-        tot = {}
-        for n, c in zip(names, wg):
-            if c is not None:
-                tot[_kind(n)] = max(tot.get(_kind(n), 0.0), float(c.double().norm()))
-        worst, pooled = {}, {}
-        for n, a, c in zip(names, gg, wg):
-            k = _kind(n)
-            # a tensor this term barely reaches (1e-6 of its kind's largest gradient) carries rounding noise only
-            if c is None or float(c.double().norm()) <= 1e-6 * tot[k]:
-                continue
-            assert a is not None, f"{term}: {n} has a gradient on the reference side and none on the other"
-            if a.dtype == torch.float16:  # fp16-storage table: autograd hands the parameter an fp16 gradient -- held to
-                c = c.half().float()       # the fp16 ROUNDING of the reference's gradient (what that storage can express)
-            e = float((a.detach().double().cpu() - c.detach().double().cpu()).norm() / c.detach().double().norm())
-            worst[k] = max(worst.get(k, 0.0), e)
-            if detail:
-                st = _outlier_stats(a, c, by_rows=k in ("table", "actor_grid"))
-                pooled[k] = [x + y for x, y in zip(pooled.get(k, [0, 0, 0.0, 0.0]), st)]
-        if detail:
-            res[term] = {k: {"rel_l2": worst[k], "outlier_frac": pooled[k][0] / max(pooled[k][1], 1),
-                             "n_outliers": pooled[k][0], "n_units": pooled[k][1],
-                             "rest_rel_l2": (pooled[k][2] / max(pooled[k][3], 1e-300)) ** 0.5} for k in worst}
-        else:
-            res[term] = worst
-    return res
-
-
-def _floors(scene):
-    """the reference's own fp32 noise floor per (loss term, parameter kind): oracle/grad_noise_floor.py ->
-    profiles/r05_grad_noise_floor.json = {scene: {"fp32_vs_fp64": detail, "perturbed_max": detail}}"""
-    import json
-
-    f = os.path.join(ROOT, "profiles", "r05_grad_noise_floor.json")
-    return json.load(open(f))[scene]
-
-
-def check_gradients_against_floor(errs, floors, report_name=None):
-    """Every (loss term, parameter kind) against THAT term's and kind's floor -- the reference's own noise: the larger of its
-    fp32-vs-fp64 rel-L2 and of its rel-L2 against itself with inputs perturbed at the fp32 rounding level (the maximum over
-    ``perturbed_trials`` draws; the noise is heavy-tailed: a ReLU-kink flip of one hidden unit switches one sample's whole
-    contribution on or off, and the two yardsticks differ by up to 6 x on the lidar terms).  Passes when
-      rel-L2 <= max(3 x floor, 1e-4),
-    or, failing that, when the difference looks like the reference's own noise and like nothing else: at most 2 x (+ 2) as
-    many units (table rows / elements) further than 1e-4 of the tensor's largest unit from the reference as the reference
-    shows against itself, and over all OTHER units a rel-L2 <= max(2e-4, 2 x the reference's own over its other units).
-    -> report {term/kind: {...}}, written to gpurun_out/ when ``report_name`` is given."""
-    f64, pert = floors["fp32_vs_fp64"], floors["perturbed_max"]
-    zero = {"rel_l2": 0.0, "outlier_frac": 0.0, "rest_rel_l2": 0.0}
-    report, bad = {}, []
-    for term, kinds in errs.items():
-        for kind, st in kinds.items():
-            fl = f64.get(term, {}).get(kind, zero)
-            pt = pert.get(term, {}).get(kind, zero)
-            floor = max(fl["rel_l2"], pt["rel_l2"])
-            tol = max(3.0 * floor, 1e-4)
-            ref_frac = max(fl["outlier_frac"], pt["outlier_frac"])
-            ref_rest = max(fl["rest_rel_l2"], pt["rest_rel_l2"])
-            ok_direct = st["rel_l2"] <= tol
-            ok_flips = (st["n_outliers"] <= 2.0 * ref_frac * st["n_units"] + 2
-                        and st["rest_rel_l2"] <= max(2e-4, 2.0 * ref_rest))
-            report[f"{term}/{kind}"] = dict(
-                rel_l2=float(f"{st['rel_l2']:.2e}"), bound=float(f"{tol:.2e}"), within_bound=ok_direct,
-                outlier_frac=float(f"{st['outlier_frac']:.2e}"), n_outliers=st["n_outliers"], n_units=st["n_units"],
-                rest_rel_l2=float(f"{st['rest_rel_l2']:.2e}"),
-                reference_fp32_vs_fp64={k: float(f"{fl[k]:.2e}") for k in zero},
-                reference_perturbed_max={k: float(f"{pt[k]:.2e}") for k in zero})
-            if not (ok_direct or ok_flips):
-                bad.append((term, kind, report[f"{term}/{kind}"]))
-    if report_name and os.path.isdir(os.path.join(ROOT, "gpurun_out")):
-        import json
-
-        json.dump(report, open(os.path.join(ROOT, "gpurun_out", report_name), "w"), indent=1)
-    assert not bad, bad
-    return report
 
 
 @pytest.mark.parametrize("with_actors", [False, True], ids=["static", "actors3"])
@@ -467,12 +80,12 @@ def test_plugin_training_step_matches_the_reference_torch_model(ref, with_actors
     at least 1e-4; where a term exceeds it, the excess must sit in as few units as the reference's own noise does and the
     rest must agree as the reference's own rest does).  The floors and the outlier statistics of the reference against itself: oracle/grad_noise_floor.py ->
     profiles/r05_grad_noise_floor.json; this test's statistics on the GPU: profiles/r05_grad_outliers_*.json."""
-    hip, refm = _build_pair(ref, with_actors)
-    b = _batch(with_actors)
-    _deterministic(hip, True), _deterministic(refm, True)
+    hip, refm = t.build_pair(ref, with_actors)
+    b = t.batch(with_actors)
+    t.deterministic(hip, True), t.deterministic(refm, True)
     assert hip.fused_training_possible()  # the fused nodes (static: ProposalRoundFn / NffRenderTrainFn; actors: OVR)
-    g_out, g_loss = _losses(hip, b, "cuda")
-    w_out, w_loss = _losses(refm, b, "cpu")
+    g_out, g_loss = t.losses(hip, b, "cuda")
+    w_out, w_loss = t.losses(refm, b, "cpu")
     assert set(g_loss) == set(w_loss), (sorted(g_loss), sorted(w_loss))
     for k in w_loss:
         a, c = float(g_loss[k]), float(w_loss[k])
@@ -481,7 +94,7 @@ def test_plugin_training_step_matches_the_reference_torch_model(ref, with_actors
         assert rel_l2(N(g_out[k]), N(w_out[k])) < 1e-4, (k, rel_l2(N(g_out[k]), N(w_out[k])))
     errs = per_loss_gradient_errors(hip, g_loss, refm, w_loss, detail=True)
     scene = "actors3" if with_actors else "static"
-    report = check_gradients_against_floor(errs, _floors(scene), f"r05_grad_outliers_{scene}.json")
+    report = check_gradients_against_floor(errs, t.floors(scene), f"r05_grad_outliers_{scene}.json")
     seen = {k for kinds in errs.values() for k in kinds}
     need = {"table", "mlp", "beta", "embedding", "lidar_head", "decoder"} | ({"actor_grid", "trajectory"} if with_actors
                                                                              else set())
@@ -504,16 +117,16 @@ def test_plugin_pose_gradients_match_the_reference_torch_model(ref, with_actors)
     static table, both proposal rounds' tables and (actor scene) the box-frame positions of the in-box samples.  The plugin
     hands the rays that gradient from nrhip_encode_bwd_rays / nrhip_actor_pair_positions_bwd_rays; it is held to the
     reference model's, per loss term, like every other parameter kind -- and the ray gradients themselves as well."""
-    hip, refm = _build_pair(ref, with_actors, pose_opt=True)
-    b = _batch(with_actors)
-    _deterministic(hip, True), _deterministic(refm, True)
+    hip, refm = t.build_pair(ref, with_actors, pose_opt=True)
+    b = t.batch(with_actors)
+    t.deterministic(hip, True), t.deterministic(refm, True)
     assert hip.fused_training_possible()
 
     def step(m, device):
         m.zero_grad(set_to_none=True)
-        rb = _bundle(b, device)
+        rb = t.bundle(b, device)
         out = m.get_outputs(rb, patch_size=(b["patch"], b["patch"]), calc_lidar_losses=True)
-        labels = _labels(b, device)
+        labels = t.labels(b, device)
         return rb, out, m.get_loss_dict(out, labels, m.get_metrics_dict(out, labels))
 
     g_rb, g_out, g_loss = step(hip, "cuda")
@@ -531,10 +144,10 @@ def test_plugin_pose_gradients_match_the_reference_torch_model(ref, with_actors)
     ray_err = [rel_l2(N(a), N(c)) for a, c in zip(gs, ws)]
     errs = per_loss_gradient_errors(hip, g_loss, refm, w_loss, detail=True)
     scene = ("actors3" if with_actors else "static") + "_pose"
-    report = check_gradients_against_floor(errs, _floors(scene), f"r05_grad_outliers_{scene}.json")
+    report = check_gradients_against_floor(errs, t.floors(scene), f"r05_grad_outliers_{scene}.json")
     reached = [t for t, kinds in errs.items() if "pose" in kinds]
     assert {"rgb_loss", "interlevel_loss", "depth_loss", "camera_opt_regularizer"} <= set(reached), reached
-    fl = _floors(scene)["fp32_vs_fp64"]["__ray_grads__"]
+    fl = t.floors(scene)["fp32_vs_fp64"]["__ray_grads__"]
     print("ray gradients (origins, directions) rel-L2:", ray_err, "reference fp32 vs fp64:", fl,
           "pose:", {k: (v["rel_l2"], v["bound"]) for k, v in report.items() if k.endswith("/pose")})
     for e, f in zip(ray_err, fl):
@@ -546,13 +159,13 @@ def test_plugin_training_step_32_actors_fp16_tables_matches_the_reference_torch_
     the main field's static table and its 32 actor grids in fp16 storage on the plugin, the reference's fp32 tables holding
     the same (rounded) values -- outputs, every loss term, every parameter gradient per loss term (actor grids and
     trajectories included; fp16 gradients against the fp16 rounding of the reference's)."""
-    hip, refm = _build_pair(ref, True, n_actors=32, fp16_tables=True)
-    b = _batch(True, n_actors=32)
-    _deterministic(hip, True), _deterministic(refm, True)
+    hip, refm = t.build_pair(ref, True, n_actors=32, fp16_tables=True)
+    b = t.batch(True, n_actors=32)
+    t.deterministic(hip, True), t.deterministic(refm, True)
     assert hip.fused_training_possible()
     assert hip.field.hashgrid.static_grid.hash_table.dtype == torch.float16 and len(hip.field.hashgrid.actor_grids) == 32
-    g_out, g_loss = _losses(hip, b, "cuda")
-    w_out, w_loss = _losses(refm, b, "cpu")
+    g_out, g_loss = t.losses(hip, b, "cuda")
+    w_out, w_loss = t.losses(refm, b, "cpu")
     assert set(g_loss) == set(w_loss)
     for k in w_loss:
         a, c = float(g_loss[k]), float(w_loss[k])
@@ -560,7 +173,7 @@ def test_plugin_training_step_32_actors_fp16_tables_matches_the_reference_torch_
     for k in ("rgb", "depth", "accumulation", "intensity", "ray_drop_logits", "prop_depth_0", "prop_depth_1"):
         assert rel_l2(N(g_out[k]), N(w_out[k])) < 1e-4, (k, rel_l2(N(g_out[k]), N(w_out[k])))
     errs = per_loss_gradient_errors(hip, g_loss, refm, w_loss, detail=True)
-    report = check_gradients_against_floor(errs, _floors("actors32"), "r05_grad_outliers_actors32_fp16.json")
+    report = check_gradients_against_floor(errs, t.floors("actors32"), "r05_grad_outliers_actors32_fp16.json")
     seen = {k for kinds in errs.values() for k in kinds}
     assert {"table", "mlp", "actor_grid", "trajectory", "beta", "embedding"} <= seen, seen
     # many actors really take part (this batch: 10 of the 32 grids receive a gradient, several boxes along most rays)
@@ -578,15 +191,15 @@ def test_plugin_training_step_with_the_hip_rgb_decoder(ref):
     own path -- the SAME torch modules under torch.autocast(fp16) with the GradScaler's loss scale on the GPU: against the
     reference's fp32 CPU model the HIP decoder may not be further off than 1.5 x what that is (+ a floor): output, loss and
     every decoder gradient."""
-    hip, refm = _build_pair(ref, False, fused_decoder=True)
-    b = _batch(False, patch=8, n_patches=3, n_lidar=24)  # 24 x 24 px patches: BatchNorm statistics over > 1000 pixels
-    _deterministic(hip, True), _deterministic(refm, True)
-    w_out, w_loss = _losses(refm, b, "cpu")
+    hip, refm = t.build_pair(ref, False, fused_decoder=True)
+    b = t.batch(False, patch=8, n_patches=3, n_lidar=24)  # 24 x 24 px patches: BatchNorm statistics over > 1000 pixels
+    t.deterministic(hip, True), t.deterministic(refm, True)
+    w_out, w_loss = t.losses(refm, b, "cpu")
     sum(w_loss.values()).backward()
-    want = {n: p.grad for n, p in refm.named_parameters() if n.startswith("rgb_decoder") and not _analytically_zero(n)}
+    want = {n: p.grad for n, p in refm.named_parameters() if n.startswith("rgb_decoder") and not t.analytically_zero(n)}
 
     def run(loss_scale=1.0):
-        out, loss = _losses(hip, b, "cuda")
+        out, loss = t.losses(hip, b, "cuda")
         (sum(loss.values()) * loss_scale).backward()
         return out, loss
 
@@ -674,7 +287,7 @@ def _sample_level_gradients(hip, refm, b, terms):
              refm.field.mlp_feature.layers[1].register_forward_hook(lambda m, i, o: pre.__setitem__("feat1", o.detach()))]
     hg.forward, hg._get_actor_indices, con.forward = spy_fwd, spy_idx, spy_con
     try:
-        w_out, w_loss = _losses(refm, b, "cpu")
+        w_out, w_loss = t.losses(refm, b, "cpu")
     finally:
         hg.forward, hg._get_actor_indices, con.forward = real_fwd, real_idx, real_con
         for h in hooks:
@@ -710,7 +323,7 @@ def _sample_level_gradients(hip, refm, b, terms):
     ag.ops.mlp_bwd = spy_mlp_bwd
     ag.ActorPairPositionsFn.forward, ag.ActorPairPositionsFn.backward = staticmethod(spy_pf), staticmethod(spy_pb)
     try:
-        g_out, g_loss = _losses(hip, b, "cuda")
+        g_out, g_loss = t.losses(hip, b, "cuda")
         hp = [p for p in hip.parameters() if p.requires_grad]
         for term in terms:
             rec.pop("rows", None), rec.pop("gpos", None)
@@ -822,9 +435,9 @@ def test_every_gradient_outlier_has_a_class(ref, scene):
     their cause at the SAMPLE level: each differing sample is a ReLU-kink sample or a duplicate-index sample, each differing
     pair position gradient sits on a lattice plane of an actor grid or inherits from such a sample; anything else fails."""
     big = scene == "actors32_fp16"
-    hip, refm = _build_pair(ref, True, n_actors=32 if big else 3, fp16_tables=big)
-    b = _batch(True, n_actors=32 if big else 3)
-    _deterministic(hip, True), _deterministic(refm, True)
+    hip, refm = t.build_pair(ref, True, n_actors=32 if big else 3, fp16_tables=big)
+    b = t.batch(True, n_actors=32 if big else 3)
+    t.deterministic(hip, True), t.deterministic(refm, True)
     terms = ["rgb_loss", "distortion_loss", "depth_loss", "intensity_loss", "carving_loss", "ray_drop_loss"]
     rep = classify_gradient_outliers(hip, refm, b, terms, f"r06_grad_outlier_classes_{scene}.json")
     print(scene, {t_: {k: v for k, v in e.items() if k != "unclassified"} for t_, e in rep.items()})
@@ -837,16 +450,16 @@ def test_plugin_training_step_in_the_non_default_modes_runs_fused_and_matches_th
     for the final samples and both proposal rounds) ran on the operator-level path up to round 5; round 6: the fused
     training nodes cover them (the density head inside nrhip_sdf_render_fwd/bwd, the normalisation over the nodes' outputs).
     Same checks as the default-mode step: every loss term, the outputs, every parameter gradient per loss term."""
-    hip, refm = _build_pair(ref, False, use_sdf="density" not in mode, normalize_depth="normalize_depth" in mode)
-    b = _batch(False)
-    _deterministic(hip, True), _deterministic(refm, True)
+    hip, refm = t.build_pair(ref, False, use_sdf="density" not in mode, normalize_depth="normalize_depth" in mode)
+    b = t.batch(False)
+    t.deterministic(hip, True), t.deterministic(refm, True)
     if "density" in mode:  # a translucent medium: raw densities around exp(-1.5) per metre
         with torch.no_grad():
             for m in (hip, refm):
                 m.field.mlp_geo.layers[-1].bias[0] = -1.5
     assert hip.fused_training_possible()
-    g_out, g_loss = _losses(hip, b, "cuda")
-    w_out, w_loss = _losses(refm, b, "cpu")
+    g_out, g_loss = t.losses(hip, b, "cuda")
+    w_out, w_loss = t.losses(refm, b, "cpu")
     assert set(g_loss) == set(w_loss)
     for k in w_loss:
         a, c = float(g_loss[k]), float(w_loss[k])
@@ -854,7 +467,7 @@ def test_plugin_training_step_in_the_non_default_modes_runs_fused_and_matches_th
     for k in ("rgb", "depth", "accumulation", "intensity", "ray_drop_logits", "prop_depth_0", "prop_depth_1"):
         assert rel_l2(N(g_out[k]), N(w_out[k])) < 1e-4, (k, rel_l2(N(g_out[k]), N(w_out[k])))
     errs = per_loss_gradient_errors(hip, g_loss, refm, w_loss, detail=True)
-    check_gradients_against_floor(errs, _floors("static"))
+    check_gradients_against_floor(errs, t.floors("static"))
     seen = {k for kinds in errs.values() for k in kinds}
     assert {"table", "mlp", "embedding", "lidar_head", "decoder"} <= seen and ("beta" in seen) == ("density" not in mode)
     # ... and tight in absolute terms on the terms that reach every parameter (the density head's exp amplifies the ReLU-kink

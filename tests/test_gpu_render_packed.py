@@ -17,7 +17,9 @@ import neurad_oracle as O
 import packed_restatement as PR
 import synth
 from conftest import rel_l2
-from test_gpu_parity import TOL, dev, field_params, host, to_spec
+from builders import field_params
+from gpu_util import TOL, dev, host, make_field, ray_bundle, to_spec
+from gpu_util import ops  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,19 +29,10 @@ RAGGED = [0, 1, 15, 16, 17, 0, 0, 31, 32, 33, 48, 2, 64, 65, 130, 1, 0, 16, 16, 
 LG = 11  # T = 2^11 per level: seconds per test
 
 
-@pytest.fixture(scope="module")
-def ops():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from neurad_studio_amd import ops as _ops
-
-    return _ops
-
-
 def params(L, F, H, use_sdf, beta=3.0, scale=None):
     """field_params for any fused grid: geo layer 0 takes L * F inputs"""
     p = field_params(use_sdf=use_sdf, L=L, F=F, lg=LG, H=H, mn=16, mx=1024, scale=(2.0 if use_sdf else 0.5) if scale is None else scale)
-    if L * F != 32:
-        p.geo_w[0] = synth.linear(H, L * F, 200)[0]
+    p.geo_b[0] = synth.linear(H, 32, 200)[1]  # this bias keeps the range of a 32-input layer whatever L * F is
     if use_sdf:
         p.beta = beta  # keeps alpha off saturation so that the compositing is exercised
     return p
@@ -247,7 +240,6 @@ def test_volumetric_sampler_render(ops, use_sdf, monkeypatch):
     from neurad_studio_amd.model_components.ray_samplers import VolumetricSampler
     from neurad_studio_amd.model_components.renderers import render_packed
     from neurad_studio_amd.shims.nerfacc import OccGridEstimator
-    from test_gpu_packed import make_field, ray_bundle
 
     R = 96
     est = OccGridEstimator([-5, -5, -5, 5, 5, 5], resolution=16)

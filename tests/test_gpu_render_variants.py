@@ -7,17 +7,11 @@ import torch
 
 import neurad_oracle as O
 from conftest import rel_l2
-from test_gpu_parity import RENDER_CFGS, TOL, _sample_rays, dev, field_params, host, to_spec
+from builders import RENDER_CFGS, field_params, sample_rays
+from gpu_util import TOL, dev, host, to_spec
+from gpu_util import ops  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ops():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from neurad_studio_amd import ops as _ops
-
-    return _ops
 
 
 def test_ray_order_is_a_permutation_grouped_by_region(ops):
@@ -129,7 +123,7 @@ def test_render_with_processing_order_vs_oracle(ops, cfg, ordered):
     if use_sdf:
         p.beta = 3.0
     fs = to_spec(ops, p)
-    o, d, area, s, e, eu = _sample_rays(R, S, seed=R + S)
+    o, d, area, s, e, eu = sample_rays(R, S, seed=R + S)
     ref = O.render_rays(p, o, d, area, s, e)
     edges = dev(eu)
     order = ops.ray_order(dev(o), dev(d), p.static_scale) if ordered else None
@@ -149,7 +143,7 @@ def test_order_never_changes_results_more_rays_than_waves(ops):
     p.beta = 2.0
     fs = to_spec(ops, p)
     R, S = 9000, 37
-    o, d, area, s, e, eu = _sample_rays(R, S, seed=3)
+    o, d, area, s, e, eu = sample_rays(R, S, seed=3)
     edges, do, dd, da = dev(eu), dev(o), dev(d), dev(area)
     orders = [None, ops.ray_order(do, dd, p.static_scale), torch.randperm(R, device="cuda").to(torch.int32),
               torch.arange(R - 1, -1, -1, device="cuda", dtype=torch.int32)]
@@ -181,7 +175,7 @@ def test_early_ray_termination_bounded(ops, use_sdf):
         p.beta = 6.0  # alphas around 0.5: transmittance falls below 1e-3 after a dozen samples
     R, S = 300, 96
     eps = 1e-3
-    o, d, area, s, e, eu = _sample_rays(R, S, seed=21)
+    o, d, area, s, e, eu = sample_rays(R, S, seed=21)
     # density head: shift the logit until the medium is opaque enough to cut rays but not so dense that the exact
     # weights underflow to 0 on their own
     for bump in (0.0, -3.0, -2.0, -1.0, 1.0, 2.0, 3.0):
@@ -230,7 +224,7 @@ def test_split_bf16_matrix_products_are_fp32_equivalent(switches):
         p = field_params(L=L, F=F, lg=12, H=64, mn=mn, mx=mx)
         fs = to_spec(ops, p)
         R, S = 300, 72
-        o, d, area, s, e, _ = _sample_rays(R, S, seed=11)
+        o, d, area, s, e, _ = sample_rays(R, S, seed=11)
         args = (fs, dev(o), dev(d), dev(area), dev(s), dev(e))
         switches.unset("NRHIP_MLP_SPLIT_BF16")
         switches.set("NRHIP_MLP_PAIRS", "0")  # (the default since round 5 is the fp16-pair form, tested below)
@@ -255,7 +249,7 @@ def test_fp16_pair_matrix_products_are_fp32_equivalent(switches):
     from neurad_studio_amd import ops
 
     R, S = 300, 72
-    o, d, area, s, e, _ = _sample_rays(R, S, seed=11)
+    o, d, area, s, e, _ = sample_rays(R, S, seed=11)
     rays = (dev(o), dev(d), dev(area), dev(s), dev(e))
 
     def both(fs):
@@ -309,7 +303,7 @@ def test_fp16_pair_products_in_the_training_forward(switches):
     from neurad_studio_amd import ops
 
     R, S = 200, 32
-    o, d, area, s, e, _ = _sample_rays(R, S, seed=13)
+    o, d, area, s, e, _ = sample_rays(R, S, seed=13)
     rays = (dev(o), dev(d), dev(area), dev(s), dev(e))
 
     def both(fs):

@@ -7,11 +7,10 @@ starts from its own hash tables and MLP weights, applies the same averaged gradi
 converge to one model (only rank 0's copy is checkpointed).
 
 Two ranks share cuda:0 and exchange over gloo; each is seeded as the reference seeds it and built through
-``TrainerConfig.setup`` -> ``trainer.setup()`` on the synthetic drive of tests/test_gpu_plugin_pipeline.py (3 cameras, 2 lidar
+``TrainerConfig.setup`` -> ``trainer.setup()`` on the synthetic drive of tests/plugin_harness.py (3 cameras, 2 lidar
 sweeps, 3 actors).  Nothing writes the same values on both ranks: only the pipeline can make them equal.  The parent
 process does not touch the GPU."""
 import os
-import socket
 import sys
 
 import pytest
@@ -20,17 +19,12 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import ref_import  # noqa: E402
+from gpu_util import free_port  # noqa: E402
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not ref_import.reference_available(), reason="no reference (oracle/_ref ships with the lease)")]
 
 K = 3
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _cpu(t):
@@ -52,7 +46,7 @@ def _worker(rank, world, port, root, table_dtype, ret):
     import nerfstudio.models.neurad as ref_neurad
     from nerfstudio.pipelines.ad_pipeline import ADPipeline
 
-    import test_gpu_plugin_pipeline as P
+    import plugin_harness as P
     from neurad_studio_amd.integration.pipeline import ADHipPipeline
     from neurad_studio_amd.integration.trainer import HipTrainer
     from neurad_studio_amd.optim import HashGridAdam, TableGradScaler
@@ -60,7 +54,7 @@ def _worker(rank, world, port, root, table_dtype, ret):
     ref_neurad.VGGPerceptualLossPix2Pix = torch.nn.Identity  # (loss.vgg_mult = 0 at test size; no weights to load)
     data = Path(root) / f"rank{rank}"
     data.mkdir(parents=True)
-    cfg = P._method_config(data)
+    cfg = P.method_config(data)
     cfg.pipeline.model.table_dtype = table_dtype
     cfg.output_dir, cfg.experiment_name, cfg.timestamp = data / "outputs", "synthetic-drive", "run"
     cfg.vis = "none"
@@ -120,7 +114,7 @@ def test_ranks_seeded_apart_train_one_model(table_dtype, tmp_path):
     world = 2
     with mp.Manager() as mgr:
         ret = mgr.dict()
-        mp.spawn(_worker, args=(world, _free_port(), str(tmp_path), table_dtype, ret), nprocs=world, join=True)
+        mp.spawn(_worker, args=(world, free_port(), str(tmp_path), table_dtype, ret), nprocs=world, join=True)
         res = {k: ret[k] for k in ret.keys()}
     built0, built1, setup0, setup1 = res["built0"], res["built1"], res["setup0"], res["setup1"]
     table = "field.hashgrid.static_grid.hash_table"

@@ -7,143 +7,15 @@ a product that passes through the subnormals (< 2^-126) keeps no relative precis
 gradient anyone uses.  A whole-tensor rel-L2 is dominated by the largest entries and would not see one wrong ray."""
 import numpy as np
 import pytest
-import torch
 
 import neurad_oracle as O
 import synth
-from test_gpu_field_shapes import shape_params, to_spec
+from builders import sample_rays, shape_params
+from gpu_util import dev, host64, to_spec
+from gpu_util import ops  # noqa: F401  (fixture)
+from sharp_refs import R, SAMPLES, TINY, U, check, ref_alpha, ref_density, sharp_alphas, sharp_bins
 
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -24  # fp32 unit roundoff
-TINY = 2.0 ** -126  # fp32's smallest normal number
-ONE_BELOW = np.float32(1.0 - 2.0 ** -24)  # the largest fp32 below 1
-R = 13  # not a multiple of the 4 rays per workgroup
-SAMPLES = [1, 16, 63, 64, 65, 130]  # one sample, one chunk, the 64-sample carry and the ragged last chunk
-
-
-@pytest.fixture(scope="module")
-def ops():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from neurad_studio_amd import ops as _ops
-
-    return _ops
-
-
-def dev(a, dtype=torch.float32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
-
-
-def host(t):
-    return t.detach().cpu().numpy().astype(np.float64)
-
-
-def f64(a):
-    return torch.tensor(np.asarray(a, np.float64), dtype=torch.float64)
-
-
-def check(got, ref, bound, what):
-    """per element: finite wherever the reference is, and |got - ref| <= bound"""
-    got, ref, bound = (np.broadcast_to(np.asarray(v, np.float64), np.shape(got)) for v in (got, ref, bound))
-    fin = np.isfinite(ref)
-    bad_inf = fin & ~np.isfinite(got)
-    assert not bad_inf.any(), f"{what}: non-finite where the reference is finite at {np.argwhere(bad_inf)[:5].tolist()}"
-    err = np.where(fin, np.abs(got - ref), 0.0)
-    over = err > bound
-    if over.any():
-        k = tuple(np.argwhere(over)[0])
-        raise AssertionError(f"{what}: {int(over.sum())} elements off, first {k}: got {got[k]!r} want {ref[k]!r} "
-                             f"bound {bound[k]!r} (max err/bound {float((err / np.maximum(bound, 1e-300)).max()):.3g})")
-
-
-# ---- inputs -----------------------------------------------------------------------------------------------------------
-def sharp_alphas(S, seed):
-    """rays of ordinary alphas with exact 1, 1 - 2^-24 and exact 0 sprinkled in, and rays with runs of each; one ray with
-    no special value at all (the path the kernels took before), one ray opaque from its first sample on"""
-    a = synth.uniform((R, S), 0.0, 1.0, seed)
-    pick = synth.uniform((R, S), 0.0, 1.0, seed + 1)
-    a = np.where(pick < 0.06, np.float32(1.0), a)
-    a = np.where((pick >= 0.06) & (pick < 0.14), ONE_BELOW, a)
-    a = np.where((pick >= 0.14) & (pick < 0.24), np.float32(0.0), a)
-    a = np.where((pick >= 0.24) & (pick < 0.5), a * np.float32(1e-3), a)
-    lo, hi = S // 3, S // 3 + max(1, S // 4)
-    a[1, lo:hi] = 1.0
-    a[2, lo:hi] = ONE_BELOW
-    a[3, lo:hi] = 0.0
-    a[4, lo:] = ONE_BELOW  # transmittance through the subnormals to 0 without an exact zero factor
-    a[5] = synth.uniform((S,), 0.0, 0.2, seed + 2)
-    a[6, 0] = 1.0
-    a[7, -1] = 1.0
-    a[8, : S // 2] = 0.0
-    a[8, S // 2] = 1.0
-    return np.ascontiguousarray(a, np.float32)
-
-
-def sharp_bins(S, seed):
-    """(starts, ends, sigmas): sigma * delta from 1e-4 past 88 (exp underflows), zero-length bins, a sky bin at 1e10"""
-    e = np.cumsum(synth.uniform((R, S + 1), 0.0, 2.0, seed), -1).astype(np.float32)
-    zero = synth.uniform((R, S), 0, 1, seed + 1) < 0.15
-    for s in range(S):  # zero-length bins: e[s+1] == e[s]
-        e[:, s + 1] = np.where(zero[:, s], e[:, s], np.maximum(e[:, s + 1], e[:, s]))
-    e[::3, -1] = 1e10  # sky
-    sig = np.exp(synth.uniform((R, S), -9.0, 5.0, seed + 2)).astype(np.float32)
-    big = synth.uniform((R, S), 0, 1, seed + 3) < 0.1
-    sig = np.where(big, np.float32(200.0), sig)  # sigma * delta > 88 wherever delta > 0.44
-    sig[1] = 1e-3
-    st, en = np.ascontiguousarray(e[:, :-1]), np.ascontiguousarray(e[:, 1:])
-    return st, en, np.ascontiguousarray(sig), e
-
-
-# ---- float64 references -----------------------------------------------------------------------------------------------
-def excl_trans(a):
-    return torch.cumprod(torch.cat([torch.ones_like(a[:, :1]), 1 - a[:, :-1]], -1), -1)
-
-
-def ref_alpha(a32, gw, gt):
-    """nerfacc dense render_weight_from_alpha (cumprod) in float64 autograd -> w, T, dL/dalpha, mag(dL/dalpha)"""
-    a = f64(a32).requires_grad_(True)
-    T = excl_trans(a)
-    w = a * T
-    (w * f64(gw) + T * f64(gt)).sum().backward()
-    # the same with |upstream|: d/da_i sum(|gw| w + |gt| T) = |gw_i| T_i - sum_{k>i} |G_k| prod_{j<k, j!=i}(1 - a_j), so
-    # |gw_i| T_i + sum_{k>i} |G_k| prod(...) = 2 |gw_i| T_i - that
-    b = f64(a32).requires_grad_(True)
-    Tb = excl_trans(b)
-    (b * Tb * f64(np.abs(gw)) + Tb * f64(np.abs(gt))).sum().backward()
-    mag = 2 * np.abs(gw) * T.detach().numpy() - b.grad.numpy()
-    return w.detach().numpy(), T.detach().numpy(), a.grad.numpy(), mag
-
-
-def suffix_excl(v):
-    """sum_{k>i} v_k in float64, summed from the end: its rounding is relative to the suffix's own terms"""
-    return np.concatenate([np.flip(np.cumsum(np.flip(v[:, 1:], -1), -1), -1), np.zeros_like(v[:, :1])], -1)
-
-
-def ref_density(delta32, sig32, gw):
-    """render_weight_from_density in float64 (sd = sigma * delta) -> w, T, alpha, dL/dsigma, and the per-element error
-    scale of the fp32 kernels: T = exp(-(sum of sd)) carries the sum's absolute rounding (S u sum sd) as a relative
-    error, alpha = 1 - exp(-sd) an absolute one (2u), and the suffix sum of the backward S u of its terms' magnitudes.
-    dL/dsigma_i = delta_i (gw_i T_i e^(-sd_i) - sum_{k>i} gw_k w_k) is written out rather than taken from autograd: torch's
-    float64 backward of the exclusive cumsum leaves ~2^-53 of the ray's LARGEST term in every entry, more than the
-    1e-24-sized gradients behind an opaque sample that this test holds the kernels to."""
-    S = sig32.shape[1]
-    dl = np.asarray(delta32, np.float64)
-    sd = np.asarray(sig32, np.float64) * dl
-    cinn = np.cumsum(sd, -1)
-    cexn = np.concatenate([np.zeros_like(sd[:, :1]), cinn[:, :-1]], -1)
-    Tn = np.exp(-cexn)
-    an = -np.expm1(-sd)
-    w = an * Tn
-    g = np.asarray(gw, np.float64)
-    head = g * Tn * np.exp(-sd)
-    grad = dl * (head - suffix_excl(g * w))
-    ag = np.abs(g)
-    e_head = ag * Tn * np.exp(-sd) * (1 + cinn)
-    e_term = ag * Tn * (an * (1 + cexn) + 1.0 / (S + 4))
-    gscale = 4 * (S + 4) * U * dl * (e_head + suffix_excl(e_term))
-    fscale = 4 * (S + 4) * U * Tn * (1 + cexn)
-    return w, Tn, an, grad, fscale, gscale
-
 
 # ---- the compositing ops ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("S", SAMPLES)
@@ -156,15 +28,15 @@ def test_render_weight_from_alpha_saturated(ops, S):
     w, t = ops.render_weight_from_alpha(dev(a))
     rw, rt, rga, mag = ref_alpha(a, gw, gt)
     rtol = 2 * (S + 2) * U  # S - 1 products per transmittance, one more for the weight
-    check(host(w), rw, TINY + rtol * rw, "weights")
-    check(host(t), rt, TINY + rtol * rt, "trans")
+    check(host64(w), rw, TINY + rtol * rw, "weights")
+    check(host64(t), rt, TINY + rtol * rt, "trans")
     # the forward is one product scan: exact zeros stay exact zeros, and the ray without special values is untouched
-    assert (host(w)[a == 0] == 0).all() and (host(t)[:, 1:][np.cumsum(a == 1, -1)[:, :-1] > 0] == 0).all()
-    ga = host(ops.render_weight_from_alpha_bwd(dev(a), dev(gw), dev(gt)))
+    assert (host64(w)[a == 0] == 0).all() and (host64(t)[:, 1:][np.cumsum(a == 1, -1)[:, :-1] > 0] == 0).all()
+    ga = host64(ops.render_weight_from_alpha_bwd(dev(a), dev(gw), dev(gt)))
     gscale = np.abs(gw).max(-1, keepdims=True) + np.abs(gt).max(-1, keepdims=True)
     # T_k's S products, the term's product, the S-term suffix sum, the division, the subtraction
     check(ga, rga, 2.0 ** -100 * gscale + 4 * (S + 8) * U * mag, "dL/dalpha")
-    ga0 = host(ops.render_weight_from_alpha_bwd(dev(a), dev(gw)))  # grad_t = None
+    ga0 = host64(ops.render_weight_from_alpha_bwd(dev(a), dev(gw)))  # grad_t = None
     _, _, rga0, mag0 = ref_alpha(a, gw, np.zeros_like(gt))
     check(ga0, rga0, 2.0 ** -100 * gscale + 4 * (S + 8) * U * mag0, "dL/dalpha (no grad_t)")
 
@@ -177,15 +49,15 @@ def test_render_weight_from_density_saturated(ops, S):
     gw = synth.normal((R, S), 50 + S)
     rw, rt, ra, rgs, fscale, gscale = ref_density(delta, sig, gw)
     w, t, a = ops.render_weight_from_density(dev(st), dev(en), dev(sig))
-    check(host(w), rw, TINY + fscale, "weights")
-    check(host(t), rt, TINY + fscale, "trans")
-    check(host(a), ra, TINY + 4 * U, "alphas")
-    gs = host(ops.render_weight_from_density_bwd(dev(st), dev(en), dev(sig), dev(gw)))
+    check(host64(w), rw, TINY + fscale, "weights")
+    check(host64(t), rt, TINY + fscale, "trans")
+    check(host64(a), ra, TINY + 4 * U, "alphas")
+    gs = host64(ops.render_weight_from_density_bwd(dev(st), dev(en), dev(sig), dev(gw)))
     atol = TINY * (delta.astype(np.float64) + 1) * np.abs(gw).max(-1, keepdims=True)
     check(gs, rgs, atol + gscale, "dL/dsigma")
-    w2 = host(ops.weights_from_density(dev(delta), dev(sig)))
+    w2 = host64(ops.weights_from_density(dev(delta), dev(sig)))
     check(w2, rw, TINY + fscale, "weights_from_density")
-    gs2 = host(ops.weights_from_density_bwd(dev(delta), dev(sig), dev(gw)))
+    gs2 = host64(ops.weights_from_density_bwd(dev(delta), dev(sig), dev(gw)))
     check(gs2, rgs, atol + gscale, "weights_from_density_bwd")
 
 
@@ -200,14 +72,14 @@ def test_prop_weights_saturated(ops, S):
     gw, gd = synth.normal((R, S), 70 + S), synth.normal((R, 1), 71 + S)
     rw, _, _, _, fscale, _ = ref_density(delta, dens, gw)
     w, depth = ops.prop_weights_fwd(dev(e), dev(dens))
-    check(host(w), rw, TINY + fscale, "weights")
+    check(host64(w), rw, TINY + fscale, "weights")
     rdepth = (rw * mid).sum(-1, keepdims=True)
-    check(host(depth), rdepth, TINY + ((fscale + S * U * rw) * np.abs(mid)).sum(-1, keepdims=True), "depth")
+    check(host64(depth), rdepth, TINY + ((fscale + S * U * rw) * np.abs(mid)).sum(-1, keepdims=True), "depth")
     # backward: the upstream of each weight is gw + g_depth * mid
     G = gw.astype(np.float64) + gd.astype(np.float64) * mid
     _, _, _, rgs, _, gscale = ref_density(delta, dens, G)
     _, _, _, _, _, gscale2 = ref_density(delta, dens, np.abs(gw) + np.abs(gd * mid))
-    gs = host(ops.prop_weights_bwd(dev(e), dev(dens), dev(gw), dev(gd)))
+    gs = host64(ops.prop_weights_bwd(dev(e), dev(dens), dev(gw), dev(gd)))
     atol = TINY * (delta.astype(np.float64) + 1) * np.abs(G).max(-1, keepdims=True)
     check(gs, rgs, atol + gscale + gscale2, "dL/ddensity")
 
@@ -234,22 +106,22 @@ def test_composite_saturated(ops, S, C):
     w2, rf, rd, ra, mid = ref_composite(w, feats, st, en)
     of, od, oa = ops.composite_fwd(dev(w), dev(feats), dev(st), dev(en))
     sw = w.astype(np.float64).sum(-1, keepdims=True)
-    check(host(oa), ra, 2 * S * U * sw, "acc")
+    check(host64(oa), ra, 2 * S * U * sw, "acc")
     absf = np.abs(feats.astype(np.float64))
     fb = 2 * (S + 4) * U * ((np.abs(w2)[..., None] * absf).sum(1) + (1 + sw) * absf[:, -1])
-    check(host(of), rf, fb, "features")
-    check(host(od), rd, 2 * (S + 2) * U * (np.abs(w2[:, :-1]) * np.abs(mid[:, :-1])).sum(-1, keepdims=True), "depth")
+    check(host64(of), rf, fb, "features")
+    check(host64(od), rd, 2 * (S + 2) * U * (np.abs(w2[:, :-1]) * np.abs(mid[:, :-1])).sum(-1, keepdims=True), "depth")
     gF, gD, gA = synth.normal((R, C), 83), synth.normal((R, 1), 84), synth.normal((R, 1), 85)
     gw, gf = ops.composite_bwd(dev(w), dev(feats), dev(st), dev(en), dev(gF), dev(gD), dev(gA))
     # df_sc = w2_s gF_c ; dw_s = q_s - q_{S-1} + g_acc + g_depth mid_s [s < S-1],  q_s = sum_c gF_c f_sc
     gF64 = gF.astype(np.float64)
     rgf = w2[..., None] * gF64[:, None, :]
-    check(host(gf), rgf, 2 * (S + 2) * U * (np.abs(rgf) + (1 + sw)[..., None] * np.abs(gF64)[:, None, :]), "d features")
+    check(host64(gf), rgf, 2 * (S + 2) * U * (np.abs(rgf) + (1 + sw)[..., None] * np.abs(gF64)[:, None, :]), "d features")
     q = (feats.astype(np.float64) * gF64[:, None, :]).sum(-1)
     qm = (absf * np.abs(gF64)[:, None, :]).sum(-1)
     dm = np.where(np.arange(S)[None] < S - 1, mid, 0.0)
     rgw = q - q[:, -1:] + gA + gD * dm
-    check(host(gw), rgw, 2 * (C + 4) * U * (qm + qm[:, -1:] + np.abs(gA) + np.abs(gD * dm)), "d weights")
+    check(host64(gw), rgw, 2 * (C + 4) * U * (qm + qm[:, -1:] + np.abs(gA) + np.abs(gD * dm)), "d weights")
 
 
 @pytest.mark.parametrize("pair", ["0", "1"])
@@ -273,7 +145,7 @@ def test_sdf_render_saturated(ops, switches, S, pair):
     beta = dev(np.array([beta_raw], np.float32))
     a, w_ns, out, depth, acc = ops.sdf_render_fwd(dev(sdf), beta, 0.1, dev(feats), dev(e))
     b = beta_raw + 0.1
-    a32 = host(a)
+    a32 = host64(a)
     x = -sdf.astype(np.float64) * np.float64(np.float32(b))
     sig = 1 / (1 + np.exp(-x))
     # fp32 sigmoid of the fp32 product: the product's rounding moves x by u|x|, the sigmoid's own by a few ulp
@@ -283,12 +155,12 @@ def test_sdf_render_saturated(ops, switches, S, pair):
     rw, rT, _, _ = ref_alpha(a32.astype(np.float32), np.zeros((R, S)), np.zeros((R, S)))
     st, en = e[:, :-1], e[:, 1:]
     w2, rf, rd, ra, mid = ref_composite(rw, feats, st, en)
-    check(host(w_ns), rw[:, :-1], TINY + 2 * (S + 2) * U * rw[:, :-1], "weights_ns")
-    check(host(acc), rw.sum(-1, keepdims=True), TINY + 2 * (S + 2) * U * rw.sum(-1, keepdims=True), "acc")
+    check(host64(w_ns), rw[:, :-1], TINY + 2 * (S + 2) * U * rw[:, :-1], "weights_ns")
+    check(host64(acc), rw.sum(-1, keepdims=True), TINY + 2 * (S + 2) * U * rw.sum(-1, keepdims=True), "acc")
     absf = np.abs(feats.astype(np.float64))
     sw = rw.sum(-1, keepdims=True)
-    check(host(out), rf, 4 * (S + 4) * U * ((np.abs(w2)[..., None] * absf).sum(1) + (1 + sw) * absf[:, -1]), "features")
-    check(host(depth), rd, TINY + 4 * (S + 4) * U * (rw[:, :-1] * np.abs(mid[:, :-1])).sum(-1, keepdims=True), "depth")
+    check(host64(out), rf, 4 * (S + 4) * U * ((np.abs(w2)[..., None] * absf).sum(1) + (1 + sw) * absf[:, -1]), "features")
+    check(host64(depth), rd, TINY + 4 * (S + 4) * U * (rw[:, :-1] * np.abs(mid[:, :-1])).sum(-1, keepdims=True), "depth")
     # backward: upstream on features, depth, acc and the weights without the sky sample
     gF, gD, gA = synth.normal((R, C), 93), synth.normal((R, 1), 94), synth.normal((R, 1), 95)
     gWns = synth.normal((R, S - 1), 96)
@@ -296,7 +168,7 @@ def test_sdf_render_saturated(ops, switches, S, pair):
                                              dev(gWns))
     gF64 = gF.astype(np.float64)
     rgf = w2[..., None] * gF64[:, None, :]
-    check(host(gfeat), rgf, 4 * (S + 4) * U * (np.abs(rgf) + (1 + sw)[..., None] * np.abs(gF64)[:, None, :]), "d features")
+    check(host64(gfeat), rgf, 4 * (S + 4) * U * (np.abs(rgf) + (1 + sw)[..., None] * np.abs(gF64)[:, None, :]), "d features")
     # dL/dw_s (as composite_bwd), then the alpha-mode backward, then sigmoid' = alpha (1 - alpha) and x = -sdf beta
     q = (feats.astype(np.float64) * gF64[:, None, :]).sum(-1)
     qm = (absf * np.abs(gF64)[:, None, :]).sum(-1)
@@ -310,12 +182,12 @@ def test_sdf_render_saturated(ops, switches, S, pair):
     ds = a64 * (1 - a64)
     rgsdf = -rga * ds * b
     bound = (2.0 ** -100 * np.abs(gw_mag).max(-1, keepdims=True) + 4 * (S + C + 8) * U * mag) * ds * b
-    check(host(gsdf), rgsdf, bound, "d sdf")
+    check(host64(gsdf), rgsdf, bound, "d sdf")
     # d beta_raw = sum over rays and samples of -ds * x / beta ... = sum(rga * ds * (-sdf)) (beta_raw > 0)
     rgb = float((rga * ds * -sdf.astype(np.float64)).sum())
     gb_bound = float((bound / b * np.abs(sdf)).sum()) + 2 * R * S * U * float((np.abs(rga * ds * sdf)).sum())
-    check(host(gbeta).reshape(()), rgb, gb_bound + 1e-30, "d beta")
-    assert np.isfinite(host(gsdf)).all()
+    check(host64(gbeta).reshape(()), rgb, gb_bound + 1e-30, "d beta")
+    assert np.isfinite(host64(gsdf)).all()
 
 
 @pytest.mark.parametrize("S", [16, 65])
@@ -332,10 +204,10 @@ def test_sdf_render_density_head_saturated(ops, S):
     sd = np.exp(x.astype(np.float64)) * delta
     ra = -np.expm1(-sd)
     # fp32 exp(x) (relative 2u) times delta: sd off by 3u sd, alpha by (1 - alpha) 3u sd
-    check(host(a), ra, TINY + 4 * U * ra + (1 - ra) * 3 * U * sd, "alpha")
-    a32 = host(a)
+    check(host64(a), ra, TINY + 4 * U * ra + (1 - ra) * 3 * U * sd, "alpha")
+    a32 = host64(a)
     rw, _, _, _ = ref_alpha(a32.astype(np.float32), np.zeros((R, S)), np.zeros((R, S)))
-    check(host(acc), rw.sum(-1, keepdims=True), TINY + 2 * (S + 2) * U * rw.sum(-1, keepdims=True), "acc")
+    check(host64(acc), rw.sum(-1, keepdims=True), TINY + 2 * (S + 2) * U * rw.sum(-1, keepdims=True), "acc")
     gF, gD, gA = synth.normal((R, C), 103), synth.normal((R, 1), 104), synth.normal((R, 1), 105)
     gfeat, gx, gbeta = ops.sdf_render_bwd(dev(x), None, 0.0, a, dev(feats), dev(e), dev(gF), dev(gD), dev(gA), None)
     assert gbeta is None
@@ -354,17 +226,11 @@ def test_sdf_render_density_head_saturated(ops, S):
     a64 = a32.astype(np.float64)
     chain = (1 - a64) * delta * np.exp(np.clip(x.astype(np.float64), -15, 15))
     bound = (2.0 ** -100 * gw_mag.max(-1, keepdims=True) + 4 * (S + C + 8) * U * mag) * chain
-    check(host(gx), rga * chain, bound, "d x")
+    check(host64(gx), rga * chain, bound, "d x")
 
 
 # ---- the fused render kernels at sharp beta -------------------------------------------------------------------------
 FUSED = [(16, 2, 64), (8, 4, 32), (4, 8, 64), (1, 4, 32), (4, 2, 64), (4, 4, 32), (8, 2, 64)]  # (L, F, H)
-
-
-def _rays(Rr, S, seed, far=60.0):
-    o, d, area, _ = synth.rays(Rr, seed)
-    _, eu, _ = O.power_sampler(np.zeros(Rr), np.full(Rr, far, np.float32), S)
-    return o, d, area, np.ascontiguousarray(eu[:, :-1]), np.ascontiguousarray(eu[:, 1:]), eu
 
 
 def _sharp_field(L, F, H, head, half, rays):
@@ -399,26 +265,26 @@ def test_render_fwd_sharp_surfaces(ops, shape, head, half, order):
     composited weights, accumulation, depth and features of each ray are held to."""
     L, F, H = shape
     Rr, S = 37, 48
-    o, d, area, s, e, eu = _rays(Rr, S, seed=L * 10 + F)
+    o, d, area, s, e, eu = sample_rays(Rr, S, seed=L * 10 + F, fars=60.0)
     p = _sharp_field(L, F, H, head, half, (o, d, area, s, e))
     fs = to_spec(ops, p, half=half)
     ref = O.render_rays(p, o, d, area, s, e)
     do, dd, da = dev(o), dev(d), dev(area)
     edges = dev(eu)
     kw = {"order": ops.ray_order(do, dd, p.static_scale)} if order else {}
-    feats, depth, acc, w = (host(v) for v in ops.render_fwd(fs, do, dd, da, edges[:, :-1], edges[:, 1:],
-                                                            return_weights=True, **kw))
+    feats, depth, acc, w = (host64(v) for v in ops.render_fwd(fs, do, dd, da, edges[:, :-1], edges[:, 1:],
+                                                              return_weights=True, **kw))
     f2, sdf2, head2 = ops.field_fwd(fs, do, dd, da, dev(s), dev(e))
     rw = ref["weights"].astype(np.float64)
     if p.use_sdf:
         beta = abs(p.beta) + p.beta_min
         ra = ref["alpha"].astype(np.float64)
         rsdf = ref["sdf"].reshape(Rr, S).astype(np.float64)
-        got_sdf = host(sdf2).reshape(Rr, S)
+        got_sdf = host64(sdf2).reshape(Rr, S)
         # the geometry MLP in fp32 against the oracle's fp32: a few 1e-6 of the layer's magnitude
         sdf_tol = 1e-5 * (1 + np.abs(rsdf))
         check(got_sdf, rsdf, sdf_tol, "sdf")
-        got_a = host(head2).reshape(Rr, S)
+        got_a = host64(head2).reshape(Rr, S)
         # alpha's sensitivity to sdf is beta alpha (1 - alpha) <= beta / 4; the mean-value bound with the larger of the two
         # alphas' alpha (1 - alpha) would need the kernel's; beta / 4 * sdf_tol caps it where the sigmoid turns
         slope = beta * np.maximum(ra * (1 - ra), 0.25 * (np.abs(-rsdf * beta) < 40))
@@ -431,7 +297,7 @@ def test_render_fwd_sharp_surfaces(ops, shape, head, half, order):
     assert sat > 0.5, f"only {sat:.2f} of the rays saturate"
     if got_a is None:  # density head: sigma from the kernel's per-sample head, alpha as render_weight_from_density
         rden = ref["density"].reshape(Rr, S).astype(np.float64)
-        got_den = host(head2).reshape(Rr, S)
+        got_den = host64(head2).reshape(Rr, S)
         # sigma = exp(x): the geometry output's fp32 error (as sdf_tol above) is a relative error of sigma
         check(got_den, rden, TINY + rden * np.expm1(1e-5 * (1 + np.abs(np.log(np.maximum(rden, TINY))))), "density")
         got_a = 1 - np.exp(-got_den * (e - s).astype(np.float64))
@@ -449,4 +315,4 @@ def test_render_fwd_sharp_surfaces(ops, shape, head, half, order):
     # fp32 feature error (1e-5 of its size) under weights that sum to at most 1
     check(feats, ref["features"], 2 * S * ray_b * fmax + 1e-5 * (1 + fmax), "features")
     # the per-sample features themselves
-    check(host(f2).reshape(Rr, S, -1), rfeat, 1e-5 * (1 + np.abs(rfeat)), "per-sample features")
+    check(host64(f2).reshape(Rr, S, -1), rfeat, 1e-5 * (1 + np.abs(rfeat)), "per-sample features")

@@ -12,15 +12,12 @@ import pytest
 import torch
 
 import synth
+from gpu_util import cuda
 
 pytestmark = pytest.mark.gpu
 
 ACTOR_Y = (-24.0, -8.0, 8.0, 24.0)  # four parked 4 m cubes at x = 20 m, far enough apart that a ray window sees one
 S = 48
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _parked_cars():
@@ -48,10 +45,10 @@ def _proposal():
     assert p.hashgrid.share_actor_table_grads and len(p.hashgrid.actor_grids) == len(ACTOR_Y)
     w, _ = synth.linear(1, 6, 77, bias=False)
     with torch.no_grad():
-        p.hashgrid.static_grid.hash_table.copy_(dev(synth.hash_table(6 * 2**11, 1, seed=91, scale=2.0)))
+        p.hashgrid.static_grid.hash_table.copy_(cuda(synth.hash_table(6 * 2**11, 1, seed=91, scale=2.0)))
         for i, gr in enumerate(p.hashgrid.actor_grids):
-            gr.hash_table.copy_(dev(synth.hash_table(4 * 2**8, 1, seed=500 + i, scale=1.5)))
-        p.density_decoder.weight.copy_(dev(w + np.float32(0.3)))
+            gr.hash_table.copy_(cuda(synth.hash_table(4 * 2**8, 1, seed=500 + i, scale=1.5)))
+        p.density_decoder.weight.copy_(cuda(w + np.float32(0.3)))
     return p
 
 
@@ -75,14 +72,14 @@ def _samples(actors, seed, n_rays=1024):
     dist = np.linalg.norm(d, axis=-1)
     d = (d / dist[:, None]).astype(np.float32)
     edges = (dist[:, None] + np.linspace(-1.2, 1.2, S + 1)[None]).astype(np.float32)
-    rb = RayBundle(origins=dev(o.astype(np.float32)), directions=dev(d), pixel_area=torch.full((n_rays, 1), 2.43e-6, device="cuda"),
-                   times=dev(synth.uniform((n_rays, 1), 0.1, 0.9, seed + 2)))
-    return rb.get_ray_samples(dev(edges[:, :-1])[..., None], dev(edges[:, 1:])[..., None])
+    rb = RayBundle(origins=cuda(o.astype(np.float32)), directions=cuda(d), pixel_area=torch.full((n_rays, 1), 2.43e-6, device="cuda"),
+                   times=cuda(synth.uniform((n_rays, 1), 0.1, 0.9, seed + 2)))
+    return rb.get_ray_samples(cuda(edges[:, :-1])[..., None], cuda(edges[:, 1:])[..., None])
 
 
 def _loss(p, rs, seed):
     dens = p.get_density(rs)[0]
-    return (dens * dev(synth.uniform(tuple(dens.shape), 0.5, 1.5, seed))).sum()
+    return (dens * cuda(synth.uniform(tuple(dens.shape), 0.5, 1.5, seed))).sum()
 
 
 def _grads(p):
@@ -181,13 +178,13 @@ def _field(table=None):
     f = NeuRADField(cfg, actors=None, static_scale=100.0).cuda().eval()
     with torch.no_grad():
         t = f.hashgrid.static_grid.hash_table
-        t.copy_(dev(synth.hash_table(t.shape[0], 4, seed=51, scale=0.5)) if table is None else table)
+        t.copy_(cuda(synth.hash_table(t.shape[0], 4, seed=51, scale=0.5)) if table is None else table)
         for k, l in enumerate(f.mlp_geo.layers):
             w, b = synth.linear(l.out_features, l.in_features, 200 + 10 * k)
-            l.weight.copy_(dev(w)), l.bias.copy_(dev(b))
+            l.weight.copy_(cuda(w)), l.bias.copy_(cuda(b))
         for k, l in enumerate(f.mlp_feature.layers):
             w, b = synth.linear(l.out_features, l.in_features, 300 + 10 * k)
-            l.weight.copy_(dev(w)), l.bias.copy_(dev(b))
+            l.weight.copy_(cuda(w)), l.bias.copy_(cuda(b))
     return f
 
 
@@ -203,7 +200,7 @@ def test_sharded_table_adam_step_invalidates_the_eval_relayout(monkeypatch):
     R = 2048
     o, d, area, _ = synth.rays(R, 5)
     edges = np.linspace(0.5, 60.0, 33, dtype=np.float32)[None].repeat(R, 0)
-    args = (dev(o), dev(d), dev(area), dev(edges[:, :-1]), dev(edges[:, 1:]))
+    args = (cuda(o), cuda(d), cuda(area), cuda(edges[:, :-1]), cuda(edges[:, 1:]))
 
     def render(field):
         with torch.no_grad():

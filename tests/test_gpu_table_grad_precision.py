@@ -18,28 +18,14 @@ import torch
 
 import neurad_oracle as O
 import synth
+from gpu_util import dev, host64_via32
+from gpu_util import ops  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
 LAYOUT = (4, 1, 14, 16, 1024)  # (L, F, log2 T, min_res, max_res): proposal-grid-like, several slices per level
 N = (1 << 16) + 37
-
-
-@pytest.fixture(scope="module")
-def ops():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from neurad_studio_amd import ops as _ops
-
-    return _ops
-
-
-def dev(a, dtype=torch.float32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
-
-
-def host(t):
-    return t.detach().float().cpu().numpy().astype(np.float64)
 
 
 def log2_slice(L, F, lg, n_slots=1):
@@ -133,7 +119,7 @@ def test_hashgrid_bwd_binned_per_entry_bound(ops, monkeypatch, switches, pairs, 
     x = positions(N, 3)
     go = sharp_gradients(N, L, F, 11, scale)
     spec = ops.GridSpec(L, F, lg, mn, mx)
-    got = host(ops.hashgrid_bwd(spec, None, dev(x), dev(go))).reshape(-1)
+    got = host64_via32(ops.hashgrid_bwd(spec, None, dev(x), dev(go))).reshape(-1)
     ref, a, n, recs, tmax, amax, ts = reference(x, go, L, F, lg, mn, mx)
     pair = pairs == "all"
     bnd, q = bound_for(ref, a, n, recs, tmax, amax, ts, L, F, lg, pair)
@@ -213,7 +199,7 @@ def test_binned_quantum_is_exactly_the_designs(ops, monkeypatch, switches):
         targets.append(s)
     xs, gs = x[rows], go[rows]
     spec = ops.GridSpec(L, F, lg, mn, mx)
-    got = host(ops.hashgrid_bwd(spec, None, dev(xs), dev(gs))).reshape(-1)
+    got = host64_via32(ops.hashgrid_bwd(spec, None, dev(xs), dev(gs))).reshape(-1)
     ref, a, n, recs, tmax, amax, ts2 = reference(xs, gs, L, F, lg, mn, mx)
     assert ts2 == ts and np.array_equal(recs, cnt)
     # vmax: the largest fp32 record of the level.  The fp32 product is within 8u of the float64 term; where that straddles a
@@ -258,12 +244,12 @@ def test_hashgrid_adam_step_on_binned_gradient(ops, monkeypatch):
     opt = HashGridAdam([p], lr=lr, eps=1e-15)
     p.grad = got
     opt.step()
-    upd = host(p.detach() - table).reshape(-1)
-    p64 = torch.nn.Parameter(torch.tensor(host(table)))
+    upd = host64_via32(p.detach() - table).reshape(-1)
+    p64 = torch.nn.Parameter(torch.tensor(host64_via32(table)))
     opt64 = torch.optim.Adam([p64], lr=lr, eps=1e-15)
     p64.grad = torch.tensor(ref.reshape(-1, F))
     opt64.step()
-    upd64 = (p64.detach() - torch.tensor(host(table))).numpy().reshape(-1)
+    upd64 = (p64.detach() - torch.tensor(host64_via32(table))).numpy().reshape(-1)
     off = np.abs(upd - upd64) > lr / 2
     explained = bnd >= np.abs(ref) / 2
     print(f"\n[adam] entries with a gradient {int((n > 0).sum())}, updates off by > lr/2: {int(off.sum())} "
@@ -296,9 +282,9 @@ def test_multi_grid_binned_per_entry_bound_and_fp16_overflow(ops, monkeypatch, s
     for k in range(n_grids):
         ref, a, n, recs, _, _, ts = refs[k]
         bnd, q = bound_for(ref, a, n, recs, tmax, amax, ts, L, F, lg, ops_pairs_default(F))
-        g32 = host(out32[k]).reshape(-1)
+        g32 = host64_via32(out32[k]).reshape(-1)
         assert out16[k].dtype == torch.float16
-        g16 = host(out16[k]).reshape(-1)
+        g16 = host64_via32(out16[k]).reshape(-1)
         assert np.isfinite(g32).all()  # (|g| <= 1e2 * 2^24 * n: far inside fp32's range at either scale)
         check_entries(g32, ref, bnd, f"multi grid {k} fp32")
         fin = np.abs(ref) + bnd < 65504  # surely inside fp16's range
@@ -344,7 +330,7 @@ def test_binned_poisoning_hits_exactly_the_poisoned_entries(ops, monkeypatch, sw
     for r, c, v in bad:
         go[r, c] = v
     spec = ops.GridSpec(L, F, lg, mn, mx)
-    got = host(ops.hashgrid_bwd(spec, None, dev(x), dev(go))).reshape(-1)
+    got = host64_via32(ops.hashgrid_bwd(spec, None, dev(x), dev(go))).reshape(-1)
     want = np.zeros(got.shape, bool)
     for r, c, _ in bad:
         l, j = divmod(c, F)

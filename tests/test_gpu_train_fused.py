@@ -8,26 +8,13 @@ import torch
 
 import synth
 from conftest import load_golden, rel_l2
+from builders import trajectories
+from gpu_util import actor_rays, bundle, dev, glue_bundle, glue_model, host, small_model, torch_sdf_render
+from gpu_util import ops  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
 TIGHT = 2e-5
-
-
-@pytest.fixture(scope="module")
-def ops():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    from neurad_studio_amd import ops as _ops
-
-    return _ops
-
-
-def dev(a, dtype=torch.float32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def _edges(R, S, seed, extra=0):
@@ -63,20 +50,6 @@ def test_prop_weights_from_edges_fwd_bwd_vs_torch(ops, shape):
     assert rel_l2(host(ops.prop_weights_bwd(edges, dens, gw, None)), host(td.grad)) < TOL
 
 
-def _torch_sdf_render(sdf, beta, beta_min, feat, edges):
-    """models/neurad.py:373-395 + model_components/utils.py:21-41 as torch ops (fp64)"""
-    R, S = sdf.shape
-    alpha = torch.sigmoid(-sdf * (beta.abs() + beta_min))
-    trans = torch.cumprod(torch.cat([torch.ones(R, 1, dtype=sdf.dtype, device=sdf.device), 1 - alpha[:, :-1]], -1), -1)
-    w = alpha * trans
-    acc = w.sum(-1, keepdim=True)
-    w2 = torch.cat([w[:, :-1], w[:, -1:] + 1 - acc], -1)
-    out = (w2[..., None] * feat).sum(1)
-    mid = (edges[:, :-1] + edges[:, 1:]) / 2
-    depth = (w2[:, :-1] * mid[:, :-1]).sum(-1, keepdim=True)
-    return alpha, w2[:, :-1], out, depth, acc
-
-
 @pytest.mark.parametrize("pair", ["0", "1"], ids=["ray-per-wave", "two-rays-per-wave"])
 @pytest.mark.parametrize("cfg", [(23, 32, 32, 16, 2.5), (7, 70, 32, 0, -3.0), (9, 5, 12, 4, 0.7), (4, 2, 3, 0, 20.0),
                                  (10, 17, 32, 0, 1.5), (1, 32, 32, 0, 4.0)])
@@ -93,7 +66,7 @@ def test_sdf_render_fwd_bwd_vs_torch(ops, cfg, pair, switches):
     assert out.shape == (R, Cc + A)
     ts, tf = sdf.double().requires_grad_(True), feat.double().requires_grad_(True)
     tb = beta.double().requires_grad_(True)
-    ra, rw, ro, rd, rc = _torch_sdf_render(ts, tb, 1e-4, tf, edges.double())
+    ra, rw, ro, rd, rc = torch_sdf_render(ts, tb, 1e-4, tf, edges.double())
     assert rel_l2(host(alpha), host(ra)) < TIGHT and rel_l2(host(w_ns), host(rw)) < TIGHT
     assert rel_l2(host(out[:, :Cc]), host(ro)) < TIGHT and rel_l2(host(depth), host(rd)) < TIGHT
     assert rel_l2(host(acc), host(rc)) < TIGHT
@@ -107,7 +80,7 @@ def test_sdf_render_fwd_bwd_vs_torch(ops, cfg, pair, switches):
     assert abs(float(gbeta) / float(tb.grad) - 1) < 1e-3
     # optional upstream gradients absent
     ts.grad = tf.grad = tb.grad = None
-    ra, rw, ro, rd, rc = _torch_sdf_render(ts, tb, 1e-4, tf, edges.double())
+    ra, rw, ro, rd, rc = torch_sdf_render(ts, tb, 1e-4, tf, edges.double())
     (ro * gF[:, :Cc].double()).sum().backward()
     gfeat, gsdf, gbeta = ops.sdf_render_bwd(sdf, beta, 1e-4, alpha, feat, edges, gF[:, :Cc], None, None, None)
     assert rel_l2(host(gsdf), host(ts.grad)) < TOL and abs(float(gbeta) / float(tb.grad) - 1) < 1e-3
@@ -235,12 +208,6 @@ def test_weighted_loss_sum_matches_python_sum(ops):
 
 
 # ---- the composed step ------------------------------------------------------------------------------------------------
-def _glue_model(g):
-    from test_gpu_model_glue import build_model, bundle
-
-    return build_model(g), bundle
-
-
 def _losses(m, out, g, is_lidar, fused_metrics):
     from neurad_studio_amd.model_components.lidar_losses import LidarLossSettings, lidar_loss_dict, lidar_metrics, lidar_rows
     from neurad_studio_amd.model_components.losses import distortion_loss, zipnerf_interlevel_loss
@@ -267,14 +234,14 @@ def test_fused_training_step_vs_reference_golden_and_operator_path():
     g = load_golden("model_train_glue")
     grads, outs = {}, {}
     for mode in ("fused", "operator"):
-        m, bundle = _glue_model(g)
+        m = glue_model(g)
         m.train()
         m.sampler.eval(), m.field.eval()  # deterministic sampling, as in the generator
         for p in m.proposal_fields:
             p.eval()
         m.fused_training = mode == "fused"
         assert m.fused_training_possible() == (mode == "fused")
-        out = m.get_nff_outputs(bundle(g), calc_lidar_losses=True)
+        out = m.get_nff_outputs(glue_bundle(g), calc_lidar_losses=True)
         is_lidar = dev(g["is_lidar"], torch.bool)
         metrics, losses, intensity, logits = _losses(m, out, g, is_lidar, fused_metrics=mode == "fused")
         for k in ("features", "depth", "accumulation", "prop_depth_0", "prop_depth_1"):
@@ -314,8 +281,6 @@ def test_fused_training_step_vs_reference_golden_and_operator_path():
 def test_fused_training_path_with_jitter_runs_and_matches_operator_path_given_the_same_draws():
     """training-mode jitter on: both paths draw torch.rand in the same order ([R,S+1] for the power bins, then one draw per
     PDF round), so with the same seed they walk the same samples"""
-    from test_gpu_modules import bundle, small_model
-
     res = {}
     for mode in ("fused", "operator"):
         m = small_model(True).train()
@@ -338,7 +303,6 @@ def test_fused_training_path_with_jitter_runs_and_matches_operator_path_given_th
 def _actor_model():
     from neurad_studio_amd.model_components.dynamic_actors import DynamicActors, DynamicActorsConfig
     from neurad_studio_amd.models.neurad import NeuRADHotPath, NeuRADHotPathConfig
-    from test_gpu_actors import trajectories
 
     torch.manual_seed(1)
     c = NeuRADHotPathConfig(appearance_dim=16)
@@ -362,21 +326,6 @@ def _actor_model():
     return m
 
 
-def _actor_rays(R=384):
-    from neurad_studio_amd.cameras.rays import RayBundle
-
-    gen = torch.Generator().manual_seed(5)
-    times = 1.0 + torch.rand(R, 1, generator=gen)  # all three trajectories exist in [1, 2]
-    a = torch.arange(R) % 3  # look at actor a, where it is at the ray's time (test_gpu_actors.trajectories), from ~4 m
-    tgt = torch.stack([12.0 + 2.0 * times[:, 0] + a, torch.tensor([8.0, -6.0, -5.0])[a], torch.full((R,), 0.5)], -1)
-    side = torch.nn.functional.normalize(torch.randn(R, 3, generator=gen) * torch.tensor([1.0, 1.0, 0.15]), dim=-1)
-    o = tgt + 4.0 * side
-    d = torch.nn.functional.normalize(tgt + 0.3 * torch.randn(R, 3, generator=gen) - o, dim=-1)
-    d[::4] = -d[::4]  # every fourth ray looks away
-    return RayBundle(origins=o.cuda(), directions=d.cuda(), pixel_area=torch.full((R, 1), 2.7e-7, device="cuda"),
-                     times=times.cuda(), metadata={"sensor_idxs": torch.randint(0, 2, (R, 1), generator=gen).cuda()})
-
-
 def test_fused_training_with_dynamic_actors_matches_the_operator_level_path():
     """A scene with dynamic actors through the fused training nodes: samples inside a box take their encoding row and view
     direction from the differentiable actor branch (nrhip_field_fwd_train_ovr), the proposal rounds take the fields' own
@@ -391,7 +340,7 @@ def test_fused_training_with_dynamic_actors_matches_the_operator_level_path():
         m.fused_training = mode == "fused"
         assert m.field.hashgrid.has_actors() and m.fused_training_possible() == (mode == "fused")
         torch.manual_seed(77)
-        out = m.get_nff_outputs(_actor_rays())
+        out = m.get_nff_outputs(actor_rays())
         loss = (out["features"].square().mean() + 1e-3 * out["depth"].mean() + out["accumulation"].mean()
                 + 0.01 * zipnerf_interlevel_loss(out["weights_list"], out["ray_samples_list"])
                 + 0.02 * distortion_loss(out["weights_list"], out["ray_samples_list"]) + 1e-3 * out["prop_depth_1"].mean())

@@ -6,6 +6,7 @@ import pytest
 import neurad_oracle as O
 import synth
 from conftest import load_golden, rel_l2
+from builders import field_params, mlp_params, prop_params
 
 TOL = 1e-5  # oracle restates the same fp32 ops; the product bar (HIP vs oracle) is 1e-4 rel-L2
 
@@ -49,20 +50,10 @@ def test_sh():
     assert rel_l2(O.sh_deg4(g["d01"]), g["y"]) < 1e-6
 
 
-def _mlp_params(cfg):
-    i, n, w, o = (int(v) for v in cfg)
-    dims = [i] + [w] * (n - 1) + [o]
-    ws, bs = [], []
-    for k in range(n):
-        wk, bk = synth.linear(dims[k + 1], dims[k], 100 + 10 * k)
-        ws.append(wk), bs.append(bk)
-    return ws, bs
-
-
 @pytest.mark.parametrize("tag", ["geo64", "feat64", "geo32", "lidar"])
 def test_mlp_fwd_bwd(tag):
     g = load_golden(f"mlp_{tag}")
-    ws, bs = _mlp_params(g["cfg"])
+    ws, bs = mlp_params(g["cfg"])
     y, hidden = O.mlp_fwd(g["x"], ws, bs, return_hidden=True)
     assert rel_l2(y, g["y"]) < TOL
     dx, dws, dbs = O.mlp_bwd(hidden, ws, g["grad_out"])
@@ -78,18 +69,6 @@ def test_contraction():
     assert rel_l2(m, g["cmean"]) < 1e-6
     assert rel_l2(s, g["cstd"][:, 0]) < 1e-6
     assert m.min() >= 0 and m.max() <= 1
-
-
-def field_params(use_sdf=True):
-    grid = O.GridParams(synth.hash_table(8 * 2**11, 4, seed=51, scale=0.5), 8, 32, 8192, 11)
-    gw, gb, fw, fb = [], [], [], []
-    for k, (o, i) in enumerate([(32, 32), (33, 32)]):
-        w, b = synth.linear(o, i, 200 + 10 * k)
-        gw.append(w), gb.append(b)
-    for k, (o, i) in enumerate([(32, 48), (32, 32), (32, 32)]):
-        w, b = synth.linear(o, i, 300 + 10 * k)
-        fw.append(w), fb.append(b)
-    return O.FieldParams(grid, 100.0, gw, gb, fw, fb, use_sdf=use_sdf)
 
 
 @pytest.mark.parametrize("tag", ["sdf", "density"])
@@ -124,12 +103,6 @@ def test_field_forward_multisampled():
     out = O.field_fwd(p, g["o"], g["d"], g["area"], st, en, num_multisamples=M)
     assert rel_l2(out["feature"], gm["feature"]) < TOL and rel_l2(out["sdf"], gm["sdf"]) < TOL
     assert rel_l2(out["alpha"], gm["alpha"]) < TOL and rel_l2(gm["alpha"], g["alpha"]) > 1e-3
-
-
-def prop_params(seed, lg=11):
-    w, _ = synth.linear(1, 6, seed + 1, bias=False)
-    return O.ProposalParams(O.GridParams(synth.hash_table(6 * 2**lg, 1, seed=seed, scale=2.0), 6, 128, 4096, lg),
-                            100.0, w + np.float32(0.3))
 
 
 def test_ray_gradients_vs_reference_autograd():

@@ -6,7 +6,7 @@ import ctypes
 import pytest
 import torch
 
-from test_abi import header_functions
+from host_gate import header_functions
 
 PACKED = ["nrhip_packed_segments", "nrhip_packed_weight_from_density", "nrhip_packed_weight_from_density_bwd",
           "nrhip_packed_weight_from_alpha", "nrhip_packed_weight_from_alpha_bwd", "nrhip_packed_accumulate",

@@ -23,16 +23,10 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import neurad_oracle as O  # noqa: E402
 import ref_import  # noqa: E402
 from conftest import rel_l2  # noqa: E402
+from plugin_harness import N_native as N  # noqa: E402  (no cast to fp32 here: the oracle's float64 and int64 stay)
+from plugin_harness import T, dense_nerfacc  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not ref_import.reference_available(), reason="reference tree not present")
-
-
-def T(a):
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32)))
-
-
-def N(t):
-    return t.detach().cpu().numpy()
 
 
 # ---- operator level ---------------------------------------------------------------------------------------------
@@ -288,23 +282,6 @@ def test_reference_raysamples_and_headnames_flow_through_the_hip_field(ref, monk
         assert rel_l2(N(out[k]), N(want[k])) < 1e-5, k
 
 
-def _tiny_nerfacc():
-    """dense-mode nerfacc 0.5.2 maths for the REFERENCE model on CPU (it imports a stubbed nerfacc here)"""
-    import types
-
-    m = types.ModuleType("nerfacc")
-
-    def render_weight_from_alpha(alphas, **kw):
-        trans = torch.cumprod(torch.cat([torch.ones_like(alphas[..., :1]), 1 - alphas[..., :-1]], -1), -1)
-        return trans * alphas, trans
-
-    def accumulate_along_rays(weights, values=None, ray_indices=None, n_rays=None):
-        return weights.sum(-1, keepdim=True) if values is None else (weights[..., None] * values).sum(-2)
-
-    m.render_weight_from_alpha, m.accumulate_along_rays = render_weight_from_alpha, accumulate_along_rays
-    return m
-
-
 def test_neurad_hip_method_builds_the_reference_model_and_matches_its_torch_eval(ref, monkeypatch):
     import nerfstudio.model_components.renderers as ref_renderers
     import nerfstudio.models.neurad as ref_neurad
@@ -355,7 +332,7 @@ def test_neurad_hip_method_builds_the_reference_model_and_matches_its_torch_eval
             p.hashgrid.static_grid.hash_table.mul_(2000.0)
     refm.load_state_dict(hip.state_dict())
     # the reference on CPU: real compositing instead of its 0.5 placeholder (models/neurad.py:713-715)
-    na = _tiny_nerfacc()
+    na = dense_nerfacc()
     monkeypatch.setattr(ref_neurad, "nerfacc", na)
     monkeypatch.setattr(ref_renderers, "nerfacc", na)
     monkeypatch.setattr(type(refm), "_render_weights",
@@ -423,7 +400,7 @@ def test_neurad_hip_plugin_training_step_on_the_fused_nodes_matches_the_referenc
         m.sampler.eval(), m.field.eval()
         for p in m.proposal_fields:
             p.eval()
-    na = _tiny_nerfacc()
+    na = dense_nerfacc()
     monkeypatch.setattr(ref_neurad, "nerfacc", na)
     monkeypatch.setattr(ref_renderers, "nerfacc", na)
     monkeypatch.setattr(type(refm), "_render_weights",
@@ -469,7 +446,6 @@ def test_neurad_hip_plugin_training_step_on_the_fused_nodes_matches_the_referenc
         ref_sd = torch.cat([want["ray_samples_list"][i].spacing_starts[..., 0],
                             want["ray_samples_list"][i].spacing_ends[..., -1:, 0]], -1)
         assert rel_l2(N(ray_samples_to_sdist(got["ray_samples_list"][i])), N(ref_sd)) < 1e-5, i
-
 
 
 def test_plugin_decoder_adapter_is_the_reference_decoder_call_without_a_copy(ref):

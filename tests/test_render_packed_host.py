@@ -3,34 +3,13 @@ packed instantiation set of csrc/render_variants.h).  No GPU.
 
 The field checks run in a child process, as tests/test_fused_shapes_gate.py does: importing the field module binds
 FieldHeadNames for the whole process."""
-import json
 import os
 import subprocess
-import sys
 
-from test_fused_shapes_gate import ROOT, VARIANTS, gate_constants, variant_rows
+from host_gate import VARIANTS, gate_constants, run_child, variant_rows
 
 CHILD = r'''
-import json, sys
-import torch
-from neurad_studio_amd.fields.neurad_field import NeuRADField, NeuRADFieldConfig, _FUSED_GRIDS
-from neurad_studio_amd.model_components.dynamic_actors import DynamicActors, DynamicActorsConfig
-
-
-def field_config(L, F, H):
-    cfg = NeuRADFieldConfig(geo_hidden_dim=H, nff_hidden_dim=H)
-    st, ac = cfg.grid.static, cfg.grid.actor
-    st.num_levels, st.hashgrid_dim, st.log2_hashmap_size = L, F, 10
-    ac.num_levels, ac.hashgrid_dim, ac.log2_hashmap_size = min(2, L), F, 8
-    return cfg
-
-
-def make_actors():
-    p = torch.eye(4).repeat(2, 1, 1)
-    p[:, :3, 3] = torch.tensor([10.0, 0.0, 0.5])
-    traj = {"timestamps": torch.tensor([0.0, 1.0]), "poses": p, "dims": torch.tensor([2.0, 4.5, 1.6]),
-            "symmetric": torch.tensor(True), "deformable": torch.tensor(False)}
-    return DynamicActors(DynamicActorsConfig(), trajectories=[traj])
+from neurad_studio_amd.fields.neurad_field import _FUSED_GRIDS
 
 
 def raised(fn):
@@ -67,15 +46,8 @@ print(json.dumps(out))
 '''
 
 
-def child():
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([ROOT] + [p for p in [os.environ.get("PYTHONPATH")] if p]))
-    r = subprocess.run([sys.executable, "-c", CHILD], capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return json.loads(r.stdout.strip().splitlines()[-1])
-
-
 def test_packed_gate_and_argument_errors():
-    res = child()
+    res = run_child(CHILD)
     gate = res["gate"]
     assert len([k for k in gate if k.startswith("static")]) == 14
     for k, v in gate.items():
