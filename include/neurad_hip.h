@@ -766,6 +766,46 @@ int nrhip_render_fwd_packed(const nrhip_field* f, const nrhip_packed_rays* rays,
                             float* out_depth /*[R]*/, float* out_acc /*[R]*/, float* out_weights /*[M] or NULL*/,
                             float early_stop_eps, void* stream);
 
+/* ---- training on packed samples: the packed counterparts of nrhip_field_fwd_train, nrhip_sdf_render_fwd / _bwd and
+ *      nrhip_encode_bwd_binned.  No atomics, no allocation, no host synchronisation (graph-capturable).                  */
+/* nrhip_field_fwd_train on the march's packed samples: the same per-sample kernel (every `PerSample, Static, F32` row of
+ * csrc/render_variants.h, fp32 and fp16 tables), ray constants read per ray, every per-sample row stored at the PACKED
+ * sample index.  geo_out [M] = the geometry MLP's first output (sdf / raw density), head [M] = sigmoid(-geo_out beta) with
+ * the descriptor's beta, or exp(geo_out).  rays->order is honoured.  n_rays == 0 and n_samples == 0 are no-ops that read
+ * no pointer; n_samples >= 2^31 is NRHIP_ERR_UNSUPPORTED; the save buffers must be 16-byte aligned.                      */
+int nrhip_field_fwd_train_packed(const nrhip_field* f, const nrhip_packed_rays* rays, float* feature /*[M,32]*/,
+                                 float* geo_out /*[M]*/, float* head /*[M]*/, float* save_enc /*[M,L*F]*/,
+                                 float* save_geo_hidden /*[M,H]*/, float* save_feat_in /*[M,48]*/,
+                                 float* save_feat_hidden /*[M,2H]*/, void* stream);
+/* head + packed compositing.  beta: DEVICE pointer to the raw parameter, alpha = sigmoid(-geo_out (|beta| + beta_min));
+ * beta == NULL: the density head, alpha = 1 - exp(-trunc_exp(geo_out) (t_end - t_start)).  Compositing as
+ * nrhip_packed_composite_fwd (no sky residual, depth over all samples, zeros for an empty segment).  alpha [M] is what the
+ * backward starts from.  Backward: each of g_features / g_depth / g_accumulation / g_weights may be NULL (g_features
+ * NULL: grad_features is not written -- it is zero); grad_beta [1] = sign(beta) x the fixed-order sum of one partial per
+ * wavefront (workspace: nrhip_sdf_render_packed_bwd_workspace(r) floats), bitwise reproducible; the density head leaves
+ * grad_beta alone.  r == 0 is a no-op that reads no pointer (the backward zeroes grad_beta).                           */
+int nrhip_sdf_render_packed_fwd(const float* geo_out /*[M]*/, const float* beta /*device [1] or NULL*/, float beta_min,
+                                const float* features /*[M,C]*/, const float* t_starts, const float* t_ends,
+                                const int64_t* segments, int64_t r, int32_t c, float* alpha /*[M]*/, float* weights /*[M]*/,
+                                float* out_features /*[R,C]*/, float* out_depth /*[R]*/, float* out_accumulation /*[R]*/,
+                                void* stream);
+int nrhip_sdf_render_packed_bwd_workspace(int64_t r, int64_t* floats);
+int nrhip_sdf_render_packed_bwd(const float* geo_out, const float* beta, float beta_min, const float* alpha,
+                                const float* features, const float* t_starts, const float* t_ends, const int64_t* segments,
+                                const float* g_features /*[R,C]*/, const float* g_depth /*[R]*/,
+                                const float* g_accumulation /*[R]*/, const float* g_weights /*[M]*/, int64_t r, int32_t c,
+                                float* grad_features /*[M,C]*/, float* grad_geo_out /*[M]*/, float* grad_beta /*[1]*/,
+                                float* workspace, void* stream);
+/* nrhip_encode_bwd_binned / _f16 for packed samples: ray_of [M] (the march's ray_indices, values in [0, n_rays)) names
+ * each sample's ray; grad_out [M, L*F].  Workspace: nrhip_encode_bwd_binned_workspace(g, n_samples); `overwrite` and the
+ * fp16 one-round rule as for the dense pair.  rays->segments and rays->order are not read.                             */
+int nrhip_encode_bwd_binned_packed(const nrhip_grid* g, float static_scale, const nrhip_packed_rays* rays,
+                                   const int64_t* ray_of, const float* grad_out, float* grad_table, int32_t overwrite,
+                                   void* workspace, int64_t workspace_bytes, void* stream);
+int nrhip_encode_bwd_binned_packed_f16(const nrhip_grid* g, float static_scale, const nrhip_packed_rays* rays,
+                                       const int64_t* ray_of, const float* grad_out, void* grad_table_fp16, void* workspace,
+                                       int64_t workspace_bytes, void* stream);
+
 /* ---- S5+M1 fused: ProposalNetworkSampler as driven by NeuRADModel._get_ray_samples
  *      (ray_samplers.py:623-666, models/neurad.py:443-459).  One wave marches one ray through
  *      power bins -> (density -> weights -> pdf resample) x n_rounds, entirely on chip.

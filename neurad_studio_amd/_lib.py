@@ -189,6 +189,12 @@ PROTOTYPES = {
     "nrhip_render_fwd": [C.POINTER(Field), C.POINTER(Rays), P, P, P, P, P],
     "nrhip_render_fwd_ex": [C.POINTER(Field), C.POINTER(Rays), P, P, P, P, F32, P],
     "nrhip_render_fwd_packed": [C.POINTER(Field), C.POINTER(PackedRays), P, P, P, P, F32, P],
+    "nrhip_field_fwd_train_packed": [C.POINTER(Field), C.POINTER(PackedRays), P, P, P, P, P, P, P, P],
+    "nrhip_sdf_render_packed_fwd": [P, P, F32, P, P, P, P, I64, I32, P, P, P, P, P, P],
+    "nrhip_sdf_render_packed_bwd_workspace": [I64, C.POINTER(I64)],
+    "nrhip_sdf_render_packed_bwd": [P, P, F32, P, P, P, P, P, P, P, P, P, I64, I32, P, P, P, P, P],
+    "nrhip_encode_bwd_binned_packed": [C.POINTER(Grid), F32, C.POINTER(PackedRays), P, P, P, I32, P, I64, P],
+    "nrhip_encode_bwd_binned_packed_f16": [C.POINTER(Grid), F32, C.POINTER(PackedRays), P, P, P, P, I64, P],
     "nrhip_ray_order": [P, P, I64, F32, F32, I32, P, P],
     "nrhip_ray_order_workspace": [I64, I32, C.POINTER(I64)],
     "nrhip_ray_order_large": [P, P, I64, F32, F32, I32, P, I64, P, P],

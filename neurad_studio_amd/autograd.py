@@ -251,7 +251,7 @@ class FieldTrainFn(torch.autograd.Function):
 
 
 def _field_backward(spec, scale, table_dtype, need_table, o, d, a, starts, ends, enc, hg, xf, hf, params, g_feature, g_geo_out,
-                    override=None, rays=None):
+                    override=None, rays=None, ray_of=None):
     """Backward of the fused field forward from (dL/dfeature [N,32], dL/dgeo_out [N]): feature-MLP gradients -> residual ->
     geometry-MLP gradients -> table gradient.  -> (grad table or None, the ten MLP parameter gradients in argument order,
     gradient of the override rows or None, (dL/d origins, dL/d directions) or Nones).  override = (ovr_row [N], pair_idx
@@ -259,7 +259,8 @@ def _field_backward(spec, scale, table_dtype, need_table, o, d, a, starts, ends,
     pair gets its sample's row, as the reference's index_put does (neurad_encoding.py:184-185) -- and send nothing to the
     static table.  rays = (table, need_o, need_d): the bundle's rays require grad (camera optimizer) -> the static samples'
     dL/d enc also goes back to the ray through the positions (`_ray_grads`; the overridden rows are zero by then: their
-    share comes through ActorPairPositionsFn)."""
+    share comes through ActorPairPositionsFn).  ray_of int64 [M]: packed samples -- o / d / a are per RAY, starts / ends [M],
+    and the table gradient comes from ``ops.encode_bwd_packed``."""
     gw, gb, fw, fb = list(params[0:4:2]), list(params[1:4:2]), list(params[4:10:2]), list(params[5:10:2])
     # feature = embedding + mlp_feature([embedding | sh])
     if ops.field_feature_bwd_supported(fw, fb):
@@ -278,8 +279,12 @@ def _field_backward(spec, scale, table_dtype, need_table, o, d, a, starts, ends,
         # exactly-zero rows send no records (encode_bwd_binned: prep).  The overridden samples are the pair list's samples
         # (every sample of a pair has a winning pair): P rows written, not a pass over all N (85 us at 2 M samples)
         genc.index_fill_(0, pair_idx, 0.0)
-    gt = _like_param(ops.encode_bwd(spec, scale, o, d, a, starts, ends, genc, out_dtype=table_dtype), table_dtype) \
-        if need_table else None
+    gt = None
+    if need_table and ray_of is not None:
+        gt = _like_param(ops.encode_bwd_packed(spec, scale, o, d, a, starts, ends, ray_of, genc, out_dtype=table_dtype),
+                         table_dtype)
+    elif need_table:
+        gt = _like_param(ops.encode_bwd(spec, scale, o, d, a, starts, ends, genc, out_dtype=table_dtype), table_dtype)
     grads = [ggw[0], ggb[0], ggw[1], ggb[1], gfw[0], gfb[0], gfw[1], gfb[1], gfw[2], gfb[2]]
     god = (None, None) if rays is None else _ray_grads(rays[1], rays[2], spec, rays[0], scale, o, d, a, starts, ends, genc)
     return gt, grads, g_rows, god
@@ -719,6 +724,53 @@ class NffRenderTrainFn(torch.autograd.Function):
         g_beta = gbeta.reshape(beta.shape) if (ctx.needs_input_grad[3] and not ctx.density_head) else None
         return (gt, None, None, g_beta, None, go, gd, None, None, g_emb, None, None, None, None, None, g_rows, None, None,
                 *grads)
+
+
+class NffRenderPackedTrainFn(torch.autograd.Function):
+    """NffRenderTrainFn for the occupancy march's packed samples (static scene): fused field forward on packed samples ->
+    head (SigmoidDensity with the learnable beta, or trunc_exp) + packed compositing -> features, depth, accumulation,
+    weights.  Compositing as PackedCompositeFn: no sky residual, depth = sum w mid over all samples, zeros for a ray
+    without samples.  No appearance embedding (callers append it per ray), no ray gradients.
+
+    args: table, spec, static_scale, beta (raw parameter) | None (density head), beta_min, origins [R,3], directions [R,3],
+    pixel_area [R], t_starts [M], t_ends [M], segments int64 [R+1], ray_indices int64 [M], order | None, gw0, gb0, gw1,
+    gb1, fw0, fb0, fw1, fb1, fw2, fb2
+    -> features [R,32], depth [R,1], accumulation [R,1], weights [M]"""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area, t_starts, t_ends, segments,
+                ray_indices, order, *params):
+        ctx.set_materialize_grads(False)
+        R, M = segments.shape[0] - 1, t_starts.numel()
+        ctx.empty = M == 0
+        if ctx.empty:  # answered on the host: nothing to launch, nothing to differentiate
+            z = lambda *shape: torch.zeros(shape, device=origins.device, dtype=torch.float32)  # noqa: E731
+            return z(R, 32), z(R, 1), z(R, 1), z(0)
+        gw, gb, fw, fb = list(params[0:4:2]), list(params[1:4:2]), list(params[4:10:2]), list(params[5:10:2])
+        fs = ops.FieldSpec(spec, table, static_scale, gw, gb, fw, fb, use_sdf=True, beta=1.0)  # (kernel head unused)
+        (feature, geo, _head), (enc, hg, xf, hf) = ops.field_fwd_train_packed(fs, origins, directions, pixel_area, t_starts,
+                                                                              t_ends, segments, order=order)
+        alpha, w, out, depth, acc = ops.sdf_render_packed_fwd(geo, beta, beta_min, feature, t_starts, t_ends, segments)
+        ctx.spec, ctx.scale, ctx.table_dtype, ctx.beta_min = spec, static_scale, table.dtype, beta_min
+        ctx.density_head = beta is None
+        ctx.save_for_backward(origins, directions, pixel_area, t_starts, t_ends, segments, ray_indices, enc, hg, xf, hf,
+                              feature, geo, alpha, geo.new_empty(0) if beta is None else beta, *params)
+        return out, depth, acc, w
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, g_out, g_depth, g_acc, g_w):
+        none = (None,) * 23
+        if ctx.empty or (g_out is None and g_depth is None and g_acc is None and g_w is None):
+            return none
+        o, d, a, ts, te, seg, ri, enc, hg, xf, hf, feature, geo, alpha, beta, *params = ctx.saved_tensors
+        gfeat, ggeo, gbeta = ops.sdf_render_packed_bwd(geo, None if ctx.density_head else beta, ctx.beta_min, alpha, feature,
+                                                       ts, te, seg, g_out, g_depth, g_acc, g_w)
+        gt, grads, _, _ = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a, ts, te, enc,
+                                          hg, xf, hf, params, gfeat, ggeo, ray_of=ri)
+        g_beta = gbeta.reshape(beta.shape) if (ctx.needs_input_grad[3] and not ctx.density_head) else None
+        return (gt, None, None, g_beta, *([None] * 9), *grads)
 
 
 class LidarLossFn(torch.autograd.Function):

@@ -223,6 +223,34 @@ struct EncodeSrc {  // H2+H3+H1+H4 (nrhip_encode_bwd): positions from ray sample
   __device__ bool silent(int64_t w0, int64_t n_rows) const { return rows_are_zero(go, width, w0, n_rows); }
   __device__ int coherent_rays(int64_t first, int64_t count) const { return coherent_rays_of(r, first, count); }
 };
+struct PackedEncodeSrc {  // EncodeSrc for packed samples (nrhip_encode_bwd_binned_packed): sample i belongs to ray ray_of[i]
+  static constexpr bool kMulti = false;
+  const float* o;     // [R, 3]
+  const float* d;     // [R, 3]
+  const float* area;  // [R]
+  const float* starts;  // [M]
+  const float* ends;    // [M]
+  const int64_t* ray_of;  // [M] the march's ray_indices
+  float scale;
+  const float* go;
+  int L;
+  __device__ float4 position(int64_t i) const {
+    const int64_t ray = ray_of[i];
+    const SamplePos p = sample_position(o[3 * ray], o[3 * ray + 1], o[3 * ray + 2], d[3 * ray], d[3 * ray + 1],
+                                        d[3 * ray + 2], area[ray], starts[i], ends[i], scale);
+    return make_float4(p.x, p.y, p.z, p.std);
+  }
+  __device__ float pre(int64_t) const { return 0.f; }
+  template <int F>
+  __device__ void grad(int64_t i, int l, float sc, float std, float, float (&gv)[F]) const {
+    const float rw = rescale_weight(sc, std);
+#pragma unroll
+    for (int k = 0; k < F; ++k) gv[k] = go[(i * L + l) * F + k] * rw;
+  }
+  int width;  // L * F
+  __device__ bool silent(int64_t w0, int64_t n_rows) const { return rows_are_zero(go, width, w0, n_rows); }
+  __device__ int coherent_rays(int64_t, int64_t) const { return 0; }  // ragged rays: no [R, S] block to transpose
+};
 struct GridSrc {  // H1 (nrhip_hashgrid_bwd): positions given
   static constexpr bool kMulti = false;
   const float* x;
@@ -890,6 +918,49 @@ extern "C" int nrhip_encode_bwd_binned_f16(const nrhip_grid* g, float static_sca
   gd.dtype = 1;  // fp16 grad_table
   const EncodeSrc src{to_dev(*rays), static_scale, grad_out, gd.L, gd.L * gd.F};
   return run_binned("encode_bwd_binned_f16", gd, src, n, static_cast<float*>(grad_table_fp16), true, workspace,
+                    workspace_bytes, (hipStream_t)stream);
+}
+
+// the packed pair: samples [M] of ragged rays, ray_of [M] = the march's ray_indices (every entry in [0, n_rays))
+static int check_packed_src(const char* what, const nrhip_packed_rays* rays, const int64_t* ray_of, const float* grad_out,
+                            const void* grad_table, float static_scale) {
+  NR_REQUIRE(rays, NRHIP_ERR_INVALID_ARG, "%s: rays descriptor is NULL", what);
+  NR_REQUIRE(rays->n_rays >= 0 && rays->n_samples >= 0, NRHIP_ERR_INVALID_ARG, "%s: negative ray/sample count", what);
+  NR_REQUIRE(rays->n_samples < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "%s: M >= 2^31", what);
+  NR_REQUIRE(grad_table && static_scale > 0.f, NRHIP_ERR_INVALID_ARG, "%s: NULL grad_table or non-positive scale", what);
+  NR_REQUIRE(rays->n_samples == 0 || (rays->n_rays > 0 && rays->origins && rays->directions && rays->pixel_area &&
+                                      rays->t_starts && rays->t_ends && ray_of && grad_out),
+             NRHIP_ERR_INVALID_ARG, "%s: samples without rays, or a NULL pointer", what);
+  return NRHIP_OK;
+}
+
+extern "C" int nrhip_encode_bwd_binned_packed(const nrhip_grid* g, float static_scale, const nrhip_packed_rays* rays,
+                                              const int64_t* ray_of, const float* grad_out, float* grad_table,
+                                              int32_t overwrite, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int e = validate_grid(g)) return e;
+  if (int e = check_packed_src("encode_bwd_binned_packed", rays, ray_of, grad_out, grad_table, static_scale)) return e;
+  const int64_t n = rays->n_samples;
+  if (n == 0) return NRHIP_OK;
+  GridDev gd = to_dev(*g);
+  gd.dtype = 0;  // fp32 grad_table, whatever the table's storage type (g->param_dtype) is
+  const PackedEncodeSrc src{rays->origins, rays->directions, rays->pixel_area, rays->t_starts, rays->t_ends, ray_of,
+                            static_scale,  grad_out,         gd.L,             gd.L * gd.F};
+  return run_binned("encode_bwd_binned_packed", gd, src, n, grad_table, overwrite != 0, workspace, workspace_bytes,
+                    (hipStream_t)stream);
+}
+
+extern "C" int nrhip_encode_bwd_binned_packed_f16(const nrhip_grid* g, float static_scale, const nrhip_packed_rays* rays,
+                                                  const int64_t* ray_of, const float* grad_out, void* grad_table_fp16,
+                                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int e = validate_grid(g)) return e;
+  if (int e = check_packed_src("encode_bwd_binned_packed_f16", rays, ray_of, grad_out, grad_table_fp16, static_scale)) return e;
+  const int64_t n = rays->n_samples;
+  NR_REQUIRE(n > 0, NRHIP_ERR_INVALID_ARG, "encode_bwd_binned_packed_f16: every element is written: at least one sample");
+  GridDev gd = to_dev(*g);
+  gd.dtype = 1;  // fp16 grad_table
+  const PackedEncodeSrc src{rays->origins, rays->directions, rays->pixel_area, rays->t_starts, rays->t_ends, ray_of,
+                            static_scale,  grad_out,         gd.L,             gd.L * gd.F};
+  return run_binned("encode_bwd_binned_packed_f16", gd, src, n, static_cast<float*>(grad_table_fp16), true, workspace,
                     workspace_bytes, (hipStream_t)stream);
 }
 

@@ -460,3 +460,52 @@ extern "C" int nrhip_packed_composite_bwd(const float* t_starts, const float* t_
                   grad_features);
   return check_launch("packed_composite_bwd");
 }
+
+// ---- head + packed compositing for training (packed_composite.h: head_fwd_kernel / head_bwd_kernel): the packed sibling
+// of nrhip_sdf_render_fwd / _bwd.  `beta` is a device pointer to the raw parameter (NULL: the density head).
+extern "C" int nrhip_sdf_render_packed_fwd(const float* geo_out, const float* beta, float beta_min, const float* features,
+                                           const float* t_starts, const float* t_ends, const int64_t* segments, int64_t r,
+                                           int32_t c, float* alpha, float* weights, float* out_features, float* out_depth,
+                                           float* out_accumulation, void* stream) {
+  PACKED_COMMON("sdf_render_packed_fwd", r, segments, c);
+  NR_REQUIRE(out_features && out_depth && out_accumulation, NRHIP_ERR_INVALID_ARG,
+             "sdf_render_packed_fwd: a per-ray output is NULL");
+  const nrhip::packed::Plan p = nrhip::packed::plan_for(c, features, out_features, nullptr);
+  PACKED_LAUNCH(head_fwd_kernel, r, stream, t_starts, t_ends, geo_out, beta, beta_min, features, segments, r, c, p.lp, p.k,
+                alpha, weights, out_features, out_depth, out_accumulation);
+  return check_launch("sdf_render_packed_fwd");
+}
+
+extern "C" int nrhip_sdf_render_packed_bwd_workspace(int64_t r, int64_t* floats) {
+  NR_REQUIRE(floats && r >= 0, NRHIP_ERR_INVALID_ARG, "sdf_render_packed_bwd_workspace: bad argument");
+  *floats = (int64_t)nrhip::packed::blocks_for(r) * nrhip::packed::kWaves;  // one partial of d beta per wave
+  return NRHIP_OK;
+}
+
+extern "C" int nrhip_sdf_render_packed_bwd(const float* geo_out, const float* beta, float beta_min, const float* alpha,
+                                           const float* features, const float* t_starts, const float* t_ends,
+                                           const int64_t* segments, const float* g_features, const float* g_depth,
+                                           const float* g_accumulation, const float* g_weights, int64_t r, int32_t c,
+                                           float* grad_features, float* grad_geo_out, float* grad_beta, float* workspace,
+                                           void* stream) {
+  NR_REQUIRE(r >= 0, NRHIP_ERR_INVALID_ARG, "sdf_render_packed_bwd: negative ray count");
+  NR_REQUIRE(c >= 1, NRHIP_ERR_INVALID_ARG, "sdf_render_packed_bwd: channel count %d < 1", (int)c);
+  NR_REQUIRE(grad_beta || !beta, NRHIP_ERR_INVALID_ARG, "sdf_render_packed_bwd: grad_beta is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  if (r == 0) {
+    if (grad_beta && hipMemsetAsync(grad_beta, 0, sizeof(float), st) != hipSuccess) return check_launch("sdf_render_packed_bwd");
+    return NRHIP_OK;
+  }
+  NR_REQUIRE(segments, NRHIP_ERR_INVALID_ARG, "sdf_render_packed_bwd: segments is NULL");
+  NR_REQUIRE(grad_features && grad_geo_out && workspace, NRHIP_ERR_INVALID_ARG,
+             "sdf_render_packed_bwd: a gradient output or the workspace is NULL");
+  const nrhip::packed::Plan p = nrhip::packed::plan_for(c, features, g_features, grad_features);
+  // (g_features == NULL: no feature term upstream; grad_features = w gF is then left to the caller -- it is zero)
+  PACKED_LAUNCH(head_bwd_kernel, r, stream, t_starts, t_ends, geo_out, beta, beta_min, alpha, g_features ? features : nullptr,
+                segments, g_features, g_depth, g_accumulation, g_weights, r, c, p.lp, p.k, grad_geo_out, grad_features,
+                workspace);
+  if (beta)
+    nrhip::packed::beta_reduce_kernel<<<1, 64, 0, st>>>(workspace, nrhip::packed::blocks_for(r) * nrhip::packed::kWaves, beta,
+                                                        grad_beta);
+  return check_launch("sdf_render_packed_bwd");
+}

@@ -2,7 +2,8 @@
 // render_weight_from_density / accumulate_along_rays and their fusion, forward and backward.
 // `seg` is int64 [R+1]: ray r owns the packed samples [seg[r], seg[r+1]).  Owner-computes: one wavefront walks one ray in
 // chunks of 64 samples with a carried prefix (the structure of the dense kernels of composite.hip, same arithmetic), rays
-// are handed out grid-stride over a capped grid.  No atomics (bitwise reproducible), no LDS, nothing allocated.
+// are handed out grid-stride over a capped grid.  No atomics (bitwise reproducible), no LDS, nothing allocated.  The same
+// structure carries the training node's head + compositing (head_fwd_kernel / head_bwd_kernel at the end of the file).
 //
 // Channel rows [M,C]: when C is a multiple of 4 (and the rows are 16-byte aligned) LP lanes share a sample and each owns K
 // float4 of its row, LP * K == C / 4 -- C = 32: 8 lanes x 1, C = 48: 4 lanes x 3 -- so every load / store of a wave is a
@@ -61,6 +62,56 @@ __device__ __forceinline__ float class_sum(float v, int lp) {
   return v;
 }
 
+// sum_j w_j f_j over one chunk of a ray (cnt live samples from i0, lane = sample, w = its weight; 0 on a dead lane).  Vector
+// path: into the running float4 rows `fa`; generic C: one wave reduction per channel, the row's running sum lives in `of`
+// (owner-only, in order; the ray's first chunk, i0 == sb, starts it)
+__device__ __forceinline__ void accumulate_rows(const float* __restrict__ feat, float* __restrict__ of, int64_t ray,
+                                                int64_t sb, int64_t i0, int cnt, float w, int C, int LP, int K, int lane,
+                                                float4 (&fa)[kMaxK]) {
+  const int sub = lane & (LP - 1), sl = lane / LP, spw = 64 / LP;
+  if (K > 0) {
+    for (int j0 = 0; j0 < cnt; j0 += spw) {
+      const int j = j0 + sl;
+      const float wj = __shfl(w, j, 64);
+      if (j < cnt) {
+        const float4* fp = reinterpret_cast<const float4*>(feat + (i0 + j) * C) + sub;
+#pragma unroll
+        for (int k = 0; k < kMaxK; ++k)
+          if (k < K) {
+            const float4 f4 = fp[k * LP];
+            fa[k].x = fmaf(wj, f4.x, fa[k].x);
+            fa[k].y = fmaf(wj, f4.y, fa[k].y);
+            fa[k].z = fmaf(wj, f4.z, fa[k].z);
+            fa[k].w = fmaf(wj, f4.w, fa[k].w);
+          }
+      }
+    }
+  } else {
+    const bool live = lane < cnt;
+    for (int ch = 0; ch < C; ++ch) {
+      const float p = wscan::reduce<wscan::Add>(live ? w * feat[(i0 + lane) * C + ch] : 0.f);
+      if (lane == 0) of[ray * C + ch] = (i0 == sb ? 0.f : of[ray * C + ch]) + p;
+    }
+  }
+}
+
+// the ray's row of `of` once its chunks are through: the class sums of `fa` (vector path), zeros for an empty segment
+// (generic C: a ray with samples has its row in place already)
+__device__ __forceinline__ void store_rows(float* __restrict__ of, int64_t ray, bool empty, int C, int LP, int K, int lane,
+                                           const float4 (&fa)[kMaxK]) {
+  if (K > 0) {
+#pragma unroll
+    for (int k = 0; k < kMaxK; ++k)
+      if (k < K) {
+        float4 v = fa[k];
+        v.x = class_sum(v.x, LP), v.y = class_sum(v.y, LP), v.z = class_sum(v.z, LP), v.w = class_sum(v.w, LP);
+        if (lane < LP) reinterpret_cast<float4*>(of + ray * C)[(lane & (LP - 1)) + k * LP] = v;
+      }
+  } else if (empty) {
+    for (int ch = lane; ch < C; ch += 64) of[ray * C + ch] = 0.f;
+  }
+}
+
 // Forward of every packed op.  ts / te: interval ends [M] (kDensity: needed; otherwise only for the depth).  x [M]: alphas,
 // sigmas or weights.  feat [M,C], read iff `of` is given (an empty batch has no feat to point at, its rows of `of` are still
 // zeroed).  Outputs, each may be NULL: of [R,C] = sum w f, od [R] = sum w (ts + te) / 2, oa [R] = sum w, and per sample ow
@@ -73,7 +124,6 @@ __global__ __launch_bounds__(64 * kWaves) void fwd_kernel(const float* __restric
                                                           float* __restrict__ oa, float* __restrict__ ow,
                                                           float* __restrict__ ot, float* __restrict__ oal) {
   const int lane = threadIdx.x & 63;
-  const int sub = lane & (LP - 1), sl = lane / LP, spw = 64 / LP;
   for (int64_t ray = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); ray < R; ray += (int64_t)gridDim.x * kWaves) {
     const int64_t sb = seg[ray], se = seg[ray + 1];
     float carry = (MODE == kAlpha) ? 1.f : 0.f;
@@ -111,47 +161,9 @@ __global__ __launch_bounds__(64 * kWaves) void fwd_kernel(const float* __restric
       }
       acc += w;
       if (od && live) dep += w * ((ts[i] + te[i]) / 2.f);
-      if (of) {
-        const int cnt = (int)(se - i0 < 64 ? se - i0 : 64);
-        if (K > 0) {
-          for (int j0 = 0; j0 < cnt; j0 += spw) {
-            const int j = j0 + sl;
-            const float wj = __shfl(w, j, 64);
-            if (j < cnt) {
-              const float4* fp = reinterpret_cast<const float4*>(feat + (i0 + j) * C) + sub;
-#pragma unroll
-              for (int k = 0; k < kMaxK; ++k)
-                if (k < K) {
-                  const float4 f4 = fp[k * LP];
-                  fa[k].x = fmaf(wj, f4.x, fa[k].x);
-                  fa[k].y = fmaf(wj, f4.y, fa[k].y);
-                  fa[k].z = fmaf(wj, f4.z, fa[k].z);
-                  fa[k].w = fmaf(wj, f4.w, fa[k].w);
-                }
-            }
-          }
-        } else {
-          // generic C: one wave reduction per channel and chunk, the row's running sum lives in `of` (owner-only, in order)
-          for (int ch = 0; ch < C; ++ch) {
-            const float p = wscan::reduce<wscan::Add>(live ? w * feat[i * C + ch] : 0.f);
-            if (lane == 0) of[ray * C + ch] = (i0 == sb ? 0.f : of[ray * C + ch]) + p;
-          }
-        }
-      }
+      if (of) accumulate_rows(feat, of, ray, sb, i0, (int)(se - i0 < 64 ? se - i0 : 64), w, C, LP, K, lane, fa);
     }
-    if (of) {
-      if (K > 0) {
-#pragma unroll
-        for (int k = 0; k < kMaxK; ++k)
-          if (k < K) {
-            float4 v = fa[k];
-            v.x = class_sum(v.x, LP), v.y = class_sum(v.y, LP), v.z = class_sum(v.z, LP), v.w = class_sum(v.w, LP);
-            if (lane < LP) reinterpret_cast<float4*>(of + ray * C)[sub + k * LP] = v;
-          }
-      } else if (sb >= se) {
-        for (int ch = lane; ch < C; ch += 64) of[ray * C + ch] = 0.f;
-      }
-    }
+    if (of) store_rows(of, ray, sb >= se, C, LP, K, lane, fa);
     if (oa) {
       acc = wscan::reduce<wscan::Add>(acc);
       if (lane == 0) oa[ray] = acc;
@@ -161,6 +173,57 @@ __global__ __launch_bounds__(64 * kWaves) void fwd_kernel(const float* __restric
       if (lane == 0) od[ray] = dep;
     }
   }
+}
+
+// What reaches the weights of one chunk of `ray` from the per-ray and per-sample cotangents (bwd_kernel: G), lane = sample:
+// the chunk starts at i0 with cnt live samples, g4 = the ray's row of gF (vector path), ga / gd its gA / gD.  With `write`,
+// the chunk's rows of gf = w gF.  feat == NULL: no feature term (and gF, gf are not touched).
+__device__ __forceinline__ float upstream_of_chunk(const float* __restrict__ ts, const float* __restrict__ te,
+                                                   const float* __restrict__ feat, const float* __restrict__ gF,
+                                                   const float* __restrict__ gW, float* __restrict__ gf, int64_t ray,
+                                                   int C, int LP, int K, const float4 (&g4)[kMaxK], float ga, float gd,
+                                                   bool has_gd, int64_t i0, int cnt, float w, bool write, int lane) {
+  const int sub = lane & (LP - 1), sl = lane / LP, spw = 64 / LP;
+  const int64_t i = i0 + lane;
+  const bool live = lane < cnt;
+  float G = ga;
+  if (gW && live) G += gW[i];
+  if (has_gd && live) G += gd * ((ts[i] + te[i]) / 2.f);
+  if (feat) {
+    float qs = 0.f;
+    if (K > 0) {
+      for (int j0 = 0; j0 < cnt; j0 += spw) {
+        const int j = j0 + sl;
+        const float wj = __shfl(w, j, 64);
+        float q = 0.f;
+        if (j < cnt) {
+          const float4* fp = reinterpret_cast<const float4*>(feat + (i0 + j) * C) + sub;
+          float4* gp = reinterpret_cast<float4*>(gf + (i0 + j) * C) + sub;
+#pragma unroll
+          for (int k = 0; k < kMaxK; ++k)
+            if (k < K) {
+              const float4 f4 = fp[k * LP];
+              q = fmaf(g4[k].x, f4.x, q);
+              q = fmaf(g4[k].y, f4.y, q);
+              q = fmaf(g4[k].z, f4.z, q);
+              q = fmaf(g4[k].w, f4.w, q);
+              if (write && gf) gp[k * LP] = make_float4(wj * g4[k].x, wj * g4[k].y, wj * g4[k].z, wj * g4[k].w);
+            }
+        }
+        q = group_sum(q, LP);
+        const float t = __shfl(q, (lane & (spw - 1)) * LP, 64);  // sample j0 + s sits in the lanes [s LP, (s+1) LP)
+        if ((lane & ~(spw - 1)) == j0) qs = t;
+      }
+    } else if (live) {
+      for (int ch = 0; ch < C; ++ch) {
+        const float g = gF[ray * C + ch];
+        qs = fmaf(g, feat[i * C + ch], qs);
+        if (write && gf) gf[i * C + ch] = w * g;
+      }
+    }
+    G += qs;
+  }
+  return live ? G : 0.f;
 }
 
 // Backward of every packed op.  Upstream: gF [R,C] (with feat), gD [R], gA [R] per ray, gW [M] on the weights and gT [M] on
@@ -178,7 +241,7 @@ __global__ __launch_bounds__(64 * kWaves) void bwd_kernel(const float* __restric
                                                           int64_t R, int C, int LP, int K, float* __restrict__ gx,
                                                           float* __restrict__ gf) {
   const int lane = threadIdx.x & 63;
-  const int sub = lane & (LP - 1), sl = lane / LP, spw = 64 / LP;
+  const int sub = lane & (LP - 1);
   for (int64_t ray = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); ray < R; ray += (int64_t)gridDim.x * kWaves) {
     const int64_t sb = seg[ray], se = seg[ray + 1];
     if (sb >= se) continue;
@@ -190,48 +253,8 @@ __global__ __launch_bounds__(64 * kWaves) void bwd_kernel(const float* __restric
     for (int k = 0; k < kMaxK; ++k)
       g4[k] = (feat && k < K) ? reinterpret_cast<const float4*>(gF + ray * C)[sub + k * LP] : make_float4(0.f, 0.f, 0.f, 0.f);
 
-    // G of the chunk at i0 (cnt live samples), lane = sample; with `write`, the chunk's rows of gf from the weights w
     auto upstream = [&](int64_t i0, int cnt, float w, bool write) -> float {
-      const int64_t i = i0 + lane;
-      const bool live = lane < cnt;
-      float G = ga;
-      if (gW && live) G += gW[i];
-      if (gD && live) G += gd * ((ts[i] + te[i]) / 2.f);
-      if (feat) {
-        float qs = 0.f;
-        if (K > 0) {
-          for (int j0 = 0; j0 < cnt; j0 += spw) {
-            const int j = j0 + sl;
-            const float wj = __shfl(w, j, 64);
-            float q = 0.f;
-            if (j < cnt) {
-              const float4* fp = reinterpret_cast<const float4*>(feat + (i0 + j) * C) + sub;
-              float4* gp = reinterpret_cast<float4*>(gf + (i0 + j) * C) + sub;
-#pragma unroll
-              for (int k = 0; k < kMaxK; ++k)
-                if (k < K) {
-                  const float4 f4 = fp[k * LP];
-                  q = fmaf(g4[k].x, f4.x, q);
-                  q = fmaf(g4[k].y, f4.y, q);
-                  q = fmaf(g4[k].z, f4.z, q);
-                  q = fmaf(g4[k].w, f4.w, q);
-                  if (write && gf) gp[k * LP] = make_float4(wj * g4[k].x, wj * g4[k].y, wj * g4[k].z, wj * g4[k].w);
-                }
-            }
-            q = group_sum(q, LP);
-            const float t = __shfl(q, (lane & (spw - 1)) * LP, 64);  // sample j0 + s sits in the lanes [s LP, (s+1) LP)
-            if ((lane & ~(spw - 1)) == j0) qs = t;
-          }
-        } else if (live) {
-          for (int ch = 0; ch < C; ++ch) {
-            const float g = gF[ray * C + ch];
-            qs = fmaf(g, feat[i * C + ch], qs);
-            if (write && gf) gf[i * C + ch] = w * g;
-          }
-        }
-        G += qs;
-      }
-      return live ? G : 0.f;
+      return upstream_of_chunk(ts, te, feat, gF, gW, gf, ray, C, LP, K, g4, ga, gd, gD != nullptr, i0, cnt, w, write, lane);
     };
 
     if (MODE == kWeights) {
@@ -326,6 +349,143 @@ __global__ __launch_bounds__(64 * kWaves) void bwd_kernel(const float* __restric
       }
       suffix += wscan::first(incl_r);
     }
+  }
+}
+
+// ---- head + packed compositing (training: nrhip_sdf_render_packed_fwd / _bwd), the packed sibling of train_fused.hip's
+// sdf_render kernels.  x [M] is the geometry MLP's first output; beta_ptr points at the RAW parameter on the device (no host
+// read), NULL selects the density head:
+//   SDF head      alpha = sigmoid(-x (|beta| + beta_min))
+//   density head  alpha = 1 - exp(-trunc_exp(x) (te - ts))          (d trunc_exp = exp(clamp(x, -15, 15)))
+// and the compositing is fwd_kernel<kAlpha>'s on those alphas -- no sky residual, depth over all samples, zeros for a ray
+// without samples.  The alphas are an output: the backward starts from them.
+__device__ __forceinline__ float head_alpha(float x, float delta, bool dens, float beta) {
+  return dens ? -expm1f(-expf(x) * delta) : sigmoidf_(-x * beta);
+}
+
+__global__ __launch_bounds__(64 * kWaves) void head_fwd_kernel(const float* __restrict__ ts, const float* __restrict__ te,
+                                                               const float* __restrict__ x,
+                                                               const float* __restrict__ beta_ptr, float beta_min,
+                                                               const float* __restrict__ feat,
+                                                               const int64_t* __restrict__ seg, int64_t R, int C, int LP,
+                                                               int K, float* __restrict__ oal, float* __restrict__ ow,
+                                                               float* __restrict__ of, float* __restrict__ od,
+                                                               float* __restrict__ oa) {
+  const int lane = threadIdx.x & 63;
+  const bool dens = beta_ptr == nullptr;
+  const float beta = dens ? 0.f : fabsf(*beta_ptr) + beta_min;
+  for (int64_t ray = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); ray < R; ray += (int64_t)gridDim.x * kWaves) {
+    const int64_t sb = seg[ray], se = seg[ray + 1];
+    float carry = 1.f, acc = 0.f, dep = 0.f;
+    float4 fa[kMaxK];
+#pragma unroll
+    for (int k = 0; k < kMaxK; ++k) fa[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t i0 = sb; i0 < se; i0 += 64) {
+      const int64_t i = i0 + lane;
+      const bool live = i < se;
+      const float t0 = live ? ts[i] : 0.f, t1 = live ? te[i] : 0.f;
+      const float alpha = live ? head_alpha(x[i], t1 - t0, dens, beta) : 0.f;
+      const float incl = wscan::incl<wscan::Mul>(1.f - alpha, lane);
+      const float w = alpha * (carry * wscan::shift_up1(incl, 1.f, lane));
+      carry *= wscan::last(incl);
+      if (live) {
+        if (oal) oal[i] = alpha;
+        if (ow) ow[i] = w;
+      }
+      acc += w;
+      dep += w * ((t0 + t1) / 2.f);
+      accumulate_rows(feat, of, ray, sb, i0, (int)(se - i0 < 64 ? se - i0 : 64), w, C, LP, K, lane, fa);
+    }
+    store_rows(of, ray, sb >= se, C, LP, K, lane, fa);
+    acc = wscan::reduce<wscan::Add>(acc);
+    dep = wscan::reduce<wscan::Add>(dep);
+    if (lane == 0) {
+      oa[ray] = acc;
+      od[ray] = dep;
+    }
+  }
+}
+
+// Backward: bwd_kernel<kAlpha>'s suffix scan over the saved alphas, chained into the head.  (An alpha of exactly 1 needs
+// no restarted product scan here: both heads multiply d alpha by 1 - alpha.)  gx [M] = d x, gf [M,C] = w gF, and d beta
+// leaves as one partial per WAVE in gb_part [gridDim.x * kWaves] (its rays in grid-stride order: a function of R alone),
+// summed in a fixed order by beta_reduce_kernel -- no atomics, bitwise reproducible.  feat == NULL: no gF upstream.
+__global__ __launch_bounds__(64 * kWaves) void head_bwd_kernel(
+    const float* __restrict__ ts, const float* __restrict__ te, const float* __restrict__ x,
+    const float* __restrict__ beta_ptr, float beta_min, const float* __restrict__ al, const float* __restrict__ feat,
+    const int64_t* __restrict__ seg, const float* __restrict__ gF, const float* __restrict__ gD,
+    const float* __restrict__ gA, const float* __restrict__ gW, int64_t R, int C, int LP, int K, float* __restrict__ gx,
+    float* __restrict__ gf, float* __restrict__ gb_part) {
+  const int lane = threadIdx.x & 63;
+  const int sub = lane & (LP - 1);
+  const bool dens = beta_ptr == nullptr;
+  const float beta = dens ? 0.f : fabsf(*beta_ptr) + beta_min;
+  float gb = 0.f;
+  for (int64_t ray = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6); ray < R; ray += (int64_t)gridDim.x * kWaves) {
+    const int64_t sb = seg[ray], se = seg[ray + 1];
+    if (sb >= se) continue;
+    const int64_t n = se - sb;
+    const int64_t nchunk = (n + 63) / 64;
+    const float gd = gD ? gD[ray] : 0.f, ga = gA ? gA[ray] : 0.f;
+    float4 g4[kMaxK];
+#pragma unroll
+    for (int k = 0; k < kMaxK; ++k)
+      g4[k] = (feat && k < K) ? reinterpret_cast<const float4*>(gF + ray * C)[sub + k * LP] : make_float4(0.f, 0.f, 0.f, 0.f);
+    // the forward's carry into every chunk, lane c keeps chunk c's (chunks past 63 restart from chunk 63's)
+    float saved = 1.f;
+    {
+      float carry = 1.f;
+      for (int64_t ch = 0; ch < nchunk; ++ch) {
+        if (lane == ch) saved = carry;
+        const int64_t i = sb + ch * 64 + lane;
+        carry *= wscan::last(wscan::incl<wscan::Mul>(i < se ? 1.f - al[i] : 1.f, lane));
+      }
+    }
+    float suffix = 0.f;  // sum over the samples of later chunks
+    for (int64_t ch = nchunk - 1; ch >= 0; --ch) {
+      float carry = __shfl(saved, (int)(ch < 63 ? ch : 63), 64);
+      for (int64_t p = 63; p < ch; ++p)  // rays longer than 4096 samples: walk on from chunk 63 (full chunks)
+        carry *= wscan::last(wscan::incl<wscan::Mul>(1.f - al[sb + p * 64 + lane], lane));
+      const int64_t s = ch * 64 + lane, i = sb + s;
+      const bool live = s < n;
+      const int cnt = (int)(n - ch * 64 < 64 ? n - ch * 64 : 64);
+      const float alpha = live ? al[i] : 0.f;
+      const float incl = wscan::incl<wscan::Mul>(1.f - alpha, lane);
+      const float T = carry * wscan::shift_up1(incl, 1.f, lane);
+      const float G = upstream_of_chunk(ts, te, feat, gF, gW, gf, ray, C, LP, K, g4, ga, gd, gD != nullptr, sb + ch * 64, cnt,
+                                        live ? alpha * T : 0.f, true, lane);
+      const float term = live ? G * alpha * T : 0.f;
+      const float incl_r = wscan::rincl<wscan::Add>(term, lane);
+      const float after = wscan::shift_down1(incl_r, 0.f, lane) + suffix;  // sum_{k>i} G_k w_k
+      if (live) {
+        const float xi = x[i];
+        if (dens) {
+          // d sigma = delta (G T (1 - alpha) - after), then trunc_exp's backward
+          const float gsig = (G * T * (1.f - alpha) - after) * (te[i] - ts[i]);
+          gx[i] = gsig * expf(fminf(fmaxf(xi, -15.f), 15.f));
+        } else {
+          const float gal = G * T - after / fmaxf(1.f - alpha, 1e-10f);
+          const float ds = gal * alpha * (1.f - alpha);  // sigmoid'(u), u = -x beta
+          gx[i] = -ds * beta;
+          gb -= ds * xi;
+        }
+      }
+      suffix += wscan::first(incl_r);
+    }
+  }
+  gb = wscan::reduce<wscan::Add>(gb);
+  if (lane == 0) gb_part[blockIdx.x * kWaves + (threadIdx.x >> 6)] = gb;
+}
+
+// d beta = sign(beta) sum(partials): one wavefront, fixed summation order
+__global__ __launch_bounds__(64) void beta_reduce_kernel(const float* __restrict__ part, int n,
+                                                         const float* __restrict__ beta_ptr, float* __restrict__ out) {
+  float t = 0.f;
+  for (int i = threadIdx.x; i < n; i += 64) t += part[i];
+  t = wscan::reduce<wscan::Add>(t);
+  if (threadIdx.x == 0) {
+    const float b = *beta_ptr;
+    out[0] = b > 0.f ? t : (b < 0.f ? -t : 0.f);  // d|b|/db = sign(b), 0 at 0 like torch
   }
 }
 

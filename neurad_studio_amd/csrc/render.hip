@@ -41,7 +41,9 @@
 //     ray's base and sample count are two scalar loads of `segments`; the pipeline's "wrap to the next ray" decisions use the
 //     PENDING ray's own tile count; the ray constants stay per ray, so no per-sample copy of them and no per-sample feature
 //     exists anywhere on the route.  Compositing is nrhip_packed_composite_fwd's: no sky residual, depth over all samples,
-//     zeros for a ray without samples (which costs one dead tile's gathers and no MLP).
+//     zeros for a ray without samples (which costs one dead tile's gathers and no MLP).  The per-sample kernel (Lay::PackedRows, training:
+//     nrhip_field_fwd_train_packed) stores at the packed sample index and carries no compositing state: a lane past the
+//     ray's end and a ray without samples store nothing.
 // The sky residual (models/neurad.py:381: w_{S-1} += 1 - sum w) is folded into the last tile -- the accumulated weight is
 // complete there, so no copy of the last sample's features has to be kept.
 #include "common.h"
@@ -789,7 +791,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
   constexpr bool COMPOSITE = OUT == Out::Composite;
   constexpr bool ACT = SRC == Src::Actors, RELAY = SRC == Src::EvalTable, OVR = SRC == Src::Overrides;
   constexpr bool PAIRS = PROD == Prod::F16Pairs;
-  constexpr bool PACKED = LAY == Lay::Packed;
+  constexpr bool PACKED = LAY != Lay::Dense;  // (Packed: composited, PackedRows: per-sample rows)
   const int64_t* const segs = reinterpret_cast<const int64_t*>(tables);  // PACKED: [R + 1]
   // OVR (training forward of a scene with dynamic actors): samples inside an actor box take their encoding row and view
   // direction from the caller (the differentiable actor branch computed them for the few hit samples) instead of the
@@ -995,8 +997,8 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     __builtin_amdgcn_sched_barrier(0);
 
     if constexpr (PACKED) {
-      if (cn <= 0) {  // wave-uniform: a ray without samples writes its zeros and runs no MLP on the dead tile
-        if (j == 0) {
+      if (cn <= 0) {  // wave-uniform: a ray without samples writes its zeros (per-sample output: nothing) and runs no MLP
+        if (COMPOSITE && j == 0) {
           float* fp = out_feat + ray * 32;
           *reinterpret_cast<f32x4*>(fp + 4 * g) = f32x4{0.f, 0.f, 0.f, 0.f};
           *reinterpret_cast<f32x4*>(fp + 16 + 4 * g) = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1015,7 +1017,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     int64_t srow = 0;
     if constexpr (!COMPOSITE) {
       saving = sv.enc != nullptr && live;
-      srow = ray * S + s;
+      srow = PACKED ? (int64_t)cb + s : ray * S + s;  // (PACKED: the packed sample index; the ray constants stay per ray)
       if (saving) {
         constexpr float u = PAIRS ? 1.f / kPairAct : 1.f;  // (tile units -> true units: a power of two, exact)
         float* ep = sv.enc + srow * EF::LF + EF::W * g;  // dense [N, L*F]: this lane group's W columns
@@ -1145,12 +1147,13 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
         o[1] += e[1];
       }
       if (live) {
-        float* fp = out_feat + (ray * S + s) * 32;
+        const int64_t si = PACKED ? (int64_t)cb + s : ray * S + s;
+        float* fp = out_feat + si * 32;
         stream_store(fp + 4 * g, o[0]);
         stream_store(fp + 16 + 4 * g, o[1]);
         if (g == 0) {
-          out_sdf[ray * S + s] = sdf;
-          out_alpha[ray * S + s] = a_or_d;
+          out_sdf[si] = sdf;
+          out_alpha[si] = a_or_d;
         }
       }
     } else {
@@ -1327,7 +1330,7 @@ struct RenderArgs {
 
 template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD, Lay LAY = Lay::Dense>
 static int launch_render(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
-  constexpr bool OVR = SRC == Src::Overrides, PACKED = LAY == Lay::Packed;
+  constexpr bool OVR = SRC == Src::Overrides, PACKED = LAY != Lay::Dense;
   constexpr size_t lds = ((SRC == Src::Actors || OVR) ? Lds<H, PROD>::TOTAL_ACT : Lds<H, PROD>::TOTAL) * sizeof(float);
   auto kern = render_kernel<L, F, H, HALF, OUT, SRC, PROD, LAY>;
   static int cap = 0;  // persistent grid: CUs x resident workgroups per CU, queried once per instantiation
@@ -1411,8 +1414,9 @@ static int dispatch_render(const nrhip_field* f, const nrhip_rays* rays, Out out
 // A row of the table in the packed layout, where render_variant_ok admits it (the packed kernels have no rows of their own)
 template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD>
 static int launch_packed_row(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
-  if constexpr (render_variant_ok(L, F, OUT, SRC, PROD, Lay::Packed)) {
-    return launch_render<L, F, H, HALF, OUT, SRC, PROD, Lay::Packed>(fd, rd, a);
+  constexpr Lay LAY = OUT == Out::Composite ? Lay::Packed : Lay::PackedRows;
+  if constexpr (render_variant_ok(L, F, OUT, SRC, PROD, LAY)) {
+    return launch_render<L, F, H, HALF, OUT, SRC, PROD, LAY>(fd, rd, a);
   } else {
     set_error("fused field kernel: no packed form of this variant");
     return NRHIP_ERR_UNSUPPORTED;
@@ -1421,9 +1425,10 @@ static int launch_packed_row(const FieldDev& fd, const RaysDev& rd, const Render
 
 // dispatch_render for packed samples: choose_variant's preference among the rows that have a packed form (the fp16
 // pairs where the table has them, else the fp32 MFMA).  rd.S carries M, a.segments the segments.
-static int dispatch_render_packed(const nrhip_field* f, const RaysDev& rd, const RenderArgs& a) {
-  Variant v = choose_variant(f, Out::Composite, Src::Static);
-  if (!render_variant_ok(v.L, v.F, v.out, v.src, v.prod, Lay::Packed)) v.src = Src::Static, v.prod = Prod::F32;
+static int dispatch_render_packed(const nrhip_field* f, Out out, const RaysDev& rd, const RenderArgs& a) {
+  Variant v = choose_variant(f, out, Src::Static);
+  if (!render_variant_ok(v.L, v.F, v.out, v.src, v.prod, out == Out::Composite ? Lay::Packed : Lay::PackedRows))
+    v.src = Src::Static, v.prod = Prod::F32;
   const FieldDev fd = to_dev(*f);
   const bool half = f->grid.param_dtype == 1;
 #define X(L_, F_, H_, O_, S_, P_)                                                                \
@@ -1578,7 +1583,26 @@ extern "C" int nrhip_render_fwd_packed(const nrhip_field* f, const nrhip_packed_
   a.feat = out_features, a.depth = out_depth, a.acc = out_acc, a.w = out_weights;
   a.stop_eps = early_stop_eps, a.stream = st, a.segments = rays->segments;
   const RaysDev rd{R, (int)M, 0, rays->origins, rays->directions, rays->pixel_area, rays->t_starts, rays->t_ends, rays->order};
-  return dispatch_render_packed(f, rd, a);
+  return dispatch_render_packed(f, Out::Composite, rd, a);
+}
+
+extern "C" int nrhip_field_fwd_train_packed(const nrhip_field* f, const nrhip_packed_rays* rays, float* feature,
+                                            float* geo_out, float* head, float* save_enc, float* save_geo_hidden,
+                                            float* save_feat_in, float* save_feat_hidden, void* stream) {
+  if (int e = validate_field(f)) return e;
+  NR_REQUIRE(rays, NRHIP_ERR_INVALID_ARG, "field_fwd_train_packed: rays descriptor is NULL");
+  const int64_t R = rays->n_rays, M = rays->n_samples;
+  NR_REQUIRE(R >= 0 && M >= 0, NRHIP_ERR_INVALID_ARG, "field_fwd_train_packed: negative ray/sample count");
+  if (R == 0 || M == 0) return NRHIP_OK;  // nothing per sample to write: no pointer is read
+  NR_REQUIRE(M < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "field_fwd_train_packed: M >= 2^31");
+  RenderArgs a{};
+  a.feat = feature, a.sdf = geo_out, a.alpha = head, a.stream = (hipStream_t)stream, a.segments = rays->segments;
+  a.sv = SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
+  if (int e = check_train_buffers("field_fwd_train_packed", feature, geo_out, head, a.sv)) return e;
+  NR_REQUIRE(rays->origins && rays->directions && rays->pixel_area && rays->t_starts && rays->t_ends && rays->segments,
+             NRHIP_ERR_INVALID_ARG, "field_fwd_train_packed: rays descriptor has a NULL pointer");
+  const RaysDev rd{R, (int)M, 0, rays->origins, rays->directions, rays->pixel_area, rays->t_starts, rays->t_ends, rays->order};
+  return dispatch_render_packed(f, Out::PerSample, rd, a);
 }
 
 extern "C" int nrhip_render_fwd_actors(const nrhip_field* f, const nrhip_actors* a, const nrhip_rays* rays,

@@ -165,6 +165,11 @@ class NeuRADField(nn.Module):
         render_variant_ok); scenes with dynamic actors take the operator path."""
         return not self.hashgrid.has_actors() and self.fused_supported()
 
+    def fused_packed_train_supported(self) -> bool:
+        """Can ``render_train_packed`` train this field on PACKED samples as one node?  ``fused_packed_supported`` (static
+        scene, a fused configuration) with the fused training forward's own condition (biases on every layer)."""
+        return self.fused_packed_supported() and self._fused_train_ok()
+
     def train(self, mode: bool = True):
         """a mode switch drops the cached host copy of beta: writes through ``beta.data`` (EMA / weight averaging, some
         optimizers) do not bump the version counter the cache is keyed on, and they happen between training and eval"""
@@ -245,6 +250,40 @@ class NeuRADField(nn.Module):
                 segments = ops.packed_segments(ray_indices, int(num_rays))
             return ops.render_fwd_packed(self.field_spec(), origins, directions, pixel_area, t_starts, t_ends, segments,
                                          return_weights, early_stop_eps=early_stop_eps, order=order)
+
+    def render_train_packed(self, origins, directions, pixel_area, t_starts, t_ends, *, segments: Optional[Tensor] = None,
+                            ray_indices: Optional[Tensor] = None, num_rays: Optional[int] = None):
+        """Training counterpart of ``render_packed``: field -> head (learnable-beta SDF head, or trunc_exp) -> packed
+        compositing as ONE autograd node (autograd.NffRenderPackedTrainFn).  Arguments as ``render_packed``: per-RAY origins
+        / directions [R,3] and pixel_area [R] (or [R,1]), per-sample t_starts / t_ends [M], exactly one of ``segments`` int64
+        [R+1] or ``ray_indices`` int64 [M] (sorted) + ``num_rays``; the other one is derived on the device.
+        -> features [R,32], depth [R,1] (sum w mid), accumulation [R,1], weights [M]; compositing as
+        renderers.render_packed.  Gradients reach the table, the MLPs and beta -- not the rays."""
+        if (segments is None) == (ray_indices is None):
+            raise ValueError("render_train_packed: give exactly one of segments / ray_indices (+ num_rays)")
+        if ray_indices is not None and num_rays is None:
+            raise ValueError("render_train_packed: ray_indices needs num_rays")
+        operator = "use the operator route, forward() on the packed RaySamples + renderers.render_packed"
+        if self.hashgrid.has_actors():
+            raise NotImplementedError(f"render_train_packed: the occupancy route is static, no dynamic actors; {operator}")
+        if not self.fused_packed_train_supported():
+            raise NotImplementedError(f"render_train_packed: a fused-kernel configuration only (see fused_supported); {operator}")
+        if torch.is_grad_enabled() and (origins.requires_grad or directions.requires_grad):
+            raise NotImplementedError(f"render_train_packed: no gradient reaches the rays through packed samples; {operator}")
+        hg, g = self.hashgrid, self.hashgrid.static_grid
+        t_starts, t_ends = t_starts.reshape(-1), t_ends.reshape(-1)
+        with torch.no_grad():
+            if segments is None:
+                segments = ops.packed_segments(ray_indices, int(num_rays))
+            else:
+                ray_indices = ops.packed_ray_indices(segments, t_starts.shape[0])
+            order = ops.ray_order(origins, directions, hg.static_scale) if (self.order_rays and origins.shape[0]) else None
+        beta, beta_min = (self.sdf_to_density.beta, self.sdf_to_density.beta_min_value) if self.config.use_sdf else (None, 0.0)
+        return ag.NffRenderPackedTrainFn.apply(
+            g.hash_table, g.spec, hg.static_scale, beta, beta_min, origins, directions, pixel_area.reshape(-1), t_starts,
+            t_ends, segments, ray_indices.reshape(-1), order,
+            *[t for l in self.mlp_geo.layers for t in (l.weight, l.bias)],
+            *[t for l in self.mlp_feature.layers for t in (l.weight, l.bias)])
 
     def render_train(self, origins, directions, pixel_area, edges, appearance=None, times: Optional[Tensor] = None,
                      actor_cand=None):

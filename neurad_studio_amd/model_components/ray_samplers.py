@@ -211,8 +211,10 @@ class VolumetricSampler(Sampler):
         raise RuntimeError("The VolumetricSampler fuses sample generation and density check together. "
                            "Please call forward() directly.")
 
-    def _march(self, ray_bundle: RayBundle, render_step_size, near_plane, far_plane, alpha_thre, cone_angle):
-        """-> contiguous origins, directions and the march's packed (ray_indices, starts, ends)"""
+    def _march(self, ray_bundle: RayBundle, render_step_size, near_plane, far_plane, alpha_thre, cone_angle,
+               stratified: Optional[bool] = None):
+        """-> contiguous origins, directions and the march's packed (ray_indices, starts, ends).  stratified: None = in
+        training mode only"""
         rays_o, rays_d = ray_bundle.origins.contiguous(), ray_bundle.directions.contiguous()
         t_min = t_max = None
         if ray_bundle.nears is not None and ray_bundle.fars is not None:
@@ -221,7 +223,8 @@ class VolumetricSampler(Sampler):
             rays_o=rays_o, rays_d=rays_d, t_min=t_min, t_max=t_max,
             sigma_fn=self._wrap(self.density_fn, rays_o, rays_d, ray_bundle.times),
             alpha_fn=self._wrap(self.alpha_fn, rays_o, rays_d, ray_bundle.times), render_step_size=render_step_size,
-            near_plane=near_plane, far_plane=1e10 if far_plane is None else far_plane, stratified=self.training,
+            near_plane=near_plane, far_plane=1e10 if far_plane is None else far_plane,
+            stratified=self.training if stratified is None else stratified,
             cone_angle=cone_angle, alpha_thre=alpha_thre)
         return rays_o, rays_d, ray_indices, starts, ends
 
@@ -269,6 +272,36 @@ class VolumetricSampler(Sampler):
         if getattr(field, "fused_packed_supported", lambda: False)():
             f, d, a, w = field.render_packed(rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri, num_rays=R,
                                              return_weights=True, early_stop_eps=early_stop_eps)
+            return {"features": f, "depth": d, "accumulation": a, "weights": w[:, None], **marched}
+        from ..field_components.field_heads import FieldHeadNames
+        from .renderers import render_packed
+
+        if starts.shape[0] == 0:
+            z = lambda c: torch.zeros((R, c), device=rays_o.device, dtype=torch.float32)  # noqa: E731
+            return {"features": z(field.config.nff_out_dim), "depth": z(1), "accumulation": z(1),
+                    "weights": starts.new_zeros((0, 1)), **marched}
+        rs = self._gather(ray_bundle, rays_o, rays_d, ri, starts, ends)
+        out = field(rs)
+        kw = {"alpha": out[FieldHeadNames.ALPHA]} if FieldHeadNames.ALPHA in out else {"density": out[FieldHeadNames.DENSITY]}
+        return {**render_packed(out[FieldHeadNames.FEATURE], rs, ri, R, **kw), **marched}
+
+    def render_train(self, field, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0,
+                     far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0) -> dict:
+        """Training counterpart of ``render``: a stratified march + field + compositing with autograd -> the same keys.  A
+        field that trains on packed samples as one node (``fused_packed_train_supported``, ``fused_training`` on) gets the
+        BUNDLE'S per-ray tensors and the packed intervals (``render_train_packed``: no per-sample copy of origins /
+        directions / pixel area, the head and the compositing in one kernel each way).  Any other field, ``fused_training =
+        False`` and rays that require grad (the node sends no gradient to them) take forward() on the gathered RaySamples +
+        renderers.render_packed.  A march without samples returns zero rows."""
+        R = ray_bundle.origins.shape[0]
+        rays_o, rays_d, ri, starts, ends = self._march(ray_bundle, render_step_size, near_plane, far_plane, alpha_thre,
+                                                       cone_angle, stratified=True)
+        marched = {"ray_indices": ri, "t_starts": starts, "t_ends": ends}
+        rays_need_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+        if (getattr(field, "fused_training", False) and not rays_need_grad
+                and getattr(field, "fused_packed_train_supported", lambda: False)()):
+            f, d, a, w = field.render_train_packed(rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri,
+                                                   num_rays=R)
             return {"features": f, "depth": d, "accumulation": a, "weights": w[:, None], **marched}
         from ..field_components.field_heads import FieldHeadNames
         from .renderers import render_packed

@@ -1399,17 +1399,14 @@ def packed_composite_fwd(t_starts, t_ends, sigmas_or_alphas, features, segments,
     return of, od, oa, ow
 
 
-def render_fwd_packed(fs: FieldSpec, origins, directions, pixel_area, t_starts, t_ends, segments,
-                      return_weights: bool = False, early_stop_eps: float = 0.0, order: Optional[Tensor] = None):
-    """The fused render kernel on the march's packed samples: per-RAY origins [R,3] / directions [R,3] / pixel_area [R],
-    per-sample t_starts / t_ends [M], segments int64 [R+1] -> features [R,32], depth [R,1] (sum w mid, not normalised),
-    accumulation [R,1] (, weights [M]); compositing as ``packed_composite_fwd`` (no sky residual, zeros for a ray without
-    samples).  early_stop_eps / order: see ``render_fwd``."""
+def _c_packed_rays(who: str, origins, directions, pixel_area, t_starts, t_ends, segments, order: Optional[Tensor] = None):
+    """-> (nrhip_packed_rays, the tensors it points to): per-RAY origins [R,3] / directions [R,3] / pixel_area [R], per-sample
+    t_starts / t_ends [M], segments int64 [R+1], optional processing order int32 [R]"""
     o, d = _chk(origins, "origins"), _chk(directions, "directions")
     a = _chk(pixel_area.reshape(-1), "pixel_area")
     seg, R = _seg(segments)
     if o.shape != (R, 3) or d.shape != (R, 3) or a.shape != (R,):
-        raise ValueError(f"render_fwd_packed: origins / directions [R,3] and pixel_area [R] with R = {R} = len(segments) - 1")
+        raise ValueError(f"{who}: origins / directions [R,3] and pixel_area [R] with R = {R} = len(segments) - 1")
     s = _flat(t_starts, "t_starts")
     e = _flat(t_ends, "t_ends", s.shape[0])
     r = _lib.PackedRays()
@@ -1421,11 +1418,130 @@ def render_fwd_packed(fs: FieldSpec, origins, directions, pixel_area, t_starts, 
         if order.shape != (R,):
             raise ValueError(f"order must be int32 [R={R}], got {tuple(order.shape)}")
         r.order = order.data_ptr()
-    f, keep = fs.c_field()
-    feats, depth, acc, _ = _render_outputs(R, 0, o.device, False)
-    w = torch.empty_like(s) if return_weights else None
+    return r, (o, d, a, s, e, seg, order)
+
+
+def render_fwd_packed(fs: FieldSpec, origins, directions, pixel_area, t_starts, t_ends, segments,
+                      return_weights: bool = False, early_stop_eps: float = 0.0, order: Optional[Tensor] = None):
+    """The fused render kernel on the march's packed samples: per-RAY origins [R,3] / directions [R,3] / pixel_area [R],
+    per-sample t_starts / t_ends [M], segments int64 [R+1] -> features [R,32], depth [R,1] (sum w mid, not normalised),
+    accumulation [R,1] (, weights [M]); compositing as ``packed_composite_fwd`` (no sky residual, zeros for a ray without
+    samples).  early_stop_eps / order: see ``render_fwd``."""
+    r, keep = _c_packed_rays("render_fwd_packed", origins, directions, pixel_area, t_starts, t_ends, segments, order)
+    f, keep2 = fs.c_field()
+    feats, depth, acc, _ = _render_outputs(r.n_rays, 0, keep[0].device, False)
+    w = torch.empty_like(keep[3]) if return_weights else None
     launch("nrhip_render_fwd_packed", f, r, feats, depth, acc, w, float(early_stop_eps))
     return (feats, depth, acc, w) if return_weights else (feats, depth, acc)
+
+
+def field_fwd_train_packed(fs: FieldSpec, origins, directions, pixel_area, t_starts, t_ends, segments,
+                           order: Optional[Tensor] = None, out=None):
+    """``field_fwd_train`` on the march's packed samples (ray constants per RAY, every row at the packed sample index):
+    -> (feature [M,32], geo_out [M], head [M]), (enc [M,L*F], geo_hidden [M,H], feat_in [M,48], feat_hidden [M,2H]).
+    ``out``: the seven buffers to write into (rows past M are left alone)."""
+    r, keep = _c_packed_rays("field_fwd_train_packed", origins, directions, pixel_area, t_starts, t_ends, segments, order)
+    f, keep2 = fs.c_field()
+    m, dev = r.n_samples, keep[0].device
+    H, LF = fs.geo_w[0].shape[0], fs.grid.out_dim
+    if out is None:
+        mk = lambda *c: torch.empty((m, *c), device=dev, dtype=torch.float32)  # noqa: E731
+        out = (mk(32), mk(), mk(), mk(LF), mk(H), mk(48), mk(2 * H))
+    else:
+        widths = (32, None, None, LF, H, 48, 2 * H)
+        out = tuple(_chk(t, "out") for t in out)
+        if len(out) != 7 or any(t.shape[0] < m or (t.shape[1:] != ((w,) if w else ())) for t, w in zip(out, widths)):
+            raise ValueError("field_fwd_train_packed: out = (feature, geo_out, head, enc, geo_hidden, feat_in, feat_hidden)")
+    launch("nrhip_field_fwd_train_packed", f, r, *out)
+    return out[:3], out[3:]
+
+
+def sdf_render_packed_fwd(geo_out, beta: Optional[Tensor], beta_min: float, features, t_starts, t_ends, segments):
+    """Head + packed compositing.  geo_out [M], beta = the raw learnable parameter (device, 1 element; None: the density
+    head, sigma = trunc_exp(geo_out)), features [M,C] -> alpha [M], weights [M], features [R,C], depth [R,1], acc [R,1]"""
+    x = _flat(geo_out, "geo_out")
+    M = x.shape[0]
+    s, e = _flat(t_starts, "t_starts", M), _flat(t_ends, "t_ends", M)
+    f = _chk(features, "features")
+    if f.dim() != 2 or f.shape[0] != M or f.shape[1] < 1:
+        raise ValueError("features must be [M,C] with one row per sample")
+    b = _opt(beta, "beta")
+    if b is not None and b.numel() != 1:
+        raise ValueError("sdf_render_packed_fwd: beta must have one element")
+    seg, R = _seg(segments)
+    Cc = f.shape[1]
+    mk = lambda *shape: torch.empty(shape, device=x.device, dtype=torch.float32)  # noqa: E731
+    alpha, w, of, od, oa = torch.empty_like(x), torch.empty_like(x), mk(R, Cc), mk(R, 1), mk(R, 1)
+    launch("nrhip_sdf_render_packed_fwd", x, b, float(beta_min), f, s, e, seg, R, Cc, alpha, w, of, od, oa)
+    return alpha, w, of, od, oa
+
+
+def sdf_render_packed_bwd(geo_out, beta: Optional[Tensor], beta_min: float, alpha, features, t_starts, t_ends, segments,
+                          g_features=None, g_depth=None, g_accumulation=None, g_weights=None):
+    """-> grad_features [M,C], grad_geo_out [M], grad_beta [1] (None for the density head).  Each upstream may be None."""
+    x = _flat(geo_out, "geo_out")
+    M = x.shape[0]
+    al, s, e = _flat(alpha, "alpha", M), _flat(t_starts, "t_starts", M), _flat(t_ends, "t_ends", M)
+    f = _chk(features, "features")
+    if f.dim() != 2 or f.shape[0] != M or f.shape[1] < 1:
+        raise ValueError("features must be [M,C] with one row per sample")
+    b = _opt(beta, "beta")
+    seg, R = _seg(segments)
+    Cc = f.shape[1]
+    gF = None
+    if g_features is not None:
+        gF = _chk(g_features, "g_features")
+        if gF.shape != (R, Cc):
+            raise ValueError(f"g_features must be [{R},{Cc}]")
+    gd = None if g_depth is None else _flat(g_depth, "g_depth", R)
+    ga = None if g_accumulation is None else _flat(g_accumulation, "g_accumulation", R)
+    gw = None if g_weights is None else _flat(g_weights, "g_weights", M)
+    gf = torch.empty_like(f) if gF is not None else torch.zeros_like(f)  # (no upstream on the features: not written)
+    gx = torch.empty_like(x)
+    gbeta = None if b is None else torch.empty((1,), device=x.device, dtype=torch.float32)
+    ws, _ = _workspace("nrhip_sdf_render_packed_bwd_workspace", R, device=x.device, dtype=torch.float32)
+    launch("nrhip_sdf_render_packed_bwd", x, b, float(beta_min), al, f, s, e, seg, gF, gd, ga, gw, R, Cc, gf, gx, gbeta, ws)
+    return gf, gx, gbeta
+
+
+def packed_ray_indices(segments: Tensor, n_samples: int) -> Tensor:
+    """segments int64 [R+1] -> the ray of every sample, int64 [M]; on the device, no host read"""
+    seg, R = _seg(segments)
+    i = torch.arange(int(n_samples), device=seg.device, dtype=torch.int64)
+    return torch.searchsorted(seg[1:], i, right=True)
+
+
+def encode_bwd_packed(spec: GridSpec, static_scale: float, origins, directions, pixel_area, t_starts, t_ends, ray_indices,
+                      grad_out, out_dtype=torch.float32):
+    """``encode_bwd`` for packed samples: ray_indices int64 [M] names each sample's ray.  -> grad table [L*T, F], in fp16
+    where the partition writes an fp16-storage table's gradient itself (as ``encode_bwd``).  Below ``_BINNED_MIN_SAMPLES``,
+    or for a table the partition cannot slice, the ray constants are gathered per sample for the atomic entry point."""
+    ri = _chk(ray_indices.reshape(-1), "ray_indices", torch.int64)
+    n = ri.shape[0]
+    grad_out = _chk(grad_out, "grad_out")
+    dev = grad_out.device
+    half = _binned_table_grad(n, out_dtype)[1]
+    gt = torch.empty((spec.table_rows, spec.features_per_level), device=dev, dtype=torch.float16 if half else torch.float32)
+    g = spec.c_grid(gt)
+    ws = _table_grad_workspace(g, n, dev)
+    if ws is None:  # a tiny batch, or tables too large to cut into LDS slices: memory-side atomics on [M,1] rays (fp32 only)
+        o, d = _chk(origins, "origins")[ri], _chk(directions, "directions")[ri]
+        a = _chk(pixel_area.reshape(-1), "pixel_area")[ri]
+        return encode_bwd(spec, static_scale, o, d, a, _flat(t_starts, "t_starts", n).reshape(n, 1),
+                          _flat(t_ends, "t_ends", n).reshape(n, 1), grad_out, out_dtype)
+    o, d, a = _chk(origins, "origins"), _chk(directions, "directions"), _chk(pixel_area.reshape(-1), "pixel_area")
+    if o.dim() != 2 or o.shape[1] != 3 or d.shape != o.shape or a.shape != (o.shape[0],):
+        raise ValueError("encode_bwd_packed: origins / directions [R,3] and pixel_area [R]")
+    s, e = _flat(t_starts, "t_starts", n), _flat(t_ends, "t_ends", n)
+    r = _lib.PackedRays()
+    r.n_rays, r.n_samples = o.shape[0], n
+    r.origins, r.directions, r.pixel_area = o.data_ptr(), d.data_ptr(), a.data_ptr()
+    r.t_starts, r.t_ends = s.data_ptr(), e.data_ptr()
+    if half:  # the fp16 gradient of an fp16-storage table, written by the partition itself
+        launch("nrhip_encode_bwd_binned_packed_f16", g, float(static_scale), r, ri, grad_out, gt, ws, ws.numel())
+    else:  # overwrite = 1: the partition writes every element of the gradient, no zero-fill
+        launch("nrhip_encode_bwd_binned_packed", g, float(static_scale), r, ri, grad_out, gt, 1, ws, ws.numel())
+    return gt
 
 
 def packed_composite_bwd(t_starts, t_ends, sigmas_or_alphas, features, segments, density_mode: bool, g_features,
