@@ -530,7 +530,11 @@ __global__ __launch_bounds__(256) void proposal_sampler_kernel(SamplerDev sd, co
         }
         const float dd = live ? (t1 - t0) * dens : 0.f;
         const float incl = wscan_add(dd, lane);
-        float w = (1.f - expf(-dd)) * expf(-(carry + incl - dd));
+        // exclusive sum = the inclusive sum of the lane below, not `incl - dd`: subtracting a lane's own term leaves that
+        // term's rounding (u * dd) in the transmittance exponent -- at an opaque sample (dd ~ 1e5) a few percent of T, and
+        // inf - inf at a density past fp32's range
+        const float excl = wscan::shift_up1(incl, 0.f, lane);
+        float w = (1.f - expf(-dd)) * expf(-(carry + excl));
         if (w != w) w = 0.f;  // nan_to_num
         w = fminf(fmaxf(w, -3.4028234663852886e38f), 3.4028234663852886e38f);
         if (live) {

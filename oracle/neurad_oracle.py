@@ -523,13 +523,23 @@ def _pow_like_aten(base, e: float):
 
 
 def power_fn(x, lam: float):
+    """lam = 1: the identity, lam = 0: log1p (the limits of the general expression, utils/math.py:541-560)"""
     x = np.asarray(x, f32)
+    if lam == 1:
+        return x.astype(f32)
+    if lam == 0:
+        return np.log1p(x).astype(f32)
     lam_1 = abs(lam - 1)
     return (f32(lam_1 / lam) * (_pow_like_aten(x / f32(lam_1) + f32(1), lam) - f32(1))).astype(f32)
 
 
 def inv_power_fn(x, lam: float, eps: float = 1e-10):
+    """lam = 1: the identity, lam = 0: expm1 (utils/math.py:563-579)"""
     x = np.asarray(x, f32)
+    if lam == 1:
+        return x.astype(f32)
+    if lam == 0:
+        return np.expm1(x).astype(f32)
     lam_1 = abs(lam - 1)
     base = np.maximum(x * f32(lam) / f32(lam_1) + f32(1), f32(eps))
     return ((_pow_like_aten(base, 1 / lam) - f32(1)) * f32(lam_1)).astype(f32)
@@ -549,12 +559,31 @@ class Spacing:
         return (inv_power_fn(x * self.s_far + (f32(1) - x) * self.s_near, self.lam) / f32(self.scaling)).astype(f32)
 
 
+def linspace(start: float, end: float, steps: int) -> np.ndarray:
+    """torch.linspace in fp32 as ATen's scalar loop and its GPU kernel evaluate an element (RangeFactories): the step
+    rounded to fp32, the lower half counted up from ``start``, the upper half down from ``end``, each product and sum
+    rounded on its own.  ATen's VECTORISED CPU loop instead adds j * step to the rounded first element of each SIMD vector,
+    so torch on a CPU gives other last bits, depending on the vector width, wherever the step is not a power of two; and
+    numpy's linspace works in float64 and rounds once.  The three agree where the step is exact (128, 64, 32 samples:
+    what the reference goldens pin); at other counts (37, ...) no golden pins the last bit, and this is by construction the
+    expression of the HIP kernels (csrc/sampler.hip: linspace_at) -- a bit-for-bit comparison with them there checks the
+    kernels' indexing and jitter arithmetic, not the formula."""
+    start, end = f32(start), f32(end)
+    if steps == 1:
+        return np.array([start], f32)
+    step = f32((end - start) / f32(steps - 1))
+    i = np.arange(steps)
+    lo = (start + (step * i.astype(f32)).astype(f32)).astype(f32)
+    hi = (end - (step * (steps - 1 - i).astype(f32)).astype(f32)).astype(f32)
+    return np.where(i < steps // 2, lo, hi).astype(f32)
+
+
 def power_sampler(nears, fars, num_samples: int, lam: float = -1.0, scaling: float = 0.1, t_rand=None):
     """-> (spacing bins [R,S+1], euclidean bins [R,S+1], Spacing).  ``t_rand`` [R,S+1] injects the
     training-mode stratified jitter (ray_samplers.py:104-112); None = eval mode."""
     nears = np.asarray(nears, f32).reshape(-1, 1)
     fars = np.asarray(fars, f32).reshape(-1, 1)
-    bins = np.linspace(0.0, 1.0, num_samples + 1, dtype=f32)[None, :]
+    bins = linspace(0.0, 1.0, num_samples + 1)[None, :]
     if t_rand is not None:
         centers = (bins[..., 1:] + bins[..., :-1]) / f32(2)
         upper = np.concatenate([centers, bins[..., -1:]], -1)
@@ -581,7 +610,7 @@ def pdf_sample(weights, spacing_bins, num_samples: int, spacing: Spacing, histog
     cdf = np.minimum(f32(1), np.cumsum(pdf.astype(np.float64), -1).astype(f32))
     cdf = np.concatenate([np.zeros_like(cdf[..., :1]), cdf], -1)
     nb = num_samples + 1
-    u = np.linspace(0.0, 1.0 - (1.0 / nb), nb, dtype=f32)
+    u = linspace(0.0, 1.0 - (1.0 / nb), nb)
     if rand is not None:
         u = u[None, :] + np.asarray(rand, f32) / f32(nb)
     else:
