@@ -805,6 +805,19 @@ int nrhip_encode_bwd_binned_packed(const nrhip_grid* g, float static_scale, cons
 int nrhip_encode_bwd_binned_packed_f16(const nrhip_grid* g, float static_scale, const nrhip_packed_rays* rays,
                                        const int64_t* ray_of, const float* grad_out, void* grad_table_fp16, void* workspace,
                                        int64_t workspace_bytes, void* stream);
+/* nrhip_encode_bwd_rays for packed samples: dL/d(origins), dL/d(directions) [R,3] of the static encoding path from
+ * grad_out [M, L*F] = dL/d(rescaled features) at the packed sample index -- what a camera optimizer receives when the model
+ * samples through the occupancy grid.  Each sample's arithmetic is nrhip_encode_bwd_rays' (one shared body); a group of
+ * lanes_per_ray lanes (16 / 32 / 64; 0: chosen from the mean count M / R by the dense rule, > 32 -> 64, > 16 -> 32, else 16)
+ * owns ray r, strides over the samples [segments[r], segments[r+1]), merges by xor-butterfly and WRITES both rows: no
+ * atomics, no workspace, bit-reproducible; a ray's rows depend on its own samples and the group size only.  A ray without
+ * samples gets zeros; rows of grad_out that are exactly zero skip their gathers.  fp32 and fp16-storage tables, every
+ * n_features.  n_rays == 0 is a no-op that reads no pointer; n_samples == 0 zeroes both outputs without a launch;
+ * n_samples >= 2^31 is NRHIP_ERR_UNSUPPORTED.  Sample indices are clamped into [0, M).  rays->order is not read.
+ * No allocation, no host synchronisation (graph-capturable).                                                            */
+int nrhip_encode_bwd_rays_packed(const nrhip_grid* g, const void* table, float static_scale, const nrhip_packed_rays* rays,
+                                 const float* grad_out /*[M, L*F]*/, int32_t lanes_per_ray /*0 = choose*/,
+                                 float* grad_origins /*[R,3]*/, float* grad_directions /*[R,3]*/, void* stream);
 
 /* ---- S5+M1 fused: ProposalNetworkSampler as driven by NeuRADModel._get_ray_samples
  *      (ray_samplers.py:623-666, models/neurad.py:443-459).  One wave marches one ray through

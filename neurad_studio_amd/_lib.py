@@ -195,6 +195,7 @@ PROTOTYPES = {
     "nrhip_sdf_render_packed_bwd": [P, P, F32, P, P, P, P, P, P, P, P, P, I64, I32, P, P, P, P, P],
     "nrhip_encode_bwd_binned_packed": [C.POINTER(Grid), F32, C.POINTER(PackedRays), P, P, P, I32, P, I64, P],
     "nrhip_encode_bwd_binned_packed_f16": [C.POINTER(Grid), F32, C.POINTER(PackedRays), P, P, P, P, I64, P],
+    "nrhip_encode_bwd_rays_packed": [C.POINTER(Grid), P, F32, C.POINTER(PackedRays), P, I32, P, P, P],
     "nrhip_ray_order": [P, P, I64, F32, F32, I32, P, P],
     "nrhip_ray_order_workspace": [I64, I32, C.POINTER(I64)],
     "nrhip_ray_order_large": [P, P, I64, F32, F32, I32, P, I64, P, P],

@@ -19,11 +19,15 @@ from . import ops
 _E15, _EM15 = 3269017.3724721107, 3.0590232050182579e-07  # exp(+-15): trunc_exp's backward clamp (activations.py:37-41)
 
 
-def _ray_grads(need_o: bool, need_d: bool, spec, table, scale, o, d, a, starts, ends, genc):
-    """(dL/d origins, dL/d directions) of a static encoding from dL/d(rescaled features), None where not needed"""
+def _ray_grads(need_o: bool, need_d: bool, spec, table, scale, o, d, a, starts, ends, genc, segments=None):
+    """(dL/d origins, dL/d directions) of a static encoding from dL/d(rescaled features), None where not needed.  segments
+    int64 [R+1]: packed samples -- o / d / a per RAY, starts / ends [M] (nrhip_encode_bwd_rays_packed)"""
     if not (need_o or need_d):
         return None, None
-    go, gd = ops.encode_bwd_rays(spec, table, scale, o, d, a, starts, ends, genc)
+    if segments is not None:
+        go, gd = ops.encode_bwd_rays_packed(spec, table, scale, o, d, a, starts, ends, segments, genc)
+    else:
+        go, gd = ops.encode_bwd_rays(spec, table, scale, o, d, a, starts, ends, genc)
     return (go if need_o else None), (gd if need_d else None)
 
 
@@ -260,7 +264,8 @@ def _field_backward(spec, scale, table_dtype, need_table, o, d, a, starts, ends,
     static table.  rays = (table, need_o, need_d): the bundle's rays require grad (camera optimizer) -> the static samples'
     dL/d enc also goes back to the ray through the positions (`_ray_grads`; the overridden rows are zero by then: their
     share comes through ActorPairPositionsFn).  ray_of int64 [M]: packed samples -- o / d / a are per RAY, starts / ends [M],
-    and the table gradient comes from ``ops.encode_bwd_packed``."""
+    and the table gradient comes from ``ops.encode_bwd_packed``; rays is then (table, need_o, need_d, segments [R+1]) and the
+    ray gradients come from the packed kernel (``ops.encode_bwd_rays_packed``)."""
     gw, gb, fw, fb = list(params[0:4:2]), list(params[1:4:2]), list(params[4:10:2]), list(params[5:10:2])
     # feature = embedding + mlp_feature([embedding | sh])
     if ops.field_feature_bwd_supported(fw, fb):
@@ -286,7 +291,8 @@ def _field_backward(spec, scale, table_dtype, need_table, o, d, a, starts, ends,
     elif need_table:
         gt = _like_param(ops.encode_bwd(spec, scale, o, d, a, starts, ends, genc, out_dtype=table_dtype), table_dtype)
     grads = [ggw[0], ggb[0], ggw[1], ggb[1], gfw[0], gfb[0], gfw[1], gfb[1], gfw[2], gfb[2]]
-    god = (None, None) if rays is None else _ray_grads(rays[1], rays[2], spec, rays[0], scale, o, d, a, starts, ends, genc)
+    god = (None, None) if rays is None else _ray_grads(rays[1], rays[2], spec, rays[0], scale, o, d, a, starts, ends, genc,
+                                                       segments=rays[3] if ray_of is not None else None)
     return gt, grads, g_rows, god
 
 
@@ -730,7 +736,10 @@ class NffRenderPackedTrainFn(torch.autograd.Function):
     """NffRenderTrainFn for the occupancy march's packed samples (static scene): fused field forward on packed samples ->
     head (SigmoidDensity with the learnable beta, or trunc_exp) + packed compositing -> features, depth, accumulation,
     weights.  Compositing as PackedCompositeFn: no sky residual, depth = sum w mid over all samples, zeros for a ray
-    without samples.  No appearance embedding (callers append it per ray), no ray gradients.
+    without samples.  No appearance embedding (callers append it per ray).  Origins / directions that require grad (a camera
+    optimizer moved them) get their gradient through the static encoding from ``ops.encode_bwd_rays_packed`` on the dL/d enc
+    the backward forms anyway -- the table is saved for it, as in NffRenderTrainFn; with fixed rays nothing extra is saved
+    and nothing extra is launched.  t_starts / t_ends are constants (the march is no_grad).
 
     args: table, spec, static_scale, beta (raw parameter) | None (density head), beta_min, origins [R,3], directions [R,3],
     pixel_area [R], t_starts [M], t_ends [M], segments int64 [R+1], ray_indices int64 [M], order | None, gw0, gb0, gw1,
@@ -754,8 +763,10 @@ class NffRenderPackedTrainFn(torch.autograd.Function):
         alpha, w, out, depth, acc = ops.sdf_render_packed_fwd(geo, beta, beta_min, feature, t_starts, t_ends, segments)
         ctx.spec, ctx.scale, ctx.table_dtype, ctx.beta_min = spec, static_scale, table.dtype, beta_min
         ctx.density_head = beta is None
+        ctx.rays = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]  # a camera optimizer moved the rays
         ctx.save_for_backward(origins, directions, pixel_area, t_starts, t_ends, segments, ray_indices, enc, hg, xf, hf,
-                              feature, geo, alpha, geo.new_empty(0) if beta is None else beta, *params)
+                              feature, geo, alpha, geo.new_empty(0) if beta is None else beta, *params,
+                              *([table] if ctx.rays else []))
         return out, depth, acc, w
 
     @staticmethod
@@ -767,10 +778,13 @@ class NffRenderPackedTrainFn(torch.autograd.Function):
         o, d, a, ts, te, seg, ri, enc, hg, xf, hf, feature, geo, alpha, beta, *params = ctx.saved_tensors
         gfeat, ggeo, gbeta = ops.sdf_render_packed_bwd(geo, None if ctx.density_head else beta, ctx.beta_min, alpha, feature,
                                                        ts, te, seg, g_out, g_depth, g_acc, g_w)
-        gt, grads, _, _ = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a, ts, te, enc,
-                                          hg, xf, hf, params, gfeat, ggeo, ray_of=ri)
+        rays = None
+        if ctx.rays:
+            params, rays = params[:-1], (params[-1], ctx.needs_input_grad[5], ctx.needs_input_grad[6], seg)
+        gt, grads, _, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a, ts, te,
+                                                 enc, hg, xf, hf, params, gfeat, ggeo, rays=rays, ray_of=ri)
         g_beta = gbeta.reshape(beta.shape) if (ctx.needs_input_grad[3] and not ctx.density_head) else None
-        return (gt, None, None, g_beta, *([None] * 9), *grads)
+        return (gt, None, None, g_beta, None, go, gd, *([None] * 6), *grads)
 
 
 class LidarLossFn(torch.autograd.Function):

@@ -97,7 +97,8 @@ extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
 // 514: nrhip_render_fwd_packed (+ nrhip_packed_rays): the fused render kernel on packed samples
 // 515: training on packed samples: nrhip_field_fwd_train_packed, nrhip_sdf_render_packed_fwd / _bwd / _bwd_workspace,
 //      nrhip_encode_bwd_binned_packed / _f16
-extern "C" int nrhip_version(void) { return 515; }
+// 516: nrhip_encode_bwd_rays_packed: ray gradients through packed samples
+extern "C" int nrhip_version(void) { return 516; }
 
 extern "C" int nrhip_tuning_reload(void) {
   nrhip::g_tuning = nrhip::read_tuning();

@@ -71,9 +71,43 @@ __global__ __launch_bounds__(256) void hashgrid_multi_bwd_input_kernel(GridDev g
 // One group of G lanes per ray (G = 16 / 32 / 64 by samples per ray), lanes stride over the samples, xor-butterfly over the
 // group, lane 0 WRITES the ray's two rows: no atomics, bit-reproducible.  Samples whose whole gradient row is zero (behind
 // an opaque surface; rows overridden by an actor) skip their 8 L gathers.
-template <int F, bool HALF>
+// ONE kernel body for both sample layouts; `Rays` says where a ray's samples lie (the three accessors below):
+//   RaysDev        [R,S] samples, intervals with a row stride                       (nrhip_encode_bwd_rays)
+//   PackedRaysDev  the occupancy march's ragged segments: ray r owns the samples [segs[r], segs[r + 1]) of the [M]-shaped
+//                  interval arrays and of go [M, L*F]; origins / directions / pixel area stay per RAY and are read once per
+//                  ray.  A ray's rows depend on its own samples and on G alone (lane `sub` adds the samples sub, sub + G, ...
+//                  in that order, then the butterfly), never on where the ray sits in the batch; a ray without samples gets
+//                  two rows of zeros.  The count is clamped into [0, M] and every index into [0, M): segments that break
+//                  their precondition still read inside the arrays.              (nrhip_encode_bwd_rays_packed)
+struct PackedRaysDev {
+  int64_t R;
+  int M;  // 1 <= M < 2^31: a batch without samples never reaches the kernel
+  const float* o;
+  const float* d;
+  const float* area;
+  const float* starts;
+  const float* ends;
+  const int64_t* segs;
+};
+// samples of the ray; row of go that holds sample s of the ray; index of its interval in starts / ends
+__device__ __forceinline__ int ray_sample_count(const RaysDev& r, int64_t) { return r.S; }
+__device__ __forceinline__ int64_t ray_sample_row(const RaysDev& r, int64_t ray, int s) { return ray * r.S + s; }
+__device__ __forceinline__ int64_t ray_sample_interval(const RaysDev& r, int64_t ray, int s) { return ray * r.stride + s; }
+__device__ __forceinline__ int ray_sample_count(const PackedRaysDev& r, int64_t ray) {
+  const int64_t n = r.segs[ray + 1] - r.segs[ray];
+  return (int)(n < (int64_t)r.M ? n : (int64_t)r.M);
+}
+__device__ __forceinline__ int64_t ray_sample_row(const PackedRaysDev& r, int64_t ray, int s) {
+  const int64_t i = r.segs[ray] + s;
+  return i < 0 ? 0 : (i < (int64_t)r.M ? i : (int64_t)r.M - 1);
+}
+__device__ __forceinline__ int64_t ray_sample_interval(const PackedRaysDev& r, int64_t ray, int s) {
+  return ray_sample_row(r, ray, s);
+}
+
+template <int F, bool HALF, class Rays>
 __global__ __launch_bounds__(256) void encode_bwd_rays_kernel(GridDev g, const void* __restrict__ table, float scale,
-                                                               RaysDev r, const float* __restrict__ go, int G,
+                                                               Rays r, const float* __restrict__ go, int G,
                                                                float* __restrict__ g_o, float* __restrict__ g_d) {
   const int lane = threadIdx.x & 63;
   const int sub = lane & (G - 1);
@@ -85,13 +119,14 @@ __global__ __launch_bounds__(256) void encode_bwd_rays_kernel(GridDev g, const v
     const float ox_ = r.o[3 * ray], oy_ = r.o[3 * ray + 1], oz_ = r.o[3 * ray + 2];
     const float dx_ = r.d[3 * ray], dy_ = r.d[3 * ray + 1], dz_ = r.d[3 * ray + 2];
     const float area = r.area[ray];
-    for (int s = sub; s < r.S; s += G) {
-      const int64_t i = ray * r.S + s;
+    for (int s = sub; s < ray_sample_count(r, ray); s += G) {
+      const int64_t i = ray_sample_row(r, ray, s);
       const float* gi = go + i * (int64_t)(g.L * F);
       bool any = false;
       for (int k = 0; k < g.L * F; ++k) any |= gi[k] != 0.f;
       if (!any) continue;
-      const float t0 = r.starts[ray * r.stride + s], t1 = r.ends[ray * r.stride + s];
+      const int64_t ti = ray_sample_interval(r, ray, s);
+      const float t0 = r.starts[ti], t1 = r.ends[ti];
       const SamplePos gs = sample_gaussian(ox_, oy_, oz_, dx_, dy_, dz_, area, t0, t1);
       const SamplePos p = contract_gaussian(gs.x, gs.y, gs.z, gs.std, scale);
       float gx = 0.f, gy = 0.f, gz = 0.f, gstd = 0.f;
@@ -196,8 +231,45 @@ extern "C" int nrhip_encode_bwd_rays(const nrhip_grid* g, const void* table, flo
   const int blocks = grid_for(rd.R * G, 256);
   const hipStream_t st = (hipStream_t)stream;
   dispatch_f(gd.F, g->param_dtype == 1, [&](auto F, auto H) {
-    encode_bwd_rays_kernel<F, H><<<blocks, 256, 0, st>>>(gd, table, static_scale, rd, grad_out, G, grad_origins,
-                                                         grad_directions);
+    encode_bwd_rays_kernel<F, H, RaysDev><<<blocks, 256, 0, st>>>(gd, table, static_scale, rd, grad_out, G, grad_origins,
+                                                                  grad_directions);
   });
   return check_launch("encode_bwd_rays");
+}
+
+extern "C" int nrhip_encode_bwd_rays_packed(const nrhip_grid* g, const void* table, float static_scale,
+                                            const nrhip_packed_rays* rays, const float* grad_out, int32_t lanes_per_ray,
+                                            float* grad_origins, float* grad_directions, void* stream) {
+  if (int e = validate_grid(g)) return e;
+  NR_REQUIRE(rays, NRHIP_ERR_INVALID_ARG, "encode_bwd_rays_packed: rays descriptor is NULL");
+  NR_REQUIRE(rays->n_rays >= 0 && rays->n_samples >= 0, NRHIP_ERR_INVALID_ARG,
+             "encode_bwd_rays_packed: negative ray/sample count");
+  NR_REQUIRE(rays->n_samples < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "encode_bwd_rays_packed: M >= 2^31");
+  NR_REQUIRE(static_scale > 0.f, NRHIP_ERR_INVALID_ARG, "encode_bwd_rays_packed: non-positive scale");
+  NR_REQUIRE(lanes_per_ray == 0 || lanes_per_ray == 16 || lanes_per_ray == 32 || lanes_per_ray == 64, NRHIP_ERR_INVALID_ARG,
+             "encode_bwd_rays_packed: lanes_per_ray %d not in {0, 16, 32, 64}", lanes_per_ray);
+  const int64_t R = rays->n_rays, M = rays->n_samples;
+  NR_REQUIRE(M == 0 || R > 0, NRHIP_ERR_INVALID_ARG, "encode_bwd_rays_packed: samples without rays");
+  if (R == 0) return NRHIP_OK;
+  NR_REQUIRE(grad_origins && grad_directions, NRHIP_ERR_INVALID_ARG, "encode_bwd_rays_packed: NULL output");
+  const hipStream_t st = (hipStream_t)stream;
+  if (M == 0) {  // no ray has a sample: two blocks of zeros, no launch
+    const size_t bytes = (size_t)R * 3 * sizeof(float);
+    if (hipMemsetAsync(grad_origins, 0, bytes, st) != hipSuccess || hipMemsetAsync(grad_directions, 0, bytes, st) != hipSuccess)
+      return check_launch("encode_bwd_rays_packed");
+    return NRHIP_OK;
+  }
+  NR_REQUIRE(table && grad_out && rays->origins && rays->directions && rays->pixel_area && rays->t_starts && rays->t_ends &&
+                 rays->segments,
+             NRHIP_ERR_INVALID_ARG, "encode_bwd_rays_packed: NULL pointer");
+  const GridDev gd = to_dev(*g);
+  const PackedRaysDev rd{R, (int)M, rays->origins, rays->directions, rays->pixel_area, rays->t_starts, rays->t_ends, rays->segments};
+  // the dense rule on the MEAN count M / R (both are shapes: no device read)
+  const int G = lanes_per_ray ? lanes_per_ray : (M > 32 * R ? 64 : (M > 16 * R ? 32 : 16));
+  const int blocks = grid_for(R * G, 256);
+  dispatch_f(gd.F, g->param_dtype == 1, [&](auto F, auto H) {
+    encode_bwd_rays_kernel<F, H, PackedRaysDev><<<blocks, 256, 0, st>>>(gd, table, static_scale, rd, grad_out, G,
+                                                                        grad_origins, grad_directions);
+  });
+  return check_launch("encode_bwd_rays_packed");
 }

@@ -252,13 +252,17 @@ class NeuRADField(nn.Module):
                                          return_weights, early_stop_eps=early_stop_eps, order=order)
 
     def render_train_packed(self, origins, directions, pixel_area, t_starts, t_ends, *, segments: Optional[Tensor] = None,
-                            ray_indices: Optional[Tensor] = None, num_rays: Optional[int] = None):
+                            ray_indices: Optional[Tensor] = None, num_rays: Optional[int] = None,
+                            ray_gradients: bool = False):
         """Training counterpart of ``render_packed``: field -> head (learnable-beta SDF head, or trunc_exp) -> packed
         compositing as ONE autograd node (autograd.NffRenderPackedTrainFn).  Arguments as ``render_packed``: per-RAY origins
         / directions [R,3] and pixel_area [R] (or [R,1]), per-sample t_starts / t_ends [M], exactly one of ``segments`` int64
         [R+1] or ``ray_indices`` int64 [M] (sorted) + ``num_rays``; the other one is derived on the device.
         -> features [R,32], depth [R,1] (sum w mid), accumulation [R,1], weights [M]; compositing as
-        renderers.render_packed.  Gradients reach the table, the MLPs and beta -- not the rays."""
+        renderers.render_packed.  Gradients reach the table, the MLPs and beta.  Rays that require grad (a camera optimizer
+        moved them) are refused by default, as before; ``ray_gradients=True`` opts in: the node then also returns dL/d origins
+        and dL/d directions through the static encoding (nrhip_encode_bwd_rays_packed: one launch, no atomics, bit-reproducible;
+        t_starts / t_ends stay constants of the march).  With fixed rays the flag changes nothing."""
         if (segments is None) == (ray_indices is None):
             raise ValueError("render_train_packed: give exactly one of segments / ray_indices (+ num_rays)")
         if ray_indices is not None and num_rays is None:
@@ -268,7 +272,7 @@ class NeuRADField(nn.Module):
             raise NotImplementedError(f"render_train_packed: the occupancy route is static, no dynamic actors; {operator}")
         if not self.fused_packed_train_supported():
             raise NotImplementedError(f"render_train_packed: a fused-kernel configuration only (see fused_supported); {operator}")
-        if torch.is_grad_enabled() and (origins.requires_grad or directions.requires_grad):
+        if not ray_gradients and torch.is_grad_enabled() and (origins.requires_grad or directions.requires_grad):
             raise NotImplementedError(f"render_train_packed: no gradient reaches the rays through packed samples; {operator}")
         hg, g = self.hashgrid, self.hashgrid.static_grid
         t_starts, t_ends = t_starts.reshape(-1), t_ends.reshape(-1)

@@ -286,22 +286,26 @@ class VolumetricSampler(Sampler):
         return {**render_packed(out[FieldHeadNames.FEATURE], rs, ri, R, **kw), **marched}
 
     def render_train(self, field, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0,
-                     far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0) -> dict:
+                     far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0,
+                     fused_ray_gradients: bool = False) -> dict:
         """Training counterpart of ``render``: a stratified march + field + compositing with autograd -> the same keys.  A
         field that trains on packed samples as one node (``fused_packed_train_supported``, ``fused_training`` on) gets the
         BUNDLE'S per-ray tensors and the packed intervals (``render_train_packed``: no per-sample copy of origins /
         directions / pixel area, the head and the compositing in one kernel each way).  Any other field, ``fused_training =
-        False`` and rays that require grad (the node sends no gradient to them) take forward() on the gathered RaySamples +
-        renderers.render_packed.  A march without samples returns zero rows."""
+        False`` and, by default, rays that require grad take forward() on the gathered RaySamples + renderers.render_packed.
+        ``fused_ray_gradients=True`` keeps rays that require grad (a camera optimizer) on the node, which then returns their
+        gradients itself (``render_train_packed(..., ray_gradients=True)``); same keys, same shapes.  A march without samples
+        returns zero rows."""
         R = ray_bundle.origins.shape[0]
         rays_o, rays_d, ri, starts, ends = self._march(ray_bundle, render_step_size, near_plane, far_plane, alpha_thre,
                                                        cone_angle, stratified=True)
         marched = {"ray_indices": ri, "t_starts": starts, "t_ends": ends}
         rays_need_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
-        if (getattr(field, "fused_training", False) and not rays_need_grad
+        if (getattr(field, "fused_training", False) and (fused_ray_gradients or not rays_need_grad)
                 and getattr(field, "fused_packed_train_supported", lambda: False)()):
+            kw = {"ray_gradients": True} if rays_need_grad else {}
             f, d, a, w = field.render_train_packed(rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri,
-                                                   num_rays=R)
+                                                   num_rays=R, **kw)
             return {"features": f, "depth": d, "accumulation": a, "weights": w[:, None], **marched}
         from ..field_components.field_heads import FieldHeadNames
         from .renderers import render_packed

@@ -1544,6 +1544,23 @@ def encode_bwd_packed(spec: GridSpec, static_scale: float, origins, directions, 
     return gt
 
 
+def encode_bwd_rays_packed(spec: GridSpec, table: Tensor, static_scale: float, origins, directions, pixel_area, t_starts,
+                           t_ends, segments, grad_out, lanes_per_ray: int = 0) -> Tuple[Tensor, Tensor]:
+    """``encode_bwd_rays`` for the march's packed samples: dL/d(origins), dL/d(directions) [R,3] from dL/d(rescaled
+    features) [M, L*F] at the packed sample index.  One kernel, a group of lanes per ray over its segment, no atomics:
+    bit-reproducible, a ray's rows depend on its own samples and the group size only; zeros for a ray without samples.
+    lanes_per_ray: 16 / 32 / 64 forces the group size, 0 lets the library choose it from the mean count M / R."""
+    if grad_out.numel() != t_starts.numel() * spec.out_dim:  # (shapes only: answered before any device is asked for)
+        raise ValueError(f"grad_out has {grad_out.numel()} elements, expected {t_starts.numel() * spec.out_dim}")
+    r, keep = _c_packed_rays("encode_bwd_rays_packed", origins, directions, pixel_area, t_starts, t_ends, segments)
+    grad_out = _chk(grad_out, "grad_out")
+    g = spec.c_grid(table)
+    out = torch.empty((2, r.n_rays, 3), device=keep[0].device, dtype=torch.float32)
+    launch("nrhip_encode_bwd_rays_packed", g, _chk(table, "table", table.dtype), float(static_scale), r, grad_out,
+           int(lanes_per_ray), out[0], out[1])
+    return out[0], out[1]
+
+
 def packed_composite_bwd(t_starts, t_ends, sigmas_or_alphas, features, segments, density_mode: bool, g_features,
                          g_depth=None, g_accumulation=None, g_weights=None, need_grad_x=True, need_grad_features=True):
     """-> (grad sigmas / alphas [M] or None, grad features [M,C] or None)"""

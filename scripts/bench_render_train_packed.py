@@ -9,7 +9,11 @@ one process:
       sample a ray of one sample), the torch head, renderers.render_packed (PackedCompositeFn).
 Appends ONE JSON line (M, the segment-length histogram, device clocks under load, medians, the ratio (b)/(a), and the rel-L2
 of (a) against (b) on outputs and gradients) to profiles/bench_render_train_packed.jsonl.  Fails without a GPU.
-    python scripts/bench_render_train_packed.py [--reps 100] [--warmup 10] [--out profiles/bench_render_train_packed.jsonl]"""
+--ray-grads: the same two routes at the same size with origins and directions that REQUIRE GRAD (a camera optimizer moved
+them), their two gradients added to what each step computes: (a) is the node with ray_gradients=True (its ray gradients from
+nrhip_encode_bwd_rays_packed), (b) the fallback VolumetricSampler.render_train takes by default for such rays (the gathers'
+index_add_ backward folds the per-sample rows to rays).  The line's "bench" is then "render_train_packed_ray_grads".
+    python scripts/bench_render_train_packed.py [--ray-grads] [--reps 100] [--warmup 10] [--out profiles/bench_render_train_packed.jsonl]"""
 import argparse
 import json
 import os
@@ -78,6 +82,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--ray-grads", action="store_true", help="rays that require grad: the opt-in node against the fallback")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_render_train_packed.jsonl"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -89,19 +94,22 @@ def main():
     M = int(ri.shape[0])
     o = ((torch.rand((R, 3), generator=gen) * 2 - 1) * 3.5).cuda()
     d = torch.nn.functional.normalize(torch.randn((R, 3), generator=gen), dim=-1).cuda()
+    if args.ray_grads:
+        o.requires_grad_(True), d.requires_grad_(True)
     area = torch.full((R, 1), 2.4e-6, device="cuda")
     ri, ts, te = torch.from_numpy(ri).cuda(), torch.from_numpy(ts).cuda(), torch.from_numpy(te).cuda()
     rb = RayBundle(origins=o, directions=d, pixel_area=area)
     cot = [torch.randn(s, generator=gen).cuda() for s in ((R, 32), (R, 1), (R, 1), (M,))]
     fld = make_field(gen)
     assert fld.fused_packed_train_supported()
-    params = [p for p in fld.parameters() if p.requires_grad]
+    params = [p for p in fld.parameters() if p.requires_grad] + ([o, d] if args.ray_grads else [])
+    names = [n for n, p in fld.named_parameters() if p.requires_grad] + (["origins", "directions"] if args.ray_grads else [])
 
     def loss_of(outs):
         return sum((t.reshape(c.shape) * c).sum() for t, c in zip(outs, cot))
 
     def route_a():
-        outs = fld.render_train_packed(o, d, area, ts, te, ray_indices=ri, num_rays=R)
+        outs = fld.render_train_packed(o, d, area, ts, te, ray_indices=ri, num_rays=R, ray_gradients=args.ray_grads)
         return outs, torch.autograd.grad(loss_of(outs), params, allow_unused=True)
 
     def route_b():
@@ -114,7 +122,7 @@ def main():
 
     (oa, ga), (ob, gb) = route_a(), route_b()
     agree = {k: rel_l2(x, y) for k, x, y in zip(("features", "depth", "accumulation", "weights"), oa, ob)}
-    agree.update({f"d {n}": rel_l2(x, y) for (n, _), x, y in zip(fld.named_parameters(), ga, gb) if x is not None})
+    agree.update({f"d {n}": rel_l2(x, y) for n, x, y in zip(names, ga, gb) if x is not None})
     times = {"a_fused_node": [], "b_operator_route": []}
     clocks = device_state(0)  # (sampled under a load of its own)
     for rep in range(args.warmup + args.reps):
@@ -124,7 +132,8 @@ def main():
                 times[key].append(t)
     med = {k: median(v) for k, v in times.items()}
     line = {
-        "bench": "render_train_packed", "field": "neurad_default_8x4_h32", "levels": L, "features_per_level": F, "hidden": H,
+        "bench": "render_train_packed_ray_grads" if args.ray_grads else "render_train_packed",
+        "field": "neurad_default_8x4_h32", "levels": L, "features_per_level": F, "hidden": H,
         "head": "sdf", "log2_table": LOG2_T, "table_dtype": "fp32", "rays": R, "M": M,
         "segments": {"min": int(counts.min()), "mean": float(counts.mean()), "median": float(np.median(counts)),
                      "p99": float(np.percentile(counts, 99)), "max": int(counts.max()),
