@@ -10,7 +10,10 @@ hash grid the rays were encoded with (nrhip_encode_bwd_rays; view directions car
 """
 from __future__ import annotations
 
+from typing import NamedTuple, Optional
+
 import torch
+from torch import Tensor
 from torch.amp import custom_bwd, custom_fwd
 
 from . import ops
@@ -19,16 +22,45 @@ from . import ops
 _E15, _EM15 = 3269017.3724721107, 3.0590232050182579e-07  # exp(+-15): trunc_exp's backward clamp (activations.py:37-41)
 
 
-def _ray_grads(need_o: bool, need_d: bool, spec, table, scale, o, d, a, starts, ends, genc, segments=None):
-    """(dL/d origins, dL/d directions) of a static encoding from dL/d(rescaled features), None where not needed.  segments
-    int64 [R+1]: packed samples -- o / d / a per RAY, starts / ends [M] (nrhip_encode_bwd_rays_packed)"""
-    if not (need_o or need_d):
+class Samples(NamedTuple):
+    """Where the samples of a batch of rays lie -- what the backward of a static encoding needs to know about the layout.
+    Dense: starts / ends [R,S].  Packed (the occupancy march's ragged output): starts / ends are t_starts / t_ends [M],
+    segments int64 [R+1] bounds each ray's samples and ray_indices int64 [M] names each sample's ray.  Origins, directions
+    and pixel area are per RAY in both."""
+
+    starts: Tensor
+    ends: Tensor
+    segments: Optional[Tensor] = None
+    ray_indices: Optional[Tensor] = None
+
+    def table_grad(self, spec, scale, o, d, a, genc, out_dtype):
+        """grad table [L*T, F] from dL/d(rescaled features)"""
+        if self.segments is None:
+            return ops.encode_bwd(spec, scale, o, d, a, self.starts, self.ends, genc, out_dtype=out_dtype)
+        return ops.encode_bwd_packed(spec, scale, o, d, a, self.starts, self.ends, self.ray_indices, genc, out_dtype=out_dtype)
+
+    def ray_grads(self, spec, table, scale, o, d, a, genc):
+        """dL/d origins, dL/d directions [R,3] from dL/d(rescaled features)"""
+        if self.segments is None:
+            return ops.encode_bwd_rays(spec, table, scale, o, d, a, self.starts, self.ends, genc)
+        return ops.encode_bwd_rays_packed(spec, table, scale, o, d, a, self.starts, self.ends, self.segments, genc)
+
+
+class RayGrads(NamedTuple):
+    """the bundle's rays require grad (a camera optimizer moved them): the table their samples were encoded with (saved for
+    this alone) and which of the two gradients autograd asked for"""
+
+    table: Tensor
+    need_o: bool
+    need_d: bool
+
+
+def _ray_grads(want: Optional[RayGrads], spec, scale, o, d, a, samples: Samples, genc):
+    """(dL/d origins, dL/d directions) of a static encoding from dL/d(rescaled features), None where not needed"""
+    if want is None or not (want.need_o or want.need_d):
         return None, None
-    if segments is not None:
-        go, gd = ops.encode_bwd_rays_packed(spec, table, scale, o, d, a, starts, ends, segments, genc)
-    else:
-        go, gd = ops.encode_bwd_rays(spec, table, scale, o, d, a, starts, ends, genc)
-    return (go if need_o else None), (gd if need_d else None)
+    go, gd = samples.ray_grads(spec, want.table, scale, o, d, a, genc)
+    return (go if want.need_o else None), (gd if want.need_d else None)
 
 
 def _proposal_genc(dens, gdens, decoder_weight):
@@ -214,8 +246,8 @@ class EncodeFn(torch.autograd.Function):
         o, d, a, s, e, *tab = ctx.saved_tensors
         g = g.contiguous()
         gt = ops.encode_bwd(ctx.spec, ctx.scale, o, d, a, s, e, g, out_dtype=ctx.table_dtype) if ctx.needs_input_grad[0] else None
-        go, gd = (None, None) if not ctx.rays else _ray_grads(ctx.needs_input_grad[3], ctx.needs_input_grad[4], ctx.spec,
-                                                              tab[0], ctx.scale, o, d, a, s, e, g)
+        want = RayGrads(tab[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]) if ctx.rays else None
+        go, gd = _ray_grads(want, ctx.spec, ctx.scale, o, d, a, Samples(s, e), g)
         return _like_param(gt, ctx.table_dtype), None, None, go, gd, None, None, None
 
 
@@ -248,24 +280,24 @@ class FieldTrainFn(torch.autograd.Function):
         o, d, a, s, e, enc, hg, xf, hf, *params = ctx.saved_tensors
         rays = None
         if ctx.rays:
-            params, rays = params[:-1], (params[-1], ctx.needs_input_grad[5], ctx.needs_input_grad[6])
-        gt, grads, _, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a, s, e,
-                                                 enc, hg, xf, hf, params, g_feature.contiguous(), g_geo_out, rays=rays)
+            params, rays = params[:-1], RayGrads(params[-1], ctx.needs_input_grad[5], ctx.needs_input_grad[6])
+        gt, grads, _, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a,
+                                                 Samples(s, e), enc, hg, xf, hf, params, g_feature.contiguous(), g_geo_out,
+                                                 rays=rays)
         return (gt, None, None, None, None, go, gd, None, None, None, *grads, *([None] if ctx.has_order else []))
 
 
-def _field_backward(spec, scale, table_dtype, need_table, o, d, a, starts, ends, enc, hg, xf, hf, params, g_feature, g_geo_out,
-                    override=None, rays=None, ray_of=None):
+def _field_backward(spec, scale, table_dtype, need_table, o, d, a, samples: Samples, enc, hg, xf, hf, params, g_feature,
+                    g_geo_out, override=None, rays: Optional[RayGrads] = None):
     """Backward of the fused field forward from (dL/dfeature [N,32], dL/dgeo_out [N]): feature-MLP gradients -> residual ->
     geometry-MLP gradients -> table gradient.  -> (grad table or None, the ten MLP parameter gradients in argument order,
-    gradient of the override rows or None, (dL/d origins, dL/d directions) or Nones).  override = (ovr_row [N], pair_idx
-    [P]): samples whose encoding row came from the caller (actor boxes) hand dL/d enc to those rows -- every (sample, actor)
-    pair gets its sample's row, as the reference's index_put does (neurad_encoding.py:184-185) -- and send nothing to the
-    static table.  rays = (table, need_o, need_d): the bundle's rays require grad (camera optimizer) -> the static samples'
-    dL/d enc also goes back to the ray through the positions (`_ray_grads`; the overridden rows are zero by then: their
-    share comes through ActorPairPositionsFn).  ray_of int64 [M]: packed samples -- o / d / a are per RAY, starts / ends [M],
-    and the table gradient comes from ``ops.encode_bwd_packed``; rays is then (table, need_o, need_d, segments [R+1]) and the
-    ray gradients come from the packed kernel (``ops.encode_bwd_rays_packed``)."""
+    gradient of the override rows or None, (dL/d origins, dL/d directions) or Nones).  samples: the layout of the N samples
+    (dense or packed; o / d / a per RAY), which decides the kernels of the table and the ray gradients.  override = (ovr_row
+    [N], pair_idx [P]): samples whose encoding row came from the caller (actor boxes) hand dL/d enc to those rows -- every
+    (sample, actor) pair gets its sample's row, as the reference's index_put does (neurad_encoding.py:184-185) -- and send
+    nothing to the static table.  rays: the bundle's rays require grad (camera optimizer) -> the static samples' dL/d enc
+    also goes back to the ray through the positions (`_ray_grads`; the overridden rows are zero by then: their share comes
+    through ActorPairPositionsFn)."""
     gw, gb, fw, fb = list(params[0:4:2]), list(params[1:4:2]), list(params[4:10:2]), list(params[5:10:2])
     # feature = embedding + mlp_feature([embedding | sh])
     if ops.field_feature_bwd_supported(fw, fb):
@@ -284,16 +316,9 @@ def _field_backward(spec, scale, table_dtype, need_table, o, d, a, starts, ends,
         # exactly-zero rows send no records (encode_bwd_binned: prep).  The overridden samples are the pair list's samples
         # (every sample of a pair has a winning pair): P rows written, not a pass over all N (85 us at 2 M samples)
         genc.index_fill_(0, pair_idx, 0.0)
-    gt = None
-    if need_table and ray_of is not None:
-        gt = _like_param(ops.encode_bwd_packed(spec, scale, o, d, a, starts, ends, ray_of, genc, out_dtype=table_dtype),
-                         table_dtype)
-    elif need_table:
-        gt = _like_param(ops.encode_bwd(spec, scale, o, d, a, starts, ends, genc, out_dtype=table_dtype), table_dtype)
+    gt = _like_param(samples.table_grad(spec, scale, o, d, a, genc, table_dtype), table_dtype) if need_table else None
     grads = [ggw[0], ggb[0], ggw[1], ggb[1], gfw[0], gfb[0], gfw[1], gfb[1], gfw[2], gfb[2]]
-    god = (None, None) if rays is None else _ray_grads(rays[1], rays[2], spec, rays[0], scale, o, d, a, starts, ends, genc,
-                                                       segments=rays[3] if ray_of is not None else None)
-    return gt, grads, g_rows, god
+    return gt, grads, g_rows, _ray_grads(rays, spec, scale, o, d, a, samples, genc)
 
 
 class MLPFn(torch.autograd.Function):
@@ -558,8 +583,8 @@ class ProposalDensityFn(torch.autograd.Function):
             gt, gdec = _like_param(gt, ctx.ps.table.dtype), gdec.reshape(ctx.ps.decoder_weight.shape)
         go, gd = (None, None)
         if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
-            go, gd = _ray_grads(ctx.needs_input_grad[4], ctx.needs_input_grad[5], ctx.ps.grid, ctx.ps.table,
-                                ctx.ps.static_scale, o, d, a, s, e, _proposal_genc(dens, g, ctx.ps.decoder_weight))
+            go, gd = _ray_grads(RayGrads(ctx.ps.table, ctx.needs_input_grad[4], ctx.needs_input_grad[5]), ctx.ps.grid,
+                                ctx.ps.static_scale, o, d, a, Samples(s, e), _proposal_genc(dens, g, ctx.ps.decoder_weight))
         return gt, gdec, None, None, go, gd, None, None, None
 
 
@@ -637,8 +662,9 @@ class ProposalRoundFn(torch.autograd.Function):
             gt, gdec = _like_param(gt, ctx.ps.table.dtype), gdec.reshape(ctx.ps.decoder_weight.shape)
         go, gd = (None, None)
         if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:  # the rays moved with a camera optimizer
-            go, gd = _ray_grads(ctx.needs_input_grad[4], ctx.needs_input_grad[5], ctx.ps.grid, ctx.ps.table,
-                                ctx.ps.static_scale, o, d, a, starts, ends, _proposal_genc(dens, gdens, ctx.ps.decoder_weight))
+            go, gd = _ray_grads(RayGrads(ctx.ps.table, ctx.needs_input_grad[4], ctx.needs_input_grad[5]), ctx.ps.grid,
+                                ctx.ps.static_scale, o, d, a, Samples(starts, ends),
+                                _proposal_genc(dens, gdens, ctx.ps.decoder_weight))
         return gt, gdec, None, None, go, gd, None, None
 
 
@@ -721,9 +747,9 @@ class NffRenderTrainFn(torch.autograd.Function):
             g_emb = ops.appearance_bwd(g_out[:, C_:], sensor_idx, times, ctx.emb_cfg[0], ctx.emb_cfg[1], ctx.emb_cfg[2],
                                        ctx.n_embed)
         override = (opt.pop(0), opt.pop(0)) if ctx.has_ovr else None
-        rays = (opt.pop(0), ctx.needs_input_grad[5], ctx.needs_input_grad[6]) if ctx.rays else None
+        rays = RayGrads(opt.pop(0), ctx.needs_input_grad[5], ctx.needs_input_grad[6]) if ctx.rays else None
         gt, grads, g_rows, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a,
-                                                      edges[:, :-1], edges[:, 1:], enc, hg, xf, hf, params,
+                                                      Samples(edges[:, :-1], edges[:, 1:]), enc, hg, xf, hf, params,
                                                       gfeat.view(R * S, C_), gsdf.view(-1), override=override, rays=rays)
         if not ctx.needs_input_grad[15]:
             g_rows = None
@@ -780,9 +806,9 @@ class NffRenderPackedTrainFn(torch.autograd.Function):
                                                        ts, te, seg, g_out, g_depth, g_acc, g_w)
         rays = None
         if ctx.rays:
-            params, rays = params[:-1], (params[-1], ctx.needs_input_grad[5], ctx.needs_input_grad[6], seg)
-        gt, grads, _, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a, ts, te,
-                                                 enc, hg, xf, hf, params, gfeat, ggeo, rays=rays, ray_of=ri)
+            params, rays = params[:-1], RayGrads(params[-1], ctx.needs_input_grad[5], ctx.needs_input_grad[6])
+        gt, grads, _, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a,
+                                                 Samples(ts, te, seg, ri), enc, hg, xf, hf, params, gfeat, ggeo, rays=rays)
         g_beta = gbeta.reshape(beta.shape) if (ctx.needs_input_grad[3] and not ctx.density_head) else None
         return (gt, None, None, g_beta, None, go, gd, *([None] * 6), *grads)
 

@@ -82,6 +82,16 @@ int validate_rays(const nrhip_rays* r) {
   return NRHIP_OK;
 }
 
+int validate_packed_rays(const char* who, const nrhip_packed_rays* r, bool need_segments) {
+  NR_REQUIRE(r, NRHIP_ERR_INVALID_ARG, "%s: rays descriptor is NULL", who);
+  NR_REQUIRE(r->n_rays >= 0 && r->n_samples >= 0, NRHIP_ERR_INVALID_ARG, "%s: negative ray/sample count", who);
+  NR_REQUIRE(r->n_samples < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "%s: M >= 2^31", who);
+  if (r->n_rays == 0 || r->n_samples == 0) return NRHIP_OK;
+  NR_REQUIRE(r->origins && r->directions && r->pixel_area && r->t_starts && r->t_ends && (r->segments || !need_segments),
+             NRHIP_ERR_INVALID_ARG, "%s: rays descriptor has a NULL pointer", who);
+  return NRHIP_OK;
+}
+
 }  // namespace nrhip
 
 extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }

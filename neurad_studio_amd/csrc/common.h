@@ -79,6 +79,45 @@ inline RaysDev to_dev(const nrhip_rays& r) {
 }
 int validate_rays(const nrhip_rays* r);
 
+// nrhip_packed_rays on the device: the occupancy march's ragged segments.  Ray r owns the samples [segs[r], segs[r + 1]) of
+// the [M]-shaped interval arrays and of every per-sample tensor; origins / directions / pixel area stay per RAY.  segs is
+// NULL where the caller names a sample's ray another way (the table gradient's ray_of).
+struct PackedRaysDev {
+  int64_t R;
+  int M;  // 1 <= M < 2^31: a batch without samples never reaches a kernel
+  const float* o;
+  const float* d;
+  const float* area;
+  const float* starts;
+  const float* ends;
+  const int64_t* segs;
+};
+inline PackedRaysDev to_dev(const nrhip_packed_rays& r) {
+  return PackedRaysDev{r.n_rays, (int)r.n_samples, r.origins, r.directions, r.pixel_area, r.t_starts, r.t_ends, r.segments};
+}
+// The one check of the descriptor, for every entry point that takes one (`who` names it in the message): not NULL, counts
+// not negative, M < 2^31, and -- unless the batch has no rays or no samples, when nothing is read -- no NULL array; the
+// segments only where the entry point walks them.
+int validate_packed_rays(const char* who, const nrhip_packed_rays* r, bool need_segments);
+
+// Where a ray's samples lie, for kernels written once over both layouts: samples of the ray; row of a per-sample tensor
+// that holds sample s of the ray; index of its interval in starts / ends.  Packed: the count is clamped into [0, M] and
+// every index into [0, M), so segments that break their precondition still read inside the arrays.
+__device__ __forceinline__ int ray_sample_count(const RaysDev& r, int64_t) { return r.S; }
+__device__ __forceinline__ int64_t ray_sample_row(const RaysDev& r, int64_t ray, int s) { return ray * r.S + s; }
+__device__ __forceinline__ int64_t ray_sample_interval(const RaysDev& r, int64_t ray, int s) { return ray * r.stride + s; }
+__device__ __forceinline__ int ray_sample_count(const PackedRaysDev& r, int64_t ray) {
+  const int64_t n = r.segs[ray + 1] - r.segs[ray];
+  return (int)(n < (int64_t)r.M ? n : (int64_t)r.M);
+}
+__device__ __forceinline__ int64_t ray_sample_row(const PackedRaysDev& r, int64_t ray, int s) {
+  const int64_t i = r.segs[ray] + s;
+  return i < 0 ? 0 : (i < (int64_t)r.M ? i : (int64_t)r.M - 1);
+}
+__device__ __forceinline__ int64_t ray_sample_interval(const PackedRaysDev& r, int64_t ray, int s) {
+  return ray_sample_row(r, ray, s);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Table element loads: F features of one entry, fp32 or fp16 storage, one vector load each.
 // ---------------------------------------------------------------------------------------------

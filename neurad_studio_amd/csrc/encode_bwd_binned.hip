@@ -194,16 +194,17 @@ __device__ __forceinline__ bool rows_are_zero(const float* __restrict__ g, int w
   return z;
 }
 
-// Where the samples and their feature gradients come from (pass A is otherwise identical):
-//   position(i) -> (x, y, z in [0,1]^3, aux);  grad(i, l, level scale, aux, gv[F]) -> dL/d(level-l features of sample i)
+// Where the samples and their feature gradients come from (pass A is otherwise identical).  A source is two parts:
+//   where the positions come from    position(i) -> (x, y, z in [0,1]^3, aux)
+//   what the per-level gradient is   pre(i) -> the level-independent factor, once per sample (a workgroup may walk all levels)
+//                                    grad(i, l, level scale, aux, pre, gv[F]) -> dL/d(level-l features of sample i)
+//                                    silent(w0, n_rows) -> the sample w0 + lane sends nothing (whole waves call it)
+// and SampleSrc puts one of each together (base classes in this order: the kernel argument is the members side by side).
 __device__ __forceinline__ int coherent_rays_of(const RaysDev& r, int64_t first_sample, int64_t count);  // (see `prep`)
 
-struct EncodeSrc {  // H2+H3+H1+H4 (nrhip_encode_bwd): positions from ray samples, gradient of the rescaled features
-  static constexpr bool kMulti = false;
+struct DenseRayPos {  // H2+H3 of [R,S] ray samples: sample i is sample i % S of ray i / S
   RaysDev r;
   float scale;
-  const float* go;
-  int L;
   __device__ float4 position(int64_t i) const {
     const int64_t ray = i / r.S;
     const int s = (int)(i - ray * r.S);
@@ -212,106 +213,42 @@ struct EncodeSrc {  // H2+H3+H1+H4 (nrhip_encode_bwd): positions from ray sample
                                         r.ends[ray * r.stride + s], scale);
     return make_float4(p.x, p.y, p.z, p.std);
   }
-  __device__ float pre(int64_t) const { return 0.f; }
-  template <int F>
-  __device__ void grad(int64_t i, int l, float sc, float std, float, float (&gv)[F]) const {
-    const float rw = rescale_weight(sc, std);
-#pragma unroll
-    for (int k = 0; k < F; ++k) gv[k] = go[(i * L + l) * F + k] * rw;
-  }
-  int width;  // L * F
-  __device__ bool silent(int64_t w0, int64_t n_rows) const { return rows_are_zero(go, width, w0, n_rows); }
-  __device__ int coherent_rays(int64_t first, int64_t count) const { return coherent_rays_of(r, first, count); }
 };
-struct PackedEncodeSrc {  // EncodeSrc for packed samples (nrhip_encode_bwd_binned_packed): sample i belongs to ray ray_of[i]
-  static constexpr bool kMulti = false;
-  const float* o;     // [R, 3]
-  const float* d;     // [R, 3]
-  const float* area;  // [R]
-  const float* starts;  // [M]
-  const float* ends;    // [M]
-  const int64_t* ray_of;  // [M] the march's ray_indices
+struct PackedRayPos {  // the same of packed samples (common.h PackedRaysDev): sample i belongs to ray ray_of[i]
+  PackedRaysDev r;        // (the segments are not read: the partition walks samples, not rays)
+  const int64_t* ray_of;  // [M] the march's ray_indices, every entry in [0, R)
   float scale;
-  const float* go;
-  int L;
   __device__ float4 position(int64_t i) const {
     const int64_t ray = ray_of[i];
-    const SamplePos p = sample_position(o[3 * ray], o[3 * ray + 1], o[3 * ray + 2], d[3 * ray], d[3 * ray + 1],
-                                        d[3 * ray + 2], area[ray], starts[i], ends[i], scale);
+    const SamplePos p = sample_position(r.o[3 * ray], r.o[3 * ray + 1], r.o[3 * ray + 2], r.d[3 * ray], r.d[3 * ray + 1],
+                                        r.d[3 * ray + 2], r.area[ray], r.starts[i], r.ends[i], scale);
     return make_float4(p.x, p.y, p.z, p.std);
   }
+};
+struct GivenPos {  // positions given, [N,3]
+  const float* x;
+  __device__ float4 position(int64_t i) const { return make_float4(x[3 * i], x[3 * i + 1], x[3 * i + 2], 0.f); }
+};
+
+template <bool RESCALED>
+struct RowGrad {  // rows of go [N, L*F]; RESCALED: of the rescaled features (H4), aux = the sample's contracted std
+  const float* go;
+  int L;
+  int width;  // L * F
   __device__ float pre(int64_t) const { return 0.f; }
   template <int F>
   __device__ void grad(int64_t i, int l, float sc, float std, float, float (&gv)[F]) const {
-    const float rw = rescale_weight(sc, std);
+    float rw = 1.f;
+    if constexpr (RESCALED) rw = rescale_weight(sc, std);
 #pragma unroll
-    for (int k = 0; k < F; ++k) gv[k] = go[(i * L + l) * F + k] * rw;
+    for (int k = 0; k < F; ++k) gv[k] = RESCALED ? go[(i * L + l) * F + k] * rw : go[(i * L + l) * F + k];
   }
-  int width;  // L * F
   __device__ bool silent(int64_t w0, int64_t n_rows) const { return rows_are_zero(go, width, w0, n_rows); }
-  __device__ int coherent_rays(int64_t, int64_t) const { return 0; }  // ragged rays: no [R, S] block to transpose
 };
-struct GridSrc {  // H1 (nrhip_hashgrid_bwd): positions given
-  static constexpr bool kMulti = false;
-  const float* x;
-  const float* go;
-  int L;
-  __device__ float4 position(int64_t i) const { return make_float4(x[3 * i], x[3 * i + 1], x[3 * i + 2], 0.f); }
-  __device__ float pre(int64_t) const { return 0.f; }
-  template <int F>
-  __device__ void grad(int64_t i, int l, float, float, float, float (&gv)[F]) const {
-#pragma unroll
-    for (int k = 0; k < F; ++k) gv[k] = go[(i * L + l) * F + k];
-  }
-  int width;  // L * F
-  __device__ bool silent(int64_t w0, int64_t n_rows) const { return rows_are_zero(go, width, w0, n_rows); }
-  __device__ int coherent_rays(int64_t, int64_t) const { return 0; }  // bare positions: no rays to compare
-};
-struct MultiSrc {  // H5's per-actor grids (nrhip_hashgrid_multi_bwd_binned): positions given, ONE of n_grids tables per sample
-  static constexpr bool kMulti = true;  // `count` / `emit` read the slot from the position's fourth component
-  const float* x;
-  const float* go;
-  const int* gid;      // [N] grid of each sample (< 0 or >= n_grids: the sample sends nothing)
-  const int* slot_of;  // [n_grids] position of the grid's gradient in the output block, < 0: no gradient wanted
-  int n_grids;
-  int L;
-  int width;  // L * F
-  __device__ int slot(int64_t i) const {
-    const int g_ = gid[i];
-    return (g_ >= 0 && g_ < n_grids) ? slot_of[g_] : -1;
-  }
-  // (the fourth component is the std of the ray-sample sources; here it carries the slot to `count` / `emit`)
-  __device__ float4 position(int64_t i) const { return make_float4(x[3 * i], x[3 * i + 1], x[3 * i + 2], __int_as_float(slot(i))); }
-  __device__ float pre(int64_t) const { return 0.f; }
-  template <int F>
-  __device__ void grad(int64_t i, int l, float, float, float, float (&gv)[F]) const {
-#pragma unroll
-    for (int k = 0; k < F; ++k) gv[k] = go[(i * L + l) * F + k];
-  }
-  __device__ bool silent(int64_t w0, int64_t n_rows) const {
-    bool z = rows_are_zero(go, width, w0, n_rows);
-    const int64_t i = w0 + (threadIdx.x & 63);
-    if (i < n_rows && slot(i) < 0) z = true;
-    return z;
-  }
-  __device__ int coherent_rays(int64_t, int64_t) const { return 0; }
-};
-struct ProposalSrc {  // S2 (nrhip_proposal_density_bwd): density = trunc_exp(decoder . rescaled features), F = 1
-  static constexpr bool kMulti = false;
-  RaysDev r;
-  float scale;
+struct ProposalGrad {  // S2: density = trunc_exp(decoder . rescaled features), F = 1
   const float* dec;
   const float* dens;
   const float* gd;
-  __device__ float4 position(int64_t i) const {
-    const int64_t ray = i / r.S;
-    const int s = (int)(i - ray * r.S);
-    const SamplePos p = sample_position(r.o[3 * ray], r.o[3 * ray + 1], r.o[3 * ray + 2], r.d[3 * ray],
-                                        r.d[3 * ray + 1], r.d[3 * ray + 2], r.area[ray], r.starts[ray * r.stride + s],
-                                        r.ends[ray * r.stride + s], scale);
-    return make_float4(p.x, p.y, p.z, p.std);
-  }
-  // the level-independent factor of a sample's gradient, once per sample (a workgroup may walk all levels)
   __device__ float pre(int64_t i) const {
     const float xlog = logf(dens[i]);  // activations.py:37-41: g * exp(clamp(x, -15, 15))
     return gd[i] * expf(fminf(fmaxf(xlog, -15.f), 15.f));
@@ -324,7 +261,40 @@ struct ProposalSrc {  // S2 (nrhip_proposal_density_bwd): density = trunc_exp(de
     const int64_t i = w0 + (threadIdx.x & 63);
     return i < n_rows ? gd[i] == 0.f : true;
   }
-  __device__ int coherent_rays(int64_t first, int64_t count) const { return coherent_rays_of(r, first, count); }
+};
+
+template <class Pos, class Grad>
+struct SampleSrc : Pos, Grad {
+  static constexpr bool kMulti = false;
+  // rays of a chunk that may be walked sample-index-major (see `prep`); 0 where there is no [R,S] block to transpose:
+  // ragged rays, bare positions
+  __device__ int coherent_rays(int64_t first, int64_t count) const {
+    if constexpr (std::is_same_v<Pos, DenseRayPos>) return coherent_rays_of(this->r, first, count);
+    return 0;
+  }
+};
+using EncodeSrc = SampleSrc<DenseRayPos, RowGrad<true>>;         // H2+H3+H1+H4 (nrhip_encode_bwd_binned)
+using PackedEncodeSrc = SampleSrc<PackedRayPos, RowGrad<true>>;  // the same on packed samples (nrhip_encode_bwd_binned_packed)
+using GridSrc = SampleSrc<GivenPos, RowGrad<false>>;             // H1 (nrhip_hashgrid_bwd_binned)
+using ProposalSrc = SampleSrc<DenseRayPos, ProposalGrad>;        // S2 (nrhip_proposal_density_bwd_binned)
+
+struct MultiSrc : GridSrc {  // H5's per-actor grids (nrhip_hashgrid_multi_bwd_binned): ONE of n_grids tables per sample
+  static constexpr bool kMulti = true;  // `count` / `emit` read the slot from the position's fourth component
+  const int* gid;      // [N] grid of each sample (< 0 or >= n_grids: the sample sends nothing)
+  const int* slot_of;  // [n_grids] position of the grid's gradient in the output block, < 0: no gradient wanted
+  int n_grids;
+  __device__ int slot(int64_t i) const {
+    const int g_ = gid[i];
+    return (g_ >= 0 && g_ < n_grids) ? slot_of[g_] : -1;
+  }
+  // (the fourth component is the std of the ray-sample sources; here it carries the slot to `count` / `emit`)
+  __device__ float4 position(int64_t i) const { return make_float4(x[3 * i], x[3 * i + 1], x[3 * i + 2], __int_as_float(slot(i))); }
+  __device__ bool silent(int64_t w0, int64_t n_rows) const {
+    bool z = GridSrc::silent(w0, n_rows);
+    const int64_t i = w0 + (threadIdx.x & 63);
+    if (i < n_rows && slot(i) < 0) z = true;
+    return z;
+  }
 };
 
 // ---- prep ----------------------------------------------------------------------------------------------------
@@ -891,77 +861,68 @@ int run_binned(const char* what, const GridDev& gd, const Src& src, int64_t n, f
 
 }  // namespace
 
+// The ray-sample entry points, one body per layout; grad_dtype: 0 an fp32 grad_table, 1 the fp16 gradient of an fp16-storage
+// table, which is written once (overwrite) and therefore needs a sample.  It goes into gd.dtype, whatever the table's own
+// storage type (g->param_dtype) is.
+static int encode_binned_dense(const char* who, int grad_dtype, const nrhip_grid* g, float static_scale, const nrhip_rays* rays,
+                               const float* grad_out, void* grad_table, bool overwrite, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  if (int e = validate_grid(g)) return e;
+  if (int e = validate_rays(rays)) return e;
+  NR_REQUIRE(grad_out && grad_table && static_scale > 0.f, NRHIP_ERR_INVALID_ARG, "%s: bad argument", who);
+  const int64_t n = rays->n_rays * rays->n_samples;
+  NR_REQUIRE(n > 0 || grad_dtype == 0, NRHIP_ERR_INVALID_ARG, "%s: every element is written: at least one sample", who);
+  if (n == 0) return NRHIP_OK;
+  GridDev gd = to_dev(*g);
+  gd.dtype = grad_dtype;
+  const EncodeSrc src{{to_dev(*rays), static_scale}, {grad_out, gd.L, gd.L * gd.F}};
+  return run_binned(who, gd, src, n, static_cast<float*>(grad_table), overwrite, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// packed samples [M] of ragged rays; ray_of [M] = the march's ray_indices (the segments are not needed)
+static int encode_binned_packed(const char* who, int grad_dtype, const nrhip_grid* g, float static_scale,
+                                const nrhip_packed_rays* rays, const int64_t* ray_of, const float* grad_out, void* grad_table,
+                                bool overwrite, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int e = validate_grid(g)) return e;
+  if (int e = validate_packed_rays(who, rays, false)) return e;
+  NR_REQUIRE(grad_table && static_scale > 0.f, NRHIP_ERR_INVALID_ARG, "%s: NULL grad_table or non-positive scale", who);
+  const int64_t n = rays->n_samples;
+  NR_REQUIRE(n == 0 || (rays->n_rays > 0 && ray_of && grad_out), NRHIP_ERR_INVALID_ARG,
+             "%s: samples without rays, or a NULL pointer", who);
+  NR_REQUIRE(n > 0 || grad_dtype == 0, NRHIP_ERR_INVALID_ARG, "%s: every element is written: at least one sample", who);
+  if (n == 0) return NRHIP_OK;
+  GridDev gd = to_dev(*g);
+  gd.dtype = grad_dtype;
+  const PackedEncodeSrc src{{to_dev(*rays), ray_of, static_scale}, {grad_out, gd.L, gd.L * gd.F}};
+  return run_binned(who, gd, src, n, static_cast<float*>(grad_table), overwrite, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 extern "C" int nrhip_encode_bwd_binned(const nrhip_grid* g, float static_scale, const nrhip_rays* rays,
                                        const float* grad_out, float* grad_table, int32_t overwrite, void* workspace,
                                        int64_t workspace_bytes, void* stream) {
-  if (int e = validate_grid(g)) return e;
-  if (int e = validate_rays(rays)) return e;
-  NR_REQUIRE(grad_out && grad_table && static_scale > 0.f, NRHIP_ERR_INVALID_ARG, "encode_bwd_binned: bad argument");
-  const int64_t n = rays->n_rays * rays->n_samples;
-  if (n == 0) return NRHIP_OK;
-  GridDev gd = to_dev(*g);
-  gd.dtype = 0;  // fp32 grad_table, whatever the table's storage type (g->param_dtype) is
-  const EncodeSrc src{to_dev(*rays), static_scale, grad_out, gd.L, gd.L * gd.F};
-  return run_binned("encode_bwd_binned", gd, src, n, grad_table, overwrite != 0, workspace, workspace_bytes,
-                    (hipStream_t)stream);
+  return encode_binned_dense("encode_bwd_binned", 0, g, static_scale, rays, grad_out, grad_table, overwrite != 0, workspace,
+                             workspace_bytes, stream);
 }
 
 extern "C" int nrhip_encode_bwd_binned_f16(const nrhip_grid* g, float static_scale, const nrhip_rays* rays,
                                            const float* grad_out, void* grad_table_fp16, void* workspace,
                                            int64_t workspace_bytes, void* stream) {
-  if (int e = validate_grid(g)) return e;
-  if (int e = validate_rays(rays)) return e;
-  NR_REQUIRE(grad_out && grad_table_fp16 && static_scale > 0.f, NRHIP_ERR_INVALID_ARG, "encode_bwd_binned_f16: bad argument");
-  const int64_t n = rays->n_rays * rays->n_samples;
-  NR_REQUIRE(n > 0, NRHIP_ERR_INVALID_ARG, "encode_bwd_binned_f16: every element is written: at least one sample");
-  GridDev gd = to_dev(*g);
-  gd.dtype = 1;  // fp16 grad_table
-  const EncodeSrc src{to_dev(*rays), static_scale, grad_out, gd.L, gd.L * gd.F};
-  return run_binned("encode_bwd_binned_f16", gd, src, n, static_cast<float*>(grad_table_fp16), true, workspace,
-                    workspace_bytes, (hipStream_t)stream);
-}
-
-// the packed pair: samples [M] of ragged rays, ray_of [M] = the march's ray_indices (every entry in [0, n_rays))
-static int check_packed_src(const char* what, const nrhip_packed_rays* rays, const int64_t* ray_of, const float* grad_out,
-                            const void* grad_table, float static_scale) {
-  NR_REQUIRE(rays, NRHIP_ERR_INVALID_ARG, "%s: rays descriptor is NULL", what);
-  NR_REQUIRE(rays->n_rays >= 0 && rays->n_samples >= 0, NRHIP_ERR_INVALID_ARG, "%s: negative ray/sample count", what);
-  NR_REQUIRE(rays->n_samples < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "%s: M >= 2^31", what);
-  NR_REQUIRE(grad_table && static_scale > 0.f, NRHIP_ERR_INVALID_ARG, "%s: NULL grad_table or non-positive scale", what);
-  NR_REQUIRE(rays->n_samples == 0 || (rays->n_rays > 0 && rays->origins && rays->directions && rays->pixel_area &&
-                                      rays->t_starts && rays->t_ends && ray_of && grad_out),
-             NRHIP_ERR_INVALID_ARG, "%s: samples without rays, or a NULL pointer", what);
-  return NRHIP_OK;
+  return encode_binned_dense("encode_bwd_binned_f16", 1, g, static_scale, rays, grad_out, grad_table_fp16, true, workspace,
+                             workspace_bytes, stream);
 }
 
 extern "C" int nrhip_encode_bwd_binned_packed(const nrhip_grid* g, float static_scale, const nrhip_packed_rays* rays,
                                               const int64_t* ray_of, const float* grad_out, float* grad_table,
                                               int32_t overwrite, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int e = validate_grid(g)) return e;
-  if (int e = check_packed_src("encode_bwd_binned_packed", rays, ray_of, grad_out, grad_table, static_scale)) return e;
-  const int64_t n = rays->n_samples;
-  if (n == 0) return NRHIP_OK;
-  GridDev gd = to_dev(*g);
-  gd.dtype = 0;  // fp32 grad_table, whatever the table's storage type (g->param_dtype) is
-  const PackedEncodeSrc src{rays->origins, rays->directions, rays->pixel_area, rays->t_starts, rays->t_ends, ray_of,
-                            static_scale,  grad_out,         gd.L,             gd.L * gd.F};
-  return run_binned("encode_bwd_binned_packed", gd, src, n, grad_table, overwrite != 0, workspace, workspace_bytes,
-                    (hipStream_t)stream);
+  return encode_binned_packed("encode_bwd_binned_packed", 0, g, static_scale, rays, ray_of, grad_out, grad_table, overwrite != 0,
+                              workspace, workspace_bytes, stream);
 }
 
 extern "C" int nrhip_encode_bwd_binned_packed_f16(const nrhip_grid* g, float static_scale, const nrhip_packed_rays* rays,
                                                   const int64_t* ray_of, const float* grad_out, void* grad_table_fp16,
                                                   void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int e = validate_grid(g)) return e;
-  if (int e = check_packed_src("encode_bwd_binned_packed_f16", rays, ray_of, grad_out, grad_table_fp16, static_scale)) return e;
-  const int64_t n = rays->n_samples;
-  NR_REQUIRE(n > 0, NRHIP_ERR_INVALID_ARG, "encode_bwd_binned_packed_f16: every element is written: at least one sample");
-  GridDev gd = to_dev(*g);
-  gd.dtype = 1;  // fp16 grad_table
-  const PackedEncodeSrc src{rays->origins, rays->directions, rays->pixel_area, rays->t_starts, rays->t_ends, ray_of,
-                            static_scale,  grad_out,         gd.L,             gd.L * gd.F};
-  return run_binned("encode_bwd_binned_packed_f16", gd, src, n, static_cast<float*>(grad_table_fp16), true, workspace,
-                    workspace_bytes, (hipStream_t)stream);
+  return encode_binned_packed("encode_bwd_binned_packed_f16", 1, g, static_scale, rays, ray_of, grad_out, grad_table_fp16, true,
+                              workspace, workspace_bytes, stream);
 }
 
 extern "C" int nrhip_hashgrid_bwd_binned(const nrhip_grid* g, const float* x, const float* grad_out, int64_t n,
@@ -972,7 +933,7 @@ extern "C" int nrhip_hashgrid_bwd_binned(const nrhip_grid* g, const float* x, co
   if (n == 0) return NRHIP_OK;
   GridDev gd = to_dev(*g);
   gd.dtype = 0;  // fp32 grad_table
-  const GridSrc src{x, grad_out, gd.L, gd.L * gd.F};
+  const GridSrc src{{x}, {grad_out, gd.L, gd.L * gd.F}};
   return run_binned("hashgrid_bwd_binned", gd, src, n, grad_table, overwrite != 0, workspace, workspace_bytes,
                     (hipStream_t)stream);
 }
@@ -997,7 +958,7 @@ extern "C" int nrhip_hashgrid_multi_bwd_binned(const nrhip_grid* g, int32_t n_gr
   NR_REQUIRE(((int64_t)n_slots << gd.log2T) < ((int64_t)1 << 32) - 1, NRHIP_ERR_UNSUPPORTED,
              "hashgrid_multi_bwd_binned: %d tables of 2^%d entries exceed 32-bit entry numbers", n_slots, gd.log2T);
   gd.dtype = block_dtype;  // the block's type: 1 = fp16 gradients for fp16-storage tables (one round only)
-  const MultiSrc src{x, grad_out, grid_id, slot_of, n_grids, gd.L, gd.L * gd.F};
+  const MultiSrc src{{{x}, {grad_out, gd.L, gd.L * gd.F}}, grid_id, slot_of, n_grids};
   return run_binned("hashgrid_multi_bwd_binned", gd, src, n, static_cast<float*>(grad_block), true, workspace, workspace_bytes,
                     (hipStream_t)stream, n_slots);
 }
@@ -1010,7 +971,7 @@ int proposal_table_grad_binned(const nrhip_proposal* p, const nrhip_rays* rays, 
   const int64_t n = rays->n_rays * rays->n_samples;
   GridDev gd = to_dev(p->grid);
   gd.dtype = 0;  // (here the descriptor's param_dtype is the TABLE's storage type; this entry point's grad_table is fp32)
-  const ProposalSrc src{to_dev(*rays), p->static_scale, p->decoder_weight, density, grad_density};
+  const ProposalSrc src{{to_dev(*rays), p->static_scale}, {p->decoder_weight, density, grad_density}};
   return run_binned("proposal_density_bwd_binned", gd, src, n, grad_table, overwrite, workspace, workspace_bytes,
                     (hipStream_t)stream);
 }

@@ -71,40 +71,11 @@ __global__ __launch_bounds__(256) void hashgrid_multi_bwd_input_kernel(GridDev g
 // One group of G lanes per ray (G = 16 / 32 / 64 by samples per ray), lanes stride over the samples, xor-butterfly over the
 // group, lane 0 WRITES the ray's two rows: no atomics, bit-reproducible.  Samples whose whole gradient row is zero (behind
 // an opaque surface; rows overridden by an actor) skip their 8 L gathers.
-// ONE kernel body for both sample layouts; `Rays` says where a ray's samples lie (the three accessors below):
-//   RaysDev        [R,S] samples, intervals with a row stride                       (nrhip_encode_bwd_rays)
-//   PackedRaysDev  the occupancy march's ragged segments: ray r owns the samples [segs[r], segs[r + 1]) of the [M]-shaped
-//                  interval arrays and of go [M, L*F]; origins / directions / pixel area stay per RAY and are read once per
-//                  ray.  A ray's rows depend on its own samples and on G alone (lane `sub` adds the samples sub, sub + G, ...
-//                  in that order, then the butterfly), never on where the ray sits in the batch; a ray without samples gets
-//                  two rows of zeros.  The count is clamped into [0, M] and every index into [0, M): segments that break
-//                  their precondition still read inside the arrays.              (nrhip_encode_bwd_rays_packed)
-struct PackedRaysDev {
-  int64_t R;
-  int M;  // 1 <= M < 2^31: a batch without samples never reaches the kernel
-  const float* o;
-  const float* d;
-  const float* area;
-  const float* starts;
-  const float* ends;
-  const int64_t* segs;
-};
-// samples of the ray; row of go that holds sample s of the ray; index of its interval in starts / ends
-__device__ __forceinline__ int ray_sample_count(const RaysDev& r, int64_t) { return r.S; }
-__device__ __forceinline__ int64_t ray_sample_row(const RaysDev& r, int64_t ray, int s) { return ray * r.S + s; }
-__device__ __forceinline__ int64_t ray_sample_interval(const RaysDev& r, int64_t ray, int s) { return ray * r.stride + s; }
-__device__ __forceinline__ int ray_sample_count(const PackedRaysDev& r, int64_t ray) {
-  const int64_t n = r.segs[ray + 1] - r.segs[ray];
-  return (int)(n < (int64_t)r.M ? n : (int64_t)r.M);
-}
-__device__ __forceinline__ int64_t ray_sample_row(const PackedRaysDev& r, int64_t ray, int s) {
-  const int64_t i = r.segs[ray] + s;
-  return i < 0 ? 0 : (i < (int64_t)r.M ? i : (int64_t)r.M - 1);
-}
-__device__ __forceinline__ int64_t ray_sample_interval(const PackedRaysDev& r, int64_t ray, int s) {
-  return ray_sample_row(r, ray, s);
-}
-
+// ONE kernel body for both sample layouts; `Rays` says where a ray's samples lie, through the ray_sample_* accessors of
+// common.h: RaysDev, [R,S] samples with a row stride (nrhip_encode_bwd_rays), or PackedRaysDev, the march's ragged segments
+// (nrhip_encode_bwd_rays_packed; go is [M, L*F] at the packed sample index).  Ray constants are read once per ray.  A ray's
+// rows depend on its own samples and on G alone (lane `sub` adds the samples sub, sub + G, ... in that order, then the
+// butterfly), never on where the ray sits in the batch; a ray without samples gets two rows of zeros.
 template <int F, bool HALF, class Rays>
 __global__ __launch_bounds__(256) void encode_bwd_rays_kernel(GridDev g, const void* __restrict__ table, float scale,
                                                                Rays r, const float* __restrict__ go, int G,
@@ -241,10 +212,7 @@ extern "C" int nrhip_encode_bwd_rays_packed(const nrhip_grid* g, const void* tab
                                             const nrhip_packed_rays* rays, const float* grad_out, int32_t lanes_per_ray,
                                             float* grad_origins, float* grad_directions, void* stream) {
   if (int e = validate_grid(g)) return e;
-  NR_REQUIRE(rays, NRHIP_ERR_INVALID_ARG, "encode_bwd_rays_packed: rays descriptor is NULL");
-  NR_REQUIRE(rays->n_rays >= 0 && rays->n_samples >= 0, NRHIP_ERR_INVALID_ARG,
-             "encode_bwd_rays_packed: negative ray/sample count");
-  NR_REQUIRE(rays->n_samples < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "encode_bwd_rays_packed: M >= 2^31");
+  if (int e = validate_packed_rays("encode_bwd_rays_packed", rays, true)) return e;
   NR_REQUIRE(static_scale > 0.f, NRHIP_ERR_INVALID_ARG, "encode_bwd_rays_packed: non-positive scale");
   NR_REQUIRE(lanes_per_ray == 0 || lanes_per_ray == 16 || lanes_per_ray == 32 || lanes_per_ray == 64, NRHIP_ERR_INVALID_ARG,
              "encode_bwd_rays_packed: lanes_per_ray %d not in {0, 16, 32, 64}", lanes_per_ray);
@@ -259,11 +227,9 @@ extern "C" int nrhip_encode_bwd_rays_packed(const nrhip_grid* g, const void* tab
       return check_launch("encode_bwd_rays_packed");
     return NRHIP_OK;
   }
-  NR_REQUIRE(table && grad_out && rays->origins && rays->directions && rays->pixel_area && rays->t_starts && rays->t_ends &&
-                 rays->segments,
-             NRHIP_ERR_INVALID_ARG, "encode_bwd_rays_packed: NULL pointer");
+  NR_REQUIRE(table && grad_out, NRHIP_ERR_INVALID_ARG, "encode_bwd_rays_packed: NULL pointer");
   const GridDev gd = to_dev(*g);
-  const PackedRaysDev rd{R, (int)M, rays->origins, rays->directions, rays->pixel_area, rays->t_starts, rays->t_ends, rays->segments};
+  const PackedRaysDev rd = to_dev(*rays);
   // the dense rule on the MEAN count M / R (both are shapes: no device read)
   const int G = lanes_per_ray ? lanes_per_ray : (M > 32 * R ? 64 : (M > 16 * R ? 32 : 16));
   const int blocks = grid_for(R * G, 256);

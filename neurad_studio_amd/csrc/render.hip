@@ -547,8 +547,8 @@ __device__ __forceinline__ void load_pending(PendingTile& p, int64_t pos, int t,
   p.ncand = cand_count ? cand_count[ray] : 0;
 }
 
-// Lay::Packed: ray r owns the samples [segs[r], segs[r + 1]) of the [M]-shaped interval arrays, M = rr.S >= 1 (a batch
-// without samples never reaches the kernel).  The index of every load stays inside [0, M): a lane past the ray's end reads
+// Lay::Packed: the layout of PackedRaysDev (common.h) read through the kernel's own arguments (packed_launch_rays below):
+// M = rr.S >= 1.  This pipeline clamps for itself -- the index of every load stays inside [0, M): a lane past the ray's end reads
 // the ray's last sample; an empty segment gives b - 1 <= M - 1, which is -1 only for b == 0, where sample 0 stands in.
 // The last clamp holds the reads inside the arrays even for segments that break their precondition.
 __device__ __forceinline__ void load_pending_packed(PendingTile& p, int64_t pos, int t, const RayRange& rr, int j,
@@ -1555,20 +1555,25 @@ extern "C" int nrhip_render_fwd(const nrhip_field* f, const nrhip_rays* rays, fl
   return nrhip_render_fwd_ex(f, rays, out_features, out_depth, out_acc, out_weights, 0.f, stream);
 }
 
+// The RaysDev that launch_render takes for Lay::Packed / Lay::PackedRows: `S` carries the sample count M, the stride is 0,
+// and the segments travel beside it in RenderArgs (the kernel reads them through its `tables` argument).
+static RaysDev packed_launch_rays(const nrhip_packed_rays& rays) {
+  const PackedRaysDev p = to_dev(rays);
+  return RaysDev{p.R, p.M, 0, p.o, p.d, p.area, p.starts, p.ends, rays.order};
+}
+
 extern "C" int nrhip_render_fwd_packed(const nrhip_field* f, const nrhip_packed_rays* rays, float* out_features,
                                        float* out_depth, float* out_acc, float* out_weights, float early_stop_eps,
                                        void* stream) {
   if (int e = validate_field(f)) return e;
-  NR_REQUIRE(rays, NRHIP_ERR_INVALID_ARG, "render_fwd_packed: rays descriptor is NULL");
-  const int64_t R = rays->n_rays, M = rays->n_samples;
-  NR_REQUIRE(R >= 0 && M >= 0, NRHIP_ERR_INVALID_ARG, "render_fwd_packed: negative ray/sample count");
+  if (int e = validate_packed_rays("render_fwd_packed", rays, true)) return e;
+  const int64_t R = rays->n_rays;
   if (R == 0) return NRHIP_OK;
   NR_REQUIRE(out_features && out_depth && out_acc, NRHIP_ERR_INVALID_ARG, "render_fwd_packed: NULL output");
   NR_REQUIRE(early_stop_eps >= 0.f && early_stop_eps < 1.f, NRHIP_ERR_INVALID_ARG,
              "render_fwd_packed: early_stop_eps %g not in [0,1)", (double)early_stop_eps);
-  NR_REQUIRE(M < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "render_fwd_packed: M >= 2^31");
   hipStream_t st = (hipStream_t)stream;
-  if (M == 0) {  // every segment is empty: no sample pointer (and no segment) is read, the per-ray outputs are zeroed
+  if (rays->n_samples == 0) {  // every segment is empty: no sample pointer (and no segment) is read, the per-ray outputs are zeroed
     if (hipMemsetAsync(out_features, 0, (size_t)R * 32 * sizeof(float), st) != hipSuccess ||
         hipMemsetAsync(out_depth, 0, (size_t)R * sizeof(float), st) != hipSuccess ||
         hipMemsetAsync(out_acc, 0, (size_t)R * sizeof(float), st) != hipSuccess) {
@@ -1577,32 +1582,23 @@ extern "C" int nrhip_render_fwd_packed(const nrhip_field* f, const nrhip_packed_
     }
     return NRHIP_OK;
   }
-  NR_REQUIRE(rays->origins && rays->directions && rays->pixel_area && rays->t_starts && rays->t_ends && rays->segments,
-             NRHIP_ERR_INVALID_ARG, "render_fwd_packed: rays descriptor has a NULL pointer");
   RenderArgs a{};
   a.feat = out_features, a.depth = out_depth, a.acc = out_acc, a.w = out_weights;
   a.stop_eps = early_stop_eps, a.stream = st, a.segments = rays->segments;
-  const RaysDev rd{R, (int)M, 0, rays->origins, rays->directions, rays->pixel_area, rays->t_starts, rays->t_ends, rays->order};
-  return dispatch_render_packed(f, Out::Composite, rd, a);
+  return dispatch_render_packed(f, Out::Composite, packed_launch_rays(*rays), a);
 }
 
 extern "C" int nrhip_field_fwd_train_packed(const nrhip_field* f, const nrhip_packed_rays* rays, float* feature,
                                             float* geo_out, float* head, float* save_enc, float* save_geo_hidden,
                                             float* save_feat_in, float* save_feat_hidden, void* stream) {
   if (int e = validate_field(f)) return e;
-  NR_REQUIRE(rays, NRHIP_ERR_INVALID_ARG, "field_fwd_train_packed: rays descriptor is NULL");
-  const int64_t R = rays->n_rays, M = rays->n_samples;
-  NR_REQUIRE(R >= 0 && M >= 0, NRHIP_ERR_INVALID_ARG, "field_fwd_train_packed: negative ray/sample count");
-  if (R == 0 || M == 0) return NRHIP_OK;  // nothing per sample to write: no pointer is read
-  NR_REQUIRE(M < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "field_fwd_train_packed: M >= 2^31");
+  if (int e = validate_packed_rays("field_fwd_train_packed", rays, true)) return e;
+  if (rays->n_rays == 0 || rays->n_samples == 0) return NRHIP_OK;  // nothing per sample to write: no pointer is read
   RenderArgs a{};
   a.feat = feature, a.sdf = geo_out, a.alpha = head, a.stream = (hipStream_t)stream, a.segments = rays->segments;
   a.sv = SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
   if (int e = check_train_buffers("field_fwd_train_packed", feature, geo_out, head, a.sv)) return e;
-  NR_REQUIRE(rays->origins && rays->directions && rays->pixel_area && rays->t_starts && rays->t_ends && rays->segments,
-             NRHIP_ERR_INVALID_ARG, "field_fwd_train_packed: rays descriptor has a NULL pointer");
-  const RaysDev rd{R, (int)M, 0, rays->origins, rays->directions, rays->pixel_area, rays->t_starts, rays->t_ends, rays->order};
-  return dispatch_render_packed(f, Out::PerSample, rd, a);
+  return dispatch_render_packed(f, Out::PerSample, packed_launch_rays(*rays), a);
 }
 
 extern "C" int nrhip_render_fwd_actors(const nrhip_field* f, const nrhip_actors* a, const nrhip_rays* rays,

@@ -146,13 +146,27 @@ def _c_mlp(weights: Sequence[Tensor], biases: Sequence[Optional[Tensor]]) -> Tup
     return m, keep
 
 
+def _ray_constants(origins: Tensor, directions: Tensor, pixel_area: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """what both ray descriptors hold per RAY, checked: origins [R,3], directions [R,3], pixel_area flattened to [R]"""
+    return _chk(origins, "origins"), _chk(directions, "directions"), _chk(pixel_area.reshape(-1), "pixel_area")
+
+
+def _ray_order(r, order: Optional[Tensor]) -> Optional[Tensor]:
+    """the optional processing order of a ray descriptor ``r``: int32 [R] from ``ray_order`` (locality hint for the fused
+    kernels), checked and stored -> the tensor the descriptor now points to"""
+    if order is not None:
+        order = _chk(order, "order", torch.int32)
+        if order.shape != (r.n_rays,):
+            raise ValueError(f"order must be int32 [R={r.n_rays}], got {tuple(order.shape)}")
+        r.order = order.data_ptr()
+    return order
+
+
 def _c_rays(origins: Tensor, directions: Tensor, pixel_area: Tensor, starts: Tensor, ends: Tensor,
             order: Optional[Tensor] = None):
     """starts/ends: [R,S] each, or views into one [R,S+1] edge tensor (stride S+1) -- no copies are made.
-    order: optional int32 [R] processing order from ``ray_order`` (locality hint for the fused kernels)."""
-    o = _chk(origins, "origins")
-    d = _chk(directions, "directions")
-    a = _chk(pixel_area.reshape(-1), "pixel_area")
+    order: see ``_ray_order``."""
+    o, d, a = _ray_constants(origins, directions, pixel_area)
     R = o.shape[0]
     if starts.dim() != 2 or starts.shape != ends.shape or starts.shape[0] != R:
         raise ValueError(f"starts/ends must be [R,S] with R={R}; got {tuple(starts.shape)}, {tuple(ends.shape)}")
@@ -166,12 +180,7 @@ def _c_rays(origins: Tensor, directions: Tensor, pixel_area: Tensor, starts: Ten
     r.origins, r.directions, r.pixel_area = o.data_ptr(), d.data_ptr(), a.data_ptr()
     r.starts, r.ends = starts.data_ptr(), ends.data_ptr()
     r.sample_stride = starts.stride(0) if R > 1 else max(S, 1)
-    if order is not None:
-        order = _chk(order, "order", torch.int32)
-        if order.shape != (R,):
-            raise ValueError(f"order must be int32 [R={R}], got {tuple(order.shape)}")
-        r.order = order.data_ptr()
-    return r, (o, d, a, starts, ends, order)
+    return r, (o, d, a, starts, ends, _ray_order(r, order))
 
 
 _RAY_ORDER_LARGE = 16384  # rays above which ray_order takes the multi-workgroup counting sort
@@ -221,6 +230,30 @@ def _table_grad_workspace(c_grid, n_samples: int, device) -> Optional[Tensor]:
     return ws if need > 0 else None
 
 
+def _table_grad(spec: "GridSpec", n_samples: int, device, out_dtype, binned, atomic) -> Tensor:
+    """The gradient [L*T, F] of one table from ``n_samples`` samples, by the partition where ``_table_grad_workspace`` has
+    scratch for it.  binned(suffix, c_grid, *tail) launches the caller's partition entry point: its name + suffix ("_f16":
+    the fp16 gradient of an fp16-storage table, written by the partition itself, one round) with its own arguments between
+    the grid and ``tail`` = (grad_table[, overwrite = 1: every element is written, no zero-fill], workspace, bytes).
+    atomic() -> the gradient by memory-side atomics (fp32 only; the caller casts): a tiny batch, or a table too large to cut
+    into LDS slices."""
+    half = _binned_table_grad(n_samples, out_dtype)[1]
+    dtype = torch.float16 if half else torch.float32
+    g = spec.c_grid(dtype)
+    ws = _table_grad_workspace(g, n_samples, device)
+    if ws is None:
+        return atomic()
+    gt = torch.empty((spec.table_rows, spec.features_per_level), device=device, dtype=dtype)
+    binned("_f16" if half else "", g, gt, *(() if half else (1,)), ws, ws.numel())
+    return gt
+
+
+def _zero_table_grad(spec: "GridSpec", device) -> Tuple[_lib.Grid, Tensor]:
+    """-> (grid descriptor, zeros [L*T, F] fp32) for an atomic (accumulating) entry point"""
+    gt = torch.zeros((spec.table_rows, spec.features_per_level), device=device, dtype=torch.float32)
+    return spec.c_grid(gt), gt
+
+
 def hashgrid_fwd(spec: GridSpec, table: Tensor, x: Tensor) -> Tensor:
     x = _chk(x, "x")
     if x.dim() != 2 or x.shape[1] != 3:
@@ -233,14 +266,15 @@ def hashgrid_fwd(spec: GridSpec, table: Tensor, x: Tensor) -> Tensor:
 
 def hashgrid_bwd(spec: GridSpec, table_like: Tensor, x: Tensor, grad_out: Tensor) -> Tensor:
     x, grad_out = _chk(x, "x"), _chk(grad_out, "grad_out")
-    gt = torch.empty((spec.table_rows, spec.features_per_level), device=x.device, dtype=torch.float32)
-    g = spec.c_grid(gt)
-    ws = _table_grad_workspace(g, x.shape[0], x.device)
-    if ws is not None:  # overwrite = 1: the partition writes every element of the gradient, no zero-fill
-        launch("nrhip_hashgrid_bwd_binned", g, x, grad_out, x.shape[0], gt, 1, ws, ws.numel())
-    else:
-        launch("nrhip_hashgrid_bwd", g, x, grad_out, x.shape[0], gt.zero_())
-    return gt
+    n = x.shape[0]
+
+    def atomic():
+        g, gt = _zero_table_grad(spec, x.device)
+        launch("nrhip_hashgrid_bwd", g, x, grad_out, n, gt)
+        return gt
+
+    return _table_grad(spec, n, x.device, torch.float32,
+                       lambda sfx, g, *tail: launch("nrhip_hashgrid_bwd_binned" + sfx, g, x, grad_out, n, *tail), atomic)
 
 
 _POINTER_TABLES: dict = {}
@@ -374,22 +408,15 @@ def encode_bwd(spec: GridSpec, static_scale: float, origins, directions, pixel_a
     itself where it can (one round, i.e. <= 2^23 samples) -- otherwise fp32 is returned and the caller casts."""
     r, keep = _c_rays(origins, directions, pixel_area, starts, ends)
     grad_out = _chk(grad_out, "grad_out")
-    n = r.n_rays * r.n_samples
-    half = _binned_table_grad(n, out_dtype)[1]
-    gt = torch.empty((spec.table_rows, spec.features_per_level), device=origins.device,
-                     dtype=torch.float16 if half else torch.float32)
-    g = spec.c_grid(gt)
-    ws = _table_grad_workspace(g, n, origins.device)
-    if ws is not None and half:  # the fp16 gradient of an fp16-storage table, written by the partition itself
-        launch("nrhip_encode_bwd_binned_f16", g, float(static_scale), r, grad_out, gt, ws, ws.numel())
-    elif ws is not None:  # overwrite = 1: the partition writes every element of the gradient, no zero-fill
-        launch("nrhip_encode_bwd_binned", g, float(static_scale), r, grad_out, gt, 1, ws, ws.numel())
-    else:  # tables too large to cut into LDS slices, or a tiny batch: memory-side atomics (fp32 only)
-        if gt.dtype != torch.float32:
-            gt = torch.empty((spec.table_rows, spec.features_per_level), device=origins.device, dtype=torch.float32)
-            g = spec.c_grid(gt)
-        launch("nrhip_encode_bwd", g, float(static_scale), r, grad_out, gt.zero_())
-    return gt
+    scale = float(static_scale)
+
+    def atomic():
+        g, gt = _zero_table_grad(spec, origins.device)
+        launch("nrhip_encode_bwd", g, scale, r, grad_out, gt)
+        return gt
+
+    return _table_grad(spec, r.n_rays * r.n_samples, origins.device, out_dtype,
+                       lambda sfx, g, *tail: launch("nrhip_encode_bwd_binned" + sfx, g, scale, r, grad_out, *tail), atomic)
 
 
 def encode_bwd_rays(spec: GridSpec, table: Tensor, static_scale: float, origins, directions, pixel_area, starts, ends,
@@ -1399,26 +1426,25 @@ def packed_composite_fwd(t_starts, t_ends, sigmas_or_alphas, features, segments,
     return of, od, oa, ow
 
 
-def _c_packed_rays(who: str, origins, directions, pixel_area, t_starts, t_ends, segments, order: Optional[Tensor] = None):
+def _c_packed_rays(who: str, origins, directions, pixel_area, t_starts, t_ends, segments: Optional[Tensor] = None,
+                   order: Optional[Tensor] = None):
     """-> (nrhip_packed_rays, the tensors it points to): per-RAY origins [R,3] / directions [R,3] / pixel_area [R], per-sample
-    t_starts / t_ends [M], segments int64 [R+1], optional processing order int32 [R]"""
-    o, d = _chk(origins, "origins"), _chk(directions, "directions")
-    a = _chk(pixel_area.reshape(-1), "pixel_area")
-    seg, R = _seg(segments)
+    t_starts / t_ends [M], segments int64 [R+1] (None: left NULL, for the entry points that take ray_indices instead), optional
+    processing order int32 [R]"""
+    o, d, a = _ray_constants(origins, directions, pixel_area)
+    seg, R = (None, o.shape[0]) if segments is None else _seg(segments)
     if o.shape != (R, 3) or d.shape != (R, 3) or a.shape != (R,):
-        raise ValueError(f"{who}: origins / directions [R,3] and pixel_area [R] with R = {R} = len(segments) - 1")
+        raise ValueError(f"{who}: origins / directions [R,3] and pixel_area [R]"
+                         + ("" if seg is None else f" with R = {R} = len(segments) - 1"))
     s = _flat(t_starts, "t_starts")
     e = _flat(t_ends, "t_ends", s.shape[0])
     r = _lib.PackedRays()
     r.n_rays, r.n_samples = R, s.shape[0]
     r.origins, r.directions, r.pixel_area = o.data_ptr(), d.data_ptr(), a.data_ptr()
-    r.t_starts, r.t_ends, r.segments = s.data_ptr(), e.data_ptr(), seg.data_ptr()
-    if order is not None:
-        order = _chk(order, "order", torch.int32)
-        if order.shape != (R,):
-            raise ValueError(f"order must be int32 [R={R}], got {tuple(order.shape)}")
-        r.order = order.data_ptr()
-    return r, (o, d, a, s, e, seg, order)
+    r.t_starts, r.t_ends = s.data_ptr(), e.data_ptr()
+    if seg is not None:
+        r.segments = seg.data_ptr()
+    return r, (o, d, a, s, e, seg, _ray_order(r, order))
 
 
 def render_fwd_packed(fs: FieldSpec, origins, directions, pixel_area, t_starts, t_ends, segments,
@@ -1519,29 +1545,19 @@ def encode_bwd_packed(spec: GridSpec, static_scale: float, origins, directions, 
     ri = _chk(ray_indices.reshape(-1), "ray_indices", torch.int64)
     n = ri.shape[0]
     grad_out = _chk(grad_out, "grad_out")
-    dev = grad_out.device
-    half = _binned_table_grad(n, out_dtype)[1]
-    gt = torch.empty((spec.table_rows, spec.features_per_level), device=dev, dtype=torch.float16 if half else torch.float32)
-    g = spec.c_grid(gt)
-    ws = _table_grad_workspace(g, n, dev)
-    if ws is None:  # a tiny batch, or tables too large to cut into LDS slices: memory-side atomics on [M,1] rays (fp32 only)
-        o, d = _chk(origins, "origins")[ri], _chk(directions, "directions")[ri]
-        a = _chk(pixel_area.reshape(-1), "pixel_area")[ri]
-        return encode_bwd(spec, static_scale, o, d, a, _flat(t_starts, "t_starts", n).reshape(n, 1),
+
+    def binned(sfx, g, *tail):
+        r, keep = _c_packed_rays("encode_bwd_packed", origins, directions, pixel_area, t_starts, t_ends)
+        if r.n_samples != n:
+            raise ValueError(f"t_starts: {r.n_samples} samples, expected {n}")
+        launch("nrhip_encode_bwd_binned_packed" + sfx, g, float(static_scale), r, ri, grad_out, *tail)
+
+    def atomic():  # on [M,1] rays
+        o, d, a = _ray_constants(origins, directions, pixel_area)
+        return encode_bwd(spec, static_scale, o[ri], d[ri], a[ri], _flat(t_starts, "t_starts", n).reshape(n, 1),
                           _flat(t_ends, "t_ends", n).reshape(n, 1), grad_out, out_dtype)
-    o, d, a = _chk(origins, "origins"), _chk(directions, "directions"), _chk(pixel_area.reshape(-1), "pixel_area")
-    if o.dim() != 2 or o.shape[1] != 3 or d.shape != o.shape or a.shape != (o.shape[0],):
-        raise ValueError("encode_bwd_packed: origins / directions [R,3] and pixel_area [R]")
-    s, e = _flat(t_starts, "t_starts", n), _flat(t_ends, "t_ends", n)
-    r = _lib.PackedRays()
-    r.n_rays, r.n_samples = o.shape[0], n
-    r.origins, r.directions, r.pixel_area = o.data_ptr(), d.data_ptr(), a.data_ptr()
-    r.t_starts, r.t_ends = s.data_ptr(), e.data_ptr()
-    if half:  # the fp16 gradient of an fp16-storage table, written by the partition itself
-        launch("nrhip_encode_bwd_binned_packed_f16", g, float(static_scale), r, ri, grad_out, gt, ws, ws.numel())
-    else:  # overwrite = 1: the partition writes every element of the gradient, no zero-fill
-        launch("nrhip_encode_bwd_binned_packed", g, float(static_scale), r, ri, grad_out, gt, 1, ws, ws.numel())
-    return gt
+
+    return _table_grad(spec, n, grad_out.device, out_dtype, binned, atomic)
 
 
 def encode_bwd_rays_packed(spec: GridSpec, table: Tensor, static_scale: float, origins, directions, pixel_area, t_starts,

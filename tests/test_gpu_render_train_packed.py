@@ -383,3 +383,44 @@ def test_node_forward_and_backward_replay_in_a_graph(ops):
         assert len(captured) == len(eager)
         for a, b in zip(eager, captured):
             assert torch.equal(a, b.detach())
+
+
+# ---- 7. the table gradient's two ray-sample sources ------------------------------------------------------------------------
+def source_batch():
+    """48 rays of 0 .. 40 samples, the first, the last and two more empty; with the contraction at 20 m the samples (out to
+    60 m from origins ~N(0, 5 m)) lie on both sides of it"""
+    counts = np.random.default_rng(41).integers(1, 41, 48)
+    counts[[0, 9, 30, 47]] = 0
+    counts[[3, 21]] = 40, 1
+    return T.packed_rays(tuple(int(c) for c in counts), 37)
+
+
+@pytest.mark.parametrize("F", [2, 4])
+@pytest.mark.parametrize("out_dtype", [torch.float32, torch.float16], ids=["fp32", "fp16"])
+def test_packed_source_equals_the_dense_source_on_one_sample_rays(ops, monkeypatch, F, out_dtype):
+    """ops.encode_bwd_packed against ops.encode_bwd on the same samples as [M,1] rays (ray constants gathered by
+    ray_indices).  Both run the partition over the same sample order with the ray-major walk (S = 1 < 16 on the dense side,
+    the packed source never transposes), the same positions and the same gradient rows: the same bits."""
+    L, lg, scale = 2, 8, 20.0
+    rays = source_batch()
+    o, d, a, ts, te, seg, ri = T.on_device(rays)
+    counts = np.diff(rays[5])
+    M = int(counts.sum())
+    assert len(counts) == 48 and counts.max() == 40 and counts[0] == 0 and counts[-1] == 0 and (counts == 0).sum() >= 3
+    mid = rays[0][host(ri)] + rays[1][host(ri)] * ((rays[3] + rays[4]) / 2)[:, None]
+    mag = np.abs(mid / scale).max(-1)
+    assert (mag < 1).sum() > 100 and (mag >= 1).sum() > 100
+    spec = ops.GridSpec(L, F, lg, 16, 1024)
+    g = synth.normal((M, L * F), 61)
+    g[::9] = 0.0  # silent samples: dropped by `prep` on both sides
+    g = dev(g)
+    monkeypatch.setattr(ops, "_BINNED_MIN_SAMPLES", 1)
+    assert ops._table_grad_workspace(spec.c_grid(out_dtype), M, g.device) is not None  # the partition, not the atomics
+    packed = ops.encode_bwd_packed(spec, scale, o, d, a, ts, te, ri, g, out_dtype=out_dtype)
+    dense = ops.encode_bwd(spec, scale, o[ri], d[ri], a[ri], ts[:, None], te[:, None], g, out_dtype=out_dtype)
+    assert packed.dtype == dense.dtype == out_dtype and packed.shape == (L << lg, F)
+    diff = (packed.double() - dense.double()).abs()
+    print(f"F={F} {out_dtype}: M={M}, non-zero entries {int((dense != 0).sum())}, max |packed - dense| {float(diff.max()):.3e}, "
+          f"bitwise {torch.equal(packed, dense)}")
+    assert float(dense.float().abs().max()) > 0
+    assert torch.equal(packed, dense)

@@ -127,3 +127,73 @@ def test_shim_packed_signatures_fail_with_the_right_exception():
         render_packed(v, None, ri, 3)
     with pytest.raises(ValueError):
         render_packed(v, None, ri, 3, density=w, alpha=w)
+
+
+# ---- the nrhip_packed_rays descriptor: the same bad descriptor to every entry point that takes one -------------------
+F32 = ctypes.c_float
+INVALID_ARG, UNSUPPORTED = 1, 2  # NRHIP_ERR_INVALID_ARG, NRHIP_ERR_UNSUPPORTED
+RAY_POINTERS = ("origins", "directions", "pixel_area", "t_starts", "t_ends", "segments")
+
+
+def _field():
+    """an nrhip_field the validation accepts; every pointer is the same non-null address"""
+    from neurad_studio_amd import _lib
+
+    f = _lib.Field()
+    g = f.grid
+    g.num_levels, g.n_features, g.log2_table_size, g.param_dtype = 8, 4, 11, 0
+    for l in range(8):
+        g.scalings[l] = 16.0 * 2 ** l
+    f.table, f.static_scale, f.use_sdf, f.beta = 0x1000, 100.0, 1, 3.0
+    f.geo.in_dim, f.geo.hidden_dim, f.geo.out_dim, f.geo.num_layers = 32, 32, 33, 2
+    f.feat.in_dim, f.feat.hidden_dim, f.feat.out_dim, f.feat.num_layers = 48, 32, 32, 3
+    for k in range(3):
+        f.geo.weight[k] = f.geo.bias[k] = f.feat.weight[k] = f.feat.bias[k] = 0x1000
+    return f
+
+
+def _packed_rays(r, m, null=None):
+    from neurad_studio_amd import _lib
+
+    p = _lib.PackedRays()
+    p.n_rays, p.n_samples = r, m
+    for name in RAY_POINTERS:
+        setattr(p, name, None if name == null else 0x1000)
+    return p
+
+
+def _descriptor_calls(lib, workspace_bytes=1 << 20):
+    """name in the messages -> call(rays): the five entry points that take an nrhip_packed_rays, every other argument valid"""
+    f, o = _field(), ONE
+    return {
+        "render_fwd_packed": lambda rays: lib.nrhip_render_fwd_packed(f, rays, o, o, o, o, F32(0.0), None),
+        "field_fwd_train_packed": lambda rays: lib.nrhip_field_fwd_train_packed(f, rays, *(o,) * 7, None),
+        "encode_bwd_rays_packed": lambda rays: lib.nrhip_encode_bwd_rays_packed(f.grid, o, F32(100.0), rays, o, I32(0), o, o, None),
+        "encode_bwd_binned_packed": lambda rays: lib.nrhip_encode_bwd_binned_packed(
+            f.grid, F32(100.0), rays, o, o, o, I32(1), o, I64(workspace_bytes), None),
+        "encode_bwd_binned_packed_f16": lambda rays: lib.nrhip_encode_bwd_binned_packed_f16(
+            f.grid, F32(100.0), rays, o, o, o, o, I64(workspace_bytes), None),
+    }
+
+
+def test_every_descriptor_entry_point_refuses_the_same_bad_descriptor(lib):
+    """NULL descriptor, negative R, negative M, M = 2^31: the code, and the entry point's own name in the message."""
+    err = lib.nrhip_last_error
+    for who, call in _descriptor_calls(lib).items():
+        for rays, code, fragment in ((None, INVALID_ARG, b"NULL"), (_packed_rays(-1, 8), INVALID_ARG, b"negative"),
+                                     (_packed_rays(4, -8), INVALID_ARG, b"negative"),
+                                     (_packed_rays(4, 1 << 31), UNSUPPORTED, b"2^31")):
+            assert call(rays) == code, (who, fragment)
+            assert err().startswith(who.encode() + b":") and fragment in err(), (who, err())
+
+
+def test_every_descriptor_entry_point_names_itself_for_a_null_ray_pointer(lib):
+    """One NULL pointer of the descriptor at a time, at R = 4, M = 8.  The binned pair finds a sample's ray through ray_of and
+    never reads the segments: with NULL segments it goes on to its next check, which a 16-byte workspace fails (so that
+    nothing is launched on the placeholder addresses)."""
+    err = lib.nrhip_last_error
+    for null in RAY_POINTERS:
+        for who, call in _descriptor_calls(lib, workspace_bytes=16).items():
+            assert call(_packed_rays(4, 8, null=null)) == INVALID_ARG, (who, null)
+            want = b"workspace" if (null == "segments" and "binned" in who) else b"NULL pointer"
+            assert err().startswith(who.encode() + b":") and want in err(), (who, null, err())
