@@ -333,6 +333,24 @@ int nrhip_camera_rays(const nrhip_camera_table* cams, const int64_t* camera_indi
                       int64_t n_rays, float* origins, float* directions, float* pixel_area, float* directions_norm,
                       float* times, void* stream);
 
+/* The lens of the cameras of one call (ABI 517).  All cameras share the type; a Cameras object of mixed types is the
+ * caller's to refuse (the reference's own loop, cameras.py:792-800, fills the rays of one type only). */
+typedef struct {
+  int32_t camera_type;      /* CameraType value (cameras.py:43-55): 1 PERSPECTIVE, 2 FISHEYE; others NRHIP_ERR_UNSUPPORTED */
+  const float* distortion;  /* [C,6] k1 k2 k3 k4 p1 p2 (Cameras.distortion_params), or NULL: no undistortion */
+} nrhip_camera_lens;
+/* nrhip_camera_rays for PERSPECTIVE or FISHEYE cameras with OpenCV lens distortion: each of the pixel and its +1 x / +1 y
+ * neighbours is undistorted by the reference's Newton solve (camera_utils.py:655-758: ten iterations from the distorted
+ * point, step 0 where |denominator| <= 1e-3; an all-zero row comes back bit for bit), then turned into a direction --
+ * (u, -v, -1), or for FISHEYE (u sin t / t, -v sin t / t, -cos t) with t = |(u, v)| clipped to [0, pi]
+ * (cameras.py:800-815).  Everything after that is nrhip_camera_rays: PERSPECTIVE with distortion NULL gives its bits.
+ * Mirrored from the reference: a FISHEYE ray exactly at the principal point (t = 0) is NaN in directions, directions_norm
+ * and pixel_area, and the rays one pixel to its left / above it are NaN in pixel_area. */
+int nrhip_camera_rays_lens(const nrhip_camera_table* cams, const nrhip_camera_lens* lens,
+                           const int64_t* camera_indices /*[R]*/, const float* coords /*[R,2]*/, int64_t n_rays,
+                           float* origins, float* directions, float* pixel_area, float* directions_norm, float* times,
+                           void* stream);
+
 typedef struct {
   const float* lidar_to_worlds;             /* [Ln,3,4] */
   const float* times;                       /* [Ln] or NULL */

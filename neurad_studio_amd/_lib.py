@@ -110,6 +110,10 @@ class CameraTable(C.Structure):
                 ("shutter_extent", C.c_void_p)]
 
 
+class CameraLens(C.Structure):  # nrhip_camera_lens
+    _fields_ = [("camera_type", C.c_int32), ("distortion", C.c_void_p)]
+
+
 class LidarTable(C.Structure):
     _fields_ = [("lidar_to_worlds", C.c_void_p), ("times", C.c_void_p), ("velocities", C.c_void_p),
                 ("horizontal_beam_divergence", C.c_void_p), ("vertical_beam_divergence", C.c_void_p),
@@ -200,6 +204,7 @@ PROTOTYPES = {
     "nrhip_ray_order_workspace": [I64, I32, C.POINTER(I64)],
     "nrhip_ray_order_large": [P, P, I64, F32, F32, I32, P, I64, P, P],
     "nrhip_camera_rays": [C.POINTER(CameraTable), P, P, I64, P, P, P, P, P, P],
+    "nrhip_camera_rays_lens": [C.POINTER(CameraTable), C.POINTER(CameraLens), P, P, I64, P, P, P, P, P, P],
     "nrhip_lidar_rays": [C.POINTER(LidarTable), P, P, I32, I64, P, P, P, P, P, P, P],
     "nrhip_patch_sample": [P, P, I64, I32, I32, I32, I32, I32, I32, P, P, I32, P, P, P, P],
     "nrhip_lidar_point_sample": [P, P, P, P, P, I32, I32, I32, I64, P, P, P],

@@ -2,6 +2,14 @@
 ``Lidars.generate_rays(lidar_indices, points)`` of the reference (nerfstudio/cameras/cameras.py:560-968,
 cameras/lidars.py:399-460), one HIP kernel each (csrc/raygen.hip).
 
+``camera_rays`` covers PERSPECTIVE and FISHEYE cameras (one type per ``Cameras`` object), with the reference's Newton
+undistortion of ``distortion_params`` (camera_utils.py:655-758) inside the kernel: FISHEYE with or without coefficients
+(the ZOD dataparser's cameras), PERSPECTIVE with non-zero coefficients only on request (``undistort_perspective=True``).
+Mixed types and every other camera type (FISHEYE624, equirectangular, VR180 / ODS, orthophoto) raise
+NotImplementedError; ``distortion_params_delta`` and ``camera_opt_to_camera`` are not taken.  Mirrored from the
+reference: a FISHEYE ray exactly at the principal point is NaN (theta = 0 in u sin(theta) / theta), and the pixel area of
+the rays one pixel to its left / above it is NaN.
+
 ``cameras`` / ``lidars`` are the reference's own objects (or anything with the same tensor attributes: camera_to_worlds,
 fx, fy, cx, cy, width, height, times, metadata, camera_type, distortion_params | lidar_to_worlds, times, metadata,
 horizontal_beam_divergence, vertical_beam_divergence, assume_ego_compensated, valid_lidar_distance_threshold).  The
@@ -18,39 +26,49 @@ from .. import _lib
 from ..ops import _chk, launch
 from .rays import RayBundle
 
-PERSPECTIVE = 1  # CameraType.PERSPECTIVE.value (cameras/cameras.py:43-55)
+PERSPECTIVE, FISHEYE = 1, 2  # CameraType values (cameras/cameras.py:43-55)
 
 
 def _f32(t: Tensor) -> Tensor:
     return _chk(t.reshape(t.shape[0], -1).to(torch.float32), "sensor table")
 
 
-_ELIGIBLE: dict = {}  # id(cameras) -> (key, error message | None)
+_ELIGIBLE: dict = {}  # id(cameras) -> (key, camera type, distorted, error message | None)
 
 
-def _check_cameras(cameras) -> None:
-    """PERSPECTIVE, undistorted cameras only.  The two `.any()` checks read the device, i.e. they synchronise the host with
-    the stream: they run ONCE per Cameras object (keyed on the identity and in-place version of its two tensors), not once
-    per training step."""
+def _check_cameras(cameras, undistort_perspective: bool):
+    """-> (camera type, distorted) of a Cameras object the kernels cover: one type, PERSPECTIVE or FISHEYE.  The unique()
+    and any() read the device, i.e. they synchronise the host with the stream: they run ONCE per Cameras object (keyed on the
+    identity and in-place version of its two tensors), not once per training step."""
     ct, dp = cameras.camera_type, getattr(cameras, "distortion_params", None)
     key = tuple((t.data_ptr(), t._version, tuple(t.shape)) if isinstance(t, Tensor) else None for t in (ct, dp))
     hit = _ELIGIBLE.get(id(cameras))
     if hit is None or hit[0] != key:
+        types = [PERSPECTIVE] if ct is None else torch.unique(ct).tolist()
         err = None
-        if ct is not None and bool((ct != PERSPECTIVE).any()):
-            err = "device ray generation covers PERSPECTIVE cameras; use Cameras.generate_rays otherwise"
-        elif dp is not None and bool((dp != 0).any()):
-            err = "device ray generation covers undistorted cameras; use Cameras.generate_rays otherwise"
+        if len(types) != 1:  # the reference's own loop (cameras.py:792-800) only fills the first matching type's rays
+            err = f"device ray generation needs cameras of one type, got types {types}"
+        elif types[0] not in (PERSPECTIVE, FISHEYE):
+            err = (f"device ray generation covers PERSPECTIVE and FISHEYE cameras, not type {types[0]}; use "
+                   "Cameras.generate_rays otherwise")
+        distorted = dp is not None and bool((dp != 0).any())
         if len(_ELIGIBLE) >= 64:
             _ELIGIBLE.clear()
-        hit = _ELIGIBLE[id(cameras)] = (key, err)
-    if hit[1] is not None:
-        raise NotImplementedError(hit[1])
+        hit = _ELIGIBLE[id(cameras)] = (key, types[0], distorted, err)
+    _, camera_type, distorted, err = hit
+    if err is None and camera_type == PERSPECTIVE and distorted and not undistort_perspective:
+        err = ("device ray generation covers undistorted PERSPECTIVE cameras unless undistort_perspective=True; use "
+               "Cameras.generate_rays otherwise")
+    if err is not None:
+        raise NotImplementedError(err)
+    return camera_type, distorted
 
 
-def camera_rays(cameras, camera_indices: Tensor, coords: Tensor, bundle_cls=RayBundle):
-    """camera_indices [R,1] (or [R]) long, coords [R,2] = (y, x) pixel-centre coordinates."""
-    _check_cameras(cameras)
+def camera_rays(cameras, camera_indices: Tensor, coords: Tensor, bundle_cls=RayBundle, *, undistort_perspective: bool = False):
+    """camera_indices [R,1] (or [R]) long, coords [R,2] = (y, x) pixel-centre coordinates.  FISHEYE cameras, with or without
+    ``distortion_params``, are covered as they are; PERSPECTIVE cameras with non-zero ``distortion_params`` only with
+    ``undistort_perspective=True``."""
+    camera_type, distorted = _check_cameras(cameras, undistort_perspective)
     idx = _chk(camera_indices.reshape(-1).long(), "camera_indices", torch.int64)
     xy = _chk(coords.reshape(-1, 2).to(torch.float32), "coords")
     R, dev = idx.shape[0], idx.device
@@ -72,7 +90,17 @@ def camera_rays(cameras, camera_indices: Tensor, coords: Tensor, bundle_cls=RayB
     area = torch.empty((R, 1), device=dev)
     norm = torch.empty((R, 1), device=dev)
     times = None if times_tab is None else torch.empty((R, 1), device=dev)
-    launch("nrhip_camera_rays", t, idx, xy, R, o, d, area, norm, times)
+    if camera_type == PERSPECTIVE and not distorted:
+        launch("nrhip_camera_rays", t, idx, xy, R, o, d, area, norm, times)
+    else:
+        lens = _lib.CameraLens()
+        lens.camera_type = camera_type
+        if distorted:  # all-zero coefficients pass through the solve bit for bit: NULL skips it
+            table = _f32(cameras.distortion_params)
+            if table.shape != (keep[0].shape[0], 6):
+                raise ValueError(f"distortion_params: expected [{keep[0].shape[0]}, 6], got {tuple(table.shape)}")
+            lens.distortion = table.data_ptr()
+        launch("nrhip_camera_rays_lens", t, lens, idx, xy, R, o, d, area, norm, times)
     skip = ("rolling_shutter_time", "time_to_center_pixel", "rs_direction") if rs else ()
     metadata = {k: v[idx] for k, v in md.items() if isinstance(v, Tensor) and k not in skip}
     metadata["directions_norm"] = norm

@@ -108,7 +108,8 @@ extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
 // 515: training on packed samples: nrhip_field_fwd_train_packed, nrhip_sdf_render_packed_fwd / _bwd / _bwd_workspace,
 //      nrhip_encode_bwd_binned_packed / _f16
 // 516: nrhip_encode_bwd_rays_packed: ray gradients through packed samples
-extern "C" int nrhip_version(void) { return 516; }
+// 517: nrhip_camera_rays_lens (+ nrhip_camera_lens): FISHEYE and lens-distorted cameras
+extern "C" int nrhip_version(void) { return 517; }
 
 extern "C" int nrhip_tuning_reload(void) {
   nrhip::g_tuning = nrhip::read_tuning();

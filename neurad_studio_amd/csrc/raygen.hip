@@ -1,14 +1,23 @@
 // ray generation on the device -- the step immediately before the hot path.
 //
-//   nrhip_camera_rays  == Cameras._generate_rays_from_coords for PERSPECTIVE cameras without lens distortion, incl. the
-//                         rolling-shutter correction of origins and times (nerfstudio/cameras/cameras.py:560-968);
-//   nrhip_lidar_rays   == Lidars._generate_rays_from_points (nerfstudio/cameras/lidars.py:399-460).
+//   nrhip_camera_rays      == Cameras._generate_rays_from_coords for PERSPECTIVE cameras without lens distortion, incl. the
+//                             rolling-shutter correction of origins and times (nerfstudio/cameras/cameras.py:560-968);
+//   nrhip_camera_rays_lens == the same for PERSPECTIVE or FISHEYE cameras with OpenCV lens distortion k1 k2 k3 k4 p1 p2
+//                             (camera_utils.py:655-758).  All cameras of a call share the type and the kernel is compiled
+//                             per type, so a wave never diverges on it;
+//   nrhip_lidar_rays       == Lidars._generate_rays_from_points (nerfstudio/cameras/lidars.py:399-460).
 //
 // The reference runs ~40 torch ops per batch for each (index_select of the per-sensor tables, stacks, masked selects,
-// norms).  Here one thread produces one ray: the sensor row is a handful of broadcast loads (rays of a 32x32 patch share
-// one camera; lidar points of a scan share one lidar), outputs go out as whole [R,3] / [R,1] rows.  Arithmetic mirrors
-// torch op for op (separately rounded mul/add/div: -ffp-contract=off) so that directions agree to the ulp -- a ray's
-// direction feeds floor() in every hash-grid level downstream.
+// norms) and, with distortion, ten Newton iterations of ~60 ops each over a [3,R,2] stack.  Here one thread produces one
+// ray: the sensor row is a handful of broadcast loads (rays of a 32x32 patch share one camera; lidar points of a scan
+// share one lidar), the Newton solve of the pixel and its two neighbours stays in registers, outputs go out as whole
+// [R,3] / [R,1] rows.  Arithmetic mirrors torch op for op (separately rounded mul/add/div: -ffp-contract=off) so that
+// directions agree to the ulp -- a ray's direction feeds floor() in every hash-grid level downstream.
+//
+// Mirrored, not repaired: a FISHEYE ray exactly at the principal point has theta = 0, where the reference's
+// (u * sin theta) / theta is 0 * 0 / 0 = NaN (cameras.py:809-814).  Its direction and directions_norm are NaN, and so is
+// the pixel area of that ray and of the rays one pixel to its left and one pixel above it, whose neighbour it is.  The
+// lens kernel evaluates the same expressions and returns the same NaNs.
 #include "common.h"
 
 namespace nrhip {
@@ -29,9 +38,12 @@ __device__ __forceinline__ Vec3 rotate(const float* __restrict__ m /*3x4 row maj
   return o;
 }
 
+// kNanNorm: a NaN norm stays NaN, as in torch.maximum (camera_utils.py:607); fmaxf returns the epsilon for it
+template <bool kNanNorm = false>
 __device__ __forceinline__ float norm3(Vec3 v) {
 #pragma clang fp contract(off)
-  return fmaxf(sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z), kNormEps);
+  const float n = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
+  return kNanNorm ? (n < kNormEps ? kNormEps : n) : fmaxf(n, kNormEps);
 }
 
 struct CameraTable {
@@ -49,23 +61,17 @@ struct CameraTable {
   int rs_mode;                  // 0 none, 1 vertical (rows), 2 horizontal (cols), 3 horizontal reversed
 };
 
-__global__ __launch_bounds__(256) void camera_rays_kernel(CameraTable t, const int64_t* __restrict__ cam_idx,
-                                                          const float* __restrict__ coords, int64_t n,
-                                                          float* __restrict__ origins, float* __restrict__ directions,
-                                                          float* __restrict__ pixel_area, float* __restrict__ dir_norm,
-                                                          float* __restrict__ times) {
+// From the camera-frame directions of a pixel (d0) and of its +1 x / +1 y neighbours (d1, d2) to the ray: rotation into
+// the world, normalisation, pixel area, rolling-shutter origin and time (cameras.py:900-960).
+template <bool kNanNorm>
+__device__ __forceinline__ void finish_camera_ray(const CameraTable& t, int64_t c, int64_t i, float x, float y, Vec3 d0,
+                                                  Vec3 d1, Vec3 d2, float* __restrict__ origins,
+                                                  float* __restrict__ directions, float* __restrict__ pixel_area,
+                                                  float* __restrict__ dir_norm, float* __restrict__ times) {
 #pragma clang fp contract(off)
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int64_t c = cam_idx[i];
-  const float y = coords[2 * i], x = coords[2 * i + 1];
-  const float fx = t.fx[c], fy = t.fy[c], cx = t.cx[c], cy = t.cy[c];
-  // image-plane coordinates and the two neighbours one pixel away (cameras.py:631-633), OpenCV -> OpenGL (:668)
-  const float u0 = (x - cx) / fx, u1 = ((x - cx) + 1.f) / fx;
-  const float v0 = -((y - cy) / fy), v1 = -(((y - cy) + 1.f) / fy);
   const float* m = t.c2w + 12 * c;
-  Vec3 d0 = rotate(m, u0, v0, -1.f), d1 = rotate(m, u1, v0, -1.f), d2 = rotate(m, u0, v1, -1.f);
-  const float n0 = norm3(d0), n1 = norm3(d1), n2 = norm3(d2);
+  d0 = rotate(m, d0.x, d0.y, d0.z), d1 = rotate(m, d1.x, d1.y, d1.z), d2 = rotate(m, d2.x, d2.y, d2.z);
+  const float n0 = norm3<kNanNorm>(d0), n1 = norm3<kNanNorm>(d1), n2 = norm3<kNanNorm>(d2);
   d0.x /= n0, d0.y /= n0, d0.z /= n0;
   d1.x /= n1, d1.y /= n1, d1.z /= n1;
   d2.x /= n2, d2.y /= n2, d2.z /= n2;
@@ -86,6 +92,95 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(CameraTable t, const i
   pixel_area[i] = dx * dy;
   dir_norm[i] = n0;
   if (times) times[i] = tm;
+}
+
+__global__ __launch_bounds__(256) void camera_rays_kernel(CameraTable t, const int64_t* __restrict__ cam_idx,
+                                                          const float* __restrict__ coords, int64_t n,
+                                                          float* __restrict__ origins, float* __restrict__ directions,
+                                                          float* __restrict__ pixel_area, float* __restrict__ dir_norm,
+                                                          float* __restrict__ times) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t c = cam_idx[i];
+  const float y = coords[2 * i], x = coords[2 * i + 1];
+  const float fx = t.fx[c], fy = t.fy[c], cx = t.cx[c], cy = t.cy[c];
+  // image-plane coordinates and the two neighbours one pixel away (cameras.py:631-633), OpenCV -> OpenGL (:668)
+  const float u0 = (x - cx) / fx, u1 = ((x - cx) + 1.f) / fx;
+  const float v0 = -((y - cy) / fy), v1 = -(((y - cy) + 1.f) / fy);
+  finish_camera_ray<false>(t, c, i, x, y, {u0, v0, -1.f}, {u1, v0, -1.f}, {u0, v1, -1.f}, origins, directions, pixel_area,
+                           dir_norm, times);
+}
+
+// ---- lens distortion and the fisheye model ----------------------------------------------------------------------------
+constexpr int kPerspective = 1, kFisheye = 2;  // CameraType values (cameras.py:43-55)
+
+// radial_and_tangential_undistort (camera_utils.py:721-758) of one point: Newton's method from the distorted point, exactly
+// ten iterations, residual and Jacobian with the expression trees of _compute_residual_and_jacobian (:655-717) -- Python's
+// precedence spelled out, every product and sum rounded on its own.  With all six coefficients zero the residual is 0 and
+// the step -0: the point comes back bit for bit.
+__device__ __forceinline__ void undistort(const float* __restrict__ k, float& px, float& py) {
+#pragma clang fp contract(off)
+  const float k1 = k[0], k2 = k[1], k3 = k[2], k4 = k[3], p1 = k[4], p2 = k[5];
+  const float xd = px, yd = py;
+  float x = xd, y = yd;
+  for (int it = 0; it < 10; ++it) {
+    const float r = x * x + y * y;
+    const float d = 1.f + r * (k1 + r * (k2 + r * (k3 + r * k4)));
+    const float fx = ((d * x + ((2.f * p1) * x) * y) + p2 * (r + (2.f * x) * x)) - xd;
+    const float fy = ((d * y + ((2.f * p2) * x) * y) + p1 * (r + (2.f * y) * y)) - yd;
+    const float d_r = k1 + r * (2.f * k2 + r * (3.f * k3 + (r * 4.f) * k4));
+    const float d_x = (2.f * x) * d_r, d_y = (2.f * y) * d_r;
+    const float fx_x = ((d + d_x * x) + (2.f * p1) * y) + (6.f * p2) * x;
+    const float fx_y = (d_y * x + (2.f * p1) * x) + (2.f * p2) * y;
+    const float fy_x = (d_x * y + (2.f * p2) * y) + (2.f * p1) * x;
+    const float fy_y = ((d + d_y * y) + (2.f * p2) * x) + (6.f * p1) * y;
+    const float den = fy_x * fx_y - fx_x * fy_y;
+    const float x_num = fx * fy_y - fy * fx_y, y_num = fy * fx_x - fx * fy_x;
+    const bool ok = fabsf(den) > 1e-3f;
+    x = x + (ok ? x_num / den : 0.f);
+    y = y + (ok ? y_num / den : 0.f);
+  }
+  px = x, py = y;
+}
+
+// image-plane point (OpenCV, undistorted) -> direction in the camera frame (OpenGL: v negated, cameras.py:667)
+template <int kType>
+__device__ __forceinline__ Vec3 camera_direction(float u, float v) {
+#pragma clang fp contract(off)
+  v = -v;
+  if (kType == kPerspective) return {u, v, -1.f};
+  // FISHEYE (cameras.py:800-815).  sinf / cosf, not the fast intrinsics: the direction feeds floor() downstream
+  float theta = sqrtf(u * u + v * v);
+  theta = theta < 0.f ? 0.f : (theta > 3.14159274101257324f ? 3.14159274101257324f : theta);  // torch.clip keeps a NaN
+  const float s = sinf(theta);
+  return {(u * s) / theta, (v * s) / theta, -cosf(theta)};
+}
+
+template <int kType>
+__global__ __launch_bounds__(256) void camera_rays_lens_kernel(CameraTable t, const float* __restrict__ distortion,
+                                                               const int64_t* __restrict__ cam_idx,
+                                                               const float* __restrict__ coords, int64_t n,
+                                                               float* __restrict__ origins, float* __restrict__ directions,
+                                                               float* __restrict__ pixel_area, float* __restrict__ dir_norm,
+                                                               float* __restrict__ times) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t c = cam_idx[i];
+  const float y = coords[2 * i], x = coords[2 * i + 1];
+  const float fx = t.fx[c], fy = t.fy[c], cx = t.cx[c], cy = t.cy[c];
+  // the pixel, its +1 x and its +1 y neighbour on the image plane (cameras.py:631-635)
+  float u[3] = {(x - cx) / fx, ((x - cx) + 1.f) / fx, (x - cx) / fx};
+  float v[3] = {(y - cy) / fy, (y - cy) / fy, ((y - cy) + 1.f) / fy};
+  if (distortion) {
+    const float* k = distortion + 6 * c;
+    // an all-zero row passes through the solve unchanged: skipped (rays of a patch share the camera, the branch is uniform)
+    if (k[0] != 0.f || k[1] != 0.f || k[2] != 0.f || k[3] != 0.f || k[4] != 0.f || k[5] != 0.f)
+      for (int j = 0; j < 3; ++j) undistort(k, u[j], v[j]);
+  }
+  finish_camera_ray<true>(t, c, i, x, y, camera_direction<kType>(u[0], v[0]), camera_direction<kType>(u[1], v[1]),
+                          camera_direction<kType>(u[2], v[2]), origins, directions, pixel_area, dir_norm, times);
 }
 
 struct LidarTable {
@@ -220,23 +315,55 @@ __global__ __launch_bounds__(256) void lidar_point_sample_kernel(const int64_t* 
 
 using namespace nrhip;
 
+// the checks both camera entry points make before a launch; 0 or the error code
+static int check_camera_args(const char* who, const nrhip_camera_table* cams, const int64_t* camera_indices,
+                             const float* coords, float* origins, float* directions, float* pixel_area,
+                             float* directions_norm, float* times) {
+  NR_REQUIRE(cams->camera_to_worlds && cams->fx && cams->fy && cams->cx && cams->cy && camera_indices && coords && origins &&
+                 directions && pixel_area && directions_norm,
+             NRHIP_ERR_INVALID_ARG, "%s: NULL pointer", who);
+  NR_REQUIRE(cams->rolling_shutter >= 0 && cams->rolling_shutter <= 3, NRHIP_ERR_INVALID_ARG, "%s: rolling_shutter mode", who);
+  NR_REQUIRE(cams->rolling_shutter == 0 || (cams->rolling_shutter_time && cams->time_to_center_pixel && cams->velocities &&
+                                            cams->shutter_extent && cams->times && times),
+             NRHIP_ERR_INVALID_ARG, "%s: rolling shutter needs duration, time_to_center_pixel, velocities, extent, times", who);
+  return NRHIP_OK;
+}
+
+static CameraTable camera_table(const nrhip_camera_table* cams) {
+  return {cams->camera_to_worlds, cams->fx, cams->fy, cams->cx, cams->cy, cams->times, cams->rolling_shutter_time,
+          cams->time_to_center_pixel, cams->velocities, cams->shutter_extent, cams->rolling_shutter};
+}
+
 extern "C" int nrhip_camera_rays(const nrhip_camera_table* cams, const int64_t* camera_indices, const float* coords,
                                  int64_t n_rays, float* origins, float* directions, float* pixel_area,
                                  float* directions_norm, float* times, void* stream) {
   NR_REQUIRE(cams && n_rays >= 0, NRHIP_ERR_INVALID_ARG, "camera_rays: bad argument");
   if (n_rays == 0) return NRHIP_OK;
-  NR_REQUIRE(cams->camera_to_worlds && cams->fx && cams->fy && cams->cx && cams->cy && camera_indices && coords && origins &&
-                 directions && pixel_area && directions_norm,
-             NRHIP_ERR_INVALID_ARG, "camera_rays: NULL pointer");
-  NR_REQUIRE(cams->rolling_shutter >= 0 && cams->rolling_shutter <= 3, NRHIP_ERR_INVALID_ARG, "camera_rays: rolling_shutter mode");
-  NR_REQUIRE(cams->rolling_shutter == 0 || (cams->rolling_shutter_time && cams->time_to_center_pixel && cams->velocities &&
-                                            cams->shutter_extent && cams->times && times),
-             NRHIP_ERR_INVALID_ARG, "camera_rays: rolling shutter needs duration, time_to_center_pixel, velocities, extent, times");
-  CameraTable t{cams->camera_to_worlds, cams->fx, cams->fy, cams->cx, cams->cy, cams->times, cams->rolling_shutter_time,
-                cams->time_to_center_pixel, cams->velocities, cams->shutter_extent, cams->rolling_shutter};
-  camera_rays_kernel<<<grid_for(n_rays, 256), 256, 0, (hipStream_t)stream>>>(t, camera_indices, coords, n_rays, origins,
-                                                                            directions, pixel_area, directions_norm, times);
+  if (int rc = check_camera_args("camera_rays", cams, camera_indices, coords, origins, directions, pixel_area,
+                                 directions_norm, times))
+    return rc;
+  camera_rays_kernel<<<grid_for(n_rays, 256), 256, 0, (hipStream_t)stream>>>(
+      camera_table(cams), camera_indices, coords, n_rays, origins, directions, pixel_area, directions_norm, times);
   return check_launch("camera_rays");
+}
+
+extern "C" int nrhip_camera_rays_lens(const nrhip_camera_table* cams, const nrhip_camera_lens* lens,
+                                      const int64_t* camera_indices, const float* coords, int64_t n_rays, float* origins,
+                                      float* directions, float* pixel_area, float* directions_norm, float* times,
+                                      void* stream) {
+  NR_REQUIRE(cams && lens, NRHIP_ERR_INVALID_ARG, "camera_rays_lens: NULL camera table or lens");
+  NR_REQUIRE(n_rays >= 0, NRHIP_ERR_INVALID_ARG, "camera_rays_lens: negative n_rays");
+  NR_REQUIRE(lens->camera_type == kPerspective || lens->camera_type == kFisheye, NRHIP_ERR_UNSUPPORTED,
+             "camera_rays_lens: camera type %d (1 PERSPECTIVE and 2 FISHEYE are covered)", (int)lens->camera_type);
+  if (n_rays == 0) return NRHIP_OK;
+  if (int rc = check_camera_args("camera_rays_lens", cams, camera_indices, coords, origins, directions, pixel_area,
+                                 directions_norm, times))
+    return rc;
+  const auto kernel = lens->camera_type == kFisheye ? camera_rays_lens_kernel<kFisheye> : camera_rays_lens_kernel<kPerspective>;
+  kernel<<<grid_for(n_rays, 256), 256, 0, (hipStream_t)stream>>>(camera_table(cams), lens->distortion, camera_indices, coords,
+                                                                 n_rays, origins, directions, pixel_area, directions_norm,
+                                                                 times);
+  return check_launch("camera_rays_lens");
 }
 
 extern "C" int nrhip_lidar_rays(const nrhip_lidar_table* lidars, const int64_t* lidar_indices, const float* points,
