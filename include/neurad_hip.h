@@ -680,6 +680,24 @@ int nrhip_occgrid_march_levels(const nrhip_occgrid_levels* grid, const float* or
                                float far_plane, float cone_angle, int32_t max_candidates, int32_t* counts,
                                const int64_t* offsets, int64_t* ray_indices, float* t_starts, float* t_ends,
                                void* stream);
+/* The box-aware march (ABI 518), for scenes with dynamic actors.  The grid is a time-independent world-space grid built
+ * from static densities: the cells inside an actor's box at a ray's time are empty to it, and the plain march drops exactly
+ * the intervals the actors live in.  Here the candidate intervals are those of nrhip_occgrid_march_levels (same clipping,
+ * stepping, cone_angle and t_rand), and one is kept iff its level's cell is set (that entry point's test, unchanged) OR its
+ * sample position -- the mean the field evaluates, t_start + (t_end - t_start) / 2 along the ray -- lies strictly inside
+ * the box of one of the ray's candidate actors: cand_count [R], cand_actor [R,K], cand_w2b [R,K,12] as nrhip_actor_prepare
+ * writes them at the ray's time (K = actors->max_candidates; one list per RAY -- prepare them from any two distinct points
+ * of the ray's line, nothing here is sized by the sample count).  Position and in-box test are the device functions the
+ * field kernels call, so march and field agree on every sample bit for bit.  Of `actors` only n_actors, bounds and
+ * max_candidates are read.  Same two passes and outputs; with every cand_count zero the outputs are those of
+ * nrhip_occgrid_march_levels bit for bit.                                                                             */
+int nrhip_occgrid_march_levels_actors(const nrhip_occgrid_levels* grid, const nrhip_actors* actors,
+                                      const int32_t* cand_count, const int32_t* cand_actor, const float* cand_w2b,
+                                      const float* origins, const float* directions, const float* t_min /*[R] or NULL*/,
+                                      const float* t_max /*[R] or NULL*/, const float* t_rand /*[R] or NULL*/, int64_t r,
+                                      float render_step_size, float near_plane, float far_plane, float cone_angle,
+                                      int32_t max_candidates, int32_t* counts, const int64_t* offsets,
+                                      int64_t* ray_indices, float* t_starts, float* t_ends, void* stream);
 /* ---- occupancy-grid maintenance (modelled on nerfacc 0.5 OccGridEstimator._update / mark_invisible_cells; the rule is
  *      stated in csrc/occgrid_update.h and restated in tests/occgrid_update_restatement.py -- parity with nerfacc itself is
  *      unpinned, like the march).  occs fp32 [levels*res^3]; occs < 0 marks an invisible cell.  No entry point allocates,
@@ -783,6 +801,20 @@ typedef struct {
 int nrhip_render_fwd_packed(const nrhip_field* f, const nrhip_packed_rays* rays, float* out_features /*[R,32]*/,
                             float* out_depth /*[R]*/, float* out_acc /*[R]*/, float* out_weights /*[M] or NULL*/,
                             float early_stop_eps, void* stream);
+
+/* nrhip_render_fwd_packed for a scene with dynamic actors (ABI 518): the packed counterpart of nrhip_render_fwd_actors.
+ * cand_*: one candidate list per RAY (nrhip_actor_prepare on two distinct points of the ray's line; row length
+ * a->max_candidates).  Three launches, no host round trip: the device-side split of the processing order into rays without
+ * / with candidates, nrhip_render_fwd_packed's kernel over the first slice, the actor-aware packed kernel (every
+ * `Composite, Actors, F32` row of csrc/render_variants.h, fp32 and fp16 tables) over the second.  Compositing, early_stop_eps,
+ * order, n_rays == 0 and n_samples == 0 as nrhip_render_fwd_packed; overlapping boxes: the highest actor index wins; the
+ * grid restrictions of nrhip_render_fwd_actors apply.  With every cand_count zero the outputs are those of
+ * nrhip_render_fwd_packed bit for bit.  workspace: device scratch of (n_rays + 4) int32.                                */
+int nrhip_render_fwd_packed_actors(const nrhip_field* f, const nrhip_actors* a, const nrhip_packed_rays* rays,
+                                   const int32_t* cand_count, const int32_t* cand_actor, const float* cand_w2b,
+                                   float* out_features /*[R,32]*/, float* out_depth /*[R]*/, float* out_acc /*[R]*/,
+                                   float* out_weights /*[M] or NULL*/, float early_stop_eps, int32_t* workspace,
+                                   void* stream);
 
 /* ---- training on packed samples: the packed counterparts of nrhip_field_fwd_train, nrhip_sdf_render_fwd / _bwd and
  *      nrhip_encode_bwd_binned.  No atomics, no allocation, no host synchronisation (graph-capturable).                  */

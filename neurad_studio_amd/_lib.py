@@ -193,6 +193,8 @@ PROTOTYPES = {
     "nrhip_render_fwd": [C.POINTER(Field), C.POINTER(Rays), P, P, P, P, P],
     "nrhip_render_fwd_ex": [C.POINTER(Field), C.POINTER(Rays), P, P, P, P, F32, P],
     "nrhip_render_fwd_packed": [C.POINTER(Field), C.POINTER(PackedRays), P, P, P, P, F32, P],
+    "nrhip_render_fwd_packed_actors": [C.POINTER(Field), C.POINTER(Actors), C.POINTER(PackedRays), P, P, P, P, P, P, P, F32,
+                                       P, P],
     "nrhip_field_fwd_train_packed": [C.POINTER(Field), C.POINTER(PackedRays), P, P, P, P, P, P, P, P],
     "nrhip_sdf_render_packed_fwd": [P, P, F32, P, P, P, P, I64, I32, P, P, P, P, P, P],
     "nrhip_sdf_render_packed_bwd_workspace": [I64, C.POINTER(I64)],
@@ -239,6 +241,8 @@ PROTOTYPES = {
     "nrhip_render_fwd_actors": [C.POINTER(Field), C.POINTER(Actors), C.POINTER(Rays), P, P, P, P, P, P, P, F32, P, P],
     "nrhip_occgrid_march": [C.POINTER(OccGrid), P, P, P, P, P, I64, F32, F32, F32, F32, I32, P, P, P, P, P, P],
     "nrhip_occgrid_march_levels": [C.POINTER(OccGridLevels), P, P, P, P, P, I64, F32, F32, F32, F32, I32, P, P, P, P, P, P],
+    "nrhip_occgrid_march_levels_actors": [C.POINTER(OccGridLevels), C.POINTER(Actors), P, P, P, P, P, P, P, P, I64, F32,
+                                          F32, F32, F32, I32, P, P, P, P, P, P],
     "nrhip_occgrid_update_workspace": [I32, I32, C.POINTER(I64)],
     "nrhip_occgrid_update_candidates": [C.POINTER(OccGridLevels), P, I32, I32, P, P, P, P, P, P, P, I64, P],
     "nrhip_occgrid_update_apply": [C.POINTER(OccGridLevels), P, I64, P, P, P, F32, F32, P, I64, P],

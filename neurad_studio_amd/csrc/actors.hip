@@ -154,10 +154,8 @@ __device__ __forceinline__ ActorHit find_hit(const ActorsDev& a, const RaysDev& 
   for (int c = 0; c < n; ++c) {  // ascending actor index; the LAST hit wins (neurad_encoding.py:184-185 on CPU)
     const float* w = cand_w2b + (ray * a.K + c) * 12;
     const int act = cand_actor[ray * a.K + c];
-    const float bx = w[0] * g.x + w[1] * g.y + w[2] * g.z + w[3];
-    const float by = w[4] * g.x + w[5] * g.y + w[6] * g.z + w[7];
-    const float bz = w[8] * g.x + w[9] * g.y + w[10] * g.z + w[11];
-    if (fabsf(bx) < a.bounds[3 * act] && fabsf(by) < a.bounds[3 * act + 1] && fabsf(bz) < a.bounds[3 * act + 2]) {
+    float bx, by, bz;
+    if (box_contains(w, a.bounds + 3 * act, g.x, g.y, g.z, bx, by, bz)) {
       h.actor = act, h.px = bx, h.py = by, h.pz = bz, wsel = w;
     }
   }

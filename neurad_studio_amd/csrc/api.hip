@@ -109,7 +109,8 @@ extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
 //      nrhip_encode_bwd_binned_packed / _f16
 // 516: nrhip_encode_bwd_rays_packed: ray gradients through packed samples
 // 517: nrhip_camera_rays_lens (+ nrhip_camera_lens): FISHEYE and lens-distorted cameras
-extern "C" int nrhip_version(void) { return 517; }
+// 518: nrhip_occgrid_march_levels_actors, nrhip_render_fwd_packed_actors: the occupancy route with dynamic actors (eval)
+extern "C" int nrhip_version(void) { return 518; }
 
 extern "C" int nrhip_tuning_reload(void) {
   nrhip::g_tuning = nrhip::read_tuning();

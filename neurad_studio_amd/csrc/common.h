@@ -331,6 +331,17 @@ __device__ __forceinline__ SamplePos sample_gaussian(float ox, float oy, float o
   return p;
 }
 
+// H5: is the world-space point (x, y, z) strictly inside a box?  w: the box's 3x4 world->box matrix (a row of cand_w2b),
+// b: its half sizes [3].  -> the box-frame position as well.  THE in-box test: find_hit (actors.hip) and the box-aware
+// occupancy march (occgrid.hip) both call it on sample_gaussian's mean, so field and march agree on every sample.
+__device__ __forceinline__ bool box_contains(const float* w, const float* b, float x, float y, float z, float& bx, float& by,
+                                             float& bz) {
+  bx = w[0] * x + w[1] * y + w[2] * z + w[3];
+  by = w[4] * x + w[5] * y + w[6] * z + w[7];
+  bz = w[8] * x + w[9] * y + w[10] * z + w[11];
+  return fabsf(bx) < b[0] && fabsf(by) < b[1] && fabsf(bz) < b[2];
+}
+
 // H3 alone: ScaledSceneContraction(order=inf) of a gaussian -> [0,1]^3 (spatial_distortions.py:103-141)
 __device__ __forceinline__ SamplePos contract_gaussian(float mx, float my, float mz, float std, float scale) {
 #pragma clang fp contract(off)

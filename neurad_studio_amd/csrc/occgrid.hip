@@ -10,6 +10,11 @@
 // outermost box; a candidate's level is the first l whose (closed) box contains its midpoint -- the outermost level when
 // rounding puts it outside all of them -- and it is kept iff binaries[l] is set at the cell the same floor-and-clamp rule
 // gives in that level; step sizes do not depend on the level.  One level: exactly the single-grid march.
+// Dynamic actors (nrhip_occgrid_march_levels_actors): the grid is a time-independent world-space grid built from static
+// densities, so the cells inside an actor's box at a ray's time are empty to it.  The box-aware march generates the same
+// candidates and keeps one iff its cell is set (the test above, unchanged) OR its sample position -- sample_gaussian's mean,
+// t0 + (t1 - t0) / 2, the position the field evaluates -- lies strictly inside the box of one of the ray's candidate
+// actors (box_contains, common.h: the function find_hit calls).  March and field agree on every sample bit for bit.
 // One wavefront marches one ray 64 candidates at a time: ballot(occupied) -> popcount prefix -> compacted store.
 #include "common.h"
 #include "occgrid_update.h"
@@ -72,18 +77,42 @@ __device__ __forceinline__ bool occupied(const OccDev& g, const float* o, const 
   return g.bin[(int64_t)lvl * g.res * g.res * g.res + idx] != 0;
 }
 
-// WRITE=false: counts[ray] ; WRITE=true: packed outputs at offsets[ray]
-template <bool WRITE>
-__global__ __launch_bounds__(256) void occgrid_march_kernel(OccDev g, const float* __restrict__ origins,
-                                                            const float* __restrict__ dirs,
-                                                            const float* __restrict__ t_min,
-                                                            const float* __restrict__ t_max,
-                                                            const float* __restrict__ t_rand, int64_t R, float step,
-                                                            float near_plane, float far_plane, float cone,
-                                                            int max_candidates, int32_t* __restrict__ counts,
-                                                            const int64_t* __restrict__ offsets,
-                                                            int64_t* __restrict__ ray_indices,
-                                                            float* __restrict__ t_starts, float* __restrict__ t_ends) {
+// The candidate boxes of the box-aware march (nrhip_occgrid_march_levels_actors): the per-ray lists of nrhip_actor_prepare
+// and the actors' half sizes.  All NULL / 0 in the plain march.
+struct MarchBoxes {
+  const int32_t* cand_count;  // [R]
+  const int32_t* cand_actor;  // [R, K]
+  const float* cand_w2b;      // [R, K, 12]
+  const float* bounds;        // [A, 3]
+  int K, A;
+};
+
+// Is the sample [ts, te] of the ray inside the box of one of its first n candidates?  The field's own position and test:
+// sample_gaussian's mean (the pixel area only enters the std, which nothing here reads) and box_contains, which find_hit
+// calls too.  n <= K and the actor index is clamped into [0, A): every read stays inside the lists.
+__device__ __forceinline__ bool in_candidate_box(const MarchBoxes& b, int64_t ray, int n, const float* o, const float* d,
+                                                 float ts, float te) {
+  const SamplePos g = sample_gaussian(o[0], o[1], o[2], d[0], d[1], d[2], 0.f, ts, te);
+  bool in = false;
+  for (int c = 0; c < n; ++c) {
+    const int64_t e = ray * b.K + c;
+    const int act = min(max(b.cand_actor[e], 0), b.A - 1);
+    float bx, by, bz;
+    in = box_contains(b.cand_w2b + e * 12, b.bounds + 3 * act, g.x, g.y, g.z, bx, by, bz) || in;
+  }
+  return in;
+}
+
+// One wavefront marches one ray.  WRITE=false: counts[ray] ; WRITE=true: packed outputs at offsets[ray].  BOXES: a candidate
+// interval whose cell is empty is still kept when its sample lies inside a candidate actor's box.
+template <bool WRITE, bool BOXES>
+__device__ __forceinline__ void march_ray(const OccDev& g, const MarchBoxes& mb, const float* __restrict__ origins,
+                                          const float* __restrict__ dirs, const float* __restrict__ t_min,
+                                          const float* __restrict__ t_max, const float* __restrict__ t_rand, int64_t R,
+                                          float step, float near_plane, float far_plane, float cone, int max_candidates,
+                                          int32_t* __restrict__ counts, const int64_t* __restrict__ offsets,
+                                          int64_t* __restrict__ ray_indices, float* __restrict__ t_starts,
+                                          float* __restrict__ t_ends) {
   const int lane = threadIdx.x & 63;
   const int64_t ray = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (ray >= R) return;
@@ -92,6 +121,8 @@ __global__ __launch_bounds__(256) void occgrid_march_kernel(OccDev g, const floa
   float near = fmaxf(near_plane, t_min ? t_min[ray] : near_plane);
   const float far = fminf(far_plane, t_max ? t_max[ray] : far_plane);
   if (t_rand) near += t_rand[ray] * step;  // stratified=True (nerfacc shifts the near plane by U(0,1)*step)
+  int nbox = 0;
+  if constexpr (BOXES) nbox = min(max(mb.cand_count[ray], 0), mb.K);
   March m;
   int total = 0;
   if (setup_march(g, o, d, near, far, step, cone, m)) {
@@ -100,7 +131,8 @@ __global__ __launch_bounds__(256) void occgrid_march_kernel(OccDev g, const floa
       const float ts = m.at(k);
       const float te = fminf(m.at(k + 1), m.t_far);
       const bool in_range = ts < m.t_far && te > ts;
-      const bool keep = in_range && occupied(g, o, d, 0.5f * (ts + te));
+      bool keep = in_range && occupied(g, o, d, 0.5f * (ts + te));
+      if constexpr (BOXES) keep = keep || (in_range && nbox > 0 && in_candidate_box(mb, ray, nbox, o, d, ts, te));
       const unsigned long long mk = __ballot(keep);
       if (WRITE && keep) {
         const int64_t pos = offsets[ray] + total + __popcll(mk & ((1ull << lane) - 1ull));
@@ -113,6 +145,36 @@ __global__ __launch_bounds__(256) void occgrid_march_kernel(OccDev g, const floa
     }
   }
   if (!WRITE && lane == 0) counts[ray] = total;
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void occgrid_march_kernel(OccDev g, const float* __restrict__ origins,
+                                                            const float* __restrict__ dirs,
+                                                            const float* __restrict__ t_min,
+                                                            const float* __restrict__ t_max,
+                                                            const float* __restrict__ t_rand, int64_t R, float step,
+                                                            float near_plane, float far_plane, float cone,
+                                                            int max_candidates, int32_t* __restrict__ counts,
+                                                            const int64_t* __restrict__ offsets,
+                                                            int64_t* __restrict__ ray_indices,
+                                                            float* __restrict__ t_starts, float* __restrict__ t_ends) {
+  march_ray<WRITE, false>(g, MarchBoxes{}, origins, dirs, t_min, t_max, t_rand, R, step, near_plane, far_plane, cone,
+                          max_candidates, counts, offsets, ray_indices, t_starts, t_ends);
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void occgrid_march_actors_kernel(OccDev g, MarchBoxes mb, const float* __restrict__ origins,
+                                                                   const float* __restrict__ dirs,
+                                                                   const float* __restrict__ t_min,
+                                                                   const float* __restrict__ t_max,
+                                                                   const float* __restrict__ t_rand, int64_t R, float step,
+                                                                   float near_plane, float far_plane, float cone,
+                                                                   int max_candidates, int32_t* __restrict__ counts,
+                                                                   const int64_t* __restrict__ offsets,
+                                                                   int64_t* __restrict__ ray_indices,
+                                                                   float* __restrict__ t_starts, float* __restrict__ t_ends) {
+  march_ray<WRITE, true>(g, mb, origins, dirs, t_min, t_max, t_rand, R, step, near_plane, far_plane, cone, max_candidates,
+                         counts, offsets, ray_indices, t_starts, t_ends);
 }
 
 static int to_dev(const nrhip_occgrid* g, OccDev& d) {
@@ -147,7 +209,7 @@ static int to_dev(const nrhip_occgrid_levels* g, OccDev& d) {
 static int march(const OccDev& d, const float* origins, const float* directions, const float* t_min, const float* t_max,
                  const float* t_rand, int64_t r, float render_step_size, float near_plane, float far_plane,
                  float cone_angle, int32_t max_candidates, int32_t* counts, const int64_t* offsets, int64_t* ray_indices,
-                 float* t_starts, float* t_ends, void* stream) {
+                 float* t_starts, float* t_ends, void* stream, const MarchBoxes* boxes = nullptr) {
   NR_REQUIRE(r >= 0 && render_step_size > 0.f && cone_angle >= 0.f && max_candidates >= 1, NRHIP_ERR_INVALID_ARG,
              "occgrid_march: bad argument");
   if (r == 0) return NRHIP_OK;
@@ -156,14 +218,26 @@ static int march(const OccDev& d, const float* origins, const float* directions,
   const hipStream_t st = (hipStream_t)stream;
   if (!offsets) {
     NR_REQUIRE(counts, NRHIP_ERR_INVALID_ARG, "occgrid_march: counting pass needs `counts`");
-    occgrid_march_kernel<false><<<blocks, 256, 0, st>>>(d, origins, directions, t_min, t_max, t_rand, r,
-                                                        render_step_size, near_plane, far_plane, cone_angle,
-                                                        max_candidates, counts, nullptr, nullptr, nullptr, nullptr);
+    if (boxes)
+      occgrid_march_actors_kernel<false><<<blocks, 256, 0, st>>>(d, *boxes, origins, directions, t_min, t_max, t_rand, r,
+                                                                 render_step_size, near_plane, far_plane, cone_angle,
+                                                                 max_candidates, counts, nullptr, nullptr, nullptr, nullptr);
+    else
+      occgrid_march_kernel<false><<<blocks, 256, 0, st>>>(d, origins, directions, t_min, t_max, t_rand, r,
+                                                          render_step_size, near_plane, far_plane, cone_angle,
+                                                          max_candidates, counts, nullptr, nullptr, nullptr, nullptr);
   } else {
     NR_REQUIRE(ray_indices && t_starts && t_ends, NRHIP_ERR_INVALID_ARG, "occgrid_march: write pass needs outputs");
-    occgrid_march_kernel<true><<<blocks, 256, 0, st>>>(d, origins, directions, t_min, t_max, t_rand, r,
-                                                       render_step_size, near_plane, far_plane, cone_angle,
-                                                       max_candidates, nullptr, offsets, ray_indices, t_starts, t_ends);
+    if (boxes)
+      occgrid_march_actors_kernel<true><<<blocks, 256, 0, st>>>(d, *boxes, origins, directions, t_min, t_max, t_rand, r,
+                                                                render_step_size, near_plane, far_plane, cone_angle,
+                                                                max_candidates, nullptr, offsets, ray_indices, t_starts,
+                                                                t_ends);
+    else
+      occgrid_march_kernel<true><<<blocks, 256, 0, st>>>(d, origins, directions, t_min, t_max, t_rand, r,
+                                                         render_step_size, near_plane, far_plane, cone_angle,
+                                                         max_candidates, nullptr, offsets, ray_indices, t_starts,
+                                                         t_ends);
   }
   return check_launch("occgrid_march");
 }
@@ -192,6 +266,29 @@ extern "C" int nrhip_occgrid_march_levels(const nrhip_occgrid_levels* grid, cons
   if (int e = to_dev(grid, d)) return e;
   return march(d, origins, directions, t_min, t_max, t_rand, r, render_step_size, near_plane, far_plane, cone_angle,
                max_candidates, counts, offsets, ray_indices, t_starts, t_ends, stream);
+}
+
+// The box-aware march: nrhip_occgrid_march_levels, and a candidate interval whose cell is empty is kept all the same when its
+// sample position lies inside the box of one of the ray's candidate actors (the lists of nrhip_actor_prepare at the ray's
+// time).  With every cand_count zero the outputs are those of nrhip_occgrid_march_levels bit for bit.
+extern "C" int nrhip_occgrid_march_levels_actors(const nrhip_occgrid_levels* grid, const nrhip_actors* actors,
+                                                 const int32_t* cand_count, const int32_t* cand_actor,
+                                                 const float* cand_w2b, const float* origins, const float* directions,
+                                                 const float* t_min, const float* t_max, const float* t_rand, int64_t r,
+                                                 float render_step_size, float near_plane, float far_plane,
+                                                 float cone_angle, int32_t max_candidates, int32_t* counts,
+                                                 const int64_t* offsets, int64_t* ray_indices, float* t_starts,
+                                                 float* t_ends, void* stream) {
+  OccDev d;
+  if (int e = to_dev(grid, d)) return e;
+  NR_REQUIRE(actors && actors->n_actors >= 1 && actors->bounds, NRHIP_ERR_INVALID_ARG,
+             "occgrid_march_levels_actors: NULL actors descriptor, no actor or NULL bounds");
+  NR_REQUIRE(r == 0 || (cand_count && cand_actor && cand_w2b), NRHIP_ERR_INVALID_ARG,
+             "occgrid_march_levels_actors: NULL candidate list");
+  const MarchBoxes mb{cand_count, cand_actor, cand_w2b, actors->bounds,
+                      actors->max_candidates > 0 ? actors->max_candidates : NRHIP_DEFAULT_ACTOR_CANDIDATES, actors->n_actors};
+  return march(d, origins, directions, t_min, t_max, t_rand, r, render_step_size, near_plane, far_plane, cone_angle,
+               max_candidates, counts, offsets, ray_indices, t_starts, t_ends, stream, &mb);
 }
 
 // ---- grid maintenance (occgrid_update.h) ---------------------------------------------------------------------------------

@@ -44,6 +44,9 @@
 //     zeros for a ray without samples (which costs one dead tile's gathers and no MLP).  The per-sample kernel (Lay::PackedRows, training:
 //     nrhip_field_fwd_train_packed) stores at the packed sample index and carries no compositing state: a lane past the
 //     ray's end and a ray without samples store nothing.
+//   * PACKED SAMPLES WITH ACTORS (Lay::PackedActors instantiations, eval: nrhip_render_fwd_packed_actors): the two above
+//     together -- the pending tile of a packed ray also carries the ray's candidate count, the candidate walk is the dense actor
+//     kernel's, the compositing the packed kernel's.  One candidate list per RAY; nothing is sized by the sample count.
 // The sky residual (models/neurad.py:381: w_{S-1} += 1 - sum w) is folded into the last tile -- the accumulated weight is
 // complete there, so no copy of the last sample's features has to be kept.
 #include "common.h"
@@ -555,7 +558,8 @@ __device__ __forceinline__ void load_pending_packed(PendingTile& p, int64_t pos,
                                                     const int32_t* __restrict__ order, const float* __restrict__ ro,
                                                     const float* __restrict__ rd, const float* __restrict__ rarea,
                                                     const float* __restrict__ rstarts, const float* __restrict__ rends,
-                                                    const int64_t* __restrict__ segs, int& first, int& count) {
+                                                    const int64_t* __restrict__ segs, int& first, int& count,
+                                                    const int32_t* __restrict__ cand_count = nullptr) {
   p.pos = pos, p.t = t, p.valid = pos < rr.end;
   const int64_t pc = p.valid ? pos : rr.end - 1;
   const int64_t ray = order ? (int64_t)order[pc] : pc;
@@ -571,7 +575,7 @@ __device__ __forceinline__ void load_pending_packed(PendingTile& p, int64_t pos,
   p.ox = ro[3 * ray], p.oy = ro[3 * ray + 1], p.oz = ro[3 * ray + 2];
   p.dx = rd[3 * ray], p.dy = rd[3 * ray + 1], p.dz = rd[3 * ray + 2];
   p.area = rarea[ray];
-  p.ncand = 0;
+  p.ncand = cand_count ? cand_count[ray] : 0;  // (Lay::PackedActors)
 }
 
 // H2 + H3 + the hash of H1 for one pending tile, then all gathers issued back to back (no waits in here beyond the
@@ -774,7 +778,10 @@ __device__ __forceinline__ void blend_tile(const TileFetch<EncFrame<L, F>::LPL, 
 // L levels, F features/level (L*F <= 32, see EncFrame), H hidden width, HALF = fp16 table; OUT / SRC / PROD / LAY: the
 // variant (render_variants.h).  Lay::Packed takes the sample count M in `S` and the segments [R + 1] through `tables`
 // (no new argument: the existing kernels keep their argument block), and composites as nrhip_packed_composite_fwd does:
-// no sky-residual sample, depth over all samples, zeros for a ray without samples.
+// no sky-residual sample, depth over all samples, zeros for a ray without samples.  Lay::PackedActors is Lay::Packed with
+// Src::Actors: `tables` is the actors' own, the segments come through `sv.enc`.  A lane past its ray's end holds the ray's
+// last sample (load_pending_packed), so it walks the candidate list like a live lane and weighs nothing; the candidate
+// row index is ray * K with ray < R, the slot < cand_count[ray] <= K: inside [0, R K), as in the dense actor kernel.
 template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD, Lay LAY = Lay::Dense>
 __global__ __launch_bounds__(256, 2) void render_kernel(
     FieldDev fd, int64_t n_rays, int S, int stride, const int32_t* __restrict__ order, const float* __restrict__ ro,
@@ -791,8 +798,12 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
   constexpr bool COMPOSITE = OUT == Out::Composite;
   constexpr bool ACT = SRC == Src::Actors, RELAY = SRC == Src::EvalTable, OVR = SRC == Src::Overrides;
   constexpr bool PAIRS = PROD == Prod::F16Pairs;
-  constexpr bool PACKED = LAY != Lay::Dense;  // (Packed: composited, PackedRows: per-sample rows)
-  const int64_t* const segs = reinterpret_cast<const int64_t*>(tables);  // PACKED: [R + 1]
+  constexpr bool PACKED = LAY != Lay::Dense;  // (Packed / PackedActors: composited, PackedRows: per-sample rows)
+  // PACKED: [R + 1].  The actor kernel needs `tables` for its table pointers: its segments travel in the first of the save
+  // pointers, which no composited kernel reads
+  const int64_t* const segs = LAY == Lay::PackedActors ? reinterpret_cast<const int64_t*>(sv.enc)
+                                                       : reinterpret_cast<const int64_t*>(tables);
+  const int32_t* const pcand = ACT ? cand_count : nullptr;  // PACKED: the candidate counts the pending tile reads
   // OVR (training forward of a scene with dynamic actors): samples inside an actor box take their encoding row and view
   // direction from the caller (the differentiable actor branch computed them for the few hit samples) instead of the
   // static lookup.  The three actor-only pointer arguments carry the overrides:
@@ -853,7 +864,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
   PendingTile q;
   int qb = 0, qn = 0;  // PACKED: first sample and sample count of q's ray (wave-uniform)
   auto tiles_of = [](int n) { return n > 16 ? (n + 15) >> 4 : 1; };  // PACKED: a ray without samples walks one dead tile
-  if constexpr (PACKED) load_pending_packed(q, pos, 0, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn);
+  if constexpr (PACKED) load_pending_packed(q, pos, 0, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
   else load_pending(q, pos, 0, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
   int64_t ray = q.ray;
   int cb = 0, cn = 0;  // PACKED: first sample and sample count of the ray in `tf`
@@ -863,7 +874,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
   if constexpr (OVR) ta = (q.valid && j < S) ? ovr_row[q.ray * S + j] : -1;  // override row of this lane's sample of `tf`
   {
     const bool wrap = (PACKED ? tiles_of(cn) : ntile) == 1;
-    if constexpr (PACKED) load_pending_packed(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn);
+    if constexpr (PACKED) load_pending_packed(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
     else load_pending(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
   }
 
@@ -974,7 +985,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     // ---- issue the next tile's gathers: they fly while this tile runs through the MLPs ---------------
     if (ray_done && q.valid && q.pos == pos) {  // terminated early: q still points into this ray -> skip to the next ray
       // (one exposed round trip)
-      if constexpr (PACKED) load_pending_packed(q, pos + pos_step, 0, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn);
+      if constexpr (PACKED) load_pending_packed(q, pos + pos_step, 0, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
       else load_pending(q, pos + pos_step, 0, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
     }
     const bool have_next = q.valid;
@@ -989,7 +1000,7 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     {
       const bool wrap = nt + 1 == (PACKED ? tiles_of(nn) : ntile);  // request the small loads of the tile after it
       if constexpr (PACKED)
-        load_pending_packed(q, wrap ? npos + pos_step : npos, wrap ? 0 : nt + 1, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn);
+        load_pending_packed(q, wrap ? npos + pos_step : npos, wrap ? 0 : nt + 1, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
       else
         load_pending(q, wrap ? npos + pos_step : npos, wrap ? 0 : nt + 1, rr, j, order, ro, rd, rarea, rstarts, rends,
                      cand_count);
@@ -1330,7 +1341,7 @@ struct RenderArgs {
 
 template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD, Lay LAY = Lay::Dense>
 static int launch_render(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
-  constexpr bool OVR = SRC == Src::Overrides, PACKED = LAY != Lay::Dense;
+  constexpr bool OVR = SRC == Src::Overrides, PACKED = LAY == Lay::Packed || LAY == Lay::PackedRows;
   constexpr size_t lds = ((SRC == Src::Actors || OVR) ? Lds<H, PROD>::TOTAL_ACT : Lds<H, PROD>::TOTAL) * sizeof(float);
   auto kern = render_kernel<L, F, H, HALF, OUT, SRC, PROD, LAY>;
   static int cap = 0;  // persistent grid: CUs x resident workgroups per CU, queried once per instantiation
@@ -1346,10 +1357,13 @@ static int launch_render(const FieldDev& fd, const RaysDev& rd, const RenderArgs
   const int64_t want = (rd.R + 3) / 4;
   const int blocks = (int)(want < cap ? want : cap);
   const ActorLaunch& al = a.actors;
+  SaveDev sv = a.sv;
+  // (Lay::PackedActors: `tables` is taken, the segments go through the first save pointer -- read, never written)
+  if constexpr (LAY == Lay::PackedActors) sv.enc = reinterpret_cast<float*>(const_cast<int64_t*>(a.segments));
   // (the override kernel reads its three arrays through the actor kernel's pointer arguments, the packed kernel its
   // segments through the last of them and M = rd.S: see render_kernel)
   kern<<<blocks, 256, lds, a.stream>>>(fd, rd.R, rd.S, rd.stride, rd.order, rd.o, rd.d, rd.area, rd.starts, rd.ends, a.feat,
-                                       a.depth, a.acc, a.w, a.sdf, a.alpha, a.sv, a.stop_eps, a.range, al.ad,
+                                       a.depth, a.acc, a.w, a.sdf, a.alpha, sv, a.stop_eps, a.range, al.ad,
                                        OVR ? a.ovr.row : al.cand_count, al.cand_actor, OVR ? a.ovr.rows : al.cand_w2b,
                                        OVR ? a.ovr.dirs : al.bounds,
                                        PACKED ? reinterpret_cast<const void* const*>(a.segments) : al.tables);
@@ -1438,6 +1452,31 @@ static int dispatch_render_packed(const nrhip_field* f, Out out, const RaysDev& 
   NRHIP_RENDER_VARIANTS(X)
 #undef X
   set_error("fused field kernel: no instantiation for L=%d F=%d H=%d", v.L, v.F, v.H);
+  return NRHIP_ERR_UNSUPPORTED;
+}
+
+// The packed form of a `Composite, Actors, F32` row (Lay::PackedActors; no rows of its own either)
+template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD>
+static int launch_packed_actors_row(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
+  if constexpr (render_variant_ok(L, F, OUT, SRC, PROD, Lay::PackedActors)) {
+    return launch_render<L, F, H, HALF, OUT, SRC, PROD, Lay::PackedActors>(fd, rd, a);
+  } else {
+    set_error("fused field kernel with actors: no packed form of this variant");
+    return NRHIP_ERR_UNSUPPORTED;
+  }
+}
+
+static int dispatch_render_packed_actors(const nrhip_field* f, const RaysDev& rd, const RenderArgs& a) {
+  const Variant v = choose_variant(f, Out::Composite, Src::Actors);
+  const FieldDev fd = to_dev(*f);
+  const bool half = f->grid.param_dtype == 1;
+#define X(L_, F_, H_, O_, S_, P_)                                                                       \
+  if (same(v, {L_, F_, H_, Out::O_, Src::S_, Prod::P_}))                                                \
+    return half ? launch_packed_actors_row<L_, F_, H_, true, Out::O_, Src::S_, Prod::P_>(fd, rd, a)     \
+                : launch_packed_actors_row<L_, F_, H_, false, Out::O_, Src::S_, Prod::P_>(fd, rd, a);
+  NRHIP_RENDER_VARIANTS(X)
+#undef X
+  set_error("fused field kernel with actors: no instantiation for L=%d F=%d H=%d", v.L, v.F, v.H);
   return NRHIP_ERR_UNSUPPORTED;
 }
 
@@ -1644,4 +1683,59 @@ extern "C" int nrhip_render_fwd_actors(const nrhip_field* f, const nrhip_actors*
   if (int e = dispatch_render(f, &split, Out::Composite, Src::Static, ra)) return e;
   ra.range = ranges + 2, ra.actors = al;
   return dispatch_render(f, &split, Out::Composite, Src::Actors, ra);
+}
+
+// The packed counterpart of nrhip_render_fwd_actors: the same three launches on the march's ragged segments.
+extern "C" int nrhip_render_fwd_packed_actors(const nrhip_field* f, const nrhip_actors* a, const nrhip_packed_rays* rays,
+                                              const int32_t* cand_count, const int32_t* cand_actor, const float* cand_w2b,
+                                              float* out_features, float* out_depth, float* out_acc, float* out_weights,
+                                              float early_stop_eps, int32_t* workspace, void* stream) {
+  if (int e = validate_field(f)) return e;
+  if (int e = validate_packed_rays("render_fwd_packed_actors", rays, true)) return e;
+  NR_REQUIRE(a, NRHIP_ERR_INVALID_ARG, "render_fwd_packed_actors: actors descriptor is NULL");
+  if (int e = validate_grid(&a->grid)) return e;
+  const int64_t R = rays->n_rays;
+  if (R == 0) return NRHIP_OK;
+  NR_REQUIRE(out_features && out_depth && out_acc, NRHIP_ERR_INVALID_ARG, "render_fwd_packed_actors: NULL output");
+  NR_REQUIRE(early_stop_eps >= 0.f && early_stop_eps < 1.f, NRHIP_ERR_INVALID_ARG,
+             "render_fwd_packed_actors: early_stop_eps %g not in [0,1)", (double)early_stop_eps);
+  NR_REQUIRE(f->grid.param_dtype == a->grid.param_dtype, NRHIP_ERR_UNSUPPORTED,
+             "render_fwd_packed_actors: the static and the actor tables must share one storage type (fp32 or fp16)");
+  NR_REQUIRE(a->grid.n_features == f->grid.n_features && a->grid.num_levels <= f->grid.num_levels, NRHIP_ERR_UNSUPPORTED,
+             "render_fwd_packed_actors: actor grid (L=%d F=%d) must have the static grid's features per level (F=%d) and at "
+             "most its levels (L=%d); use the unfused ops",
+             a->grid.num_levels, a->grid.n_features, f->grid.n_features, f->grid.num_levels);
+  hipStream_t st = (hipStream_t)stream;
+  if (rays->n_samples == 0) {  // as nrhip_render_fwd_packed: nothing per sample is read, the per-ray outputs are zeroed
+    if (hipMemsetAsync(out_features, 0, (size_t)R * 32 * sizeof(float), st) != hipSuccess ||
+        hipMemsetAsync(out_depth, 0, (size_t)R * sizeof(float), st) != hipSuccess ||
+        hipMemsetAsync(out_acc, 0, (size_t)R * sizeof(float), st) != hipSuccess) {
+      set_error("render_fwd_packed_actors: zeroing the outputs failed");
+      return NRHIP_ERR_LAUNCH;
+    }
+    return NRHIP_OK;
+  }
+  NR_REQUIRE(cand_count && cand_actor && cand_w2b && workspace && a->bounds && a->tables && a->n_actors >= 1 &&
+                 a->actor_scale > 0.f,
+             NRHIP_ERR_INVALID_ARG, "render_fwd_packed_actors: NULL pointer / empty actor set");
+  NR_REQUIRE(R < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "render_fwd_packed_actors: n_rays >= 2^31");
+  RenderArgs ra{};
+  ra.feat = out_features, ra.depth = out_depth, ra.acc = out_acc, ra.w = out_weights;
+  ra.stop_eps = early_stop_eps, ra.stream = st, ra.segments = rays->segments;
+  ActorLaunch al;
+  al.ad.K = a->max_candidates > 0 ? a->max_candidates : NRHIP_DEFAULT_ACTOR_CANDIDATES;
+  al.ad.La = a->grid.num_levels, al.ad.log2T = a->grid.log2_table_size, al.ad.scale = a->actor_scale;
+  for (int l = 0; l < NRHIP_MAX_LEVELS; ++l) al.ad.scal[l] = a->grid.scalings[l];
+  al.cand_count = cand_count, al.cand_actor = cand_actor, al.cand_w2b = cand_w2b, al.bounds = a->bounds, al.tables = a->tables;
+  // the split of nrhip_render_fwd_actors: rays without candidates run the static packed kernel, the others the actor-aware one
+  int32_t* order2 = workspace;
+  int32_t* ranges = workspace + R;
+  actor_partition_kernel<<<1, kPartThreads, 0, st>>>(cand_count, rays->order, R, order2, ranges);
+  if (int e = check_launch("actor_partition")) return e;
+  RaysDev rd = packed_launch_rays(*rays);
+  rd.order = order2;
+  ra.range = ranges;
+  if (int e = dispatch_render_packed(f, Out::Composite, rd, ra)) return e;
+  ra.range = ranges + 2, ra.actors = al;
+  return dispatch_render_packed_actors(f, rd, ra);
 }

@@ -30,6 +30,7 @@ enum class Lay {
   Dense,   // [R, S] with a row stride: every ray has S samples
   Packed,  // [M] + segments [R + 1]: ray r owns the samples [segments[r], segments[r + 1]) (the occupancy march's output)
   PackedRows,  // the same addressing for the per-sample kernel: every output and saved row at the packed sample index
+  PackedActors,  // Packed for a scene with dynamic actors: the composited kernel with the per-sample table select
 };
 
 // The legal mixes, asserted by the kernel for every instantiation.
@@ -39,6 +40,9 @@ constexpr bool render_variant_ok(int L, int F, Out out, Src src, Prod prod, Lay 
   if (lay == Lay::Packed && !(out == Out::Composite && src == Src::Static && prod != Prod::Bf16Split)) return false;
   // ... and the per-sample static-scene kernel with fp32 products (the packed training forward), derived the same way
   if (lay == Lay::PackedRows && !(out == Out::PerSample && src == Src::Static && prod == Prod::F32)) return false;
+  // ... and the composited actor kernel, fp32 products: every `Composite, Actors, F32` row, derived the same way
+  // (render.hip: dispatch_render_packed_actors)
+  if (lay == Lay::PackedActors && !(out == Out::Composite && src == Src::Actors && prod == Prod::F32)) return false;
   // actors (static and actor tables share one storage type) and the eval-table layout: the composited eval kernel
   if ((src == Src::Actors || src == Src::EvalTable) && out != Out::Composite) return false;
   // row overrides: the per-sample training forward
@@ -57,7 +61,8 @@ constexpr bool render_variant_ok(int L, int F, Out out, Src src, Prod prod, Lay 
 
 // X(L, F, H, output, source, products): one line per instantiation; every line exists for fp32 and fp16 tables, and every
 // `Composite, Static` line with `F32` or `F16Pairs` products for dense and packed samples, every `PerSample, Static, F32`
-// line for dense samples and packed rows (render_variant_ok).
+// line for dense samples and packed rows, every `Composite, Actors, F32` line for dense and packed samples
+// (render_variant_ok).
 // L * F == 32 (L = 16, 8, 4) fills the kernel's encoding frame; the smaller grids live in the padded frame (EncFrame):
 // BASELINE config[0]'s 1 x 4, NeuRAD tiny's 4 x 2, and the L * F == 16 grids 4 x 4 and 8 x 2 -- fp32 products only.
 #define NRHIP_RENDER_VARIANTS(X)        \

@@ -174,6 +174,13 @@ class NeuRADHashEncoding(nn.Module):
         spec = self.actor_spec()
         return spec, ops.actor_prepare(spec, origins, directions, pixel_area, starts, ends, times, edit=self.actor_edit())
 
+    def prepare_actors_line(self, origins, directions, t0, t1, times):
+        """``prepare_actors`` without [R,S] edges: one candidate list per ray from the ray's line through its points at t0
+        and t1 (floats or [R]; finite and distinct), at the ray's time, with the eval-time actor edit -- what the box-aware
+        occupancy march and the fused packed render with actors take (ops.actor_prepare_line)."""
+        spec = self.actor_spec()
+        return spec, ops.actor_prepare_line(spec, origins, directions, t0, t1, times, edit=self.actor_edit())
+
     def sample_ray_flip(self, origins) -> Optional[Tensor]:
         """-1 with prob flip_prob else +1, per ray, training only (neurad_encoding.py:212-215)."""
         p = self.config.actor.flip_prob

@@ -165,6 +165,12 @@ class NeuRADField(nn.Module):
         render_variant_ok); scenes with dynamic actors take the operator path."""
         return not self.hashgrid.has_actors() and self.fused_supported()
 
+    def fused_packed_actors_supported(self) -> bool:
+        """Can the fused render kernel composite the PACKED samples of this field's scene WITH its dynamic actors
+        (``render_packed(..., times=...)``, nrhip_render_fwd_packed_actors)?  A field with actors that ``fused_supported(
+        with_actors=True)`` covers: the packed actor kernels are the table's `Composite, Actors, F32` rows."""
+        return self.hashgrid.has_actors() and self.fused_supported(with_actors=True)
+
     def fused_packed_train_supported(self) -> bool:
         """Can ``render_train_packed`` train this field on PACKED samples as one node?  ``fused_packed_supported`` (static
         scene, a fused configuration) with the fused training forward's own condition (biases on every layer)."""
@@ -228,12 +234,16 @@ class NeuRADField(nn.Module):
 
     def render_packed(self, origins, directions, pixel_area, t_starts, t_ends, *, segments: Optional[Tensor] = None,
                       ray_indices: Optional[Tensor] = None, num_rays: Optional[int] = None, return_weights=False,
-                      early_stop_eps: float = 0.0, order: Optional[Tensor] = None):
+                      early_stop_eps: float = 0.0, order: Optional[Tensor] = None, times: Optional[Tensor] = None,
+                      actor_cand=None):
         """``render`` for the packed samples of an occupancy march, one kernel: per-RAY origins / directions [R,3] and
         pixel_area [R] (or [R,1]), per-sample t_starts / t_ends [M], and exactly one of ``segments`` int64 [R+1] or
         ``ray_indices`` int64 [M] (sorted) + ``num_rays``.  -> features [R,32], depth [R,1] (sum w mid), accumulation [R,1]
         (, weights [M]), composited as renderers.render_packed does (no sky residual; a ray without samples gets zeros).
-        Inference only: training goes through forward() + renderers.render_packed."""
+        Inference only: training goes through forward() + renderers.render_packed.
+        A scene with dynamic actors (``fused_packed_actors_supported``) needs ``times`` [R], the rays' times, or ``actor_cand``,
+        the per-RAY candidate lists already computed (``hashgrid.prepare_actors_line``; a march with boxes shares them): a sample
+        inside an actor's box then reads that actor's grid, as in ``render``.  Without either an actor field is refused."""
         if (segments is None) == (ray_indices is None):
             raise ValueError("render_packed: give exactly one of segments / ray_indices (+ num_rays)")
         if ray_indices is not None and num_rays is None:
@@ -242,12 +252,22 @@ class NeuRADField(nn.Module):
                 isinstance(t, Tensor) and t.requires_grad for t in (origins, directions, t_starts, t_ends))):
             raise RuntimeError("render_packed has no backward: call it under torch.no_grad(); a grad-enabled call goes "
                                "through forward() on the packed RaySamples + renderers.render_packed")
-        if not self.fused_packed_supported():
-            raise NotImplementedError("fused packed render kernel: static scenes of the fused configurations only; use the "
+        with_actors = (times is not None or actor_cand is not None) and self.fused_packed_actors_supported()
+        if not with_actors and not self.fused_packed_supported():
+            raise NotImplementedError("fused packed render kernel: static scenes of the fused configurations only (scenes "
+                                      "with dynamic actors: pass the rays' times); use the "
                                       "operator path, forward() on the packed RaySamples + renderers.render_packed")
         with torch.no_grad():
             if segments is None:
                 segments = ops.packed_segments(ray_indices, int(num_rays))
+            if with_actors:
+                if actor_cand is not None:
+                    spec, cand = self.hashgrid.actor_spec(), actor_cand
+                else:
+                    spec, cand = self.hashgrid.prepare_actors_line(origins, directions, 0.0, 1.0, times)
+                return ops.render_fwd_packed_actors(self.field_spec(), spec, cand, origins, directions, pixel_area, t_starts,
+                                                    t_ends, segments, return_weights, early_stop_eps=early_stop_eps,
+                                                    order=order)
             return ops.render_fwd_packed(self.field_spec(), origins, directions, pixel_area, t_starts, t_ends, segments,
                                          return_weights, early_stop_eps=early_stop_eps, order=order)
 

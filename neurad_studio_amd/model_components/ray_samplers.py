@@ -211,11 +211,32 @@ class VolumetricSampler(Sampler):
         raise RuntimeError("The VolumetricSampler fuses sample generation and density check together. "
                            "Please call forward() directly.")
 
+    @staticmethod
+    def _actor_boxes(field, ray_bundle: RayBundle):
+        """``actor_boxes=True``: (ActorSpec, the per-RAY candidate lists at the rays' times), computed once for the march and
+        the fused render.  The eval-time actor edit is honoured (hashgrid.prepare_actors_line)."""
+        hg = getattr(field, "hashgrid", None)
+        if hg is None or not hg.has_actors():
+            raise ValueError("actor_boxes=True: the field has no dynamic actors (the plain march is the default)")
+        if ray_bundle.times is None:
+            raise ValueError("actor_boxes=True: the ray bundle has no times (an actor's box is where it is at the ray's time)")
+        with torch.no_grad():
+            return hg.prepare_actors_line(ray_bundle.origins.detach().contiguous(), ray_bundle.directions.detach().contiguous(),
+                                          0.0, 1.0, ray_bundle.times.reshape(-1).float())
+
     def _march(self, ray_bundle: RayBundle, render_step_size, near_plane, far_plane, alpha_thre, cone_angle,
-               stratified: Optional[bool] = None):
+               stratified: Optional[bool] = None, actor_boxes=None):
         """-> contiguous origins, directions and the march's packed (ray_indices, starts, ends).  stratified: None = in
-        training mode only"""
+        training mode only.  actor_boxes: (ActorSpec, cand) for the box-aware march (``_actor_boxes``), None = the plain one"""
         rays_o, rays_d = ray_bundle.origins.contiguous(), ray_bundle.directions.contiguous()
+        kw = {}
+        if actor_boxes is not None:
+            import inspect
+
+            if "actor_boxes" not in inspect.signature(self.occupancy_grid.sampling).parameters:
+                raise TypeError(f"actor_boxes=True: {type(self.occupancy_grid).__name__}.sampling takes no `actor_boxes` "
+                                "(a march that knows nothing of the boxes would drop the actors' samples)")
+            kw["actor_boxes"] = actor_boxes
         t_min = t_max = None
         if ray_bundle.nears is not None and ray_bundle.fars is not None:
             t_min, t_max = ray_bundle.nears.contiguous().reshape(-1), ray_bundle.fars.contiguous().reshape(-1)
@@ -225,13 +246,17 @@ class VolumetricSampler(Sampler):
             alpha_fn=self._wrap(self.alpha_fn, rays_o, rays_d, ray_bundle.times), render_step_size=render_step_size,
             near_plane=near_plane, far_plane=1e10 if far_plane is None else far_plane,
             stratified=self.training if stratified is None else stratified,
-            cone_angle=cone_angle, alpha_thre=alpha_thre)
+            cone_angle=cone_angle, alpha_thre=alpha_thre, **kw)
         return rays_o, rays_d, ray_indices, starts, ends
 
     def forward(self, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0,
-                far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0):
+                far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0,
+                actor_boxes: bool = False, field=None):
+        """actor_boxes=True (with ``field``, the field whose actors are meant, and a bundle with times): the box-aware march
+        -- the samples inside an actor's box at the ray's time are kept although the static grid calls their cells empty."""
+        boxes = self._actor_boxes(field, ray_bundle) if actor_boxes else None
         rays_o, rays_d, ray_indices, starts, ends = self._march(ray_bundle, render_step_size, near_plane, far_plane,
-                                                                alpha_thre, cone_angle)
+                                                                alpha_thre, cone_angle, actor_boxes=boxes)
         if starts.shape[0] == 0:  # single fake sample (ray_samplers.py:541-547)
             ray_indices = torch.zeros((1,), dtype=torch.long, device=rays_o.device)
             starts = torch.ones((1,), dtype=torch.float32, device=rays_o.device)
@@ -255,20 +280,28 @@ class VolumetricSampler(Sampler):
     @torch.no_grad()
     def render(self, field, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0,
                far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0,
-               early_stop_eps: float = 0.0) -> dict:
+               early_stop_eps: float = 0.0, actor_boxes: bool = False) -> dict:
         """Eval: march + field + compositing -> ``features`` [R,32], ``depth`` [R,1] (sum w mid), ``accumulation`` [R,1],
         ``weights`` [M,1] and the march's ``ray_indices`` / ``t_starts`` / ``t_ends`` [M].  A field with a packed fused
         kernel (``fused_packed_supported``) gets the BUNDLE'S per-ray tensors and the packed intervals in one kernel: no
         per-sample copy of origins / directions / pixel area, no per-sample feature.  Any other field takes forward() on
         the gathered RaySamples + renderers.render_packed: the same keys.  A march without samples returns zero rows (the
         single fake sample of forward() serves its callers' shapes and is not needed here).  early_stop_eps: the fused
-        route's ray termination (see ops.render_fwd); the operator route is exact."""
+        route's ray termination (see ops.render_fwd); the operator route is exact.
+        actor_boxes=True (a field with dynamic actors, a bundle with times; default off): the candidate lists are computed
+        once per ray, the march keeps the samples inside the actors' boxes, and a field with ``fused_packed_actors_supported``
+        renders them with the fused packed-actors kernel; any other field takes the operator route on the same samples."""
         if self.training:
             raise RuntimeError("VolumetricSampler.render is the eval route; training calls forward() + renderers.render_packed")
         R = ray_bundle.origins.shape[0]
+        boxes = self._actor_boxes(field, ray_bundle) if actor_boxes else None
         rays_o, rays_d, ri, starts, ends = self._march(ray_bundle, render_step_size, near_plane, far_plane, alpha_thre,
-                                                       cone_angle)
+                                                       cone_angle, actor_boxes=boxes)
         marched = {"ray_indices": ri, "t_starts": starts, "t_ends": ends}
+        if boxes is not None and getattr(field, "fused_packed_actors_supported", lambda: False)():
+            f, d, a, w = field.render_packed(rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri, num_rays=R,
+                                             return_weights=True, early_stop_eps=early_stop_eps, actor_cand=boxes[1])
+            return {"features": f, "depth": d, "accumulation": a, "weights": w[:, None], **marched}
         if getattr(field, "fused_packed_supported", lambda: False)():
             f, d, a, w = field.render_packed(rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri, num_rays=R,
                                              return_weights=True, early_stop_eps=early_stop_eps)
@@ -287,7 +320,7 @@ class VolumetricSampler(Sampler):
 
     def render_train(self, field, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0,
                      far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0,
-                     fused_ray_gradients: bool = False) -> dict:
+                     fused_ray_gradients: bool = False, actor_boxes: bool = False) -> dict:
         """Training counterpart of ``render``: a stratified march + field + compositing with autograd -> the same keys.  A
         field that trains on packed samples as one node (``fused_packed_train_supported``, ``fused_training`` on) gets the
         BUNDLE'S per-ray tensors and the packed intervals (``render_train_packed``: no per-sample copy of origins /
@@ -295,10 +328,12 @@ class VolumetricSampler(Sampler):
         False`` and, by default, rays that require grad take forward() on the gathered RaySamples + renderers.render_packed.
         ``fused_ray_gradients=True`` keeps rays that require grad (a camera optimizer) on the node, which then returns their
         gradients itself (``render_train_packed(..., ray_gradients=True)``); same keys, same shapes.  A march without samples
-        returns zero rows."""
+        returns zero rows.  actor_boxes=True (a field with dynamic actors, a bundle with times): the box-aware march; the
+        field then trains on its samples on the operator route (there is no fused training node with actors)."""
         R = ray_bundle.origins.shape[0]
+        boxes = self._actor_boxes(field, ray_bundle) if actor_boxes else None
         rays_o, rays_d, ri, starts, ends = self._march(ray_bundle, render_step_size, near_plane, far_plane, alpha_thre,
-                                                       cone_angle, stratified=True)
+                                                       cone_angle, stratified=True, actor_boxes=boxes)
         marched = {"ray_indices": ri, "t_starts": starts, "t_ends": ends}
         rays_need_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
         if (getattr(field, "fused_training", False) and (fused_ray_gradients or not rays_need_grad)

@@ -989,6 +989,19 @@ def actor_prepare(spec: ActorSpec, origins, directions, pixel_area, starts, ends
     return cnt, act, w2b, None
 
 
+def actor_prepare_line(spec: ActorSpec, origins, directions, t0, t1, times, edit: Optional[dict] = None):
+    """``actor_prepare`` for rays that have no [R,S] sample edges (the packed samples of an occupancy march): one candidate
+    list per RAY from the ray's line through origins + directions * t0 and origins + directions * t1 (floats or [R] tensors;
+    finite, t0 != t1).  The cull measures the distance to the infinite line, so any two distinct points give the candidates
+    of every sample on the ray.  Nothing is sized by the number of samples."""
+    o = _chk(origins, "origins")
+    R, dev = o.shape[0], o.device
+    col = lambda t: (t.reshape(R).float() if isinstance(t, Tensor) else torch.full((R,), float(t), device=dev))  # noqa: E731
+    ends = torch.stack([col(t0), col(t1)], dim=1)  # two zero-length samples: their means are the two points
+    area = torch.zeros((R,), device=dev, dtype=torch.float32)  # (enters a sample's std only, which the cull does not read)
+    return actor_prepare(spec, o, directions, area, ends, ends, times, edit=edit)
+
+
 def actor_encode(spec: ActorSpec, cand, origins, directions, pixel_area, starts, ends, features: Tensor,
                  ray_flip: Optional[Tensor] = None):
     """Overwrites the rows of ``features`` [N,out_dim] whose sample lies inside an actor box (in place).
@@ -1169,19 +1182,33 @@ def actor_density_splice_bwd(rows, weight, sample_idx, winner, logit, density_ou
 
 
 def occgrid_march(grid: OccGridSpec, origins, directions, render_step_size, near_plane=0.0, far_plane=1e10,
-                  t_min=None, t_max=None, cone_angle=0.0, t_rand=None, max_candidates=1 << 16):
+                  t_min=None, t_max=None, cone_angle=0.0, t_rand=None, max_candidates=1 << 16, actor_boxes=None):
     """Two-pass packed march: count -> exclusive prefix sum (one host sync for the allocation, like nerfacc) -> write.
-    -> (ray_indices int64 [M], t_starts [M], t_ends [M], segments int64 [R+1])"""
+    -> (ray_indices int64 [M], t_starts [M], t_ends [M], segments int64 [R+1])
+    actor_boxes = (ActorSpec, cand): the box-aware march (nrhip_occgrid_march_levels_actors) -- an interval whose cell is
+    empty is kept all the same when its sample lies inside the box of one of the ray's candidate actors (cand = the per-RAY
+    lists of ``actor_prepare`` / ``actor_prepare_line`` at the ray's time).  None: the plain march."""
     o, d = _chk(origins, "origins"), _chk(directions, "directions")
     R, dev = o.shape[0], o.device
-    if grid.binaries.dim() == 4:  # [L,res,res,res]: the levels-aware entry point (L = 1: the same samples bit for bit)
+    head: tuple = ()
+    if actor_boxes is not None:
+        spec, cand = actor_boxes
+        a, keep_a = spec.c_actors()
+        cnt, act, w2b = (_chk(cand[0], "cand_count", torch.int32), _chk(cand[1], "cand_actor", torch.int32),
+                         _chk(cand[2], "cand_w2b"))
+        if cnt.shape != (R,) or act.shape != (R, a.max_candidates) or w2b.shape != (R, a.max_candidates, 12):
+            raise ValueError(f"occgrid_march: candidate lists must be [R], [R,K], [R,K,12] with R = {R}, K = "
+                             f"{a.max_candidates}: one list per ray")
+        g, keep = grid.c_levels()
+        entry, head = "nrhip_occgrid_march_levels_actors", (a, cnt, act, w2b)
+    elif grid.binaries.dim() == 4:  # [L,res,res,res]: the levels-aware entry point (L = 1: the same samples bit for bit)
         g, keep = grid.c_levels()
         entry = "nrhip_occgrid_march_levels"
     else:
         g, keep = grid.c_grid()
         entry = "nrhip_occgrid_march"
     counts = torch.zeros((R,), dtype=torch.int32, device=dev)
-    args = (g, o, d, _opt(t_min, "t_min"), _opt(t_max, "t_max"), _opt(t_rand, "t_rand"), R, float(render_step_size),
+    args = (g, *head, o, d, _opt(t_min, "t_min"), _opt(t_max, "t_max"), _opt(t_rand, "t_rand"), R, float(render_step_size),
             float(near_plane), float(far_plane), float(cone_angle), int(max_candidates))
     launch(entry, *args, counts, None, None, None, None)
     seg = torch.zeros((R + 1,), dtype=torch.int64, device=dev)
@@ -1458,6 +1485,29 @@ def render_fwd_packed(fs: FieldSpec, origins, directions, pixel_area, t_starts, 
     feats, depth, acc, _ = _render_outputs(r.n_rays, 0, keep[0].device, False)
     w = torch.empty_like(keep[3]) if return_weights else None
     launch("nrhip_render_fwd_packed", f, r, feats, depth, acc, w, float(early_stop_eps))
+    return (feats, depth, acc, w) if return_weights else (feats, depth, acc)
+
+
+def render_fwd_packed_actors(fs: FieldSpec, spec: "ActorSpec", cand, origins, directions, pixel_area, t_starts, t_ends,
+                             segments, return_weights: bool = False, early_stop_eps: float = 0.0,
+                             order: Optional[Tensor] = None, out=None):
+    """``render_fwd_packed`` for a scene with dynamic actors, still one route of three launches and no per-sample tensor:
+    cand = one candidate list per RAY (``actor_prepare_line``).  Same outputs and compositing as ``render_fwd_packed``.
+    ``out``: the buffers to write into, (features [R,32], depth [R,1], accumulation [R,1], weights [M] or None)."""
+    r, keep = _c_packed_rays("render_fwd_packed_actors", origins, directions, pixel_area, t_starts, t_ends, segments, order)
+    f, keep2 = fs.c_field()
+    a, keep3 = spec.c_actors()
+    R, dev = r.n_rays, keep[0].device
+    cnt, act, w2b = (_chk(cand[0], "cand_count", torch.int32), _chk(cand[1], "cand_actor", torch.int32),
+                     _chk(cand[2], "cand_w2b"))
+    if cnt.shape != (R,) or act.shape != (R, a.max_candidates) or w2b.shape != (R, a.max_candidates, 12):
+        raise ValueError(f"render_fwd_packed_actors: candidate lists must be [R], [R,K], [R,K,12] with R = {R}, K = "
+                         f"{a.max_candidates}: one list per ray")
+    feats, depth, acc, _ = _render_outputs(R, 0, dev, False, None if out is None else tuple(out[:3]))
+    w = (torch.empty_like(keep[3]) if out is None or out[3] is None else _flat(out[3], "weights", keep[3].shape[0])) \
+        if return_weights else None
+    work = torch.empty((R + 4,), device=dev, dtype=torch.int32)
+    launch("nrhip_render_fwd_packed_actors", f, a, r, cnt, act, w2b, feats, depth, acc, w, float(early_stop_eps), work)
     return (feats, depth, acc, w) if return_weights else (feats, depth, acc)
 
 

@@ -151,12 +151,15 @@ class OccGridEstimator(torch.nn.Module):
 
     def sampling(self, rays_o, rays_d, sigma_fn=None, alpha_fn=None, near_plane: float = 0.0, far_plane: float = 1e10,
                  t_min=None, t_max=None, render_step_size: float = 1e-3, early_stop_eps: float = 1e-4,
-                 alpha_thre: float = 0.0, stratified: bool = False, cone_angle: float = 0.0):
+                 alpha_thre: float = 0.0, stratified: bool = False, cone_angle: float = 0.0, actor_boxes=None):
+        """actor_boxes (a keyword beyond nerfacc's signature): None = the plain march; (ops.ActorSpec, cand) = the box-aware
+        march -- an interval inside the box of one of the ray's candidate actors is kept whatever its cell says
+        (ops.occgrid_march).  The visibility filter below applies to whatever sigma_fn / alpha_fn return, as before."""
         from .. import ops
 
         t_rand = torch.rand((rays_o.shape[0],), device=rays_o.device) if stratified else None
         ri, ts, te, seg = ops.occgrid_march(self._spec(), rays_o, rays_d, render_step_size, near_plane, far_plane, t_min,
-                                            t_max, cone_angle, t_rand)
+                                            t_max, cone_angle, t_rand, actor_boxes=actor_boxes)
         if (alpha_thre > 0.0 or early_stop_eps > 0.0) and (sigma_fn is not None or alpha_fn is not None) and ri.numel():
             if alpha_thre > 0.0:  # (the one host read of this route: out of scope to move it to the device)
                 alpha_thre = min(alpha_thre, float(self.occs.mean().item()))
