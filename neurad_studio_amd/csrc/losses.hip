@@ -35,6 +35,8 @@ __host__ __device__ constexpr int ray_lds_floats(int sf, int sp) { return 2 * (s
 // ds_bpermute each as shuffles, three times per ray and chunk
 __device__ __forceinline__ double wave_sum_d(double v) { return wscan::reduce<wscan::Add>(v); }
 __device__ __forceinline__ float wave_sum_f(float v) { return wscan::reduce<wscan::Add>(v); }
+// torch's clamp_min(0): a NaN stays a NaN (fmaxf would return the 0 and hide an inf - inf of a fine bin without width)
+__device__ __forceinline__ float clamp_min0(float v) { return v < 0.f ? 0.f : v; }
 // inclusive prefix sum of arr[0..n) in place: fp64 accumulation, every prefix rounded to fp32 (see header)
 __device__ __forceinline__ void scan_inplace(float* arr, int n, int lane) {
   double carry = 0.0;
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(64 * kRaysPerBlock) void interlevel_loss_kernel(
   wave_fence();
   scan_inplace(y2 + 1, M - 1, lane);
   wave_fence();
-  for (int m = lane; m < M - 1; m += 64) y2[m + 1] = fmaxf(y2[m + 1], 0.f);
+  for (int m = lane; m < M - 1; m += 64) y2[m + 1] = clamp_min0(y2[m + 1]);
   if (lane == 0) y2[0] = 0.f;  // yr[0]
   wave_fence();
   // ---- piecewise-linear pdf -> piecewise-quadratic cdf (losses.py:691-693), then the 0 / 1 padding (695-698) -----
@@ -136,7 +138,7 @@ __global__ __launch_bounds__(64 * kRaysPerBlock) void interlevel_loss_kernel(
   for (int k = lane; k < sp; k += 64) {
     const float ws = L.v[k + 1] - L.v[k];
     const float p = wp[k], den = p + 1e-5f;
-    const float d = fmaxf(ws - p, 0.f);
+    const float d = clamp_min0(ws - p);
     part += d * d / den;
     if (gwp) gwp[ray * sp + k] = -(2.f * d / den + d * d / (den * den));
   }
@@ -242,10 +244,11 @@ extern "C" int nrhip_lidar_carving(const float* starts, const float* ends, int32
                                    const uint8_t* is_lidar, const uint8_t* did_return, const float* distance,
                                    float carving_epsilon, float non_return_lidar_distance, int64_t r, int32_t s,
                                    uint8_t* is_close, float* loss_per_ray, float* grad_weights, void* stream) {
-  NR_REQUIRE(starts && ends && is_lidar && distance && r >= 0 && s >= 0 && (is_close || loss_per_ray || grad_weights),
-             NRHIP_ERR_INVALID_ARG, "lidar_carving: bad argument");
+  NR_REQUIRE(r >= 0 && s >= 0, NRHIP_ERR_INVALID_ARG, "lidar_carving: bad argument");
+  if (r == 0) return NRHIP_OK;  // no rays: empty tensors have no address
+  NR_REQUIRE(starts && ends && is_lidar && distance && (is_close || loss_per_ray || grad_weights), NRHIP_ERR_INVALID_ARG,
+             "lidar_carving: bad argument");
   NR_REQUIRE(weights || (!loss_per_ray && !grad_weights), NRHIP_ERR_INVALID_ARG, "lidar_carving: the loss needs the weights");
-  if (r == 0) return NRHIP_OK;
   nrhip::lidar_carving_kernel<<<(int)((r + 3) / 4), 256, 0, (hipStream_t)stream>>>(
       starts, ends, sample_stride > 0 ? sample_stride : s, weights, is_lidar, did_return, distance, carving_epsilon,
       non_return_lidar_distance, r, s, is_close, loss_per_ray, grad_weights);

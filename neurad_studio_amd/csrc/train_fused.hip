@@ -1035,8 +1035,12 @@ extern "C" int nrhip_lidar_losses(const float* const* depths, int32_t n_levels, 
   a.err = scratch, a.stat = scratch + n, a.part = scratch + n + 4;
   static thread_local bool configured = false;
   if (!configured) {
-    (void)hipFuncSetAttribute((const void*)lidar_finish_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kLossLds * (int)sizeof(float));
+    // batches of 16384 .. kLossLds rays ask for 64 .. 128 KB of dynamic LDS: a refusal is this call's error, not a
+    // launch failure later
+    const hipError_t e = hipFuncSetAttribute((const void*)lidar_finish_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             kLossLds * (int)sizeof(float));
+    NR_REQUIRE(e == hipSuccess, NRHIP_ERR_LAUNCH, "lidar_losses: %d bytes of dynamic LDS refused: %s",
+               kLossLds * (int)sizeof(float), hipGetErrorString(e));
     configured = true;
   }
   lidar_rays_kernel<<<a.blocks, 256, 0, (hipStream_t)stream>>>(a);
