@@ -827,6 +827,41 @@ int nrhip_field_fwd_train_packed(const nrhip_field* f, const nrhip_packed_rays* 
                                  float* geo_out /*[M]*/, float* head /*[M]*/, float* save_enc /*[M,L*F]*/,
                                  float* save_geo_hidden /*[M,H]*/, float* save_feat_in /*[M,48]*/,
                                  float* save_feat_hidden /*[M,2H]*/, void* stream);
+/* The same with ROW OVERRIDES (ABI 519): nrhip_field_fwd_train_ovr on packed samples -- the training forward of a scene with
+ * dynamic actors on the march's output.  ovr_row [M] int32 is indexed by the PACKED sample index (-1: the static scene);
+ * ovr_rows [P, L*F] (16-byte aligned) and ovr_dirs [P, 3] as for the dense kernel: a sample with ovr_row >= 0 takes its
+ * encoding row and the view direction of its SH inputs from the caller, save_enc holds the overriding row, and no static
+ * gather is done for it.  The five `PerSample, Overrides, F32` rows of csrc/render_variants.h, fp32 and fp16 static tables.
+ * order, n_rays == 0, n_samples == 0, n_samples >= 2^31 and the alignment of the save buffers as above.                  */
+int nrhip_field_fwd_train_packed_ovr(const nrhip_field* f, const nrhip_packed_rays* rays, const int32_t* ovr_row /*[M]*/,
+                                     const float* ovr_rows, const float* ovr_dirs, float* feature /*[M,32]*/,
+                                     float* geo_out /*[M]*/, float* head /*[M]*/, float* save_enc /*[M,L*F]*/,
+                                     float* save_geo_hidden /*[M,H]*/, float* save_feat_in /*[M,48]*/,
+                                     float* save_feat_hidden /*[M,2H]*/, void* stream);
+/* Actor geometry of packed samples (ABI 519), from one candidate list per RAY (nrhip_actor_prepare on the ray's line, or the
+ * box-aware march's own lists): ray_of [M] int64 (the march's ray_indices, clamped into [0, n_rays)) names each sample's ray;
+ * rays->segments and rays->order are not read.  hits [M, NRHIP_MAX_SAMPLE_CONTAINMENTS] as nrhip_actor_hits writes them,
+ * hit [M] the winning actor (highest index) or -1 and directions [M,3] (may be NULL) the winner's box-frame, renormalised
+ * direction with the training x-flip (ray_flip [R] +-1 or NULL) -- the ray direction outside every box -- as
+ * nrhip_actor_encode.  No feature rows are written.  Position and containment are the dense kernels' own device functions:
+ * uniform segments give their bits.  A sample of a ray without candidates reads its ray index, the candidate count and the
+ * ray direction only.  n_rays == 0 and n_samples == 0 are no-ops that read no pointer.                                   */
+int nrhip_actor_find_packed(const nrhip_actors* a, const nrhip_packed_rays* rays, const int64_t* ray_of,
+                            const int32_t* cand_count, const int32_t* cand_actor, const float* cand_w2b,
+                            int32_t* hits /*[M,8]*/, int32_t* hit /*[M]*/, float* directions /*[M,3] or NULL*/,
+                            const float* ray_flip, void* stream);
+/* nrhip_actor_pair_positions_fwd / _bwd on packed samples (ABI 519): sample_idx [P] int64 is a PACKED sample index (clamped
+ * into [0, M)), its ray comes from ray_of [M]; times and ray_flip stay per ray ([R]).  The same kernel bodies as the dense
+ * pair; the backward ACCUMULATES (atomics) into grad_positions / grad_rotations_6d.  No gradient reaches the rays.        */
+int nrhip_actor_pair_positions_fwd_packed(const nrhip_actors* a, const nrhip_packed_rays* rays, const int64_t* ray_of,
+                                          const float* times, const int64_t* sample_idx, const int32_t* actor_idx,
+                                          const float* ray_flip /*[R] or NULL*/, int64_t n_pairs, float* x01, float* cstd,
+                                          void* stream);
+int nrhip_actor_pair_positions_bwd_packed(const nrhip_actors* a, const nrhip_packed_rays* rays, const int64_t* ray_of,
+                                          const float* times, const int64_t* sample_idx, const int32_t* actor_idx,
+                                          const float* ray_flip, int64_t n_pairs, const float* grad_x01,
+                                          const float* grad_cstd, float* grad_positions, float* grad_rotations_6d,
+                                          void* stream);
 /* head + packed compositing.  beta: DEVICE pointer to the raw parameter, alpha = sigmoid(-geo_out (|beta| + beta_min));
  * beta == NULL: the density head, alpha = 1 - exp(-trunc_exp(geo_out) (t_end - t_start)).  Compositing as
  * nrhip_packed_composite_fwd (no sky residual, depth over all samples, zeros for an empty segment).  alpha [M] is what the

@@ -196,6 +196,10 @@ PROTOTYPES = {
     "nrhip_render_fwd_packed_actors": [C.POINTER(Field), C.POINTER(Actors), C.POINTER(PackedRays), P, P, P, P, P, P, P, F32,
                                        P, P],
     "nrhip_field_fwd_train_packed": [C.POINTER(Field), C.POINTER(PackedRays), P, P, P, P, P, P, P, P],
+    "nrhip_field_fwd_train_packed_ovr": [C.POINTER(Field), C.POINTER(PackedRays), P, P, P, P, P, P, P, P, P, P, P],
+    "nrhip_actor_find_packed": [C.POINTER(Actors), C.POINTER(PackedRays), P, P, P, P, P, P, P, P, P],
+    "nrhip_actor_pair_positions_fwd_packed": [C.POINTER(Actors), C.POINTER(PackedRays), P, P, P, P, P, I64, P, P, P],
+    "nrhip_actor_pair_positions_bwd_packed": [C.POINTER(Actors), C.POINTER(PackedRays), P, P, P, P, P, I64, P, P, P, P, P],
     "nrhip_sdf_render_packed_fwd": [P, P, F32, P, P, P, P, I64, I32, P, P, P, P, P, P],
     "nrhip_sdf_render_packed_bwd_workspace": [I64, C.POINTER(I64)],
     "nrhip_sdf_render_packed_bwd": [P, P, F32, P, P, P, P, P, P, P, P, P, I64, I32, P, P, P, P, P],

@@ -117,6 +117,28 @@ class ActorPairPositionsFn(torch.autograd.Function):
         return (gp, gr) + (None,) * 10
 
 
+class ActorPairPositionsPackedFn(torch.autograd.Function):
+    """ActorPairPositionsFn for the occupancy march's packed samples: sample_idx [P] is a packed sample index, ray_indices
+    int64 [M] names each sample's ray, times and flip are per RAY.  The rays get no gradient here (callers refuse rays that
+    require grad).  args: actor_positions, actor_rotations_6d, spec, origins [R,3], directions [R,3], pixel_area [R],
+    t_starts [M], t_ends [M], ray_indices, times [R], sample_idx, actor_idx, flip [R] | None -> x01 [P,3], cstd [P]"""
+
+    @staticmethod
+    def forward(ctx, positions, rotations_6d, spec, origins, directions, pixel_area, t_starts, t_ends, ray_indices, times,
+                sample_idx, actor_idx, flip):
+        ctx.spec, ctx.flip = spec, flip
+        ctx.save_for_backward(origins, directions, pixel_area, t_starts, t_ends, ray_indices, times, sample_idx, actor_idx)
+        return ops.actor_pair_positions_packed(spec, origins, directions, pixel_area, t_starts, t_ends, ray_indices, times,
+                                               sample_idx, actor_idx, flip)
+
+    @staticmethod
+    def backward(ctx, g_x01, g_cstd):
+        o, d, a, s, e, ri, times, si, ai = ctx.saved_tensors
+        gp, gr = ops.actor_pair_positions_packed_bwd(ctx.spec, o, d, a, s, e, ri, times, si, ai, ctx.flip,
+                                                     g_x01.contiguous(), g_cstd.contiguous())
+        return (gp, gr) + (None,) * 11
+
+
 class MultiHashGridFn(torch.autograd.Function):
     """HashEncoding.pytorch_fwd over several grids of one shape: row i looks into tables[grid_id[i]] -- the per-actor
     grids of NeuRADHashEncoding in one launch (`_get_actor_features_slow` loops over actor ids,
@@ -776,41 +798,92 @@ class NffRenderPackedTrainFn(torch.autograd.Function):
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area, t_starts, t_ends, segments,
                 ray_indices, order, *params):
-        ctx.set_materialize_grads(False)
-        R, M = segments.shape[0] - 1, t_starts.numel()
-        ctx.empty = M == 0
-        if ctx.empty:  # answered on the host: nothing to launch, nothing to differentiate
-            z = lambda *shape: torch.zeros(shape, device=origins.device, dtype=torch.float32)  # noqa: E731
-            return z(R, 32), z(R, 1), z(R, 1), z(0)
-        gw, gb, fw, fb = list(params[0:4:2]), list(params[1:4:2]), list(params[4:10:2]), list(params[5:10:2])
-        fs = ops.FieldSpec(spec, table, static_scale, gw, gb, fw, fb, use_sdf=True, beta=1.0)  # (kernel head unused)
-        (feature, geo, _head), (enc, hg, xf, hf) = ops.field_fwd_train_packed(fs, origins, directions, pixel_area, t_starts,
-                                                                              t_ends, segments, order=order)
-        alpha, w, out, depth, acc = ops.sdf_render_packed_fwd(geo, beta, beta_min, feature, t_starts, t_ends, segments)
-        ctx.spec, ctx.scale, ctx.table_dtype, ctx.beta_min = spec, static_scale, table.dtype, beta_min
-        ctx.density_head = beta is None
-        ctx.rays = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]  # a camera optimizer moved the rays
-        ctx.save_for_backward(origins, directions, pixel_area, t_starts, t_ends, segments, ray_indices, enc, hg, xf, hf,
-                              feature, geo, alpha, geo.new_empty(0) if beta is None else beta, *params,
-                              *([table] if ctx.rays else []))
-        return out, depth, acc, w
+        return _packed_train_forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area,
+                                     t_starts, t_ends, segments, ray_indices, order, params)
 
     @staticmethod
     @custom_bwd(device_type="cuda")
     def backward(ctx, g_out, g_depth, g_acc, g_w):
-        none = (None,) * 23
-        if ctx.empty or (g_out is None and g_depth is None and g_acc is None and g_w is None):
-            return none
-        o, d, a, ts, te, seg, ri, enc, hg, xf, hf, feature, geo, alpha, beta, *params = ctx.saved_tensors
-        gfeat, ggeo, gbeta = ops.sdf_render_packed_bwd(geo, None if ctx.density_head else beta, ctx.beta_min, alpha, feature,
-                                                       ts, te, seg, g_out, g_depth, g_acc, g_w)
-        rays = None
-        if ctx.rays:
-            params, rays = params[:-1], RayGrads(params[-1], ctx.needs_input_grad[5], ctx.needs_input_grad[6])
-        gt, grads, _, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a,
-                                                 Samples(ts, te, seg, ri), enc, hg, xf, hf, params, gfeat, ggeo, rays=rays)
-        g_beta = gbeta.reshape(beta.shape) if (ctx.needs_input_grad[3] and not ctx.density_head) else None
+        back = _packed_train_backward(ctx, g_out, g_depth, g_acc, g_w)
+        if back is None:
+            return (None,) * 23
+        gt, g_beta, go, gd, _, grads = back
         return (gt, None, None, g_beta, None, go, gd, *([None] * 6), *grads)
+
+
+def _packed_train_forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area, t_starts, t_ends,
+                          segments, ray_indices, order, params, override=None, pair_idx=None):
+    """forward of the two packed training nodes.  override = (ovr_row [M], ovr_rows [P,L*F], ovr_dirs [P,3]) with pair_idx [P]
+    (dynamic actors) or None (the static scene: the launches of the static node).  In both nodes origins / directions are
+    inputs 5 / 6."""
+    ctx.set_materialize_grads(False)
+    R, M = segments.shape[0] - 1, t_starts.numel()
+    ctx.empty = M == 0
+    if ctx.empty:  # answered on the host: nothing to launch, nothing to differentiate
+        z = lambda *shape: torch.zeros(shape, device=origins.device, dtype=torch.float32)  # noqa: E731
+        return z(R, 32), z(R, 1), z(R, 1), z(0)
+    gw, gb, fw, fb = list(params[0:4:2]), list(params[1:4:2]), list(params[4:10:2]), list(params[5:10:2])
+    fs = ops.FieldSpec(spec, table, static_scale, gw, gb, fw, fb, use_sdf=True, beta=1.0)  # (kernel head unused)
+    extra = {} if override is None else {"override": override}
+    (feature, geo, _head), (enc, hg, xf, hf) = ops.field_fwd_train_packed(fs, origins, directions, pixel_area, t_starts,
+                                                                          t_ends, segments, order=order, **extra)
+    alpha, w, out, depth, acc = ops.sdf_render_packed_fwd(geo, beta, beta_min, feature, t_starts, t_ends, segments)
+    ctx.spec, ctx.scale, ctx.table_dtype, ctx.beta_min = spec, static_scale, table.dtype, beta_min
+    ctx.density_head = beta is None
+    ctx.has_ovr = override is not None
+    ctx.rays = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]  # a camera optimizer moved the rays
+    ctx.save_for_backward(origins, directions, pixel_area, t_starts, t_ends, segments, ray_indices, enc, hg, xf, hf,
+                          feature, geo, alpha, geo.new_empty(0) if beta is None else beta, *params,
+                          *([override[0], pair_idx] if ctx.has_ovr else []), *([table] if ctx.rays else []))
+    return out, depth, acc, w
+
+
+def _packed_train_backward(ctx, g_out, g_depth, g_acc, g_w):
+    """-> None (nothing to differentiate) or (grad table, grad beta, grad origins, grad directions, grad of the override
+    rows or None, the ten MLP parameter gradients)"""
+    if ctx.empty or (g_out is None and g_depth is None and g_acc is None and g_w is None):
+        return None
+    o, d, a, ts, te, seg, ri, enc, hg, xf, hf, feature, geo, alpha, beta, *rest = ctx.saved_tensors
+    params, opt = rest[:10], list(rest[10:])
+    gfeat, ggeo, gbeta = ops.sdf_render_packed_bwd(geo, None if ctx.density_head else beta, ctx.beta_min, alpha, feature,
+                                                   ts, te, seg, g_out, g_depth, g_acc, g_w)
+    override = (opt.pop(0), opt.pop(0)) if ctx.has_ovr else None
+    rays = RayGrads(opt.pop(0), ctx.needs_input_grad[5], ctx.needs_input_grad[6]) if ctx.rays else None
+    gt, grads, g_rows, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a,
+                                                  Samples(ts, te, seg, ri), enc, hg, xf, hf, params, gfeat, ggeo,
+                                                  override=override, rays=rays)
+    g_beta = gbeta.reshape(beta.shape) if (ctx.needs_input_grad[3] and not ctx.density_head) else None
+    return gt, g_beta, go, gd, g_rows, grads
+
+
+class NffRenderPackedActorsTrainFn(torch.autograd.Function):
+    """NffRenderPackedTrainFn with ROW OVERRIDES: the packed training node of a scene with dynamic actors.  The samples inside
+    an actor box take their encoding row and view direction from the caller (ops.field_fwd_train_packed with ``override``),
+    exactly as NffRenderTrainFn does on dense samples; the backward hands dL/d enc of those samples to ``ovr_rows`` (every
+    (sample, actor) pair gets its sample's row) and sends nothing of them to the static table.
+
+    args: as NffRenderPackedTrainFn up to ``order``, then ovr_row int32 [M] (row of ovr_rows or -1, at the packed sample
+    index), ovr_rows [P,L*F], ovr_dirs [P,3], pair_idx int64 [P] (the packed sample index of each pair), then the ten MLP
+    parameters -> features [R,32], depth [R,1], accumulation [R,1], weights [M]"""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area, t_starts, t_ends, segments,
+                ray_indices, order, ovr_row, ovr_rows, ovr_dirs, pair_idx, *params):
+        return _packed_train_forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area,
+                                     t_starts, t_ends, segments, ray_indices, order, params,
+                                     override=(ovr_row, ovr_rows, ovr_dirs), pair_idx=pair_idx)
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, g_out, g_depth, g_acc, g_w):
+        back = _packed_train_backward(ctx, g_out, g_depth, g_acc, g_w)
+        if back is None:
+            return (None,) * 27
+        gt, g_beta, go, gd, g_rows, grads = back
+        if not ctx.needs_input_grad[14]:
+            g_rows = None
+        return (gt, None, None, g_beta, None, go, gd, *([None] * 6), None, g_rows, None, None, *grads)
 
 
 class LidarLossFn(torch.autograd.Function):

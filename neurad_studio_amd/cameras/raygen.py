@@ -17,6 +17,7 @@ result is a RayBundle of the class passed as ``bundle_cls`` (default: this packa
 inside nerfstudio types)."""
 from __future__ import annotations
 
+import weakref
 from typing import Optional
 
 import torch
@@ -34,6 +35,15 @@ def _f32(t: Tensor) -> Tensor:
 
 
 _ELIGIBLE: dict = {}  # id(cameras) -> (key, camera type, distorted, error message | None)
+# id(cameras) -> the object an entry was made for: a weak reference, or the object itself where its type takes none (it then
+# lives as long as its entry).  An id -- and with the caching allocator the tensors' addresses, versions and shapes, i.e. the
+# whole key -- comes back once an object is freed: without this a NEW Cameras object could meet a dead one's entry.
+_OWNER: dict = {}
+
+
+def _owns(cameras) -> bool:
+    own = _OWNER.get(id(cameras))
+    return own is cameras or (isinstance(own, weakref.ref) and own() is cameras)
 
 
 def _check_cameras(cameras, undistort_perspective: bool):
@@ -43,7 +53,7 @@ def _check_cameras(cameras, undistort_perspective: bool):
     ct, dp = cameras.camera_type, getattr(cameras, "distortion_params", None)
     key = tuple((t.data_ptr(), t._version, tuple(t.shape)) if isinstance(t, Tensor) else None for t in (ct, dp))
     hit = _ELIGIBLE.get(id(cameras))
-    if hit is None or hit[0] != key:
+    if hit is None or hit[0] != key or not _owns(cameras):
         types = [PERSPECTIVE] if ct is None else torch.unique(ct).tolist()
         err = None
         if len(types) != 1:  # the reference's own loop (cameras.py:792-800) only fills the first matching type's rays
@@ -53,8 +63,12 @@ def _check_cameras(cameras, undistort_perspective: bool):
                    "Cameras.generate_rays otherwise")
         distorted = dp is not None and bool((dp != 0).any())
         if len(_ELIGIBLE) >= 64:
-            _ELIGIBLE.clear()
+            _ELIGIBLE.clear(), _OWNER.clear()
         hit = _ELIGIBLE[id(cameras)] = (key, types[0], distorted, err)
+        try:
+            _OWNER[id(cameras)] = weakref.ref(cameras)
+        except TypeError:
+            _OWNER[id(cameras)] = cameras
     _, camera_type, distorted, err = hit
     if err is None and camera_type == PERSPECTIVE and distorted and not undistort_perspective:
         err = ("device ray generation covers undistorted PERSPECTIVE cameras unless undistort_perspective=True; use "

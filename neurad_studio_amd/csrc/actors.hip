@@ -2,6 +2,9 @@
 // candidate list (one wavefront per ray, lane = actor, ballot/popcount compaction).  Per sample: in-box test over
 // the ray's few candidates, then the actor's own 3-D hash grid replaces the static features (torch-path
 // semantics: per-actor grids, highest actor index wins on overlap, neurad_encoding.py:184-185,256-263).
+// The per-sample geometry (find_hit, sample_hits) and the pair kernels are written once over both sample layouts: dense
+// [R,S] rows, and the occupancy march's packed samples with their ray named by ray_of [M] (nrhip_actor_find_packed,
+// nrhip_actor_pair_positions_fwd_packed / _bwd_packed) -- the same arithmetic, so the layouts agree bit for bit.
 #include "common.h"
 
 namespace nrhip {
@@ -137,18 +140,21 @@ struct ActorHit {
   float px, py, pz, std, dx, dy, dz;
 };
 
-__device__ __forceinline__ ActorHit find_hit(const ActorsDev& a, const RaysDev& r, int64_t i,
+// RD: RaysDev (row i = ray * S + s) or PackedRaysDev (row i = packed sample index, its ray from ray_of): one body, so the two
+// layouts agree bit for bit on every sample (common.h: ray_sample_ray_of_row / ray_sample_interval_of_row)
+template <class RD>
+__device__ __forceinline__ ActorHit find_hit(const ActorsDev& a, const RD& r, const int64_t* ray_of, int64_t i,
                                              const int32_t* cand_count, const int32_t* cand_actor,
                                              const float* cand_w2b) {
   ActorHit h;
   h.actor = -1;
-  const int64_t ray = i / r.S;
-  const int s = (int)(i - ray * r.S);
+  const int64_t ray = ray_sample_ray_of_row(r, ray_of, i);
   const int n = cand_count[ray];
   h.dx = r.d[3 * ray], h.dy = r.d[3 * ray + 1], h.dz = r.d[3 * ray + 2];
   if (n == 0) return h;
+  const int64_t iv = ray_sample_interval_of_row(r, ray, i);
   const SamplePos g = sample_gaussian(r.o[3 * ray], r.o[3 * ray + 1], r.o[3 * ray + 2], h.dx, h.dy, h.dz, r.area[ray],
-                                      r.starts[ray * r.stride + s], r.ends[ray * r.stride + s]);
+                                      r.starts[iv], r.ends[iv]);
   h.std = g.std;
   const float* wsel = nullptr;
   for (int c = 0; c < n; ++c) {  // ascending actor index; the LAST hit wins (neurad_encoding.py:184-185 on CPU)
@@ -182,7 +188,7 @@ __global__ __launch_bounds__(256) void actor_encode_kernel(ActorsDev a, RaysDev 
                                                             int32_t* __restrict__ hit) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= r.R * r.S) return;
-  const ActorHit h = find_hit(a, r, i, cand_count, cand_actor, cand_w2b);
+  const ActorHit h = find_hit(a, r, nullptr, i, cand_count, cand_actor, cand_w2b);
   if (dirs) dirs[3 * i] = h.dx, dirs[3 * i + 1] = h.dy, dirs[3 * i + 2] = h.dz;
   if (hit) hit[i] = h.actor;
   if (h.actor < 0) return;
@@ -208,7 +214,7 @@ __global__ __launch_bounds__(256) void actor_density_kernel(ActorsDev a, RaysDev
                                                              float* __restrict__ dens, int32_t* __restrict__ hit) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= r.R * r.S) return;
-  const ActorHit h = find_hit(a, r, i, cand_count, cand_actor, cand_w2b);
+  const ActorHit h = find_hit(a, r, nullptr, i, cand_count, cand_actor, cand_w2b);
   if (hit) hit[i] = h.actor;
   if (h.actor < 0) return;
   const SamplePos p = contract_gaussian(h.px, h.py, h.pz, h.std, a.scale);
@@ -226,21 +232,19 @@ __global__ __launch_bounds__(256) void actor_density_kernel(ActorsDev a, RaysDev
 // every (sample, candidate) containment, not only the winner: the reference's index_put backward hands the
 // upstream gradient to ALL duplicate (ray, sample) rows (neurad_encoding.py:184-185,256-263), so overlapping
 // actors all receive gradients -- the training path needs the full list to reproduce that.
-__global__ __launch_bounds__(256) void actor_hits_kernel(ActorsDev a, RaysDev r, const int32_t* __restrict__ cand_count,
-                                                          const int32_t* __restrict__ cand_actor,
-                                                          const float* __restrict__ cand_w2b,
-                                                          int32_t* __restrict__ hits) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= r.R * r.S) return;
-  const int64_t ray = i / r.S;
-  const int s = (int)(i - ray * r.S);
+template <class RD>
+__device__ __forceinline__ void sample_hits(const ActorsDev& a, const RD& r, const int64_t* ray_of, int64_t i,
+                                            const int32_t* __restrict__ cand_count,
+                                            const int32_t* __restrict__ cand_actor, const float* __restrict__ cand_w2b,
+                                            int32_t* __restrict__ hits) {
+  const int64_t ray = ray_sample_ray_of_row(r, ray_of, i);
   const int n = cand_count[ray];
 #pragma unroll
   for (int c = 0; c < KH; ++c) hits[i * KH + c] = -1;
   if (n == 0) return;
+  const int64_t iv = ray_sample_interval_of_row(r, ray, i);
   const SamplePos g = sample_gaussian(r.o[3 * ray], r.o[3 * ray + 1], r.o[3 * ray + 2], r.d[3 * ray], r.d[3 * ray + 1],
-                                      r.d[3 * ray + 2], r.area[ray], r.starts[ray * r.stride + s],
-                                      r.ends[ray * r.stride + s]);
+                                      r.d[3 * ray + 2], r.area[ray], r.starts[iv], r.ends[iv]);
   int slot = 0;  // compacted, ascending actor order; beyond KH overlapping boxes the lowest indices drop out, the
                  // winner (highest index = last entry) stays
   for (int c = 0; c < n; ++c) {
@@ -257,6 +261,35 @@ __global__ __launch_bounds__(256) void actor_hits_kernel(ActorsDev a, RaysDev r,
       hits[i * KH + slot++] = act;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void actor_hits_kernel(ActorsDev a, RaysDev r, const int32_t* __restrict__ cand_count,
+                                                          const int32_t* __restrict__ cand_actor,
+                                                          const float* __restrict__ cand_w2b,
+                                                          int32_t* __restrict__ hits) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= r.R * r.S) return;
+  sample_hits(a, r, nullptr, i, cand_count, cand_actor, cand_w2b, hits);
+}
+
+// Packed samples (training on the occupancy march's output): nrhip_actor_hits and the geometry half of nrhip_actor_encode
+// in one pass over the M samples -- every containment, the winner, and the winner's box-frame direction (the ray's own
+// outside every box).  No feature rows: the training node takes them from the differentiable pair branch.  A sample of a
+// ray without candidates reads its ray index, the candidate count and the ray direction: no interval, no origin, no
+// candidate.
+__global__ __launch_bounds__(256) void actor_find_packed_kernel(ActorsDev a, PackedRaysDev r,
+                                                                 const int64_t* __restrict__ ray_of,
+                                                                 const int32_t* __restrict__ cand_count,
+                                                                 const int32_t* __restrict__ cand_actor,
+                                                                 const float* __restrict__ cand_w2b,
+                                                                 int32_t* __restrict__ hits, int32_t* __restrict__ hit,
+                                                                 float* __restrict__ dirs) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)r.M) return;
+  sample_hits(a, r, ray_of, i, cand_count, cand_actor, cand_w2b, hits);
+  const ActorHit h = find_hit(a, r, ray_of, i, cand_count, cand_actor, cand_w2b);
+  hit[i] = h.actor;
+  if (dirs) dirs[3 * i] = h.dx, dirs[3 * i + 1] = h.dy, dirs[3 * i + 2] = h.dz;
 }
 
 static int to_dev(const nrhip_actors* a, ActorsDev& d) {
@@ -348,6 +381,22 @@ extern "C" int nrhip_actor_hits(const nrhip_actors* a, const nrhip_rays* rays, c
   actor_hits_kernel<<<grid_for(n, 256), 256, 0, (hipStream_t)stream>>>(d, to_dev(*rays), cand_count, cand_actor,
                                                                       cand_w2b, hits);
   return check_launch("actor_hits");
+}
+
+extern "C" int nrhip_actor_find_packed(const nrhip_actors* a, const nrhip_packed_rays* rays, const int64_t* ray_of,
+                                       const int32_t* cand_count, const int32_t* cand_actor, const float* cand_w2b,
+                                       int32_t* hits, int32_t* hit, float* directions, const float* ray_flip,
+                                       void* stream) {
+  ActorsDev d;
+  if (int e = to_dev(a, d)) return e;
+  d.flip = ray_flip;
+  if (int e = validate_packed_rays("actor_find_packed", rays, false)) return e;
+  if (rays->n_rays == 0 || rays->n_samples == 0) return NRHIP_OK;
+  NR_REQUIRE(ray_of && cand_count && cand_actor && cand_w2b && hits && hit, NRHIP_ERR_INVALID_ARG,
+             "actor_find_packed: NULL pointer");
+  actor_find_packed_kernel<<<grid_for(rays->n_samples, 256), 256, 0, (hipStream_t)stream>>>(
+      d, to_dev(*rays), ray_of, cand_count, cand_actor, cand_w2b, hits, hit, directions);
+  return check_launch("actor_find_packed");
 }
 
 extern "C" int nrhip_actor_density(const nrhip_actors* a, const nrhip_rays* rays, const int32_t* cand_count,
@@ -446,20 +495,22 @@ __device__ __forceinline__ void pair_box_position(const PairFrame& f, const Samp
   pos[0] *= flip;
 }
 
-__global__ __launch_bounds__(256) void actor_pair_positions_kernel(ActorsDev a, RaysDev r, const float* __restrict__ times,
+// RD / ray_of: as find_hit -- sample_idx is a row index of the layout
+template <class RD>
+__global__ __launch_bounds__(256) void actor_pair_positions_kernel(ActorsDev a, RD r, const int64_t* __restrict__ ray_of,
+                                                                   const float* __restrict__ times,
                                                                    const int64_t* __restrict__ sample_idx,
                                                                    const int32_t* __restrict__ actor_idx,
                                                                    const float* __restrict__ ray_flip, int64_t n_pairs,
                                                                    float* __restrict__ x01, float* __restrict__ cstd) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= n_pairs) return;
-  const int64_t i = sample_idx[p], ray = i / r.S;
-  const int s = (int)(i - ray * r.S);
+  const int64_t i = sample_idx[p], ray = ray_sample_ray_of_row(r, ray_of, i);
+  const int64_t iv = ray_sample_interval_of_row(r, ray, i);
   PairFrame f;
   pair_frame(a, actor_idx[p], times[ray], f);
   const SamplePos g = sample_gaussian(r.o[3 * ray], r.o[3 * ray + 1], r.o[3 * ray + 2], r.d[3 * ray], r.d[3 * ray + 1],
-                                      r.d[3 * ray + 2], r.area[ray], r.starts[ray * r.stride + s],
-                                      r.ends[ray * r.stride + s]);
+                                      r.d[3 * ray + 2], r.area[ray], r.starts[iv], r.ends[iv]);
   float pos[3];
   pair_box_position(f, g, ray_flip ? ray_flip[ray] : 1.f, pos);
   const SamplePos c = contract_gaussian(pos[0], pos[1], pos[2], g.std, a.scale);
@@ -467,8 +518,10 @@ __global__ __launch_bounds__(256) void actor_pair_positions_kernel(ActorsDev a, 
   cstd[p] = c.std;
 }
 
+template <class RD>
 __global__ __launch_bounds__(256) void actor_pair_positions_bwd_kernel(
-    ActorsDev a, RaysDev r, const float* __restrict__ times, const int64_t* __restrict__ sample_idx,
+    ActorsDev a, RD r, const int64_t* __restrict__ ray_of, const float* __restrict__ times,
+    const int64_t* __restrict__ sample_idx,
     const int32_t* __restrict__ actor_idx, const float* __restrict__ ray_flip, int64_t n_pairs,
     const float* __restrict__ g_x01, const float* __restrict__ g_cstd, float* __restrict__ g_positions,
     float* __restrict__ g_rot6, float* __restrict__ g_origins, float* __restrict__ g_directions, int combine_runs) {
@@ -478,14 +531,13 @@ __global__ __launch_bounds__(256) void actor_pair_positions_bwd_kernel(
   const bool live = p0 < n_pairs;
   const int64_t p = live ? p0 : n_pairs - 1;
   const int lane = threadIdx.x & 63;
-  const int64_t i = sample_idx[p], ray = i / r.S;
-  const int s = (int)(i - ray * r.S);
+  const int64_t i = sample_idx[p], ray = ray_sample_ray_of_row(r, ray_of, i);
+  const int64_t iv = ray_sample_interval_of_row(r, ray, i);
   const int act = actor_idx[p];
   PairFrame f;
   pair_frame(a, act, times[ray], f);
   const SamplePos g = sample_gaussian(r.o[3 * ray], r.o[3 * ray + 1], r.o[3 * ray + 2], r.d[3 * ray], r.d[3 * ray + 1],
-                                      r.d[3 * ray + 2], r.area[ray], r.starts[ray * r.stride + s],
-                                      r.ends[ray * r.stride + s]);
+                                      r.d[3 * ray + 2], r.area[ray], r.starts[iv], r.ends[iv]);
   const float flip = ray_flip ? ray_flip[ray] : 1.f;
   float pos[3];
   pair_box_position(f, g, flip, pos);
@@ -511,7 +563,7 @@ __global__ __launch_bounds__(256) void actor_pair_positions_bwd_kernel(
   if (g_origins && live) {
     // d pos / d mean = -d pos / d t: the sample's world position moves with the ray (camera optimizer,
     // cameras/camera_optimizers.py:173-182); mean = o + d t_mid with t_mid a constant (detached bins)
-    const float t0 = r.starts[ray * r.stride + s], t1 = r.ends[ray * r.stride + s];
+    const float t0 = r.starts[iv], t1 = r.ends[iv];
     const float tm = t0 + (t1 - t0) / 2.f;
     for (int c = 0; c < 3; ++c) {
       atomicAdd(g_origins + 3 * ray + c, -gt[c]);
@@ -629,8 +681,8 @@ extern "C" int nrhip_actor_pair_positions_fwd(const nrhip_actors* a, const nrhip
   NR_REQUIRE(n_pairs >= 0 && a->actor_scale > 0.f, NRHIP_ERR_INVALID_ARG, "actor_pair_positions: bad argument");
   if (n_pairs == 0) return NRHIP_OK;
   NR_REQUIRE(times && sample_idx && actor_idx && x01 && cstd, NRHIP_ERR_INVALID_ARG, "actor_pair_positions: NULL pointer");
-  actor_pair_positions_kernel<<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
-      d, to_dev(*rays), times, sample_idx, actor_idx, ray_flip, n_pairs, x01, cstd);
+  actor_pair_positions_kernel<RaysDev><<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
+      d, to_dev(*rays), nullptr, times, sample_idx, actor_idx, ray_flip, n_pairs, x01, cstd);
   return check_launch("actor_pair_positions_fwd");
 }
 
@@ -645,8 +697,8 @@ extern "C" int nrhip_actor_pair_positions_bwd(const nrhip_actors* a, const nrhip
   if (n_pairs == 0) return NRHIP_OK;
   NR_REQUIRE(times && sample_idx && actor_idx && grad_x01 && grad_cstd && grad_positions && grad_rotations_6d,
              NRHIP_ERR_INVALID_ARG, "actor_pair_positions_bwd: NULL pointer");
-  actor_pair_positions_bwd_kernel<<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
-      d, to_dev(*rays), times, sample_idx, actor_idx, ray_flip, n_pairs, grad_x01, grad_cstd, grad_positions,
+  actor_pair_positions_bwd_kernel<RaysDev><<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
+      d, to_dev(*rays), nullptr, times, sample_idx, actor_idx, ray_flip, n_pairs, grad_x01, grad_cstd, grad_positions,
       grad_rotations_6d, nullptr, nullptr, tuning().pair_bwd_runs ? 1 : 0);
   return check_launch("actor_pair_positions_bwd");
 }
@@ -665,10 +717,50 @@ extern "C" int nrhip_actor_pair_positions_bwd_rays(const nrhip_actors* a, const 
   NR_REQUIRE(times && sample_idx && actor_idx && grad_x01 && grad_cstd && grad_positions && grad_rotations_6d &&
                  grad_origins && grad_directions,
              NRHIP_ERR_INVALID_ARG, "actor_pair_positions_bwd_rays: NULL pointer");
-  actor_pair_positions_bwd_kernel<<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
-      d, to_dev(*rays), times, sample_idx, actor_idx, ray_flip, n_pairs, grad_x01, grad_cstd, grad_positions,
+  actor_pair_positions_bwd_kernel<RaysDev><<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
+      d, to_dev(*rays), nullptr, times, sample_idx, actor_idx, ray_flip, n_pairs, grad_x01, grad_cstd, grad_positions,
       grad_rotations_6d, grad_origins, grad_directions, tuning().pair_bwd_runs ? 1 : 0);
   return check_launch("actor_pair_positions_bwd_rays");
+}
+
+// The pair kernels on packed samples: sample_idx is a packed sample index, ray_of [M] names its ray, times / ray_flip stay
+// per ray.  The same kernel bodies; no gradient to the rays (nrhip_actor_pair_positions_bwd_rays has no packed form).
+extern "C" int nrhip_actor_pair_positions_fwd_packed(const nrhip_actors* a, const nrhip_packed_rays* rays,
+                                                     const int64_t* ray_of, const float* times, const int64_t* sample_idx,
+                                                     const int32_t* actor_idx, const float* ray_flip, int64_t n_pairs,
+                                                     float* x01, float* cstd, void* stream) {
+  ActorsDev d;
+  if (int e = to_dev(a, d)) return e;
+  if (int e = validate_packed_rays("actor_pair_positions_fwd_packed", rays, false)) return e;
+  NR_REQUIRE(n_pairs >= 0 && a->actor_scale > 0.f, NRHIP_ERR_INVALID_ARG, "actor_pair_positions_fwd_packed: bad argument");
+  if (n_pairs == 0) return NRHIP_OK;
+  NR_REQUIRE(rays->n_rays >= 1 && rays->n_samples >= 1, NRHIP_ERR_INVALID_ARG,
+             "actor_pair_positions_fwd_packed: pairs of a batch without samples");
+  NR_REQUIRE(ray_of && times && sample_idx && actor_idx && x01 && cstd, NRHIP_ERR_INVALID_ARG,
+             "actor_pair_positions_fwd_packed: NULL pointer");
+  actor_pair_positions_kernel<PackedRaysDev><<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
+      d, to_dev(*rays), ray_of, times, sample_idx, actor_idx, ray_flip, n_pairs, x01, cstd);
+  return check_launch("actor_pair_positions_fwd_packed");
+}
+
+extern "C" int nrhip_actor_pair_positions_bwd_packed(const nrhip_actors* a, const nrhip_packed_rays* rays,
+                                                     const int64_t* ray_of, const float* times, const int64_t* sample_idx,
+                                                     const int32_t* actor_idx, const float* ray_flip, int64_t n_pairs,
+                                                     const float* grad_x01, const float* grad_cstd, float* grad_positions,
+                                                     float* grad_rotations_6d, void* stream) {
+  ActorsDev d;
+  if (int e = to_dev(a, d)) return e;
+  if (int e = validate_packed_rays("actor_pair_positions_bwd_packed", rays, false)) return e;
+  NR_REQUIRE(n_pairs >= 0 && a->actor_scale > 0.f, NRHIP_ERR_INVALID_ARG, "actor_pair_positions_bwd_packed: bad argument");
+  if (n_pairs == 0) return NRHIP_OK;
+  NR_REQUIRE(rays->n_rays >= 1 && rays->n_samples >= 1, NRHIP_ERR_INVALID_ARG,
+             "actor_pair_positions_bwd_packed: pairs of a batch without samples");
+  NR_REQUIRE(ray_of && times && sample_idx && actor_idx && grad_x01 && grad_cstd && grad_positions && grad_rotations_6d,
+             NRHIP_ERR_INVALID_ARG, "actor_pair_positions_bwd_packed: NULL pointer");
+  actor_pair_positions_bwd_kernel<PackedRaysDev><<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
+      d, to_dev(*rays), ray_of, times, sample_idx, actor_idx, ray_flip, n_pairs, grad_x01, grad_cstd, grad_positions,
+      grad_rotations_6d, nullptr, nullptr, tuning().pair_bwd_runs ? 1 : 0);
+  return check_launch("actor_pair_positions_bwd_packed");
 }
 
 // ---- the (sample, actor) pairs of a hits table, in order, without torch's nonzero -----------------------------------------

@@ -110,7 +110,9 @@ extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
 // 516: nrhip_encode_bwd_rays_packed: ray gradients through packed samples
 // 517: nrhip_camera_rays_lens (+ nrhip_camera_lens): FISHEYE and lens-distorted cameras
 // 518: nrhip_occgrid_march_levels_actors, nrhip_render_fwd_packed_actors: the occupancy route with dynamic actors (eval)
-extern "C" int nrhip_version(void) { return 518; }
+// 519: training on packed samples of a scene with dynamic actors: nrhip_field_fwd_train_packed_ovr, nrhip_actor_find_packed,
+//      nrhip_actor_pair_positions_fwd_packed / _bwd_packed
+extern "C" int nrhip_version(void) { return 519; }
 
 extern "C" int nrhip_tuning_reload(void) {
   nrhip::g_tuning = nrhip::read_tuning();

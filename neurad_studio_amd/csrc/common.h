@@ -117,6 +117,20 @@ __device__ __forceinline__ int64_t ray_sample_row(const PackedRaysDev& r, int64_
 __device__ __forceinline__ int64_t ray_sample_interval(const PackedRaysDev& r, int64_t ray, int s) {
   return ray_sample_row(r, ray, s);
 }
+// The other way round, for kernels with one thread per SAMPLE: the ray of the sample in row i of a per-sample tensor and
+// the index of its interval.  Dense: the row is ray * S + s.  Packed: ray_of [M] (the march's ray_indices) names the ray
+// and the row is the interval's own index; both are clamped into their arrays, segs is not read.
+__device__ __forceinline__ int64_t ray_sample_ray_of_row(const RaysDev& r, const int64_t*, int64_t i) { return i / r.S; }
+__device__ __forceinline__ int64_t ray_sample_interval_of_row(const RaysDev& r, int64_t ray, int64_t i) {
+  return ray_sample_interval(r, ray, (int)(i - ray * r.S));
+}
+__device__ __forceinline__ int64_t ray_sample_ray_of_row(const PackedRaysDev& r, const int64_t* ray_of, int64_t i) {
+  const int64_t ray = ray_of[i < 0 ? 0 : (i < (int64_t)r.M ? i : (int64_t)r.M - 1)];
+  return ray < 0 ? 0 : (ray < r.R ? ray : r.R - 1);
+}
+__device__ __forceinline__ int64_t ray_sample_interval_of_row(const PackedRaysDev& r, int64_t, int64_t i) {
+  return i < 0 ? 0 : (i < (int64_t)r.M ? i : (int64_t)r.M - 1);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Table element loads: F features of one entry, fp32 or fp16 storage, one vector load each.

@@ -47,6 +47,9 @@
 //   * PACKED SAMPLES WITH ACTORS (Lay::PackedActors instantiations, eval: nrhip_render_fwd_packed_actors): the two above
 //     together -- the pending tile of a packed ray also carries the ray's candidate count, the candidate walk is the dense actor
 //     kernel's, the compositing the packed kernel's.  One candidate list per RAY; nothing is sized by the sample count.
+//   * PACKED ROWS WITH OVERRIDES (Lay::PackedRowsOvr instantiations, training: nrhip_field_fwd_train_packed_ovr): the
+//     per-sample packed kernel of a scene with dynamic actors -- a sample whose entry of ovr_row [M] (read at the packed
+//     sample index) is >= 0 takes its encoding row and view direction from the caller, as in the dense Overrides kernels.
 // The sky residual (models/neurad.py:381: w_{S-1} += 1 - sum w) is folded into the last tile -- the accumulated weight is
 // complete there, so no copy of the last sample's features has to be kept.
 #include "common.h"
@@ -782,6 +785,9 @@ __device__ __forceinline__ void blend_tile(const TileFetch<EncFrame<L, F>::LPL, 
 // Src::Actors: `tables` is the actors' own, the segments come through `sv.enc`.  A lane past its ray's end holds the ray's
 // last sample (load_pending_packed), so it walks the candidate list like a live lane and weighs nothing; the candidate
 // row index is ray * K with ray < R, the slot < cand_count[ray] <= K: inside [0, R K), as in the dense actor kernel.
+// Lay::PackedRowsOvr is Lay::PackedRows with Src::Overrides: the two features' argument slots do not collide (overrides in
+// `cand_count` / `cand_w2b` / `bounds`, segments in `tables`), and ovr_row [M] is read at the packed sample index of a live
+// lane only -- inside [0, M).
 template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD, Lay LAY = Lay::Dense>
 __global__ __launch_bounds__(256, 2) void render_kernel(
     FieldDev fd, int64_t n_rays, int S, int stride, const int32_t* __restrict__ order, const float* __restrict__ ro,
@@ -871,7 +877,9 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
   if constexpr (PACKED) cb = qb, cn = qn;
   if constexpr (ACT) issue_tile_actors<L, F, HALF>(fd, ad, q, g, mask, scal_l, ascal_l, cand_actor, cand_w2b, bounds, tables, tf, ta);
   else issue_tile<L, F, HALF, RELAY>(fd, q, g, mask, scal_l, tf, lay_l);
-  if constexpr (OVR) ta = (q.valid && j < S) ? ovr_row[q.ray * S + j] : -1;  // override row of this lane's sample of `tf`
+  // override row of this lane's sample of `tf` (PACKED: at the packed sample index; q's segment is still qb / qn here)
+  if constexpr (OVR && PACKED) ta = (q.valid && j < qn && qb + j >= 0 && qb + j < S) ? ovr_row[qb + j] : -1;
+  else if constexpr (OVR) ta = (q.valid && j < S) ? ovr_row[q.ray * S + j] : -1;
   {
     const bool wrap = (PACKED ? tiles_of(cn) : ntile) == 1;
     if constexpr (PACKED) load_pending_packed(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
@@ -996,7 +1004,12 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     // unconditional (see load_pending)
     if constexpr (ACT) issue_tile_actors<L, F, HALF>(fd, ad, q, g, mask, scal_l, ascal_l, cand_actor, cand_w2b, bounds, tables, tf, ta);
     else issue_tile<L, F, HALF, RELAY>(fd, q, g, mask, scal_l, tf, lay_l);
-    if constexpr (OVR) ta = (q.valid && 16 * q.t + j < S) ? ovr_row[q.ray * S + 16 * q.t + j] : -1;
+    if constexpr (OVR && PACKED) {
+      const int s2 = 16 * q.t + j;
+      ta = (q.valid && s2 < qn && qb + s2 >= 0 && qb + s2 < S) ? ovr_row[qb + s2] : -1;
+    } else if constexpr (OVR) {
+      ta = (q.valid && 16 * q.t + j < S) ? ovr_row[q.ray * S + 16 * q.t + j] : -1;
+    }
     {
       const bool wrap = nt + 1 == (PACKED ? tiles_of(nn) : ntile);  // request the small loads of the tile after it
       if constexpr (PACKED)
@@ -1341,7 +1354,8 @@ struct RenderArgs {
 
 template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD, Lay LAY = Lay::Dense>
 static int launch_render(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
-  constexpr bool OVR = SRC == Src::Overrides, PACKED = LAY == Lay::Packed || LAY == Lay::PackedRows;
+  constexpr bool OVR = SRC == Src::Overrides;
+  constexpr bool PACKED = LAY == Lay::Packed || LAY == Lay::PackedRows || LAY == Lay::PackedRowsOvr;
   constexpr size_t lds = ((SRC == Src::Actors || OVR) ? Lds<H, PROD>::TOTAL_ACT : Lds<H, PROD>::TOTAL) * sizeof(float);
   auto kern = render_kernel<L, F, H, HALF, OUT, SRC, PROD, LAY>;
   static int cap = 0;  // persistent grid: CUs x resident workgroups per CU, queried once per instantiation
@@ -1477,6 +1491,31 @@ static int dispatch_render_packed_actors(const nrhip_field* f, const RaysDev& rd
   NRHIP_RENDER_VARIANTS(X)
 #undef X
   set_error("fused field kernel with actors: no instantiation for L=%d F=%d H=%d", v.L, v.F, v.H);
+  return NRHIP_ERR_UNSUPPORTED;
+}
+
+// The packed form of a `PerSample, Overrides, F32` row (Lay::PackedRowsOvr; no rows of its own either)
+template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD>
+static int launch_packed_ovr_row(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
+  if constexpr (render_variant_ok(L, F, OUT, SRC, PROD, Lay::PackedRowsOvr)) {
+    return launch_render<L, F, H, HALF, OUT, SRC, PROD, Lay::PackedRowsOvr>(fd, rd, a);
+  } else {
+    set_error("field_fwd_train_packed_ovr: no packed form of this variant");
+    return NRHIP_ERR_UNSUPPORTED;
+  }
+}
+
+static int dispatch_render_packed_ovr(const nrhip_field* f, const RaysDev& rd, const RenderArgs& a) {
+  const Variant v = choose_variant(f, Out::PerSample, Src::Overrides);
+  const FieldDev fd = to_dev(*f);
+  const bool half = f->grid.param_dtype == 1;
+#define X(L_, F_, H_, O_, S_, P_)                                                                    \
+  if (same(v, {L_, F_, H_, Out::O_, Src::S_, Prod::P_}))                                             \
+    return half ? launch_packed_ovr_row<L_, F_, H_, true, Out::O_, Src::S_, Prod::P_>(fd, rd, a)     \
+                : launch_packed_ovr_row<L_, F_, H_, false, Out::O_, Src::S_, Prod::P_>(fd, rd, a);
+  NRHIP_RENDER_VARIANTS(X)
+#undef X
+  set_error("field_fwd_train_packed_ovr: no instantiation for L=%d F=%d H=%d", v.L, v.F, v.H);
   return NRHIP_ERR_UNSUPPORTED;
 }
 
@@ -1638,6 +1677,27 @@ extern "C" int nrhip_field_fwd_train_packed(const nrhip_field* f, const nrhip_pa
   a.sv = SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
   if (int e = check_train_buffers("field_fwd_train_packed", feature, geo_out, head, a.sv)) return e;
   return dispatch_render_packed(f, Out::PerSample, packed_launch_rays(*rays), a);
+}
+
+extern "C" int nrhip_field_fwd_train_packed_ovr(const nrhip_field* f, const nrhip_packed_rays* rays,
+                                                const int32_t* ovr_row, const float* ovr_rows, const float* ovr_dirs,
+                                                float* feature, float* geo_out, float* head, float* save_enc,
+                                                float* save_geo_hidden, float* save_feat_in, float* save_feat_hidden,
+                                                void* stream) {
+  if (int e = validate_field(f)) return e;
+  if (int e = validate_packed_rays("field_fwd_train_packed_ovr", rays, true)) return e;
+  if (rays->n_rays == 0 || rays->n_samples == 0) return NRHIP_OK;  // nothing per sample to write: no pointer is read
+  RenderArgs a{};
+  a.feat = feature, a.sdf = geo_out, a.alpha = head, a.stream = (hipStream_t)stream, a.segments = rays->segments;
+  a.sv = SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
+  a.ovr = OverrideLaunch{ovr_row, ovr_rows, ovr_dirs};
+  if (int e = check_train_buffers("field_fwd_train_packed_ovr", feature, geo_out, head, a.sv)) return e;
+  NR_REQUIRE(ovr_row && ovr_rows && ovr_dirs, NRHIP_ERR_INVALID_ARG, "field_fwd_train_packed_ovr: NULL pointer");
+  NR_REQUIRE((reinterpret_cast<uintptr_t>(ovr_rows) & 15) == 0, NRHIP_ERR_INVALID_ARG,
+             "field_fwd_train_packed_ovr: override rows must be 16-byte aligned");
+  NR_REQUIRE(f->grid.param_dtype == 0 || f->grid.param_dtype == 1, NRHIP_ERR_INVALID_ARG,
+             "field_fwd_train_packed_ovr: dtype");
+  return dispatch_render_packed_ovr(f, packed_launch_rays(*rays), a);
 }
 
 extern "C" int nrhip_render_fwd_actors(const nrhip_field* f, const nrhip_actors* a, const nrhip_rays* rays,

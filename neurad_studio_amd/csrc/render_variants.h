@@ -31,6 +31,7 @@ enum class Lay {
   Packed,  // [M] + segments [R + 1]: ray r owns the samples [segments[r], segments[r + 1]) (the occupancy march's output)
   PackedRows,  // the same addressing for the per-sample kernel: every output and saved row at the packed sample index
   PackedActors,  // Packed for a scene with dynamic actors: the composited kernel with the per-sample table select
+  PackedRowsOvr,  // PackedRows with row overrides: the packed training forward of a scene with dynamic actors
 };
 
 // The legal mixes, asserted by the kernel for every instantiation.
@@ -43,6 +44,9 @@ constexpr bool render_variant_ok(int L, int F, Out out, Src src, Prod prod, Lay 
   // ... and the composited actor kernel, fp32 products: every `Composite, Actors, F32` row, derived the same way
   // (render.hip: dispatch_render_packed_actors)
   if (lay == Lay::PackedActors && !(out == Out::Composite && src == Src::Actors && prod == Prod::F32)) return false;
+  // ... and the per-sample kernel with row overrides, fp32 products: every `PerSample, Overrides, F32` row, derived the
+  // same way (render.hip: dispatch_render_packed_ovr)
+  if (lay == Lay::PackedRowsOvr && !(out == Out::PerSample && src == Src::Overrides && prod == Prod::F32)) return false;
   // actors (static and actor tables share one storage type) and the eval-table layout: the composited eval kernel
   if ((src == Src::Actors || src == Src::EvalTable) && out != Out::Composite) return false;
   // row overrides: the per-sample training forward
@@ -61,8 +65,8 @@ constexpr bool render_variant_ok(int L, int F, Out out, Src src, Prod prod, Lay 
 
 // X(L, F, H, output, source, products): one line per instantiation; every line exists for fp32 and fp16 tables, and every
 // `Composite, Static` line with `F32` or `F16Pairs` products for dense and packed samples, every `PerSample, Static, F32`
-// line for dense samples and packed rows, every `Composite, Actors, F32` line for dense and packed samples
-// (render_variant_ok).
+// line for dense samples and packed rows, every `Composite, Actors, F32` line for dense and packed samples, every
+// `PerSample, Overrides, F32` line for dense samples and packed rows (render_variant_ok).
 // L * F == 32 (L = 16, 8, 4) fills the kernel's encoding frame; the smaller grids live in the padded frame (EncFrame):
 // BASELINE config[0]'s 1 x 4, NeuRAD tiny's 4 x 2, and the L * F == 16 grids 4 x 4 and 8 x 2 -- fp32 products only.
 #define NRHIP_RENDER_VARIANTS(X)        \

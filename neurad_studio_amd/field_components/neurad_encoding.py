@@ -222,12 +222,15 @@ class NeuRADHashEncoding(nn.Module):
         return any(gr.hash_table.requires_grad for gr in self.actor_grids) or (
             self.config.require_actor_grad and self.actors.actor_positions.requires_grad)
 
-    def actor_pair_rows(self, hit, hits, origins, directions, pixel_area, starts, ends, times, flip):
+    def actor_pair_rows(self, hit, hits, origins, directions, pixel_area, starts, ends, times, flip, ray_indices=None):
         """Training path of the actor rows (B1): the kernels found WHICH samples lie in WHICH actor; the few hit rows
         are recomputed differentiably -- box-frame position through nrhip_actor_pair_positions_fwd/bwd (gradient to the
         trajectories when ``require_actor_grad``), the actor grids through MultiHashGridFn (table scatter-add, and
         nrhip_hashgrid_bwd_input for dL/dx).  -> None, or (idx [P] flat sample index, winner [P] bool: the actor the
-        forward kernels used for that sample (highest index), rows [P, La*Fa] rescaled actor features)."""
+        forward kernels used for that sample (highest index), rows [P, La*Fa] rescaled actor features).
+        ``ray_indices`` int64 [M]: the samples are PACKED (an occupancy march's output) -- starts / ends are t_starts /
+        t_ends [M], hit [M] and hits [M,8] and the returned idx are at the packed sample index, times [R] and flip [R] stay
+        per ray (nrhip_actor_pair_positions_fwd_packed / _bwd_packed); everything else is the same."""
         if self.actor_edit() is not None:
             # the differentiable rows are recomputed from the trajectories themselves (nrhip_actor_pair_positions_*), which
             # know nothing of the edit; the reference edits for rendering only (pipelines/ad_pipeline.py:476-480)
@@ -242,9 +245,14 @@ class NeuRADHashEncoding(nn.Module):
         spec = self.actor_spec()
         pose_grad = torch.is_grad_enabled() and self.config.require_actor_grad
         with torch.set_grad_enabled(pose_grad):
-            x01, cstd = ag.ActorPairPositionsFn.apply(self.actors.actor_positions, self.actors.actor_rotations_6d, spec,
-                                                      origins, directions, pixel_area.reshape(-1), starts, ends, times, idx,
-                                                      act, flip)
+            if ray_indices is None:
+                x01, cstd = ag.ActorPairPositionsFn.apply(self.actors.actor_positions, self.actors.actor_rotations_6d, spec,
+                                                          origins, directions, pixel_area.reshape(-1), starts, ends, times,
+                                                          idx, act, flip)
+            else:
+                x01, cstd = ag.ActorPairPositionsPackedFn.apply(
+                    self.actors.actor_positions, self.actors.actor_rotations_6d, spec, origins, directions,
+                    pixel_area.reshape(-1), starts, ends, ray_indices, times, idx, act, flip)
         act = act.long()
         ids = self.actors.actor_to_id[act]
         # _get_actor_features_slow loops over the actor ids; all actor grids share one shape, so one multi-grid

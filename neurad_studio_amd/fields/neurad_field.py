@@ -273,7 +273,7 @@ class NeuRADField(nn.Module):
 
     def render_train_packed(self, origins, directions, pixel_area, t_starts, t_ends, *, segments: Optional[Tensor] = None,
                             ray_indices: Optional[Tensor] = None, num_rays: Optional[int] = None,
-                            ray_gradients: bool = False):
+                            ray_gradients: bool = False, times: Optional[Tensor] = None, actor_cand=None):
         """Training counterpart of ``render_packed``: field -> head (learnable-beta SDF head, or trunc_exp) -> packed
         compositing as ONE autograd node (autograd.NffRenderPackedTrainFn).  Arguments as ``render_packed``: per-RAY origins
         / directions [R,3] and pixel_area [R] (or [R,1]), per-sample t_starts / t_ends [M], exactly one of ``segments`` int64
@@ -282,19 +282,43 @@ class NeuRADField(nn.Module):
         renderers.render_packed.  Gradients reach the table, the MLPs and beta.  Rays that require grad (a camera optimizer
         moved them) are refused by default, as before; ``ray_gradients=True`` opts in: the node then also returns dL/d origins
         and dL/d directions through the static encoding (nrhip_encode_bwd_rays_packed: one launch, no atomics, bit-reproducible;
-        t_starts / t_ends stay constants of the march).  With fixed rays the flag changes nothing."""
+        t_starts / t_ends stay constants of the march).  With fixed rays the flag changes nothing.
+
+        Dynamic actors (``fused_packed_actors_train_supported``): ``times`` [R], the rays' times -- with ``actor_cand``, the
+        per-RAY candidate lists already computed (``hashgrid.prepare_actors_line``; a march with boxes shares them), they
+        are not computed again; ``actor_cand`` alone is a ValueError, the pair positions need the times -- select
+        the node with row overrides (autograd.NffRenderPackedActorsTrainFn), built as ``render_train`` builds it on dense
+        samples: the kernels find which packed samples lie in which box (ops.actor_find_packed), ``actor_pair_rows``
+        produces their rows differentiably, and the fused forward takes them and their box-frame view directions in place
+        of the static lookup.  Gradients then also reach the actor grids and, with ``require_actor_grad``, the
+        trajectories.  If no sample lies in a box the call is the static node, bit for bit.  The training x-flip is drawn
+        once per RAY (``sample_ray_flip``: R draws), as the dense node draws it; the operator route on packed samples draws
+        it per sample, so for 0 < flip_prob < 1 the two routes flip different samples by design.  With actors, rays that
+        require grad are refused even under ``ray_gradients=True``: the actor branch's ray gradient is not built on packed
+        samples.  Without ``times`` / ``actor_cand`` an actor field is refused as before.  One host read (the number of
+        pairs): not graph-capturable, like the dense actor node."""
         if (segments is None) == (ray_indices is None):
             raise ValueError("render_train_packed: give exactly one of segments / ray_indices (+ num_rays)")
         if ray_indices is not None and num_rays is None:
             raise ValueError("render_train_packed: ray_indices needs num_rays")
         operator = "use the operator route, forward() on the packed RaySamples + renderers.render_packed"
-        if self.hashgrid.has_actors():
-            raise NotImplementedError(f"render_train_packed: the occupancy route is static, no dynamic actors; {operator}")
-        if not self.fused_packed_train_supported():
-            raise NotImplementedError(f"render_train_packed: a fused-kernel configuration only (see fused_supported); {operator}")
-        if not ray_gradients and torch.is_grad_enabled() and (origins.requires_grad or directions.requires_grad):
-            raise NotImplementedError(f"render_train_packed: no gradient reaches the rays through packed samples; {operator}")
         hg, g = self.hashgrid, self.hashgrid.static_grid
+        with_actors = hg.has_actors() and (times is not None or actor_cand is not None)
+        if with_actors:
+            if not self.fused_packed_actors_train_supported():
+                raise NotImplementedError(f"render_train_packed with dynamic actors: a fused-kernel configuration with "
+                                          f"actors only (see fused_packed_actors_train_supported); {operator}")
+            if torch.is_grad_enabled() and (origins.requires_grad or directions.requires_grad):
+                raise NotImplementedError(f"render_train_packed with dynamic actors: no gradient reaches the rays through the "
+                                          f"actor branch on packed samples; {operator}")
+        else:
+            if hg.has_actors():
+                raise NotImplementedError(f"render_train_packed: the occupancy route is static, no dynamic actors (pass the "
+                                          f"rays' times for the node with actors); {operator}")
+            if not self.fused_packed_train_supported():
+                raise NotImplementedError(f"render_train_packed: a fused-kernel configuration only (see fused_supported); {operator}")
+            if not ray_gradients and torch.is_grad_enabled() and (origins.requires_grad or directions.requires_grad):
+                raise NotImplementedError(f"render_train_packed: no gradient reaches the rays through packed samples; {operator}")
         t_starts, t_ends = t_starts.reshape(-1), t_ends.reshape(-1)
         with torch.no_grad():
             if segments is None:
@@ -303,11 +327,52 @@ class NeuRADField(nn.Module):
                 ray_indices = ops.packed_ray_indices(segments, t_starts.shape[0])
             order = ops.ray_order(origins, directions, hg.static_scale) if (self.order_rays and origins.shape[0]) else None
         beta, beta_min = (self.sdf_to_density.beta, self.sdf_to_density.beta_min_value) if self.config.use_sdf else (None, 0.0)
-        return ag.NffRenderPackedTrainFn.apply(
-            g.hash_table, g.spec, hg.static_scale, beta, beta_min, origins, directions, pixel_area.reshape(-1), t_starts,
-            t_ends, segments, ray_indices.reshape(-1), order,
-            *[t for l in self.mlp_geo.layers for t in (l.weight, l.bias)],
-            *[t for l in self.mlp_feature.layers for t in (l.weight, l.bias)])
+        head = (g.hash_table, g.spec, hg.static_scale, beta, beta_min, origins, directions, pixel_area.reshape(-1), t_starts,
+                t_ends, segments, ray_indices.reshape(-1), order)
+        params = [t for l in self.mlp_geo.layers for t in (l.weight, l.bias)] + \
+                 [t for l in self.mlp_feature.layers for t in (l.weight, l.bias)]
+        if with_actors and t_starts.shape[0] and origins.shape[0]:
+            ovr = self._actor_overrides_packed(origins, directions, pixel_area.reshape(-1), t_starts, t_ends,
+                                               ray_indices.reshape(-1), None if times is None else times.reshape(-1),
+                                               actor_cand)
+            if ovr is not None:
+                return ag.NffRenderPackedActorsTrainFn.apply(*head, *ovr, *params)
+        return ag.NffRenderPackedTrainFn.apply(*head, *params)
+
+    def fused_packed_actors_train_supported(self) -> bool:
+        """Can ``render_train_packed(..., times=...)`` train this field's scene WITH its dynamic actors on PACKED samples as
+        one node?  ``fused_packed_actors_supported`` (an actor field of a fused configuration: the packed override kernels
+        are the table's `PerSample, Overrides, F32` rows) with the fused training forward's own condition (biases)."""
+        return self.fused_packed_actors_supported() and self._fused_train_ok()
+
+    def _actor_overrides_packed(self, origins, directions, pixel_area, t_starts, t_ends, ray_indices, times, actor_cand=None):
+        """``_actor_overrides`` on packed samples -> (ovr_row int32 [M], rows [P,L*F], box-frame view directions [P,3],
+        pair_idx [P]: packed sample index of every (sample, actor) pair), or None when no sample lies in a box.  No [M, L*F]
+        scratch rows: the geometry kernel writes none."""
+        hg = self.hashgrid
+        M = t_starts.shape[0]
+        if times is None:  # (actor_cand alone fixes the boxes, not the pair positions' poses)
+            raise ValueError("dynamic actors need ray times (the pair positions are interpolated at the ray's time)")
+        flip = hg.sample_ray_flip(origins)  # one draw per ray, as the dense node
+        with torch.no_grad():
+            if actor_cand is not None:
+                spec, cand = hg.actor_spec(), actor_cand
+            else:
+                spec, cand = hg.prepare_actors_line(origins, directions, 0.0, 1.0, times)
+            hits, hit, dirs = ops.actor_find_packed(spec, cand, origins, directions, pixel_area, t_starts, t_ends,
+                                                    ray_indices, flip)
+        pr =hg.actor_pair_rows(hit, hits, origins, directions, pixel_area, t_starts, t_ends, times, flip,
+                                ray_indices=ray_indices)
+        if pr is None:
+            return None
+        idx, winner, f = pr
+        rows = torch.nn.functional.pad(f, (0, hg.get_out_dim() - f.shape[1])).contiguous()
+        with torch.no_grad():
+            P = idx.shape[0]
+            slot = torch.where(winner, torch.arange(P, device=idx.device), -1)  # one winner per sample: amax picks it
+            ov = torch.full((M,), -1, device=idx.device, dtype=torch.int64).scatter_reduce_(0, idx, slot, reduce="amax")
+            pdirs = dirs.index_select(0, idx).contiguous()
+        return ov.to(torch.int32), rows, pdirs, idx
 
     def render_train(self, origins, directions, pixel_area, edges, appearance=None, times: Optional[Tensor] = None,
                      actor_cand=None):

@@ -320,7 +320,8 @@ class VolumetricSampler(Sampler):
 
     def render_train(self, field, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0,
                      far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0,
-                     fused_ray_gradients: bool = False, actor_boxes: bool = False) -> dict:
+                     fused_ray_gradients: bool = False, actor_boxes: bool = False,
+                     fused_actor_training: bool = False) -> dict:
         """Training counterpart of ``render``: a stratified march + field + compositing with autograd -> the same keys.  A
         field that trains on packed samples as one node (``fused_packed_train_supported``, ``fused_training`` on) gets the
         BUNDLE'S per-ray tensors and the packed intervals (``render_train_packed``: no per-sample copy of origins /
@@ -328,14 +329,24 @@ class VolumetricSampler(Sampler):
         False`` and, by default, rays that require grad take forward() on the gathered RaySamples + renderers.render_packed.
         ``fused_ray_gradients=True`` keeps rays that require grad (a camera optimizer) on the node, which then returns their
         gradients itself (``render_train_packed(..., ray_gradients=True)``); same keys, same shapes.  A march without samples
-        returns zero rows.  actor_boxes=True (a field with dynamic actors, a bundle with times): the box-aware march; the
-        field then trains on its samples on the operator route (there is no fused training node with actors)."""
+        returns zero rows.  actor_boxes=True (a field with dynamic actors, a bundle with times): the box-aware march; by
+        default the field then trains on its samples on the operator route.  ``fused_actor_training=True`` (opt-in, default
+        off) with ``actor_boxes=True`` hands the march's candidate lists on to the fused training node with actors
+        (``render_train_packed(..., times=..., actor_cand=...)``: one computation serves march and node) when the field has
+        one (``fused_packed_actors_train_supported``), ``fused_training`` is on and the rays are fixed; anything else takes
+        the operator route as before.  The node draws the training x-flip once per ray, the operator route once per sample."""
         R = ray_bundle.origins.shape[0]
         boxes = self._actor_boxes(field, ray_bundle) if actor_boxes else None
         rays_o, rays_d, ri, starts, ends = self._march(ray_bundle, render_step_size, near_plane, far_plane, alpha_thre,
                                                        cone_angle, stratified=True, actor_boxes=boxes)
         marched = {"ray_indices": ri, "t_starts": starts, "t_ends": ends}
         rays_need_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+        if (fused_actor_training and boxes is not None and getattr(field, "fused_training", False) and not rays_need_grad
+                and getattr(field, "fused_packed_actors_train_supported", lambda: False)()):
+            f, d, a, w = field.render_train_packed(rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri,
+                                                   num_rays=R, times=ray_bundle.times.reshape(-1).float(),
+                                                   actor_cand=boxes[1])
+            return {"features": f, "depth": d, "accumulation": a, "weights": w[:, None], **marched}
         if (getattr(field, "fused_training", False) and (fused_ray_gradients or not rays_need_grad)
                 and getattr(field, "fused_packed_train_supported", lambda: False)()):
             kw = {"ray_gradients": True} if rays_need_grad else {}

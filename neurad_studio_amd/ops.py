@@ -1512,10 +1512,12 @@ def render_fwd_packed_actors(fs: FieldSpec, spec: "ActorSpec", cand, origins, di
 
 
 def field_fwd_train_packed(fs: FieldSpec, origins, directions, pixel_area, t_starts, t_ends, segments,
-                           order: Optional[Tensor] = None, out=None):
+                           order: Optional[Tensor] = None, out=None, override=None):
     """``field_fwd_train`` on the march's packed samples (ray constants per RAY, every row at the packed sample index):
     -> (feature [M,32], geo_out [M], head [M]), (enc [M,L*F], geo_hidden [M,H], feat_in [M,48], feat_hidden [M,2H]).
-    ``out``: the seven buffers to write into (rows past M are left alone)."""
+    ``out``: the seven buffers to write into (rows past M are left alone).
+    override = (ovr_row int32 [M] (row index or -1, at the packed sample index), ovr_rows [P,L*F], ovr_dirs [P,3]): as
+    ``field_fwd_train`` (nrhip_field_fwd_train_packed_ovr)."""
     r, keep = _c_packed_rays("field_fwd_train_packed", origins, directions, pixel_area, t_starts, t_ends, segments, order)
     f, keep2 = fs.c_field()
     m, dev = r.n_samples, keep[0].device
@@ -1528,8 +1530,86 @@ def field_fwd_train_packed(fs: FieldSpec, origins, directions, pixel_area, t_sta
         out = tuple(_chk(t, "out") for t in out)
         if len(out) != 7 or any(t.shape[0] < m or (t.shape[1:] != ((w,) if w else ())) for t, w in zip(out, widths)):
             raise ValueError("field_fwd_train_packed: out = (feature, geo_out, head, enc, geo_hidden, feat_in, feat_hidden)")
-    launch("nrhip_field_fwd_train_packed", f, r, *out)
+    if override is not None:
+        ov, rows, dirs = override
+        ov, rows, dirs = _chk(ov.reshape(-1), "ovr_row", torch.int32), _chk(rows, "ovr_rows"), _chk(dirs, "ovr_dirs")
+        if ov.shape[0] != m or rows.dim() != 2 or rows.shape[1] != LF or dirs.shape != (rows.shape[0], 3):
+            raise ValueError(f"field_fwd_train_packed: override = (int32 [M], [P,{LF}], [P,3])")
+        launch("nrhip_field_fwd_train_packed_ovr", f, r, ov, rows, dirs, *out)
+    else:
+        launch("nrhip_field_fwd_train_packed", f, r, *out)
     return out[:3], out[3:]
+
+
+def _packed_ray_of(who: str, r, ray_indices: Tensor) -> Tensor:
+    """the march's ray_indices for the packed descriptor ``r``: int64 [M], one per sample"""
+    ri = _chk(ray_indices.reshape(-1), "ray_indices", torch.int64)
+    if ri.shape[0] != r.n_samples:
+        raise ValueError(f"{who}: ray_indices has {ri.shape[0]} entries, expected one per sample ({r.n_samples})")
+    return ri
+
+
+def actor_find_packed(spec: "ActorSpec", cand, origins, directions, pixel_area, t_starts, t_ends, ray_indices,
+                      ray_flip: Optional[Tensor] = None):
+    """``actor_hits`` and the geometry of ``actor_encode`` on packed samples, in one pass and without feature rows: cand = one
+    candidate list per RAY, ray_indices int64 [M] names each sample's ray, ray_flip [R] +-1 or None.
+    -> (hits [M,8] int32, hit [M] int32: the winning actor or -1, directions [M,3]: box frame where hit, else the ray's)"""
+    r, keep = _c_packed_rays("actor_find_packed", origins, directions, pixel_area, t_starts, t_ends)
+    a, keep2 = spec.c_actors()
+    ri = _packed_ray_of("actor_find_packed", r, ray_indices)
+    R, m, dev = r.n_rays, r.n_samples, keep[0].device
+    cnt, act, w2b = (_chk(cand[0], "cand_count", torch.int32), _chk(cand[1], "cand_actor", torch.int32),
+                     _chk(cand[2], "cand_w2b"))
+    if cnt.shape != (R,) or act.shape != (R, a.max_candidates) or w2b.shape != (R, a.max_candidates, 12):
+        raise ValueError(f"actor_find_packed: candidate lists must be [R], [R,K], [R,K,12] with R = {R}, K = "
+                         f"{a.max_candidates}: one list per ray")
+    flip = _opt(ray_flip, "ray_flip")
+    if flip is not None and flip.shape[0] != R:
+        raise ValueError(f"actor_find_packed: ray_flip is per ray, [R = {R}]")
+    hits = torch.empty((m, _lib.MAX_SAMPLE_CONTAINMENTS), dtype=torch.int32, device=dev)
+    hit = torch.empty((m,), dtype=torch.int32, device=dev)
+    dirs = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    launch("nrhip_actor_find_packed", a, r, ri, cnt, act, w2b, hits, hit, dirs, flip)
+    return hits, hit, dirs
+
+
+def _packed_pair_args(who: str, spec: "ActorSpec", origins, directions, pixel_area, t_starts, t_ends, ray_indices, times,
+                      sample_idx, actor_idx, ray_flip):
+    r, keep = _c_packed_rays(who, origins, directions, pixel_area, t_starts, t_ends)
+    a, keep2 = spec.c_actors()
+    ri = _packed_ray_of(who, r, ray_indices)
+    si, ai = _chk(sample_idx, "sample_idx", torch.int64), _chk(actor_idx, "actor_idx", torch.int32)
+    t, flip = _chk(times.reshape(-1), "times"), _opt(ray_flip, "ray_flip")
+    if t.shape[0] != r.n_rays or (flip is not None and flip.shape[0] != r.n_rays) or ai.shape != si.shape:
+        raise ValueError(f"{who}: times / ray_flip are per ray ([R = {r.n_rays}]), sample_idx / actor_idx [P]")
+    return a, r, ri, t, si, ai, flip
+
+
+def actor_pair_positions_packed(spec: "ActorSpec", origins, directions, pixel_area, t_starts, t_ends, ray_indices, times,
+                                sample_idx: Tensor, actor_idx: Tensor, ray_flip: Optional[Tensor] = None):
+    """``actor_pair_positions`` on packed samples: sample_idx [P] int64 is a packed sample index, ray_indices int64 [M] names
+    each sample's ray, times / ray_flip are per ray.  -> (x01 [P,3], cstd [P])"""
+    a, r, ri, t, si, ai, flip = _packed_pair_args("actor_pair_positions_packed", spec, origins, directions, pixel_area,
+                                                  t_starts, t_ends, ray_indices, times, sample_idx, actor_idx, ray_flip)
+    P_ = si.shape[0]
+    x01 = torch.empty((P_, 3), dtype=torch.float32, device=si.device)
+    cstd = torch.empty((P_,), dtype=torch.float32, device=si.device)
+    launch("nrhip_actor_pair_positions_fwd_packed", a, r, ri, t, si, ai, flip, P_, x01, cstd)
+    return x01, cstd
+
+
+def actor_pair_positions_packed_bwd(spec: "ActorSpec", origins, directions, pixel_area, t_starts, t_ends, ray_indices, times,
+                                    sample_idx, actor_idx, ray_flip, grad_x01: Tensor, grad_cstd: Tensor):
+    """-> (grad actor_positions [Tn,A,3], grad actor_rotations_6d [Tn,A,6]), accumulated with atomics as
+    ``actor_pair_positions_bwd``; the rays get no gradient on this path"""
+    a, r, ri, t, si, ai, flip = _packed_pair_args("actor_pair_positions_packed_bwd", spec, origins, directions, pixel_area,
+                                                  t_starts, t_ends, ray_indices, times, sample_idx, actor_idx, ray_flip)
+    flat = torch.zeros((a.n_times * a.n_actors * 9,), dtype=torch.float32, device=si.device)
+    gp = flat[: a.n_times * a.n_actors * 3].view(a.n_times, a.n_actors, 3)
+    gr = flat[a.n_times * a.n_actors * 3:].view(a.n_times, a.n_actors, 6)
+    launch("nrhip_actor_pair_positions_bwd_packed", a, r, ri, t, si, ai, flip, si.shape[0], _chk(grad_x01, "grad_x01"),
+           _chk(grad_cstd, "grad_cstd"), gp, gr)
+    return gp, gr
 
 
 def sdf_render_packed_fwd(geo_out, beta: Optional[Tensor], beta_min: float, features, t_starts, t_ends, segments):

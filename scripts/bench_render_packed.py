@@ -82,11 +82,11 @@ def street(n_per_row=12):
     return out
 
 
-def main_actors(args):
-    from bench import device_state
+def actor_scene():
+    """The street scene of --actors (scripts/bench_render_train_packed.py --actors trains on the same samples): the field in
+    eval mode, its actors, the grid's binaries, the rays, their candidate lists and the box-aware march's packed samples"""
     from neurad_studio_amd.model_components.dynamic_actors import DynamicActors, DynamicActorsConfig
 
-    clocks = device_state(0)
     gen = torch.Generator().manual_seed(0)
     L, F, H, base, max_res = FIELDS["neurad_default_8x4_h32"]
     cfg = NeuRADFieldConfig(geo_hidden_dim=H, nff_hidden_dim=H)
@@ -99,7 +99,6 @@ def main_actors(args):
         for t in [fld.hashgrid.static_grid.hash_table] + [g.hash_table for g in fld.hashgrid.actor_grids]:
             t.copy_(((torch.rand(t.shape, generator=gen) * 2 - 1) * 0.5).to(t.device))
     assert fld.fused_packed_actors_supported()
-    A = int(actors.n_actors)
     binaries = torch.rand((RES, RES, RES), generator=gen) < 0.3
     centres = (torch.arange(RES) + 0.5) * (8.0 / RES) - 4.0
     cx, cy, cz = torch.meshgrid(centres, centres, centres, indexing="ij")
@@ -116,6 +115,20 @@ def main_actors(args):
     spec, cand = fld.hashgrid.prepare_actors_line(o, d, 0.0, 1.0, times)
     plain_m = int(ops.occgrid_march(grid, o, d, STEP)[0].shape[0])
     ri, ts, te, seg = ops.occgrid_march(grid, o, d, STEP, actor_boxes=(spec, cand))
+    return dict(cfg=cfg, fld=fld, actors=actors, binaries=binaries, o=o, d=d, area=area, times=times, cand=cand,
+                plain_m=plain_m, ri=ri, ts=ts, te=te, seg=seg, gen=gen)
+
+
+def main_actors(args):
+    from bench import device_state
+
+    clocks = device_state(0)
+    sc = actor_scene()
+    L, F, H, _, _ = FIELDS["neurad_default_8x4_h32"]
+    cfg, fld, actors, binaries, o, d, area, times, cand = (sc[k] for k in ("cfg", "fld", "actors", "binaries", "o", "d", "area",
+                                                                            "times", "cand"))
+    plain_m, ri, ts, te, seg = (sc[k] for k in ("plain_m", "ri", "ts", "te", "seg"))
+    A = int(actors.n_actors)
     M = int(ri.shape[0])
     counts = (seg[1:] - seg[:-1]).cpu().numpy()
     rb = RayBundle(origins=o, directions=d, pixel_area=area, times=times[:, None])

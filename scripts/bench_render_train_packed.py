@@ -13,7 +13,16 @@ of (a) against (b) on outputs and gradients) to profiles/bench_render_train_pack
 them), their two gradients added to what each step computes: (a) is the node with ray_gradients=True (its ray gradients from
 nrhip_encode_bwd_rays_packed), (b) the fallback VolumetricSampler.render_train takes by default for such rays (the gathers'
 index_add_ backward folds the per-sample rows to rays).  The line's "bench" is then "render_train_packed_ray_grads".
-    python scripts/bench_render_train_packed.py [--ray-grads] [--reps 100] [--warmup 10] [--out profiles/bench_render_train_packed.jsonl]"""
+--actors: the street scene of scripts/bench_render_packed.py --actors (65 536 rays, 24 moving actors, the box-aware march's
+packed samples, NeuRAD's default field with 4 x 4 actor grids) in training mode, flip_prob = 0 (the two routes draw the flip
+differently: per ray against per sample; a non-zero flip is not measured).  The march and the per-ray candidate lists are
+outside the timed region; timed, alternating, forward + backward (static table, MLPs, beta, the 24 actor tables, the
+trajectories):
+  (a) NeuRADField.render_train_packed(..., times=..., actor_cand=...): autograd.NffRenderPackedActorsTrainFn;
+  (b) the operator route on the same samples: gathers, the field with actors on [M,1], the torch head, renderers.render_packed
+      (what VolumetricSampler.render_train(..., actor_boxes=True) does by default; it computes its own per-sample lists).
+The line's "bench" is "render_train_packed_actors".  No ratio is promised.
+    python scripts/bench_render_train_packed.py [--ray-grads | --actors] [--reps 100] [--warmup 10] [--out profiles/bench_render_train_packed.jsonl]"""
 import argparse
 import json
 import os
@@ -78,15 +87,88 @@ def ragged_samples(rng):
     return counts, ri, ts.astype(np.float32), (ts + np.float32(STEP)).astype(np.float32)
 
 
+def main_actors(args):
+    import bench_render_packed as BP  # (scripts/ is sys.path[0]: the scene is that script's)
+    from bench import device_state
+
+    sc = BP.actor_scene()
+    fld, o, d, area, times, cand, ri, ts, te, seg = (sc[k] for k in ("fld", "o", "d", "area", "times", "cand", "ri", "ts", "te", "seg"))
+    rays, M = o.shape[0], int(ri.shape[0])
+    counts = (seg[1:] - seg[:-1]).cpu().numpy()
+    fld.train()
+    fld.hashgrid.config.actor.flip_prob = 0.0
+    assert fld.fused_packed_actors_train_supported()
+    rb = RayBundle(origins=o, directions=d, pixel_area=area, times=times[:, None])
+    cot = [torch.randn(s, generator=sc["gen"]).cuda() for s in ((rays, 32), (rays, 1), (rays, 1), (M,))]
+    named = [(n, p) for n, p in fld.named_parameters() if p.requires_grad]
+    names, params = [n for n, _ in named], [p for _, p in named]
+
+    def loss_of(outs):
+        return sum((t.reshape(c.shape) * c).sum() for t, c in zip(outs, cot))
+
+    def route_a():
+        outs = fld.render_train_packed(o, d, area, ts, te, ray_indices=ri, num_rays=rays, times=times, actor_cand=cand)
+        return outs, torch.autograd.grad(loss_of(outs), params, allow_unused=True)
+
+    def route_b():
+        rs = VolumetricSampler._gather(rb, o, d, ri, ts, te)
+        out = fld(rs)
+        res = render_packed(out[FieldHeadNames.FEATURE], rs, ri, rays, alpha=out[FieldHeadNames.ALPHA])
+        outs = (res["features"], res["depth"], res["accumulation"], res["weights"][:, 0])
+        return outs, torch.autograd.grad(loss_of(outs), params, allow_unused=True)
+
+    (oa, ga), (ob, gb) = route_a(), route_b()
+    agree = {k: rel_l2(x, y) for k, x, y in zip(("features", "depth", "accumulation", "weights"), oa, ob)}
+    tabs = [rel_l2(x, y) for n, x, y in zip(names, ga, gb) if x is not None and y is not None and ".actor_grids." in n]
+    agree.update({f"d {n}": rel_l2(x, y) for n, x, y in zip(names, ga, gb)
+                  if x is not None and y is not None and ".actor_grids." not in n})
+    agree["d actor tables (max of %d)" % len(tabs)] = max(tabs)
+    del oa, ga, ob, gb
+    keys = ("a_fused_node_actors", "b_operator_route")
+    lap = {k: [] for k in keys}
+    clocks = device_state(0)
+    for rep in range(args.warmup + args.reps):
+        for key, fn in zip(keys, (route_a, route_b)):  # alternating
+            t = timed(fn)
+            if rep >= args.warmup:
+                lap[key].append(t)
+    med = {k: median(v) for k, v in lap.items()}
+    acfg = sc["cfg"].grid.actor
+    line = {
+        "bench": "render_train_packed_actors", "field": "neurad_default_8x4_h32", "levels": L, "features_per_level": F,
+        "hidden": H, "head": "sdf", "log2_table": BP.LOG2_T, "table_dtype": "fp32", "actors": int(sc["actors"].n_actors),
+        "actor_grid": [acfg.num_levels, acfg.hashgrid_dim, acfg.log2_hashmap_size], "flip_prob": 0.0,
+        "rays": rays, "grid": BP.RES, "step": BP.STEP, "M": M, "M_plain_march": sc["plain_m"],
+        "rays_with_candidates": float((cand[0] > 0).float().mean()),
+        "segments": {"min": int(counts.min()), "median": float(np.median(counts)), "p99": float(np.percentile(counts, 99)),
+                     "max": int(counts.max()), "empty_share": float((counts == 0).mean())},
+        "device": torch.cuda.get_device_name(0), "clocks_under_load": clocks, "reps": args.reps, "warmup": args.warmup,
+        "median_us": med, "min_us": {k: min(v) for k, v in lap.items()}, "max_us": {k: max(v) for k, v in lap.items()},
+        "ratio_b_over_a": med[keys[1]] / med[keys[0]],
+        "note": "forward + backward; march and per-ray candidate lists outside the timed region; (b) computes its own "
+                "per-sample lists",
+        "a_vs_b_rel_l2": agree,
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "a") as f:
+        f.write(json.dumps(line) + "\n")
+    print(json.dumps(line))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--ray-grads", action="store_true", help="rays that require grad: the opt-in node against the fallback")
+    ap.add_argument("--actors", action="store_true", help="the fused node with dynamic actors against the operator route")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_render_train_packed.jsonl"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_render_train_packed: no GPU")
+    if args.actors:
+        if args.ray_grads:
+            raise SystemExit("bench_render_train_packed: --actors and --ray-grads do not combine (the node refuses both)")
+        return main_actors(args)
     from bench import device_state
 
     gen = torch.Generator().manual_seed(0)
