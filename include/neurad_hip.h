@@ -951,6 +951,38 @@ int nrhip_interlevel_loss(const float* c, const float* w, int32_t n_fine, const 
 int nrhip_distortion_loss(const float* c, const float* w, int32_t n_samples, int64_t r, float* loss_per_ray,
                           float* grad_w, void* stream);
 
+/* ---- lidar scan evaluation (csrc/lidar_eval.hip): the chamfer distance of NeuRADModel.get_image_metrics_and_images
+ *      (models/neurad.py:614-618; utils/math.py:745-798, there 2 ceil(N / 1000) torch.cdist blocks) ------------------------
+ * A point set is fp32 [n, stride]: the first three floats of a row are xyz, the row stride (floats) is >= 3, so
+ * points[:, :3] of an [N,5] scan and homogeneous [N,4] points go in without a copy; valid is uint8 [n] or NULL (all valid).
+ *
+ * nrhip_nearest_sq_dist: out[i] = min over the valid targets j of |q_i - t_j|^2, as three rounded fp32 subtractions, then
+ * fma(dz, dz, fma(dy, dy, dx * dx)), the minimum by fminf -- never |a|^2 + |b|^2 - 2ab.  Against the exact value of the
+ * fp32 inputs |out_i - ref_i| <= 6 * 2^-24 * ref_i.  A valid query without a valid target gets +inf; an invalid query gets
+ * 0 (written); a valid target with a NaN coordinate is ignored by every query; a valid query with a NaN coordinate gets
+ * +inf; neither touches any other row.  n == 0 or m == 0 reads nothing of the empty set.
+ * Brute force: one lane holds Q queries in registers, the targets stream through LDS in tiles of NRHIP_NEAREST_TILE; when
+ * the queries alone cannot fill the chip the target range is split over `split` workgroups whose partial minima meet in an
+ * unsigned atomic min on the float's bits.  plan: 0 = chosen from n and m alone (nrhip_nearest_plan, host logic), else
+ * Q | split << 8 with Q in {1, 2, 4}, split in [1, 64].  Every plan, and every order of the targets, gives the same bits.
+ * Counts >= 2^31 are NRHIP_ERR_UNSUPPORTED.                                                                            */
+#define NRHIP_NEAREST_TILE 1024
+int nrhip_nearest_sq_dist(const float* query, int32_t stride_q, const uint8_t* query_valid, int64_t n, const float* target,
+                          int32_t stride_t, const uint8_t* target_valid, int64_t m, int32_t plan, float* out, void* stream);
+int nrhip_nearest_plan(int64_t n, int64_t m, int32_t* q /*host*/, int32_t* split /*host*/);
+/* chamfer_distance (utils/math.py:745-798): result [1] (device) = (S2T + T2S) / (normalize_with_target ? #valid targets : 1),
+ * S2T = sum over the valid sources of their nearest squared distance to the valid targets, T2S the other way round.  Both
+ * sums are accumulated in float64 in a fixed order (per-workgroup partials, then one fixed-order pass) and the result is
+ * rounded to fp32 once: bitwise reproducible, no float atomics, no host read.  Empty sets follow IEEE arithmetic: a side
+ * without valid points contributes 0 and leaves the other side's points at +inf; 0 / 0 is NaN.  source_sq_dist [n] /
+ * target_sq_dist [m] (either may be NULL) receive the per-point values of nrhip_nearest_sq_dist.  workspace: device scratch
+ * of nrhip_chamfer_workspace bytes (host logic), 16-byte aligned.                                                       */
+int nrhip_chamfer_workspace(int64_t n, int64_t m, int64_t* bytes /*host*/);
+int nrhip_chamfer_distance(const float* source, int32_t stride_s, const uint8_t* source_valid, int64_t n,
+                           const float* target, int32_t stride_t, const uint8_t* target_valid, int64_t m,
+                           int32_t normalize_with_target, int32_t plan, float* result, float* source_sq_dist,
+                           float* target_sq_dist, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- the training step's glue as kernels (csrc/train_fused.hip) ---------------------------------------------------
  * What the reference spreads over dozens of elementwise torch ops per step between the field / sampler kernels.
  * `edges` is a bin-edge tensor e[R, >= S+1] with row stride edge_stride (floats): sample s of a ray spans

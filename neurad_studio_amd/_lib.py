@@ -122,6 +122,7 @@ class LidarTable(C.Structure):
 
 MAX_SAMPLE_CONTAINMENTS = 8  # NRHIP_MAX_SAMPLE_CONTAINMENTS
 GRAD_ROWS_PER_BLOCK = 256   # NRHIP_GRAD_ROWS_PER_BLOCK
+NEAREST_TILE = 1024         # NRHIP_NEAREST_TILE
 P, I32, I64, F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> argtypes : exactly the prototypes of include/neurad_hip.h (tests/test_abi.py cross-checks this
@@ -281,6 +282,10 @@ PROTOTYPES = {
     "nrhip_lidar_losses": [C.POINTER(P), I32, P, P, P, P, P, P, I64, F32, F32, F32, P, P, P, P],
     "nrhip_lidar_losses_workspace": [I64, C.POINTER(I64)],
     "nrhip_lidar_losses_bwd": [P, P, P, P, P, I32, I64, I64, C.POINTER(P), P, P, P],
+    "nrhip_nearest_sq_dist": [P, I32, P, I64, P, I32, P, I64, I32, P, P],
+    "nrhip_nearest_plan": [I64, I64, C.POINTER(I32), C.POINTER(I32)],
+    "nrhip_chamfer_workspace": [I64, I64, C.POINTER(I64)],
+    "nrhip_chamfer_distance": [P, I32, P, I64, P, I32, P, I64, I32, I32, P, P, P, P, I64, P],
 }
 
 _lib = None

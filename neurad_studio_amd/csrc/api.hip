@@ -92,6 +92,14 @@ int validate_packed_rays(const char* who, const nrhip_packed_rays* r, bool need_
   return NRHIP_OK;
 }
 
+int validate_points(const char* who, const float* points, int32_t stride, int64_t n) {
+  NR_REQUIRE(n >= 0, NRHIP_ERR_INVALID_ARG, "%s: negative count", who);
+  NR_REQUIRE(stride >= 3, NRHIP_ERR_INVALID_ARG, "%s: row stride %d < 3 floats", who, stride);
+  NR_REQUIRE(n < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "%s: count >= 2^31", who);
+  NR_REQUIRE(points || n == 0, NRHIP_ERR_INVALID_ARG, "%s: NULL pointer with %lld points", who, (long long)n);
+  return NRHIP_OK;
+}
+
 }  // namespace nrhip
 
 extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
@@ -112,7 +120,8 @@ extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
 // 518: nrhip_occgrid_march_levels_actors, nrhip_render_fwd_packed_actors: the occupancy route with dynamic actors (eval)
 // 519: training on packed samples of a scene with dynamic actors: nrhip_field_fwd_train_packed_ovr, nrhip_actor_find_packed,
 //      nrhip_actor_pair_positions_fwd_packed / _bwd_packed
-extern "C" int nrhip_version(void) { return 519; }
+// 520: lidar scan evaluation: nrhip_nearest_sq_dist (+ nrhip_nearest_plan), nrhip_chamfer_distance (+ _workspace)
+extern "C" int nrhip_version(void) { return 520; }
 
 extern "C" int nrhip_tuning_reload(void) {
   nrhip::g_tuning = nrhip::read_tuning();

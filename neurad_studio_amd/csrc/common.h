@@ -99,6 +99,9 @@ inline PackedRaysDev to_dev(const nrhip_packed_rays& r) {
 // not negative, M < 2^31, and -- unless the batch has no rays or no samples, when nothing is read -- no NULL array; the
 // segments only where the entry point walks them.
 int validate_packed_rays(const char* who, const nrhip_packed_rays* r, bool need_segments);
+// A point set [n, stride >= 3 floats] (`who` names the entry point and the set): count not negative and < 2^31, stride >= 3,
+// no NULL array unless the set is empty.
+int validate_points(const char* who, const float* points, int32_t stride, int64_t n);
 
 // Where a ray's samples lie, for kernels written once over both layouts: samples of the ray; row of a per-sample tensor
 // that holds sample s of the ray; index of its interval in starts / ends.  Packed: the count is clamped into [0, M] and

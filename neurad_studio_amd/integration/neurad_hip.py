@@ -41,6 +41,7 @@ from ..fields.neurad_field import NeuRADProposalField as HipNeuRADProposalField
 from ..model_components import losses as hip_losses
 from ..model_components import ray_samplers as hip_samplers
 from ..model_components import renderers as hip_renderers
+from ..model_components.lidar_metrics import lidar_eval_metrics, masked_return_metrics, scalars_to_host
 from ..models.neurad import FusedEvalMixin, FusedTrainMixin
 from ..optim import HashGridAdam
 from ..shims import nerfacc as hip_nerfacc
@@ -112,6 +113,11 @@ class NeuRADHipModelConfig(NeuRADModelConfig):
     the quantile as a radix select) and every per-step metric without boolean-mask indexing -- the reference's formulation
     costs ~15 `x[mask]` (a nonzero + a device->host read each) and a `float(beta)` per step, which serialise the host with the
     GPU.  Same keys, same values (tests/test_gpu_reference_plugin.py); False: the reference's own get_metrics_dict."""
+    fused_lidar_eval: bool = False
+    """Evaluation of a lidar scan (``ns-eval``, in-training eval) on the device: get_outputs_for_lidar builds its rays with
+    cameras/raygen.py:lidar_rays, the lidar branch of get_image_metrics_and_images (models/neurad.py:589-620) runs as masked
+    reductions plus the chamfer kernel (csrc/lidar_eval.hip) and reads its five scalars with one device->host transfer.
+    False: the reference's own methods (torch ray generation, ~8 boolean-mask gathers, chunked torch.cdist)."""
     table_dtype: Literal["float32", "float16"] = "float32"
     """Storage of the main field's hash tables (static grid + actor grids).  "float16" (BASELINE config[4]; what tiny-cuda-nn
     stores): half the gather bytes; gradients arrive in fp16 and HashGridAdam keeps fp32 master copies (optim.py).  State
@@ -204,6 +210,11 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
         """the reference's method (models/neurad.py:337-366) with the RGB CNN decoder on the HIP kernels: fp16 operands, fp32
         accumulation -- what the reference's mixed-precision trainer runs through MIOpen"""
         layout, self._batch_layout = self._batch_layout, None
+        if self._all_lidar_bundle:
+            # a whole lidar scan (get_outputs_for_lidar): every row goes to the lidar head; models/neurad.py:348-365 would
+            # gather by two boolean masks and run the CNN decoder on an empty batch
+            intensity, ray_drop_logit = self.lidar_decoder(features).float().split(1, dim=-1)
+            return None, intensity.sigmoid(), ray_drop_logit
         if (layout is not None and is_lidar is not None and not intensity_for_cam and features.is_cuda
                 and sum(layout) == features.shape[0] and layout[0] > 0 and layout[1] > 0):
             # models/neurad.py:345-366 with the two masks replaced by the layout's views
@@ -250,18 +261,9 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
         did_return = batch["did_return"].index_select(0, rows[0])[:, 0]
         target_i, distance = batch["lidar"][..., 3:4], batch["distance"]
         with torch.no_grad():  # the four eval metrics the reference logs every step (models/neurad.py:477-483)
-            ret = did_return[:, None]
-            n_ret = ret.sum().clamp_min(1)
             pred = outputs["depth"].detach().index_select(0, rows[0])
-            sq = (pred - distance) ** 2
-            # median over the returned rays: the lower of the two middle values (torch.median), via a sort with the others at
-            # +inf and a device-side index
-            srt = torch.where(ret, sq, torch.full_like(sq, float("inf"))).reshape(-1).sort().values
-            m["depth_median_l2"] = srt.gather(0, ((n_ret - 1) // 2).reshape(1))[0]
-            m["depth_mean_rel_l2"] = (torch.where(ret, ((pred - distance) / distance) ** 2, torch.zeros_like(sq))).sum() / n_ret
-            m["intensity_rmse"] = (torch.where(ret, (outputs["intensity"].detach() - target_i) ** 2,
-                                               torch.zeros_like(sq)).sum() / n_ret).sqrt()
-            m["ray_drop_accuracy"] = ((outputs["ray_drop_logits"].detach().sigmoid() > 0.5).squeeze(-1) == ~did_return).float().mean()
+            m.update(masked_return_metrics(pred, distance, outputs["intensity"].detach(), target_i,
+                                            outputs["ray_drop_logits"].detach(), did_return))
         cfg = LidarLossSettings(depth_mult=loss.depth_mult, intensity_mult=loss.intensity_mult, carving_mult=loss.carving_mult,
                                 quantile_threshold=loss.quantile_threshold,
                                 non_return_lidar_distance=loss.non_return_lidar_distance,
@@ -274,6 +276,68 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
             m["sdf_to_density"] = self.field.sdf_to_density.beta.detach()  # (the reference: float(beta), a host read per step)
         self.camera_optimizer.get_metrics_dict(m)
         return m
+
+    # ---- evaluation of a lidar scan (fused_lidar_eval) ---------------------------------------------------------------------
+    _all_lidar_bundle = False
+
+    @torch.no_grad()
+    def get_outputs_for_lidar(self, lidar, batch):
+        """models/ad_model.py:85-114 with the rays from the device generator (cameras/raygen.py:lidar_rays, in the reference's
+        RayBundle class) and the whole scan through the lidar head without a mask gather; the render itself is the reference's
+        chunk loop (get_outputs_for_camera_ray_bundle) over the fused eval kernels.  Same keys as the reference except "rgb",
+        which the reference fills with an empty tensor for a scan."""
+        if not self.config.fused_lidar_eval:
+            return super().get_outputs_for_lidar(lidar, batch)
+        from nerfstudio.cameras.rays import RayBundle
+        from nerfstudio.utils.poses import inverse as pose_inverse
+
+        from ..cameras.raygen import lidar_rays
+
+        assert isinstance(batch["lidar_idx"], int), "All lidar points are assumed to be from the same scan."
+        dev = self.device
+        points, lidar = batch["lidar"].to(dev), lidar.to(dev)
+        n = points.shape[0]
+        ray_bundle = lidar_rays(lidar, torch.zeros((n, 1), dtype=torch.long, device=dev), points, bundle_cls=RayBundle)
+        ray_bundle.camera_indices = torch.full((n, 1), batch["lidar_idx"], dtype=torch.long, device=dev)
+        batch["is_lidar"] = ray_bundle.metadata["is_lidar"]
+        batch["distance"] = ray_bundle.metadata["directions_norm"]
+        batch["did_return"] = ray_bundle.metadata["did_return"]
+        self._all_lidar_bundle = True
+        try:
+            outputs = self.get_outputs_for_camera_ray_bundle(ray_bundle)
+        finally:
+            self._all_lidar_bundle = False
+        # points in the lidar's frame (models/ad_model.py:108-113)
+        w2l = pose_inverse(lidar.lidar_to_worlds[0])
+        world = ray_bundle.origins + ray_bundle.directions * outputs["depth"]
+        outputs["points"] = (w2l @ torch.cat([world, torch.ones_like(world[..., :1])], dim=-1).unsqueeze(-1)).squeeze(-1)
+        return outputs, batch
+
+    def get_image_metrics_and_images(self, outputs, batch):
+        """The image branch is the reference's; with ``fused_lidar_eval`` the lidar branch (models/neurad.py:589-620) is
+        ``_fused_lidar_eval_metrics``: the same five keys, every value a Python float -- the reference returns a 0-dim tensor
+        for ``chamfer_distance`` in its fallback case (nothing predicted to return, or nothing returned), this path a float."""
+        if not (self.config.fused_lidar_eval and "lidar" in batch and outputs["depth"].shape[0] == batch["lidar"].shape[0]):
+            return super().get_image_metrics_and_images(outputs, batch)
+        metrics, images = super().get_image_metrics_and_images(outputs, {k: v for k, v in batch.items() if k != "lidar"})
+        metrics.update(self._fused_lidar_eval_metrics(outputs, batch))
+        return metrics, images
+
+    def _fused_lidar_eval_metrics(self, outputs, batch):
+        """every ray of ``outputs`` is a ray of the scan ``batch["lidar"]`` (what get_outputs_for_lidar renders):
+        model_components/lidar_metrics.py:lidar_eval_metrics with this model's loss settings"""
+        dev, loss = self.device, self.config.loss
+        points = batch["lidar"].to(dev)
+        for key in ("is_lidar", "did_return"):  # (models/neurad.py:591-594)
+            if key not in batch:
+                batch[key] = torch.ones(points.shape[0], 1, dtype=torch.bool, device=dev)
+        return lidar_eval_metrics(outputs, points, batch["distance"].to(dev), batch["did_return"][:, 0].to(dev),
+                                  loss.ray_drop_loss_mult, loss.non_return_lidar_distance, to_host=self._scalars_to_host)
+
+    @staticmethod
+    def _scalars_to_host(values):
+        """THE device->host transfer of the lidar eval metrics (one per scan; tests count the calls)"""
+        return scalars_to_host(values)
 
 
 def _trainer_config():

@@ -2050,6 +2050,93 @@ def lidar_losses_bwd(saved, inverse: Tensor, upstream: Tensor, n_levels: int, n_
     return gds, gi, gl
 
 
+# ---- lidar scan evaluation (csrc/lidar_eval.hip): nearest neighbour and chamfer distance, no autograd -------------------------
+NEAREST_TILE = _lib.NEAREST_TILE
+NEAREST_QS = (1, 2, 4)  # query points per lane the kernel is instantiated for
+
+
+def _points(t: Tensor, name: str) -> Tuple[Tensor, int]:
+    """a point set [n, >= 3] fp32 -> (the tensor, its row stride in floats): a strided view of rows goes in as it is
+    (``scan[:, :3]`` of an [N,5] scan, homogeneous [N,4] points); anything else is made contiguous"""
+    if not isinstance(t, Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(t)}")
+    if not t.is_cuda:
+        raise _lib.NeuradHipError(f"{name}: tensor is on {t.device}; the HIP path needs a GPU tensor (no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected torch.float32, got {t.dtype}")
+    if t.dim() != 2 or t.shape[1] < 3:
+        raise ValueError(f"{name}: expected [n, >= 3], got {tuple(t.shape)}")
+    if t.shape[0] >= 2 ** 31:
+        raise _lib.NeuradHipError(f"{name}: {t.shape[0]} points >= 2^31")
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < 3):
+        t = t.contiguous()
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), 3))
+
+
+def _valid(v: Optional[Tensor], n: int, name: str) -> Optional[Tensor]:
+    if v is None:
+        return None
+    v = v.reshape(-1)
+    if not v.is_cuda:
+        raise _lib.NeuradHipError(f"{name}: tensor is on {v.device}; the HIP path needs a GPU tensor (no CPU fallback)")
+    if v.shape[0] != n:
+        raise ValueError(f"{name}: {v.shape[0]} entries for {n} points")
+    v = v.contiguous()
+    return v.view(torch.uint8) if v.dtype == torch.bool else _chk(v, name, torch.uint8)
+
+
+def _nearest_plan_arg(plan) -> int:
+    """None -> 0 (the library chooses from N and M); (Q, split) -> Q | split << 8"""
+    if plan is None:
+        return 0
+    q, split = plan
+    if int(q) not in NEAREST_QS or not 1 <= int(split) <= 64:
+        raise ValueError(f"plan=(Q, split): Q in {NEAREST_QS}, split in [1, 64]; got {plan}")
+    return int(q) | int(split) << 8
+
+
+def nearest_plan(n: int, m: int) -> Tuple[int, int]:
+    """(Q, split) the library picks for n queries against m targets (host logic)"""
+    q, split = C.c_int32(0), C.c_int32(0)
+    call("nrhip_nearest_plan", int(n), int(m), C.byref(q), C.byref(split))
+    return q.value, split.value
+
+
+def nearest_sq_dist(query: Tensor, target: Tensor, query_valid: Optional[Tensor] = None,
+                    target_valid: Optional[Tensor] = None, plan=None) -> Tensor:
+    """-> [N] fp32: for every query the squared distance to its nearest valid target (direct differences; +inf without a
+    valid target, 0 for an invalid query).  query / target [*, >= 3] fp32, strided rows allowed; *_valid bool / uint8 [*].
+    plan=(Q, split) forces the launch plan; every plan gives the same bits."""
+    q, sq = _points(query, "query")
+    t, st = _points(target, "target")
+    n, m = q.shape[0], t.shape[0]
+    qv, tv = _valid(query_valid, n, "query_valid"), _valid(target_valid, m, "target_valid")
+    out = torch.empty((n,), device=q.device, dtype=torch.float32)
+    launch("nrhip_nearest_sq_dist", q if n else None, sq, qv if n else None, n, t if m else None, st, tv if m else None, m,
+           _nearest_plan_arg(plan), out if n else None)
+    return out
+
+
+def chamfer_distance(source: Tensor, target: Tensor, source_valid: Optional[Tensor] = None,
+                     target_valid: Optional[Tensor] = None, normalize_with_target: bool = False,
+                     return_per_point: bool = False, plan=None):
+    """utils/math.py:745-798 on masked point sets -> 0-dim fp32 tensor on the device (no host read): the sum over the valid
+    sources of their nearest squared distance to the valid targets, plus the same the other way round, divided by the number
+    of valid targets when ``normalize_with_target``.  return_per_point: -> (value, source_sq_dist [N], target_sq_dist [M])."""
+    s, ss = _points(source, "source")
+    t, st = _points(target, "target")
+    n, m = s.shape[0], t.shape[0]
+    sv, tv = _valid(source_valid, n, "source_valid"), _valid(target_valid, m, "target_valid")
+    dev = s.device
+    result = torch.empty((), device=dev, dtype=torch.float32)
+    ds = torch.empty((n,), device=dev, dtype=torch.float32) if return_per_point else None
+    dt = torch.empty((m,), device=dev, dtype=torch.float32) if return_per_point else None
+    ws, need = _workspace("nrhip_chamfer_workspace", n, m, device=dev, dtype=torch.uint8)
+    launch("nrhip_chamfer_distance", s if n else None, ss, sv if n else None, n, t if m else None, st, tv if m else None, m,
+           1 if normalize_with_target else 0, _nearest_plan_arg(plan), result, ds if n else None, dt if m else None, ws, need)
+    return (result, ds, dt) if return_per_point else result
+
+
 # ---- SURVEY §8(e): the level-sparse gradient exchange's device side (csrc/grad_rows.hip; parallel/data_parallel.py) ----------
 def grad_rows_count(grad: Tensor, n_levels: int):
     """grad [n_levels * T, F] fp32 -> (level_counts [n_levels] int64 = non-zero rows per level, block_offsets [n_levels, nblk]
