@@ -7,11 +7,17 @@
 //     p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)          [AdamW: p *= 1 - lr * wd first]
 // plus the one thing a hash table allows: rows that have NEVER received a gradient have g = m = v = 0, for which the
 // update is exactly a no-op -- the kernel reads (g, m, v), sees three zeros and touches nothing else (no read of p, no
-// writes): 12 instead of 28 bytes per such element, with bit-identical results.  Coarse levels (res^3 << T: most of
-// their hashed rows are never addressed) and sparsely observed scenes are mostly such rows.
+// writes): 12 instead of 28 bytes per such element.  The results are bit-identical to the plain arithmetic when eps > 0 in
+// fp32 and there is no weight decay, and only then is the shortcut taken: with decay the row still shrinks, and with an eps
+// that rounds to 0 the arithmetic gives 0 / 0 = NaN (torch's result too), in the body and in the scalar tail alike, so what
+// one element becomes never depends on where in the tensor it sits.  (m and v are never -0: both start at +0 and neither
+// update can produce it.)  Coarse levels (res^3 << T: most of their hashed rows are never addressed) and sparsely observed
+// scenes are mostly such rows.
 // 16-byte accesses, grid-stride, no atomics; the state (step, exp_avg, exp_avg_sq) stays in torch.optim.Adam's
 // state_dict layout (neurad_studio_amd/optim.py), so checkpoints interchange.
 #include <hip/hip_fp16.h>
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -71,7 +77,7 @@ __device__ __forceinline__ void adam_tensor(const AdamTensor& t, int64_t first, 
     float4 vv = reinterpret_cast<const float4*>(t.v)[i];
     const bool dead = gv.x == 0.f && gv.y == 0.f && gv.z == 0.f && gv.w == 0.f && mv.x == 0.f && mv.y == 0.f &&
                       mv.z == 0.f && mv.w == 0.f && vv.x == 0.f && vv.y == 0.f && vv.z == 0.f && vv.w == 0.f;
-    if (dead && t.a.decay == 1.f) continue;  // exact no-op: never-touched rows cost three reads
+    if (dead && t.a.decay == 1.f && t.a.eps > 0.f) continue;  // exact no-op: never-touched rows cost three reads
     float4 pv = reinterpret_cast<float4*>(t.p)[i];
     adam_elem(pv.x, gv.x, mv.x, vv.x, t.a);
     adam_elem(pv.y, gv.y, mv.y, vv.y, t.a);
@@ -287,6 +293,26 @@ int check_tensor(const char* what, const float* param, const void* grad, const f
   return NRHIP_OK;
 }
 
+// Everything that can be refused about the tensors of a many-tensor call, checked BEFORE the first launch: a call over more
+// than 24 tensors is several launches, and an error must mean that nothing was touched (no earlier batch updated, no step
+// count advanced).  The launch loops below repeat none of it.
+template <typename T>
+int check_many(const char* what, const T* tensors, int32_t n_tensors) {
+  for (int k = 0; k < n_tensors; ++k) {
+    const T& in = tensors[k];
+    NR_REQUIRE(in.n >= 0 && (in.grad_dtype == 0 || in.grad_dtype == 1), NRHIP_ERR_INVALID_ARG,
+               "%s: tensor %d: n >= 0, grad_dtype 0 (fp32) or 1 (fp16)", what, k);
+    if constexpr (std::is_same_v<T, nrhip_adam_tensor_dev>) {
+      NR_REQUIRE(in.step, NRHIP_ERR_INVALID_ARG, "%s: tensor %d: a device step scalar", what, k);
+    } else {
+      NR_REQUIRE(in.n == 0 || in.step >= 1, NRHIP_ERR_INVALID_ARG, "%s: tensor %d: step >= 1 required", what, k);
+    }
+    if (in.n == 0) continue;
+    if (int e = check_tensor(what, in.param, in.grad, in.exp_avg, in.exp_avg_sq, in.image_fp16)) return e;
+  }
+  return NRHIP_OK;
+}
+
 }  // namespace
 
 extern "C" int nrhip_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step,
@@ -304,6 +330,9 @@ extern "C" int nrhip_adam_step(float* param, const float* grad, float* exp_avg, 
 extern "C" int nrhip_adam_step_many(const nrhip_adam_tensor* tensors, int32_t n_tensors, double lr, double beta1, double beta2,
                                     double eps, double weight_decay, double grad_scale, void* stream) {
   NR_REQUIRE(n_tensors >= 0 && (tensors || n_tensors == 0), NRHIP_ERR_INVALID_ARG, "adam_step_many: bad argument");
+  NR_REQUIRE(lr >= 0. && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0., NRHIP_ERR_INVALID_ARG,
+             "adam_step_many: bad hyper-parameter");
+  if (int e = check_many("adam_step_many", tensors, n_tensors)) return e;
   int k = 0;
   while (k < n_tensors) {
     AdamMany many;
@@ -313,10 +342,7 @@ extern "C" int nrhip_adam_step_many(const nrhip_adam_tensor* tensors, int32_t n_
     for (int j = k; j < n_tensors && live < kAdamMany; ++j) live += tensors[j].n > 0 ? 1 : 0;
     for (; k < n_tensors && many.count < kAdamMany; ++k) {
       const nrhip_adam_tensor& in = tensors[k];
-      NR_REQUIRE(in.n >= 0 && (in.grad_dtype == 0 || in.grad_dtype == 1), NRHIP_ERR_INVALID_ARG,
-                 "adam_step_many: tensor %d: n >= 0, grad_dtype 0 (fp32) or 1 (fp16)", k);
       if (in.n == 0) continue;
-      if (int e = check_tensor("adam_step_many", in.param, in.grad, in.exp_avg, in.exp_avg_sq, in.image_fp16)) return e;
       AdamTensor& t = many.t[many.count++];
       t = AdamTensor{in.param, in.grad, in.exp_avg, in.exp_avg_sq, reinterpret_cast<__half*>(in.image_fp16), in.n, {},
                      in.grad_dtype, blocks};
@@ -348,6 +374,7 @@ extern "C" int nrhip_adam_step_many_dev(const nrhip_adam_tensor_dev* tensors, in
   NR_REQUIRE(workspace || n_tensors == 0, NRHIP_ERR_INVALID_ARG, "adam_step_many_dev: workspace required");
   NR_REQUIRE(lr >= 0. && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0., NRHIP_ERR_INVALID_ARG,
              "adam_step_many_dev: bad hyper-parameter");
+  if (int e = check_many("adam_step_many_dev", tensors, n_tensors)) return e;
   AdamCtl* ctl = reinterpret_cast<AdamCtl*>(workspace);
   int k = 0, slot = 0;
   while (k < n_tensors) {
@@ -359,10 +386,7 @@ extern "C" int nrhip_adam_step_many_dev(const nrhip_adam_tensor_dev* tensors, in
     for (int j = k; j < n_tensors && live < kAdamMany; ++j) live += tensors[j].n > 0 ? 1 : 0;
     for (; k < n_tensors && many.count < kAdamMany; ++k) {
       const nrhip_adam_tensor_dev& in = tensors[k];
-      NR_REQUIRE(in.n >= 0 && (in.grad_dtype == 0 || in.grad_dtype == 1) && in.step, NRHIP_ERR_INVALID_ARG,
-                 "adam_step_many_dev: tensor %d: n >= 0, grad_dtype 0 (fp32) or 1 (fp16), a device step scalar", k);
       if (in.n == 0) continue;
-      if (int e = check_tensor("adam_step_many_dev", in.param, in.grad, in.exp_avg, in.exp_avg_sq, in.image_fp16)) return e;
       pr.step[many.count] = in.step;
       AdamTensor& t = many.t[many.count++];
       t = AdamTensor{in.param, in.grad, in.exp_avg, in.exp_avg_sq, reinterpret_cast<__half*>(in.image_fp16), in.n, {},
@@ -390,6 +414,13 @@ extern "C" int nrhip_adam_step_many_dev(const nrhip_adam_tensor_dev* tensors, in
 extern "C" int nrhip_nonfinite_check_many(const nrhip_check_tensor* tensors, int32_t n_tensors, float* found_inf, void* stream) {
   NR_REQUIRE(n_tensors >= 0 && (tensors || n_tensors == 0) && found_inf, NRHIP_ERR_INVALID_ARG,
              "nonfinite_check_many: bad argument");
+  for (int j = 0; j < n_tensors; ++j) {  // every refusal before the first launch: an error means nothing was flagged
+    const nrhip_check_tensor& in = tensors[j];
+    NR_REQUIRE(in.n >= 0 && (in.dtype == 0 || in.dtype == 1), NRHIP_ERR_INVALID_ARG,
+               "nonfinite_check_many: tensor %d: n >= 0, dtype 0 (fp32) or 1 (fp16)", j);
+    NR_REQUIRE(in.n == 0 || (in.data && (reinterpret_cast<uintptr_t>(in.data) & 15) == 0), NRHIP_ERR_INVALID_ARG,
+               "nonfinite_check_many: tensor %d must be a 16-byte aligned device pointer", j);
+  }
   int k = 0;
   while (k < n_tensors) {
     CheckMany many;
@@ -399,11 +430,7 @@ extern "C" int nrhip_nonfinite_check_many(const nrhip_check_tensor* tensors, int
     for (int j = k; j < n_tensors && live < kCheckMany; ++j) live += tensors[j].n > 0 ? 1 : 0;
     for (; k < n_tensors && many.count < kCheckMany; ++k) {
       const nrhip_check_tensor& in = tensors[k];
-      NR_REQUIRE(in.n >= 0 && (in.dtype == 0 || in.dtype == 1), NRHIP_ERR_INVALID_ARG,
-                 "nonfinite_check_many: tensor %d: n >= 0, dtype 0 (fp32) or 1 (fp16)", k);
       if (in.n == 0) continue;
-      NR_REQUIRE(in.data && (reinterpret_cast<uintptr_t>(in.data) & 15) == 0, NRHIP_ERR_INVALID_ARG,
-                 "nonfinite_check_many: tensor %d must be a 16-byte aligned device pointer", k);
       int b = blocks_for(in.dtype ? in.n >> 1 : in.n);
       if (b > 1024 && live > 1) b = 1024;
       many.t[many.count++] = CheckTensor{in.data, in.n, in.dtype, blocks};
