@@ -1181,6 +1181,55 @@ int nrhip_rgb_decoder_fwd(const nrhip_rgb_decoder* d, const float* features, voi
 int nrhip_rgb_decoder_bwd(const nrhip_rgb_decoder* d, const float* features, const void* saved, const float* rgb,
                           const float* grad_rgb, void* workspace, float* grad_features, float* grad_params, void* stream);
 
+/* ---- VGG-19 perceptual loss (model_components/losses.py:582-625): the network up to relu5_1 on cat([rgb, image]), L1 on
+ *          the five relu{i}_1 features, a gradient into the rendered half.  Activations and gradients are NHWC fp16,
+ *          accumulation is fp32.  Channel counts are 3, 64, 128, 256 or 512; the 3-channel (image) side is STORED with
+ *          NRHIP_VGG_IMAGE_CHANNELS channels, the rest zero.
+ *
+ * Working scale.  A fp16 gradient tensor comes with a device `state` of two floats {amax, S}: stored = S * true with S a
+ * power of two, amax = the largest stored magnitude, kept by an unsigned atomic max on the float's bits (the caller zeroes
+ * the state before the producer runs).  A consumer multiplies by the power of two p that brings amax into [0.5, 1) in its
+ * epilogue -- exact -- and writes S_out = S_in * p.  A non-finite value makes amax, p and everything after it NaN.  There
+ * is no host read.                                                                                                      */
+#define NRHIP_VGG_IMAGE_CHANNELS 16
+#define NRHIP_L1_ITEMS 2048 /* elements per workgroup of the L1 kernels */
+/* torch Conv2d weight [cout][cin][3][3] fp32 -> fragment order, nrhip_conv3x3_pack_bytes bytes.  mode 0: forward;
+ * mode 1: the same convolution's input gradient (taps flipped, channels swapped): nrhip_conv3x3(cin = cout, cout = cin)
+ * on a mode-1 pack IS conv2d_backward w.r.t. the input.                                                                 */
+int nrhip_conv3x3_pack_bytes(int32_t cout, int32_t cin, int32_t mode, int64_t* bytes);
+int nrhip_conv3x3_pack(const float* weight, int32_t cout, int32_t cin, int32_t mode, void* wfrag, void* stream);
+/* Host logic: the launch plan of a convolution over n_pixels = b * h * w pixels.  A wave owns 32 * pixel_blocks pixels x
+ * 32 * channel_blocks output channels; plan 0 chooses pixel_blocks from n_pixels and cout alone, 1 or 2 forces it.
+ * Every plan gives the same bits.                                                                                      */
+int nrhip_conv3x3_plan(int64_t n_pixels, int32_t cin, int32_t cout, int32_t plan, int32_t* pixel_blocks,
+                       int32_t* channel_blocks, int64_t* waves);
+/* out [b,h,w,cout] = fp16(conv3x3(in [b,h,w,cin], pad 1) * p + bias), then ReLU if `relu`, then zero where mask <= 0
+ * (mask: fp16, out's shape; the ReLU mask of the layer's stored input in the backward).  bias, mask, in_state, out_state
+ * may be NULL; p = 1 without in_state; with out_state the kernel tracks amax and writes S_out.                         */
+int nrhip_conv3x3(const void* in, const void* wfrag, const float* bias, const void* mask, const float* in_state,
+                  float* out_state, void* out, int32_t b, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t relu,
+                  int32_t plan, void* stream);
+/* max_pool2d(2, 2), floor mode, on [b,h,w,c] fp16 (c a multiple of 8) -> [b,h/2,w/2,c].  The backward recomputes the
+ * first maximum of every window in row-major order from `in` (no index tensor) and writes ALL of grad_in: zero off the
+ * maximum and in a dropped odd row / column.                                                                            */
+int nrhip_maxpool2_fwd(const void* in, void* out, int64_t b, int32_t h, int32_t w, int32_t c, void* stream);
+int nrhip_maxpool2_bwd(const void* in, const void* grad_out, const float* in_state, float* out_state, void* grad_in,
+                       int64_t b, int32_t h, int32_t w, int32_t c, void* stream);
+/* out [1] = (accum ? *accum : 0) + weight * mean |fx - fy| over n fp16 elements: float64 per-workgroup partials
+ * (NRHIP_L1_ITEMS elements each) in `workspace`, added in a fixed order, one rounding to fp32.  Bit-reproducible.         */
+int nrhip_l1_feature_workspace(int64_t n, int64_t* bytes);
+int nrhip_l1_feature_fwd(const void* fx, const void* fy, int64_t n, float weight, const float* accum, void* workspace,
+                         int64_t workspace_bytes, float* out, void* stream);
+/* grad_fx = S * (weight * grad_loss[0] / n * sign(fx - fy) (* [fx > 0] if mask_fx) + above / S_above), sign(0) = 0, as
+ * fp16.  Without `above` S brings the constant into [0.5, 1) and the value is rounded once from float64; with `above`
+ * (a gradient tensor of the same shape and its state) both are brought to a common power of two and added in fp32.      */
+int nrhip_l1_feature_bwd(const void* fx, const void* fy, int64_t n, float weight, const float* grad_loss, int32_t mask_fx,
+                         const void* above, const float* above_state, float* out_state, void* grad_fx, void* stream);
+/* cat([x, y]) of two fp32 [n_pixels, 3] images -> fp16 [2 * n_pixels, NRHIP_VGG_IMAGE_CHANNELS]                         */
+int nrhip_vgg_stage_images(const float* x, const float* y, int64_t n_pixels, void* out, void* stream);
+/* grad [n_pixels, 3] fp32 = grad16 [n_pixels, NRHIP_VGG_IMAGE_CHANNELS] / S (state = {amax, S} of grad16)               */
+int nrhip_vgg_image_grad(const void* grad16, const float* state, int64_t n_pixels, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,10 @@ class NeuRADHipModelConfig(NeuRADModelConfig):
     dicts load into either (load_state_dict casts), so fp32 neurad checkpoints interchange."""
     proposal_table_dtype: Literal["float32", "float16"] = "float32"
     """... and of the proposal fields' static tables (their actor grids stay fp32: the fused sampler reads those as fp32)."""
+    fused_vgg_loss: bool = False
+    """The VGG perceptual term (``loss.vgg_mult``, models/neurad.py:260,537-538) as one autograd node on csrc/vgg_loss.hip
+    (model_components/perceptual.py): ``self.vgg_loss`` adopts the reference module's tensors, so the state dict and
+    ``get_loss_dict`` stay the reference's.  False: the reference's torch module (MIOpen under autocast)."""
 
 
 class _NchwDecoderAdapter(torch.nn.Module):
@@ -162,6 +166,10 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
         assert isinstance(self.field, HipNeuRADField), "config.field._target must be the HIP NeuRADField"
         self.fused_eval, self.early_stop_eps, self.order_rays = cfg.fused_eval, cfg.early_stop_eps, cfg.order_rays
         self.fused_training = cfg.fused_training
+        if cfg.fused_vgg_loss:
+            from neurad_studio_amd.model_components.perceptual import VGGPerceptualLoss
+
+            self.vgg_loss = VGGPerceptualLoss.from_reference(self.vgg_loss)
         s = cfg.sampling
         self.sampler = hip_samplers.ProposalNetworkSampler(
             num_proposal_samples_per_ray=s.num_proposal_samples, num_nerf_samples_per_ray=s.num_nerf_samples,
