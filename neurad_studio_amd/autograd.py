@@ -22,27 +22,137 @@ from . import ops
 _E15, _EM15 = 3269017.3724721107, 3.0590232050182579e-07  # exp(+-15): trunc_exp's backward clamp (activations.py:37-41)
 
 
-class Samples(NamedTuple):
-    """Where the samples of a batch of rays lie -- what the backward of a static encoding needs to know about the layout.
-    Dense: starts / ends [R,S].  Packed (the occupancy march's ragged output): starts / ends are t_starts / t_ends [M],
-    segments int64 [R+1] bounds each ray's samples and ray_indices int64 [M] names each sample's ray.  Origins, directions
-    and pixel area are per RAY in both."""
+class DenseSamples:
+    """Where the samples of a batch of rays lie, and every operation that depends on it: the one place that tells dense
+    samples from the march's packed ones (`PackedSamples`).  Dense: starts / ends [R,S] -- for the render node (`on_edges`)
+    the views of its bin edges [R,S+1], last edge = sky distance.  Origins, directions and pixel area are per RAY in both."""
 
-    starts: Tensor
-    ends: Tensor
-    segments: Optional[Tensor] = None
-    ray_indices: Optional[Tensor] = None
+    ray_indices = None  # (a ray's samples are a row)
+
+    def __init__(self, starts, ends):
+        self.starts, self.ends = starts, ends
+
+    @classmethod
+    def on_edges(cls, edges, emb_weight=None, sensor_idx=None, times=None, emb_cfg=(1.0, 1, False), emb_shape=(0, 0)):
+        """NffRenderTrainFn's dense samples: the appearance embedding (emb_weight [E,A] | None, sensor_idx | None, times |
+        None, (duration, n_per_sensor, temporal)) is written beside the composited features.  emb_shape: (E, A) for the
+        backward, which has the weight no more."""
+        self = cls(edges[:, :-1], edges[:, 1:])
+        self.edges, self.emb_weight, self.sensor_idx, self.times, self.emb_cfg = edges, emb_weight, sensor_idx, times, emb_cfg
+        self.n_embed, self.A = emb_shape if emb_weight is None else emb_weight.shape
+        return self
+
+    def saved(self):
+        """(the tensors the render node saves for this layout, how its backward builds the layout from them again)"""
+        cfg, shape = self.emb_cfg, (self.n_embed, self.A)
+        return (self.edges, self.sensor_idx, self.times), lambda e, s, t: DenseSamples.on_edges(e, None, s, t, cfg, shape)
+
+    def empty_outputs(self, device):
+        """the render node's outputs when there is nothing to launch, else None"""
+        return None
+
+    def cand_samples(self, pixel_area):
+        """the samples a ray batch's actor candidate lists come from (prepare_actors); None: the rays' lines alone"""
+        return pixel_area, self.starts, self.ends
+
+    def field_fwd_train(self, fs, o, d, a, order, override):
+        return ops.field_fwd_train(fs, o, d, a, self.starts, self.ends, order=order, override=override)
+
+    def render_fwd(self, geo, beta, beta_min, feature):
+        """head + compositing -> alpha, weights of the non-sky samples [R,S-1], features [R,C+A], depth [R,1], acc [R,1]"""
+        R, S = self.starts.shape
+        alpha, w_ns, out, depth, acc = ops.sdf_render_fwd(geo.view(R, S), beta, beta_min, feature.view(R, S, -1), self.edges,
+                                                          extra_cols=self.A)
+        if self.A:
+            ops.appearance_fwd(self.emb_weight, self.sensor_idx, self.times, *self.emb_cfg, R, out=out[:, out.shape[1] - self.A:])
+        return alpha, w_ns, out, depth, acc
+
+    def render_bwd(self, geo, beta, beta_min, alpha, feature, g_out, g_depth, g_acc, g_w, need):
+        """-> dL/d feature [N,C], dL/d geo [N], dL/d beta | None, the gradients of `on_edges`' arguments (need: which)"""
+        (R, S), C = self.starts.shape, feature.shape[-1]
+        if g_out is None:
+            g_out = torch.zeros((R, C + self.A), device=geo.device, dtype=torch.float32)
+        gfeat, ggeo, gbeta = ops.sdf_render_bwd(geo.view(R, S), beta, beta_min, alpha, feature.view(R, S, C), self.edges,
+                                                g_out[:, :C], g_depth, g_acc, g_w)
+        g_emb = None
+        if self.A and need[1]:
+            g_emb = ops.appearance_bwd(g_out[:, C:], self.sensor_idx, self.times, *self.emb_cfg, self.n_embed)
+        return gfeat.view(R * S, C), ggeo.view(-1), gbeta, (None, g_emb, None, None, None)
+
+    def actor_geometry(self, spec, cand, o, d, a, flip, out_dim):
+        """-> hits [N,8] (every actor containing the sample), hit [N] (the winning one or -1), view directions [N,3]"""
+        scratch = torch.empty((self.starts.numel(), out_dim), device=o.device, dtype=torch.float32)  # (hit rows land here)
+        dirs, hit = ops.actor_encode(spec, cand, o, d, a, self.starts, self.ends, scratch, flip)
+        return ops.actor_hits(spec, cand, o, d, a, self.starts, self.ends), hit, dirs
+
+    def pair_positions(self, spec, o, d, a, times, sample_idx, actor_idx, flip):
+        return ops.actor_pair_positions(spec, o, d, a, self.starts, self.ends, times, sample_idx, actor_idx, flip)
+
+    def pair_positions_bwd(self, spec, o, d, a, times, si, ai, flip, g_x01, g_cstd, need_o, need_d):
+        """-> grad actor_positions, grad actor_rotations_6d, dL/d origins | None, dL/d directions | None"""
+        if need_o or need_d:  # the rays move with a camera optimizer: the in-box samples' share of its gradient
+            gp, gr, go, gd = ops.actor_pair_positions_bwd(spec, o, d, a, self.starts, self.ends, times, si, ai, flip, g_x01,
+                                                          g_cstd, ray_grads=True)
+            return gp, gr, (go if need_o else None), (gd if need_d else None)
+        return (*ops.actor_pair_positions_bwd(spec, o, d, a, self.starts, self.ends, times, si, ai, flip, g_x01, g_cstd), None, None)
 
     def table_grad(self, spec, scale, o, d, a, genc, out_dtype):
         """grad table [L*T, F] from dL/d(rescaled features)"""
-        if self.segments is None:
-            return ops.encode_bwd(spec, scale, o, d, a, self.starts, self.ends, genc, out_dtype=out_dtype)
-        return ops.encode_bwd_packed(spec, scale, o, d, a, self.starts, self.ends, self.ray_indices, genc, out_dtype=out_dtype)
+        return ops.encode_bwd(spec, scale, o, d, a, self.starts, self.ends, genc, out_dtype=out_dtype)
 
     def ray_grads(self, spec, table, scale, o, d, a, genc):
         """dL/d origins, dL/d directions [R,3] from dL/d(rescaled features)"""
-        if self.segments is None:
-            return ops.encode_bwd_rays(spec, table, scale, o, d, a, self.starts, self.ends, genc)
+        return ops.encode_bwd_rays(spec, table, scale, o, d, a, self.starts, self.ends, genc)
+
+
+class PackedSamples:
+    """`DenseSamples` for the occupancy march's ragged output: starts / ends are t_starts / t_ends [M], segments int64 [R+1]
+    bounds each ray's samples and ray_indices int64 [M] names each sample's ray (an operation needs one or the other).
+    Compositing as PackedCompositeFn: no sky residual, depth = sum w mid over all samples, zeros for a ray without samples;
+    no appearance embedding (callers append it per ray); the rays get no gradient through the pair positions."""
+
+    def __init__(self, starts, ends, segments=None, ray_indices=None):
+        self.starts, self.ends, self.segments, self.ray_indices = starts, ends, segments, ray_indices
+
+    def saved(self):
+        return (self.starts, self.ends, self.segments, self.ray_indices), PackedSamples
+
+    def empty_outputs(self, device):
+        if self.starts.numel():
+            return None
+        z = lambda *shape: torch.zeros(shape, device=device, dtype=torch.float32)  # noqa: E731
+        R = self.segments.shape[0] - 1
+        return z(R, 32), z(R, 1), z(R, 1), z(0)
+
+    def cand_samples(self, pixel_area):
+        return None
+
+    def field_fwd_train(self, fs, o, d, a, order, override):
+        return ops.field_fwd_train_packed(fs, o, d, a, self.starts, self.ends, self.segments, order=order, override=override)
+
+    def render_fwd(self, geo, beta, beta_min, feature):
+        """head + packed compositing -> alpha [M], weights [M], features [R,C], depth [R,1], acc [R,1]"""
+        return ops.sdf_render_packed_fwd(geo, beta, beta_min, feature, self.starts, self.ends, self.segments)
+
+    def render_bwd(self, geo, beta, beta_min, alpha, feature, g_out, g_depth, g_acc, g_w, need):
+        return (*ops.sdf_render_packed_bwd(geo, beta, beta_min, alpha, feature, self.starts, self.ends, self.segments, g_out,
+                                           g_depth, g_acc, g_w), (None,) * 4)
+
+    def actor_geometry(self, spec, cand, o, d, a, flip, out_dim):
+        return ops.actor_find_packed(spec, cand, o, d, a, self.starts, self.ends, self.ray_indices, flip)  # (no scratch rows)
+
+    def pair_positions(self, spec, o, d, a, times, sample_idx, actor_idx, flip):
+        return ops.actor_pair_positions_packed(spec, o, d, a, self.starts, self.ends, self.ray_indices, times, sample_idx,
+                                               actor_idx, flip)
+
+    def pair_positions_bwd(self, spec, o, d, a, times, si, ai, flip, g_x01, g_cstd, need_o, need_d):
+        return (*ops.actor_pair_positions_packed_bwd(spec, o, d, a, self.starts, self.ends, self.ray_indices, times, si, ai,
+                                                     flip, g_x01, g_cstd), None, None)
+
+    def table_grad(self, spec, scale, o, d, a, genc, out_dtype):
+        return ops.encode_bwd_packed(spec, scale, o, d, a, self.starts, self.ends, self.ray_indices, genc, out_dtype=out_dtype)
+
+    def ray_grads(self, spec, table, scale, o, d, a, genc):
         return ops.encode_bwd_rays_packed(spec, table, scale, o, d, a, self.starts, self.ends, self.segments, genc)
 
 
@@ -55,7 +165,7 @@ class RayGrads(NamedTuple):
     need_d: bool
 
 
-def _ray_grads(want: Optional[RayGrads], spec, scale, o, d, a, samples: Samples, genc):
+def _ray_grads(want: Optional[RayGrads], spec, scale, o, d, a, samples, genc):
     """(dL/d origins, dL/d directions) of a static encoding from dL/d(rescaled features), None where not needed"""
     if want is None or not (want.need_o or want.need_d):
         return None, None
@@ -93,50 +203,30 @@ class ActorPairPositionsFn(torch.autograd.Function):
     """Box-frame contracted positions of (sample, actor) pairs, differentiable w.r.t. the trajectory parameters
     (interpolate_trajectories_6d -> rotation_6d_to_matrix -> pose inverse -> transform -> flip -> contraction, see
     csrc/actors.hip).  args: actor_positions [Tn,A,3], actor_rotations_6d [Tn,A,6] (the tensors inside ``spec``, passed
-    so that autograd sees them), spec, origins, directions, pixel_area, starts, ends, times, sample_idx, actor_idx, flip.
-    -> x01 [P,3], cstd [P]"""
+    so that autograd sees them), spec, origins, directions, pixel_area, starts, ends, times, sample_idx, actor_idx, flip
+    -- dense samples: starts / ends [R,S], sample_idx [P] a flat sample index -- and for the occupancy march's packed
+    samples ray_indices int64 [M]: starts / ends are t_starts / t_ends [M], sample_idx is a packed sample index, times and
+    flip stay per RAY, and the rays get no gradient (callers refuse rays that require grad).  -> x01 [P,3], cstd [P]"""
 
     @staticmethod
     def forward(ctx, positions, rotations_6d, spec, origins, directions, pixel_area, starts, ends, times, sample_idx,
-                actor_idx, flip):
+                actor_idx, flip, ray_indices=None):
         ctx.spec, ctx.flip = spec, flip
-        ctx.save_for_backward(origins, directions, pixel_area, starts, ends, times, sample_idx, actor_idx)
-        return ops.actor_pair_positions(spec, origins, directions, pixel_area, starts, ends, times, sample_idx, actor_idx,
-                                        flip)
+        ctx.save_for_backward(origins, directions, pixel_area, starts, ends, times, sample_idx, actor_idx, ray_indices)
+        return _pair_samples(starts, ends, ray_indices).pair_positions(spec, origins, directions, pixel_area, times,
+                                                                       sample_idx, actor_idx, flip)
 
     @staticmethod
     def backward(ctx, g_x01, g_cstd):
-        o, d, a, s, e, times, si, ai = ctx.saved_tensors
-        need_o, need_d = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
-        if need_o or need_d:  # the rays move with a camera optimizer: the in-box samples' share of its gradient
-            gp, gr, go, gd = ops.actor_pair_positions_bwd(ctx.spec, o, d, a, s, e, times, si, ai, ctx.flip,
-                                                          g_x01.contiguous(), g_cstd.contiguous(), ray_grads=True)
-            return (gp, gr, None, go if need_o else None, gd if need_d else None) + (None,) * 7
-        gp, gr = ops.actor_pair_positions_bwd(ctx.spec, o, d, a, s, e, times, si, ai, ctx.flip, g_x01.contiguous(),
-                                              g_cstd.contiguous())
-        return (gp, gr) + (None,) * 10
+        o, d, a, s, e, times, si, ai, ri = ctx.saved_tensors
+        gp, gr, go, gd = _pair_samples(s, e, ri).pair_positions_bwd(
+            ctx.spec, o, d, a, times, si, ai, ctx.flip, g_x01.contiguous(), g_cstd.contiguous(), ctx.needs_input_grad[3],
+            ctx.needs_input_grad[4])
+        return (gp, gr, None, go, gd) + (None,) * (len(ctx.needs_input_grad) - 5)
 
 
-class ActorPairPositionsPackedFn(torch.autograd.Function):
-    """ActorPairPositionsFn for the occupancy march's packed samples: sample_idx [P] is a packed sample index, ray_indices
-    int64 [M] names each sample's ray, times and flip are per RAY.  The rays get no gradient here (callers refuse rays that
-    require grad).  args: actor_positions, actor_rotations_6d, spec, origins [R,3], directions [R,3], pixel_area [R],
-    t_starts [M], t_ends [M], ray_indices, times [R], sample_idx, actor_idx, flip [R] | None -> x01 [P,3], cstd [P]"""
-
-    @staticmethod
-    def forward(ctx, positions, rotations_6d, spec, origins, directions, pixel_area, t_starts, t_ends, ray_indices, times,
-                sample_idx, actor_idx, flip):
-        ctx.spec, ctx.flip = spec, flip
-        ctx.save_for_backward(origins, directions, pixel_area, t_starts, t_ends, ray_indices, times, sample_idx, actor_idx)
-        return ops.actor_pair_positions_packed(spec, origins, directions, pixel_area, t_starts, t_ends, ray_indices, times,
-                                               sample_idx, actor_idx, flip)
-
-    @staticmethod
-    def backward(ctx, g_x01, g_cstd):
-        o, d, a, s, e, ri, times, si, ai = ctx.saved_tensors
-        gp, gr = ops.actor_pair_positions_packed_bwd(ctx.spec, o, d, a, s, e, ri, times, si, ai, ctx.flip,
-                                                     g_x01.contiguous(), g_cstd.contiguous())
-        return (gp, gr) + (None,) * 11
+def _pair_samples(starts, ends, ray_indices):
+    return DenseSamples(starts, ends) if ray_indices is None else PackedSamples(starts, ends, ray_indices=ray_indices)
 
 
 class MultiHashGridFn(torch.autograd.Function):
@@ -269,7 +359,7 @@ class EncodeFn(torch.autograd.Function):
         g = g.contiguous()
         gt = ops.encode_bwd(ctx.spec, ctx.scale, o, d, a, s, e, g, out_dtype=ctx.table_dtype) if ctx.needs_input_grad[0] else None
         want = RayGrads(tab[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]) if ctx.rays else None
-        go, gd = _ray_grads(want, ctx.spec, ctx.scale, o, d, a, Samples(s, e), g)
+        go, gd = _ray_grads(want, ctx.spec, ctx.scale, o, d, a, DenseSamples(s, e), g)
         return _like_param(gt, ctx.table_dtype), None, None, go, gd, None, None, None
 
 
@@ -304,12 +394,12 @@ class FieldTrainFn(torch.autograd.Function):
         if ctx.rays:
             params, rays = params[:-1], RayGrads(params[-1], ctx.needs_input_grad[5], ctx.needs_input_grad[6])
         gt, grads, _, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a,
-                                                 Samples(s, e), enc, hg, xf, hf, params, g_feature.contiguous(), g_geo_out,
+                                                 DenseSamples(s, e), enc, hg, xf, hf, params, g_feature.contiguous(), g_geo_out,
                                                  rays=rays)
         return (gt, None, None, None, None, go, gd, None, None, None, *grads, *([None] if ctx.has_order else []))
 
 
-def _field_backward(spec, scale, table_dtype, need_table, o, d, a, samples: Samples, enc, hg, xf, hf, params, g_feature,
+def _field_backward(spec, scale, table_dtype, need_table, o, d, a, samples, enc, hg, xf, hf, params, g_feature,
                     g_geo_out, override=None, rays: Optional[RayGrads] = None):
     """Backward of the fused field forward from (dL/dfeature [N,32], dL/dgeo_out [N]): feature-MLP gradients -> residual ->
     geometry-MLP gradients -> table gradient.  -> (grad table or None, the ten MLP parameter gradients in argument order,
@@ -606,7 +696,7 @@ class ProposalDensityFn(torch.autograd.Function):
         go, gd = (None, None)
         if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
             go, gd = _ray_grads(RayGrads(ctx.ps.table, ctx.needs_input_grad[4], ctx.needs_input_grad[5]), ctx.ps.grid,
-                                ctx.ps.static_scale, o, d, a, Samples(s, e), _proposal_genc(dens, g, ctx.ps.decoder_weight))
+                                ctx.ps.static_scale, o, d, a, DenseSamples(s, e), _proposal_genc(dens, g, ctx.ps.decoder_weight))
         return gt, gdec, None, None, go, gd, None, None, None
 
 
@@ -685,7 +775,7 @@ class ProposalRoundFn(torch.autograd.Function):
         go, gd = (None, None)
         if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:  # the rays moved with a camera optimizer
             go, gd = _ray_grads(RayGrads(ctx.ps.table, ctx.needs_input_grad[4], ctx.needs_input_grad[5]), ctx.ps.grid,
-                                ctx.ps.static_scale, o, d, a, Samples(starts, ends),
+                                ctx.ps.static_scale, o, d, a, DenseSamples(starts, ends),
                                 _proposal_genc(dens, gdens, ctx.ps.decoder_weight))
         return gt, gdec, None, None, go, gd, None, None
 
@@ -712,178 +802,71 @@ class PropWeightsFn(torch.autograd.Function):
 
 
 class NffRenderTrainFn(torch.autograd.Function):
-    """get_nff_outputs behind the sampler (models/neurad.py:373-395) for the static scene as ONE node: fused field forward
-    (NeuRADField.forward) -> SigmoidDensity with the learnable beta -> render_weight_from_alpha -> accumulation, sky
-    residual, features, depth -> appearance embedding written beside the features.
+    """get_nff_outputs behind the sampler (models/neurad.py:373-395) as ONE node: fused field forward (NeuRADField.forward)
+    -> SigmoidDensity with the learnable beta -> weights -> compositing, on dense samples given by their bin edges
+    (`DenseSamples.on_edges`: render_weight_from_alpha, accumulation, sky residual, features, depth, appearance embedding
+    written beside the features) or on the occupancy march's packed samples (`PackedSamples`).  What differs between the
+    two is the layout's; the t_starts / t_ends of a march are constants (it is no_grad).
 
     beta = None: the density head (use_sdf = False: trunc_exp -> render_weight_from_density, models/neurad.py:718-723).
-    args: table, spec, static_scale, beta (raw parameter), beta_min, origins, directions, pixel_area, edges [R,S+1] (last
-    edge = sky distance), emb_weight | None, sensor_idx | None, times | None, (duration, n_per_sensor, temporal), order |
-    None, ovr_row | None, ovr_rows | None, ovr_dirs | None, pair_idx | None (dynamic actors: the rows of the samples
-    inside a box, ops.field_fwd_train), gw0, gb0, gw1, gb1, fw0, fb0, fw1, fb1, fw2, fb2
-    -> features [R, 32 + A], depth [R,1], accumulation [R,1], weights of the non-sky samples [R,S-1]"""
+    Dynamic actors: the samples inside an actor box take their encoding row and view direction from the caller
+    (``override`` of ops.field_fwd_train / _packed); the backward hands dL/d enc of those samples to ``ovr_rows`` (every
+    (sample, actor) pair gets its sample's row) and sends nothing of them to the static table.  Origins / directions that
+    require grad (a camera optimizer moved them) get their gradient through the static encoding from the dL/d enc the
+    backward forms anyway -- the table is saved for that alone; with fixed rays nothing extra is saved or launched.
+
+    args: table, spec, static_scale, beta (raw parameter) | None, beta_min, origins [R,3], directions [R,3], pixel_area [R],
+    order | None, ovr_row int32 [N] | None (row of ovr_rows or -1, per sample), ovr_rows [P,L*F] | None, ovr_dirs [P,3] | None,
+    pair_idx int64 [P] | None (the sample of each pair), gw0, gb0, gw1, gb1, fw0, fb0, fw1, fb1, fw2, fb2, then the layout:
+    DenseSamples.on_edges, edges [R,S+1], emb_weight | None, sensor_idx | None, times | None, (duration, n_per_sensor,
+    temporal) -- or PackedSamples, t_starts [M], t_ends [M], segments int64 [R+1], ray_indices int64 [M].  Its tensors are
+    arguments of their own: custom_fwd's cast walks the arguments and cannot rebuild an object that holds them.
+    -> dense: features [R, 32 + A], depth [R,1], accumulation [R,1], weights of the non-sky samples [R,S-1]
+       packed: features [R,32], depth [R,1], accumulation [R,1], weights [M]"""
 
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area, edges, emb_weight,
-                sensor_idx, times, emb_cfg, order, ovr_row, ovr_rows, ovr_dirs, pair_idx, *params):
-        ctx.set_materialize_grads(False)
+    def forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area, order, ovr_row, ovr_rows,
+                ovr_dirs, pair_idx, *rest):
+        ctx.set_materialize_grads(False)  # an output nobody used arrives as None, not as a tensor of zeros
+        params, samples = rest[:10], rest[10](*rest[11:])
+        out = samples.empty_outputs(origins.device)
+        ctx.empty = out is not None
+        if ctx.empty:  # answered on the host: nothing to launch, nothing to differentiate
+            return out
         gw, gb, fw, fb = list(params[0:4:2]), list(params[1:4:2]), list(params[4:10:2]), list(params[5:10:2])
         fs = ops.FieldSpec(spec, table, static_scale, gw, gb, fw, fb, use_sdf=True, beta=1.0)  # (kernel head unused)
-        override = None if ovr_rows is None else (ovr_row, ovr_rows, ovr_dirs)
-        (feature, sdf, _head), (enc, hg, xf, hf) = ops.field_fwd_train(fs, origins, directions, pixel_area, edges[:, :-1],
-                                                                      edges[:, 1:], order=order, override=override)
         ctx.has_ovr = ovr_rows is not None
-        R, S = edges.shape[0], edges.shape[1] - 1
-        A = 0 if emb_weight is None else emb_weight.shape[1]
-        alpha, w_ns, out, depth, acc = ops.sdf_render_fwd(sdf.view(R, S), beta, beta_min, feature.view(R, S, -1), edges,
-                                                          extra_cols=A)
-        if A:
-            ops.appearance_fwd(emb_weight, sensor_idx, times, emb_cfg[0], emb_cfg[1], emb_cfg[2], R, out=out[:, out.shape[1] - A:])
-        ctx.spec, ctx.scale, ctx.table_dtype, ctx.beta_min, ctx.emb_cfg = spec, static_scale, table.dtype, beta_min, emb_cfg
-        ctx.n_embed, ctx.A = (0 if emb_weight is None else emb_weight.shape[0]), A
-        ctx.has = (sensor_idx is not None, times is not None)
-        ctx.rays = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]  # a camera optimizer moved the rays
-        opt = ([t for t in (sensor_idx, times) if t is not None] + ([ovr_row, pair_idx] if ctx.has_ovr else [])
-               + ([table] if ctx.rays else []))
+        (feature, geo, _head), (enc, hg, xf, hf) = samples.field_fwd_train(
+            fs, origins, directions, pixel_area, order, (ovr_row, ovr_rows, ovr_dirs) if ctx.has_ovr else None)
+        alpha, w, out, depth, acc = samples.render_fwd(geo, beta, beta_min, feature)
+        ctx.spec, ctx.scale, ctx.table_dtype, ctx.beta_min = spec, static_scale, table.dtype, beta_min
         ctx.density_head = beta is None
-        ctx.save_for_backward(origins, directions, pixel_area, edges, enc, hg, xf, hf, feature, sdf, alpha,
-                              sdf.new_empty(0) if beta is None else beta, *params, *opt)
-        return out, depth, acc, w_ns
+        ctx.rays = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]  # a camera optimizer moved the rays
+        where, ctx.samples = samples.saved()
+        ctx.save_for_backward(origins, directions, pixel_area, enc, hg, xf, hf, feature, geo, alpha,
+                              geo.new_empty(0) if beta is None else beta, *params,
+                              *([ovr_row, pair_idx] if ctx.has_ovr else []), *([table] if ctx.rays else []), *where)
+        return out, depth, acc, w
 
     @staticmethod
     @custom_bwd(device_type="cuda")
-    def backward(ctx, g_out, g_depth, g_acc, g_wns):
-        o, d, a, edges, enc, hg, xf, hf, feature, sdf, alpha, beta, *rest = ctx.saved_tensors
+    def backward(ctx, g_out, g_depth, g_acc, g_w):
+        need = ctx.needs_input_grad
+        if ctx.empty or (g_out is None and g_depth is None and g_acc is None and g_w is None):
+            return (None,) * len(need)
+        o, d, a, enc, hg, xf, hf, feature, geo, alpha, beta, *rest = ctx.saved_tensors
         params, opt = rest[:10], list(rest[10:])
-        sensor_idx = opt.pop(0) if ctx.has[0] else None
-        times = opt.pop(0) if ctx.has[1] else None
-        R, S = edges.shape[0], edges.shape[1] - 1
-        C_ = feature.shape[-1]
-        if g_out is None:
-            g_out = torch.zeros((R, C_ + ctx.A), device=o.device, dtype=torch.float32)
-        gfeat, gsdf, gbeta = ops.sdf_render_bwd(sdf.view(R, S), None if ctx.density_head else beta, ctx.beta_min, alpha,
-                                                feature.view(R, S, C_), edges, g_out[:, :C_], g_depth, g_acc, g_wns)
-        g_emb = None
-        if ctx.A and ctx.needs_input_grad[9]:
-            g_emb = ops.appearance_bwd(g_out[:, C_:], sensor_idx, times, ctx.emb_cfg[0], ctx.emb_cfg[1], ctx.emb_cfg[2],
-                                       ctx.n_embed)
         override = (opt.pop(0), opt.pop(0)) if ctx.has_ovr else None
-        rays = RayGrads(opt.pop(0), ctx.needs_input_grad[5], ctx.needs_input_grad[6]) if ctx.rays else None
-        gt, grads, g_rows, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a,
-                                                      Samples(edges[:, :-1], edges[:, 1:]), enc, hg, xf, hf, params,
-                                                      gfeat.view(R * S, C_), gsdf.view(-1), override=override, rays=rays)
-        if not ctx.needs_input_grad[15]:
-            g_rows = None
-        g_beta = gbeta.reshape(beta.shape) if (ctx.needs_input_grad[3] and not ctx.density_head) else None
-        return (gt, None, None, g_beta, None, go, gd, None, None, g_emb, None, None, None, None, None, g_rows, None, None,
-                *grads)
-
-
-class NffRenderPackedTrainFn(torch.autograd.Function):
-    """NffRenderTrainFn for the occupancy march's packed samples (static scene): fused field forward on packed samples ->
-    head (SigmoidDensity with the learnable beta, or trunc_exp) + packed compositing -> features, depth, accumulation,
-    weights.  Compositing as PackedCompositeFn: no sky residual, depth = sum w mid over all samples, zeros for a ray
-    without samples.  No appearance embedding (callers append it per ray).  Origins / directions that require grad (a camera
-    optimizer moved them) get their gradient through the static encoding from ``ops.encode_bwd_rays_packed`` on the dL/d enc
-    the backward forms anyway -- the table is saved for it, as in NffRenderTrainFn; with fixed rays nothing extra is saved
-    and nothing extra is launched.  t_starts / t_ends are constants (the march is no_grad).
-
-    args: table, spec, static_scale, beta (raw parameter) | None (density head), beta_min, origins [R,3], directions [R,3],
-    pixel_area [R], t_starts [M], t_ends [M], segments int64 [R+1], ray_indices int64 [M], order | None, gw0, gb0, gw1,
-    gb1, fw0, fb0, fw1, fb1, fw2, fb2
-    -> features [R,32], depth [R,1], accumulation [R,1], weights [M]"""
-
-    @staticmethod
-    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area, t_starts, t_ends, segments,
-                ray_indices, order, *params):
-        return _packed_train_forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area,
-                                     t_starts, t_ends, segments, ray_indices, order, params)
-
-    @staticmethod
-    @custom_bwd(device_type="cuda")
-    def backward(ctx, g_out, g_depth, g_acc, g_w):
-        back = _packed_train_backward(ctx, g_out, g_depth, g_acc, g_w)
-        if back is None:
-            return (None,) * 23
-        gt, g_beta, go, gd, _, grads = back
-        return (gt, None, None, g_beta, None, go, gd, *([None] * 6), *grads)
-
-
-def _packed_train_forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area, t_starts, t_ends,
-                          segments, ray_indices, order, params, override=None, pair_idx=None):
-    """forward of the two packed training nodes.  override = (ovr_row [M], ovr_rows [P,L*F], ovr_dirs [P,3]) with pair_idx [P]
-    (dynamic actors) or None (the static scene: the launches of the static node).  In both nodes origins / directions are
-    inputs 5 / 6."""
-    ctx.set_materialize_grads(False)
-    R, M = segments.shape[0] - 1, t_starts.numel()
-    ctx.empty = M == 0
-    if ctx.empty:  # answered on the host: nothing to launch, nothing to differentiate
-        z = lambda *shape: torch.zeros(shape, device=origins.device, dtype=torch.float32)  # noqa: E731
-        return z(R, 32), z(R, 1), z(R, 1), z(0)
-    gw, gb, fw, fb = list(params[0:4:2]), list(params[1:4:2]), list(params[4:10:2]), list(params[5:10:2])
-    fs = ops.FieldSpec(spec, table, static_scale, gw, gb, fw, fb, use_sdf=True, beta=1.0)  # (kernel head unused)
-    extra = {} if override is None else {"override": override}
-    (feature, geo, _head), (enc, hg, xf, hf) = ops.field_fwd_train_packed(fs, origins, directions, pixel_area, t_starts,
-                                                                          t_ends, segments, order=order, **extra)
-    alpha, w, out, depth, acc = ops.sdf_render_packed_fwd(geo, beta, beta_min, feature, t_starts, t_ends, segments)
-    ctx.spec, ctx.scale, ctx.table_dtype, ctx.beta_min = spec, static_scale, table.dtype, beta_min
-    ctx.density_head = beta is None
-    ctx.has_ovr = override is not None
-    ctx.rays = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]  # a camera optimizer moved the rays
-    ctx.save_for_backward(origins, directions, pixel_area, t_starts, t_ends, segments, ray_indices, enc, hg, xf, hf,
-                          feature, geo, alpha, geo.new_empty(0) if beta is None else beta, *params,
-                          *([override[0], pair_idx] if ctx.has_ovr else []), *([table] if ctx.rays else []))
-    return out, depth, acc, w
-
-
-def _packed_train_backward(ctx, g_out, g_depth, g_acc, g_w):
-    """-> None (nothing to differentiate) or (grad table, grad beta, grad origins, grad directions, grad of the override
-    rows or None, the ten MLP parameter gradients)"""
-    if ctx.empty or (g_out is None and g_depth is None and g_acc is None and g_w is None):
-        return None
-    o, d, a, ts, te, seg, ri, enc, hg, xf, hf, feature, geo, alpha, beta, *rest = ctx.saved_tensors
-    params, opt = rest[:10], list(rest[10:])
-    gfeat, ggeo, gbeta = ops.sdf_render_packed_bwd(geo, None if ctx.density_head else beta, ctx.beta_min, alpha, feature,
-                                                   ts, te, seg, g_out, g_depth, g_acc, g_w)
-    override = (opt.pop(0), opt.pop(0)) if ctx.has_ovr else None
-    rays = RayGrads(opt.pop(0), ctx.needs_input_grad[5], ctx.needs_input_grad[6]) if ctx.rays else None
-    gt, grads, g_rows, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, ctx.needs_input_grad[0], o, d, a,
-                                                  Samples(ts, te, seg, ri), enc, hg, xf, hf, params, gfeat, ggeo,
-                                                  override=override, rays=rays)
-    g_beta = gbeta.reshape(beta.shape) if (ctx.needs_input_grad[3] and not ctx.density_head) else None
-    return gt, g_beta, go, gd, g_rows, grads
-
-
-class NffRenderPackedActorsTrainFn(torch.autograd.Function):
-    """NffRenderPackedTrainFn with ROW OVERRIDES: the packed training node of a scene with dynamic actors.  The samples inside
-    an actor box take their encoding row and view direction from the caller (ops.field_fwd_train_packed with ``override``),
-    exactly as NffRenderTrainFn does on dense samples; the backward hands dL/d enc of those samples to ``ovr_rows`` (every
-    (sample, actor) pair gets its sample's row) and sends nothing of them to the static table.
-
-    args: as NffRenderPackedTrainFn up to ``order``, then ovr_row int32 [M] (row of ovr_rows or -1, at the packed sample
-    index), ovr_rows [P,L*F], ovr_dirs [P,3], pair_idx int64 [P] (the packed sample index of each pair), then the ten MLP
-    parameters -> features [R,32], depth [R,1], accumulation [R,1], weights [M]"""
-
-    @staticmethod
-    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area, t_starts, t_ends, segments,
-                ray_indices, order, ovr_row, ovr_rows, ovr_dirs, pair_idx, *params):
-        return _packed_train_forward(ctx, table, spec, static_scale, beta, beta_min, origins, directions, pixel_area,
-                                     t_starts, t_ends, segments, ray_indices, order, params,
-                                     override=(ovr_row, ovr_rows, ovr_dirs), pair_idx=pair_idx)
-
-    @staticmethod
-    @custom_bwd(device_type="cuda")
-    def backward(ctx, g_out, g_depth, g_acc, g_w):
-        back = _packed_train_backward(ctx, g_out, g_depth, g_acc, g_w)
-        if back is None:
-            return (None,) * 27
-        gt, g_beta, go, gd, g_rows, grads = back
-        if not ctx.needs_input_grad[14]:
-            g_rows = None
-        return (gt, None, None, g_beta, None, go, gd, *([None] * 6), None, g_rows, None, None, *grads)
+        rays = RayGrads(opt.pop(0), need[5], need[6]) if ctx.rays else None
+        samples = ctx.samples(*opt)
+        gfeat, ggeo, gbeta, g_where = samples.render_bwd(geo, None if ctx.density_head else beta, ctx.beta_min, alpha, feature,
+                                                         g_out, g_depth, g_acc, g_w, need[24:])
+        gt, grads, g_rows, (go, gd) = _field_backward(ctx.spec, ctx.scale, ctx.table_dtype, need[0], o, d, a, samples, enc, hg,
+                                                      xf, hf, params, gfeat, ggeo, override=override, rays=rays)
+        g_beta = gbeta.reshape(beta.shape) if (need[3] and not ctx.density_head) else None
+        return (gt, None, None, g_beta, None, go, gd, None, None, None, g_rows if need[10] else None, None, None, *grads,
+                None, *g_where)
 
 
 class LidarLossFn(torch.autograd.Function):

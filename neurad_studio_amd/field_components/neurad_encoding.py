@@ -245,14 +245,9 @@ class NeuRADHashEncoding(nn.Module):
         spec = self.actor_spec()
         pose_grad = torch.is_grad_enabled() and self.config.require_actor_grad
         with torch.set_grad_enabled(pose_grad):
-            if ray_indices is None:
-                x01, cstd = ag.ActorPairPositionsFn.apply(self.actors.actor_positions, self.actors.actor_rotations_6d, spec,
-                                                          origins, directions, pixel_area.reshape(-1), starts, ends, times,
-                                                          idx, act, flip)
-            else:
-                x01, cstd = ag.ActorPairPositionsPackedFn.apply(
-                    self.actors.actor_positions, self.actors.actor_rotations_6d, spec, origins, directions,
-                    pixel_area.reshape(-1), starts, ends, ray_indices, times, idx, act, flip)
+            x01, cstd = ag.ActorPairPositionsFn.apply(self.actors.actor_positions, self.actors.actor_rotations_6d, spec,
+                                                      origins, directions, pixel_area.reshape(-1), starts, ends, times,
+                                                      idx, act, flip, *(() if ray_indices is None else (ray_indices,)))
         act = act.long()
         ids = self.actors.actor_to_id[act]
         # _get_actor_features_slow loops over the actor ids; all actor grids share one shape, so one multi-grid

@@ -141,6 +141,8 @@ class NeuRADField(nn.Module):
             param_groups["fields"] += list(self.sdf_to_density.parameters())
 
     # ---- fused path -----------------------------------------------------------------------------
+    # The gates: each is a line over the same two facts -- which configurations the kernels are instantiated for
+    # (``fused_supported``) and whether every layer has a bias (``_fused_train_ok``, the training forward's own condition).
     def fused_supported(self, with_actors: bool = False) -> bool:
         """Can the fused kernels evaluate this field?  ``with_actors``: the composited eval kernel also covers scenes
         with dynamic actors (per-sample table select, nrhip_render_fwd_actors) when the actor grids share the static
@@ -159,6 +161,15 @@ class NeuRADField(nn.Module):
         return ((g.num_levels, g.features_per_level) in _FUSED_GRIDS and c.geo_num_layers == 2 and c.nff_num_layers == 3
                 and c.geo_hidden_dim == c.nff_hidden_dim and c.geo_hidden_dim in (32, 64) and c.nff_out_dim == 32)
 
+    def _fused_train_ok(self) -> bool:
+        """The fused training forward needs biases on every layer (fp32 or fp16-storage table: the kernel reads either,
+        the table gradient is formed in fp32 and handed to autograd in the table's dtype)."""
+        return all(l.bias is not None for l in list(self.mlp_geo.layers) + list(self.mlp_feature.layers))
+
+    def fused_train_supported(self) -> bool:
+        """Can ``render_train`` train this field, static or with its dynamic actors, on dense samples as one node?"""
+        return self.fused_supported(with_actors=True) and self._fused_train_ok()
+
     def fused_packed_supported(self) -> bool:
         """Can the fused render kernel composite this field's PACKED samples (``render_packed``)?  The static scene of every
         field ``fused_supported`` covers: the packed kernels are the table's composited static rows (csrc/render_variants.h:
@@ -175,6 +186,12 @@ class NeuRADField(nn.Module):
         """Can ``render_train_packed`` train this field on PACKED samples as one node?  ``fused_packed_supported`` (static
         scene, a fused configuration) with the fused training forward's own condition (biases on every layer)."""
         return self.fused_packed_supported() and self._fused_train_ok()
+
+    def fused_packed_actors_train_supported(self) -> bool:
+        """Can ``render_train_packed(..., times=...)`` train this field's scene WITH its dynamic actors on PACKED samples as
+        one node?  ``fused_packed_actors_supported`` (an actor field of a fused configuration: the packed override kernels
+        are the table's `PerSample, Overrides, F32` rows) with the fused training forward's own condition (biases)."""
+        return self.fused_packed_actors_supported() and self._fused_train_ok()
 
     def train(self, mode: bool = True):
         """a mode switch drops the cached host copy of beta: writes through ``beta.data`` (EMA / weight averaging, some
@@ -203,13 +220,40 @@ class NeuRADField(nn.Module):
             self._beta_cache = (key, float(self.sdf_to_density.get_beta().detach()))
         return self._beta_cache[1]
 
+    def _mlp_params(self) -> list:
+        """gw0, gb0, gw1, gb1, fw0, fb0, fw1, fb1, fw2, fb2: the order the fused nodes take the MLP parameters in"""
+        return [t for l in self.mlp_geo.layers for t in (l.weight, l.bias)] + \
+               [t for l in self.mlp_feature.layers for t in (l.weight, l.bias)]
+
+    def _beta_args(self) -> Tuple[Optional[Tensor], float]:
+        """(beta, beta_min) of the render nodes; use_sdf = False (fields/neurad_field.py:149-151): beta = None selects
+        the density head in the node"""
+        return (self.sdf_to_density.beta, self.sdf_to_density.beta_min_value) if self.config.use_sdf else (None, 0.0)
+
     def field_spec(self) -> ops.FieldSpec:
         g = self.hashgrid.static_grid
-        beta = self._beta_value()
-        return ops.FieldSpec(g.spec, g.hash_table.detach(), self.hashgrid.static_scale,
-                             [l.weight.detach() for l in self.mlp_geo.layers], [l.bias.detach() for l in self.mlp_geo.layers],
-                             [l.weight.detach() for l in self.mlp_feature.layers],
-                             [l.bias.detach() for l in self.mlp_feature.layers], use_sdf=self.config.use_sdf, beta=beta)
+        p = [t.detach() for t in self._mlp_params()]
+        return ops.FieldSpec(g.spec, g.hash_table.detach(), self.hashgrid.static_scale, p[0:4:2], p[1:4:2], p[4:10:2],
+                             p[5:10:2], use_sdf=self.config.use_sdf, beta=self._beta_value())
+
+    def _actor_cand(self, actor_cand, origins, directions, times, samples=None):
+        """(ActorSpec, the candidate lists of a ray batch): the caller's -- they depend on the ray's line only, so one list
+        per ray batch serves every field -- or computed here, from ``samples`` = (pixel_area, starts, ends) [R,S] of the
+        batch (``prepare_actors``) or, without them, from the rays' points at t = 0 and 1 (``prepare_actors_line``)"""
+        hg = self.hashgrid
+        if actor_cand is not None:
+            return hg.actor_spec(), actor_cand
+        if samples is not None:
+            return hg.prepare_actors(origins, directions, *samples, times)
+        return hg.prepare_actors_line(origins, directions, 0.0, 1.0, times)
+
+    @staticmethod
+    def _check_packed_args(who, segments, ray_indices, num_rays):
+        """packed samples come with exactly one of segments / ray_indices + num_rays; ``who``: the calling method"""
+        if (segments is None) == (ray_indices is None):
+            raise ValueError(f"{who}: give exactly one of segments / ray_indices (+ num_rays)")
+        if ray_indices is not None and num_rays is None:
+            raise ValueError(f"{who}: ray_indices needs num_rays")
 
     @torch.no_grad()
     def render(self, origins, directions, pixel_area, starts, ends, return_weights=False, early_stop_eps: float = 0.0,
@@ -221,12 +265,9 @@ class NeuRADField(nn.Module):
         if not self.fused_supported(with_actors=True):
             raise NotImplementedError("fused render kernel: configuration not instantiated; use forward() + renderers")
         if self.hashgrid.has_actors():
-            if actor_cand is not None:
-                spec, cand = self.hashgrid.actor_spec(), actor_cand
-            elif times is None:
+            if actor_cand is None and times is None:
                 raise ValueError("dynamic actors need ray times")
-            else:
-                spec, cand = self.hashgrid.prepare_actors(origins, directions, pixel_area, starts, ends, times)
+            spec, cand = self._actor_cand(actor_cand, origins, directions, times, (pixel_area, starts, ends))
             return ops.render_fwd_actors(self.field_spec(), spec, cand, origins, directions, pixel_area, starts, ends,
                                          return_weights, early_stop_eps=early_stop_eps, order=order)
         return ops.render_fwd(self.field_spec(), origins, directions, pixel_area, starts, ends, return_weights,
@@ -244,10 +285,7 @@ class NeuRADField(nn.Module):
         A scene with dynamic actors (``fused_packed_actors_supported``) needs ``times`` [R], the rays' times, or ``actor_cand``,
         the per-RAY candidate lists already computed (``hashgrid.prepare_actors_line``; a march with boxes shares them): a sample
         inside an actor's box then reads that actor's grid, as in ``render``.  Without either an actor field is refused."""
-        if (segments is None) == (ray_indices is None):
-            raise ValueError("render_packed: give exactly one of segments / ray_indices (+ num_rays)")
-        if ray_indices is not None and num_rays is None:
-            raise ValueError("render_packed: ray_indices needs num_rays")
+        self._check_packed_args("render_packed", segments, ray_indices, num_rays)
         if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or any(
                 isinstance(t, Tensor) and t.requires_grad for t in (origins, directions, t_starts, t_ends))):
             raise RuntimeError("render_packed has no backward: call it under torch.no_grad(); a grad-enabled call goes "
@@ -261,10 +299,7 @@ class NeuRADField(nn.Module):
             if segments is None:
                 segments = ops.packed_segments(ray_indices, int(num_rays))
             if with_actors:
-                if actor_cand is not None:
-                    spec, cand = self.hashgrid.actor_spec(), actor_cand
-                else:
-                    spec, cand = self.hashgrid.prepare_actors_line(origins, directions, 0.0, 1.0, times)
+                spec, cand = self._actor_cand(actor_cand, origins, directions, times)
                 return ops.render_fwd_packed_actors(self.field_spec(), spec, cand, origins, directions, pixel_area, t_starts,
                                                     t_ends, segments, return_weights, early_stop_eps=early_stop_eps,
                                                     order=order)
@@ -275,7 +310,7 @@ class NeuRADField(nn.Module):
                             ray_indices: Optional[Tensor] = None, num_rays: Optional[int] = None,
                             ray_gradients: bool = False, times: Optional[Tensor] = None, actor_cand=None):
         """Training counterpart of ``render_packed``: field -> head (learnable-beta SDF head, or trunc_exp) -> packed
-        compositing as ONE autograd node (autograd.NffRenderPackedTrainFn).  Arguments as ``render_packed``: per-RAY origins
+        compositing as ONE autograd node (autograd.NffRenderTrainFn on autograd.PackedSamples).  Arguments as ``render_packed``: per-RAY origins
         / directions [R,3] and pixel_area [R] (or [R,1]), per-sample t_starts / t_ends [M], exactly one of ``segments`` int64
         [R+1] or ``ray_indices`` int64 [M] (sorted) + ``num_rays``; the other one is derived on the device.
         -> features [R,32], depth [R,1] (sum w mid), accumulation [R,1], weights [M]; compositing as
@@ -287,7 +322,7 @@ class NeuRADField(nn.Module):
         Dynamic actors (``fused_packed_actors_train_supported``): ``times`` [R], the rays' times -- with ``actor_cand``, the
         per-RAY candidate lists already computed (``hashgrid.prepare_actors_line``; a march with boxes shares them), they
         are not computed again; ``actor_cand`` alone is a ValueError, the pair positions need the times -- select
-        the node with row overrides (autograd.NffRenderPackedActorsTrainFn), built as ``render_train`` builds it on dense
+        the node with row overrides (the same node's ``override`` arguments), built as ``render_train`` builds it on dense
         samples: the kernels find which packed samples lie in which box (ops.actor_find_packed), ``actor_pair_rows``
         produces their rows differentiably, and the fused forward takes them and their box-frame view directions in place
         of the static lookup.  Gradients then also reach the actor grids and, with ``require_actor_grad``, the
@@ -297,12 +332,9 @@ class NeuRADField(nn.Module):
         require grad are refused even under ``ray_gradients=True``: the actor branch's ray gradient is not built on packed
         samples.  Without ``times`` / ``actor_cand`` an actor field is refused as before.  One host read (the number of
         pairs): not graph-capturable, like the dense actor node."""
-        if (segments is None) == (ray_indices is None):
-            raise ValueError("render_train_packed: give exactly one of segments / ray_indices (+ num_rays)")
-        if ray_indices is not None and num_rays is None:
-            raise ValueError("render_train_packed: ray_indices needs num_rays")
+        self._check_packed_args("render_train_packed", segments, ray_indices, num_rays)
         operator = "use the operator route, forward() on the packed RaySamples + renderers.render_packed"
-        hg, g = self.hashgrid, self.hashgrid.static_grid
+        hg = self.hashgrid
         with_actors = hg.has_actors() and (times is not None or actor_cand is not None)
         if with_actors:
             if not self.fused_packed_actors_train_supported():
@@ -326,53 +358,11 @@ class NeuRADField(nn.Module):
             else:
                 ray_indices = ops.packed_ray_indices(segments, t_starts.shape[0])
             order = ops.ray_order(origins, directions, hg.static_scale) if (self.order_rays and origins.shape[0]) else None
-        beta, beta_min = (self.sdf_to_density.beta, self.sdf_to_density.beta_min_value) if self.config.use_sdf else (None, 0.0)
-        head = (g.hash_table, g.spec, hg.static_scale, beta, beta_min, origins, directions, pixel_area.reshape(-1), t_starts,
-                t_ends, segments, ray_indices.reshape(-1), order)
-        params = [t for l in self.mlp_geo.layers for t in (l.weight, l.bias)] + \
-                 [t for l in self.mlp_feature.layers for t in (l.weight, l.bias)]
+        where = (t_starts, t_ends, segments, ray_indices.reshape(-1))
+        ovr = None
         if with_actors and t_starts.shape[0] and origins.shape[0]:
-            ovr = self._actor_overrides_packed(origins, directions, pixel_area.reshape(-1), t_starts, t_ends,
-                                               ray_indices.reshape(-1), None if times is None else times.reshape(-1),
-                                               actor_cand)
-            if ovr is not None:
-                return ag.NffRenderPackedActorsTrainFn.apply(*head, *ovr, *params)
-        return ag.NffRenderPackedTrainFn.apply(*head, *params)
-
-    def fused_packed_actors_train_supported(self) -> bool:
-        """Can ``render_train_packed(..., times=...)`` train this field's scene WITH its dynamic actors on PACKED samples as
-        one node?  ``fused_packed_actors_supported`` (an actor field of a fused configuration: the packed override kernels
-        are the table's `PerSample, Overrides, F32` rows) with the fused training forward's own condition (biases)."""
-        return self.fused_packed_actors_supported() and self._fused_train_ok()
-
-    def _actor_overrides_packed(self, origins, directions, pixel_area, t_starts, t_ends, ray_indices, times, actor_cand=None):
-        """``_actor_overrides`` on packed samples -> (ovr_row int32 [M], rows [P,L*F], box-frame view directions [P,3],
-        pair_idx [P]: packed sample index of every (sample, actor) pair), or None when no sample lies in a box.  No [M, L*F]
-        scratch rows: the geometry kernel writes none."""
-        hg = self.hashgrid
-        M = t_starts.shape[0]
-        if times is None:  # (actor_cand alone fixes the boxes, not the pair positions' poses)
-            raise ValueError("dynamic actors need ray times (the pair positions are interpolated at the ray's time)")
-        flip = hg.sample_ray_flip(origins)  # one draw per ray, as the dense node
-        with torch.no_grad():
-            if actor_cand is not None:
-                spec, cand = hg.actor_spec(), actor_cand
-            else:
-                spec, cand = hg.prepare_actors_line(origins, directions, 0.0, 1.0, times)
-            hits, hit, dirs = ops.actor_find_packed(spec, cand, origins, directions, pixel_area, t_starts, t_ends,
-                                                    ray_indices, flip)
-        pr =hg.actor_pair_rows(hit, hits, origins, directions, pixel_area, t_starts, t_ends, times, flip,
-                                ray_indices=ray_indices)
-        if pr is None:
-            return None
-        idx, winner, f = pr
-        rows = torch.nn.functional.pad(f, (0, hg.get_out_dim() - f.shape[1])).contiguous()
-        with torch.no_grad():
-            P = idx.shape[0]
-            slot = torch.where(winner, torch.arange(P, device=idx.device), -1)  # one winner per sample: amax picks it
-            ov = torch.full((M,), -1, device=idx.device, dtype=torch.int64).scatter_reduce_(0, idx, slot, reduce="amax")
-            pdirs = dirs.index_select(0, idx).contiguous()
-        return ov.to(torch.int32), rows, pdirs, idx
+            ovr = self._actor_overrides(ag.PackedSamples(*where), origins, directions, pixel_area.reshape(-1), times, actor_cand)
+        return self._render_node(origins, directions, pixel_area, order, ovr, ag.PackedSamples, *where)
 
     def render_train(self, origins, directions, pixel_area, edges, appearance=None, times: Optional[Tensor] = None,
                      actor_cand=None):
@@ -388,47 +378,46 @@ class NeuRADField(nn.Module):
         the static lookup (nrhip_field_fwd_train_ovr).  The backward hands every (sample, actor) pair its sample's row
         gradient, as the reference's index_put does, and the static table nothing for those samples."""
         hg = self.hashgrid
-        if not (self.fused_supported(with_actors=True) and self._fused_train_ok()):
+        if not self.fused_train_supported():
             raise NotImplementedError("render_train: a fused-kernel configuration only (see fused_supported)")
-        g = hg.static_grid
         emb, sensor, etimes, emb_cfg = appearance if appearance is not None else (None, None, None, (1.0, 1, False))
         order = ops.ray_order(origins, directions, hg.static_scale) if self.order_rays else None
-        ovr = (None, None, None, None)
+        ovr = None
         if hg.has_actors():
-            if times is None:
-                raise ValueError("dynamic actors need ray times")
-            ovr = self._actor_overrides(origins, directions, pixel_area.reshape(-1), edges, times.reshape(-1), actor_cand)
-        # use_sdf = False (fields/neurad_field.py:149-151): the density head -- beta = None selects it in the node
-        beta, beta_min = (self.sdf_to_density.beta, self.sdf_to_density.beta_min_value) if self.config.use_sdf else (None, 0.0)
-        return ag.NffRenderTrainFn.apply(
-            g.hash_table, g.spec, hg.static_scale, beta, beta_min, origins, directions,
-            pixel_area.reshape(-1), edges, emb, sensor, etimes, emb_cfg, order, *ovr,
-            *[t for l in self.mlp_geo.layers for t in (l.weight, l.bias)],
-            *[t for l in self.mlp_feature.layers for t in (l.weight, l.bias)])
+            ovr = self._actor_overrides(ag.DenseSamples.on_edges(edges), origins, directions, pixel_area.reshape(-1), times,
+                                        actor_cand)
+        return self._render_node(origins, directions, pixel_area, order, ovr, ag.DenseSamples.on_edges, edges, emb, sensor,
+                                 etimes, emb_cfg)
 
-    def _actor_overrides(self, origins, directions, pixel_area, edges, times, actor_cand=None):
-        """-> (ovr_row int32 [N]: row of the sample's WINNING actor (highest index containing it) or -1, rows [P,L*F],
-        box-frame view directions [P,3], pair_idx [P]: flat sample index of every (sample, actor) pair) or four Nones"""
+    def _render_node(self, origins, directions, pixel_area, order, ovr, layout, *where):
+        """autograd.NffRenderTrainFn on the samples ``layout(*where)``; ovr: ``_actor_overrides``' rows or None (static)"""
+        hg, g = self.hashgrid, self.hashgrid.static_grid
+        return ag.NffRenderTrainFn.apply(g.hash_table, g.spec, hg.static_scale, *self._beta_args(), origins, directions,
+                                         pixel_area.reshape(-1), order, *(ovr or (None,) * 4), *self._mlp_params(), layout, *where)
+
+    def _actor_overrides(self, samples, origins, directions, pixel_area, times, actor_cand=None):
+        """The rows of the samples inside an actor box, for the node's ``override``.  samples: their layout (autograd.
+        DenseSamples / PackedSamples), which does the geometry step -- on packed samples without [M, L*F] scratch rows.
+        -> (ovr_row int32 [N]: row of the sample's WINNING actor (highest index containing it) or -1, rows [P,L*F], box-frame
+        view directions [P,3], pair_idx [P]: sample index of every (sample, actor) pair), or None when no sample lies in a box"""
         hg = self.hashgrid
-        starts, ends = edges[:, :-1], edges[:, 1:]
-        N = starts.shape[0] * starts.shape[1]
-        flip = hg.sample_ray_flip(origins)
+        if times is None:  # (actor_cand alone fixes the boxes, not the pair positions' poses)
+            raise ValueError("dynamic actors need ray times (the pair positions are interpolated at the ray's time)")
+        times = times.reshape(-1)
+        flip = hg.sample_ray_flip(origins)  # one draw per ray, before the candidate lists: seeded runs depend on the order
         with torch.no_grad():
-            # candidate lists depend on the ray's line only: one list per ray batch serves every field (as in eval)
-            spec, cand = (hg.actor_spec(), actor_cand) if actor_cand is not None else hg.prepare_actors(
-                origins, directions, pixel_area, starts, ends, times)
-            scratch = torch.empty((N, hg.get_out_dim()), device=origins.device, dtype=torch.float32)  # (hit rows land here)
-            dirs, hit = ops.actor_encode(spec, cand, origins, directions, pixel_area, starts, ends, scratch, flip)
-            hits = ops.actor_hits(spec, cand, origins, directions, pixel_area, starts, ends)
-        pr = hg.actor_pair_rows(hit, hits, origins, directions, pixel_area, starts, ends, times, flip)
+            spec, cand = self._actor_cand(actor_cand, origins, directions, times, samples.cand_samples(pixel_area))
+            hits, hit, dirs = samples.actor_geometry(spec, cand, origins, directions, pixel_area, flip, hg.get_out_dim())
+        pr = hg.actor_pair_rows(hit, hits, origins, directions, pixel_area, samples.starts, samples.ends, times, flip,
+                                ray_indices=samples.ray_indices)
         if pr is None:
-            return None, None, None, None
+            return None
         idx, winner, f = pr
         rows = torch.nn.functional.pad(f, (0, hg.get_out_dim() - f.shape[1])).contiguous()
         with torch.no_grad():
             P = idx.shape[0]
             slot = torch.where(winner, torch.arange(P, device=idx.device), -1)  # one winner per sample: amax picks it
-            ov = torch.full((N,), -1, device=idx.device, dtype=torch.int64).scatter_reduce_(0, idx, slot, reduce="amax")
+            ov = torch.full((hit.shape[0],), -1, device=idx.device, dtype=torch.int64).scatter_reduce_(0, idx, slot, reduce="amax")
             pdirs = dirs.index_select(0, idx).contiguous()
         return ov.to(torch.int32), rows, pdirs, idx
 
@@ -462,8 +451,7 @@ class NeuRADField(nn.Module):
             # the learnable beta) -- reading it here would be a device->host sync per step
             feature, geo_out = ag.FieldTrainFn.apply(
                 g.hash_table, g.spec, self.hashgrid.static_scale, self.config.use_sdf, 1.0, o, d, a, starts, ends,
-                *[t for l in self.mlp_geo.layers for t in (l.weight, l.bias)],
-                *[t for l in self.mlp_feature.layers for t in (l.weight, l.bias)],
+                *self._mlp_params(),
                 *([ops.ray_order(o, d, self.hashgrid.static_scale)] if self.order_rays else []))
             return self._heads(feature.view(R, S, self.config.nff_out_dim), geo_out.view(R, S, 1))
         M = self.config.num_multisamples
@@ -503,11 +491,6 @@ class NeuRADField(nn.Module):
         else:
             out[FieldHeadNames.DENSITY] = trunc_exp(geo_out)
         return out
-
-    def _fused_train_ok(self) -> bool:
-        """The fused training forward needs biases on every layer (fp32 or fp16-storage table: the kernel reads either,
-        the table gradient is formed in fp32 and handed to autograd in the table's dtype)."""
-        return all(l.bias is not None for l in list(self.mlp_geo.layers) + list(self.mlp_feature.layers))
 
 
 @dataclass

@@ -293,30 +293,15 @@ class VolumetricSampler(Sampler):
         renders them with the fused packed-actors kernel; any other field takes the operator route on the same samples."""
         if self.training:
             raise RuntimeError("VolumetricSampler.render is the eval route; training calls forward() + renderers.render_packed")
-        R = ray_bundle.origins.shape[0]
-        boxes = self._actor_boxes(field, ray_bundle) if actor_boxes else None
-        rays_o, rays_d, ri, starts, ends = self._march(ray_bundle, render_step_size, near_plane, far_plane, alpha_thre,
-                                                       cone_angle, actor_boxes=boxes)
-        marched = {"ray_indices": ri, "t_starts": starts, "t_ends": ends}
-        if boxes is not None and getattr(field, "fused_packed_actors_supported", lambda: False)():
-            f, d, a, w = field.render_packed(rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri, num_rays=R,
-                                             return_weights=True, early_stop_eps=early_stop_eps, actor_cand=boxes[1])
-            return {"features": f, "depth": d, "accumulation": a, "weights": w[:, None], **marched}
-        if getattr(field, "fused_packed_supported", lambda: False)():
-            f, d, a, w = field.render_packed(rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri, num_rays=R,
-                                             return_weights=True, early_stop_eps=early_stop_eps)
-            return {"features": f, "depth": d, "accumulation": a, "weights": w[:, None], **marched}
-        from ..field_components.field_heads import FieldHeadNames
-        from .renderers import render_packed
 
-        if starts.shape[0] == 0:
-            z = lambda c: torch.zeros((R, c), device=rays_o.device, dtype=torch.float32)  # noqa: E731
-            return {"features": z(field.config.nff_out_dim), "depth": z(1), "accumulation": z(1),
-                    "weights": starts.new_zeros((0, 1)), **marched}
-        rs = self._gather(ray_bundle, rays_o, rays_d, ri, starts, ends)
-        out = field(rs)
-        kw = {"alpha": out[FieldHeadNames.ALPHA]} if FieldHeadNames.ALPHA in out else {"density": out[FieldHeadNames.DENSITY]}
-        return {**render_packed(out[FieldHeadNames.FEATURE], rs, ri, R, **kw), **marched}
+        def fused(boxes, rays_o, rays_d):
+            kw = {"return_weights": True, "early_stop_eps": early_stop_eps}
+            if boxes is not None and _gate(field, "fused_packed_actors_supported"):
+                return field.render_packed, {**kw, "actor_cand": boxes[1]}
+            return (field.render_packed, kw) if _gate(field, "fused_packed_supported") else None
+
+        return self._render(field, ray_bundle, (render_step_size, near_plane, far_plane, alpha_thre, cone_angle), None,
+                            actor_boxes, fused)
 
     def render_train(self, field, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0,
                      far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0,
@@ -335,23 +320,32 @@ class VolumetricSampler(Sampler):
         (``render_train_packed(..., times=..., actor_cand=...)``: one computation serves march and node) when the field has
         one (``fused_packed_actors_train_supported``), ``fused_training`` is on and the rays are fixed; anything else takes
         the operator route as before.  The node draws the training x-flip once per ray, the operator route once per sample."""
+        def fused(boxes, rays_o, rays_d):
+            rays_need_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+            if not getattr(field, "fused_training", False):
+                return None
+            if (fused_actor_training and boxes is not None and not rays_need_grad
+                    and _gate(field, "fused_packed_actors_train_supported")):
+                return field.render_train_packed, {"times": ray_bundle.times.reshape(-1).float(), "actor_cand": boxes[1]}
+            if (fused_ray_gradients or not rays_need_grad) and _gate(field, "fused_packed_train_supported"):
+                return field.render_train_packed, ({"ray_gradients": True} if rays_need_grad else {})
+            return None
+
+        return self._render(field, ray_bundle, (render_step_size, near_plane, far_plane, alpha_thre, cone_angle), True,
+                            actor_boxes, fused)
+
+    def _render(self, field, ray_bundle: RayBundle, march_args, stratified, actor_boxes, fused) -> dict:
+        """``render`` / ``render_train`` behind their route choice: march, then the call ``fused(boxes, rays_o, rays_d)``
+        picks -- (the field's packed render method, its keywords) on the BUNDLE'S per-ray tensors -- or, when it picks
+        None, the operator route: forward() on the gathered RaySamples + renderers.render_packed (a march without samples:
+        zero rows)."""
         R = ray_bundle.origins.shape[0]
         boxes = self._actor_boxes(field, ray_bundle) if actor_boxes else None
-        rays_o, rays_d, ri, starts, ends = self._march(ray_bundle, render_step_size, near_plane, far_plane, alpha_thre,
-                                                       cone_angle, stratified=True, actor_boxes=boxes)
+        rays_o, rays_d, ri, starts, ends = self._march(ray_bundle, *march_args, stratified=stratified, actor_boxes=boxes)
         marched = {"ray_indices": ri, "t_starts": starts, "t_ends": ends}
-        rays_need_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
-        if (fused_actor_training and boxes is not None and getattr(field, "fused_training", False) and not rays_need_grad
-                and getattr(field, "fused_packed_actors_train_supported", lambda: False)()):
-            f, d, a, w = field.render_train_packed(rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri,
-                                                   num_rays=R, times=ray_bundle.times.reshape(-1).float(),
-                                                   actor_cand=boxes[1])
-            return {"features": f, "depth": d, "accumulation": a, "weights": w[:, None], **marched}
-        if (getattr(field, "fused_training", False) and (fused_ray_gradients or not rays_need_grad)
-                and getattr(field, "fused_packed_train_supported", lambda: False)()):
-            kw = {"ray_gradients": True} if rays_need_grad else {}
-            f, d, a, w = field.render_train_packed(rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri,
-                                                   num_rays=R, **kw)
+        call = fused(boxes, rays_o, rays_d)
+        if call is not None:
+            f, d, a, w = call[0](rays_o, rays_d, ray_bundle.pixel_area, starts, ends, ray_indices=ri, num_rays=R, **call[1])
             return {"features": f, "depth": d, "accumulation": a, "weights": w[:, None], **marched}
         from ..field_components.field_heads import FieldHeadNames
         from .renderers import render_packed
@@ -364,3 +358,8 @@ class VolumetricSampler(Sampler):
         out = field(rs)
         kw = {"alpha": out[FieldHeadNames.ALPHA]} if FieldHeadNames.ALPHA in out else {"density": out[FieldHeadNames.DENSITY]}
         return {**render_packed(out[FieldHeadNames.FEATURE], rs, ri, R, **kw), **marched}
+
+
+def _gate(field, name: str) -> bool:
+    """a field's ``fused_*_supported`` gate; a field without it takes the operator route"""
+    return getattr(field, name, lambda: False)()

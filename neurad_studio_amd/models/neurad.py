@@ -59,12 +59,7 @@ class FusedEvalMixin:
         cfg = self.config
         sky = cfg.sampling.sky_distance
         self._scale_pixel_area(ray_bundle)
-        if ray_bundle.fars is not None:  # M1: far clamp, near default (models/neurad.py:443-449)
-            ray_bundle.fars.clamp_max_(sky)
-        else:
-            ray_bundle.fars = torch.full_like(ray_bundle.pixel_area, sky)
-        if ray_bundle.nears is None:
-            ray_bundle.nears = torch.zeros_like(ray_bundle.fars)
+        _clamp_far_default_near(ray_bundle, sky)
         o, d = ray_bundle.origins.contiguous(), ray_bundle.directions.contiguous()
         pf = list(self.proposal_fields)
         if self.reproduce_late_binding_quirk:
@@ -82,15 +77,9 @@ class FusedEvalMixin:
             times = sample_times(ray_samples)
         else:
             if field_actors or any(prop_actors):
-                # Which actors a ray can meet depends on its LINE only (bounding-sphere cull, neurad_encoding.py:225-247):
-                # one candidate list per ray, from any two samples on it, serves both proposal rounds and the field.
-                if ray_bundle.times is None:
-                    raise ValueError("dynamic actors need ray times")
+                # one candidate list per ray serves both proposal rounds and the field
+                cand = _ray_batch_actor_cand(self.field, pf, ray_bundle, o, d)
                 times = ray_bundle.times.reshape(-1)
-                n = ray_bundle.nears.reshape(-1)  # two one-metre samples at the start of the ray: a well-conditioned line
-                hg = self.field.hashgrid if field_actors else pf[0].hashgrid
-                _, cand = hg.prepare_actors(o, d, ray_bundle.pixel_area.reshape(-1), torch.stack([n, n + 1], -1),
-                                            torch.stack([n + 1, n + 2], -1), times)
             ray_samples, prop_weights, prop_ray_samples = self.sampler.generate_fused(
                 ray_bundle, pf, sky, actor_cand=cand if any(prop_actors) else None)
             fr = ray_samples.frustums
@@ -145,7 +134,7 @@ class FusedTrainMixin:
     def fused_training_possible(self) -> bool:
         f = self.field
         return (self.fused_training and self.training and torch.is_grad_enabled() and f.fused_training
-                and f.fused_supported(with_actors=True) and f._fused_train_ok()
+                and f.fused_train_supported()
                 and isinstance(self.sampler.initial_sampler, PowerSampler))
 
     def _fused_train_nff_outputs(self, ray_bundle: RayBundle, calc_lidar_losses: bool) -> Dict[str, Tensor]:
@@ -155,12 +144,7 @@ class FusedTrainMixin:
         cfg, smp = self.config, self.sampler
         sky = cfg.sampling.sky_distance
         self._scale_pixel_area_nosync(ray_bundle)
-        if ray_bundle.fars is None:
-            ray_bundle.fars = torch.full_like(ray_bundle.pixel_area, sky)
-        else:
-            ray_bundle.fars.clamp_max_(sky)
-        if ray_bundle.nears is None:
-            ray_bundle.nears = torch.zeros_like(ray_bundle.fars)
+        _clamp_far_default_near(ray_bundle, sky)
         o, d = ray_bundle.origins.contiguous(), ray_bundle.directions.contiguous()
         a = ray_bundle.pixel_area.reshape(-1)
         R, dev = o.shape[0], o.device
@@ -179,15 +163,8 @@ class FusedTrainMixin:
         train_props = smp._proposals_train_this_step()
         cand = None
         if self.field.hashgrid.has_actors() or any(p.hashgrid.has_actors() for p in pfs):
-            # which actors a ray can meet depends on its LINE only (bounding-sphere cull, neurad_encoding.py:225-247): one
-            # candidate list per step serves both proposal rounds and the field, as in eval (was: one launch per field call)
-            if ray_bundle.times is None:
-                raise ValueError("dynamic actors need ray times")
-            n0 = ray_bundle.nears.reshape(-1)
-            hg0 = self.field.hashgrid if self.field.hashgrid.has_actors() else next(p.hashgrid for p in pfs if p.hashgrid.has_actors())
-            with torch.no_grad():
-                _, cand = hg0.prepare_actors(o, d, a, torch.stack([n0, n0 + 1], -1), torch.stack([n0 + 1, n0 + 2], -1),
-                                             ray_bundle.times.reshape(-1))
+            # one candidate list per step serves both proposal rounds and the field, as in eval
+            cand = _ray_batch_actor_cand(self.field, pfs, ray_bundle, o, d)
         nff: Dict[str, Tensor] = {}
         weights_list, samples_list = [], []
         lidar_terms = self.training and calc_lidar_losses
@@ -247,6 +224,30 @@ class FusedTrainMixin:
             else:
                 nff["non_nearby_weights_loss"] = ag.CarvingLossFn.apply(w_ns, eu[:, :S - 1], eu[:, 1:S], *carve)
         return nff
+
+
+def _clamp_far_default_near(ray_bundle, sky: float) -> None:
+    """M1: far clamp, near default (models/neurad.py:443-449), in place on the bundle"""
+    if ray_bundle.fars is None:
+        ray_bundle.fars = torch.full_like(ray_bundle.pixel_area, sky)
+    else:
+        ray_bundle.fars.clamp_max_(sky)
+    if ray_bundle.nears is None:
+        ray_bundle.nears = torch.zeros_like(ray_bundle.fars)
+
+
+@torch.no_grad()
+def _ray_batch_actor_cand(field, proposal_fields, ray_bundle, o, d):
+    """One actor candidate list per ray batch, for every field evaluated on it: which actors a ray can meet depends on its
+    LINE only (bounding-sphere cull, neurad_encoding.py:225-247), so any two samples on it do -- two one-metre samples at the
+    start of the ray, a well-conditioned line.  From the field's hashgrid if it has actors, else the first proposal field's
+    that has."""
+    if ray_bundle.times is None:
+        raise ValueError("dynamic actors need ray times")
+    n = ray_bundle.nears.reshape(-1)
+    hg = next(f.hashgrid for f in (field, *proposal_fields) if f.hashgrid.has_actors())
+    return hg.prepare_actors(o, d, ray_bundle.pixel_area.reshape(-1), torch.stack([n, n + 1], -1),
+                             torch.stack([n + 1, n + 2], -1), ray_bundle.times.reshape(-1))[1]
 
 
 def _expected_depth(depth: Tensor, w: Tensor, edges: Tensor) -> Tensor:
@@ -400,12 +401,7 @@ class NeuRADHotPath(FusedEvalMixin, FusedTrainMixin, nn.Module):
     # ---- M1 (models/neurad.py:443-459), operator-level path ---------------------------------------
     def _get_ray_samples(self, ray_bundle: RayBundle):
         sky = self.config.sampling.sky_distance
-        if ray_bundle.fars is None:
-            ray_bundle.fars = torch.full_like(ray_bundle.pixel_area, sky)
-        else:
-            ray_bundle.fars.clamp_max_(sky)
-        if ray_bundle.nears is None:
-            ray_bundle.nears = torch.zeros_like(ray_bundle.fars)
+        _clamp_far_default_near(ray_bundle, sky)
         ray_samples, prop_weights, prop_ray_samples = self.sampler(ray_bundle, self.density_fns, pass_ray_samples=True)
         # sky stretch, in place on the sampler's edge tensors: the last bin ends at sky_distance
         fr = ray_samples.frustums

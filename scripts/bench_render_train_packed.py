@@ -4,7 +4,7 @@ with march-like ragged sample counts (mean ~32 per ray, a tenth of the rays empt
 backward (gradients of the table, the ten MLP tensors and beta), timed with device events after a warm-up, alternating in
 one process:
   (a) the fused node of VolumetricSampler.render_train: NeuRADField.render_train_packed on the bundle's per-ray tensors
-      (autograd.NffRenderPackedTrainFn);
+      (autograd.NffRenderTrainFn on autograd.PackedSamples);
   (b) the operator route: per-sample gathers of origins / directions / pixel area, the field on [M,1] (FieldTrainFn, every
       sample a ray of one sample), the torch head, renderers.render_packed (PackedCompositeFn).
 Appends ONE JSON line (M, the segment-length histogram, device clocks under load, medians, the ratio (b)/(a), and the rel-L2
@@ -18,7 +18,7 @@ packed samples, NeuRAD's default field with 4 x 4 actor grids) in training mode,
 differently: per ray against per sample; a non-zero flip is not measured).  The march and the per-ray candidate lists are
 outside the timed region; timed, alternating, forward + backward (static table, MLPs, beta, the 24 actor tables, the
 trajectories):
-  (a) NeuRADField.render_train_packed(..., times=..., actor_cand=...): autograd.NffRenderPackedActorsTrainFn;
+  (a) NeuRADField.render_train_packed(..., times=..., actor_cand=...): autograd.NffRenderTrainFn with row overrides;
   (b) the operator route on the same samples: gathers, the field with actors on [M,1], the torch head, renderers.render_packed
       (what VolumetricSampler.render_train(..., actor_boxes=True) does by default; it computes its own per-sample lists).
 The line's "bench" is "render_train_packed_actors".  No ratio is promised.

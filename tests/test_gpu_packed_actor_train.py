@@ -1,6 +1,6 @@
 """The fused training node for packed samples of a scene with dynamic actors: the packed actor geometry
 (nrhip_actor_find_packed), the packed pair positions (nrhip_actor_pair_positions_fwd_packed / _bwd_packed), the packed
-training forward with row overrides (nrhip_field_fwd_train_packed_ovr), autograd.NffRenderPackedActorsTrainFn behind
+training forward with row overrides (nrhip_field_fwd_train_packed_ovr), autograd.NffRenderTrainFn with those overrides behind
 NeuRADField.render_train_packed(..., times=...) and VolumetricSampler.render_train(..., fused_actor_training=True).
 
 Scenes, fields, routes and the comparison: tests/packed_actor_train_refs.py on top of tests/packed_actor_refs.py.  Bounds:
@@ -13,9 +13,12 @@ import torch
 
 import packed_actor_refs as PA
 import packed_actor_train_refs as TR
+import packed_train_refs as T
+import synth
 from conftest import rel_l2
 from gpu_util import cuda, dev, host, to_spec
 from gpu_util import ops  # noqa: F401  (fixture)
+from neurad_studio_amd import autograd as ag
 
 pytestmark = pytest.mark.gpu
 
@@ -137,7 +140,7 @@ def test_ragged_forward_vs_oracle_and_eval_kernel(ops, name):
     PA.close(got, ev, 1e-5, f"{name}: node vs eval kernel,")
     # the forward kernel with the node's own overrides: a guard after every per-sample buffer stays untouched
     M, H, LF = ts.shape[0], 32, 32
-    ovr = fld._actor_overrides_packed(o, d, area, ts, te, ri, times)
+    ovr = fld._actor_overrides(ag.PackedSamples(ts, te, seg, ri), o, d, area, times)
     assert ovr is not None and int((ovr[0] >= 0).sum()) == stats["in_box"] and ovr[3].shape[0] == stats["pairs"]
     bufs = [torch.full((M + 64, *w), float("nan"), device="cuda") for w in ((32,), (), (), (LF,), (H,), (48,), (2 * H,))]
     with torch.no_grad():
@@ -362,3 +365,61 @@ def test_forward_and_static_table_gradient_repeat_bit_for_bit(ops):
     for a, b in zip(runs[0][0], runs[1][0]):
         assert torch.equal(a, b)
     assert torch.equal(runs[0][1][TR.TABLE], runs[1][1][TR.TABLE])
+
+
+# ---- 10. under autocast ------------------------------------------------------------------------------------------------
+def _render_call(case):
+    """-> (the field, its extra parameters by name, call() -> the node's four outputs) of one of the three render nodes"""
+    kind, _, head = case.partition("-")
+    if kind == "dense":  # render_train with a temporal appearance embedding, one block of embedding rows per ray
+        R, S, A, n_per, duration = 23, 17, 8, 4, 8.0
+        fld = T.make_field(8, 4, 32, head == "sdf")[0]
+        o, d, area, ts, te, _, _ = T.on_device(T.packed_rays((S,) * R, 7))
+        edges = torch.cat([ts.view(R, S), te.view(R, S)[:, -1:]], dim=1)  # (the last sample's far edge is the sky distance)
+        emb = dev(synth.normal((R * n_per, A), 5)).requires_grad_(True)
+        appearance = (emb, torch.arange(R, device="cuda")[:, None], dev(synth.uniform((R, 1), 0.0, duration, 6)),
+                      (duration, n_per, True))
+        return fld, {"appearance_embedding": emb}, lambda: fld.render_train(o, d, area, edges, appearance)
+    if kind == "packed":
+        fld = T.make_field(8, 4, 32, head == "sdf")[0]
+        o, d, area, ts, te, seg, _ = T.on_device(T.packed_rays(T.RAGGED, 7))
+        return fld, {}, lambda: fld.render_train_packed(o, d, area, ts, te, segments=seg)
+    fld = TR.make_train_field("golden")[0]  # flip_prob = 0
+    dr = TR.on_device(PA.ragged_rays("golden", 48, 7))
+    return fld, {}, lambda: TR.node_route(fld, dr)
+
+
+ATOMIC = ("hashgrid.actors.actor_positions", "hashgrid.actors.actor_rotations_6d")
+
+
+@pytest.mark.parametrize("case", ["dense-sdf", "dense-density", "packed-sdf", "packed-density", "actors"])
+def test_render_nodes_under_autocast_are_the_plain_run(ops, monkeypatch, case):
+    """The trainer runs under autocast, and custom_fwd(cast_inputs=float32) walks the node's arguments: every tensor of the
+    sample layout has to be an argument of its own (a tuple subclass holding them cannot be rebuilt by the cast).  The same
+    fp32 inputs plainly and inside torch.autocast("cuda", float16), backward each time: outputs and parameter gradients are
+    torch.equal.  What makes that possible: the table gradients -- static table and actor grids -- come from the partition
+    (ops._BINNED_MIN_SAMPLES = 1: no float atomics), and a cell of the embedding's gradient receives at most two additions
+    onto zero (one block of rows per ray), which commute.  The exception are the trajectories, whose gradient the pair
+    backward accumulates with float atomics in an order that varies: compare_routes' bound for a parameter gradient."""
+    monkeypatch.setattr(ops, "_BINNED_MIN_SAMPLES", 1)
+    runs = []
+    for cast in (False, True):
+        fld, extra, call = _render_call(case)
+        with torch.autocast("cuda", dtype=torch.float16, enabled=cast):
+            outs = call()
+        assert all(t.dtype == torch.float32 for t in outs)
+        sum((t * dev(synth.normal(tuple(t.shape), 81 + k))).sum() for k, t in enumerate(outs)).backward()
+        grads = {**TR.field_grads(fld), **{n: t.grad.detach().clone() for n, t in extra.items()}}
+        runs.append(([t.detach() for t in outs], grads))
+    (out_p, grad_p), (out_c, grad_c) = runs
+    assert all(torch.equal(a, b) for a, b in zip(out_p, out_c))
+    assert set(grad_p) == set(grad_c) and TR.TABLE in grad_p and set(extra) <= set(grad_p)
+    assert (case == "actors") == all(n in grad_p for n in ATOMIC)
+    for n in grad_p:
+        assert float(grad_p[n].abs().sum()) > 0, n
+        if n in ATOMIC:
+            err = rel_l2(host(grad_p[n]).reshape(-1), host(grad_c[n]).reshape(-1))
+            print(f"d {n}: autocast vs plain rel-L2 {err:.3e} (bound 2e-4)")
+            assert err < 2e-4, (n, err)
+        else:
+            assert torch.equal(grad_p[n], grad_c[n]), n

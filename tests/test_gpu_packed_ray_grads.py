@@ -1,5 +1,5 @@
 """dL/d(origins, directions) through PACKED, occupancy-marched samples: the kernel (nrhip_encode_bwd_rays_packed /
-ops.encode_bwd_rays_packed), the node that calls it (autograd.NffRenderPackedTrainFn with rays that require grad), and the
+ops.encode_bwd_rays_packed), the node that calls it (autograd.NffRenderTrainFn on packed samples with rays that require grad), and the
 opt-ins that reach it (NeuRADField.render_train_packed(ray_gradients=True), VolumetricSampler.render_train(
 fused_ray_gradients=True)).
 

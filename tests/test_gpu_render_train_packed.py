@@ -1,4 +1,4 @@
-"""Training on PACKED samples as one node (autograd.NffRenderPackedTrainFn / NeuRADField.render_train_packed /
+"""Training on PACKED samples as one node (autograd.NffRenderTrainFn on autograd.PackedSamples / NeuRADField.render_train_packed /
 VolumetricSampler.render_train): the fused field forward storing at the packed sample index
 (nrhip_field_fwd_train_packed), head + packed compositing forward and backward (nrhip_sdf_render_packed_fwd / _bwd), and
 the table gradient from packed samples (nrhip_encode_bwd_binned_packed).
