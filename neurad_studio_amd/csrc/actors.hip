@@ -672,35 +672,57 @@ __global__ __launch_bounds__(256) void actor_density_splice_bwd_kernel(
 
 }  // namespace nrhip
 
+// The pair kernels' entry points, once over the two sample layouts.  Dense (nrhip_rays): sample_idx is a row ray * S + s,
+// no ray_of.  Packed (nrhip_packed_rays): sample_idx is a packed sample index, ray_of [M] names its ray; times / ray_flip
+// stay per ray.  The same kernel bodies; no gradient to the rays on packed samples.
+static int validate_pair_rays(const char*, const nrhip_rays* r) { return validate_rays(r); }
+static int validate_pair_rays(const char* who, const nrhip_packed_rays* r) { return validate_packed_rays(who, r, false); }
+
+enum class PairOp { Fwd, Bwd, BwdRays };
+
+// Fwd: into out0 = x01, out1 = cstd.  Bwd: g_x01, g_cstd -> out0 = grad_positions, out1 = grad_rotations_6d, and
+// (BwdRays) g_origins, g_directions
+template <PairOp OP, class Rays>
+static int pair_positions(const char* who, const nrhip_actors* a, const Rays* rays, const int64_t* ray_of,
+                          const float* times, const int64_t* sample_idx, const int32_t* actor_idx, const float* ray_flip,
+                          int64_t n_pairs, const float* g_x01, const float* g_cstd, float* out0, float* out1,
+                          float* g_origins, float* g_directions, void* stream) {
+  constexpr bool packed = std::is_same<Rays, nrhip_packed_rays>::value;
+  using RD = decltype(to_dev(*rays));
+  ActorsDev d;
+  if (int e = to_dev(a, d)) return e;
+  if (int e = validate_pair_rays(who, rays)) return e;
+  NR_REQUIRE(n_pairs >= 0 && a->actor_scale > 0.f, NRHIP_ERR_INVALID_ARG, "%s: bad argument", who);
+  if (n_pairs == 0) return NRHIP_OK;
+  NR_REQUIRE(!packed || (rays->n_rays >= 1 && rays->n_samples >= 1), NRHIP_ERR_INVALID_ARG,
+             "%s: pairs of a batch without samples", who);
+  NR_REQUIRE((ray_of || !packed) && times && sample_idx && actor_idx && out0 && out1 &&
+                 (OP == PairOp::Fwd || (g_x01 && g_cstd)) && (OP != PairOp::BwdRays || (g_origins && g_directions)),
+             NRHIP_ERR_INVALID_ARG, "%s: NULL pointer", who);
+  const dim3 blocks(grid_for(n_pairs, 256));
+  if constexpr (OP == PairOp::Fwd)
+    actor_pair_positions_kernel<RD><<<blocks, 256, 0, (hipStream_t)stream>>>(d, to_dev(*rays), ray_of, times, sample_idx,
+                                                                             actor_idx, ray_flip, n_pairs, out0, out1);
+  else
+    actor_pair_positions_bwd_kernel<RD><<<blocks, 256, 0, (hipStream_t)stream>>>(
+        d, to_dev(*rays), ray_of, times, sample_idx, actor_idx, ray_flip, n_pairs, g_x01, g_cstd, out0, out1, g_origins,
+        g_directions, tuning().pair_bwd_runs ? 1 : 0);
+  return check_launch(who);
+}
+
 extern "C" int nrhip_actor_pair_positions_fwd(const nrhip_actors* a, const nrhip_rays* rays, const float* times,
                                               const int64_t* sample_idx, const int32_t* actor_idx, const float* ray_flip,
                                               int64_t n_pairs, float* x01, float* cstd, void* stream) {
-  ActorsDev d;
-  if (int e = to_dev(a, d)) return e;
-  if (int e = validate_rays(rays)) return e;
-  NR_REQUIRE(n_pairs >= 0 && a->actor_scale > 0.f, NRHIP_ERR_INVALID_ARG, "actor_pair_positions: bad argument");
-  if (n_pairs == 0) return NRHIP_OK;
-  NR_REQUIRE(times && sample_idx && actor_idx && x01 && cstd, NRHIP_ERR_INVALID_ARG, "actor_pair_positions: NULL pointer");
-  actor_pair_positions_kernel<RaysDev><<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
-      d, to_dev(*rays), nullptr, times, sample_idx, actor_idx, ray_flip, n_pairs, x01, cstd);
-  return check_launch("actor_pair_positions_fwd");
+  return pair_positions<PairOp::Fwd>("actor_pair_positions", a, rays, nullptr, times, sample_idx, actor_idx, ray_flip,
+                                     n_pairs, nullptr, nullptr, x01, cstd, nullptr, nullptr, stream);
 }
 
 extern "C" int nrhip_actor_pair_positions_bwd(const nrhip_actors* a, const nrhip_rays* rays, const float* times,
                                               const int64_t* sample_idx, const int32_t* actor_idx, const float* ray_flip,
                                               int64_t n_pairs, const float* grad_x01, const float* grad_cstd,
                                               float* grad_positions, float* grad_rotations_6d, void* stream) {
-  ActorsDev d;
-  if (int e = to_dev(a, d)) return e;
-  if (int e = validate_rays(rays)) return e;
-  NR_REQUIRE(n_pairs >= 0 && a->actor_scale > 0.f, NRHIP_ERR_INVALID_ARG, "actor_pair_positions_bwd: bad argument");
-  if (n_pairs == 0) return NRHIP_OK;
-  NR_REQUIRE(times && sample_idx && actor_idx && grad_x01 && grad_cstd && grad_positions && grad_rotations_6d,
-             NRHIP_ERR_INVALID_ARG, "actor_pair_positions_bwd: NULL pointer");
-  actor_pair_positions_bwd_kernel<RaysDev><<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
-      d, to_dev(*rays), nullptr, times, sample_idx, actor_idx, ray_flip, n_pairs, grad_x01, grad_cstd, grad_positions,
-      grad_rotations_6d, nullptr, nullptr, tuning().pair_bwd_runs ? 1 : 0);
-  return check_launch("actor_pair_positions_bwd");
+  return pair_positions<PairOp::Bwd>("actor_pair_positions_bwd", a, rays, nullptr, times, sample_idx, actor_idx, ray_flip,
+                                     n_pairs, grad_x01, grad_cstd, grad_positions, grad_rotations_6d, nullptr, nullptr, stream);
 }
 
 extern "C" int nrhip_actor_pair_positions_bwd_rays(const nrhip_actors* a, const nrhip_rays* rays, const float* times,
@@ -709,38 +731,17 @@ extern "C" int nrhip_actor_pair_positions_bwd_rays(const nrhip_actors* a, const 
                                                    const float* grad_cstd, float* grad_positions,
                                                    float* grad_rotations_6d, float* grad_origins,
                                                    float* grad_directions, void* stream) {
-  ActorsDev d;
-  if (int e = to_dev(a, d)) return e;
-  if (int e = validate_rays(rays)) return e;
-  NR_REQUIRE(n_pairs >= 0 && a->actor_scale > 0.f, NRHIP_ERR_INVALID_ARG, "actor_pair_positions_bwd_rays: bad argument");
-  if (n_pairs == 0) return NRHIP_OK;
-  NR_REQUIRE(times && sample_idx && actor_idx && grad_x01 && grad_cstd && grad_positions && grad_rotations_6d &&
-                 grad_origins && grad_directions,
-             NRHIP_ERR_INVALID_ARG, "actor_pair_positions_bwd_rays: NULL pointer");
-  actor_pair_positions_bwd_kernel<RaysDev><<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
-      d, to_dev(*rays), nullptr, times, sample_idx, actor_idx, ray_flip, n_pairs, grad_x01, grad_cstd, grad_positions,
-      grad_rotations_6d, grad_origins, grad_directions, tuning().pair_bwd_runs ? 1 : 0);
-  return check_launch("actor_pair_positions_bwd_rays");
+  return pair_positions<PairOp::BwdRays>("actor_pair_positions_bwd_rays", a, rays, nullptr, times, sample_idx, actor_idx,
+                                         ray_flip, n_pairs, grad_x01, grad_cstd, grad_positions, grad_rotations_6d,
+                                         grad_origins, grad_directions, stream);
 }
 
-// The pair kernels on packed samples: sample_idx is a packed sample index, ray_of [M] names its ray, times / ray_flip stay
-// per ray.  The same kernel bodies; no gradient to the rays (nrhip_actor_pair_positions_bwd_rays has no packed form).
 extern "C" int nrhip_actor_pair_positions_fwd_packed(const nrhip_actors* a, const nrhip_packed_rays* rays,
                                                      const int64_t* ray_of, const float* times, const int64_t* sample_idx,
                                                      const int32_t* actor_idx, const float* ray_flip, int64_t n_pairs,
                                                      float* x01, float* cstd, void* stream) {
-  ActorsDev d;
-  if (int e = to_dev(a, d)) return e;
-  if (int e = validate_packed_rays("actor_pair_positions_fwd_packed", rays, false)) return e;
-  NR_REQUIRE(n_pairs >= 0 && a->actor_scale > 0.f, NRHIP_ERR_INVALID_ARG, "actor_pair_positions_fwd_packed: bad argument");
-  if (n_pairs == 0) return NRHIP_OK;
-  NR_REQUIRE(rays->n_rays >= 1 && rays->n_samples >= 1, NRHIP_ERR_INVALID_ARG,
-             "actor_pair_positions_fwd_packed: pairs of a batch without samples");
-  NR_REQUIRE(ray_of && times && sample_idx && actor_idx && x01 && cstd, NRHIP_ERR_INVALID_ARG,
-             "actor_pair_positions_fwd_packed: NULL pointer");
-  actor_pair_positions_kernel<PackedRaysDev><<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
-      d, to_dev(*rays), ray_of, times, sample_idx, actor_idx, ray_flip, n_pairs, x01, cstd);
-  return check_launch("actor_pair_positions_fwd_packed");
+  return pair_positions<PairOp::Fwd>("actor_pair_positions_fwd_packed", a, rays, ray_of, times, sample_idx, actor_idx,
+                                     ray_flip, n_pairs, nullptr, nullptr, x01, cstd, nullptr, nullptr, stream);
 }
 
 extern "C" int nrhip_actor_pair_positions_bwd_packed(const nrhip_actors* a, const nrhip_packed_rays* rays,
@@ -748,19 +749,9 @@ extern "C" int nrhip_actor_pair_positions_bwd_packed(const nrhip_actors* a, cons
                                                      const int32_t* actor_idx, const float* ray_flip, int64_t n_pairs,
                                                      const float* grad_x01, const float* grad_cstd, float* grad_positions,
                                                      float* grad_rotations_6d, void* stream) {
-  ActorsDev d;
-  if (int e = to_dev(a, d)) return e;
-  if (int e = validate_packed_rays("actor_pair_positions_bwd_packed", rays, false)) return e;
-  NR_REQUIRE(n_pairs >= 0 && a->actor_scale > 0.f, NRHIP_ERR_INVALID_ARG, "actor_pair_positions_bwd_packed: bad argument");
-  if (n_pairs == 0) return NRHIP_OK;
-  NR_REQUIRE(rays->n_rays >= 1 && rays->n_samples >= 1, NRHIP_ERR_INVALID_ARG,
-             "actor_pair_positions_bwd_packed: pairs of a batch without samples");
-  NR_REQUIRE(ray_of && times && sample_idx && actor_idx && grad_x01 && grad_cstd && grad_positions && grad_rotations_6d,
-             NRHIP_ERR_INVALID_ARG, "actor_pair_positions_bwd_packed: NULL pointer");
-  actor_pair_positions_bwd_kernel<PackedRaysDev><<<grid_for(n_pairs, 256), 256, 0, (hipStream_t)stream>>>(
-      d, to_dev(*rays), ray_of, times, sample_idx, actor_idx, ray_flip, n_pairs, grad_x01, grad_cstd, grad_positions,
-      grad_rotations_6d, nullptr, nullptr, tuning().pair_bwd_runs ? 1 : 0);
-  return check_launch("actor_pair_positions_bwd_packed");
+  return pair_positions<PairOp::Bwd>("actor_pair_positions_bwd_packed", a, rays, ray_of, times, sample_idx, actor_idx,
+                                     ray_flip, n_pairs, grad_x01, grad_cstd, grad_positions, grad_rotations_6d, nullptr,
+                                     nullptr, stream);
 }
 
 // ---- the (sample, actor) pairs of a hits table, in order, without torch's nonzero -----------------------------------------

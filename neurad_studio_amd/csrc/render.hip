@@ -1419,103 +1419,47 @@ static Variant choose_variant(const nrhip_field* f, Out out, Src src) {
   return {L, F, H, out, Src::Static, Prod::F32};  // 4. the fp32 MFMA
 }
 
-// Looks the chosen variant up in the table and launches it (fp32 or fp16 table by the grid's storage type).
-static int dispatch_render(const nrhip_field* f, const nrhip_rays* rays, Out out, Src src, const RenderArgs& a) {
-  const Variant v = choose_variant(f, out, src);
-  FieldDev fd = to_dev(*f);
-  if (v.src == Src::EvalTable) fd.table = f->eval_table;
-  const RaysDev rd = to_dev(*rays);
-  const bool half = f->grid.param_dtype == 1;
-#define X(L_, F_, H_, O_, S_, P_)                                                             \
-  if (same(v, {L_, F_, H_, Out::O_, Src::S_, Prod::P_}))                                      \
-    return half ? launch_render<L_, F_, H_, true, Out::O_, Src::S_, Prod::P_>(fd, rd, a)      \
-                : launch_render<L_, F_, H_, false, Out::O_, Src::S_, Prod::P_>(fd, rd, a);
-  NRHIP_RENDER_VARIANTS(X)
-#undef X
-  set_error("%s: no instantiation for L=%d F=%d H=%d",
-            src == Src::Actors ? "fused field kernel with actors" : src == Src::Overrides ? "field_fwd_train_ovr"
-                                                                                          : "fused field kernel",
-            v.L, v.F, v.H);
-  return NRHIP_ERR_UNSUPPORTED;
+// The layout a variant takes on packed samples.  The packed kernels have no rows of their own in the table: a row is
+// instantiated in this layout as well wherever render_variant_ok admits it.
+constexpr Lay packed_lay(Out out, Src src) {
+  return src == Src::Actors ? Lay::PackedActors
+         : src == Src::Overrides ? Lay::PackedRowsOvr
+         : out == Out::Composite ? Lay::Packed
+                                 : Lay::PackedRows;
 }
 
-// A row of the table in the packed layout, where render_variant_ok admits it (the packed kernels have no rows of their own)
+// One row of the table, for dense samples or (packed: rd.S carries M, a.segments the segments) in its packed layout
 template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD>
-static int launch_packed_row(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
-  constexpr Lay LAY = OUT == Out::Composite ? Lay::Packed : Lay::PackedRows;
+static int launch_row(const char* who, bool packed, const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
+  if (!packed) return launch_render<L, F, H, HALF, OUT, SRC, PROD>(fd, rd, a);
+  constexpr Lay LAY = packed_lay(OUT, SRC);
   if constexpr (render_variant_ok(L, F, OUT, SRC, PROD, LAY)) {
     return launch_render<L, F, H, HALF, OUT, SRC, PROD, LAY>(fd, rd, a);
   } else {
-    set_error("fused field kernel: no packed form of this variant");
+    set_error("%s: no packed form of this variant", who);
     return NRHIP_ERR_UNSUPPORTED;
   }
 }
 
-// dispatch_render for packed samples: choose_variant's preference among the rows that have a packed form (the fp16
-// pairs where the table has them, else the fp32 MFMA).  rd.S carries M, a.segments the segments.
-static int dispatch_render_packed(const nrhip_field* f, Out out, const RaysDev& rd, const RenderArgs& a) {
-  Variant v = choose_variant(f, out, Src::Static);
-  if (!render_variant_ok(v.L, v.F, v.out, v.src, v.prod, out == Out::Composite ? Lay::Packed : Lay::PackedRows))
-    v.src = Src::Static, v.prod = Prod::F32;
-  const FieldDev fd = to_dev(*f);
+// Looks the chosen variant up in the table and launches it (fp32 or fp16 table by the grid's storage type).  Packed
+// samples: choose_variant's preference among the rows that have a packed form -- where the preferred row has none (the
+// split products, the pair products per sample, the eval table) the fp32 MFMA row of the same source runs.  `entry` is
+// the entry point's name: the override kernels' messages carry it.
+static int dispatch_render(const char* entry, const nrhip_field* f, const RaysDev& rd, bool packed, Out out, Src src,
+                           const RenderArgs& a) {
+  Variant v = choose_variant(f, out, src);
+  if (packed && !render_variant_ok(v.L, v.F, v.out, v.src, v.prod, packed_lay(out, src))) v.src = src, v.prod = Prod::F32;
+  FieldDev fd = to_dev(*f);
+  if (v.src == Src::EvalTable) fd.table = f->eval_table;
   const bool half = f->grid.param_dtype == 1;
-#define X(L_, F_, H_, O_, S_, P_)                                                                \
-  if (same(v, {L_, F_, H_, Out::O_, Src::S_, Prod::P_}))                                         \
-    return half ? launch_packed_row<L_, F_, H_, true, Out::O_, Src::S_, Prod::P_>(fd, rd, a)     \
-                : launch_packed_row<L_, F_, H_, false, Out::O_, Src::S_, Prod::P_>(fd, rd, a);
+  const char* who = src == Src::Actors ? "fused field kernel with actors" : src == Src::Overrides ? entry : "fused field kernel";
+#define X(L_, F_, H_, O_, S_, P_)                                                                 \
+  if (same(v, {L_, F_, H_, Out::O_, Src::S_, Prod::P_}))                                          \
+    return half ? launch_row<L_, F_, H_, true, Out::O_, Src::S_, Prod::P_>(who, packed, fd, rd, a) \
+                : launch_row<L_, F_, H_, false, Out::O_, Src::S_, Prod::P_>(who, packed, fd, rd, a);
   NRHIP_RENDER_VARIANTS(X)
 #undef X
-  set_error("fused field kernel: no instantiation for L=%d F=%d H=%d", v.L, v.F, v.H);
-  return NRHIP_ERR_UNSUPPORTED;
-}
-
-// The packed form of a `Composite, Actors, F32` row (Lay::PackedActors; no rows of its own either)
-template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD>
-static int launch_packed_actors_row(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
-  if constexpr (render_variant_ok(L, F, OUT, SRC, PROD, Lay::PackedActors)) {
-    return launch_render<L, F, H, HALF, OUT, SRC, PROD, Lay::PackedActors>(fd, rd, a);
-  } else {
-    set_error("fused field kernel with actors: no packed form of this variant");
-    return NRHIP_ERR_UNSUPPORTED;
-  }
-}
-
-static int dispatch_render_packed_actors(const nrhip_field* f, const RaysDev& rd, const RenderArgs& a) {
-  const Variant v = choose_variant(f, Out::Composite, Src::Actors);
-  const FieldDev fd = to_dev(*f);
-  const bool half = f->grid.param_dtype == 1;
-#define X(L_, F_, H_, O_, S_, P_)                                                                       \
-  if (same(v, {L_, F_, H_, Out::O_, Src::S_, Prod::P_}))                                                \
-    return half ? launch_packed_actors_row<L_, F_, H_, true, Out::O_, Src::S_, Prod::P_>(fd, rd, a)     \
-                : launch_packed_actors_row<L_, F_, H_, false, Out::O_, Src::S_, Prod::P_>(fd, rd, a);
-  NRHIP_RENDER_VARIANTS(X)
-#undef X
-  set_error("fused field kernel with actors: no instantiation for L=%d F=%d H=%d", v.L, v.F, v.H);
-  return NRHIP_ERR_UNSUPPORTED;
-}
-
-// The packed form of a `PerSample, Overrides, F32` row (Lay::PackedRowsOvr; no rows of its own either)
-template <int L, int F, int H, bool HALF, Out OUT, Src SRC, Prod PROD>
-static int launch_packed_ovr_row(const FieldDev& fd, const RaysDev& rd, const RenderArgs& a) {
-  if constexpr (render_variant_ok(L, F, OUT, SRC, PROD, Lay::PackedRowsOvr)) {
-    return launch_render<L, F, H, HALF, OUT, SRC, PROD, Lay::PackedRowsOvr>(fd, rd, a);
-  } else {
-    set_error("field_fwd_train_packed_ovr: no packed form of this variant");
-    return NRHIP_ERR_UNSUPPORTED;
-  }
-}
-
-static int dispatch_render_packed_ovr(const nrhip_field* f, const RaysDev& rd, const RenderArgs& a) {
-  const Variant v = choose_variant(f, Out::PerSample, Src::Overrides);
-  const FieldDev fd = to_dev(*f);
-  const bool half = f->grid.param_dtype == 1;
-#define X(L_, F_, H_, O_, S_, P_)                                                                    \
-  if (same(v, {L_, F_, H_, Out::O_, Src::S_, Prod::P_}))                                             \
-    return half ? launch_packed_ovr_row<L_, F_, H_, true, Out::O_, Src::S_, Prod::P_>(fd, rd, a)     \
-                : launch_packed_ovr_row<L_, F_, H_, false, Out::O_, Src::S_, Prod::P_>(fd, rd, a);
-  NRHIP_RENDER_VARIANTS(X)
-#undef X
-  set_error("field_fwd_train_packed_ovr: no instantiation for L=%d F=%d H=%d", v.L, v.F, v.H);
+  set_error("%s: no instantiation for L=%d F=%d H=%d", who, v.L, v.F, v.H);
   return NRHIP_ERR_UNSUPPORTED;
 }
 
@@ -1559,6 +1503,103 @@ __global__ __launch_bounds__(kPartThreads) void actor_partition_kernel(const int
 
 using namespace nrhip;
 
+// ---- what the entry points share.  Each of them validates its own ray descriptor, turns it into a RaysDev (to_dev, or
+// packed_launch_rays with the segments beside it in RenderArgs), handles the empty batches of its layout and goes on here.
+static int check_stop_eps(const char* who, float eps) {
+  NR_REQUIRE(eps >= 0.f && eps < 1.f, NRHIP_ERR_INVALID_ARG, "%s: early_stop_eps %g not in [0,1)", who, (double)eps);
+  return NRHIP_OK;
+}
+
+// a packed batch whose segments are all empty: no sample pointer (and no segment) is read, the per-ray outputs are zeroed
+static int zero_ray_outputs(const char* who, int64_t R, float* features, float* depth, float* acc, hipStream_t st) {
+  if (hipMemsetAsync(features, 0, (size_t)R * 32 * sizeof(float), st) != hipSuccess ||
+      hipMemsetAsync(depth, 0, (size_t)R * sizeof(float), st) != hipSuccess ||
+      hipMemsetAsync(acc, 0, (size_t)R * sizeof(float), st) != hipSuccess) {
+    set_error("%s: zeroing the outputs failed", who);
+    return NRHIP_ERR_LAUNCH;
+  }
+  return NRHIP_OK;
+}
+
+// composited output (segments: packed samples only)
+static RenderArgs composite_args(float* features, float* depth, float* acc, float* weights, float stop_eps,
+                                 const int64_t* segments, void* stream) {
+  RenderArgs a{};
+  a.feat = features, a.depth = depth, a.acc = acc, a.w = weights;
+  a.stop_eps = stop_eps, a.segments = segments, a.stream = (hipStream_t)stream;
+  return a;
+}
+
+// The four training forwards past their ray descriptor: every output and save buffer present, the save buffers aligned
+// for 16-byte stores.  segments: packed samples only.  ovr (or NULL): the caller's rows for the samples inside an actor
+// box; a row index is 32 bits (packed: M < 2^31 is the descriptor's own check).
+static int field_fwd_train(const char* who, const nrhip_field* f, const RaysDev& rd, const int64_t* segments,
+                           const OverrideLaunch* ovr, float* feature, float* sdf, float* alpha, const SaveDev& sv,
+                           void* stream) {
+  NR_REQUIRE(feature && sdf && alpha && sv.enc && sv.hg && sv.xf && sv.hf, NRHIP_ERR_INVALID_ARG, "%s: NULL output", who);
+  NR_REQUIRE(((reinterpret_cast<uintptr_t>(sv.enc) | reinterpret_cast<uintptr_t>(sv.hg) |
+               reinterpret_cast<uintptr_t>(sv.xf) | reinterpret_cast<uintptr_t>(sv.hf)) & 15) == 0,
+             NRHIP_ERR_INVALID_ARG, "%s: save buffers must be 16-byte aligned", who);
+  RenderArgs a{};
+  a.feat = feature, a.sdf = sdf, a.alpha = alpha, a.sv = sv, a.segments = segments, a.stream = (hipStream_t)stream;
+  if (ovr) {
+    a.ovr = *ovr;
+    NR_REQUIRE(ovr->row && ovr->rows && ovr->dirs, NRHIP_ERR_INVALID_ARG, "%s: NULL pointer", who);
+    NR_REQUIRE((reinterpret_cast<uintptr_t>(ovr->rows) & 15) == 0, NRHIP_ERR_INVALID_ARG,
+               "%s: override rows must be 16-byte aligned", who);
+    NR_REQUIRE(segments || rd.R * rd.S < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "%s: N >= 2^31", who);
+  }
+  return dispatch_render(who, f, rd, segments != nullptr, Out::PerSample, ovr ? Src::Overrides : Src::Static, a);
+}
+
+// per-sample table select keeps the gather shape: one storage type, same features per level, no more levels than the
+// static grid
+static int check_actor_grid(const char* who, const nrhip_field* f, const nrhip_actors* a) {
+  NR_REQUIRE(f->grid.param_dtype == a->grid.param_dtype, NRHIP_ERR_UNSUPPORTED,
+             "%s: the static and the actor tables must share one storage type (fp32 or fp16)", who);
+  NR_REQUIRE(a->grid.n_features == f->grid.n_features && a->grid.num_levels <= f->grid.num_levels, NRHIP_ERR_UNSUPPORTED,
+             "%s: actor grid (L=%d F=%d) must have the static grid's features per level (F=%d) and at most its levels "
+             "(L=%d); use the unfused ops",
+             who, a->grid.num_levels, a->grid.n_features, f->grid.n_features, f->grid.num_levels);
+  return NRHIP_OK;
+}
+
+static bool actor_inputs_present(const nrhip_actors* a, const int32_t* cand_count, const int32_t* cand_actor,
+                                 const float* cand_w2b, const int32_t* workspace) {
+  return cand_count && cand_actor && cand_w2b && workspace && a->bounds && a->tables && a->n_actors >= 1 &&
+         a->actor_scale > 0.f;
+}
+
+// Most rays of a street scene pass no actor at all.  The processing order is split on the device into those rays and
+// the rays with candidates (no host round trip): the first slice runs through the plain static kernel at full speed,
+// the second through the ACT instantiation, which pays for the candidate walk in registers and latency.
+// workspace: int32 [R + 4] (the split order, then the two ranges)
+static int render_split_by_candidates(const char* who, const nrhip_field* f, const nrhip_actors* a, RaysDev rd,
+                                      bool packed, RenderArgs ra, const int32_t* cand_count, const int32_t* cand_actor,
+                                      const float* cand_w2b, int32_t* workspace) {
+  ActorLaunch al;
+  al.ad.K = a->max_candidates > 0 ? a->max_candidates : NRHIP_DEFAULT_ACTOR_CANDIDATES;
+  al.ad.La = a->grid.num_levels, al.ad.log2T = a->grid.log2_table_size, al.ad.scale = a->actor_scale;
+  for (int l = 0; l < NRHIP_MAX_LEVELS; ++l) al.ad.scal[l] = a->grid.scalings[l];
+  al.cand_count = cand_count, al.cand_actor = cand_actor, al.cand_w2b = cand_w2b, al.bounds = a->bounds, al.tables = a->tables;
+  int32_t* order2 = workspace;
+  int32_t* ranges = workspace + rd.R;
+  actor_partition_kernel<<<1, kPartThreads, 0, ra.stream>>>(cand_count, rd.order, rd.R, order2, ranges);
+  if (int e = check_launch("actor_partition")) return e;
+  rd.order = order2;
+  ra.range = ranges;
+  if (int e = dispatch_render(who, f, rd, packed, Out::Composite, Src::Static, ra)) return e;
+  ra.range = ranges + 2, ra.actors = al;
+  return dispatch_render(who, f, rd, packed, Out::Composite, Src::Actors, ra);
+}
+
+// The RaysDev that launch_render takes for the packed layouts: `S` carries the sample count M, the stride is 0, and the
+// segments travel beside it in RenderArgs (the kernel reads them through its `tables` argument or its first save pointer).
+static RaysDev packed_launch_rays(const nrhip_packed_rays& rays) {
+  const PackedRaysDev p = to_dev(rays);
+  return RaysDev{p.R, p.M, 0, p.o, p.d, p.area, p.starts, p.ends, rays.order};
+}
+
 extern "C" int nrhip_field_fwd(const nrhip_field* f, const nrhip_rays* rays, float* feature, float* sdf, float* alpha,
                                void* stream) {
   if (int e = validate_field(f)) return e;
@@ -1567,17 +1608,7 @@ extern "C" int nrhip_field_fwd(const nrhip_field* f, const nrhip_rays* rays, flo
   NR_REQUIRE(feature && sdf && alpha, NRHIP_ERR_INVALID_ARG, "field_fwd: NULL output");
   RenderArgs a{};
   a.feat = feature, a.sdf = sdf, a.alpha = alpha, a.stream = (hipStream_t)stream;
-  return dispatch_render(f, rays, Out::PerSample, Src::Static, a);
-}
-
-// the two training forwards: every output and save buffer present, the save buffers aligned for 16-byte stores
-static int check_train_buffers(const char* who, const float* feature, const float* sdf, const float* alpha,
-                               const SaveDev& sv) {
-  NR_REQUIRE(feature && sdf && alpha && sv.enc && sv.hg && sv.xf && sv.hf, NRHIP_ERR_INVALID_ARG, "%s: NULL output", who);
-  NR_REQUIRE(((reinterpret_cast<uintptr_t>(sv.enc) | reinterpret_cast<uintptr_t>(sv.hg) |
-               reinterpret_cast<uintptr_t>(sv.xf) | reinterpret_cast<uintptr_t>(sv.hf)) & 15) == 0,
-             NRHIP_ERR_INVALID_ARG, "%s: save buffers must be 16-byte aligned", who);
-  return NRHIP_OK;
+  return dispatch_render("field_fwd", f, to_dev(*rays), false, Out::PerSample, Src::Static, a);
 }
 
 extern "C" int nrhip_field_fwd_train(const nrhip_field* f, const nrhip_rays* rays, float* feature, float* sdf,
@@ -1586,11 +1617,8 @@ extern "C" int nrhip_field_fwd_train(const nrhip_field* f, const nrhip_rays* ray
   if (int e = validate_field(f)) return e;
   if (int e = validate_rays(rays)) return e;
   if (rays->n_rays == 0 || rays->n_samples == 0) return NRHIP_OK;
-  RenderArgs a{};
-  a.feat = feature, a.sdf = sdf, a.alpha = alpha, a.stream = (hipStream_t)stream;
-  a.sv = SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
-  if (int e = check_train_buffers("field_fwd_train", feature, sdf, alpha, a.sv)) return e;
-  return dispatch_render(f, rays, Out::PerSample, Src::Static, a);
+  return field_fwd_train("field_fwd_train", f, to_dev(*rays), nullptr, nullptr, feature, sdf, alpha,
+                         SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden}, stream);
 }
 
 extern "C" int nrhip_field_fwd_train_ovr(const nrhip_field* f, const nrhip_rays* rays, const int32_t* ovr_row,
@@ -1600,17 +1628,9 @@ extern "C" int nrhip_field_fwd_train_ovr(const nrhip_field* f, const nrhip_rays*
   if (int e = validate_field(f)) return e;
   if (int e = validate_rays(rays)) return e;
   if (rays->n_rays == 0 || rays->n_samples == 0) return NRHIP_OK;
-  RenderArgs a{};
-  a.feat = feature, a.sdf = sdf, a.alpha = alpha, a.stream = (hipStream_t)stream;
-  a.sv = SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
-  a.ovr = OverrideLaunch{ovr_row, ovr_rows, ovr_dirs};
-  if (int e = check_train_buffers("field_fwd_train_ovr", feature, sdf, alpha, a.sv)) return e;
-  NR_REQUIRE(ovr_row && ovr_rows && ovr_dirs, NRHIP_ERR_INVALID_ARG, "field_fwd_train_ovr: NULL pointer");
-  NR_REQUIRE((reinterpret_cast<uintptr_t>(ovr_rows) & 15) == 0, NRHIP_ERR_INVALID_ARG,
-             "field_fwd_train_ovr: override rows must be 16-byte aligned");
-  NR_REQUIRE(rays->n_rays * rays->n_samples < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "field_fwd_train_ovr: N >= 2^31");
-  NR_REQUIRE(f->grid.param_dtype == 0 || f->grid.param_dtype == 1, NRHIP_ERR_INVALID_ARG, "field_fwd_train_ovr: dtype");
-  return dispatch_render(f, rays, Out::PerSample, Src::Overrides, a);
+  const OverrideLaunch ovr{ovr_row, ovr_rows, ovr_dirs};
+  return field_fwd_train("field_fwd_train_ovr", f, to_dev(*rays), nullptr, &ovr, feature, sdf, alpha,
+                         SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden}, stream);
 }
 
 extern "C" int nrhip_render_fwd_ex(const nrhip_field* f, const nrhip_rays* rays, float* out_features, float* out_depth,
@@ -1620,12 +1640,9 @@ extern "C" int nrhip_render_fwd_ex(const nrhip_field* f, const nrhip_rays* rays,
   if (rays->n_rays == 0) return NRHIP_OK;
   NR_REQUIRE(out_features && out_depth && out_acc, NRHIP_ERR_INVALID_ARG, "render_fwd: NULL output");
   NR_REQUIRE(rays->n_samples >= 1, NRHIP_ERR_INVALID_ARG, "render_fwd: needs >= 1 sample per ray");
-  NR_REQUIRE(early_stop_eps >= 0.f && early_stop_eps < 1.f, NRHIP_ERR_INVALID_ARG,
-             "render_fwd: early_stop_eps %g not in [0,1)", (double)early_stop_eps);
-  RenderArgs a{};
-  a.feat = out_features, a.depth = out_depth, a.acc = out_acc, a.w = out_weights;
-  a.stop_eps = early_stop_eps, a.stream = (hipStream_t)stream;
-  return dispatch_render(f, rays, Out::Composite, Src::Static, a);
+  if (int e = check_stop_eps("render_fwd", early_stop_eps)) return e;
+  return dispatch_render("render_fwd", f, to_dev(*rays), false, Out::Composite, Src::Static,
+                         composite_args(out_features, out_depth, out_acc, out_weights, early_stop_eps, nullptr, stream));
 }
 
 extern "C" int nrhip_render_fwd(const nrhip_field* f, const nrhip_rays* rays, float* out_features, float* out_depth,
@@ -1633,50 +1650,29 @@ extern "C" int nrhip_render_fwd(const nrhip_field* f, const nrhip_rays* rays, fl
   return nrhip_render_fwd_ex(f, rays, out_features, out_depth, out_acc, out_weights, 0.f, stream);
 }
 
-// The RaysDev that launch_render takes for Lay::Packed / Lay::PackedRows: `S` carries the sample count M, the stride is 0,
-// and the segments travel beside it in RenderArgs (the kernel reads them through its `tables` argument).
-static RaysDev packed_launch_rays(const nrhip_packed_rays& rays) {
-  const PackedRaysDev p = to_dev(rays);
-  return RaysDev{p.R, p.M, 0, p.o, p.d, p.area, p.starts, p.ends, rays.order};
-}
-
 extern "C" int nrhip_render_fwd_packed(const nrhip_field* f, const nrhip_packed_rays* rays, float* out_features,
                                        float* out_depth, float* out_acc, float* out_weights, float early_stop_eps,
                                        void* stream) {
+  const char* who = "render_fwd_packed";
   if (int e = validate_field(f)) return e;
-  if (int e = validate_packed_rays("render_fwd_packed", rays, true)) return e;
-  const int64_t R = rays->n_rays;
-  if (R == 0) return NRHIP_OK;
-  NR_REQUIRE(out_features && out_depth && out_acc, NRHIP_ERR_INVALID_ARG, "render_fwd_packed: NULL output");
-  NR_REQUIRE(early_stop_eps >= 0.f && early_stop_eps < 1.f, NRHIP_ERR_INVALID_ARG,
-             "render_fwd_packed: early_stop_eps %g not in [0,1)", (double)early_stop_eps);
-  hipStream_t st = (hipStream_t)stream;
-  if (rays->n_samples == 0) {  // every segment is empty: no sample pointer (and no segment) is read, the per-ray outputs are zeroed
-    if (hipMemsetAsync(out_features, 0, (size_t)R * 32 * sizeof(float), st) != hipSuccess ||
-        hipMemsetAsync(out_depth, 0, (size_t)R * sizeof(float), st) != hipSuccess ||
-        hipMemsetAsync(out_acc, 0, (size_t)R * sizeof(float), st) != hipSuccess) {
-      set_error("render_fwd_packed: zeroing the outputs failed");
-      return NRHIP_ERR_LAUNCH;
-    }
-    return NRHIP_OK;
-  }
-  RenderArgs a{};
-  a.feat = out_features, a.depth = out_depth, a.acc = out_acc, a.w = out_weights;
-  a.stop_eps = early_stop_eps, a.stream = st, a.segments = rays->segments;
-  return dispatch_render_packed(f, Out::Composite, packed_launch_rays(*rays), a);
+  if (int e = validate_packed_rays(who, rays, true)) return e;
+  if (rays->n_rays == 0) return NRHIP_OK;
+  NR_REQUIRE(out_features && out_depth && out_acc, NRHIP_ERR_INVALID_ARG, "%s: NULL output", who);
+  if (int e = check_stop_eps(who, early_stop_eps)) return e;
+  if (rays->n_samples == 0) return zero_ray_outputs(who, rays->n_rays, out_features, out_depth, out_acc, (hipStream_t)stream);
+  return dispatch_render(who, f, packed_launch_rays(*rays), true, Out::Composite, Src::Static,
+                         composite_args(out_features, out_depth, out_acc, out_weights, early_stop_eps, rays->segments, stream));
 }
 
 extern "C" int nrhip_field_fwd_train_packed(const nrhip_field* f, const nrhip_packed_rays* rays, float* feature,
                                             float* geo_out, float* head, float* save_enc, float* save_geo_hidden,
                                             float* save_feat_in, float* save_feat_hidden, void* stream) {
+  const char* who = "field_fwd_train_packed";
   if (int e = validate_field(f)) return e;
-  if (int e = validate_packed_rays("field_fwd_train_packed", rays, true)) return e;
+  if (int e = validate_packed_rays(who, rays, true)) return e;
   if (rays->n_rays == 0 || rays->n_samples == 0) return NRHIP_OK;  // nothing per sample to write: no pointer is read
-  RenderArgs a{};
-  a.feat = feature, a.sdf = geo_out, a.alpha = head, a.stream = (hipStream_t)stream, a.segments = rays->segments;
-  a.sv = SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
-  if (int e = check_train_buffers("field_fwd_train_packed", feature, geo_out, head, a.sv)) return e;
-  return dispatch_render_packed(f, Out::PerSample, packed_launch_rays(*rays), a);
+  return field_fwd_train(who, f, packed_launch_rays(*rays), rays->segments, nullptr, feature, geo_out, head,
+                         SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden}, stream);
 }
 
 extern "C" int nrhip_field_fwd_train_packed_ovr(const nrhip_field* f, const nrhip_packed_rays* rays,
@@ -1684,65 +1680,34 @@ extern "C" int nrhip_field_fwd_train_packed_ovr(const nrhip_field* f, const nrhi
                                                 float* feature, float* geo_out, float* head, float* save_enc,
                                                 float* save_geo_hidden, float* save_feat_in, float* save_feat_hidden,
                                                 void* stream) {
+  const char* who = "field_fwd_train_packed_ovr";
   if (int e = validate_field(f)) return e;
-  if (int e = validate_packed_rays("field_fwd_train_packed_ovr", rays, true)) return e;
+  if (int e = validate_packed_rays(who, rays, true)) return e;
   if (rays->n_rays == 0 || rays->n_samples == 0) return NRHIP_OK;  // nothing per sample to write: no pointer is read
-  RenderArgs a{};
-  a.feat = feature, a.sdf = geo_out, a.alpha = head, a.stream = (hipStream_t)stream, a.segments = rays->segments;
-  a.sv = SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden};
-  a.ovr = OverrideLaunch{ovr_row, ovr_rows, ovr_dirs};
-  if (int e = check_train_buffers("field_fwd_train_packed_ovr", feature, geo_out, head, a.sv)) return e;
-  NR_REQUIRE(ovr_row && ovr_rows && ovr_dirs, NRHIP_ERR_INVALID_ARG, "field_fwd_train_packed_ovr: NULL pointer");
-  NR_REQUIRE((reinterpret_cast<uintptr_t>(ovr_rows) & 15) == 0, NRHIP_ERR_INVALID_ARG,
-             "field_fwd_train_packed_ovr: override rows must be 16-byte aligned");
-  NR_REQUIRE(f->grid.param_dtype == 0 || f->grid.param_dtype == 1, NRHIP_ERR_INVALID_ARG,
-             "field_fwd_train_packed_ovr: dtype");
-  return dispatch_render_packed_ovr(f, packed_launch_rays(*rays), a);
+  const OverrideLaunch ovr{ovr_row, ovr_rows, ovr_dirs};
+  return field_fwd_train(who, f, packed_launch_rays(*rays), rays->segments, &ovr, feature, geo_out, head,
+                         SaveDev{save_enc, save_geo_hidden, save_feat_in, save_feat_hidden}, stream);
 }
 
 extern "C" int nrhip_render_fwd_actors(const nrhip_field* f, const nrhip_actors* a, const nrhip_rays* rays,
                                        const int32_t* cand_count, const int32_t* cand_actor, const float* cand_w2b,
                                        float* out_features, float* out_depth, float* out_acc, float* out_weights,
                                        float early_stop_eps, int32_t* workspace, void* stream) {
+  const char* who = "render_fwd_actors";
   if (int e = validate_field(f)) return e;
   if (int e = validate_rays(rays)) return e;
-  NR_REQUIRE(a, NRHIP_ERR_INVALID_ARG, "render_fwd_actors: actors descriptor is NULL");
+  NR_REQUIRE(a, NRHIP_ERR_INVALID_ARG, "%s: actors descriptor is NULL", who);
   if (int e = validate_grid(&a->grid)) return e;
   if (rays->n_rays == 0) return NRHIP_OK;
-  NR_REQUIRE(out_features && out_depth && out_acc && cand_count && cand_actor && cand_w2b && workspace && a->bounds &&
-                 a->tables && a->n_actors >= 1 && a->actor_scale > 0.f,
-             NRHIP_ERR_INVALID_ARG, "render_fwd_actors: NULL pointer / empty actor set");
-  NR_REQUIRE(rays->n_samples >= 1, NRHIP_ERR_INVALID_ARG, "render_fwd_actors: needs >= 1 sample per ray");
-  NR_REQUIRE(early_stop_eps >= 0.f && early_stop_eps < 1.f, NRHIP_ERR_INVALID_ARG,
-             "render_fwd_actors: early_stop_eps %g not in [0,1)", (double)early_stop_eps);
-  // per-sample table select keeps the gather shape: same features per level, no more levels than the static grid
-  NR_REQUIRE(f->grid.param_dtype == a->grid.param_dtype, NRHIP_ERR_UNSUPPORTED,
-             "render_fwd_actors: the static and the actor tables must share one storage type (fp32 or fp16)");
-  NR_REQUIRE(a->grid.n_features == f->grid.n_features && a->grid.num_levels <= f->grid.num_levels, NRHIP_ERR_UNSUPPORTED,
-             "render_fwd_actors: actor grid (L=%d F=%d) must have the static grid's features per level (F=%d) and at most "
-             "its levels (L=%d); use the unfused ops",
-             a->grid.num_levels, a->grid.n_features, f->grid.n_features, f->grid.num_levels);
-  RenderArgs ra{};
-  ra.feat = out_features, ra.depth = out_depth, ra.acc = out_acc, ra.w = out_weights;
-  ra.stop_eps = early_stop_eps, ra.stream = (hipStream_t)stream;
-  ActorLaunch al;
-  al.ad.K = a->max_candidates > 0 ? a->max_candidates : NRHIP_DEFAULT_ACTOR_CANDIDATES;
-  al.ad.La = a->grid.num_levels, al.ad.log2T = a->grid.log2_table_size, al.ad.scale = a->actor_scale;
-  for (int l = 0; l < NRHIP_MAX_LEVELS; ++l) al.ad.scal[l] = a->grid.scalings[l];
-  al.cand_count = cand_count, al.cand_actor = cand_actor, al.cand_w2b = cand_w2b, al.bounds = a->bounds, al.tables = a->tables;
-  // Most rays of a street scene pass no actor at all.  The processing order is split on the device into those rays and
-  // the rays with candidates (no host round trip): the first slice runs through the plain static kernel at full speed,
-  // the second through the ACT instantiation, which pays for the candidate walk in registers and latency.
-  int32_t* order2 = workspace;
-  int32_t* ranges = workspace + rays->n_rays;
-  actor_partition_kernel<<<1, kPartThreads, 0, (hipStream_t)stream>>>(cand_count, rays->order, rays->n_rays, order2, ranges);
-  if (int e = check_launch("actor_partition")) return e;
-  nrhip_rays split = *rays;
-  split.order = order2;
-  ra.range = ranges;
-  if (int e = dispatch_render(f, &split, Out::Composite, Src::Static, ra)) return e;
-  ra.range = ranges + 2, ra.actors = al;
-  return dispatch_render(f, &split, Out::Composite, Src::Actors, ra);
+  NR_REQUIRE(out_features && out_depth && out_acc && actor_inputs_present(a, cand_count, cand_actor, cand_w2b, workspace),
+             NRHIP_ERR_INVALID_ARG, "%s: NULL pointer / empty actor set", who);
+  NR_REQUIRE(rays->n_samples >= 1, NRHIP_ERR_INVALID_ARG, "%s: needs >= 1 sample per ray", who);
+  if (int e = check_stop_eps(who, early_stop_eps)) return e;
+  if (int e = check_actor_grid(who, f, a)) return e;
+  return render_split_by_candidates(
+      who, f, a, to_dev(*rays), false,
+      composite_args(out_features, out_depth, out_acc, out_weights, early_stop_eps, nullptr, stream), cand_count,
+      cand_actor, cand_w2b, workspace);
 }
 
 // The packed counterpart of nrhip_render_fwd_actors: the same three launches on the march's ragged segments.
@@ -1750,52 +1715,21 @@ extern "C" int nrhip_render_fwd_packed_actors(const nrhip_field* f, const nrhip_
                                               const int32_t* cand_count, const int32_t* cand_actor, const float* cand_w2b,
                                               float* out_features, float* out_depth, float* out_acc, float* out_weights,
                                               float early_stop_eps, int32_t* workspace, void* stream) {
+  const char* who = "render_fwd_packed_actors";
   if (int e = validate_field(f)) return e;
-  if (int e = validate_packed_rays("render_fwd_packed_actors", rays, true)) return e;
-  NR_REQUIRE(a, NRHIP_ERR_INVALID_ARG, "render_fwd_packed_actors: actors descriptor is NULL");
+  if (int e = validate_packed_rays(who, rays, true)) return e;
+  NR_REQUIRE(a, NRHIP_ERR_INVALID_ARG, "%s: actors descriptor is NULL", who);
   if (int e = validate_grid(&a->grid)) return e;
-  const int64_t R = rays->n_rays;
-  if (R == 0) return NRHIP_OK;
-  NR_REQUIRE(out_features && out_depth && out_acc, NRHIP_ERR_INVALID_ARG, "render_fwd_packed_actors: NULL output");
-  NR_REQUIRE(early_stop_eps >= 0.f && early_stop_eps < 1.f, NRHIP_ERR_INVALID_ARG,
-             "render_fwd_packed_actors: early_stop_eps %g not in [0,1)", (double)early_stop_eps);
-  NR_REQUIRE(f->grid.param_dtype == a->grid.param_dtype, NRHIP_ERR_UNSUPPORTED,
-             "render_fwd_packed_actors: the static and the actor tables must share one storage type (fp32 or fp16)");
-  NR_REQUIRE(a->grid.n_features == f->grid.n_features && a->grid.num_levels <= f->grid.num_levels, NRHIP_ERR_UNSUPPORTED,
-             "render_fwd_packed_actors: actor grid (L=%d F=%d) must have the static grid's features per level (F=%d) and at "
-             "most its levels (L=%d); use the unfused ops",
-             a->grid.num_levels, a->grid.n_features, f->grid.n_features, f->grid.num_levels);
-  hipStream_t st = (hipStream_t)stream;
-  if (rays->n_samples == 0) {  // as nrhip_render_fwd_packed: nothing per sample is read, the per-ray outputs are zeroed
-    if (hipMemsetAsync(out_features, 0, (size_t)R * 32 * sizeof(float), st) != hipSuccess ||
-        hipMemsetAsync(out_depth, 0, (size_t)R * sizeof(float), st) != hipSuccess ||
-        hipMemsetAsync(out_acc, 0, (size_t)R * sizeof(float), st) != hipSuccess) {
-      set_error("render_fwd_packed_actors: zeroing the outputs failed");
-      return NRHIP_ERR_LAUNCH;
-    }
-    return NRHIP_OK;
-  }
-  NR_REQUIRE(cand_count && cand_actor && cand_w2b && workspace && a->bounds && a->tables && a->n_actors >= 1 &&
-                 a->actor_scale > 0.f,
-             NRHIP_ERR_INVALID_ARG, "render_fwd_packed_actors: NULL pointer / empty actor set");
-  NR_REQUIRE(R < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "render_fwd_packed_actors: n_rays >= 2^31");
-  RenderArgs ra{};
-  ra.feat = out_features, ra.depth = out_depth, ra.acc = out_acc, ra.w = out_weights;
-  ra.stop_eps = early_stop_eps, ra.stream = st, ra.segments = rays->segments;
-  ActorLaunch al;
-  al.ad.K = a->max_candidates > 0 ? a->max_candidates : NRHIP_DEFAULT_ACTOR_CANDIDATES;
-  al.ad.La = a->grid.num_levels, al.ad.log2T = a->grid.log2_table_size, al.ad.scale = a->actor_scale;
-  for (int l = 0; l < NRHIP_MAX_LEVELS; ++l) al.ad.scal[l] = a->grid.scalings[l];
-  al.cand_count = cand_count, al.cand_actor = cand_actor, al.cand_w2b = cand_w2b, al.bounds = a->bounds, al.tables = a->tables;
-  // the split of nrhip_render_fwd_actors: rays without candidates run the static packed kernel, the others the actor-aware one
-  int32_t* order2 = workspace;
-  int32_t* ranges = workspace + R;
-  actor_partition_kernel<<<1, kPartThreads, 0, st>>>(cand_count, rays->order, R, order2, ranges);
-  if (int e = check_launch("actor_partition")) return e;
-  RaysDev rd = packed_launch_rays(*rays);
-  rd.order = order2;
-  ra.range = ranges;
-  if (int e = dispatch_render_packed(f, Out::Composite, rd, ra)) return e;
-  ra.range = ranges + 2, ra.actors = al;
-  return dispatch_render_packed_actors(f, rd, ra);
+  if (rays->n_rays == 0) return NRHIP_OK;
+  NR_REQUIRE(out_features && out_depth && out_acc, NRHIP_ERR_INVALID_ARG, "%s: NULL output", who);
+  if (int e = check_stop_eps(who, early_stop_eps)) return e;
+  if (int e = check_actor_grid(who, f, a)) return e;
+  if (rays->n_samples == 0) return zero_ray_outputs(who, rays->n_rays, out_features, out_depth, out_acc, (hipStream_t)stream);
+  NR_REQUIRE(actor_inputs_present(a, cand_count, cand_actor, cand_w2b, workspace), NRHIP_ERR_INVALID_ARG,
+             "%s: NULL pointer / empty actor set", who);
+  NR_REQUIRE(rays->n_rays < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "%s: n_rays >= 2^31", who);
+  return render_split_by_candidates(
+      who, f, a, packed_launch_rays(*rays), true,
+      composite_args(out_features, out_depth, out_acc, out_weights, early_stop_eps, rays->segments, stream), cand_count,
+      cand_actor, cand_w2b, workspace);
 }

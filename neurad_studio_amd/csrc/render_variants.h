@@ -37,15 +37,14 @@ enum class Lay {
 // The legal mixes, asserted by the kernel for every instantiation.
 constexpr bool render_variant_ok(int L, int F, Out out, Src src, Prod prod, Lay lay = Lay::Dense) {
   // packed samples: the composited static-scene kernel, fp32 or pair products.  The packed kernels have no rows of their
-  // own below: every row this rule admits is instantiated in both layouts (render.hip: dispatch_render_packed)
+  // own below: every row this rule admits is instantiated in both layouts (render.hip: packed_lay, launch_row)
   if (lay == Lay::Packed && !(out == Out::Composite && src == Src::Static && prod != Prod::Bf16Split)) return false;
   // ... and the per-sample static-scene kernel with fp32 products (the packed training forward), derived the same way
   if (lay == Lay::PackedRows && !(out == Out::PerSample && src == Src::Static && prod == Prod::F32)) return false;
   // ... and the composited actor kernel, fp32 products: every `Composite, Actors, F32` row, derived the same way
-  // (render.hip: dispatch_render_packed_actors)
   if (lay == Lay::PackedActors && !(out == Out::Composite && src == Src::Actors && prod == Prod::F32)) return false;
   // ... and the per-sample kernel with row overrides, fp32 products: every `PerSample, Overrides, F32` row, derived the
-  // same way (render.hip: dispatch_render_packed_ovr)
+  // same way
   if (lay == Lay::PackedRowsOvr && !(out == Out::PerSample && src == Src::Overrides && prod == Prod::F32)) return false;
   // actors (static and actor tables share one storage type) and the eval-table layout: the composited eval kernel
   if ((src == Src::Actors || src == Src::EvalTable) && out != Out::Composite) return false;

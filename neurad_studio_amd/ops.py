@@ -1474,6 +1474,16 @@ def _c_packed_rays(who: str, origins, directions, pixel_area, t_starts, t_ends, 
     return r, (o, d, a, s, e, seg, _ray_order(r, order))
 
 
+def _c_ray_candidates(who: str, cand, R: int, K: int):
+    """one candidate list per RAY (``actor_prepare_line``), checked: -> cand_count int32 [R], cand_actor int32 [R,K],
+    cand_w2b [R,K,12]"""
+    cnt, act, w2b = (_chk(cand[0], "cand_count", torch.int32), _chk(cand[1], "cand_actor", torch.int32),
+                     _chk(cand[2], "cand_w2b"))
+    if cnt.shape != (R,) or act.shape != (R, K) or w2b.shape != (R, K, 12):
+        raise ValueError(f"{who}: candidate lists must be [R], [R,K], [R,K,12] with R = {R}, K = {K}: one list per ray")
+    return cnt, act, w2b
+
+
 def render_fwd_packed(fs: FieldSpec, origins, directions, pixel_area, t_starts, t_ends, segments,
                       return_weights: bool = False, early_stop_eps: float = 0.0, order: Optional[Tensor] = None):
     """The fused render kernel on the march's packed samples: per-RAY origins [R,3] / directions [R,3] / pixel_area [R],
@@ -1498,11 +1508,7 @@ def render_fwd_packed_actors(fs: FieldSpec, spec: "ActorSpec", cand, origins, di
     f, keep2 = fs.c_field()
     a, keep3 = spec.c_actors()
     R, dev = r.n_rays, keep[0].device
-    cnt, act, w2b = (_chk(cand[0], "cand_count", torch.int32), _chk(cand[1], "cand_actor", torch.int32),
-                     _chk(cand[2], "cand_w2b"))
-    if cnt.shape != (R,) or act.shape != (R, a.max_candidates) or w2b.shape != (R, a.max_candidates, 12):
-        raise ValueError(f"render_fwd_packed_actors: candidate lists must be [R], [R,K], [R,K,12] with R = {R}, K = "
-                         f"{a.max_candidates}: one list per ray")
+    cnt, act, w2b = _c_ray_candidates("render_fwd_packed_actors", cand, R, a.max_candidates)
     feats, depth, acc, _ = _render_outputs(R, 0, dev, False, None if out is None else tuple(out[:3]))
     w = (torch.empty_like(keep[3]) if out is None or out[3] is None else _flat(out[3], "weights", keep[3].shape[0])) \
         if return_weights else None
@@ -1558,11 +1564,7 @@ def actor_find_packed(spec: "ActorSpec", cand, origins, directions, pixel_area, 
     a, keep2 = spec.c_actors()
     ri = _packed_ray_of("actor_find_packed", r, ray_indices)
     R, m, dev = r.n_rays, r.n_samples, keep[0].device
-    cnt, act, w2b = (_chk(cand[0], "cand_count", torch.int32), _chk(cand[1], "cand_actor", torch.int32),
-                     _chk(cand[2], "cand_w2b"))
-    if cnt.shape != (R,) or act.shape != (R, a.max_candidates) or w2b.shape != (R, a.max_candidates, 12):
-        raise ValueError(f"actor_find_packed: candidate lists must be [R], [R,K], [R,K,12] with R = {R}, K = "
-                         f"{a.max_candidates}: one list per ray")
+    cnt, act, w2b = _c_ray_candidates("actor_find_packed", cand, R, a.max_candidates)
     flip = _opt(ray_flip, "ray_flip")
     if flip is not None and flip.shape[0] != R:
         raise ValueError(f"actor_find_packed: ray_flip is per ray, [R = {R}]")

@@ -313,3 +313,77 @@ def test_graph_capture_replays_bitwise(ops):
         torch.cuda.synchronize()
         for a, b in zip(captured, eager):
             assert torch.equal(a, b)
+
+
+# ---- 9. a preferred row without a packed form --------------------------------------------------------------------------
+FALLBACK_COUNTS = (0, 1, 15, 16, 17, 33, 0)
+FALLBACK_LG = 15  # level 0 (resolution 16) gets a shadow copy in the eval table: 3 * 5 bits <= log2 T
+
+
+def fallback_setup(ops, H, half):
+    p = field_params(use_sdf=True, L=8, F=4, lg=FALLBACK_LG, H=H, mn=16, mx=1024, scale=2.0)
+    p.beta = 3.0
+    rays = packed_rays(FALLBACK_COUNTS, 37)
+    assert rays[3].shape[0] == sum(FALLBACK_COUNTS) == 82
+    return to_spec(ops, p, half=half), rays
+
+
+# (8, 4, 32): no split row, the switch changes nothing on the dense side either | (8, 4, 64): choose_variant prefers the
+# `Composite, Static, Bf16Split` row, which has no packed form
+@pytest.mark.parametrize("H", [32, 64], ids=["H32", "H64"])
+@pytest.mark.parametrize("half", [False, True], ids=["fp32", "fp16"])
+def test_packed_render_falls_back_from_the_split_products(ops, switches, H, half):
+    fs, rays = fallback_setup(ops, H, half)
+    switches.set("NRHIP_MLP_PAIRS", "0")
+    want = fused_route(ops, fs, rays)
+    switches.set("NRHIP_MLP_SPLIT_BF16", "1")
+    got = fused_route(ops, fs, rays)
+    assert len(got) == 4
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["fp32", "fp16"])
+def test_packed_training_forward_falls_back_from_the_pair_products(ops, switches, half):
+    """NRHIP_MLP_PAIRS_TRAIN=1 makes the `PerSample, Static, F16Pairs` row the preferred one; packed rows exist with fp32
+    products only"""
+    fs, rays = fallback_setup(ops, 32, half)
+    args = [dev(a) for a in rays[:5]] + [dev(rays[5], torch.int64)]
+    want = ops.field_fwd_train_packed(fs, *args)
+    switches.set("NRHIP_MLP_PAIRS_TRAIN", "1")
+    got = ops.field_fwd_train_packed(fs, *args)
+    buffers = lambda res: list(res[0]) + list(res[1])  # noqa: E731
+    assert len(buffers(got)) == 7
+    for a, b in zip(buffers(got), buffers(want)):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("half", [False, True], ids=["fp32", "fp16"])
+def test_packed_render_ignores_a_handed_over_eval_table(ops, switches, monkeypatch, half):
+    """A field descriptor with eval_table / eval_layout makes the eval-table row the preferred one; it has no packed form,
+    and the fp32 row that runs instead reads the plain table."""
+    from neurad_studio_amd import _lib
+
+    fs, rays = fallback_setup(ops, 32, half)
+    switches.set("NRHIP_MLP_PAIRS", "0")
+    monkeypatch.setattr(ops, "_EVAL_RELAYOUT", True)
+    ops.clear_eval_tables()
+    relaid = ops.eval_table(fs.grid, fs.table)
+    assert relaid is not None
+    r, keep = ops._c_packed_rays("render_fwd_packed", *(dev(a) for a in rays[:5]), dev(rays[5], torch.int64))
+
+    def run(with_eval_table):
+        f, keep2 = fs.c_field()
+        if with_eval_table:
+            f.eval_table, f.eval_layout = relaid[0].data_ptr(), relaid[1]
+        out = [torch.empty((7, 32), device="cuda"), torch.empty((7, 1), device="cuda"), torch.empty((7, 1), device="cuda"),
+               torch.empty((82,), device="cuda")]
+        _lib.call("nrhip_render_fwd_packed", f, r, *(ops._ptr(t) for t in out), 0.0, ops._stream())
+        torch.cuda.synchronize()
+        return out
+
+    want, got = run(False), run(True)
+    ops.clear_eval_tables()
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+    assert bool((want[2][1:6] > 0).all())  # (the rays with samples did render something)

@@ -39,7 +39,7 @@ int main() {
 
 def test_packed_override_instantiations_are_the_override_rows(tmp_path):
     """The rule itself is asked -- the header compiled as host code: Lay::PackedRowsOvr admits exactly the five
-    `PerSample, Overrides, F32` rows (render.hip: launch_packed_ovr_row); Packed, PackedRows and PackedActors admit what
+    `PerSample, Overrides, F32` rows (render.hip: packed_lay, launch_row); Packed, PackedRows and PackedActors admit what
     they admitted before, and every row is still a dense kernel."""
     import __graft_entry__ as ge
 

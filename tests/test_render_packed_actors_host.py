@@ -28,7 +28,7 @@ int main() {
 
 def test_packed_actor_instantiations_are_the_composited_actor_rows(tmp_path):
     """The rule itself is asked -- the header compiled as host code: Lay::PackedActors admits exactly the five
-    `Composite, Actors, F32` rows (render.hip: launch_packed_actors_row)."""
+    `Composite, Actors, F32` rows (render.hip: packed_lay, launch_row)."""
     import __graft_entry__ as ge
 
     src, exe = tmp_path / "rule.cpp", tmp_path / "rule"

@@ -76,7 +76,7 @@ int main() {
 
 def test_packed_instantiations_are_the_composited_static_rows(tmp_path):
     """The dispatcher instantiates the packed layout for exactly the rows render_variant_ok(..., Lay::Packed) admits
-    (render.hip: launch_packed_row).  The rule itself is asked -- the header compiled as host code -- and must pick the
+    (render.hip: launch_row).  The rule itself is asked -- the header compiled as host code -- and must pick the
     `Composite, Static` rows with F32 or F16Pairs products: 14 + 6, every fused grid at both widths among them."""
     import __graft_entry__ as ge
 
