@@ -14,8 +14,13 @@
 //     with row_shr DPP ops; the four rows (g) carry identical copies, each accumulates for its own channels.
 // Exact fp32 (f32-input MFMA == fmaf chain): the parity target is the reference's fp32 torch path.
 //
-// What bounds this kernel on MI355X is the chip's random-line miss rate (every fine-level corner is a new 128-byte
-// line for 8-16 useful bytes), with the fp32 MFMA chain behind it.  Hence:
+// What bounds this kernel on MI355X: the far tiles of a ray by the chip's random-line miss rate (every fine-level corner
+// is a new 128-byte line for 8-16 useful bytes), the near tiles -- since the MLP products run as fp16 pairs -- by vector
+// instruction issue, VALU and MFMA together filling the SIMD's cycles.  Hence:
+//   * BLOCK GEOMETRY.  What depends on a sample alone (interval, gaussian, contraction: nine IEEE divisions and two cube
+//     roots) is computed once per sample, by the 64 lanes of the wave for a block of four consecutive tiles, and parked
+//     in the wave's own LDS rows (Lds::GEO) -- not once per tile by the four lanes that share a sample.  The blend reads
+//     the rows again instead of carrying position and std through the MLPs in registers (fill_block, get_block).
 //   * SOFTWARE PIPELINE.  A wave's (ray, tile) sequence is flattened; the 8*L/4 corner gathers of the NEXT tile (the
 //     next tile of this ray or the first tile of the wave's next ray) are issued right after the current tile's blend,
 //     BEFORE its ~170 MFMAs, and stay in flight in VGPRs during the MLP (2 waves / SIMD, ~220 VGPRs); the tile after
@@ -84,6 +89,7 @@ struct SaveDev {
 // ds_read_b128 fetches the A fragments of 4 consecutive k-steps.
 // Prod::Bf16Split: the four per-tile matrices are stored as 3-way bf16 splits (6 bytes per weight instead of 4, see
 // mfma_layer_split); Prod::F16Pairs: as fp16 pairs (hi image | lo image, 4 bytes per weight, see mfma_layer_pairs).
+constexpr int kBlockGeo = 4 * 64;  // floats of one wave's block geometry: x | y | z | std of 64 samples
 template <int H, Prod PROD = Prod::F32>
 struct Lds {
   static constexpr int NB = H / 16;        // 16-neuron blocks of a hidden layer
@@ -104,11 +110,13 @@ struct Lds {
   static constexpr int RB = SCAL + NRHIP_MAX_LEVELS;  // per wave: this ray's bias of feat L0 (fb0 + SH part), 4 x H
   static constexpr int LAY = RB + 4 * H;   // Src::EvalTable: per-level {mulY, mulZ, mask, row0} (uint32), 16-byte aligned
   static constexpr int FLG = LAY + 4 * NRHIP_MAX_LEVELS;  // Prod::F16Pairs: a weight does not fit the fp16 pair (int, 0 / 1)
-  static constexpr int TOTAL = FLG + 4;
+  static constexpr int GEO = FLG + 4;      // per wave: contracted position / std of the 64 samples of a block, [4][64]
+  static constexpr int TOTAL = GEO + 4 * kBlockGeo;
   // Src::Actors / Src::Overrides instantiations only:
   static constexpr int SHF = TOTAL;             // feat L0 SH part in fragment order: NB blocks x 4 steps
   static constexpr int ASCAL = SHF + 16 * H;    // actor grid: per-level scalings
-  static constexpr int TOTAL_ACT = ASCAL + NRHIP_MAX_LEVELS;
+  static constexpr int AGEO = ASCAL + NRHIP_MAX_LEVELS;  // Src::Actors, per wave: the block's gaussians before the contraction
+  static constexpr int TOTAL_ACT = AGEO + 4 * kBlockGeo;
 };
 
 // Fused-kernel view of the dynamic actors.  The arrays that are read at wave-uniform addresses are separate
@@ -505,7 +513,8 @@ template <int LPL, int F>
 struct TileFetch {
   float fv[LPL][8][F];  // corner entries, in flight until the blend
   float x, y, z, std;   // contracted sample position / std: the trilinear offsets and the H4 weights are re-derived from
-                        // them at blend time (3 VALU per level and axis) instead of holding 4*LPL more registers
+                        // them at blend time (3 VALU per level and axis) instead of holding 4*LPL more registers.
+                        // ACT kernels only (a sample inside a box has its own frame); the others read Lds::GEO again
   float t0, t1;
 };
 // An ACT tile carries, next to its fetch, one register: the slot (in the ray's candidate list) of the actor whose box
@@ -521,6 +530,8 @@ struct RayRange {
 
 // The tile that will be issued NEXT iteration: its sample interval (vector loads, per lane) and ray constants (scalar
 // loads) are requested one iteration ahead, so issuing its gathers never waits on a memory round trip.
+// The interval is that of the tile's BLOCK (four consecutive tiles = 64 samples of the ray): lane l holds sample
+// 64 (t / 4) + l, one coalesced load when the wave enters the block (t % 4 == 0); the block's other tiles keep it.
 struct PendingTile {
   int64_t pos;  // position in the processing order
   int64_t ray;  // ray index = order[pos] (or pos)
@@ -531,7 +542,39 @@ struct PendingTile {
   int ncand;  // ACT: number of candidate actors of the ray (wave-uniform)
 };
 
-__device__ __forceinline__ void load_pending(PendingTile& p, int64_t pos, int t, const RayRange& rr, int j,
+// Everything that depends on the sample alone, computed ONCE per sample: lane l of the wave holds sample 64 b + l of the
+// block the pending tile lies in (the four lanes of a tile's sample would each repeat the same divisions and cube roots,
+// tile after tile, with a quarter of the lanes doing distinct work).  Written when the block's first tile is issued; tile
+// k of the block takes its values from lane 16 k + j: position and std through the wave's own LDS rows (Lds::GEO; no
+// register is held across the MLPs for them, and a wave's LDS accesses execute in order: no barrier), the interval by a
+// cross-lane move out of the pending tile's registers.  A wave issues the tiles of a ray in order and always enters a ray
+// at tile 0 (early termination skips to the next ray's tile 0), so one block is live at a time.
+// Same instruction sequence on the same inputs as the per-tile form: the values are bit-identical.
+__device__ __forceinline__ float from_lane(float v, int byte_addr) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(byte_addr, __builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ void put_block(float* geo, int lane, const SamplePos& p) {
+  geo[lane] = p.x, geo[64 + lane] = p.y, geo[128 + lane] = p.z, geo[192 + lane] = p.std;
+}
+__device__ __forceinline__ SamplePos get_block(const float* geo, int src) {
+  SamplePos p;
+  p.x = geo[src], p.y = geo[64 + src], p.z = geo[128 + src], p.std = geo[192 + src];
+  return p;
+}
+
+// ACT: ageo takes the gaussian before the contraction as well (box tests, actor-frame contraction)
+template <bool ACT>
+__device__ __forceinline__ void fill_block(float* geo, float* ageo, int lane, const PendingTile& pt, float scale) {
+  if constexpr (ACT) {
+    const SamplePos gs = sample_gaussian(pt.ox, pt.oy, pt.oz, pt.dx, pt.dy, pt.dz, pt.area, pt.t0, pt.t1);
+    put_block(ageo, lane, gs);
+    put_block(geo, lane, contract_gaussian(gs.x, gs.y, gs.z, gs.std, scale));
+  } else {
+    put_block(geo, lane, sample_position(pt.ox, pt.oy, pt.oz, pt.dx, pt.dy, pt.dz, pt.area, pt.t0, pt.t1, scale));
+  }
+}
+
+__device__ __forceinline__ void load_pending(PendingTile& p, int64_t pos, int t, const RayRange& rr, int lane,
                                              const int32_t* __restrict__ order, const float* __restrict__ ro,
                                              const float* __restrict__ rd, const float* __restrict__ rarea,
                                              const float* __restrict__ rstarts, const float* __restrict__ rends,
@@ -543,10 +586,12 @@ __device__ __forceinline__ void load_pending(PendingTile& p, int64_t pos, int t,
   const int64_t pc = p.valid ? pos : rr.end - 1;
   const int64_t ray = order ? (int64_t)order[pc] : pc;
   p.ray = ray;
-  const int s = p.valid ? 16 * t + j : j;
+  const int s = p.valid ? 64 * (t >> 2) + lane : lane;  // the tile's block, one sample per lane
   const int64_t si = ray * rr.stride + (s < rr.S ? s : rr.S - 1);
-  p.t0 = rstarts[si];
-  p.t1 = rends[si];
+  if ((t & 3) == 0) {  // wave-uniform: entering a block (a tile inside one keeps the block's interval)
+    p.t0 = rstarts[si];
+    p.t1 = rends[si];
+  }
   p.ox = ro[3 * ray], p.oy = ro[3 * ray + 1], p.oz = ro[3 * ray + 2];
   p.dx = rd[3 * ray], p.dy = rd[3 * ray + 1], p.dz = rd[3 * ray + 2];
   p.area = rarea[ray];
@@ -557,7 +602,7 @@ __device__ __forceinline__ void load_pending(PendingTile& p, int64_t pos, int t,
 // M = rr.S >= 1.  This pipeline clamps for itself -- the index of every load stays inside [0, M): a lane past the ray's end reads
 // the ray's last sample; an empty segment gives b - 1 <= M - 1, which is -1 only for b == 0, where sample 0 stands in.
 // The last clamp holds the reads inside the arrays even for segments that break their precondition.
-__device__ __forceinline__ void load_pending_packed(PendingTile& p, int64_t pos, int t, const RayRange& rr, int j,
+__device__ __forceinline__ void load_pending_packed(PendingTile& p, int64_t pos, int t, const RayRange& rr, int lane,
                                                     const int32_t* __restrict__ order, const float* __restrict__ ro,
                                                     const float* __restrict__ rd, const float* __restrict__ rarea,
                                                     const float* __restrict__ rstarts, const float* __restrict__ rends,
@@ -569,12 +614,14 @@ __device__ __forceinline__ void load_pending_packed(PendingTile& p, int64_t pos,
   p.ray = ray;
   const int b = (int)segs[ray], n = (int)segs[ray + 1] - b;  // (M < 2^31)
   first = b, count = n;
-  const int s = p.valid ? 16 * t + j : j;
+  const int s = p.valid ? 64 * (t >> 2) + lane : lane;  // the tile's block, one sample per lane
   int si = b + (s < n ? s : n - 1);
   si = si < 0 ? 0 : si;
   si = si < rr.S ? si : rr.S - 1;
-  p.t0 = rstarts[si];
-  p.t1 = rends[si];
+  if ((t & 3) == 0) {  // wave-uniform: entering a block (a tile inside one keeps the block's interval)
+    p.t0 = rstarts[si];
+    p.t1 = rends[si];
+  }
   p.ox = ro[3 * ray], p.oy = ro[3 * ray + 1], p.oz = ro[3 * ray + 2];
   p.dx = rd[3 * ray], p.dy = rd[3 * ray + 1], p.dz = rd[3 * ray + 2];
   p.area = rarea[ray];
@@ -604,12 +651,13 @@ __device__ __forceinline__ void layout_corners(float x, float y, float z, float 
 template <int L, int F, bool HALF, bool RELAY = false>
 __device__ __forceinline__ void issue_tile(const FieldDev& fd, const PendingTile& pt, int g, uint32_t mask,
                                            const float* scal_lds, TileFetch<EncFrame<L, F>::LPL, F>& tf,
-                                           const uint32_t* lay_lds = nullptr) {
+                                           float* geo, int lane, const uint32_t* lay_lds = nullptr) {
   constexpr int LPL = EncFrame<L, F>::LPL;
-  tf.t0 = pt.t0;
-  tf.t1 = pt.t1;
-  const SamplePos p = sample_position(pt.ox, pt.oy, pt.oz, pt.dx, pt.dy, pt.dz, pt.area, pt.t0, pt.t1, fd.scale);
-  tf.x = p.x, tf.y = p.y, tf.z = p.z, tf.std = p.std;
+  if ((pt.t & 3) == 0) fill_block<false>(geo, nullptr, lane, pt, fd.scale);  // wave-uniform: the block's first tile
+  const int src = 16 * (pt.t & 3) + (lane & 15);  // lane 16 k + j holds this lane's sample
+  const SamplePos p = get_block(geo, src);
+  tf.t0 = from_lane(pt.t0, src << 2);
+  tf.t1 = from_lane(pt.t1, src << 2);  // (tf.x .. tf.std stay unset: the blend reads the block's rows again)
   if (!EncFrame<L, F>::busy(g)) return;  // a lane group without levels (L < 4) loads nothing
 #pragma unroll
   for (int q = 0; q < LPL; ++q) {
@@ -641,15 +689,22 @@ __device__ __forceinline__ void issue_tile_actors(const FieldDev& fd, const Acto
                                                   const int32_t* __restrict__ cand_actor,
                                                   const float* __restrict__ cand_w2b, const float* __restrict__ bounds,
                                                   const void* const* __restrict__ tables,
-                                                  TileFetch<EncFrame<L, F>::LPL, F>& tf, int& slot_out) {
+                                                  TileFetch<EncFrame<L, F>::LPL, F>& tf, int& slot_out,
+                                                  float* geo, float* ageo, int lane) {
   constexpr int LPL = EncFrame<L, F>::LPL;
   const bool busy = EncFrame<L, F>::busy(g);  // lanes of a group without levels load nothing
   const int n = __builtin_amdgcn_readfirstlane(pt.ncand);
   // 32-bit row index, made scalar explicitly: a 64-bit multiply has no scalar form
   const uint32_t row = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)pt.ray * (uint32_t)ad.K));
+  // the block's geometry (all lanes active here: the cross-lane moves of the interval read every lane of the wave)
+  if ((pt.t & 3) == 0) fill_block<true>(geo, ageo, lane, pt, fd.scale);
+  const int src = 16 * (pt.t & 3) + (lane & 15);
+  // this lane's sample: the gaussian, and its contraction in the static scene
+  const SamplePos gs = get_block(ageo, src), ps = get_block(geo, src);
+  tf.t0 = from_lane(pt.t0, src << 2);
+  tf.t1 = from_lane(pt.t1, src << 2);
   int slot = -1;
   if (n > 0) {
-    const SamplePos gs = sample_gaussian(pt.ox, pt.oy, pt.oz, pt.dx, pt.dy, pt.dz, pt.area, pt.t0, pt.t1);
     for (int c = 0; c < n; ++c) {
       const float* w = cand_w2b + (row + (uint32_t)c) * 12u;
       const int act = cand_actor[row + (uint32_t)c];
@@ -660,10 +715,7 @@ __device__ __forceinline__ void issue_tile_actors(const FieldDev& fd, const Acto
     }
   }
   slot_out = slot;
-  tf.t0 = pt.t0;
-  tf.t1 = pt.t1;
   unsigned long long todo = __ballot(slot >= 0);
-  const SamplePos gs = sample_gaussian(pt.ox, pt.oy, pt.oz, pt.dx, pt.dy, pt.dz, pt.area, pt.t0, pt.t1);
   const uint32_t amask = (1u << ad.log2T) - 1u;
   while (todo) {  // rare: the lanes inside a box, one pass per distinct winner
     const int c = __builtin_amdgcn_readlane(slot, (int)__builtin_ctzll(todo));
@@ -695,7 +747,7 @@ __device__ __forceinline__ void issue_tile_actors(const FieldDev& fd, const Acto
   // bookkeeping the compiler attaches to the rare passes above (waits, copies) sits in front of these gathers, where
   // nothing is in flight, and not between them and the MLPs.
   if (slot < 0) {
-    const SamplePos p = contract_gaussian(gs.x, gs.y, gs.z, gs.std, fd.scale);
+    const SamplePos p = ps;
     tf.x = p.x, tf.y = p.y, tf.z = p.z, tf.std = p.std;
     if (busy) {
 #pragma unroll
@@ -758,19 +810,19 @@ __device__ __forceinline__ void blend_tile_actors(const TileFetch<EncFrame<L, F>
 }
 
 template <int L, int F>
-__device__ __forceinline__ void blend_tile(const TileFetch<EncFrame<L, F>::LPL, F>& tf, int g, const float* scal_lds,
-                                           float (&feat)[8]) {
+__device__ __forceinline__ void blend_tile(const TileFetch<EncFrame<L, F>::LPL, F>& tf, const SamplePos& p, int g,
+                                           const float* scal_lds, float (&feat)[8]) {
   using EF = EncFrame<L, F>;
   constexpr int LPL = EF::LPL;
 #pragma unroll
   for (int q = 0; q < LPL; ++q) {
     const float sc = scal_lds[q];
     Corners c;  // offsets rounded exactly as hash_corners does (encodings.py:431-446)
-    const float sx = __fmul_rn(tf.x, sc), sy = __fmul_rn(tf.y, sc), sz = __fmul_rn(tf.z, sc);
+    const float sx = __fmul_rn(p.x, sc), sy = __fmul_rn(p.y, sc), sz = __fmul_rn(p.z, sc);
     c.ox = __fsub_rn(sx, floorf(sx)), c.oy = __fsub_rn(sy, floorf(sy)), c.oz = __fsub_rn(sz, floorf(sz));
     float v[F];
     lerp_corners<F>(c, tf.fv[q], v);
-    const float rw = rescale_weight(sc, tf.std);
+    const float rw = rescale_weight(sc, p.std);
 #pragma unroll
     for (int f = 0; f < F; ++f) feat[q * F + f] = EF::busy(g) ? v[f] * rw : 0.f;  // (idle groups fetched nothing)
   }
@@ -868,22 +920,25 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
   int ta = -1;  // ACT: candidate slot of the actor containing this lane's sample of the tile in `tf` (-1: none)
   const float* ascal_l = lds + Ld::ASCAL;
   PendingTile q;
+  // geometry of the block q's tile lies in, this wave's rows (written at the block's first tile: fill_block)
+  float* geo_w = lds + Ld::GEO + wid * kBlockGeo;
+  float* ageo_w = lds + (ACT ? Ld::AGEO : Ld::GEO) + wid * kBlockGeo;  // (only ACT kernels carve and touch AGEO)
   int qb = 0, qn = 0;  // PACKED: first sample and sample count of q's ray (wave-uniform)
   auto tiles_of = [](int n) { return n > 16 ? (n + 15) >> 4 : 1; };  // PACKED: a ray without samples walks one dead tile
-  if constexpr (PACKED) load_pending_packed(q, pos, 0, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
-  else load_pending(q, pos, 0, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
+  if constexpr (PACKED) load_pending_packed(q, pos, 0, rr, lane, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
+  else load_pending(q, pos, 0, rr, lane, order, ro, rd, rarea, rstarts, rends, cand_count);
   int64_t ray = q.ray;
   int cb = 0, cn = 0;  // PACKED: first sample and sample count of the ray in `tf`
   if constexpr (PACKED) cb = qb, cn = qn;
-  if constexpr (ACT) issue_tile_actors<L, F, HALF>(fd, ad, q, g, mask, scal_l, ascal_l, cand_actor, cand_w2b, bounds, tables, tf, ta);
-  else issue_tile<L, F, HALF, RELAY>(fd, q, g, mask, scal_l, tf, lay_l);
+  if constexpr (ACT) issue_tile_actors<L, F, HALF>(fd, ad, q, g, mask, scal_l, ascal_l, cand_actor, cand_w2b, bounds, tables, tf, ta, geo_w, ageo_w, lane);
+  else issue_tile<L, F, HALF, RELAY>(fd, q, g, mask, scal_l, tf, geo_w, lane, lay_l);
   // override row of this lane's sample of `tf` (PACKED: at the packed sample index; q's segment is still qb / qn here)
   if constexpr (OVR && PACKED) ta = (q.valid && j < qn && qb + j >= 0 && qb + j < S) ? ovr_row[qb + j] : -1;
   else if constexpr (OVR) ta = (q.valid && j < S) ? ovr_row[q.ray * S + j] : -1;
   {
     const bool wrap = (PACKED ? tiles_of(cn) : ntile) == 1;
-    if constexpr (PACKED) load_pending_packed(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
-    else load_pending(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
+    if constexpr (PACKED) load_pending_packed(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, lane, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
+    else load_pending(q, wrap ? pos + pos_step : pos, wrap ? 0 : 1, rr, lane, order, ro, rd, rarea, rstarts, rends, cand_count);
   }
 
   // per-ray state
@@ -946,7 +1001,9 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
         actor_tile_sh(ta, (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)ray * (uint32_t)ad.K)), g, rd[3 * ray],
                       rd[3 * ray + 1], rd[3 * ray + 2], cand_w2b, shb);
     } else {
-      blend_tile<L, F>(tf, g, scal_l, feat);
+      // position / std of this tile's samples: still in the block's LDS rows (the issue step below is what overwrites
+      // them, when the NEXT tile opens a block), so no register carries them across the MLPs
+      blend_tile<L, F>(tf, get_block(geo_w, 16 * (t & 3) + j), g, scal_l, feat);
       if constexpr (PAIRS) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) feat[k] *= kPairAct;
@@ -993,8 +1050,8 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     // ---- issue the next tile's gathers: they fly while this tile runs through the MLPs ---------------
     if (ray_done && q.valid && q.pos == pos) {  // terminated early: q still points into this ray -> skip to the next ray
       // (one exposed round trip)
-      if constexpr (PACKED) load_pending_packed(q, pos + pos_step, 0, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
-      else load_pending(q, pos + pos_step, 0, rr, j, order, ro, rd, rarea, rstarts, rends, cand_count);
+      if constexpr (PACKED) load_pending_packed(q, pos + pos_step, 0, rr, lane, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
+      else load_pending(q, pos + pos_step, 0, rr, lane, order, ro, rd, rarea, rstarts, rends, cand_count);
     }
     const bool have_next = q.valid;
     const int64_t npos = q.pos, nray = q.ray;
@@ -1002,8 +1059,8 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     int nb = 0, nn = 0;
     if constexpr (PACKED) nb = qb, nn = qn;
     // unconditional (see load_pending)
-    if constexpr (ACT) issue_tile_actors<L, F, HALF>(fd, ad, q, g, mask, scal_l, ascal_l, cand_actor, cand_w2b, bounds, tables, tf, ta);
-    else issue_tile<L, F, HALF, RELAY>(fd, q, g, mask, scal_l, tf, lay_l);
+    if constexpr (ACT) issue_tile_actors<L, F, HALF>(fd, ad, q, g, mask, scal_l, ascal_l, cand_actor, cand_w2b, bounds, tables, tf, ta, geo_w, ageo_w, lane);
+    else issue_tile<L, F, HALF, RELAY>(fd, q, g, mask, scal_l, tf, geo_w, lane, lay_l);
     if constexpr (OVR && PACKED) {
       const int s2 = 16 * q.t + j;
       ta = (q.valid && s2 < qn && qb + s2 >= 0 && qb + s2 < S) ? ovr_row[qb + s2] : -1;
@@ -1013,9 +1070,9 @@ __global__ __launch_bounds__(256, 2) void render_kernel(
     {
       const bool wrap = nt + 1 == (PACKED ? tiles_of(nn) : ntile);  // request the small loads of the tile after it
       if constexpr (PACKED)
-        load_pending_packed(q, wrap ? npos + pos_step : npos, wrap ? 0 : nt + 1, rr, j, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
+        load_pending_packed(q, wrap ? npos + pos_step : npos, wrap ? 0 : nt + 1, rr, lane, order, ro, rd, rarea, rstarts, rends, segs, qb, qn, pcand);
       else
-        load_pending(q, wrap ? npos + pos_step : npos, wrap ? 0 : nt + 1, rr, j, order, ro, rd, rarea, rstarts, rends,
+        load_pending(q, wrap ? npos + pos_step : npos, wrap ? 0 : nt + 1, rr, lane, order, ro, rd, rarea, rstarts, rends,
                      cand_count);
     }
     __builtin_amdgcn_sched_barrier(0);
