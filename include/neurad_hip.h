@@ -983,6 +983,31 @@ int nrhip_chamfer_distance(const float* source, int32_t stride_s, const uint8_t*
                            int32_t normalize_with_target, int32_t plan, float* result, float* source_sq_dist,
                            float* target_sq_dist, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- camera image evaluation (csrc/image_eval.hip): PSNR and SSIM of NeuRADModel.get_image_metrics_and_images
+ *      (models/neurad.py:265-266,585-586: torchmetrics' PeakSignalNoiseRatio(data_range=1.0) and
+ *      structural_similarity_index_measure(preds, target) with its defaults) -----------------------------------------------
+ * a, b: fp32 [h, w, c] channel-last, contiguous, h, w >= 11, c in {1, 3}.  out [2] (device) = psnr, ssim.
+ * psnr = 10 log10(psnr_range^2 / mean((a - b)^2)): the fp32 difference, squared and summed in float64 in a fixed order, the
+ * logarithm in float64, rounded to fp32 once; +inf for identical images.
+ * ssim = the mean over every 11 x 11 window that lies inside the image ((h - 10)(w - 10) per channel) of
+ *   s = (2 mu_a mu_b + c1)(2 s_ab + c2) / ((mu_a^2 + mu_b^2 + c1)(s_a^2 + s_b^2 + c2)),
+ * the moments under the separable Gaussian window (11 taps, sigma 1.5, normalised), c1 = (0.01 R)^2, c2 = (0.03 R)^2 with
+ * R = max(max a - min a, max b - min b) over both whole images (taken on the device: no host read).  torchmetrics' reflect
+ * pad followed by its crop leaves exactly these windows.  The moments are accumulated on values shifted by a per-tile pivot
+ * (tiles of NRHIP_SSIM_TILE windows per edge), so s_a^2 = sum g a'^2 - (sum g a')^2 cancels at the size of the local
+ * contrast; s is summed in float64 in a fixed order and the mean is rounded once.  ssim_map: [h - 10, w - 10, c] receives s
+ * per window, or NULL.  A NaN anywhere makes both results NaN.  Two constant images (R = 0) give ssim = NaN (0 / 0, as in
+ * the reference).  Same inputs, same bits; no atomics, no host read, no allocation.  workspace: device scratch of
+ * nrhip_image_metrics_workspace bytes (host logic), 16-byte aligned.                                                        */
+#define NRHIP_SSIM_TILE 32
+#define NRHIP_IMAGE_STAT_ITEMS 4096 /* elements per workgroup (and per float64 partial) of the squared-error pass */
+int nrhip_image_metrics_workspace(int32_t h, int32_t w, int32_t c, int64_t* bytes /*host*/);
+int nrhip_image_metrics(const float* a, const float* b, int32_t h, int32_t w, int32_t c, float psnr_range, float* ssim_map,
+                        void* workspace, int64_t workspace_bytes, float* out, void* stream);
+/* PSNR alone over n >= 1 flat elements (the training step's metric): out [1] (device).  workspace: device scratch of
+ * 8 * ceil(n / NRHIP_IMAGE_STAT_ITEMS) bytes, 8-byte aligned.                                                           */
+int nrhip_image_psnr(const float* a, const float* b, int64_t n, float psnr_range, void* workspace, float* out, void* stream);
+
 /* ---- the training step's glue as kernels (csrc/train_fused.hip) ---------------------------------------------------
  * What the reference spreads over dozens of elementwise torch ops per step between the field / sampler kernels.
  * `edges` is a bin-edge tensor e[R, >= S+1] with row stride edge_stride (floats): sample s of a ray spans

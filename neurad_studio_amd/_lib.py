@@ -125,6 +125,8 @@ GRAD_ROWS_PER_BLOCK = 256   # NRHIP_GRAD_ROWS_PER_BLOCK
 NEAREST_TILE = 1024         # NRHIP_NEAREST_TILE
 VGG_IMAGE_CHANNELS = 16     # NRHIP_VGG_IMAGE_CHANNELS
 L1_ITEMS = 2048             # NRHIP_L1_ITEMS
+SSIM_TILE = 32              # NRHIP_SSIM_TILE
+IMAGE_STAT_ITEMS = 4096     # NRHIP_IMAGE_STAT_ITEMS
 P, I32, I64, F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> argtypes : exactly the prototypes of include/neurad_hip.h (tests/test_abi.py cross-checks this
@@ -288,6 +290,9 @@ PROTOTYPES = {
     "nrhip_nearest_plan": [I64, I64, C.POINTER(I32), C.POINTER(I32)],
     "nrhip_chamfer_workspace": [I64, I64, C.POINTER(I64)],
     "nrhip_chamfer_distance": [P, I32, P, I64, P, I32, P, I64, I32, I32, P, P, P, P, I64, P],
+    "nrhip_image_metrics_workspace": [I32, I32, I32, C.POINTER(I64)],
+    "nrhip_image_metrics": [P, P, I32, I32, I32, F32, P, P, I64, P, P],
+    "nrhip_image_psnr": [P, P, I64, F32, P, P, P],
     "nrhip_conv3x3_pack_bytes": [I32, I32, I32, C.POINTER(I64)],
     "nrhip_conv3x3_pack": [P, I32, I32, I32, P, P],
     "nrhip_conv3x3_plan": [I64, I32, I32, I32, C.POINTER(I32), C.POINTER(I32), C.POINTER(I64)],

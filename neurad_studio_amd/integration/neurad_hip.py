@@ -41,6 +41,7 @@ from ..fields.neurad_field import NeuRADProposalField as HipNeuRADProposalField
 from ..model_components import losses as hip_losses
 from ..model_components import ray_samplers as hip_samplers
 from ..model_components import renderers as hip_renderers
+from ..model_components.image_metrics import PSNR, ImageEvalPair
 from ..model_components.lidar_metrics import lidar_eval_metrics, masked_return_metrics, scalars_to_host
 from ..models.neurad import FusedEvalMixin, FusedTrainMixin
 from ..optim import HashGridAdam
@@ -118,6 +119,12 @@ class NeuRADHipModelConfig(NeuRADModelConfig):
     cameras/raygen.py:lidar_rays, the lidar branch of get_image_metrics_and_images (models/neurad.py:589-620) runs as masked
     reductions plus the chamfer kernel (csrc/lidar_eval.hip) and reads its five scalars with one device->host transfer.
     False: the reference's own methods (torch ray generation, ~8 boolean-mask gathers, chunked torch.cdist)."""
+    fused_image_eval: bool = False
+    """Camera image metrics on the device (csrc/image_eval.hip, model_components/image_metrics.py): the image branch of
+    get_image_metrics_and_images (models/neurad.py:568-587) takes ``psnr`` and ``ssim`` from one launch sequence and reads both
+    with one device->host transfer (``lpips`` and the images stay the reference's), and the training step's ``psnr``
+    (models/neurad.py:465) is ``ops.image_psnr``: a device tensor, no torchmetrics module state.  False: the reference's
+    torchmetrics objects (a ``float()`` per metric; SSIM as a grouped conv2d with fp32 E[x^2] - mu^2 variances)."""
     table_dtype: Literal["float32", "float16"] = "float32"
     """Storage of the main field's hash tables (static grid + actor grids).  "float16" (BASELINE config[4]; what tiny-cuda-nn
     stores): half the gather bytes; gradients arrive in fp16 and HashGridAdam keeps fp32 master copies (optim.py).  State
@@ -154,6 +161,23 @@ def _patched(module, name, value):
         yield
     finally:
         setattr(module, name, old)
+
+
+@contextlib.contextmanager
+def _shadowed(obj, **values):
+    """instance attributes for the duration of a call, whatever they shadow: a plain attribute, a class attribute or a
+    registered submodule (``obj._modules`` and the state dict stay as they are: the instance dict is looked up first)"""
+    d, missing = obj.__dict__, object()
+    old = {k: d.get(k, missing) for k in values}
+    d.update(values)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is missing:
+                d.pop(k, None)
+            else:
+                d[k] = v
 
 
 class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
@@ -251,6 +275,9 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
             return self._fused_metrics_dict(outputs, batch)
         # the reference calls the module-level distortion_loss (models/neurad.py:524): the HIP one for this call only
         with _patched(_ref_neurad, "distortion_loss", hip_losses.distortion_loss):
+            if self.config.fused_image_eval and "image" in batch:
+                with _shadowed(self, psnr=PSNR(1.0)):  # (models/neurad.py:265: data_range=1.0)
+                    return super().get_metrics_dict(outputs, batch)
             return super().get_metrics_dict(outputs, batch)
 
     def _fused_metrics_dict(self, outputs, batch):
@@ -262,7 +289,10 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
         from ..model_components.lidar_losses import LidarLossSettings, lidar_metrics, lidar_rows
 
         loss = self.config.loss
-        m = {"psnr": self.psnr(outputs["rgb"].detach(), batch["image"])}
+        if self.config.fused_image_eval:  # a 0-dim device tensor from csrc/image_eval.hip: no metric object, no host read
+            m = {"psnr": PSNR(1.0)(outputs["rgb"].detach(), batch["image"])}
+        else:
+            m = {"psnr": self.psnr(outputs["rgb"].detach(), batch["image"])}
         is_lidar = batch["is_lidar"][:, 0]
         n_lidar = batch["lidar"].shape[0]
         rows = lidar_rows(is_lidar, n_lidar)
@@ -322,6 +352,17 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
         return outputs, batch
 
     def get_image_metrics_and_images(self, outputs, batch):
+        """With ``fused_image_eval`` the image branch (models/neurad.py:568-587) runs the reference's own code with
+        ``self.psnr`` / ``self.ssim`` answered, for this call, by model_components/image_metrics.py:ImageEvalPair: the first of
+        the two launches the image kernels and reads both scalars with one transfer (``_scalars_to_host``), the second is
+        served from it.  Same keys, every value a Python float; ``images_dict`` and ``lpips`` are the reference's."""
+        if not (self.config.fused_image_eval and "image" in batch):
+            return self._image_and_lidar_metrics(outputs, batch)
+        pair = ImageEvalPair(to_host=lambda values: self._scalars_to_host(values))
+        with _shadowed(self, psnr=pair.psnr, ssim=pair.ssim):
+            return self._image_and_lidar_metrics(outputs, batch)
+
+    def _image_and_lidar_metrics(self, outputs, batch):
         """The image branch is the reference's; with ``fused_lidar_eval`` the lidar branch (models/neurad.py:589-620) is
         ``_fused_lidar_eval_metrics``: the same five keys, every value a Python float -- the reference returns a 0-dim tensor
         for ``chamfer_distance`` in its fallback case (nothing predicted to return, or nothing returned), this path a float."""
@@ -344,7 +385,8 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
 
     @staticmethod
     def _scalars_to_host(values):
-        """THE device->host transfer of the lidar eval metrics (one per scan; tests count the calls)"""
+        """THE device->host transfer of the fused eval metrics: one per lidar scan (five scalars), one per camera image (two);
+        tests count the calls"""
         return scalars_to_host(values)
 
 

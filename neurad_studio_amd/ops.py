@@ -2139,6 +2139,59 @@ def chamfer_distance(source: Tensor, target: Tensor, source_valid: Optional[Tens
     return (result, ds, dt) if return_per_point else result
 
 
+# ---- camera image evaluation (csrc/image_eval.hip): PSNR and SSIM, no autograd ------------------------------------------------
+SSIM_TILE = _lib.SSIM_TILE
+SSIM_WINDOW = 11
+IMAGE_STAT_ITEMS = _lib.IMAGE_STAT_ITEMS
+
+
+def _image(t: Tensor, name: str) -> Tensor:
+    """[H,W,C] or [1,C,H,W] (the view the reference's moveaxis makes of an [H,W,C] image costs no copy on the way back)
+    -> contiguous channel-last fp32 [H,W,C] on the device"""
+    if not isinstance(t, Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(t)}")
+    if not t.is_cuda:
+        raise _lib.NeuradHipError(f"{name}: tensor is on {t.device}; the HIP path needs a GPU tensor (no CPU fallback)")
+    if t.dim() == 4:
+        if t.shape[0] != 1:
+            raise ValueError(f"{name}: one image per call, got a batch of {t.shape[0]}")
+        t = t[0].permute(1, 2, 0)
+    if t.dim() != 3 or t.shape[2] not in (1, 3):
+        raise ValueError(f"{name}: expected [H,W,C] or [1,C,H,W] with C in (1, 3), got {tuple(t.shape)}")
+    return t.detach().float().contiguous()
+
+
+def image_metrics(a: Tensor, b: Tensor, psnr_range: float = 1.0, return_map: bool = False):
+    """-> (psnr, ssim[, ssim_map [H-10, W-10, C]]): 0-dim fp32 tensors on the device, no host read.  torchmetrics'
+    PeakSignalNoiseRatio(data_range=psnr_range) and structural_similarity_index_measure with its defaults (11 x 11 Gaussian
+    window, sigma 1.5, data range from the two images) as include/neurad_hip.h states them."""
+    a, b = _image(a, "a"), _image(b, "b")
+    if a.shape != b.shape:
+        raise ValueError(f"image shapes differ: {tuple(a.shape)} and {tuple(b.shape)}")
+    h, w, c = a.shape
+    if h < SSIM_WINDOW or w < SSIM_WINDOW:
+        raise ValueError(f"image {h} x {w} is smaller than the {SSIM_WINDOW} x {SSIM_WINDOW} SSIM window")
+    out = torch.empty((2,), device=a.device, dtype=torch.float32)
+    ssim_map = torch.empty((h - SSIM_WINDOW + 1, w - SSIM_WINDOW + 1, c), device=a.device, dtype=torch.float32) \
+        if return_map else None
+    ws, need = _workspace("nrhip_image_metrics_workspace", h, w, c, device=a.device, dtype=torch.uint8)
+    launch("nrhip_image_metrics", a, b, h, w, c, float(psnr_range), ssim_map, ws, need, out)
+    return (out[0], out[1], ssim_map) if return_map else (out[0], out[1])
+
+
+def image_psnr(a: Tensor, b: Tensor, psnr_range: float = 1.0) -> Tensor:
+    """PSNR over all elements of two equally shaped tensors -> 0-dim fp32 tensor on the device, no host read (the training
+    step's metric, models/neurad.py:465)"""
+    a, b = _chk(a.detach().float().reshape(-1), "a"), _chk(b.detach().float().reshape(-1), "b")
+    if a.shape != b.shape or a.shape[0] == 0:
+        raise ValueError(f"image_psnr: {a.shape[0]} and {b.shape[0]} elements")
+    n = a.shape[0]
+    ws = torch.empty(((n + IMAGE_STAT_ITEMS - 1) // IMAGE_STAT_ITEMS,), device=a.device, dtype=torch.float64)
+    out = torch.empty((1,), device=a.device, dtype=torch.float32)
+    launch("nrhip_image_psnr", a, b, n, float(psnr_range), ws, out)
+    return out[0]
+
+
 # ---- SURVEY §8(e): the level-sparse gradient exchange's device side (csrc/grad_rows.hip; parallel/data_parallel.py) ----------
 def grad_rows_count(grad: Tensor, n_levels: int):
     """grad [n_levels * T, F] fp32 -> (level_counts [n_levels] int64 = non-zero rows per level, block_offsets [n_levels, nblk]
