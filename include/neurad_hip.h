@@ -1008,6 +1008,42 @@ int nrhip_image_metrics(const float* a, const float* b, int32_t h, int32_t w, in
  * 8 * ceil(n / NRHIP_IMAGE_STAT_ITEMS) bytes, 8-byte aligned.                                                           */
 int nrhip_image_psnr(const float* a, const float* b, int64_t n, float psnr_range, void* workspace, float* out, void* stream);
 
+/* ---- camera pose correction (csrc/pose_opt.hip): CameraOptimizer.apply_to_raybundle with mode "SO3xR3"
+ *      (cameras/camera_optimizers.py:139-182, cameras/lie_groups.py:24-58) and its gradient ------------------------------
+ * pose: fp32 [n_cameras, 6] (translation first, then the so(3) tangent vector: the order of the reference's code);
+ * weights: fp32 [6] or NULL (= ones); camera_indices: int64 [r]; origins, directions and the outputs: fp32 [r, 3].
+ * Forward, per ray of camera c, in fp32 in the reference's operation order (no contraction):
+ *   a = fl32(pose[c] * weights), w = a[3:6], nrms = x^2 + y^2 + z^2, theta = sqrt(max(nrms, 1e-4f)), inv = 1 / theta,
+ *   f1 = inv sin(theta), f2 = inv inv (1 - cos(theta)), R = f1 K + f2 K^2 + I with K v = w x v,
+ *   out_origins = origins + a[0:3], out_directions = R directions.
+ * Clamp rule: below nrms = 1e-4f the factors are those of theta = sqrt(1e-4f), constants; at and above it the gradient
+ * passes through them (torch.clamp).  Backward and forward decide on the same fp32 nrms.
+ * Backward: the twelve terms of a ray are grad_origins[0..2] and grad_directions[i] directions[j]; R enters linearly, so
+ * their per-camera sums determine grad_pose exactly.  Each term is formed in double (exact), scaled by 2^(B - e_c), rounded
+ * to the nearest int64 and added with a 64-bit integer atomic: 2^(e_c) is the smallest power of two above the camera's largest
+ * finite |term| (a per-camera integer max first), B = 62 - ceil(log2 max(r, 2)), so |q| <= 2^B and r of them cannot overflow.
+ * One lane per camera then evaluates the chain through the exponential map in double from the fp32 parameters, multiplies by
+ * weights and rounds to fp32 once into the dense grad_pose [n_cameras, 6].  Bound, per camera c (n_c rays, largest |term|
+ * m_c) and component k against exact arithmetic: |g - g_exact| <= 2^-22 |g_exact| + 16 n_c 2^-B m_c |weights_k|.
+ * Properties: no float atomics, no host read, no allocation, capturable in a graph; the same inputs give the same bits, ANY
+ * permutation of the rays gives the same bits, and gradients scaled by a power of two give the result scaled by it exactly
+ * (short of fp32 under- / overflow of the result).  Cameras without a ray get exact zeros.
+ * NaN rule: a ray with a non-finite gradient or direction (or a |term| above FLT_MAX) takes no part in the sums and sets its
+ * camera's flag; that camera's row of grad_pose is NaN in all six components, every other row is unaffected.
+ * Precondition: 0 <= camera_indices < n_cameras.  A ray that violates it is neither read from pose nor written to the
+ * workspace: it comes out of the forward unchanged, contributes nothing to grad_pose, and its input gradients are the output
+ * gradients.  workspace: device scratch of nrhip_pose_apply_bwd_workspace bytes (host logic; n_cameras rows of 16 64-bit
+ * words: 12 sums, the max cell, the flag, 2 spare), 8-byte aligned; the first pass clears it.  grad_in_origins (= grad_origins)
+ * and grad_in_directions (= R^T grad_directions): fp32 [r, 3] or NULL; with both NULL that kernel is skipped.
+ * r = 0 or n_cameras = 0: success, nothing is launched and nothing written.                                             */
+int nrhip_pose_apply(const float* pose, const float* weights, int32_t n_cameras, const int64_t* camera_indices,
+                     const float* origins, const float* directions, int64_t r, float* out_origins, float* out_directions,
+                     void* stream);
+int nrhip_pose_apply_bwd_workspace(int64_t r, int32_t n_cameras, int64_t* bytes /*host*/);
+int nrhip_pose_apply_bwd(const float* pose, const float* weights, int32_t n_cameras, const int64_t* camera_indices,
+                         const float* directions, const float* grad_origins, const float* grad_directions, int64_t r,
+                         void* workspace, float* grad_pose, float* grad_in_origins, float* grad_in_directions, void* stream);
+
 /* ---- the training step's glue as kernels (csrc/train_fused.hip) ---------------------------------------------------
  * What the reference spreads over dozens of elementwise torch ops per step between the field / sampler kernels.
  * `edges` is a bin-edge tensor e[R, >= S+1] with row stride edge_stride (floats): sample s of a ray spans

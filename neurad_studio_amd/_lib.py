@@ -293,6 +293,9 @@ PROTOTYPES = {
     "nrhip_image_metrics_workspace": [I32, I32, I32, C.POINTER(I64)],
     "nrhip_image_metrics": [P, P, I32, I32, I32, F32, P, P, I64, P, P],
     "nrhip_image_psnr": [P, P, I64, F32, P, P, P],
+    "nrhip_pose_apply": [P, P, I32, P, P, P, I64, P, P, P],
+    "nrhip_pose_apply_bwd_workspace": [I64, I32, C.POINTER(I64)],
+    "nrhip_pose_apply_bwd": [P, P, I32, P, P, P, P, I64, P, P, P, P, P],
     "nrhip_conv3x3_pack_bytes": [I32, I32, I32, C.POINTER(I64)],
     "nrhip_conv3x3_pack": [P, I32, I32, I32, P, P],
     "nrhip_conv3x3_plan": [I64, I32, I32, I32, C.POINTER(I32), C.POINTER(I32), C.POINTER(I64)],

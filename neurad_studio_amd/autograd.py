@@ -906,3 +906,24 @@ class WeightedSumFn(torch.autograd.Function):
         gs = (mults * g).unbind(0)
         return (None, *gs)
 
+
+class PoseApplyFn(torch.autograd.Function):
+    """CameraOptimizer.apply_to_raybundle for mode "SO3xR3" (cameras/camera_optimizers.py:173-182): -> (origins + t,
+    R directions), fp32 whatever autocast says.  Saves the parameter, the indices and the input directions, no copies.  The
+    backward returns the DENSE parameter gradient (what torch's index backward gives; order-free integer sums,
+    csrc/pose_opt.hip) and the ray gradients only when the incoming rays require them.  Under ``torch.no_grad()`` only the
+    forward kernel runs."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, pose, weights, camera_indices, origins, directions):
+        ctx.save_for_backward(pose, weights, camera_indices, directions)
+        return ops.pose_apply(pose, weights, camera_indices, origins, directions)
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, g_o, g_d):
+        pose, weights, idx, d = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gp, gi_o, gi_d = ops.pose_apply_bwd(pose, weights, idx, d, g_o.contiguous(), g_d.contiguous(), need[3], need[4])
+        return (gp if need[0] else None), None, None, gi_o, gi_d

@@ -124,6 +124,7 @@ extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
 //      additive, same number: the VGG perceptual loss -- nrhip_conv3x3 (+ _pack, _pack_bytes, _plan), nrhip_maxpool2_fwd /
 //      _bwd, nrhip_l1_feature_fwd / _bwd (+ _workspace), nrhip_vgg_stage_images, nrhip_vgg_image_grad
 //      additive, same number: camera image evaluation -- nrhip_image_metrics (+ _workspace), nrhip_image_psnr
+//      additive, same number: camera pose correction -- nrhip_pose_apply, nrhip_pose_apply_bwd (+ _workspace)
 extern "C" int nrhip_version(void) { return 520; }
 
 extern "C" int nrhip_tuning_reload(void) {

@@ -442,6 +442,10 @@ __device__ __forceinline__ double dpp(double old, double v) {
   const uint32_t hi = (uint32_t)dpp<CTRL>((int)(uint32_t)(o >> 32), (int)(uint32_t)(x >> 32));
   return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
+template <int CTRL>
+__device__ __forceinline__ long long dpp(long long old, long long v) {  // (the integer sums of pose_opt.hip)
+  return __builtin_bit_cast(long long, dpp<CTRL>(__builtin_bit_cast(double, old), __builtin_bit_cast(double, v)));
+}
 // Rows of 16 lanes.  row_shr:n = 0x110+n: lane i reads lane i-n of its row; row_shl:n = 0x100+n: lane i reads lane i+n.
 // Lanes whose source is outside the row get `fill`.
 template <int N, class T>

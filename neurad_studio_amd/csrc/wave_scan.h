@@ -22,6 +22,9 @@ __device__ __forceinline__ double lane_of(double v, int l) {
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), l);
   return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
+__device__ __forceinline__ long long lane_of(long long v, int l) {
+  return __builtin_bit_cast(long long, lane_of(__builtin_bit_cast(double, v), l));
+}
 
 struct Add {
   template <class T>

@@ -125,6 +125,15 @@ class NeuRADHipModelConfig(NeuRADModelConfig):
     with one device->host transfer (``lpips`` and the images stay the reference's), and the training step's ``psnr``
     (models/neurad.py:465) is ``ops.image_psnr``: a device tensor, no torchmetrics module state.  False: the reference's
     torchmetrics objects (a ``float()`` per metric; SSIM as a grouped conv2d with fp32 E[x^2] - mu^2 variances)."""
+    fused_camera_opt: bool = False
+    """Camera pose correction on the device (csrc/pose_opt.hip, cameras/camera_optimizers.py): with
+    ``camera_optimizer.mode = "SO3xR3"`` (the `*-scaleopt` methods) ``self.camera_optimizer`` becomes this package's
+    CameraOptimizer around the reference module's own Parameter and ``weights`` buffer (same state-dict names, parameter
+    group and checkpoints).  ``apply_to_raybundle`` is one autograd node -- one launch forwards; backwards per-camera integer
+    sums, bit-identical for any order of the rays -- and ``get_metrics_dict`` returns device tensors (the reference's
+    ``rot.mean().cpu()`` / ``rot.max().cpu()`` are two host synchronisations per step).  Deviation under AMP: the corrected
+    directions stay fp32, where the reference's ``torch.bmm`` under autocast rounds them through fp16.  False, mode "off",
+    mode "SE3" or ``non_trainable_camera_indices``: the reference's module."""
     table_dtype: Literal["float32", "float16"] = "float32"
     """Storage of the main field's hash tables (static grid + actor grids).  "float16" (BASELINE config[4]; what tiny-cuda-nn
     stores): half the gather bytes; gradients arrive in fp16 and HashGridAdam keeps fp32 master copies (optim.py).  State
@@ -194,6 +203,8 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
             from neurad_studio_amd.model_components.perceptual import VGGPerceptualLoss
 
             self.vgg_loss = VGGPerceptualLoss.from_reference(self.vgg_loss)
+        if cfg.fused_camera_opt:
+            self.use_fused_camera_optimizer()
         s = cfg.sampling
         self.sampler = hip_samplers.ProposalNetworkSampler(
             num_proposal_samples_per_ray=s.num_proposal_samples, num_nerf_samples_per_ray=s.num_nerf_samples,
@@ -216,6 +227,14 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
         if cfg.proposal_table_dtype == "float16":
             for pf in self.proposal_fields:
                 pf.hashgrid.static_grid.hash_table.data = pf.hashgrid.static_grid.hash_table.data.half()
+
+    def use_fused_camera_optimizer(self) -> None:
+        """``config.fused_camera_opt`` for a model that is already built: swaps ``self.camera_optimizer`` for
+        cameras/camera_optimizers.py:CameraOptimizer around the same Parameter object (idempotent; the reference's module
+        stays where that class does not restate it)"""
+        from ..cameras.camera_optimizers import CameraOptimizer
+
+        self.camera_optimizer = CameraOptimizer.from_reference(self.camera_optimizer)
 
     def _render_weights(self, outputs, ray_samples):
         """models/neurad.py:711-724 without the cpu placeholder and independent of which ``nerfacc`` is importable"""

@@ -2192,6 +2192,57 @@ def image_psnr(a: Tensor, b: Tensor, psnr_range: float = 1.0) -> Tensor:
     return out[0]
 
 
+# ---- camera pose correction (csrc/pose_opt.hip): the SO3xR3 camera optimizer's apply_to_raybundle and its gradient -------------
+def _pose_args(pose: Tensor, weights: Optional[Tensor], camera_indices: Tensor):
+    pose = _chk(pose, "pose")
+    if pose.dim() != 2 or pose.shape[1] != 6:
+        raise ValueError(f"pose: expected [num_cameras, 6], got {tuple(pose.shape)}")
+    weights = _opt(weights, "weights")
+    if weights is not None and weights.shape[0] != 6:
+        raise ValueError(f"weights: expected [6], got {tuple(weights.shape)}")
+    return pose, weights, _chk(camera_indices.reshape(-1), "camera_indices", torch.int64)
+
+
+def _rays3(t: Tensor, name: str, r: int) -> Tensor:
+    t = _chk(t, name)
+    if t.dim() != 2 or tuple(t.shape) != (r, 3):
+        raise ValueError(f"{name}: expected [{r}, 3], got {tuple(t.shape)}")
+    return t
+
+
+def pose_apply(pose: Tensor, weights: Optional[Tensor], camera_indices: Tensor, origins: Tensor, directions: Tensor):
+    """-> (origins + t, R directions), fp32 [R, 3]: the exponential map of SO(3) x R^3 of ``pose[camera_indices] * weights`` per
+    ray, as include/neurad_hip.h states it.  pose [C, 6] fp32, weights [6] fp32 or None, camera_indices int64 [R] inside
+    [0, C) (a ray outside comes back unchanged).  One launch, no autograd (autograd.PoseApplyFn)."""
+    pose, weights, idx = _pose_args(pose, weights, camera_indices)
+    r = idx.shape[0]
+    origins, directions = _rays3(origins, "origins", r), _rays3(directions, "directions", r)
+    if r == 0 or pose.shape[0] == 0:
+        return origins.clone(), directions.clone()
+    out_o, out_d = torch.empty_like(origins), torch.empty_like(directions)
+    launch("nrhip_pose_apply", pose, weights, pose.shape[0], idx, origins, directions, r, out_o, out_d)
+    return out_o, out_d
+
+
+def pose_apply_bwd(pose: Tensor, weights: Optional[Tensor], camera_indices: Tensor, directions: Tensor, grad_origins: Tensor,
+                   grad_directions: Tensor, need_grad_origins: bool = False, need_grad_directions: bool = False):
+    """-> (grad_pose [C, 6] dense fp32, grad_in_origins or None, grad_in_directions or None).  Per-camera integer sums: the same
+    bits for every order of the rays, no float atomics, no host read; a camera with a non-finite ray gradient gets a NaN row,
+    a camera without a ray exact zeros (include/neurad_hip.h)."""
+    pose, weights, idx = _pose_args(pose, weights, camera_indices)
+    r, c = idx.shape[0], pose.shape[0]
+    directions = _rays3(directions, "directions", r)
+    grad_origins, grad_directions = _rays3(grad_origins, "grad_origins", r), _rays3(grad_directions, "grad_directions", r)
+    gi_o = torch.empty_like(grad_origins) if need_grad_origins else None
+    gi_d = torch.empty_like(grad_directions) if need_grad_directions else None
+    if r == 0 or c == 0:
+        return torch.zeros_like(pose), gi_o, gi_d
+    grad_pose = torch.empty_like(pose)
+    ws, _ = _workspace("nrhip_pose_apply_bwd_workspace", r, c, device=pose.device, dtype=torch.uint8)
+    launch("nrhip_pose_apply_bwd", pose, weights, c, idx, directions, grad_origins, grad_directions, r, ws, grad_pose, gi_o, gi_d)
+    return grad_pose, gi_o, gi_d
+
+
 # ---- SURVEY §8(e): the level-sparse gradient exchange's device side (csrc/grad_rows.hip; parallel/data_parallel.py) ----------
 def grad_rows_count(grad: Tensor, n_levels: int):
     """grad [n_levels * T, F] fp32 -> (level_counts [n_levels] int64 = non-zero rows per level, block_offsets [n_levels, nblk]
