@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import neurad_oracle as O
+import scan_refs
 import synth
 from conftest import load_golden, rel_l2
 from builders import actor_params, field_params, trajectories
@@ -472,3 +473,18 @@ def test_actor_pairs_equal_nonzero_of_the_hits_table(n):
     pair = (h >= 0).nonzero()
     assert si.dtype == torch.int64 and ai.dtype == torch.int32
     assert torch.equal(si, pair[:, 0]) and torch.equal(ai, h[pair[:, 0], pair[:, 1]])
+
+
+@pytest.mark.parametrize("n", scan_refs.PAIRS_N_NEW)
+def test_actor_pairs_past_one_block_per_scan_thread(n):
+    """nblk = 1024, 1025, 1026: every thread of actor_pairs_scan_kernel busy with one block, then per = 2 blocks per thread
+    with the threads from c0 >= nblk on idle.  The table (tests/scan_refs.py: two hit densities, a run of 1024-sample blocks
+    without a hit next to blocks that write, a full row at n - 1) against `nonzero`, exactly."""
+    from neurad_studio_amd import ops
+
+    h = cuda(scan_refs.hits_table(n, seed=n))
+    si, ai = ops.actor_pairs(h)
+    pair = (h >= 0).nonzero()
+    assert si.dtype == torch.int64 and ai.dtype == torch.int32 and pair.shape[0] > 100000
+    assert torch.equal(si, pair[:, 0]) and torch.equal(ai, h[pair[:, 0], pair[:, 1]])
+    assert si[-8:].tolist() == [n - 1] * 8 and ai[-8:].tolist() == list(range(8))

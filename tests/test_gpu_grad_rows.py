@@ -3,6 +3,9 @@ gloo / CPU path of parallel/data_parallel.py uses: counts, ordered compaction wi
 import pytest
 import torch
 
+import scan_refs as SR
+from gpu_util import cuda
+
 pytestmark = pytest.mark.gpu
 
 
@@ -56,6 +59,41 @@ def test_count_compact_apply_match_torch(F, T):
     assert torch.equal(torch.nan_to_num(g2, nan=7.0), torch.nan_to_num(want.view(L * T, F), nan=7.0))
     # untouched levels are untouched
     assert torch.equal(g2.view(L, T, F)[4], grad.view(L, T, F)[4]) and torch.equal(g2.view(L, T, F)[0], grad.view(L, T, F)[0])
+
+
+@pytest.mark.parametrize("F", [1, 4])
+@pytest.mark.parametrize("T", SR.GRAD_T_NEW)
+def test_scan_carries_across_passes_of_1024_blocks(F, T):
+    """nblk = 1024, 1025, 1027: one full pass of rows_scan_kernel, a second pass of one block, a ragged second pass.  The
+    non-zero share differs between the levels and between the passes (tests/scan_refs.py), so an offset that lost the
+    first pass's total, or took another level's, lands on other rows.  Everything is compared exactly."""
+    from neurad_studio_amd import ops
+
+    L, nblk = 2, SR.grad_nblk(T)
+    grad = cuda(SR.sparse_grad(T, F, seed=T + F).reshape(L * T, F))
+    counts, blocks = ops.grad_rows_count(grad, L)
+    mask = (grad.view(L, T, F) != 0).any(-1)
+    assert bool(mask[:, T - 1].all())
+    assert counts.tolist() == mask.sum(1).tolist()
+    per_block = torch.nn.functional.pad(mask, (0, nblk * 256 - T)).view(L, nblk, 256).sum(-1)
+    want_blocks = torch.cumsum(per_block, 1) - per_block
+    assert blocks.shape == (L, nblk) and torch.equal(blocks.long(), want_blocks)
+    levels = [1, 0]  # list order need not be level order
+    caps = [int(counts[1]) + 3, int(counts[0])]
+    rows, vals = ops.grad_rows_compact(grad, L, blocks, levels, caps, scale=0.5)
+    o = 0
+    for l, c in zip(levels, caps):
+        want = mask[l].nonzero()[:, 0].int()
+        n = want.numel()
+        assert torch.equal(rows[o:o + n], want) and bool((rows[o + n:o + c] == -1).all())
+        assert torch.equal(vals[o:o + n], grad.view(L, T, F)[l][want.long()] * 0.5) and bool((vals[o + n:o + c] == 0).all())
+        o += c
+    g2 = grad.clone()
+    ops.grad_rows_apply(g2, L, levels, caps, rows, None, add=False)
+    assert not bool(g2.any())  # every non-zero row of both levels was listed
+    ops.grad_rows_apply(g2, L, levels, caps, rows, vals, add=True)
+    ops.grad_rows_apply(g2, L, levels, caps, rows, vals, add=True)
+    assert torch.equal(g2, grad * 0.5 + grad * 0.5)  # grad * 2 * scale, as two ranks with equal gradients would add it
 
 
 def test_empty_lists_and_argument_checks():

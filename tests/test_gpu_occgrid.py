@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import occgrid_oracle as OO
+import scan_refs as SR
 import synth
 from gpu_util import cuda
 
@@ -68,6 +69,53 @@ def test_estimator_sampling_with_alpha_pruning_and_empty_grid():
     est.binaries[:] = False
     ri3, _, _ = est.sampling(o, d, render_step_size=0.5)
     assert ri3.numel() == 0
+
+
+# ---- packed_visibility_from_alpha past a ray's first 64-sample chunk (tests/scan_refs.py; the designed crossings and the
+# band are checked in tests/test_scan_refs_host.py) ---------------------------------------------------------------------------
+@pytest.mark.parametrize("alpha_thre", SR.VIS_ALPHA_THRES)
+def test_packed_visibility_exact_across_chunks(alpha_thre):
+    """Rays of 0 to 700 samples, 13 of them (a ragged last workgroup), every 1 - alpha in {1, 1/2, 1/4} and eps = 2^-20: each
+    transmittance is a power of two, each comparison exact.  T first drops below eps inside chunk 0, at samples 63, 64 and
+    65, inside chunk 2, inside a ragged last chunk, or never; some samples see T == eps and are kept."""
+    from neurad_studio_amd import ops
+
+    seg, a = SR.vis_segments(), SR.vis_exact_alphas()
+    want = OO.packed_visibility_from_alpha(a, seg, SR.VIS_EXACT_EPS, alpha_thre)
+    keep = ops.packed_visibility_from_alpha(cuda(a), cuda(seg), SR.VIS_EXACT_EPS, alpha_thre).cpu().numpy()
+    assert 0 < want.sum() < len(want)
+    np.testing.assert_array_equal(keep, want)
+
+
+def test_packed_visibility_writes_every_entry_and_nothing_else():
+    """The mask comes from torch.empty: behind an early termination the kernel itself has to write the zeros, when the ray
+    ends one, two or several chunks later.  Into a buffer of 0xFF with a guard byte on each side."""
+    from neurad_studio_amd import ops
+
+    seg, a = SR.vis_segments(), SR.vis_exact_alphas()
+    buf = torch.full((len(a) + 2,), 0xFF, dtype=torch.uint8, device="cuda")
+    ops.launch("nrhip_packed_visibility_from_alpha", cuda(a), cuda(seg), len(seg) - 1, SR.VIS_EXACT_EPS, 0.0, buf[1:-1])
+    got = buf.cpu().numpy()
+    assert got[0] == 0xFF and got[-1] == 0xFF
+    assert set(np.unique(got[1:-1])) == {0, 1}
+    np.testing.assert_array_equal(got[1:-1].astype(bool), OO.packed_visibility_from_alpha(a, seg, SR.VIS_EXACT_EPS, 0.0))
+
+
+def test_packed_visibility_generic_alphas_vs_float64():
+    """alphas from U[0, 0.05], eps 1e-3, alpha_thre 0.02: three rays cross eps beyond their first chunk.  Samples whose
+    float64 T lies within a relative 1e-4 of eps are left out (the fp32 T is a product through fewer than 1024 roundings:
+    1024 * 2^-24 = 6.1e-5); at most 0.5 % may be, asserted from the reference alone."""
+    from neurad_studio_amd import ops
+
+    seg, a = SR.vis_segments(), SR.vis_generic_alphas()
+    eps, thre = SR.VIS_GENERIC_EPS, SR.VIS_GENERIC_ALPHA_THRE
+    want, T = SR.visibility64(a, seg, eps, thre)
+    left_out = np.abs(T - eps) <= SR.VIS_BAND * eps
+    print(f"{left_out.sum()} of {len(a)} samples left out")
+    assert left_out.mean() <= SR.VIS_MAX_LEFT_OUT
+    assert sum(c is not None and c >= SR.CHUNK for c in SR.first_below(T, seg, eps)) >= 3
+    keep = ops.packed_visibility_from_alpha(cuda(a), cuda(seg), eps, thre).cpu().numpy()
+    np.testing.assert_array_equal(keep[~left_out], want[~left_out])
 
 
 def test_volumetric_sampler_module():

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import occgrid_update_restatement as UR
+import scan_refs as SR
 import synth
 from conftest import rel_l2
 from gpu_util import cuda, host
@@ -169,6 +170,113 @@ def test_threshold_on_the_quantised_shell(occ_thre):
         gap = UR.threshold_gap(want["occs"], want["thre"])
         assert gap > 1e-3
         assert (want["mean"] > occ_thre) == (occ_thre < 5e-3)
+        ids, counts, pos = est._update(step, shell_occ_torch, occ_thre=occ_thre, ema_decay=0.95, warmup_steps=256,
+                                       **dev_draws(d, step < 256))
+        np.testing.assert_array_equal(host(counts), want["counts"])
+        np.testing.assert_array_equal(host(ids), want["ids"])
+        np.testing.assert_array_equal(bits(host(pos)), bits(want["positions"].reshape(-1, 3)))
+        np.testing.assert_array_equal(bits(host(est.occs)), bits(want["occs"]))
+        np.testing.assert_array_equal(host(est.binaries), want["binaries"])
+        print(f"step {step}: thre {want['thre']:.6g}, nearest value {gap:.3g} away, {int(want['binaries'].sum())} occupied")
+
+
+# ---- past the scans' first pass: res 65 (n_blk = 269: two blocks per scan thread; n_part = 269 at two levels) and the
+# default res 128 (n_blk = 2048, n_part = 1024); tests/scan_refs.py, preconditions in tests/test_scan_refs_host.py -----------
+@pytest.mark.parametrize("case", list(SR.CANDIDATE_CASES))
+def test_candidates_equal_the_restatement_two_blocks_per_scan_thread(case):
+    """test_candidates_equal_the_restatement's cases at res 65, the smallest resolution at which compact_scan_kernel gives
+    each thread two blocks; the last compaction block is ragged (193 cells) and the scan threads from 135 on are idle."""
+    from neurad_studio_amd import ops
+
+    res = SR.OCC_RES_NEW
+    c = SR.candidates_case(case, res)
+    L, n, n_occ, warmup = c["L"], c["n"], c["n_occ"], c["warmup"]
+    if case == "few_occupied":
+        assert 0 < n_occ[0] <= n
+    if case == "many_occupied":
+        assert n_occ[0] > n
+    if case == "two_levels":
+        assert n_occ[0] > n >= n_occ[1] > 0
+    grid = ops.OccGridSpec(torch.tensor(UNIT), cuda(c["binaries"]))
+    ids, counts, pos = ops.occgrid_update_candidates(grid, cuda(c["occs"]), warmup, **dev_draws(c["draws"], warmup))
+    assert ids.shape == (L, c["cap"]) and pos.shape == (L * c["cap"], 3)
+    np.testing.assert_array_equal(host(counts), c["counts"])
+    np.testing.assert_array_equal(host(ids), c["ids"])
+    assert (c["ids"] == -1).any() and (c["occs"] < 0).any()
+
+
+@pytest.mark.parametrize("box", [UNIT, [-1.3, -2.1, 0.2, 3.3, 1.7, 2.9]], ids=["power_of_two", "generic"])
+def test_positions_lie_in_their_cells_at_res_65(box):
+    """test_positions_lie_in_their_cells' rule at a resolution that is no power of two: within 4 ulp of the float64
+    restatement and inside the cell's faces in the update's own fp32 arithmetic.  Bit-equality with the fp32 restatement is
+    not required (1 / 65 is no fp32 number: whether the device's division rounds like numpy's is printed, not asserted)."""
+    from neurad_studio_amd import ops
+
+    res, L = SR.OCC_RES_NEW, 2
+    occs, binaries = SR.grid_state(res, L, 21)
+    d = UR.draws(res, L, False, 22)
+    d["jitter"][0, :8] = np.float32(1.0 - 2.0 ** -24)  # the largest jitter there is
+    d["jitter"][0, 8:16] = 0.0
+    aabbs = UR.level_aabbs(box, L)
+    grid = ops.OccGridSpec(torch.from_numpy(aabbs), cuda(binaries))
+    ids, counts, pos = ops.occgrid_update_candidates(grid, cuda(occs), False, **dev_draws(d, False))
+    ids, pos = host(ids), host(pos).reshape(L, -1, 3)
+    want_ids, _ = UR.candidates(occs, binaries, res, L, False, None, d["cell_draws"], d["sel_draws"])
+    np.testing.assert_array_equal(ids, want_ids)
+    want32, want64 = UR.positions(aabbs, res, ids, d["jitter"]), UR.positions(aabbs, res, ids, d["jitter"], np.float64)
+    flo, fhi = UR.cell_faces_f32(aabbs, res, ids)
+    lo, hi = UR.cell_boxes(aabbs, res, ids)
+    for l in range(L):
+        ulp = float(np.spacing(np.float32(np.abs(aabbs[l]).max())))
+        ok = ids[l] >= 0
+        err = np.abs(pos[l].astype(np.float64) - want64[l])
+        print(f"level {l}: max |p - float64 restatement| = {err[ok].max() / ulp:.2f} ulp; differs from the fp32 restatement on "
+              f"{(bits(pos[l]) != bits(want32[l])).sum()} of {pos[l].size} coordinates")
+        assert ok.sum() > 100000 and err.max() <= 4 * ulp
+        assert np.all(pos[l][ok] >= flo[l][ok]) and np.all(pos[l][ok] <= fhi[l][ok])  # fp32 faces: exactly, any box
+        assert np.all(np.abs(flo[l] - lo[l]) <= 4 * ulp) and np.all(np.abs(fhi[l] - hi[l]) <= 4 * ulp)
+        centre = ((aabbs[l, :3] + aabbs[l, 3:]) * np.float32(0.5))
+        np.testing.assert_array_equal(pos[l][~ok], np.broadcast_to(centre, pos[l][~ok].shape))
+
+
+@pytest.mark.parametrize("regime", list(SR.EMA_OCC_THRE))
+def test_ema_mean_and_threshold_over_more_than_256_partial_sums(regime):
+    """res 65, two levels: 269 partial sums, so mean_final_kernel's threads go round their loop twice.  Injected candidates
+    over the whole grid (tests/scan_refs.py: duplicates, untouched and invisible cells, a level with slots behind its count,
+    values that are multiples of 2^-10, large only behind the first 256 partial sums).  occs bit for bit and the binaries
+    on every cell against the restatement.  Precondition, from the restatement alone: no visible cell's value within 1e-3,
+    relative, of the threshold."""
+    from neurad_studio_amd import ops
+
+    res, L, occ_thre = SR.OCC_RES_NEW, 2, SR.EMA_OCC_THRE[regime]
+    assert SR.occ_sizes(res, L)[2] == 269
+    c = SR.ema_case(res, L, seed=71)
+    want = UR.ema(c["occs"], res, c["ids"], c["counts"], c["vals"], SR.EMA_DECAY)
+    want_b, thre, mean = UR.threshold(want, occ_thre)
+    gap = UR.threshold_gap(want, thre)
+    print(f"mean {mean:.6g}, thre {thre:.6g}, nearest value {gap:.3g} away, {int(want_b.sum())} occupied")
+    assert gap > 1e-3 and (mean > occ_thre) == (regime == "mean_above_occ_thre")
+    stale = np.random.default_rng(72).random((L, res, res, res)) < 0.5  # every binary is rewritten, whatever it held
+    grid = ops.OccGridSpec(torch.tensor(UNIT), cuda(stale))
+    got = cuda(c["occs"])
+    ops.occgrid_update_apply(grid, got, cuda(c["ids"]), cuda(c["counts"]), cuda(c["vals"]), SR.EMA_DECAY, occ_thre)
+    np.testing.assert_array_equal(bits(host(got)), bits(want))
+    np.testing.assert_array_equal(host(grid.binaries).reshape(-1), want_b)
+
+
+@pytest.mark.parametrize("occ_thre", [1e-3, 1e-2])
+def test_threshold_on_the_quantised_shell_at_the_default_resolution(occ_thre):
+    """test_threshold_on_the_quantised_shell at OccGridEstimator's default resolution 128, one level: n_blk = 2048 (eight
+    blocks per scan thread), n_part = 1024 (four rounds of the mean's loop).  In the unit box at a power-of-two resolution
+    the position formula is exact up to one rounding, so the position bits are compared as well.  The restatement's mean
+    lies above both thresholds here (tests/test_scan_refs_host.py), so thre = occ_thre at every step."""
+    from neurad_studio_amd.shims.nerfacc import OccGridEstimator
+
+    est = OccGridEstimator(UNIT, resolution=128, levels=1)
+    for step, d, want in SR.shell_run_default(occ_thre):
+        gap = UR.threshold_gap(want["occs"], want["thre"])
+        assert gap > 1e-3
+        assert want["mean"] > occ_thre and want["thre"] == np.float32(occ_thre)
         ids, counts, pos = est._update(step, shell_occ_torch, occ_thre=occ_thre, ema_decay=0.95, warmup_steps=256,
                                        **dev_draws(d, step < 256))
         np.testing.assert_array_equal(host(counts), want["counts"])
