@@ -656,7 +656,9 @@ __global__ __launch_bounds__(256) void actor_density_splice_bwd_kernel(
       gl = go * expf(fminf(fmaxf(logit[p], -15.f), 15.f));  // trunc_exp's backward (field_components/activations.py:37-41)
       f = gl;
     } else {
-      f = go * dens_out[s];  // shadowed pair: (shadow - shadow.detach()) * merged value
+      // shadowed pair: the merged row's gradient, i.e. the winner's -- through trunc_exp's clamped backward as well
+      // (exp is monotone: the clamped logit's exp is the clamped density)
+      f = go * fminf(fmaxf(dens_out[s], expf(-15.f)), expf(15.f));
     }
     for (int k = 0; k < la; ++k) g_rows[p * la + k] = f * w[k];
   }
