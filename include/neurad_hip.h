@@ -1291,6 +1291,43 @@ int nrhip_vgg_stage_images(const float* x, const float* y, int64_t n_pixels, voi
 /* grad [n_pixels, 3] fp32 = grad16 [n_pixels, NRHIP_VGG_IMAGE_CHANNELS] / S (state = {amax, S} of grad16)               */
 int nrhip_vgg_image_grad(const void* grad16, const float* state, int64_t n_pixels, float* grad, void* stream);
 
+/* ---- LPIPS (torchmetrics' LearnedPerceptualImagePatchSimilarity(net_type="alex", normalize=True), models/neurad.py:267,587):
+ *          AlexNet features of cat([a, b]) tapped after each ReLU, unit-normalised per pixel, a weighted squared difference
+ *          per tap, the pixel mean.  Forward only.  Activations are NHWC fp16, accumulation is fp32; the image is STORED with
+ *          NRHIP_LPIPS_IMAGE_CHANNELS channels, the last zero.                                                              */
+#define NRHIP_LPIPS_IMAGE_CHANNELS 4
+#define NRHIP_LPIPS_MIN_SIZE 31      /* below it AlexNet's second pool is empty */
+#define NRHIP_LPIPS_HEAD_PIXELS 32   /* pixels per workgroup (and per float64 partial) of the head */
+#define NRHIP_LPIPS_EPS_INSIDE 0     /* n(f) = f / sqrt(eps + sum f^2)   (torchmetrics, eps = 1e-8)  */
+#define NRHIP_LPIPS_EPS_OUTSIDE 1    /* n(f) = f / (sqrt(sum f^2) + eps) (the lpips package, 1e-10) */
+/* cat([a, b]) of two fp32 [n_pixels, 3] images in [0, 1] -> fp16 [2 * n_pixels, NRHIP_LPIPS_IMAGE_CHANNELS] holding
+ * (2 v - 1 - shift[c]) / scale[c], evaluated in float64 and rounded to fp32, then to fp16.  *flag (the caller zeroes it) is
+ * set to 1 when any value is outside [0, 1] or not finite; the call does not read it.                                      */
+int nrhip_lpips_stage_images(const float* a, const float* b, int64_t n_pixels, const float* shift, const float* scale,
+                             void* out, int32_t* flag, void* stream);
+/* One implicit-GEMM convolution, for exactly AlexNet's five layers (cin -> cout, ksize, stride, pad): 3 -> 64, 11, 4, 2;
+ * 64 -> 192, 5, 1, 2; 192 -> 384, 384 -> 256 and 256 -> 256, 3, 1, 1.  Anything else is NRHIP_ERR_UNSUPPORTED.
+ * Host logic: the plan over n_pixels OUTPUT pixels.  A wave owns 32 * pixel_blocks pixels x 32 * channel_blocks channels;
+ * plan 0 chooses pixel_blocks from n_pixels and cout, 1 or 2 forces it.  Every plan gives the same bits.                   */
+int nrhip_conv2d_plan(int64_t n_pixels, int32_t cin, int32_t cout, int32_t ksize, int32_t stride, int32_t pad, int32_t plan,
+                      int32_t* pixel_blocks, int32_t* channel_blocks, int64_t* waves);
+/* torch Conv2d weight [cout][cin][ksize][ksize] fp32 -> fragment order, nrhip_conv2d_pack_bytes bytes; reduction indices
+ * that are padding (the image's 4th channel, the 12th tap of an 11-tap row) hold zeros.                                    */
+int nrhip_conv2d_pack_bytes(int32_t cout, int32_t cin, int32_t ksize, int64_t* bytes);
+int nrhip_conv2d_pack(const float* weight, int32_t cout, int32_t cin, int32_t ksize, void* wfrag, void* stream);
+/* out [b, ho, wo, cout] = fp16(conv(in [b, h, w, cin]) + bias), then ReLU if `relu`; ho = (h + 2 pad - ksize) / stride + 1.
+ * bias may be NULL.  The image layer needs h, w >= NRHIP_LPIPS_MIN_SIZE.                                                    */
+int nrhip_conv2d(const void* in, const void* wfrag, const float* bias, void* out, int32_t b, int32_t h, int32_t w, int32_t cin,
+                 int32_t cout, int32_t ksize, int32_t stride, int32_t pad, int32_t relu, int32_t plan, void* stream);
+/* max_pool2d(3, 2), floor mode, no padding, on [b,h,w,c] fp16 (h, w >= 3, c a multiple of 8) -> [b,(h-3)/2+1,(w-3)/2+1,c]   */
+int nrhip_maxpool3s2_fwd(const void* in, void* out, int64_t b, int32_t h, int32_t w, int32_t c, void* stream);
+/* One tap's term.  feat [2 b, n_pixels, c] fp16 (the first b images against the second b), lin [c] fp32:
+ * out[i] = (accumulate ? out[i] : 0) + mean_pixels sum_c lin[c] (n(fa)_c - n(fb)_c)^2, n as eps_mode says; fp32 per pixel,
+ * float64 per-workgroup partials in `workspace` added in a fixed order, one rounding to fp32.  Bit-reproducible.           */
+int nrhip_lpips_head_workspace(int64_t b, int64_t n_pixels, int64_t* bytes);
+int nrhip_lpips_head(const void* feat, const float* lin, int64_t b, int64_t n_pixels, int32_t c, float eps, int32_t eps_mode,
+                     int32_t accumulate, void* workspace, int64_t workspace_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

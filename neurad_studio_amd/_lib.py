@@ -127,6 +127,9 @@ VGG_IMAGE_CHANNELS = 16     # NRHIP_VGG_IMAGE_CHANNELS
 L1_ITEMS = 2048             # NRHIP_L1_ITEMS
 SSIM_TILE = 32              # NRHIP_SSIM_TILE
 IMAGE_STAT_ITEMS = 4096     # NRHIP_IMAGE_STAT_ITEMS
+LPIPS_IMAGE_CHANNELS = 4    # NRHIP_LPIPS_IMAGE_CHANNELS
+LPIPS_MIN_SIZE = 31         # NRHIP_LPIPS_MIN_SIZE
+LPIPS_EPS_INSIDE, LPIPS_EPS_OUTSIDE = 0, 1  # NRHIP_LPIPS_EPS_*
 P, I32, I64, F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> argtypes : exactly the prototypes of include/neurad_hip.h (tests/test_abi.py cross-checks this
@@ -307,6 +310,14 @@ PROTOTYPES = {
     "nrhip_l1_feature_bwd": [P, P, I64, F32, P, I32, P, P, P, P, P],
     "nrhip_vgg_stage_images": [P, P, I64, P, P],
     "nrhip_vgg_image_grad": [P, P, I64, P, P],
+    "nrhip_lpips_stage_images": [P, P, I64, P, P, P, P, P],
+    "nrhip_conv2d_plan": [I64, I32, I32, I32, I32, I32, I32, C.POINTER(I32), C.POINTER(I32), C.POINTER(I64)],
+    "nrhip_conv2d_pack_bytes": [I32, I32, I32, C.POINTER(I64)],
+    "nrhip_conv2d_pack": [P, I32, I32, I32, P, P],
+    "nrhip_conv2d": [P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P],
+    "nrhip_maxpool3s2_fwd": [P, P, I64, I32, I32, I32, P],
+    "nrhip_lpips_head_workspace": [I64, I64, C.POINTER(I64)],
+    "nrhip_lpips_head": [P, P, I64, I64, I32, F32, I32, I32, P, I64, P, P],
 }
 
 _lib = None

@@ -41,7 +41,7 @@ from ..fields.neurad_field import NeuRADProposalField as HipNeuRADProposalField
 from ..model_components import losses as hip_losses
 from ..model_components import ray_samplers as hip_samplers
 from ..model_components import renderers as hip_renderers
-from ..model_components.image_metrics import PSNR, ImageEvalPair
+from ..model_components.image_metrics import PSNR, ImageEvalPair, ImageEvalTriple, lpips_eval_metric
 from ..model_components.lidar_metrics import lidar_eval_metrics, masked_return_metrics, scalars_to_host
 from ..models.neurad import FusedEvalMixin, FusedTrainMixin
 from ..optim import HashGridAdam
@@ -125,6 +125,12 @@ class NeuRADHipModelConfig(NeuRADModelConfig):
     with one device->host transfer (``lpips`` and the images stay the reference's), and the training step's ``psnr``
     (models/neurad.py:465) is ``ops.image_psnr``: a device tensor, no torchmetrics module state.  False: the reference's
     torchmetrics objects (a ``float()`` per metric; SSIM as a grouped conv2d with fp32 E[x^2] - mu^2 variances)."""
+    fused_lpips: bool = False
+    """LPIPS on the device (csrc/lpips.hip, model_components/lpips.py): ``self.lpips`` adopts the reference object's network
+    (``LPIPS.from_reference``: no tensor copied, the state dict stays the reference's) and the ``lpips`` of
+    get_image_metrics_and_images (models/neurad.py:587) is AlexNet on the fp16 matrix cores, its value and the flag of
+    torchmetrics' value-range check read with one transfer.  Together with ``fused_image_eval`` all three image metrics share
+    ONE transfer.  False: the reference's torchmetrics object (fp32 through the vendor library, two host reads)."""
     fused_camera_opt: bool = False
     """Camera pose correction on the device (csrc/pose_opt.hip, cameras/camera_optimizers.py): with
     ``camera_optimizer.mode = "SO3xR3"`` (the `*-scaleopt` methods) ``self.camera_optimizer`` becomes this package's
@@ -203,6 +209,10 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
             from neurad_studio_amd.model_components.perceptual import VGGPerceptualLoss
 
             self.vgg_loss = VGGPerceptualLoss.from_reference(self.vgg_loss)
+        if cfg.fused_lpips:
+            from neurad_studio_amd.model_components.lpips import LPIPS
+
+            self.lpips = LPIPS.from_reference(self.lpips)
         if cfg.fused_camera_opt:
             self.use_fused_camera_optimizer()
         s = cfg.sampling
@@ -374,11 +384,23 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
         """With ``fused_image_eval`` the image branch (models/neurad.py:568-587) runs the reference's own code with
         ``self.psnr`` / ``self.ssim`` answered, for this call, by model_components/image_metrics.py:ImageEvalPair: the first of
         the two launches the image kernels and reads both scalars with one transfer (``_scalars_to_host``), the second is
-        served from it.  Same keys, every value a Python float; ``images_dict`` and ``lpips`` are the reference's."""
-        if not (self.config.fused_image_eval and "image" in batch):
+        served from it.  Same keys, every value a Python float; ``images_dict`` and ``lpips`` are the reference's.
+        With ``fused_lpips`` as well, ``self.lpips`` is answered by the same object (ImageEvalTriple) and the three share the one
+        transfer; with ``fused_lpips`` alone only ``lpips`` is replaced (its value and range flag in one transfer)."""
+        cfg = self.config
+        if "image" not in batch or not (cfg.fused_image_eval or cfg.fused_lpips):
             return self._image_and_lidar_metrics(outputs, batch)
-        pair = ImageEvalPair(to_host=lambda values: self._scalars_to_host(values))
-        with _shadowed(self, psnr=pair.psnr, ssim=pair.ssim):
+        to_host = lambda values: self._scalars_to_host(values)  # noqa: E731
+        if not cfg.fused_lpips:
+            pair = ImageEvalPair(to_host=to_host)
+            shadows = dict(psnr=pair.psnr, ssim=pair.ssim)
+        elif not cfg.fused_image_eval:
+            module = self.lpips
+            shadows = dict(lpips=lambda preds, target: lpips_eval_metric(preds, target, module, to_host=to_host))
+        else:
+            triple = ImageEvalTriple(self.lpips, to_host=to_host)
+            shadows = dict(psnr=triple.psnr, ssim=triple.ssim, lpips=triple.lpips)
+        with _shadowed(self, **shadows):
             return self._image_and_lidar_metrics(outputs, batch)
 
     def _image_and_lidar_metrics(self, outputs, batch):
@@ -404,7 +426,8 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
 
     @staticmethod
     def _scalars_to_host(values):
-        """THE device->host transfer of the fused eval metrics: one per lidar scan (five scalars), one per camera image (two);
+        """THE device->host transfer of the fused eval metrics: one per lidar scan (five scalars), one per camera image (two;
+        four with ``fused_lpips``: the three metrics and LPIPS' range flag);
         tests count the calls"""
         return scalars_to_host(values)
 

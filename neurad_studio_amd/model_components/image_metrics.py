@@ -5,7 +5,11 @@ models/neurad.py:265-266, called at 465 and 585-586).
 On the device both come from ONE launch sequence of csrc/image_eval.hip (``ops.image_metrics``: the squared error and the data
 range in a first pass, the windowed moments of shifted values in a second, float64 sums in a fixed order) and travel to the
 host in ONE transfer, where the reference pays a ``float()`` per metric and forms each variance as E[x^2] - mu^2 in fp32.  On
-CPU tensors a plain torch float64 fallback runs (tests, tooling); it is not a product path.  LPIPS stays the reference's.
+CPU tensors a plain torch float64 fallback runs (tests, tooling); it is not a product path.
+
+LPIPS, the third metric of that method, is model_components/lpips.py (csrc/lpips.hip).  ``image_eval_metrics3`` and
+``ImageEvalTriple`` add it to the same ONE transfer, which also carries the device flag of torchmetrics' value-range check;
+``image_eval_metrics`` and ``ImageEvalPair`` are unchanged and leave LPIPS to the caller.
 """
 from __future__ import annotations
 
@@ -17,6 +21,7 @@ from torch import Tensor
 from .. import ops
 
 IMAGE_EVAL_KEYS = ("psnr", "ssim")
+IMAGE_EVAL_KEYS3 = ("psnr", "ssim", "lpips")
 WINDOW, SIGMA, K1, K2 = 11, 1.5, 0.01, 0.03
 
 
@@ -83,6 +88,44 @@ def image_eval_metrics(rgb: Tensor, image: Tensor,
     return dict(zip(IMAGE_EVAL_KEYS, to_host(torch.stack([psnr, ssim]))))
 
 
+def _lpips_scalars(lpips, preds: Tensor, target: Tensor) -> List[Tensor]:
+    """-> [value, flag] as 0-dim tensors of one dtype on the images' device (flag 0 where the check has been made already)"""
+    values, flag = lpips.pairs(preds, target)
+    value = values.mean()
+    return [value, torch.zeros_like(value) if flag is None else flag[0].to(value.dtype)]
+
+
+def _raise_if_flagged(flag: float) -> None:
+    if flag != 0.0:
+        from .lpips import out_of_range_error
+
+        raise out_of_range_error()
+
+
+def image_eval_metrics3(rgb: Tensor, image: Tensor, lpips,
+                        to_host: Callable[[Tensor], List[float]] = scalars_to_host) -> Dict[str, float]:
+    """``image_eval_metrics`` plus LPIPS (``lpips``: a model_components.lpips.LPIPS) -> {"psnr", "ssim", "lpips"}: floats from
+    ONE transfer of four scalars.  The fourth is the flag of LPIPS' value-range check (torchmetrics' _valid_img, a host read of
+    its own there): when it is set, the ValueError torchmetrics would have raised is raised here, after the read."""
+    if rgb.is_cuda:
+        psnr, ssim = ops.image_metrics(rgb, image.to(rgb.device))
+    else:
+        psnr, ssim = image_metrics_torch(rgb, image)
+    value, flag = _lpips_scalars(lpips, rgb, image.to(rgb.device))
+    dtype = torch.promote_types(psnr.dtype, value.dtype)  # (fp32 on the device; the float64 fallback keeps its digits)
+    *values, flagged = to_host(torch.stack([v.to(dtype) for v in (psnr, ssim, value, flag)]))
+    _raise_if_flagged(flagged)
+    return dict(zip(IMAGE_EVAL_KEYS3, values))
+
+
+def lpips_eval_metric(preds: Tensor, target: Tensor, lpips, to_host: Callable[[Tensor], List[float]] = scalars_to_host) -> float:
+    """LPIPS alone, as the reference calls it (``float(self.lpips(image, rgb))``): the value and the range flag in ONE
+    transfer, the ValueError after it"""
+    value, flagged = to_host(torch.stack(_lpips_scalars(lpips, preds, target.to(preds.device))))
+    _raise_if_flagged(flagged)
+    return value
+
+
 class PSNR(torch.nn.Module):
     """``PeakSignalNoiseRatio(data_range)`` as the model calls it (models/neurad.py:465): psnr(preds, target) -> 0-dim tensor
     on the tensors' device; no host read, no accumulated metric state"""
@@ -118,6 +161,31 @@ class ImageEvalPair:
 
     def ssim(self, preds: Tensor, target: Tensor) -> float:
         return self._get("ssim", preds, target)
+
+
+class ImageEvalTriple:
+    """``ImageEvalPair`` with ``lpips`` as the third: whichever of the three is called first on a pair of tensors launches
+    everything (``image_eval_metrics3``: one transfer) and the others are served from it"""
+
+    def __init__(self, lpips, to_host: Callable[[Tensor], List[float]] = scalars_to_host):
+        self.lpips_module, self.to_host = lpips, to_host
+        self._pair: Optional[Tuple[Tensor, Tensor]] = None
+        self._values: Dict[str, float] = {}
+
+    def _get(self, key: str, preds: Tensor, target: Tensor) -> float:
+        if self._pair is None or self._pair[0] is not preds or self._pair[1] is not target:
+            self._values = image_eval_metrics3(preds, target, self.lpips_module, to_host=self.to_host)
+            self._pair = (preds, target)
+        return self._values[key]
+
+    def psnr(self, preds: Tensor, target: Tensor) -> float:
+        return self._get("psnr", preds, target)
+
+    def ssim(self, preds: Tensor, target: Tensor) -> float:
+        return self._get("ssim", preds, target)
+
+    def lpips(self, preds: Tensor, target: Tensor) -> float:
+        return self._get("lpips", preds, target)
 
 
 def ssim(preds: Tensor, target: Tensor) -> Tensor:
