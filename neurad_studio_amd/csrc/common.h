@@ -398,6 +398,14 @@ __device__ __forceinline__ float rescale_weight(float scale_l, float std) {
   return __builtin_amdgcn_rcpf(fmaxf(scale_l * 2.f * std, 1.f));  // v_rcp_f32 (1 ulp); weights are smooth in std
 }
 
+// S2 backward: d trunc_exp(x)/dx = exp(clamp(x, -15, 15)) (activations.py:37-41) with x = log(density) recovered from the
+// saved forward output.  torch.clamp keeps a NaN where fminf / fmaxf return the other operand: a NaN density must poison
+// the gradient here as it does there, not come back as e^-15.  Finite and infinite x take the clamp as before.
+__device__ __forceinline__ float trunc_exp_bwd_factor(float density) {
+  const float x = logf(density);
+  return expf(x != x ? x : fminf(fmaxf(x, -15.f), 15.f));
+}
+
 // F3: 16 real SH components (utils/math.py:31-94) of a direction given as (dir+1)/2 -- the torch path
 // evaluates the polynomials on that [0,1]-normalised vector directly (base_field.py:136-142).
 __device__ __forceinline__ void sh4(float x, float y, float z, float (&c)[16]) {

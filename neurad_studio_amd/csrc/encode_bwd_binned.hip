@@ -250,8 +250,7 @@ struct ProposalGrad {  // S2: density = trunc_exp(decoder . rescaled features), 
   const float* dens;
   const float* gd;
   __device__ float pre(int64_t i) const {
-    const float xlog = logf(dens[i]);  // activations.py:37-41: g * exp(clamp(x, -15, 15))
-    return gd[i] * expf(fminf(fmaxf(xlog, -15.f), 15.f));
+    return gd[i] * trunc_exp_bwd_factor(dens[i]);  // activations.py:37-41: g * exp(clamp(x, -15, 15)), a NaN kept
   }
   template <int F>
   __device__ void grad(int64_t, int l, float sc, float std, float gx, float (&gv)[F]) const {

@@ -340,8 +340,7 @@ __global__ __launch_bounds__(256) void proposal_density_bwd_kernel(GridDev g, co
     const SamplePos p = sample_position(r.o[3 * ray], r.o[3 * ray + 1], r.o[3 * ray + 2], r.d[3 * ray],
                                         r.d[3 * ray + 1], r.d[3 * ray + 2], r.area[ray], r.starts[ray * r.stride + (i - ray * r.S)], r.ends[ray * r.stride + (i - ray * r.S)], scale);
     const uint32_t mask = (1u << g.log2T) - 1u;
-    const float xlog = logf(dens[i]);
-    const float gx = gd[i] * expf(fminf(fmaxf(xlog, -15.f), 15.f));
+    const float gx = gd[i] * trunc_exp_bwd_factor(dens[i]);
 #pragma unroll
     for (int l = 0; l < 8; ++l) {
       if (l < g.L) {
@@ -524,12 +523,12 @@ __global__ __launch_bounds__(256) void proposal_decoder_grad_kernel(const float*
     float gx[VEC];
     if constexpr (VEC == 4) {
       const float4 g4 = reinterpret_cast<const float4*>(gd)[i], d4 = reinterpret_cast<const float4*>(dens)[i];
-      gx[0] = g4.x * expf(fminf(fmaxf(logf(d4.x), -15.f), 15.f));
-      gx[1] = g4.y * expf(fminf(fmaxf(logf(d4.y), -15.f), 15.f));
-      gx[2] = g4.z * expf(fminf(fmaxf(logf(d4.z), -15.f), 15.f));
-      gx[3] = g4.w * expf(fminf(fmaxf(logf(d4.w), -15.f), 15.f));
+      gx[0] = g4.x * trunc_exp_bwd_factor(d4.x);
+      gx[1] = g4.y * trunc_exp_bwd_factor(d4.y);
+      gx[2] = g4.z * trunc_exp_bwd_factor(d4.z);
+      gx[3] = g4.w * trunc_exp_bwd_factor(d4.w);
     } else {
-      gx[0] = gd[i] * expf(fminf(fmaxf(logf(dens[i]), -15.f), 15.f));
+      gx[0] = gd[i] * trunc_exp_bwd_factor(dens[i]);
     }
 #pragma unroll
     for (int l = 0; l < 8; ++l)
