@@ -852,7 +852,8 @@ int nrhip_actor_find_packed(const nrhip_actors* a, const nrhip_packed_rays* rays
                             const float* ray_flip, void* stream);
 /* nrhip_actor_pair_positions_fwd / _bwd on packed samples (ABI 519): sample_idx [P] int64 is a PACKED sample index (clamped
  * into [0, M)), its ray comes from ray_of [M]; times and ray_flip stay per ray ([R]).  The same kernel bodies as the dense
- * pair; the backward ACCUMULATES (atomics) into grad_positions / grad_rotations_6d.  No gradient reaches the rays.        */
+ * pair; the backward ACCUMULATES (atomics) into grad_positions / grad_rotations_6d.  The rays' gradient is the entry point
+ * nrhip_actor_pair_positions_bwd_rays_packed below.                                                                        */
 int nrhip_actor_pair_positions_fwd_packed(const nrhip_actors* a, const nrhip_packed_rays* rays, const int64_t* ray_of,
                                           const float* times, const int64_t* sample_idx, const int32_t* actor_idx,
                                           const float* ray_flip /*[R] or NULL*/, int64_t n_pairs, float* x01, float* cstd,
@@ -862,6 +863,29 @@ int nrhip_actor_pair_positions_bwd_packed(const nrhip_actors* a, const nrhip_pac
                                           const float* ray_flip, int64_t n_pairs, const float* grad_x01,
                                           const float* grad_cstd, float* grad_positions, float* grad_rotations_6d,
                                           void* stream);
+/* dL/d(origins), dL/d(directions) [R,3] of the in-box samples of PACKED rays: the ray share of
+ * nrhip_actor_pair_positions_bwd_rays, on the pairs of nrhip_actor_pair_positions_fwd_packed (additive to ABI 520).  A pair
+ * hands its ray -gt for the origin and -gt * t_mid for the direction, gt = dL/d(interpolated translation), exactly what the
+ * dense kernel adds; the trajectory gradients stay with _bwd_packed.  This entry WRITES the two outputs (no caller zeroing),
+ * without atomics and without a workspace, an allocation or a host synchronisation (graph-capturable): bit-reproducible.
+ * PRECONDITION: sample_idx [P] is a packed sample index and NON-DECREASING -- what nrhip_actor_pairs_write produces ((sample,
+ * slot) order; several actors may share a sample).  With samples in ray order the pairs of ray r are then one range of the
+ * list; values are clamped into [0, M) when read (a clamped non-decreasing list is non-decreasing), segment bounds into
+ * [0, M], and a list that breaks the precondition gives wrong sums but no read outside the arrays.  rays->segments is
+ * required; there is no ray_of, the group knows its ray.
+ * A group of lanes_per_ray lanes (16 / 32 / 64) owns a ray: two searches of the pair list for the range of its segment,
+ * lane `sub` adds the pairs sub, sub + G, ... of the range in that order, xor butterfly, lane 0 writes.  A ray's rows depend
+ * on its own pairs and on G only; a ray without samples or without pairs gets exact zeros.  lanes_per_ray = 0: chosen on the
+ * host from the shapes alone, by the dense rule on the mean pair count n_pairs / n_rays (> 32 -> 64, > 16 -> 32, else 16;
+ * a ray far above the mean only makes its own group loop longer).
+ * n_rays == 0 is a no-op that reads no pointer; n_pairs == 0 zeroes both outputs without a launch; n_pairs > 0 on a batch
+ * without samples is NRHIP_ERR_INVALID_ARG, n_samples >= 2^31 NRHIP_ERR_UNSUPPORTED.                                      */
+int nrhip_actor_pair_positions_bwd_rays_packed(const nrhip_actors* a, const nrhip_packed_rays* rays, const float* times,
+                                               const int64_t* sample_idx, const int32_t* actor_idx,
+                                               const float* ray_flip /*[R] or NULL*/, int64_t n_pairs,
+                                               const float* grad_x01, const float* grad_cstd,
+                                               int32_t lanes_per_ray /*0 = choose*/, float* grad_origins /*[R,3]*/,
+                                               float* grad_directions /*[R,3]*/, void* stream);
 /* head + packed compositing.  beta: DEVICE pointer to the raw parameter, alpha = sigmoid(-geo_out (|beta| + beta_min));
  * beta == NULL: the density head, alpha = 1 - exp(-trunc_exp(geo_out) (t_end - t_start)).  Compositing as
  * nrhip_packed_composite_fwd (no sky residual, depth over all samples, zeros for an empty segment).  alpha [M] is what the

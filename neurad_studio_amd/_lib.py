@@ -208,6 +208,8 @@ PROTOTYPES = {
     "nrhip_actor_find_packed": [C.POINTER(Actors), C.POINTER(PackedRays), P, P, P, P, P, P, P, P, P],
     "nrhip_actor_pair_positions_fwd_packed": [C.POINTER(Actors), C.POINTER(PackedRays), P, P, P, P, P, I64, P, P, P],
     "nrhip_actor_pair_positions_bwd_packed": [C.POINTER(Actors), C.POINTER(PackedRays), P, P, P, P, P, I64, P, P, P, P, P],
+    "nrhip_actor_pair_positions_bwd_rays_packed": [C.POINTER(Actors), C.POINTER(PackedRays), P, P, P, P, I64, P, P, I32, P, P,
+                                                   P],
     "nrhip_sdf_render_packed_fwd": [P, P, F32, P, P, P, P, I64, I32, P, P, P, P, P, P],
     "nrhip_sdf_render_packed_bwd_workspace": [I64, C.POINTER(I64)],
     "nrhip_sdf_render_packed_bwd": [P, P, F32, P, P, P, P, P, P, P, P, P, I64, I32, P, P, P, P, P],

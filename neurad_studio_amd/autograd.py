@@ -27,7 +27,7 @@ class DenseSamples:
     samples from the march's packed ones (`PackedSamples`).  Dense: starts / ends [R,S] -- for the render node (`on_edges`)
     the views of its bin edges [R,S+1], last edge = sky distance.  Origins, directions and pixel area are per RAY in both."""
 
-    ray_indices = None  # (a ray's samples are a row)
+    ray_indices = segments = None  # (a ray's samples are a row)
 
     def __init__(self, starts, ends):
         self.starts, self.ends = starts, ends
@@ -109,7 +109,8 @@ class PackedSamples:
     """`DenseSamples` for the occupancy march's ragged output: starts / ends are t_starts / t_ends [M], segments int64 [R+1]
     bounds each ray's samples and ray_indices int64 [M] names each sample's ray (an operation needs one or the other).
     Compositing as PackedCompositeFn: no sky residual, depth = sum w mid over all samples, zeros for a ray without samples;
-    no appearance embedding (callers append it per ray); the rays get no gradient through the pair positions."""
+    no appearance embedding (callers append it per ray); through the pair positions the rays get their gradient from a
+    kernel of its own over the segments (ops.actor_pair_positions_packed_bwd_rays), so that path needs both."""
 
     def __init__(self, starts, ends, segments=None, ray_indices=None):
         self.starts, self.ends, self.segments, self.ray_indices = starts, ends, segments, ray_indices
@@ -146,8 +147,15 @@ class PackedSamples:
                                                actor_idx, flip)
 
     def pair_positions_bwd(self, spec, o, d, a, times, si, ai, flip, g_x01, g_cstd, need_o, need_d):
+        go = gd = None
+        if need_o or need_d:  # the in-box samples' share of a camera optimizer's gradient: one group of lanes per ray
+            if self.segments is None:
+                raise ValueError("pair positions of packed samples: rays that require grad need the samples' segments "
+                                 "(ActorPairPositionsFn's trailing argument), ray_indices alone do not bound a ray's pairs")
+            go, gd = ops.actor_pair_positions_packed_bwd_rays(spec, o, d, a, self.starts, self.ends, self.segments, times, si,
+                                                              ai, flip, g_x01, g_cstd)
         return (*ops.actor_pair_positions_packed_bwd(spec, o, d, a, self.starts, self.ends, self.ray_indices, times, si, ai,
-                                                     flip, g_x01, g_cstd), None, None)
+                                                     flip, g_x01, g_cstd), (go if need_o else None), (gd if need_d else None))
 
     def table_grad(self, spec, scale, o, d, a, genc, out_dtype):
         return ops.encode_bwd_packed(spec, scale, o, d, a, self.starts, self.ends, self.ray_indices, genc, out_dtype=out_dtype)
@@ -205,28 +213,29 @@ class ActorPairPositionsFn(torch.autograd.Function):
     csrc/actors.hip).  args: actor_positions [Tn,A,3], actor_rotations_6d [Tn,A,6] (the tensors inside ``spec``, passed
     so that autograd sees them), spec, origins, directions, pixel_area, starts, ends, times, sample_idx, actor_idx, flip
     -- dense samples: starts / ends [R,S], sample_idx [P] a flat sample index -- and for the occupancy march's packed
-    samples ray_indices int64 [M]: starts / ends are t_starts / t_ends [M], sample_idx is a packed sample index, times and
-    flip stay per RAY, and the rays get no gradient (callers refuse rays that require grad).  -> x01 [P,3], cstd [P]"""
+    samples ray_indices int64 [M]: starts / ends are t_starts / t_ends [M], sample_idx is a packed sample index (in
+    ops.actor_pairs' order), times and flip stay per RAY; rays that require grad get their gradient when the samples'
+    segments int64 [R+1] are given as well (the last argument), without them the backward raises.  -> x01 [P,3], cstd [P]"""
 
     @staticmethod
     def forward(ctx, positions, rotations_6d, spec, origins, directions, pixel_area, starts, ends, times, sample_idx,
-                actor_idx, flip, ray_indices=None):
+                actor_idx, flip, ray_indices=None, segments=None):
         ctx.spec, ctx.flip = spec, flip
-        ctx.save_for_backward(origins, directions, pixel_area, starts, ends, times, sample_idx, actor_idx, ray_indices)
+        ctx.save_for_backward(origins, directions, pixel_area, starts, ends, times, sample_idx, actor_idx, ray_indices, segments)
         return _pair_samples(starts, ends, ray_indices).pair_positions(spec, origins, directions, pixel_area, times,
                                                                        sample_idx, actor_idx, flip)
 
     @staticmethod
     def backward(ctx, g_x01, g_cstd):
-        o, d, a, s, e, times, si, ai, ri = ctx.saved_tensors
-        gp, gr, go, gd = _pair_samples(s, e, ri).pair_positions_bwd(
+        o, d, a, s, e, times, si, ai, ri, seg = ctx.saved_tensors
+        gp, gr, go, gd = _pair_samples(s, e, ri, seg).pair_positions_bwd(
             ctx.spec, o, d, a, times, si, ai, ctx.flip, g_x01.contiguous(), g_cstd.contiguous(), ctx.needs_input_grad[3],
             ctx.needs_input_grad[4])
         return (gp, gr, None, go, gd) + (None,) * (len(ctx.needs_input_grad) - 5)
 
 
-def _pair_samples(starts, ends, ray_indices):
-    return DenseSamples(starts, ends) if ray_indices is None else PackedSamples(starts, ends, ray_indices=ray_indices)
+def _pair_samples(starts, ends, ray_indices, segments=None):
+    return DenseSamples(starts, ends) if ray_indices is None else PackedSamples(starts, ends, segments, ray_indices)
 
 
 class MultiHashGridFn(torch.autograd.Function):

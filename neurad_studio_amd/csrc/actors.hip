@@ -518,6 +518,45 @@ __global__ __launch_bounds__(256) void actor_pair_positions_kernel(ActorsDev a, 
   cstd[p] = c.std;
 }
 
+// The head of one pair's backward, shared by the two backward kernels: the pair's frame f and sample gaussian g, then
+// (g_x01 [3], g_cstd [1]) -> gpos = dL/d(box-frame position) and gt = dL/d(interpolated translation).  iv: the sample's
+// interval in starts / ends; q: the ray's time.
+template <class RD>
+__device__ __forceinline__ void pair_position_grad(const ActorsDev& a, const RD& r, int64_t ray, int64_t iv, int act, float q,
+                                                   float flip, const float* __restrict__ g_x01,
+                                                   const float* __restrict__ g_cstd, PairFrame& f, SamplePos& g,
+                                                   float (&gpos)[3], float (&gt)[3]) {
+  pair_frame(a, act, q, f);
+  g = sample_gaussian(r.o[3 * ray], r.o[3 * ray + 1], r.o[3 * ray + 2], r.d[3 * ray], r.d[3 * ray + 1], r.d[3 * ray + 2],
+                      r.area[ray], r.starts[iv], r.ends[iv]);
+  float pos[3];
+  pair_box_position(f, g, flip, pos);
+  // ---- contraction backward (spatial_distortions.py:126-141, order = inf): (g_x01, g_cstd) -> g_pos ----------------
+  float m[3] = {pos[0] / a.scale, pos[1] / a.scale, pos[2] / a.scale};
+  const float am[3] = {fabsf(m[0]), fabsf(m[1]), fabsf(m[2])};
+  const float mag = fmaxf(fmaxf(am[0], am[1]), am[2]);
+  float gm[3] = {g_x01[0] / 4.f, g_x01[1] / 4.f, g_x01[2] / 4.f};  // x01 = (m' + 2) / 4
+  if (!(mag < 1.f)) {
+    // m' = k m, k = 2/mag - 1/mag^2;   cstd = (std/scale) q / 4, q = ((2 mag - 1)^(1/3) / mag)^2
+    const float k = 2.f / mag - 1.f / (mag * mag), dk = -2.f / (mag * mag) + 2.f / (mag * mag * mag);
+    const float cr = cbrtf(2.f * mag - 1.f), rr = cr / mag;
+    const float dq = 2.f * rr * ((2.f / 3.f) / (cr * cr * mag) - cr / (mag * mag));
+    const float g_mag = (gm[0] * m[0] + gm[1] * m[1] + gm[2] * m[2]) * dk + g_cstd[0] * (g.std / a.scale) * dq / 4.f;
+    inf_norm_bwd(m, am, mag, k, g_mag, gm);
+  }
+  gpos[0] = gm[0] / a.scale * flip, gpos[1] = gm[1] / a.scale, gpos[2] = gm[2] / a.scale;
+  gt[0] = -dot3(f.b1, gpos), gt[1] = -dot3(f.b2, gpos), gt[2] = -dot3(f.b3, gpos);
+}
+
+// d pos / d mean = -d pos / d t: the sample's world position moves with the ray (camera optimizer,
+// cameras/camera_optimizers.py:173-182); mean = o + d t_mid with t_mid a constant (detached bins).  A pair hands its ray
+// -gt[c] for the origin and -gt[c] * t_mid for the direction; this is t_mid.
+template <class RD>
+__device__ __forceinline__ float pair_ray_t(const RD& r, int64_t iv) {
+  const float t0 = r.starts[iv], t1 = r.ends[iv];
+  return t0 + (t1 - t0) / 2.f;
+}
+
 template <class RD>
 __global__ __launch_bounds__(256) void actor_pair_positions_bwd_kernel(
     ActorsDev a, RD r, const int64_t* __restrict__ ray_of, const float* __restrict__ times,
@@ -534,37 +573,17 @@ __global__ __launch_bounds__(256) void actor_pair_positions_bwd_kernel(
   const int64_t i = sample_idx[p], ray = ray_sample_ray_of_row(r, ray_of, i);
   const int64_t iv = ray_sample_interval_of_row(r, ray, i);
   const int act = actor_idx[p];
-  PairFrame f;
-  pair_frame(a, act, times[ray], f);
-  const SamplePos g = sample_gaussian(r.o[3 * ray], r.o[3 * ray + 1], r.o[3 * ray + 2], r.d[3 * ray], r.d[3 * ray + 1],
-                                      r.d[3 * ray + 2], r.area[ray], r.starts[iv], r.ends[iv]);
   const float flip = ray_flip ? ray_flip[ray] : 1.f;
-  float pos[3];
-  pair_box_position(f, g, flip, pos);
-  // ---- contraction backward (spatial_distortions.py:126-141, order = inf): (g_x01, g_cstd) -> g_pos ----------------
-  float m[3] = {pos[0] / a.scale, pos[1] / a.scale, pos[2] / a.scale};
-  const float am[3] = {fabsf(m[0]), fabsf(m[1]), fabsf(m[2])};
-  const float mag = fmaxf(fmaxf(am[0], am[1]), am[2]);
-  float gm[3] = {g_x01[3 * p] / 4.f, g_x01[3 * p + 1] / 4.f, g_x01[3 * p + 2] / 4.f};  // x01 = (m' + 2) / 4
-  if (!(mag < 1.f)) {
-    // m' = k m, k = 2/mag - 1/mag^2;   cstd = (std/scale) q / 4, q = ((2 mag - 1)^(1/3) / mag)^2
-    const float k = 2.f / mag - 1.f / (mag * mag), dk = -2.f / (mag * mag) + 2.f / (mag * mag * mag);
-    const float cr = cbrtf(2.f * mag - 1.f), rr = cr / mag;
-    const float dq = 2.f * rr * ((2.f / 3.f) / (cr * cr * mag) - cr / (mag * mag));
-    const float g_mag = (gm[0] * m[0] + gm[1] * m[1] + gm[2] * m[2]) * dk + g_cstd[p] * (g.std / a.scale) * dq / 4.f;
-    inf_norm_bwd(m, am, mag, k, g_mag, gm);
-  }
-  float gpos[3] = {gm[0] / a.scale * flip, gm[1] / a.scale, gm[2] / a.scale};
+  PairFrame f;
+  SamplePos g;
+  float gpos[3], gt[3];
+  pair_position_grad(a, r, ray, iv, act, times[ray], flip, g_x01 + 3 * p, g_cstd + p, f, g, gpos, gt);
   // ---- pos_i = b1_i v_0 + b2_i v_1 + b3_i v_2,  v = mean - t ---------------------------------------------------------
   const float v[3] = {g.x - f.t[0], g.y - f.t[1], g.z - f.t[2]};
-  float gb1[3], gb2[3], gb3[3], gt[3];
+  float gb1[3], gb2[3], gb3[3];
   for (int c = 0; c < 3; ++c) gb1[c] = v[0] * gpos[c], gb2[c] = v[1] * gpos[c], gb3[c] = v[2] * gpos[c];
-  gt[0] = -dot3(f.b1, gpos), gt[1] = -dot3(f.b2, gpos), gt[2] = -dot3(f.b3, gpos);
   if (g_origins && live) {
-    // d pos / d mean = -d pos / d t: the sample's world position moves with the ray (camera optimizer,
-    // cameras/camera_optimizers.py:173-182); mean = o + d t_mid with t_mid a constant (detached bins)
-    const float t0 = r.starts[iv], t1 = r.ends[iv];
-    const float tm = t0 + (t1 - t0) / 2.f;
+    const float tm = pair_ray_t(r, iv);
     for (int c = 0; c < 3; ++c) {
       atomicAdd(g_origins + 3 * ray + c, -gt[c]);
       atomicAdd(g_directions + 3 * ray + c, -gt[c] * tm);
@@ -617,6 +636,73 @@ __global__ __launch_bounds__(256) void actor_pair_positions_bwd_kernel(
       }
     }
   }
+}
+
+// ---- the ray share of the pair backward on PACKED samples, without atomics ------------------------------------------------
+// The pairs come in (sample, slot) order and packed samples in ray order, so the pairs of ray r are ONE range of the list:
+// those whose sample lies in [segs[r], segs[r + 1]).  A group of G lanes (16 / 32 / 64) owns the ray: it finds the range by
+// a lower-bound search for its first pair and a galloping search from there for its end (most rays have no pair: one
+// load), lane `sub` adds the pairs sub, sub + G, ... of the range in that order, the group merges on an xor butterfly and
+// lane 0 WRITES the two rows.  A ray's rows depend on its own pairs and on G alone; a ray without samples or without pairs
+// writes zeros and loads nothing past its segment bounds / the search.  Sample indices are clamped into [0, M) and segment
+// bounds into [0, M] where they are read, and every search position lies in [0, P): a list that breaks its precondition
+// gives wrong sums, never a read outside the arrays.
+__device__ __forceinline__ int64_t pair_sample(const int64_t* __restrict__ sample_idx, int64_t p, int64_t M) {
+  const int64_t i = sample_idx[p];
+  return i < 0 ? 0 : (i < M ? i : M - 1);
+}
+
+// first p in [lo, hi) whose sample is >= v, or hi
+__device__ __forceinline__ int64_t pair_lower_bound(const int64_t* __restrict__ sample_idx, int64_t lo, int64_t hi,
+                                                    int64_t M, int64_t v) {
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (pair_sample(sample_idx, mid, M) < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void actor_pair_positions_bwd_rays_packed_kernel(
+    ActorsDev a, PackedRaysDev r, const float* __restrict__ times, const int64_t* __restrict__ sample_idx,
+    const int32_t* __restrict__ actor_idx, const float* __restrict__ ray_flip, int64_t n_pairs,
+    const float* __restrict__ g_x01, const float* __restrict__ g_cstd, int G, float* __restrict__ g_origins,
+    float* __restrict__ g_directions) {
+  const int sub = threadIdx.x & (G - 1);
+  const int64_t ray = ((int64_t)blockIdx.x * 256 + threadIdx.x) / G;
+  const bool live_ray = ray < r.R;
+  float ao[3] = {0.f, 0.f, 0.f}, ad[3] = {0.f, 0.f, 0.f};
+  if (live_ray) {
+    const int64_t M = r.M;
+    int64_t s0 = r.segs[ray], s1 = r.segs[ray + 1];
+    s0 = s0 < 0 ? 0 : (s0 < M ? s0 : M), s1 = s1 < 0 ? 0 : (s1 < M ? s1 : M);
+    if (s0 < s1) {  // (a ray without samples has no pair)
+      const int64_t p0 = pair_lower_bound(sample_idx, 0, n_pairs, M, s0);
+      // the end of the range, galloping from p0: every pair before lo is the ray's, the pair at hi (or the list's end) is not
+      int64_t lo = p0, hi = p0, step = 1;
+      while (hi < n_pairs && pair_sample(sample_idx, hi, M) < s1) lo = hi + 1, hi += step, step <<= 1;
+      const int64_t p1 = pair_lower_bound(sample_idx, lo, hi < n_pairs ? hi : n_pairs, M, s1);
+      if (p0 < p1) {
+        const float q = times[ray], flip = ray_flip ? ray_flip[ray] : 1.f;
+        for (int64_t p = p0 + sub; p < p1; p += G) {
+          const int64_t iv = pair_sample(sample_idx, p, M);
+          PairFrame f;
+          SamplePos g;
+          float gpos[3], gt[3];
+          pair_position_grad(a, r, ray, iv, actor_idx[p], q, flip, g_x01 + 3 * p, g_cstd + p, f, g, gpos, gt);
+          const float tm = pair_ray_t(r, iv);
+          for (int c = 0; c < 3; ++c) ao[c] += -gt[c], ad[c] += -gt[c] * tm;
+        }
+      }
+    }
+  }
+  for (int off = 1; off < G; off <<= 1)
+    for (int c = 0; c < 3; ++c) {
+      ao[c] += __shfl_xor(ao[c], off, 64);
+      ad[c] += __shfl_xor(ad[c], off, 64);
+    }
+  if (live_ray && sub == 0)
+    for (int c = 0; c < 3; ++c) g_origins[3 * ray + c] = ao[c], g_directions[3 * ray + c] = ad[c];
 }
 
 // ---- proposal density of the in-box samples, training (fields/neurad_field.py:208-213 with neurad_encoding.py:150-187) ----
@@ -676,7 +762,8 @@ __global__ __launch_bounds__(256) void actor_density_splice_bwd_kernel(
 
 // The pair kernels' entry points, once over the two sample layouts.  Dense (nrhip_rays): sample_idx is a row ray * S + s,
 // no ray_of.  Packed (nrhip_packed_rays): sample_idx is a packed sample index, ray_of [M] names its ray; times / ray_flip
-// stay per ray.  The same kernel bodies; no gradient to the rays on packed samples.
+// stay per ray.  The same kernel bodies; on packed samples the rays' gradient has an entry point and a kernel of its own
+// (nrhip_actor_pair_positions_bwd_rays_packed: a group of lanes per ray, no atomics).
 static int validate_pair_rays(const char*, const nrhip_rays* r) { return validate_rays(r); }
 static int validate_pair_rays(const char* who, const nrhip_packed_rays* r) { return validate_packed_rays(who, r, false); }
 
@@ -754,6 +841,39 @@ extern "C" int nrhip_actor_pair_positions_bwd_packed(const nrhip_actors* a, cons
   return pair_positions<PairOp::Bwd>("actor_pair_positions_bwd_packed", a, rays, ray_of, times, sample_idx, actor_idx,
                                      ray_flip, n_pairs, grad_x01, grad_cstd, grad_positions, grad_rotations_6d, nullptr,
                                      nullptr, stream);
+}
+
+extern "C" int nrhip_actor_pair_positions_bwd_rays_packed(const nrhip_actors* a, const nrhip_packed_rays* rays,
+                                                          const float* times, const int64_t* sample_idx,
+                                                          const int32_t* actor_idx, const float* ray_flip, int64_t n_pairs,
+                                                          const float* grad_x01, const float* grad_cstd,
+                                                          int32_t lanes_per_ray, float* grad_origins,
+                                                          float* grad_directions, void* stream) {
+  const char* who = "actor_pair_positions_bwd_rays_packed";
+  ActorsDev d;
+  if (int e = to_dev(a, d)) return e;
+  if (int e = validate_packed_rays(who, rays, true)) return e;
+  NR_REQUIRE(n_pairs >= 0 && a->actor_scale > 0.f, NRHIP_ERR_INVALID_ARG, "%s: bad argument", who);
+  NR_REQUIRE(lanes_per_ray == 0 || lanes_per_ray == 16 || lanes_per_ray == 32 || lanes_per_ray == 64, NRHIP_ERR_INVALID_ARG,
+             "%s: lanes_per_ray %d not in {0, 16, 32, 64}", who, lanes_per_ray);
+  const int64_t R = rays->n_rays, M = rays->n_samples;
+  NR_REQUIRE(n_pairs == 0 || (R >= 1 && M >= 1), NRHIP_ERR_INVALID_ARG, "%s: pairs of a batch without samples", who);
+  if (R == 0) return NRHIP_OK;
+  NR_REQUIRE(grad_origins && grad_directions, NRHIP_ERR_INVALID_ARG, "%s: NULL pointer (output)", who);
+  const hipStream_t st = (hipStream_t)stream;
+  if (n_pairs == 0) {  // no ray has a pair: two blocks of zeros, no launch
+    const size_t bytes = (size_t)R * 3 * sizeof(float);
+    if (hipMemsetAsync(grad_origins, 0, bytes, st) != hipSuccess || hipMemsetAsync(grad_directions, 0, bytes, st) != hipSuccess)
+      return check_launch(who);
+    return NRHIP_OK;
+  }
+  NR_REQUIRE(times && sample_idx && actor_idx && grad_x01 && grad_cstd, NRHIP_ERR_INVALID_ARG, "%s: NULL pointer", who);
+  // the dense rule of nrhip_encode_bwd_rays on the MEAN pair count P / R (both are shapes: no device read)
+  const int G = lanes_per_ray ? lanes_per_ray : (n_pairs > 32 * R ? 64 : (n_pairs > 16 * R ? 32 : 16));
+  actor_pair_positions_bwd_rays_packed_kernel<<<grid_for(R * G, 256), 256, 0, st>>>(
+      d, to_dev(*rays), times, sample_idx, actor_idx, ray_flip, n_pairs, grad_x01, grad_cstd, G, grad_origins,
+      grad_directions);
+  return check_launch(who);
 }
 
 // ---- the (sample, actor) pairs of a hits table, in order, without torch's nonzero -----------------------------------------

@@ -222,7 +222,8 @@ class NeuRADHashEncoding(nn.Module):
         return any(gr.hash_table.requires_grad for gr in self.actor_grids) or (
             self.config.require_actor_grad and self.actors.actor_positions.requires_grad)
 
-    def actor_pair_rows(self, hit, hits, origins, directions, pixel_area, starts, ends, times, flip, ray_indices=None):
+    def actor_pair_rows(self, hit, hits, origins, directions, pixel_area, starts, ends, times, flip, ray_indices=None,
+                        segments=None):
         """Training path of the actor rows (B1): the kernels found WHICH samples lie in WHICH actor; the few hit rows
         are recomputed differentiably -- box-frame position through nrhip_actor_pair_positions_fwd/bwd (gradient to the
         trajectories when ``require_actor_grad``), the actor grids through MultiHashGridFn (table scatter-add, and
@@ -230,7 +231,9 @@ class NeuRADHashEncoding(nn.Module):
         forward kernels used for that sample (highest index), rows [P, La*Fa] rescaled actor features).
         ``ray_indices`` int64 [M]: the samples are PACKED (an occupancy march's output) -- starts / ends are t_starts /
         t_ends [M], hit [M] and hits [M,8] and the returned idx are at the packed sample index, times [R] and flip [R] stay
-        per ray (nrhip_actor_pair_positions_fwd_packed / _bwd_packed); everything else is the same."""
+        per ray (nrhip_actor_pair_positions_fwd_packed / _bwd_packed); everything else is the same.  ``segments`` int64 [R+1]
+        of the packed samples: needed only when the rays require grad -- under ``require_actor_grad``, as on dense samples,
+        the in-box samples then hand them their share (nrhip_actor_pair_positions_bwd_rays_packed)."""
         if self.actor_edit() is not None:
             # the differentiable rows are recomputed from the trajectories themselves (nrhip_actor_pair_positions_*), which
             # know nothing of the edit; the reference edits for rendering only (pipelines/ad_pipeline.py:476-480)
@@ -247,7 +250,8 @@ class NeuRADHashEncoding(nn.Module):
         with torch.set_grad_enabled(pose_grad):
             x01, cstd = ag.ActorPairPositionsFn.apply(self.actors.actor_positions, self.actors.actor_rotations_6d, spec,
                                                       origins, directions, pixel_area.reshape(-1), starts, ends, times,
-                                                      idx, act, flip, *(() if ray_indices is None else (ray_indices,)))
+                                                      idx, act, flip, *(() if ray_indices is None else (ray_indices,)),
+                                                      *(() if ray_indices is None or segments is None else (segments,)))
         act = act.long()
         ids = self.actors.actor_to_id[act]
         # _get_actor_features_slow loops over the actor ids; all actor grids share one shape, so one multi-grid

@@ -308,7 +308,8 @@ class NeuRADField(nn.Module):
 
     def render_train_packed(self, origins, directions, pixel_area, t_starts, t_ends, *, segments: Optional[Tensor] = None,
                             ray_indices: Optional[Tensor] = None, num_rays: Optional[int] = None,
-                            ray_gradients: bool = False, times: Optional[Tensor] = None, actor_cand=None):
+                            ray_gradients: bool = False, times: Optional[Tensor] = None, actor_cand=None,
+                            actor_ray_gradients: bool = False):
         """Training counterpart of ``render_packed``: field -> head (learnable-beta SDF head, or trunc_exp) -> packed
         compositing as ONE autograd node (autograd.NffRenderTrainFn on autograd.PackedSamples).  Arguments as ``render_packed``: per-RAY origins
         / directions [R,3] and pixel_area [R] (or [R,1]), per-sample t_starts / t_ends [M], exactly one of ``segments`` int64
@@ -329,9 +330,13 @@ class NeuRADField(nn.Module):
         trajectories.  If no sample lies in a box the call is the static node, bit for bit.  The training x-flip is drawn
         once per RAY (``sample_ray_flip``: R draws), as the dense node draws it; the operator route on packed samples draws
         it per sample, so for 0 < flip_prob < 1 the two routes flip different samples by design.  With actors, rays that
-        require grad are refused even under ``ray_gradients=True``: the actor branch's ray gradient is not built on packed
-        samples.  Without ``times`` / ``actor_cand`` an actor field is refused as before.  One host read (the number of
-        pairs): not graph-capturable, like the dense actor node."""
+        require grad are refused by default, and ``ray_gradients=True`` does not change that; ``actor_ray_gradients=True``
+        opts in: the node then returns dL/d origins and dL/d directions as the sum of two shares, the static encoding's
+        (nrhip_encode_bwd_rays_packed on the rows no actor overrides) and, under ``require_actor_grad`` as on dense samples,
+        the in-box samples' (nrhip_actor_pair_positions_bwd_rays_packed through ActorPairPositionsFn), both without
+        atomics.  Without actors, or with fixed rays, that flag changes nothing.  Without ``times`` / ``actor_cand`` an
+        actor field is refused as before.  One host read (the number of pairs): not graph-capturable, like the dense actor
+        node."""
         self._check_packed_args("render_train_packed", segments, ray_indices, num_rays)
         operator = "use the operator route, forward() on the packed RaySamples + renderers.render_packed"
         hg = self.hashgrid
@@ -340,7 +345,7 @@ class NeuRADField(nn.Module):
             if not self.fused_packed_actors_train_supported():
                 raise NotImplementedError(f"render_train_packed with dynamic actors: a fused-kernel configuration with "
                                           f"actors only (see fused_packed_actors_train_supported); {operator}")
-            if torch.is_grad_enabled() and (origins.requires_grad or directions.requires_grad):
+            if not actor_ray_gradients and torch.is_grad_enabled() and (origins.requires_grad or directions.requires_grad):
                 raise NotImplementedError(f"render_train_packed with dynamic actors: no gradient reaches the rays through the "
                                           f"actor branch on packed samples; {operator}")
         else:
@@ -409,7 +414,7 @@ class NeuRADField(nn.Module):
             spec, cand = self._actor_cand(actor_cand, origins, directions, times, samples.cand_samples(pixel_area))
             hits, hit, dirs = samples.actor_geometry(spec, cand, origins, directions, pixel_area, flip, hg.get_out_dim())
         pr = hg.actor_pair_rows(hit, hits, origins, directions, pixel_area, samples.starts, samples.ends, times, flip,
-                                ray_indices=samples.ray_indices)
+                                ray_indices=samples.ray_indices, segments=samples.segments)
         if pr is None:
             return None
         idx, winner, f = pr

@@ -306,7 +306,7 @@ class VolumetricSampler(Sampler):
     def render_train(self, field, ray_bundle: RayBundle, render_step_size: float, near_plane: float = 0.0,
                      far_plane: Optional[float] = None, alpha_thre: float = 0.01, cone_angle: float = 0.0,
                      fused_ray_gradients: bool = False, actor_boxes: bool = False,
-                     fused_actor_training: bool = False) -> dict:
+                     fused_actor_training: bool = False, fused_actor_ray_gradients: bool = False) -> dict:
         """Training counterpart of ``render``: a stratified march + field + compositing with autograd -> the same keys.  A
         field that trains on packed samples as one node (``fused_packed_train_supported``, ``fused_training`` on) gets the
         BUNDLE'S per-ray tensors and the packed intervals (``render_train_packed``: no per-sample copy of origins /
@@ -319,14 +319,19 @@ class VolumetricSampler(Sampler):
         off) with ``actor_boxes=True`` hands the march's candidate lists on to the fused training node with actors
         (``render_train_packed(..., times=..., actor_cand=...)``: one computation serves march and node) when the field has
         one (``fused_packed_actors_train_supported``), ``fused_training`` is on and the rays are fixed; anything else takes
-        the operator route as before.  The node draws the training x-flip once per ray, the operator route once per sample."""
+        the operator route as before.  ``fused_actor_ray_gradients=True`` (opt-in, default off) lifts the last of those
+        conditions: with everything else as above, rays that require grad stay on the node with actors, which returns their
+        gradients itself (``render_train_packed(..., actor_ray_gradients=True)``); without it, or with any other condition
+        unmet, the call routes exactly as before.  The node draws the training x-flip once per ray, the operator route once
+        per sample."""
         def fused(boxes, rays_o, rays_d):
             rays_need_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
             if not getattr(field, "fused_training", False):
                 return None
-            if (fused_actor_training and boxes is not None and not rays_need_grad
+            if (fused_actor_training and boxes is not None and (fused_actor_ray_gradients or not rays_need_grad)
                     and _gate(field, "fused_packed_actors_train_supported")):
-                return field.render_train_packed, {"times": ray_bundle.times.reshape(-1).float(), "actor_cand": boxes[1]}
+                return field.render_train_packed, {"times": ray_bundle.times.reshape(-1).float(), "actor_cand": boxes[1],
+                                                   **({"actor_ray_gradients": True} if rays_need_grad else {})}
             if (fused_ray_gradients or not rays_need_grad) and _gate(field, "fused_packed_train_supported"):
                 return field.render_train_packed, ({"ray_gradients": True} if rays_need_grad else {})
             return None

@@ -1603,7 +1603,7 @@ def actor_pair_positions_packed(spec: "ActorSpec", origins, directions, pixel_ar
 def actor_pair_positions_packed_bwd(spec: "ActorSpec", origins, directions, pixel_area, t_starts, t_ends, ray_indices, times,
                                     sample_idx, actor_idx, ray_flip, grad_x01: Tensor, grad_cstd: Tensor):
     """-> (grad actor_positions [Tn,A,3], grad actor_rotations_6d [Tn,A,6]), accumulated with atomics as
-    ``actor_pair_positions_bwd``; the rays get no gradient on this path"""
+    ``actor_pair_positions_bwd``; the rays' gradient is ``actor_pair_positions_packed_bwd_rays``"""
     a, r, ri, t, si, ai, flip = _packed_pair_args("actor_pair_positions_packed_bwd", spec, origins, directions, pixel_area,
                                                   t_starts, t_ends, ray_indices, times, sample_idx, actor_idx, ray_flip)
     flat = torch.zeros((a.n_times * a.n_actors * 9,), dtype=torch.float32, device=si.device)
@@ -1612,6 +1612,31 @@ def actor_pair_positions_packed_bwd(spec: "ActorSpec", origins, directions, pixe
     launch("nrhip_actor_pair_positions_bwd_packed", a, r, ri, t, si, ai, flip, si.shape[0], _chk(grad_x01, "grad_x01"),
            _chk(grad_cstd, "grad_cstd"), gp, gr)
     return gp, gr
+
+
+def actor_pair_positions_packed_bwd_rays(spec: "ActorSpec", origins, directions, pixel_area, t_starts, t_ends, segments, times,
+                                         sample_idx, actor_idx, ray_flip, grad_x01: Tensor, grad_cstd: Tensor,
+                                         lanes_per_ray: int = 0) -> Tuple[Tensor, Tensor]:
+    """The ray share of ``actor_pair_positions_bwd(..., ray_grads=True)`` on packed samples: -> (dL/d origins, dL/d
+    directions) [R,3] of the in-box samples.  segments int64 [R+1] bounds each ray's samples; sample_idx [P] int64 is a packed
+    sample index and NON-DECREASING (``actor_pairs``' order), times / ray_flip are per ray.  One kernel, a group of lanes per
+    ray over the ray's range of the pair list, no atomics: bit-reproducible, a ray's rows depend on its own pairs and the
+    group size only; zeros for a ray without pairs.  lanes_per_ray: 16 / 32 / 64 forces the group size, 0 lets the library
+    choose it from the mean count P / R."""
+    who = "actor_pair_positions_packed_bwd_rays"
+    r, keep = _c_packed_rays(who, origins, directions, pixel_area, t_starts, t_ends, segments)
+    a, keep2 = spec.c_actors()
+    si, ai = _chk(sample_idx, "sample_idx", torch.int64), _chk(actor_idx, "actor_idx", torch.int32)
+    t, flip = _chk(times.reshape(-1), "times"), _opt(ray_flip, "ray_flip")
+    if t.shape[0] != r.n_rays or (flip is not None and flip.shape[0] != r.n_rays) or ai.shape != si.shape or si.dim() != 1:
+        raise ValueError(f"{who}: times / ray_flip are per ray ([R = {r.n_rays}]), sample_idx / actor_idx [P]")
+    P_ = si.shape[0]
+    gx, gc = _chk(grad_x01, "grad_x01"), _chk(grad_cstd, "grad_cstd")
+    if gx.numel() != 3 * P_ or gc.numel() != P_:
+        raise ValueError(f"{who}: grad_x01 [P,3] and grad_cstd [P] with P = {P_}")
+    out = torch.empty((2, r.n_rays, 3), device=keep[0].device, dtype=torch.float32)
+    launch("nrhip_actor_pair_positions_bwd_rays_packed", a, r, t, si, ai, flip, P_, gx, gc, int(lanes_per_ray), out[0], out[1])
+    return out[0], out[1]
 
 
 def sdf_render_packed_fwd(geo_out, beta: Optional[Tensor], beta_min: float, features, t_starts, t_ends, segments):

@@ -22,7 +22,17 @@ trajectories):
   (b) the operator route on the same samples: gathers, the field with actors on [M,1], the torch head, renderers.render_packed
       (what VolumetricSampler.render_train(..., actor_boxes=True) does by default; it computes its own per-sample lists).
 The line's "bench" is "render_train_packed_actors".  No ratio is promised.
-    python scripts/bench_render_train_packed.py [--ray-grads | --actors] [--reps 100] [--warmup 10] [--out profiles/bench_render_train_packed.jsonl]"""
+--actors --ray-grads: the same scene and the same two routes with origins and directions that REQUIRE GRAD, their two
+gradients added to what each step computes: (a) is the node with actor_ray_gradients=True (the static share from
+nrhip_encode_bwd_rays_packed, the in-box samples' from nrhip_actor_pair_positions_bwd_rays_packed), (b) the operator route
+with the same moving rays (what VolumetricSampler.render_train takes for them by default).  The line's "bench" is
+"render_train_packed_actors_ray_grads".  No ratio is promised.
+--actors --pair-kernels: no timing of its own -- the pair backward of the scene's pairs, 20 launches each, for ONE kernel
+trace (rocprofv3 --kernel-trace --stats -- python scripts/bench_render_train_packed.py --actors --pair-kernels): the new
+kernel actor_pair_positions_bwd_rays_packed_kernel; actor_pair_positions_bwd_kernel<PackedRaysDev>, the trajectory gradients
+that stay beside it; and actor_pair_positions_bwd_kernel<RaysDev> with ray gradients on the same pairs laid out as the
+operator route lays them out ([M,1] rays), the dense atomic kernel that does both.  Prints the pair count; writes no line.
+    python scripts/bench_render_train_packed.py [--ray-grads] [--actors [--pair-kernels]] [--reps 100] [--warmup 10] [--out profiles/bench_render_train_packed.jsonl]"""
 import argparse
 import json
 import os
@@ -98,16 +108,25 @@ def main_actors(args):
     fld.train()
     fld.hashgrid.config.actor.flip_prob = 0.0
     assert fld.fused_packed_actors_train_supported()
+    if args.pair_kernels:
+        return pair_kernels(fld, o, d, area, times, cand, ri, ts, te, seg)
+    node_kw = {}
+    if args.ray_grads:
+        o, d = o.clone().requires_grad_(True), d.clone().requires_grad_(True)
+        node_kw = {"actor_ray_gradients": True}
     rb = RayBundle(origins=o, directions=d, pixel_area=area, times=times[:, None])
     cot = [torch.randn(s, generator=sc["gen"]).cuda() for s in ((rays, 32), (rays, 1), (rays, 1), (M,))]
     named = [(n, p) for n, p in fld.named_parameters() if p.requires_grad]
     names, params = [n for n, _ in named], [p for _, p in named]
+    if args.ray_grads:
+        names, params = names + ["origins", "directions"], params + [o, d]
 
     def loss_of(outs):
         return sum((t.reshape(c.shape) * c).sum() for t, c in zip(outs, cot))
 
     def route_a():
-        outs = fld.render_train_packed(o, d, area, ts, te, ray_indices=ri, num_rays=rays, times=times, actor_cand=cand)
+        outs = fld.render_train_packed(o, d, area, ts, te, ray_indices=ri, num_rays=rays, times=times, actor_cand=cand,
+                                       **node_kw)
         return outs, torch.autograd.grad(loss_of(outs), params, allow_unused=True)
 
     def route_b():
@@ -135,7 +154,8 @@ def main_actors(args):
     med = {k: median(v) for k, v in lap.items()}
     acfg = sc["cfg"].grid.actor
     line = {
-        "bench": "render_train_packed_actors", "field": "neurad_default_8x4_h32", "levels": L, "features_per_level": F,
+        "bench": "render_train_packed_actors" + ("_ray_grads" if args.ray_grads else ""),
+        "field": "neurad_default_8x4_h32", "levels": L, "features_per_level": F,
         "hidden": H, "head": "sdf", "log2_table": BP.LOG2_T, "table_dtype": "fp32", "actors": int(sc["actors"].n_actors),
         "actor_grid": [acfg.num_levels, acfg.hashgrid_dim, acfg.log2_hashmap_size], "flip_prob": 0.0,
         "rays": rays, "grid": BP.RES, "step": BP.STEP, "M": M, "M_plain_march": sc["plain_m"],
@@ -155,19 +175,42 @@ def main_actors(args):
     print(json.dumps(line))
 
 
+def pair_kernels(fld, o, d, area, times, cand, ri, ts, te, seg, launches=20):
+    """the three pair-backward kernels on the scene's pairs, for a kernel trace (see the module docstring)"""
+    from neurad_studio_amd import ops
+
+    hg = fld.hashgrid
+    spec = hg.actor_spec()
+    a = area.reshape(-1)
+    with torch.no_grad():
+        hits = ops.actor_find_packed(spec, cand, o, d, a, ts, te, ri)[0]
+        si, ai = ops.actor_pairs(hits)
+        P = int(si.shape[0])
+        gen = torch.Generator().manual_seed(3)
+        gx, gc = torch.randn((P, 3), generator=gen).cuda(), torch.randn((P,), generator=gen).cuda()
+        og, dg, ag, tg = o[ri], d[ri], a[ri], times[ri]  # the operator route's layout: every sample a ray of one sample
+        for _ in range(launches):
+            ops.actor_pair_positions_packed_bwd_rays(spec, o, d, a, ts, te, seg, times, si, ai, None, gx, gc)
+            ops.actor_pair_positions_packed_bwd(spec, o, d, a, ts, te, ri, times, si, ai, None, gx, gc)
+            ops.actor_pair_positions_bwd(spec, og, dg, ag, ts[:, None], te[:, None], tg, si, ai, None, gx, gc, ray_grads=True)
+        torch.cuda.synchronize()
+    print(json.dumps({"pair_kernels": {"pairs": P, "rays": int(o.shape[0]), "M": int(ri.shape[0]), "launches": launches}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--ray-grads", action="store_true", help="rays that require grad: the opt-in node against the fallback")
     ap.add_argument("--actors", action="store_true", help="the fused node with dynamic actors against the operator route")
+    ap.add_argument("--pair-kernels", action="store_true", help="with --actors: launch the pair-backward kernels for a kernel trace")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_render_train_packed.jsonl"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_render_train_packed: no GPU")
+    if args.pair_kernels and not args.actors:
+        raise SystemExit("bench_render_train_packed: --pair-kernels needs --actors")
     if args.actors:
-        if args.ray_grads:
-            raise SystemExit("bench_render_train_packed: --actors and --ray-grads do not combine (the node refuses both)")
         return main_actors(args)
     from bench import device_state
 
