@@ -11,8 +11,19 @@
 // norms) and, with distortion, ten Newton iterations of ~60 ops each over a [3,R,2] stack.  Here one thread produces one
 // ray: the sensor row is a handful of broadcast loads (rays of a 32x32 patch share one camera; lidar points of a scan
 // share one lidar), the Newton solve of the pixel and its two neighbours stays in registers, outputs go out as whole
-// [R,3] / [R,1] rows.  Arithmetic mirrors torch op for op (separately rounded mul/add/div: -ffp-contract=off) so that
-// directions agree to the ulp -- a ray's direction feeds floor() in every hash-grid level downstream.
+// [R,3] / [R,1] rows.
+//
+// What is mirrored, and how that was established.  A ray's direction feeds floor() in every hash-grid level downstream, so
+// the perspective and lidar kernels reproduce the BITS of the reference's fp32 CPU run (tests/golden/raygen.npz, made by
+// oracle/make_golden_raygen.py): origins, times, directions, norms and lidar pixel areas on every ray of the fixture,
+// camera pixel areas to 2 ulp (bit-equal on 99 % of rays; the rest is the order torch's sum takes over a 3-element inner
+// dimension).  Every product, sum and quotient is rounded on its own (-ffp-contract=off; the divide and sqrtf are the
+// correctly rounded ones), in the order torch applies them, with ONE exception found by comparing candidate roundings with
+// that fixture: torch.linalg.vector_norm's CPU kernel accumulates the squares as an FMA chain (norm3 below).  The
+// separately rounded form sat 1-2 ulp off on ~6 % of camera and ~12 % of lidar rays.  tests/raygen_refs.py restates the
+// kernels in numpy float32 and is pinned to the fixture (tests/test_raygen_refs_host.py); tests/test_gpu_raygen_exact.py
+// holds the kernels to it bit for bit.  The reference's GPU-side vector_norm has not been compared: nobody has measured
+// how it rounds.  The lens kernel shares finish_camera_ray, but its sinf / cosf are bounded against a float64 run instead.
 //
 // Mirrored, not repaired: a FISHEYE ray exactly at the principal point has theta = 0, where the reference's
 // (u * sin theta) / theta is 0 * 0 / 0 = NaN (cameras.py:809-814).  Its direction and directions_norm are NaN, and so is
@@ -38,12 +49,14 @@ __device__ __forceinline__ Vec3 rotate(const float* __restrict__ m /*3x4 row maj
   return o;
 }
 
-// kNanNorm: a NaN norm stays NaN, as in torch.maximum (camera_utils.py:607); fmaxf returns the epsilon for it
-template <bool kNanNorm = false>
+// torch.maximum(torch.linalg.vector_norm(v, dim=-1), _EPS) (camera_utils.py:596-608, cameras and lidars alike).  The sum
+// of squares is the single-rounded FMA chain of vector_norm's CPU kernel, established from the CPU-made fixture (see the
+// header); the explicit fmaf is the wanted contraction under contract(off).  A NaN norm stays NaN, as torch.maximum keeps
+// it: fmaxf would return the epsilon, and a lidar point with a NaN coordinate would come out as a return at distance 9e-16.
 __device__ __forceinline__ float norm3(Vec3 v) {
 #pragma clang fp contract(off)
-  const float n = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);
-  return kNanNorm ? (n < kNormEps ? kNormEps : n) : fmaxf(n, kNormEps);
+  const float n = sqrtf(fmaf(v.z, v.z, fmaf(v.y, v.y, v.x * v.x)));
+  return n < kNormEps ? kNormEps : n;
 }
 
 struct CameraTable {
@@ -63,7 +76,6 @@ struct CameraTable {
 
 // From the camera-frame directions of a pixel (d0) and of its +1 x / +1 y neighbours (d1, d2) to the ray: rotation into
 // the world, normalisation, pixel area, rolling-shutter origin and time (cameras.py:900-960).
-template <bool kNanNorm>
 __device__ __forceinline__ void finish_camera_ray(const CameraTable& t, int64_t c, int64_t i, float x, float y, Vec3 d0,
                                                   Vec3 d1, Vec3 d2, float* __restrict__ origins,
                                                   float* __restrict__ directions, float* __restrict__ pixel_area,
@@ -71,12 +83,13 @@ __device__ __forceinline__ void finish_camera_ray(const CameraTable& t, int64_t 
 #pragma clang fp contract(off)
   const float* m = t.c2w + 12 * c;
   d0 = rotate(m, d0.x, d0.y, d0.z), d1 = rotate(m, d1.x, d1.y, d1.z), d2 = rotate(m, d2.x, d2.y, d2.z);
-  const float n0 = norm3<kNanNorm>(d0), n1 = norm3<kNanNorm>(d1), n2 = norm3<kNanNorm>(d2);
+  const float n0 = norm3(d0), n1 = norm3(d1), n2 = norm3(d2);
   d0.x /= n0, d0.y /= n0, d0.z /= n0;
   d1.x /= n1, d1.y /= n1, d1.z /= n1;
   d2.x /= n2, d2.y /= n2, d2.z /= n2;
   const float ax = d0.x - d1.x, ay = d0.y - d1.y, az = d0.z - d1.z;
   const float bx = d0.x - d2.x, by = d0.y - d2.y, bz = d0.z - d2.z;
+  // torch.sqrt(torch.sum(a ** 2, dim=-1)): separately rounded, left to right -- not vector_norm, and not its FMA chain
   const float dx = sqrtf((ax * ax + ay * ay) + az * az), dy = sqrtf((bx * bx + by * by) + bz * bz);
   float ox = m[3], oy = m[7], oz = m[11];
   float tm = t.times ? t.times[c] : 0.f;
@@ -108,8 +121,8 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(CameraTable t, const i
   // image-plane coordinates and the two neighbours one pixel away (cameras.py:631-633), OpenCV -> OpenGL (:668)
   const float u0 = (x - cx) / fx, u1 = ((x - cx) + 1.f) / fx;
   const float v0 = -((y - cy) / fy), v1 = -(((y - cy) + 1.f) / fy);
-  finish_camera_ray<false>(t, c, i, x, y, {u0, v0, -1.f}, {u1, v0, -1.f}, {u0, v1, -1.f}, origins, directions, pixel_area,
-                           dir_norm, times);
+  finish_camera_ray(t, c, i, x, y, {u0, v0, -1.f}, {u1, v0, -1.f}, {u0, v1, -1.f}, origins, directions, pixel_area,
+                    dir_norm, times);
 }
 
 // ---- lens distortion and the fisheye model ----------------------------------------------------------------------------
@@ -179,8 +192,8 @@ __global__ __launch_bounds__(256) void camera_rays_lens_kernel(CameraTable t, co
     if (k[0] != 0.f || k[1] != 0.f || k[2] != 0.f || k[3] != 0.f || k[4] != 0.f || k[5] != 0.f)
       for (int j = 0; j < 3; ++j) undistort(k, u[j], v[j]);
   }
-  finish_camera_ray<true>(t, c, i, x, y, camera_direction<kType>(u[0], v[0]), camera_direction<kType>(u[1], v[1]),
-                          camera_direction<kType>(u[2], v[2]), origins, directions, pixel_area, dir_norm, times);
+  finish_camera_ray(t, c, i, x, y, camera_direction<kType>(u[0], v[0]), camera_direction<kType>(u[1], v[1]),
+                    camera_direction<kType>(u[2], v[2]), origins, directions, pixel_area, dir_norm, times);
 }
 
 struct LidarTable {

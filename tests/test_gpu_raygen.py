@@ -1,5 +1,9 @@
 """Device ray generation (csrc/raygen.hip) against the reference's own generators
-(tests/golden/raygen.npz from Cameras.generate_rays / Lidars.generate_rays, oracle/make_golden_raygen.py)."""
+(tests/golden/raygen.npz from Cameras.generate_rays / Lidars.generate_rays, oracle/make_golden_raygen.py).
+
+The perspective and lidar kernels reproduce the fixture's bits (tests/raygen_refs.py restates them and
+tests/test_raygen_refs_host.py pins the restatement to this fixture); only the camera pixel area is allowed 2 ulp, which is
+what the restatement itself is from the fixture on 5 of 512 rays.  The earlier, wider bounds stand next to the exact ones."""
 import types
 
 import numpy as np
@@ -7,6 +11,7 @@ import pytest
 import torch
 
 from conftest import load_golden, rel_l2
+from raygen_refs import ulps
 from gpu_util import cuda, host
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +38,10 @@ def test_camera_rays_vs_reference(mode):
     assert rel_l2(host(rb.pixel_area), g[f"cam_{mode}_pixel_area"]) < 2e-4  # a difference of nearly equal unit vectors
     assert np.abs(host(rb.times) - g[f"cam_{mode}_times"]).max() < 1e-6
     assert rel_l2(host(rb.metadata["directions_norm"]), g[f"cam_{mode}_directions_norm"]) < 1e-6
+    for got, q in ((rb.directions, "directions"), (rb.origins, "origins"), (rb.times, "times"),
+                   (rb.metadata["directions_norm"], "directions_norm")):
+        np.testing.assert_array_equal(host(got), g[f"cam_{mode}_{q}"].reshape(got.shape), err_msg=q)
+    assert ulps(host(rb.pixel_area), g[f"cam_{mode}_pixel_area"].reshape(-1, 1)).max() <= 2
     assert torch.equal(rb.metadata["sensor_idxs"][:, 0], cuda(g["cam_idx"])) and "rolling_shutter_time" not in rb.metadata
     assert float(rb.fars.min()) == 1_000_000.0 and rb.camera_indices.shape == (512, 1)
     cams.distortion_params = torch.ones((C, 6), device="cuda")
@@ -58,6 +67,9 @@ def test_lidar_rays_vs_reference(ego):
     np.testing.assert_array_equal(host(rb.metadata["did_return"]), g[f"lid_{tag}_did_return"])
     assert not bool(rb.metadata["did_return"].all()) and bool(rb.metadata["is_lidar"].all())
     assert np.abs(host(rb.times) - g[f"lid_{tag}_times"]).max() < 1e-6
+    for got, q in ((rb.directions, "directions"), (rb.origins, "origins"), (rb.times, "times"), (rb.pixel_area, "pixel_area"),
+                   (rb.metadata["directions_norm"], "distance")):
+        np.testing.assert_array_equal(host(got), g[f"lid_{tag}_{q}"].reshape(got.shape), err_msg=q)
     # the generated bundle drives the hot path as is
     from neurad_studio_amd import ops
 
