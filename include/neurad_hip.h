@@ -1007,6 +1007,43 @@ int nrhip_chamfer_distance(const float* source, int32_t stride_s, const uint8_t*
                            int32_t normalize_with_target, int32_t plan, float* result, float* source_sq_dist,
                            float* target_sq_dist, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- median (quantile) depth (csrc/median_depth.hip): DepthRenderer(method="median"), model_components/renderers.py:353-397,
+ *      for dense samples and -- what the reference does not have (renderers.py:390-391 raises) -- for packed ones ------------
+ * THE CONTRACT.  For a ray with samples 0..n-1, fp32 weights w_i, a threshold q and midpoints mid_i = (start_i + end_i) / 2
+ * (fp32: one rounded add, then one multiplication by 0.5):
+ *   1. c_i = float32(sum_{j<=i} w_j): the sum taken in float64 in sample order and rounded to fp32 ONCE per i.  This is
+ *      what torch.cumsum gives on the CPU (fp32 accumulated in float64); it is not the sequential fp32 sum, and not the
+ *      fp32 parallel scan torch runs on a GPU.
+ *   2. k = the first i with !(c_i < q); none: k = n - 1 (the reference's searchsorted returns n and is clamped).
+ *   3. depth = mid_k, index = k.
+ * The kernels take the float64 prefix sums from a wave-level scan: for weights whose float64 partial sums are exact (e.g.
+ * multiples of 2^-24 below 2) every order of the additions gives the same c_i, and that is what the tests pin bit for bit;
+ * otherwise a c_i may differ from the sequential float64 sum by the last float64 bit before its rounding to fp32.
+ * What follows from the three rules, each on purpose:
+ *   - an exact tie c_i == q crosses at i (searchsorted's side="left");
+ *   - a +inf weight crosses where it stands;
+ *   - a NaN weight behind the crossing is never looked at;
+ *   - c_k itself NaN (a NaN weight at or before the crossing): depth = NaN, index = k, the sample of the first NaN sum -- a
+ *     NaN is kept.  DEVIATION from the reference: its binary search treats NaN as "less than" and lands on a sample that
+ *     depends on where the NaN sits (the last one even for a ray that crossed at sample 0); that is not reproduced;
+ *   - negative weights make c non-monotone: the linear rule above still defines the result (the reference's is undefined);
+ *   - packed only: a ray without samples gets depth 0 and index -1, what accumulate_along_rays gives such a ray.
+ * Interfaces.  weights / starts / ends: fp32 [R,S] contiguous, S >= 1 (dense), or [M] with segments int64 [R+1] as
+ * nrhip_packed_segments makes them (packed; M < 2^31; segments are clamped into [0, M], so broken ones read inside the
+ * arrays).  thresholds: k HOST floats, 1 <= k <= NRHIP_MEDIAN_MAX_THRESHOLDS, read during the call and handed to the
+ * kernel by value; each must be finite (else NRHIP_ERR_INVALID_ARG).  One pass over a ray serves all k.  out_depth fp32
+ * [R,k]; out_index int32 [R,k] or NULL.  r == 0 is a no-op that reads no device pointer; m == 0 reads no sample pointer.
+ * One wavefront per ray in chunks of 64 samples with a float64 carry, left as soon as every threshold has crossed; starts /
+ * ends are read at the crossing sample only.  No LDS, no atomics, no allocation, no host read: the same inputs give the
+ * same bits.  No gradient: the result is piecewise constant in the weights.                                            */
+#define NRHIP_MEDIAN_MAX_THRESHOLDS 8
+int nrhip_median_depth(const float* weights, const float* starts, const float* ends, int64_t r, int32_t s,
+                       const float* thresholds /*host [k]*/, int32_t k, float* out_depth /*[R,k]*/,
+                       int32_t* out_index /*[R,k] or NULL*/, void* stream);
+int nrhip_median_depth_packed(const float* weights, const float* t_starts, const float* t_ends, const int64_t* segments,
+                              int64_t r, int64_t m, const float* thresholds /*host [k]*/, int32_t k,
+                              float* out_depth /*[R,k]*/, int32_t* out_index /*[R,k] or NULL*/, void* stream);
+
 /* ---- camera image evaluation (csrc/image_eval.hip): PSNR and SSIM of NeuRADModel.get_image_metrics_and_images
  *      (models/neurad.py:265-266,585-586: torchmetrics' PeakSignalNoiseRatio(data_range=1.0) and
  *      structural_similarity_index_measure(preds, target) with its defaults) -----------------------------------------------

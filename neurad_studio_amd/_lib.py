@@ -123,6 +123,7 @@ class LidarTable(C.Structure):
 MAX_SAMPLE_CONTAINMENTS = 8  # NRHIP_MAX_SAMPLE_CONTAINMENTS
 GRAD_ROWS_PER_BLOCK = 256   # NRHIP_GRAD_ROWS_PER_BLOCK
 NEAREST_TILE = 1024         # NRHIP_NEAREST_TILE
+MEDIAN_MAX_THRESHOLDS = 8   # NRHIP_MEDIAN_MAX_THRESHOLDS
 VGG_IMAGE_CHANNELS = 16     # NRHIP_VGG_IMAGE_CHANNELS
 L1_ITEMS = 2048             # NRHIP_L1_ITEMS
 SSIM_TILE = 32              # NRHIP_SSIM_TILE
@@ -295,6 +296,8 @@ PROTOTYPES = {
     "nrhip_nearest_plan": [I64, I64, C.POINTER(I32), C.POINTER(I32)],
     "nrhip_chamfer_workspace": [I64, I64, C.POINTER(I64)],
     "nrhip_chamfer_distance": [P, I32, P, I64, P, I32, P, I64, I32, I32, P, P, P, P, I64, P],
+    "nrhip_median_depth": [P, P, P, I64, I32, C.POINTER(F32), I32, P, P, P],
+    "nrhip_median_depth_packed": [P, P, P, P, I64, I64, C.POINTER(F32), I32, P, P, P],
     "nrhip_image_metrics_workspace": [I32, I32, I32, C.POINTER(I64)],
     "nrhip_image_metrics": [P, P, I32, I32, I32, F32, P, P, I64, P, P],
     "nrhip_image_psnr": [P, P, I64, F32, P, P, P],

@@ -125,6 +125,7 @@ extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
 //      _bwd, nrhip_l1_feature_fwd / _bwd (+ _workspace), nrhip_vgg_stage_images, nrhip_vgg_image_grad
 //      additive, same number: camera image evaluation -- nrhip_image_metrics (+ _workspace), nrhip_image_psnr
 //      additive, same number: camera pose correction -- nrhip_pose_apply, nrhip_pose_apply_bwd (+ _workspace)
+//      additive, same number: median depth -- nrhip_median_depth, nrhip_median_depth_packed
 extern "C" int nrhip_version(void) { return 520; }
 
 extern "C" int nrhip_tuning_reload(void) {

@@ -5,7 +5,9 @@
 // each a round trip through the LDS crossbar, and these kernels are chains of such scans: the interlevel loss runs six
 // fp64 ones per ray).
 // The association of the sums differs from a Hillis-Steele scan only across rows (prefix = total of the rows below + in-row
-// prefix); every caller is an fp32 / fp64 sum or product with tolerances, none needs a particular association.
+// prefix); every caller is an fp32 / fp64 sum or product with tolerances, none needs a particular association.  The
+// float64 scan (incl<Add>(double): the DPP moves go as two 32-bit halves, common.h) also carries median_depth.hip, whose
+// prefix sums are pinned bit for bit on weights whose float64 partial sums are exact -- there every association agrees.
 #pragma once
 #include "common.h"  // dpp<CTRL>
 

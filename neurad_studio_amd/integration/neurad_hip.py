@@ -119,6 +119,13 @@ class NeuRADHipModelConfig(NeuRADModelConfig):
     cameras/raygen.py:lidar_rays, the lidar branch of get_image_metrics_and_images (models/neurad.py:589-620) runs as masked
     reductions plus the chamfer kernel (csrc/lidar_eval.hip) and reads its five scalars with one device->host transfer.
     False: the reference's own methods (torch ray generation, ~8 boolean-mask gathers, chunked torch.cdist)."""
+    median_depth: bool = False
+    """Eval outputs also carry ``median_depth`` [R,1] (csrc/median_depth.hip): the midpoint of the first non-sky sample at
+    which the accumulated weight reaches one half -- the reference's DepthRenderer("median") with its CPU numerics, one more
+    launch per eval chunk.  Only the fused eval route produces the key (``fused_eval``; training outputs do not have it).
+    With ``fused_lidar_eval`` a scan's outputs gain ``median_points`` and its metrics ``median_depth_median_l2``,
+    ``median_depth_mean_rel_l2`` and ``median_chamfer_distance`` (SplatAD's names), all eight scalars in the one transfer.
+    False: no key, launch or host read changes."""
     fused_image_eval: bool = False
     """Camera image metrics on the device (csrc/image_eval.hip, model_components/image_metrics.py): the image branch of
     get_image_metrics_and_images (models/neurad.py:568-587) takes ``psnr`` and ``ssim`` from one launch sequence and reads both
@@ -204,7 +211,7 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
         cfg = self.config
         assert isinstance(self.field, HipNeuRADField), "config.field._target must be the HIP NeuRADField"
         self.fused_eval, self.early_stop_eps, self.order_rays = cfg.fused_eval, cfg.early_stop_eps, cfg.order_rays
-        self.fused_training = cfg.fused_training
+        self.fused_training, self.median_depth = cfg.fused_training, cfg.median_depth
         if cfg.fused_vgg_loss:
             from neurad_studio_amd.model_components.perceptual import VGGPerceptualLoss
 
@@ -376,8 +383,10 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
             self._all_lidar_bundle = False
         # points in the lidar's frame (models/ad_model.py:108-113)
         w2l = pose_inverse(lidar.lidar_to_worlds[0])
-        world = ray_bundle.origins + ray_bundle.directions * outputs["depth"]
-        outputs["points"] = (w2l @ torch.cat([world, torch.ones_like(world[..., :1])], dim=-1).unsqueeze(-1)).squeeze(-1)
+        for points, depth in (("points", "depth"), ("median_points", "median_depth")):
+            if depth in outputs:  # ("median_depth": with config.median_depth, from the fused eval chunks)
+                world = ray_bundle.origins + ray_bundle.directions * outputs[depth]
+                outputs[points] = (w2l @ torch.cat([world, torch.ones_like(world[..., :1])], dim=-1).unsqueeze(-1)).squeeze(-1)
         return outputs, batch
 
     def get_image_metrics_and_images(self, outputs, batch):
@@ -405,7 +414,8 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
 
     def _image_and_lidar_metrics(self, outputs, batch):
         """The image branch is the reference's; with ``fused_lidar_eval`` the lidar branch (models/neurad.py:589-620) is
-        ``_fused_lidar_eval_metrics``: the same five keys, every value a Python float -- the reference returns a 0-dim tensor
+        ``_fused_lidar_eval_metrics``: the same five keys (plus the three of the median depth with ``median_depth``), every
+        value a Python float -- the reference returns a 0-dim tensor
         for ``chamfer_distance`` in its fallback case (nothing predicted to return, or nothing returned), this path a float."""
         if not (self.config.fused_lidar_eval and "lidar" in batch and outputs["depth"].shape[0] == batch["lidar"].shape[0]):
             return super().get_image_metrics_and_images(outputs, batch)
@@ -415,7 +425,8 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
 
     def _fused_lidar_eval_metrics(self, outputs, batch):
         """every ray of ``outputs`` is a ray of the scan ``batch["lidar"]`` (what get_outputs_for_lidar renders):
-        model_components/lidar_metrics.py:lidar_eval_metrics with this model's loss settings"""
+        model_components/lidar_metrics.py:lidar_eval_metrics with this model's loss settings; where the outputs carry
+        ``median_depth`` and ``median_points`` (``config.median_depth``) the three LIDAR_EVAL_MEDIAN_KEYS come with it"""
         dev, loss = self.device, self.config.loss
         points = batch["lidar"].to(dev)
         for key in ("is_lidar", "did_return"):  # (models/neurad.py:591-594)
@@ -426,7 +437,8 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
 
     @staticmethod
     def _scalars_to_host(values):
-        """THE device->host transfer of the fused eval metrics: one per lidar scan (five scalars), one per camera image (two;
+        """THE device->host transfer of the fused eval metrics: one per lidar scan (five scalars; eight with
+        ``median_depth``), one per camera image (two;
         four with ``fused_lpips``: the three metrics and LPIPS' range flag);
         tests count the calls"""
         return scalars_to_host(values)

@@ -53,6 +53,8 @@ def masked_return_metrics(pred, distance, intensity, target_intensity, ray_drop_
 
 
 LIDAR_EVAL_KEYS = ("depth_median_l2", "depth_mean_rel_l2", "intensity_rmse", "ray_drop_accuracy", "chamfer_distance")
+# with outputs["median_depth"] / ["median_points"] (the plugin's ``median_depth`` flag): the same metrics on the median depth
+LIDAR_EVAL_MEDIAN_KEYS = ("median_depth_median_l2", "median_depth_mean_rel_l2", "median_chamfer_distance")
 
 
 def scalars_to_host(values: Tensor) -> List[float]:
@@ -69,7 +71,9 @@ def lidar_eval_metrics(outputs: Dict[str, Tensor], scan: Tensor, distance: Tenso
     boolean indexing; the chamfer distance on the masked point sets (predicted to return -> returned, normalised by the
     returned count); the reference's fallback -- the mean range of the returned points where no ray is predicted to return
     or none returned -- chosen with ``torch.where``; the five scalars stacked and read with ONE transfer (``to_host``).
-    Every value is a Python float: the reference returns a 0-dim tensor for ``chamfer_distance`` in its fallback case."""
+    Every value is a Python float: the reference returns a 0-dim tensor for ``chamfer_distance`` in its fallback case.
+    With outputs["median_depth"] [n,1] and outputs["median_points"] the dict also carries LIDAR_EVAL_MEDIAN_KEYS, from the
+    same code on those two, and the one transfer reads eight scalars."""
     depth, logits = outputs["depth"], outputs["ray_drop_logits"]
     m = masked_return_metrics(depth, distance, outputs["intensity"], scan[:, 3:4], logits, did_return)
     # the accuracy is a ratio of two integers: through float64, so that the fp32 result is the correctly rounded quotient the
@@ -79,11 +83,26 @@ def lidar_eval_metrics(outputs: Dict[str, Tensor], scan: Tensor, distance: Tenso
         pred_return = (logits.sigmoid() < 0.5).squeeze(-1)
     else:
         pred_return = (depth < non_return_lidar_distance).squeeze(-1)
-    chamfer = ops.chamfer_distance(outputs["points"].float(), scan.float(), source_valid=pred_return,
-                                   target_valid=did_return, normalize_with_target=True)
     fallback = torch.where(did_return, scan[:, :3].norm(dim=-1), scan.new_zeros(())).sum() / did_return.sum()
-    m["chamfer_distance"] = torch.where(pred_return.any() & did_return.any(), chamfer, fallback.float())
-    return dict(zip(LIDAR_EVAL_KEYS, to_host(torch.stack([m[k].float().reshape(()) for k in LIDAR_EVAL_KEYS]))))
+
+    def chamfer_of(points: Tensor, pred_return: Tensor) -> Tensor:
+        chamfer = ops.chamfer_distance(points.float(), scan.float(), source_valid=pred_return, target_valid=did_return,
+                                       normalize_with_target=True)
+        return torch.where(pred_return.any() & did_return.any(), chamfer, fallback.float())
+
+    m["chamfer_distance"] = chamfer_of(outputs["points"], pred_return)
+    keys = LIDAR_EVAL_KEYS
+    if "median_depth" in outputs and "median_points" in outputs:
+        # the same code on the median depth and its points (SplatAD's names, models/splatad.py:1345-1346,1505); where the
+        # returns are predicted by distance, by the median depth's own
+        median = outputs["median_depth"]
+        mm = masked_return_metrics(median, distance, outputs["intensity"], scan[:, 3:4], logits, did_return)
+        m["median_depth_median_l2"], m["median_depth_mean_rel_l2"] = mm["depth_median_l2"], mm["depth_mean_rel_l2"]
+        if not ray_drop_loss_mult > 0.0:
+            pred_return = (median < non_return_lidar_distance).squeeze(-1)
+        m["median_chamfer_distance"] = chamfer_of(outputs["median_points"], pred_return)
+        keys = LIDAR_EVAL_KEYS + LIDAR_EVAL_MEDIAN_KEYS
+    return dict(zip(keys, to_host(torch.stack([m[k].float().reshape(()) for k in keys]))))
 
 
 def chamfer_distance(source_pc: Tensor, target_pc: Tensor, chunk_size: Optional[int] = None,

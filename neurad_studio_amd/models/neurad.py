@@ -47,6 +47,11 @@ class FusedEvalMixin:
     order_rays: bool = False
     """Compute a cache-coherent processing order per eval chunk (ops.ray_order).  Pays for incoherent batches (lidar
     scans, random pixels); camera patches are coherent as they come."""
+    median_depth: bool = False
+    """True: the outputs also carry ``median_depth`` [R,1] (csrc/median_depth.hip): the midpoint of the first non-sky
+    sample at which the accumulated weight reaches one half -- a ray that never gets there before the sky reports its last
+    non-sky midpoint.  Computed from the weights the fused render kernel hands out, one more launch per chunk.  Only this
+    fused eval route produces the key: off it (training, the operator-level path) it is absent."""
     reproduce_late_binding_quirk: bool = True
     """models/neurad.py:248 builds density_fns with a late-binding closure, so BOTH proposal rounds evaluate
     proposal_fields[1]; the fused sampler has to be told the same."""
@@ -87,17 +92,19 @@ class FusedEvalMixin:
             ends = fr.ends[..., 0].clone()
             ends[:, -1] = sky  # the sky stretch of the last sample (models/neurad.py:451-455)
         order = ops.ray_order(o, d, self.field.hashgrid.static_scale) if self.order_rays else None
-        want_w = bool(cfg.normalize_depth)
+        want_w = bool(cfg.normalize_depth) or self.median_depth
         out = self.field.render(o, d, ray_bundle.pixel_area, starts, ends, return_weights=want_w,
                                 early_stop_eps=self.early_stop_eps, order=order, times=times, actor_cand=cand)
         features, depth, accumulation = out[:3]
-        if want_w:  # DepthRenderer("expected") over the non-sky samples (renderers.py:398-416)
+        if cfg.normalize_depth:  # DepthRenderer("expected") over the non-sky samples (renderers.py:398-416)
             w = out[3][:, :-1]
             steps = (starts[:, :-1] + ends[:, :-1]) / 2
             depth = (depth / (w.sum(-1, keepdim=True) + 1e-10)).clip(steps.min(), steps.max())
         if cfg.appearance_dim > 0:
             features = torch.cat([features, self._get_appearance_embedding(ray_bundle, features)], dim=-1)
         nff = {"features": features, "depth": depth, "accumulation": accumulation}
+        if self.median_depth:  # over the non-sky samples, like the expected depth and its normalisation above
+            nff["median_depth"] = ops.median_depth(out[3][:, :-1], starts[:, :-1], ends[:, :-1])
         for i, (pw, prs) in enumerate(zip(prop_weights, prop_ray_samples)):
             nff[f"prop_depth_{i}"] = self.renderer_depth(pw, prs)
         return nff

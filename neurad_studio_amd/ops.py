@@ -1453,6 +1453,48 @@ def packed_composite_fwd(t_starts, t_ends, sigmas_or_alphas, features, segments,
     return of, od, oa, ow
 
 
+# ---- median (quantile) depth (csrc/median_depth.hip; the contract: include/neurad_hip.h at nrhip_median_depth) ----
+MEDIAN_MAX_THRESHOLDS = _lib.MEDIAN_MAX_THRESHOLDS
+
+
+def _thresholds(thresholds) -> Tuple[C.Array, int]:
+    """-> (host float array, K); the count and the values are checked by the library (1 <= K <= 8, finite)"""
+    q = [float(v) for v in thresholds]
+    return (C.c_float * len(q))(*q), len(q)
+
+
+def median_depth(weights, starts, ends, thresholds=(0.5,), return_index: bool = False):
+    """weights, starts, ends [R,S] -> depth [R,K]: per threshold q the midpoint of the first sample at which
+    float32(float64 running sum of the weights) is not below q, the last sample if none is; with ``return_index`` also that
+    sample's index, int32 [R,K].  One pass serves all K thresholds.  No gradient."""
+    w = _chk(weights, "weights")
+    if w.dim() != 2:
+        raise ValueError("weights must be [R,S]")
+    R, S = w.shape
+    s, e = _chk(starts, "starts"), _chk(ends, "ends")
+    if s.shape != w.shape or e.shape != w.shape:
+        raise ValueError(f"starts / ends must be [{R},{S}] like weights")
+    q, K = _thresholds(thresholds)
+    od = torch.empty((R, K), device=w.device, dtype=torch.float32)
+    oi = torch.empty((R, K), device=w.device, dtype=torch.int32) if return_index else None
+    launch("nrhip_median_depth", w, s, e, R, S, q, K, od, oi)
+    return (od, oi) if return_index else od
+
+
+def median_depth_packed(weights, t_starts, t_ends, segments, thresholds=(0.5,), return_index: bool = False):
+    """the same over packed samples: weights, t_starts, t_ends [M], segments int64 [R+1] -> depth [R,K] (, index int32
+    [R,K]); a ray without samples gets depth 0 and index -1"""
+    w = _flat(weights, "weights")
+    M = w.shape[0]
+    s, e = _flat(t_starts, "t_starts", M), _flat(t_ends, "t_ends", M)
+    seg, R = _seg(segments)
+    q, K = _thresholds(thresholds)
+    od = torch.empty((R, K), device=w.device, dtype=torch.float32)
+    oi = torch.empty((R, K), device=w.device, dtype=torch.int32) if return_index else None
+    launch("nrhip_median_depth_packed", w if M else None, s if M else None, e if M else None, seg, R, M, q, K, od, oi)
+    return (od, oi) if return_index else od
+
+
 def _c_packed_rays(who: str, origins, directions, pixel_area, t_starts, t_ends, segments: Optional[Tensor] = None,
                    order: Optional[Tensor] = None):
     """-> (nrhip_packed_rays, the tensors it points to): per-RAY origins [R,3] / directions [R,3] / pixel_area [R], per-sample
