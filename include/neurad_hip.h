@@ -975,6 +975,72 @@ int nrhip_interlevel_loss(const float* c, const float* w, int32_t n_fine, const 
 int nrhip_distortion_loss(const float* c, const float* w, int32_t n_samples, int64_t r, float* loss_per_ray,
                           float* grad_w, void* stream);
 
+/* ---- the two per-sample loss terms on PACKED (occupancy-marched) samples (csrc/losses.hip): the distortion loss and the
+ *      lidar carving term for [M]-shaped arrays with segments int64 [R+1] as nrhip_packed_segments / the march make them,
+ *      ray r owning the samples [segments[r], segments[r+1]) -- no padding of [M] to [R, max_n], any number of samples per
+ *      ray.  Both follow the packed compositing kernels' contract: one wavefront walks one ray's segment in chunks of 64
+ *      with a carried prefix; no atomics, no LDS, no allocation, no host synchronisation (graph-capturable); every element
+ *      has one writer, so the same inputs give the same bits; an empty segment writes 0 to its ray's row of the per-ray
+ *      outputs (the caller does not pre-zero); no row past M or R is written.  r == 0 is a no-op that reads no pointer;
+ *      m == 0 reads no sample pointer (they may be NULL) and still writes the per-ray outputs as zeros; m >= 2^31 is
+ *      NRHIP_ERR_UNSUPPORTED; a negative count or a NULL required pointer is NRHIP_ERR_INVALID_ARG.  Segments are clamped
+ *      into [0, m], so broken ones read inside the arrays.
+ *
+ * nrhip_packed_distortion_loss -- THE CONTRACT.  For a ray with samples i = 0..n-1 in segment order, fp32 interval ends
+ * s_i, e_i (in whatever metric the caller chose: the march's Euclidean t, or t mapped through a monotone spacing function)
+ * and fp32 weights w_i, everything computed in float64 from the fp32 inputs:
+ *   m_i = (s_i + e_i) / 2, delta_i = e_i - s_i                       (both exact in float64)
+ *   A_i = sum_{j<i} w_j, B_i = sum_{j<i} w_j m_j;  W, Bt = the same sums over the whole ray
+ *   loss   = fp32( 2 sum_i w_i (m_i A_i - B_i) + (1/3) sum_i w_i^2 delta_i )
+ *   grad_k = fp32( 2 [ m_k (A_k - (W - A_k - w_k)) - (B_k - (Bt - B_k - w_k m_k)) ] + (2/3) w_k delta_k )
+ * PRECONDITION, unchecked like the sortedness of ray_indices: the midpoints are non-decreasing within a ray (the march
+ * guarantees it, a monotone spacing map keeps it).  Then this is the reference's
+ *   sum_i sum_j w_i w_j |m_i - m_j| + sum_i w_i^2 delta_i / 3
+ * -- lossfun_distortion (losses.py:137-148) for contiguous edges, nerfstudio_distortion_loss (losses.py:159-200) for
+ * separate starts and ends -- in O(n) instead of O(n^2), and its derivative w.r.t. the weights.  Equal midpoints,
+ * zero-width intervals and zero weights are no special case.  No gradient goes to the interval ends (the dense node
+ * detaches them too).  grad_w needs the ray's totals before any per-sample value: a ray of more than 64 samples is walked
+ * twice (the second walk repeats the first one's scans bit for bit), a shorter one once.
+ * Float64 on purpose: the prefix form cancels (m_i A_i - B_i) where the O(n^2) form adds non-negative terms; in fp32 that
+ * would cost digits exactly on the peaked weight distributions this loss produces.
+ * ERROR BOUNDS against the exact value of the formulas above on the fp32 inputs (u = 2^-53, S = sum_i |w_i|,
+ * X = max_i |m_i|, interval ends >= 0 so that delta_i <= 2 m_i):
+ *   |loss - exact|     <= 2^-24 |exact|   + c (n + 2) u X S^2
+ *   |grad_k - exact_k| <= 2^-24 |exact_k| + c (n + 2) u X S         with c = NRHIP_PACKED_DISTORTION_C = 16.
+ * The first term is the one rounding to fp32.  The second is a first-order count of the roundings (units: u X S^2 for
+ * the loss, u X S for the gradient):
+ *   - a sum of up to n float64 terms taken in ANY association (wave scan + carry) is within (n - 1) u sum|terms|, so A_i
+ *     and W carry (n - 1) [x X once multiplied by m], B_i and Bt (with the rounding of each product w_j m_j) n;
+ *   - loss: per sample |w_i| times { (n - 1) + n from A_i, B_i; 1 for the product m_i A_i; 2 for the difference (at most
+ *     2 X S); 2 for the product with w_i (same size) } = 2n + 4; summed over i: (2n + 4) S; the sum of the n terms, each at
+ *     most 2 |w_i| X S: 2 (n - 1) S; times the exact factor 2: (8n + 4) X S^2.  The width term, three roundings per sample
+ *     and the sum, on at most (2/3) X S^2: (2/3)(n + 2); the last addition, on at most (14/3) X S^2: 5.  Together
+ *     8.67n + 10.4 < 9 (n + 2);
+ *   - grad_k: A_k enters twice and W once, 3 (n - 1), plus three subtractions with results of at most S: 3; times m_k,
+ *     one more rounding: 3n + 1.  B_k twice and Bt once, 3n, the product w_k m_k, 1, and three subtractions: 3n + 4.  The
+ *     difference of the two brackets, at most 2 X S: 2; times the exact 2: 2 (6n + 7) = 12n + 14.  The width term, three
+ *     roundings on at most (4/3) X S: 4; the last addition, on at most (16/3) X S: 6.  Together 12n + 24 <= 15 (n + 2);
+ *   - the slack of both, and one more unit, cover the roundings of a float64 reference that evaluates the O(n^2) form with
+ *     exactly rounded sums (at most 3 u on each product): c = 16.                                                      */
+#define NRHIP_PACKED_DISTORTION_C 16
+int nrhip_packed_distortion_loss(const float* s_starts, const float* s_ends, const float* weights,
+                                 const int64_t* segments, int64_t r, int64_t m, float* loss_per_ray /*[R]*/,
+                                 float* grad_w /*[M] or NULL*/, void* stream);
+/* nrhip_lidar_carving on packed samples.  is_lidar uint8 [R], did_return uint8 [R] or NULL = all returned, distance [R].
+ * The mask is computed exactly as the dense kernel computes it and matches the reference bit for bit:
+ *   mid = (t_start + t_end) * 0.5f in fp32;  close = lidar && (returned ? fabsf(dist - mid) < eps : mid < non_return),
+ * both comparisons strict.  With wf_i = (lidar && !close_i) ? w_i : 0:
+ *   is_close [M] = close_i,  loss_per_ray [R] = fp32(sum_i (double)wf_i^2),  grad_weights [M] = 2 wf_i  (exact in fp32).
+ * |loss - exact| <= 2^-24 |exact| + n 2^-53 sum_i wf_i^2: the squares are exact in float64, their sum is taken in
+ * float64 in some association, then rounded to fp32 once.  A camera ray (is_lidar == 0) reads no sample and gets mask 0,
+ * loss 0 and gradient 0.  Any of the three outputs may be NULL (at least one is needed); weights may be NULL when only
+ * the mask is asked for.                                                                                              */
+int nrhip_packed_lidar_carving(const float* t_starts, const float* t_ends, const float* weights /*[M] or NULL*/,
+                               const int64_t* segments, const uint8_t* is_lidar, const uint8_t* did_return,
+                               const float* distance, float carving_epsilon, float non_return_lidar_distance, int64_t r,
+                               int64_t m, uint8_t* is_close /*[M] or NULL*/, float* loss_per_ray /*[R] or NULL*/,
+                               float* grad_weights /*[M] or NULL*/, void* stream);
+
 /* ---- lidar scan evaluation (csrc/lidar_eval.hip): the chamfer distance of NeuRADModel.get_image_metrics_and_images
  *      (models/neurad.py:614-618; utils/math.py:745-798, there 2 ceil(N / 1000) torch.cdist blocks) ------------------------
  * A point set is fp32 [n, stride]: the first three floats of a row are xyz, the row stride (floats) is >= 3, so

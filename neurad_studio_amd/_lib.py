@@ -124,6 +124,7 @@ MAX_SAMPLE_CONTAINMENTS = 8  # NRHIP_MAX_SAMPLE_CONTAINMENTS
 GRAD_ROWS_PER_BLOCK = 256   # NRHIP_GRAD_ROWS_PER_BLOCK
 NEAREST_TILE = 1024         # NRHIP_NEAREST_TILE
 MEDIAN_MAX_THRESHOLDS = 8   # NRHIP_MEDIAN_MAX_THRESHOLDS
+PACKED_DISTORTION_C = 16    # NRHIP_PACKED_DISTORTION_C
 VGG_IMAGE_CHANNELS = 16     # NRHIP_VGG_IMAGE_CHANNELS
 L1_ITEMS = 2048             # NRHIP_L1_ITEMS
 SSIM_TILE = 32              # NRHIP_SSIM_TILE
@@ -278,6 +279,8 @@ PROTOTYPES = {
                                           P, I64, C.POINTER(P), C.POINTER(P), C.POINTER(P), P],
     "nrhip_interlevel_loss": [P, P, I32, P, P, I32, F32, I64, P, P, P],
     "nrhip_distortion_loss": [P, P, I32, I64, P, P, P],
+    "nrhip_packed_distortion_loss": [P, P, P, P, I64, I64, P, P, P],
+    "nrhip_packed_lidar_carving": [P, P, P, P, P, P, P, F32, F32, I64, I64, P, P, P, P],
     "nrhip_prop_weights_fwd": [P, I32, P, I64, I32, P, P, P],
     "nrhip_prop_weights_bwd": [P, I32, P, P, P, I64, I32, P, P],
     "nrhip_sdf_render_fwd": [P, P, F32, P, P, I32, I64, I32, I32, P, P, P, I32, P, P, P],

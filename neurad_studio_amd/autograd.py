@@ -647,6 +647,27 @@ class CarvingLossFn(torch.autograd.Function):
         return (gw * g,) + (None,) * 7
 
 
+class PackedCarvingLossFn(torch.autograd.Function):
+    """``CarvingLossFn`` on packed (occupancy-marched) samples: sum over the rays of sum((w * (is_lidar & ~is_close))^2),
+    value and gradient from ONE launch.  args: weights [M], t_starts, t_ends [M], segments int64 [R+1], is_lidar, did_return
+    (None: all returned), distance (per ray), carving_epsilon, non_return_lidar_distance."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, weights, t_starts, t_ends, segments, is_lidar, did_return, distance, eps, non_return):
+        _, loss, gw = ops.packed_lidar_carving(t_starts, t_ends, segments, is_lidar, did_return, distance, eps, non_return,
+                                               weights=weights, want_mask=False)
+        ctx.save_for_backward(gw)
+        ctx.shape = weights.shape
+        return loss.sum()
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, g):
+        (gw,) = ctx.saved_tensors
+        return ((gw * g).view(ctx.shape),) + (None,) * 8
+
+
 class EmbeddingLerpFn(torch.autograd.Function):
     """C3 (models/neurad.py:423-441): per-ray lerp of two embedding rows; gradient to the embedding table only."""
 
@@ -744,6 +765,26 @@ class DistortionLossFn(torch.autograd.Function):
     def backward(ctx, go):
         (g,) = ctx.saved_tensors
         return None, g * (go / ctx.n_rays)
+
+
+class PackedDistortionLossFn(torch.autograd.Function):
+    """The distortion loss on packed (occupancy-marched) samples, O(n) per ray (include/neurad_hip.h at
+    nrhip_packed_distortion_loss): the mean over ALL R rays, a ray without samples contributes 0.  args: s_starts, s_ends
+    [M] (no gradient, like the dense node's edges), weights [M], segments int64 [R+1]."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, s_starts, s_ends, weights, segments):
+        loss, g = ops.packed_distortion_loss_rays(s_starts, s_ends, weights, segments, need_grad=True)
+        ctx.save_for_backward(g)
+        ctx.n_rays, ctx.shape = loss.shape[0], weights.shape
+        return loss.sum() / max(ctx.n_rays, 1)
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, go):
+        (g,) = ctx.saved_tensors
+        return None, None, (g * (go / max(ctx.n_rays, 1))).view(ctx.shape), None
 
 
 # ------------------------------------------------------------------------------------------------

@@ -210,6 +210,134 @@ __global__ __launch_bounds__(256) void lidar_carving_kernel(const float* __restr
   }
 }
 
+// ---- the same two per-sample terms on PACKED (occupancy-marched) samples: ray r owns the samples [seg[r], seg[r+1]) of
+// the [M]-shaped arrays, one wavefront walks one ray in chunks of 64 with a carried prefix, rays are handed out grid-stride
+// over a capped grid (the contract of packed_composite.h: no atomics, no LDS, nothing allocated, one writer per element, an
+// empty segment writes 0 to its ray's row).  The contracts and their error bounds: include/neurad_hip.h.
+namespace {
+
+constexpr int kPackedMaxBlocks = 4096;  // grid cap: 16 384 waves, the rest of the rays grid-stride
+inline int packed_blocks_for(int64_t r) {
+  const int64_t b = (r + kRaysPerBlock - 1) / kRaysPerBlock;
+  return (int)(b < kPackedMaxBlocks ? b : kPackedMaxBlocks);
+}
+// a ray's segment, clamped into [0, M]: broken segments read inside the arrays
+__device__ __forceinline__ void packed_segment(const int64_t* __restrict__ seg, int64_t ray, int64_t M, int64_t& sb,
+                                               int64_t& se) {
+  sb = seg[ray], se = seg[ray + 1];
+  sb = sb < 0 ? 0 : (sb > M ? M : sb);
+  se = se < sb ? sb : (se > M ? M : se);
+}
+
+// One chunk of a ray for the distortion loss, lane = sample, everything in float64 from the fp32 inputs: the sample's
+// weight, midpoint and width, and the sums over the EARLIER samples of the ray A = sum w_j, B = sum w_j m_j (the chunk's
+// exclusive prefix on top of the carry, taken by a shift of the inclusive scan: no own term is subtracted back out).
+struct DistChunk {
+  double w, m, d, A, B;
+};
+__device__ __forceinline__ DistChunk dist_chunk(const float* __restrict__ s, const float* __restrict__ e,
+                                                const float* __restrict__ w, int64_t i, bool live, int lane, double& cA,
+                                                double& cB) {
+  DistChunk c;
+  c.w = live ? (double)w[i] : 0.0;
+  const double si = live ? (double)s[i] : 0.0, ei = live ? (double)e[i] : 0.0;
+  c.m = (si + ei) * 0.5, c.d = ei - si;  // both exact: fp32 inputs
+  const double inA = wscan::incl<wscan::Add>(c.w, lane), inB = wscan::incl<wscan::Add>(c.w * c.m, lane);
+  c.A = cA + wscan::shift_up1(inA, 0.0, lane), c.B = cB + wscan::shift_up1(inB, 0.0, lane);
+  cA += wscan::last(inA), cB += wscan::last(inB);
+  return c;
+}
+// d loss / d w_k: the samples before k weigh m_k - m_j, those behind it m_j - m_k, with W / Bt the ray's totals of A / B
+__device__ __forceinline__ float dist_grad(const DistChunk& c, double W, double Bt) {
+  return (float)(2.0 * (c.m * (c.A - (W - c.A - c.w)) - (c.B - (Bt - c.B - c.w * c.m))) + (2.0 / 3.0) * c.w * c.d);
+}
+
+// Distortion loss of packed samples in its O(n) form (sorted midpoints: |m_i - m_j| = m_i - m_j for j < i):
+//   loss = 2 sum_i w_i (m_i A_i - B_i) + sum_i w_i^2 delta_i / 3
+// The gradient needs the ray's totals before any sample's value, so it takes TWO WALKS of the segment: the first gives the
+// loss and the totals, the second (the same scans on the same data, so the same prefixes bit for bit; its reads hit the
+// cache lines the first walk brought in) writes the gradient.  A ray of at most 64 samples has its totals after its only
+// chunk and writes the gradient in the first walk.  Without grad_w there is one walk.
+__global__ __launch_bounds__(64 * kRaysPerBlock) void packed_distortion_loss_kernel(
+    const float* __restrict__ s, const float* __restrict__ e, const float* __restrict__ w, const int64_t* __restrict__ seg,
+    int64_t R, int64_t M, float* __restrict__ loss, float* __restrict__ gw) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6); ray < R;
+       ray += (int64_t)gridDim.x * kRaysPerBlock) {
+    int64_t sb, se;
+    packed_segment(seg, ray, M, sb, se);
+    const bool single = se - sb <= 64;
+    double cA = 0.0, cB = 0.0, inter = 0.0, intra = 0.0;
+    for (int64_t i0 = sb; i0 < se; i0 += 64) {
+      const int64_t i = i0 + lane;
+      const bool live = i < se;
+      const DistChunk c = dist_chunk(s, e, w, i, live, lane, cA, cB);
+      inter += c.w * (c.m * c.A - c.B);  // a dead lane: w = 0
+      intra += c.w * c.w * c.d;
+      if (gw && single && live) gw[i] = dist_grad(c, cA, cB);
+    }
+    const double total = 2.0 * wscan::reduce<wscan::Add>(inter) + wscan::reduce<wscan::Add>(intra) / 3.0;
+    if (lane == 0) loss[ray] = (float)total;
+    if (gw && !single) {
+      const double W = cA, Bt = cB;
+      cA = 0.0, cB = 0.0;
+      for (int64_t i0 = sb; i0 < se; i0 += 64) {
+        const int64_t i = i0 + lane;
+        const bool live = i < se;
+        const DistChunk c = dist_chunk(s, e, w, i, live, lane, cA, cB);
+        if (live) gw[i] = dist_grad(c, W, Bt);
+      }
+    }
+  }
+}
+
+// lidar_carving_kernel on packed samples: the same mask, bit for bit; the squares are summed in float64.  A camera ray
+// reads no sample: its mask and gradient are zeros whatever the samples hold.
+__global__ __launch_bounds__(64 * kRaysPerBlock) void packed_lidar_carving_kernel(
+    const float* __restrict__ ts, const float* __restrict__ te, const float* __restrict__ weights,
+    const int64_t* __restrict__ seg, const uint8_t* __restrict__ is_lidar, const uint8_t* __restrict__ did_return,
+    const float* __restrict__ dist, float eps, float non_return, int64_t R, int64_t M, uint8_t* __restrict__ is_close,
+    float* __restrict__ loss_ray, float* __restrict__ grad_w) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t ray = (int64_t)blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6); ray < R;
+       ray += (int64_t)gridDim.x * kRaysPerBlock) {
+    int64_t sb, se;
+    packed_segment(seg, ray, M, sb, se);
+    const bool lidar = is_lidar[ray] != 0;
+    const bool returned = did_return ? did_return[ray] != 0 : true;
+    const float dr = dist[ray];
+    double acc = 0.0;
+    for (int64_t i = sb + lane; i < se; i += 64) {
+      bool close = false;
+      float wf = 0.f;
+      if (lidar) {
+        const float mid = (ts[i] + te[i]) * 0.5f;
+        close = returned ? fabsf(dr - mid) < eps : mid < non_return;
+        if (weights && !close) wf = weights[i];
+      }
+      if (is_close) is_close[i] = close ? 1 : 0;
+      acc += (double)wf * (double)wf;  // exact: 48 bits
+      if (grad_w) grad_w[i] = 2.f * wf;
+    }
+    if (loss_ray) {
+      acc = wave_sum_d(acc);
+      if (lane == 0) loss_ray[ray] = (float)acc;
+    }
+  }
+}
+
+// the argument checks the two packed entry points share; *launch: there are rays to run
+int packed_loss_args(const char* who, int64_t r, int64_t m, const void* segments, bool* launch) {
+  *launch = false;
+  NR_REQUIRE(r >= 0 && m >= 0, NRHIP_ERR_INVALID_ARG, "%s: negative ray or sample count", who);
+  NR_REQUIRE(m < (INT64_C(1) << 31), NRHIP_ERR_UNSUPPORTED, "%s: M >= 2^31", who);
+  if (r == 0) return NRHIP_OK;  // no rays: empty tensors have no address
+  NR_REQUIRE(segments, NRHIP_ERR_INVALID_ARG, "%s: segments is NULL", who);
+  *launch = true;
+  return NRHIP_OK;
+}
+
+}  // namespace
 }  // namespace nrhip
 
 using namespace nrhip;
@@ -253,4 +381,38 @@ extern "C" int nrhip_lidar_carving(const float* starts, const float* ends, int32
       starts, ends, sample_stride > 0 ? sample_stride : s, weights, is_lidar, did_return, distance, carving_epsilon,
       non_return_lidar_distance, r, s, is_close, loss_per_ray, grad_weights);
   return nrhip::check_launch("lidar_carving");
+}
+
+extern "C" int nrhip_packed_distortion_loss(const float* s_starts, const float* s_ends, const float* weights,
+                                            const int64_t* segments, int64_t r, int64_t m, float* loss_per_ray,
+                                            float* grad_w, void* stream) {
+  bool launch;
+  if (int rc = packed_loss_args("packed_distortion_loss", r, m, segments, &launch)) return rc;
+  if (!launch) return NRHIP_OK;
+  NR_REQUIRE(loss_per_ray, NRHIP_ERR_INVALID_ARG, "packed_distortion_loss: loss_per_ray is NULL");
+  NR_REQUIRE(m == 0 || (s_starts && s_ends && weights), NRHIP_ERR_INVALID_ARG,
+             "packed_distortion_loss: NULL sample pointer with %lld samples", (long long)m);
+  packed_distortion_loss_kernel<<<packed_blocks_for(r), 64 * kRaysPerBlock, 0, (hipStream_t)stream>>>(
+      s_starts, s_ends, weights, segments, r, m, loss_per_ray, grad_w);
+  return check_launch("packed_distortion_loss");
+}
+
+extern "C" int nrhip_packed_lidar_carving(const float* t_starts, const float* t_ends, const float* weights,
+                                          const int64_t* segments, const uint8_t* is_lidar, const uint8_t* did_return,
+                                          const float* distance, float carving_epsilon, float non_return_lidar_distance,
+                                          int64_t r, int64_t m, uint8_t* is_close, float* loss_per_ray,
+                                          float* grad_weights, void* stream) {
+  bool launch;
+  if (int rc = packed_loss_args("packed_lidar_carving", r, m, segments, &launch)) return rc;
+  if (!launch) return NRHIP_OK;
+  NR_REQUIRE(is_lidar && distance, NRHIP_ERR_INVALID_ARG, "packed_lidar_carving: is_lidar or distance is NULL");
+  NR_REQUIRE(is_close || loss_per_ray || grad_weights, NRHIP_ERR_INVALID_ARG, "packed_lidar_carving: no output (NULL)");
+  NR_REQUIRE(m == 0 || (t_starts && t_ends), NRHIP_ERR_INVALID_ARG,
+             "packed_lidar_carving: NULL sample pointer with %lld samples", (long long)m);
+  NR_REQUIRE(m == 0 || weights || (!loss_per_ray && !grad_weights), NRHIP_ERR_INVALID_ARG,
+             "packed_lidar_carving: the loss needs the weights (NULL)");
+  packed_lidar_carving_kernel<<<packed_blocks_for(r), 64 * kRaysPerBlock, 0, (hipStream_t)stream>>>(
+      t_starts, t_ends, weights, segments, is_lidar, did_return, distance, carving_epsilon, non_return_lidar_distance, r, m,
+      is_close, loss_per_ray, grad_weights);
+  return check_launch("packed_lidar_carving");
 }

@@ -124,3 +124,36 @@ def lidar_loss_dict(metrics: Dict[str, Tensor], cfg: LidarLossSettings, num_prop
         out[f"depth_loss_{i}"] = cfg.prop_lidar_loss_mult * cfg.depth_mult * metrics[f"depth_loss_{i}"]
         out[f"carving_loss_{i}"] = cfg.prop_lidar_loss_mult * cfg.carving_mult * metrics[f"carving_loss_{i}"]
     return out
+
+
+# ---- the carving term on packed, occupancy-marched samples (csrc/losses.hip: nrhip_packed_lidar_carving) ---------------
+def packed_is_close_to_lidar(t_starts: Tensor, t_ends: Tensor, is_lidar: Tensor, did_return, distance: Tensor,
+                             carving_epsilon: float, non_return_lidar_distance: float, *, segments=None, ray_indices=None,
+                             num_rays=None) -> Tensor:
+    """NeuRADModel._compute_is_close_to_lidar (models/neurad.py:677-700) for packed samples -> bool [M], bit for bit the
+    reference's mask.  t_starts / t_ends [M] or [M,1]; is_lidar bool [R], did_return bool [R] (None: every beam returned),
+    distance [R] or [R,1] over ALL rays of the batch (a camera ray's values are not looked at); exactly one of ``segments``
+    int64 [R+1] and ``ray_indices`` int64 [M] + ``num_rays``."""
+    from .. import ops
+    from .losses import packed_addressing
+
+    seg = packed_addressing(segments, ray_indices, num_rays)
+    close, _, _ = ops.packed_lidar_carving(t_starts.detach(), t_ends.detach(), seg, is_lidar, did_return, distance.detach(),
+                                           carving_epsilon, non_return_lidar_distance, want_mask=True)
+    return close
+
+
+def packed_carving_loss(weights: Tensor, t_starts: Tensor, t_ends: Tensor, is_lidar: Tensor, did_return, distance: Tensor,
+                        carving_epsilon: float, non_return_lidar_distance: float, *, segments=None, ray_indices=None,
+                        num_rays=None) -> Tensor:
+    """The carving term sum((w * (is_lidar & ~is_close_to_lidar))^2) (models/neurad.py:399-408) on packed samples -> 0-dim
+    tensor, value and gradient from one launch; arguments as ``packed_is_close_to_lidar``, weights [M] or [M,1] (what
+    ``VolumetricSampler.render_train`` returns).  It is what ``lidar_metrics(..., num_proposal_rounds=0)`` takes as
+    ``outputs["non_nearby_weights_loss"]``.  Gradient: to the weights only."""
+    from .. import autograd as ag
+    from .losses import packed_addressing
+
+    seg = packed_addressing(segments, ray_indices, num_rays)
+    return ag.PackedCarvingLossFn.apply(weights.reshape(-1), t_starts.detach().reshape(-1), t_ends.detach().reshape(-1), seg,
+                                        is_lidar, did_return, distance.detach().reshape(-1), float(carving_epsilon),
+                                        float(non_return_lidar_distance))

@@ -37,3 +37,38 @@ def zipnerf_interlevel_loss(weights_list: Sequence[Tensor], ray_samples_list: Li
 
 def distortion_loss(weights_list: Sequence[Tensor], ray_samples_list: List[RaySamples]) -> Tensor:
     return ag.DistortionLossFn.apply(ray_samples_to_sdist(ray_samples_list[-1]).detach(), weights_list[-1].squeeze(-1))
+
+
+def packed_addressing(segments, ray_indices, num_rays) -> Tensor:
+    """segments int64 [R+1] from exactly one of the two addressings of packed samples: ``segments`` itself, or the sorted
+    ``ray_indices`` [M] with ``num_rays`` (derived on the device, no host read)"""
+    if (segments is None) == (ray_indices is None):
+        raise ValueError("packed samples are addressed by exactly one of segments= and ray_indices= (with num_rays=)")
+    if segments is not None:
+        if num_rays is not None and int(num_rays) != segments.shape[0] - 1:
+            raise ValueError(f"segments holds {segments.shape[0] - 1} rays, num_rays says {int(num_rays)}")
+        return segments
+    if num_rays is None:
+        raise ValueError("ray_indices= needs num_rays=")
+    return ag.ops.packed_segments(ray_indices, int(num_rays))
+
+
+def packed_distortion_loss(weights: Tensor, starts: Tensor, ends: Tensor, *, segments=None, ray_indices=None,
+                           num_rays=None) -> Tensor:
+    """The distortion loss (losses.py:137-156; nerfstudio_distortion_loss, losses.py:159-200) on packed,
+    occupancy-marched samples: the mean over ALL rays of
+        sum_i sum_j w_i w_j |m_i - m_j| + sum_i w_i^2 (end_i - start_i) / 3,      m_i = (start_i + end_i) / 2,
+    in O(n) per ray and float64 (csrc/losses.hip; the contract and its error bound: include/neurad_hip.h at
+    nrhip_packed_distortion_loss).  A ray without samples contributes 0.  weights [M] or [M,1] (what
+    ``VolumetricSampler.render_train`` returns); starts / ends [M] or [M,1] with midpoints non-decreasing within a ray;
+    exactly one of ``segments`` int64 [R+1] and ``ray_indices`` int64 [M] + ``num_rays``.  Gradient: to the weights only.
+
+    The caller chooses the metric of ``starts`` / ``ends``.  The march's Euclidean ``t_starts`` / ``t_ends`` work as they
+    are; for an unbounded scene one wants the reference's normalised spacing instead, a monotone map that keeps the order::
+
+        sp = PowerSpacing(nears[ray_indices], fars[ray_indices], lam, scaling)
+        loss = packed_distortion_loss(out["weights"], sp.to_spacing(out["t_starts"]), sp.to_spacing(out["t_ends"]),
+                                      ray_indices=out["ray_indices"], num_rays=R)
+    """
+    seg = packed_addressing(segments, ray_indices, num_rays)
+    return ag.PackedDistortionLossFn.apply(starts.detach().reshape(-1), ends.detach().reshape(-1), weights.reshape(-1), seg)

@@ -32,6 +32,11 @@ class PowerSpacing:
         y = x * s_far + (1 - x) * s_near
         return (((y * lam / lam_1 + 1).clamp_min(1e-10) ** (1 / lam) - 1) * lam_1) / self.scaling
 
+    def to_spacing(self, t: Tensor) -> Tensor:
+        """the inverse of ``__call__``: Euclidean distance -> normalised spacing (0 at near, 1 at far), monotone in t"""
+        s_near, s_far = self._fn(self.nears), self._fn(self.fars)
+        return (self._fn(t) - s_near) / (s_far - s_near)
+
 
 def _edges_to_samples(ray_bundle: RayBundle, sp: Tensor, eu: Tensor, fn) -> RaySamples:
     return ray_bundle.get_ray_samples(bin_starts=eu[..., :-1, None], bin_ends=eu[..., 1:, None],

@@ -1495,6 +1495,57 @@ def median_depth_packed(weights, t_starts, t_ends, segments, thresholds=(0.5,), 
     return (od, oi) if return_index else od
 
 
+# ---- the per-sample loss terms on packed samples (csrc/losses.hip; the contracts: include/neurad_hip.h at
+#      nrhip_packed_distortion_loss) ----
+PACKED_DISTORTION_C = _lib.PACKED_DISTORTION_C
+
+
+def packed_distortion_loss_rays(s_starts, s_ends, weights, segments, need_grad: bool = True):
+    """distortion loss per ray of packed samples in its O(n) form: s_starts, s_ends, weights [M] (midpoints non-decreasing
+    within a ray), segments int64 [R+1] -> loss_per_ray [R], d loss_per_ray / d weights [M] (or None); a ray without samples
+    gets 0"""
+    w = _flat(weights, "weights")
+    M = w.shape[0]
+    s, e = _flat(s_starts, "s_starts", M), _flat(s_ends, "s_ends", M)
+    seg, R = _seg(segments)
+    loss = torch.empty((R,), device=w.device, dtype=torch.float32)
+    g = torch.empty_like(w) if need_grad else None
+    launch("nrhip_packed_distortion_loss", s if M else None, e if M else None, w if M else None, seg, R, M, loss,
+           g if M else None)
+    return loss, g
+
+
+def packed_lidar_carving(t_starts, t_ends, segments, is_lidar: Tensor, did_return: Optional[Tensor], distance: Tensor,
+                         carving_epsilon: float, non_return_lidar_distance: float, weights: Optional[Tensor] = None,
+                         want_mask: bool = True, want_grad: bool = True):
+    """``lidar_carving`` on packed samples: t_starts / t_ends [M], segments int64 [R+1], per-ray is_lidar / did_return (bool,
+    did_return may be None = all returned) / distance -> (is_close [M] bool or None, loss_per_ray [R] or None, grad_weights [M]
+    or None); the loss terms need ``weights`` [M]."""
+    s = _flat(t_starts, "t_starts")
+    M = s.shape[0]
+    e = _flat(t_ends, "t_ends", M)
+    seg, R = _seg(segments)
+    w = None if weights is None else _flat(weights, "weights", M)
+    if w is None and not want_mask:
+        raise ValueError("packed_lidar_carving: nothing to compute (no weights and no mask)")
+    u8 = lambda m: None if m is None else m.reshape(-1).contiguous().view(torch.uint8)  # noqa: E731  (bool is 1 byte)
+    lid, ret = u8(is_lidar), u8(did_return)
+    dist = _chk(distance.reshape(-1), "distance")
+    for v, n in ((lid, "is_lidar"), (ret, "did_return"), (dist, "distance")):
+        if v is not None and (v.shape[0] != R or v.device != s.device):
+            raise ValueError(f"{n}: expected one value per ray ({R}) on {s.device}")
+    dev = s.device
+    close = torch.empty((M,), dtype=torch.bool, device=dev) if want_mask else None
+    loss = torch.empty((R,), dtype=torch.float32, device=dev) if w is not None else None
+    gw = torch.empty((M,), dtype=torch.float32, device=dev) if (w is not None and want_grad) else None
+    if loss is None and M == 0:  # a mask of no samples: nothing to write
+        return close, None, None
+    some = lambda t: t if (t is not None and M) else None  # noqa: E731  (an empty tensor has no address)
+    launch("nrhip_packed_lidar_carving", some(s), some(e), some(w), seg, lid, ret, dist, float(carving_epsilon),
+           float(non_return_lidar_distance), R, M, some(close), loss, some(gw))
+    return close, loss, gw
+
+
 def _c_packed_rays(who: str, origins, directions, pixel_area, t_starts, t_ends, segments: Optional[Tensor] = None,
                    order: Optional[Tensor] = None):
     """-> (nrhip_packed_rays, the tensors it points to): per-RAY origins [R,3] / directions [R,3] / pixel_area [R], per-sample
