@@ -1110,6 +1110,61 @@ int nrhip_median_depth_packed(const float* weights, const float* t_starts, const
                               int64_t r, int64_t m, const float* thresholds /*host [k]*/, int32_t k,
                               float* out_depth /*[R,k]*/, int32_t* out_index /*[R,k] or NULL*/, void* stream);
 
+/* ---- surface normals from the geometry head (csrc/normals.hip; additive to ABI 520) -----------------------------------
+ * Definition.  For a sample with gaussian mean x = o + d (t0 + t1) / 2 (cameras/rays.py:109-124, M = 1):
+ *   geo  = the first output of the geometry MLP at x: the SDF, or the pre-exp logit when use_sdf = 0 (what nrhip_field_fwd
+ *          returns as sdf_or_raw);
+ *   g    = d geo / d x, through the rescale weights (neurad_encoding.py:297-304), the trilinear offsets
+ *          (encodings.py:425-464) and the scene contraction of mean AND std (spatial_distortions.py:126-141): the chain of
+ *          nrhip_encode_bwd_rays, whose origin gradient on [N,1] rays g is.  Subgradients are torch's: ReLU'(0) = 0,
+ *          clamp_min passes at equality, an inf-norm tie is split evenly over the tied axes, floor / ceil carry none;
+ *   n    = g / max(|g|_2, 1e-12) for an SDF (use_sdf = 1): it points towards free space; -g / max(|g|_2, 1e-12) in density
+ *          mode (fields/base_field.py:80-101).  A zero gradient gives a zero normal.
+ * Outputs, each optional (NULL skips the store; all NULL is NRHIP_ERR_INVALID_ARG): geo [N], gradient [N,3], normals
+ * [N,3], N = R * S at row ray * S + sample (dense) or N = M at the packed sample index.  With weights non-NULL ([R, S]
+ * with row stride weight_stride floats, 0 = S; packed: [M]) ray_normals [R,3] = sum_s w_s n_s, NOT normalised;
+ * ray_normals without weights is NRHIP_ERR_INVALID_ARG (unless the batch has no samples).  A sample with w == 0 adds nothing to its ray, not even a NaN, and
+ * when no per-sample output is asked for it is skipped entirely (no gathers; its interval may hold anything).  The order of
+ * the additions is fixed by the ray's own samples and the group width G alone (G lanes per ray, lane i adds the samples i,
+ * i + G, ... in that order, then an xor butterfly; G = the power of two >= S, at most 64; packed: S = ceil(M / R)), so a
+ * ray's row does not depend on its place in the batch; a ray or segment without samples gets zeros.
+ * rays: sample_stride is honoured (bin edges: starts = e, ends = e + 1, stride S + 1); order is a locality hint (the ray
+ * the group at a position works on), results do not depend on it.  Host-side checks: NULL descriptors; R == 0 is a no-op
+ * that reads no device pointer; S == 0 / M == 0 reads no sample pointer and zeroes ray_normals; samples without rays are
+ * NRHIP_ERR_INVALID_ARG, M >= 2^31 is NRHIP_ERR_UNSUPPORTED.  Packed segments are clamped into [0, M).
+ * Shapes: the (L, F, hidden width) of every `PerSample, Static, F32` row of csrc/render_variants.h with a two-layer
+ * geometry MLP L*F -> H -> out with biases (only row 0 of the last layer is read), fp32 and fp16 tables; anything
+ * else is NRHIP_ERR_UNSUPPORTED (compose nrhip_encode_fwd, nrhip_mlp_fwd, nrhip_mlp_bwd and nrhip_encode_bwd_rays
+ * instead).  The static scene only: a sample inside an actor's box would need that box's gradient rotated to the world.
+ * Numerics.  One thread per sample; products are fp32 VALU fma chains (no MFMA, no fp16 pairs).  Position, cells, offsets
+ * and the encoding row are nrhip_field_fwd's bits.  geo sums the same products as nrhip_field_fwd's sdf_or_raw from the
+ * same encoding bits in another order (fma chains here, the matrix cores there): the two agree within
+ * 2 (L F + H + 2) 2^-24 A_geo,  A_geo = |b1| + sum_j |w1_j| (|b0_j| + sum_k |W0_jk| |enc_k|), not to the bit.
+ * Error bound against the float64 chain on the fp32 primal (cells, offsets, masks as the reference's fp32 forward):
+ *   |g - g_ref| <= 2^-24 |g_ref| + NRHIP_NORMALS_C(L, F, H) 2^-24 A      per element,
+ * A = the same chain with every product and difference in absolute value, run on |W0|^T (|w1| mask) and |table|.  The
+ * constant is a first-order count of the roundings on the longest path of this formulation, not fitted to any output:
+ *   H          d geo / d enc_k: an fma chain over the H neurons;
+ *   F + 15     one level's sum over its features of (d geo / d enc) x (lerp derivative or rescaled value): 9 for the value
+ *              (3 complements, 3 x (mul, fma)), 3 for the rescale weight (product, v_rcp_f32), the two products;
+ *   L + 5      the level sum of those with scal_l w (and 2 scal_l w for the std term);
+ *   24         the contraction's backward (k, dk, d/dm of the std factor with cbrtf, the inf-norm share) and / scale;
+ *   196        the forward's std: sample and contraction take their cube roots from v_log_f32 / v_exp_f32 (<= 2^-19 relative
+ *              each; one in std, one squared in the contracted std: 3 x 32 units on s), which the clamped rescale weight
+ *              ~ 1 / s carries once and its derivative ~ 1 / s^2 twice (192), plus their own roundings (4).
+ * geo obeys the same form with A_geo.  A ReLU mask is a discrete choice: a sample with a hidden pre-activation inside its
+ * own rounding error may take the other branch, which the bound does not cover (nor a rescale clamp within 2^-19 of 1).
+ * The unit normal then differs per component by at most 2 |bound|_2 / |g| + 2^-22 (first order in the normalisation).
+ * No gradient flows through any output.  No atomics, no allocation, no host synchronisation: graph-capturable, and the same
+ * inputs give the same bits.                                                                                            */
+#define NRHIP_NORMALS_C(L, F, H) ((H) + (L) + (F) + 240)
+int nrhip_field_normals(const nrhip_field* f, const nrhip_rays* rays, const float* weights /*[R,weight_stride] or NULL*/,
+                        int32_t weight_stride, float* geo /*[N] or NULL*/, float* gradient /*[N,3] or NULL*/,
+                        float* normals /*[N,3] or NULL*/, float* ray_normals /*[R,3] or NULL*/, void* stream);
+int nrhip_field_normals_packed(const nrhip_field* f, const nrhip_packed_rays* rays, const float* weights /*[M] or NULL*/,
+                               float* geo /*[M] or NULL*/, float* gradient /*[M,3] or NULL*/,
+                               float* normals /*[M,3] or NULL*/, float* ray_normals /*[R,3] or NULL*/, void* stream);
+
 /* ---- camera image evaluation (csrc/image_eval.hip): PSNR and SSIM of NeuRADModel.get_image_metrics_and_images
  *      (models/neurad.py:265-266,585-586: torchmetrics' PeakSignalNoiseRatio(data_range=1.0) and
  *      structural_similarity_index_measure(preds, target) with its defaults) -----------------------------------------------

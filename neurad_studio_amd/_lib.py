@@ -132,6 +132,12 @@ IMAGE_STAT_ITEMS = 4096     # NRHIP_IMAGE_STAT_ITEMS
 LPIPS_IMAGE_CHANNELS = 4    # NRHIP_LPIPS_IMAGE_CHANNELS
 LPIPS_MIN_SIZE = 31         # NRHIP_LPIPS_MIN_SIZE
 LPIPS_EPS_INSIDE, LPIPS_EPS_OUTSIDE = 0, 1  # NRHIP_LPIPS_EPS_*
+
+
+def normals_c(num_levels: int, n_features: int, hidden_dim: int) -> int:  # NRHIP_NORMALS_C
+    return hidden_dim + num_levels + n_features + 240
+
+
 P, I32, I64, F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> argtypes : exactly the prototypes of include/neurad_hip.h (tests/test_abi.py cross-checks this
@@ -301,6 +307,8 @@ PROTOTYPES = {
     "nrhip_chamfer_distance": [P, I32, P, I64, P, I32, P, I64, I32, I32, P, P, P, P, I64, P],
     "nrhip_median_depth": [P, P, P, I64, I32, C.POINTER(F32), I32, P, P, P],
     "nrhip_median_depth_packed": [P, P, P, P, I64, I64, C.POINTER(F32), I32, P, P, P],
+    "nrhip_field_normals": [C.POINTER(Field), C.POINTER(Rays), P, I32, P, P, P, P, P],
+    "nrhip_field_normals_packed": [C.POINTER(Field), C.POINTER(PackedRays), P, P, P, P, P, P],
     "nrhip_image_metrics_workspace": [I32, I32, I32, C.POINTER(I64)],
     "nrhip_image_metrics": [P, P, I32, I32, I32, F32, P, P, I64, P, P],
     "nrhip_image_psnr": [P, P, I64, F32, P, P, P],

@@ -126,6 +126,7 @@ extern "C" const char* nrhip_last_error(void) { return nrhip::g_err; }
 //      additive, same number: camera image evaluation -- nrhip_image_metrics (+ _workspace), nrhip_image_psnr
 //      additive, same number: camera pose correction -- nrhip_pose_apply, nrhip_pose_apply_bwd (+ _workspace)
 //      additive, same number: median depth -- nrhip_median_depth, nrhip_median_depth_packed
+//      additive, same number: surface normals -- nrhip_field_normals, nrhip_field_normals_packed
 extern "C" int nrhip_version(void) { return 520; }
 
 extern "C" int nrhip_tuning_reload(void) {

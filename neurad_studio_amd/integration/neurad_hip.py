@@ -126,6 +126,11 @@ class NeuRADHipModelConfig(NeuRADModelConfig):
     With ``fused_lidar_eval`` a scan's outputs gain ``median_points`` and its metrics ``median_depth_median_l2``,
     ``median_depth_mean_rel_l2`` and ``median_chamfer_distance`` (SplatAD's names), all eight scalars in the one transfer.
     False: no key, launch or host read changes."""
+    normals: bool = False
+    """Eval outputs also carry ``normals`` [R,3] (csrc/normals.hip): the weighted sum of the non-sky samples' unit normals of
+    the geometry head (the SDF's gradient, towards free space; its negative in density mode), normalised as the
+    reference's NormalsRenderer does; one more launch per eval chunk.  Only the fused eval route produces the key, and only
+    for a static scene (dynamic actors are refused by name).  False: no key, no launch."""
     fused_image_eval: bool = False
     """Camera image metrics on the device (csrc/image_eval.hip, model_components/image_metrics.py): the image branch of
     get_image_metrics_and_images (models/neurad.py:568-587) takes ``psnr`` and ``ssim`` from one launch sequence and reads both
@@ -211,7 +216,7 @@ class NeuRADHipModel(FusedEvalMixin, FusedTrainMixin, NeuRADModel):
         cfg = self.config
         assert isinstance(self.field, HipNeuRADField), "config.field._target must be the HIP NeuRADField"
         self.fused_eval, self.early_stop_eps, self.order_rays = cfg.fused_eval, cfg.early_stop_eps, cfg.order_rays
-        self.fused_training, self.median_depth = cfg.fused_training, cfg.median_depth
+        self.fused_training, self.median_depth, self.normals = cfg.fused_training, cfg.median_depth, cfg.normals
         if cfg.fused_vgg_loss:
             from neurad_studio_amd.model_components.perceptual import VGGPerceptualLoss
 

@@ -52,6 +52,11 @@ class FusedEvalMixin:
     sample at which the accumulated weight reaches one half -- a ray that never gets there before the sky reports its last
     non-sky midpoint.  Computed from the weights the fused render kernel hands out, one more launch per chunk.  Only this
     fused eval route produces the key: off it (training, the operator-level path) it is absent."""
+    normals: bool = False
+    """True: the outputs also carry ``normals`` [R,3] (csrc/normals.hip): the weighted sum of the non-sky samples' unit
+    normals of the geometry head, from the weights the fused render kernel hands out, normalised as NormalsRenderer does
+    (/ (|.| + 1e-10)); one more launch per chunk, samples of weight zero cost nothing.  Like ``median_depth`` only this
+    fused eval route produces the key.  Refused for a field with dynamic actors or num_multisamples != 1."""
     reproduce_late_binding_quirk: bool = True
     """models/neurad.py:248 builds density_fns with a late-binding closure, so BOTH proposal rounds evaluate
     proposal_fields[1]; the fused sampler has to be told the same."""
@@ -63,6 +68,8 @@ class FusedEvalMixin:
     def fused_nff_outputs(self, ray_bundle) -> Dict[str, Tensor]:
         cfg = self.config
         sky = cfg.sampling.sky_distance
+        if self.normals:
+            self.field._check_normals("normals=True")
         self._scale_pixel_area(ray_bundle)
         _clamp_far_default_near(ray_bundle, sky)
         o, d = ray_bundle.origins.contiguous(), ray_bundle.directions.contiguous()
@@ -92,7 +99,7 @@ class FusedEvalMixin:
             ends = fr.ends[..., 0].clone()
             ends[:, -1] = sky  # the sky stretch of the last sample (models/neurad.py:451-455)
         order = ops.ray_order(o, d, self.field.hashgrid.static_scale) if self.order_rays else None
-        want_w = bool(cfg.normalize_depth) or self.median_depth
+        want_w = bool(cfg.normalize_depth) or self.median_depth or self.normals
         out = self.field.render(o, d, ray_bundle.pixel_area, starts, ends, return_weights=want_w,
                                 early_stop_eps=self.early_stop_eps, order=order, times=times, actor_cand=cand)
         features, depth, accumulation = out[:3]
@@ -105,6 +112,10 @@ class FusedEvalMixin:
         nff = {"features": features, "depth": depth, "accumulation": accumulation}
         if self.median_depth:  # over the non-sky samples, like the expected depth and its normalisation above
             nff["median_depth"] = ops.median_depth(out[3][:, :-1], starts[:, :-1], ends[:, :-1])
+        if self.normals:  # over the non-sky samples too; NormalsRenderer's normalisation of the weighted sum
+            n = self.field.normals(o, d, ray_bundle.pixel_area, starts[:, :-1], ends[:, :-1], weights=out[3][:, :-1],
+                                   want=("ray_normals",))["ray_normals"]
+            nff["normals"] = n / (torch.linalg.norm(n, dim=-1, keepdim=True) + 1e-10)
         for i, (pw, prs) in enumerate(zip(prop_weights, prop_ray_samples)):
             nff[f"prop_depth_{i}"] = self.renderer_depth(pw, prs)
         return nff

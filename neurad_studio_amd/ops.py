@@ -1640,6 +1640,107 @@ def field_fwd_train_packed(fs: FieldSpec, origins, directions, pixel_area, t_sta
     return out[:3], out[3:]
 
 
+# ---- surface normals from the geometry head (csrc/normals.hip; the contract: include/neurad_hip.h at nrhip_field_normals) ----
+NORMALS_OUTPUTS = ("geo", "gradient", "normals", "ray_normals")
+normals_c = _lib.normals_c  # NRHIP_NORMALS_C(L, F, H): the constant of the stated error bound
+
+
+def _normals_want(who: str, want, weights) -> Tuple[str, ...]:
+    want = tuple(want) if want is not None else ("gradient", "normals") + (("ray_normals",) if weights is not None else ())
+    bad = [k for k in want if k not in NORMALS_OUTPUTS]
+    if bad or not want:
+        raise ValueError(f"{who}: want must name some of {NORMALS_OUTPUTS}, got {want}")
+    if "ray_normals" in want and weights is None:
+        raise ValueError(f"{who}: ray_normals needs weights")
+    return want
+
+
+def _normals_outputs(want, n: int, r: int, device) -> dict:
+    mk = lambda *s: torch.empty(s, device=device, dtype=torch.float32)  # noqa: E731
+    shapes = {"geo": (n,), "gradient": (n, 3), "normals": (n, 3), "ray_normals": (r, 3)}
+    return {k: mk(*shapes[k]) for k in NORMALS_OUTPUTS if k in want}
+
+
+def field_normals(fs: FieldSpec, origins, directions, pixel_area, starts, ends, weights: Optional[Tensor] = None,
+                  want=None, order: Optional[Tensor] = None) -> dict:
+    """Normals of the geometry head at the samples' gaussian means, one kernel (nrhip_field_normals): ``geo`` [R,S] (the SDF
+    or the pre-exp logit), ``gradient`` [R,S,3] = d geo / d position, ``normals`` [R,S,3] = +-gradient / max(|gradient|,
+    1e-12) (+ for an SDF: towards free space; - in density mode) and, with ``weights`` [R,S] (a strided view is read in
+    place), ``ray_normals`` [R,3] = sum_s w_s normals_s (not normalised; samples of weight zero are skipped).  ``want``
+    names the outputs (default: gradient and normals, and ray_normals when weights are given) -> dict.  starts / ends as
+    ``field_fwd`` (views into bin edges are read in place); ``order``: locality hint.  No gradient flows through any
+    output.  Shapes the kernel is not instantiated for raise; ``field_normals_operators`` composes the same result."""
+    want = _normals_want("field_normals", want, weights)
+    r, keep = _c_rays(origins, directions, pixel_area, starts, ends, order)
+    f, keep2 = fs.c_field()
+    R, S = r.n_rays, r.n_samples
+    w, wstride = None, 0
+    if weights is not None:
+        if not isinstance(weights, Tensor) or not weights.is_cuda or weights.dtype != torch.float32:
+            raise _lib.NeuradHipError("field_normals: weights must be an fp32 GPU tensor (no CPU fallback)")
+        if weights.shape != (R, S):
+            raise ValueError(f"field_normals: weights must be [{R},{S}], got {tuple(weights.shape)}")
+        w = weights if (S <= 1 or weights.stride(1) == 1) and (R <= 1 or weights.stride(0) >= S) else weights.contiguous()
+        wstride = w.stride(0) if R > 1 and S > 0 else max(S, 1)
+    out = _normals_outputs(want, R * S, R, keep[0].device)
+    if any(v.numel() for v in out.values()):  # (an empty batch has nothing to write, and no address to write it to)
+        launch("nrhip_field_normals", f, r, w, int(wstride), out.get("geo"), out.get("gradient"), out.get("normals"),
+               out.get("ray_normals"))
+    return {k: (v if k == "ray_normals" else v.view(R, S, *v.shape[1:])) for k, v in out.items()}
+
+
+def field_normals_packed(fs: FieldSpec, origins, directions, pixel_area, t_starts, t_ends, segments,
+                         weights: Optional[Tensor] = None, want=None, order: Optional[Tensor] = None) -> dict:
+    """``field_normals`` on the march's packed samples (nrhip_field_normals_packed): per-RAY origins / directions [R,3] and
+    pixel_area [R], per-sample t_starts / t_ends [M], segments int64 [R+1], weights [M] -> ``geo`` [M], ``gradient`` [M,3],
+    ``normals`` [M,3] at the packed sample index, ``ray_normals`` [R,3] (zeros for a ray without samples)."""
+    want = _normals_want("field_normals_packed", want, weights)
+    r, keep = _c_packed_rays("field_normals_packed", origins, directions, pixel_area, t_starts, t_ends, segments, order)
+    f, keep2 = fs.c_field()
+    R, M = r.n_rays, r.n_samples
+    w = None if weights is None else _flat(weights, "weights", M)
+    out = _normals_outputs(want, M, R, keep[0].device)
+    if any(v.numel() for v in out.values()):
+        launch("nrhip_field_normals_packed", f, r, w if M else None, out.get("geo"), out.get("gradient"), out.get("normals"),
+               out.get("ray_normals"))
+    return out
+
+
+def field_normals_operators(fs: FieldSpec, origins, directions, pixel_area, starts, ends, weights: Optional[Tensor] = None,
+                            want=None) -> dict:
+    """The result of ``field_normals`` composed from four operator kernels, for any grid and geometry MLP: encode_fwd ->
+    mlp_fwd(save_hidden) -> mlp_bwd of a unit cotangent on column 0 -> encode_bwd_rays on [N,1] rays (the origin gradient
+    of a one-sample ray is the gradient at its position).  Two [N, L*F] round trips and the MLP's weight gradients, which
+    are dropped: the route for shapes the fused kernel does not cover and its timing baseline.  Same outputs and shapes."""
+    want = _normals_want("field_normals_operators", want, weights)
+    o, d, a = _ray_constants(origins, directions, pixel_area)
+    starts, ends = _chk(starts, "starts"), _chk(ends, "ends")
+    R, S = starts.shape
+    n = R * S
+    per = lambda t: t.repeat_interleave(S, dim=0) if S != 1 else t  # noqa: E731  (ray constants per sample)
+    o1, d1, a1, s1, e1 = per(o), per(d), per(a), starts.reshape(n, 1), ends.reshape(n, 1)
+    enc = encode_fwd(fs.grid, fs.table, fs.static_scale, o1, d1, a1, s1, e1)
+    y, hidden = mlp_fwd(enc, fs.geo_w, fs.geo_b, save_hidden=True)
+    cot = torch.zeros_like(y)
+    cot[:, 0] = 1.0
+    g_enc, _, _ = mlp_bwd(enc, hidden, cot, fs.geo_w, fs.geo_b)
+    g, _ = encode_bwd_rays(fs.grid, fs.table, fs.static_scale, o1, d1, a1, s1, e1, g_enc)
+    out = {}
+    if "geo" in want:
+        out["geo"] = y[:, 0].reshape(R, S)
+    if "gradient" in want:
+        out["gradient"] = g.reshape(R, S, 3)
+    if "normals" in want or "ray_normals" in want:
+        nrm = g / g.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+        nrm = (nrm if fs.use_sdf else -nrm).reshape(R, S, 3)
+        if "normals" in want:
+            out["normals"] = nrm
+        if "ray_normals" in want:
+            w = _chk(weights, "weights").reshape(R, S, 1)
+            out["ray_normals"] = torch.where(w != 0, w * nrm, torch.zeros_like(nrm)).sum(1)
+    return out
+
+
 def _packed_ray_of(who: str, r, ray_indices: Tensor) -> Tensor:
     """the march's ray_indices for the packed descriptor ``r``: int64 [M], one per sample"""
     ri = _chk(ray_indices.reshape(-1), "ray_indices", torch.int64)
