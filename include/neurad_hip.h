@@ -651,7 +651,10 @@ int nrhip_render_fwd_actors(const nrhip_field* f, const nrhip_actors* a, const n
  *      model_components/ray_samplers.py:483-566).  nerfacc is un-vendored and nothing in neurad-studio instantiates
  *      VolumetricSampler: the marching rule is this library's own statement (csrc/occgrid.hip header), parity
  *      unpinned.  Two passes: offsets == NULL -> per-ray counts; then, with the exclusive prefix sum of the counts as
- *      offsets, the packed (ray_indices, t_starts, t_ends) are written.                                        */
+ *      offsets, the packed (ray_indices, t_starts, t_ends) are written.
+ *      max_candidates (>= 1): the number of candidate intervals a ray may have, counted BEFORE the occupancy test --
+ *      candidates k = 0 .. max_candidates - 1 of the tiling are looked at, kept or not, and the march of the ray ends
+ *      there; a ray emits at most that many samples.  The same in all three march entry points.                */
 typedef struct {
   float aabb[6];            /* min xyz, max xyz */
   int32_t resolution;       /* res^3 cells, one level; cell index = (ix*res + iy)*res + iz */

@@ -4,6 +4,7 @@
 // here (and restated in oracle/neurad_oracle.py:occgrid_march) -- parity unpinned, see DESIGN.md:
 //   * the ray is clipped to [max(near_plane, t_min), min(far_plane, t_max)] and to the grid's AABB;
 //   * candidate intervals tile that range back to back: dt = max(t * cone_angle, step)  (uniform when cone_angle = 0);
+//     a ray has at most max_candidates of them, k = 0 .. max_candidates - 1, counted before the occupancy test;
 //   * a candidate is kept iff the cell containing its midpoint is occupied; kept intervals are emitted in order as
 //     packed (ray_index, t_start, t_end).
 // Multi-level grids (nrhip_occgrid_march_levels; the state and its update rule: occgrid_update.h): the ray is clipped to the
@@ -130,7 +131,7 @@ __device__ __forceinline__ void march_ray(const OccDev& g, const MarchBoxes& mb,
       const int k = k0 + lane;
       const float ts = m.at(k);
       const float te = fminf(m.at(k + 1), m.t_far);
-      const bool in_range = ts < m.t_far && te > ts;
+      const bool in_range = k < max_candidates && ts < m.t_far && te > ts;  // (the ballot below then ends the loop too)
       bool keep = in_range && occupied(g, o, d, 0.5f * (ts + te));
       if constexpr (BOXES) keep = keep || (in_range && nbox > 0 && in_candidate_box(mb, ray, nbox, o, d, ts, te));
       const unsigned long long mk = __ballot(keep);

@@ -1185,6 +1185,8 @@ def occgrid_march(grid: OccGridSpec, origins, directions, render_step_size, near
                   t_min=None, t_max=None, cone_angle=0.0, t_rand=None, max_candidates=1 << 16, actor_boxes=None):
     """Two-pass packed march: count -> exclusive prefix sum (one host sync for the allocation, like nerfacc) -> write.
     -> (ray_indices int64 [M], t_starts [M], t_ends [M], segments int64 [R+1])
+    max_candidates: candidate intervals per ray, counted before the occupancy test -- the first max_candidates intervals of
+    the ray's tiling are looked at, kept or not, and the ray ends there.
     actor_boxes = (ActorSpec, cand): the box-aware march (nrhip_occgrid_march_levels_actors) -- an interval whose cell is
     empty is kept all the same when its sample lies inside the box of one of the ray's candidate actors (cand = the per-RAY
     lists of ``actor_prepare`` / ``actor_prepare_line`` at the ray's time).  None: the plain march."""

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import occgrid_oracle as OO
+import occgrid_update_restatement as UR
 import scan_refs as SR
 import synth
 from gpu_util import cuda
@@ -27,13 +28,30 @@ def test_occgrid_march_vs_restatement(cone):
     t_max = synth.uniform((R,), 5.0, 60.0, 3)
     ri, ts, te, seg = ops.occgrid_march(ops.OccGridSpec(torch.from_numpy(aabb), cuda(binaries)), cuda(o), cuda(d), 0.25,
                                         near_plane=0.1, far_plane=40.0, t_max=cuda(t_max), cone_angle=cone)
-    rri, rts, rte = OO.occgrid_march(aabb, binaries, o, d, 0.25, 0.1, 40.0, None, t_max, cone)
     ri, ts, te = ri.cpu().numpy(), ts.cpu().numpy(), te.cpu().numpy()
-    # midpoint cell tests are discrete: allow a handful of boundary flips, compare the rest exactly
-    assert abs(len(ri) - len(rri)) <= 3
-    if len(ri) == len(rri):
-        np.testing.assert_array_equal(ri, rri)
-        assert np.abs(ts - rts).max() < 1e-4 and np.abs(te - rte).max() < 1e-4
+    # every candidate interval whose float64 midpoint is further than 1e-4 (in cells) from a cell face and from the box is
+    # kept or dropped exactly as the restatement says; at most 0.5 % may be that close (the three-level test's comparison)
+    m = UR.march_levels(aabb[None], binaries[None], o, d, 0.25, 0.1, 40.0, None, t_max, cone_angle=cone)
+    share = m["ambiguous"].mean()
+    print(f"{len(m['ray'])} candidates, {m['keep'].sum()} kept, {len(ri)} emitted, ambiguous share {share:.2e}")
+    assert len(m["ray"]) > 4000 and share <= 0.005
+    emitted = np.zeros(len(m["ray"]), bool)
+    first = np.searchsorted(m["ray"], np.arange(R + 1))
+    tol = 4 * 2.0 ** -23 * 40.0  # candidates are a step apart; powf may differ from the restatement's by an ulp or two
+    for r in range(R):
+        cand_ts, cand_te = m["t_start"][first[r]:first[r + 1]], m["t_end"][first[r]:first[r + 1]]
+        mine = ri == r
+        if not mine.any():
+            continue
+        assert len(cand_ts), f"ray {r}: samples from a ray the restatement never marches"
+        k = np.abs(ts[mine][:, None] - cand_ts[None]).argmin(1)
+        assert np.all(np.diff(k) > 0)
+        assert np.abs(ts[mine] - cand_ts[k]).max() <= tol and np.abs(te[mine] - cand_te[k]).max() <= tol
+        if cone == 0.0:
+            np.testing.assert_array_equal(ts[mine].view(np.int32), cand_ts[k].view(np.int32))
+        emitted[first[r] + k] = True
+    sure = ~m["ambiguous"]
+    np.testing.assert_array_equal(emitted[sure], m["keep"][sure])
     # invariants: packed order, segments, sorted non-overlapping intervals inside [near, min(far, t_max)]
     assert np.all(np.diff(ri) >= 0) and seg[-1].item() == len(ri)
     for r in np.unique(ri)[:50]:
