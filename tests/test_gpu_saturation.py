@@ -11,6 +11,7 @@ import pytest
 import neurad_oracle as O
 import synth
 from builders import sample_rays, shape_params
+from composite_refs import ref_composite
 from gpu_util import dev, host64, to_spec
 from gpu_util import ops  # noqa: F401  (fixture)
 from sharp_refs import R, SAMPLES, TINY, U, check, ref_alpha, ref_density, sharp_alphas, sharp_bins
@@ -82,17 +83,6 @@ def test_prop_weights_saturated(ops, S):
     gs = host64(ops.prop_weights_bwd(dev(e), dev(dens), dev(gw), dev(gd)))
     atol = TINY * (delta.astype(np.float64) + 1) * np.abs(G).max(-1, keepdims=True)
     check(gs, rgs, atol + gscale + gscale2, "dL/ddensity")
-
-
-def ref_composite(w32, feats, st, en):
-    """C2 in float64 from the kernel's fp32 weights"""
-    w = w32.astype(np.float64)
-    acc = w.sum(-1, keepdims=True)
-    w2 = w.copy()
-    w2[:, -1] += 1 - acc[:, 0]
-    f = feats.astype(np.float64)
-    mid = ((st + en) / np.float32(2)).astype(np.float64)
-    return w2, (w2[..., None] * f).sum(1), (w2[:, :-1] * mid[:, :-1]).sum(-1, keepdims=True), acc, mid
 
 
 @pytest.mark.parametrize("S", SAMPLES)

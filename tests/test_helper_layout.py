@@ -1,5 +1,5 @@
 """Test modules are not libraries: what tests, scripts and oracle tools share lives in plain helper modules (builders.py,
-gpu_util.py, sharp_refs.py, sampler_refs.py, decoder_refs.py, mlp_refs.py, loss_refs.py, adam_refs.py, grad_edge_refs.py, scan_refs.py, actor_refs.py, table_grad_refs.py, proposal_refs.py, raygen_refs.py, plugin_harness.py, host_gate.py, synth.py, the restatements), so that editing
+gpu_util.py, sharp_refs.py, sampler_refs.py, decoder_refs.py, mlp_refs.py, loss_refs.py, adam_refs.py, grad_edge_refs.py, scan_refs.py, actor_refs.py, table_grad_refs.py, proposal_refs.py, raygen_refs.py, composite_refs.py, plugin_harness.py, host_gate.py, synth.py, the restatements), so that editing
 a test cannot break a tool or another test."""
 import ast
 import glob
