@@ -14,6 +14,10 @@
  *    thread-local human-readable message for the last failing call on this thread.
  *  - Floating point is fp32 end to end (the parity target is the reference's implementation="torch"
  *    path).  Hash tables may be stored as fp32 (param_dtype 0) or fp16 (param_dtype 1, BASELINE config 5).
+ *  - Hash tables handed to a lookup (nrhip_hashgrid_fwd, nrhip_encode_fwd, nrhip_proposal_density_fwd) must be 16-byte
+ *    aligned: entries are fetched with vector loads of up to 16 bytes.  An fp32 table with 1 feature per level must have
+ *    log2_table_size >= 2 there (its corners are read as aligned 4-entry blocks).  Both are checked on the host:
+ *    NRHIP_ERR_INVALID_ARG for the alignment, NRHIP_ERR_UNSUPPORTED for the size.
  *  - Row-major, innermost dimension last.  R = rays, S = samples per ray, N = R*S, L = levels,
  *    F = features per level, T = 2^log2_table_size entries per level.
  */

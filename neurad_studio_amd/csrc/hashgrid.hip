@@ -381,12 +381,25 @@ __global__ __launch_bounds__(256) void proposal_density_bwd_kernel(GridDev g, co
 
 using namespace nrhip;
 
+// What the forward lookups ask of a table beyond validate_grid.  Entries are fetched with vector loads of up to 16 bytes
+// from offsets relative to `table`, so the table itself must lie on the 16-byte grid.  F = 1, fp32: load_corners_f1
+// (common.h) reads the aligned 4-entry block around a row; a level of 2 entries is half a block, and the block of the last
+// level of a grid with an odd number of levels would end 8 bytes past the table.
+static int validate_lookup_table(const char* who, const nrhip_grid* g, const void* table) {
+  NR_REQUIRE((reinterpret_cast<uintptr_t>(table) & 15) == 0, NRHIP_ERR_INVALID_ARG, "%s: the table must be 16-byte aligned", who);
+  NR_REQUIRE(!(g->n_features == 1 && g->param_dtype == 0 && g->log2_table_size < 2), NRHIP_ERR_UNSUPPORTED,
+             "%s: an fp32 table with 1 feature per level needs log2_table_size >= 2 (16-byte corner loads), got %d", who,
+             g->log2_table_size);
+  return NRHIP_OK;
+}
+
 extern "C" int nrhip_hashgrid_fwd(const nrhip_grid* g, const void* table, const float* x, int64_t n, float* out,
                                   void* stream) {
   if (int e = validate_grid(g)) return e;
   NR_REQUIRE(n >= 0, NRHIP_ERR_INVALID_ARG, "hashgrid_fwd: negative n");
   if (n == 0) return NRHIP_OK;
   NR_REQUIRE(table && x && out, NRHIP_ERR_INVALID_ARG, "hashgrid_fwd: null pointer");
+  if (int e = validate_lookup_table("hashgrid_fwd", g, table)) return e;
   const GridDev gd = to_dev(*g);
   const int blocks = grid_for(n * gd.L, 256);
   dispatch_f(gd.F, gd.dtype == 1, [&](auto F, auto H) {
@@ -413,6 +426,7 @@ extern "C" int nrhip_encode_fwd(const nrhip_grid* g, const void* table, float st
   if (int e = validate_grid(g)) return e;
   if (int e = validate_rays(rays)) return e;
   NR_REQUIRE(table && out && static_scale > 0.f, NRHIP_ERR_INVALID_ARG, "encode_fwd: bad argument");
+  if (int e = validate_lookup_table("encode_fwd", g, table)) return e;
   const int64_t n = rays->n_rays * rays->n_samples;
   if (n == 0) return NRHIP_OK;
   const GridDev gd = to_dev(*g);
@@ -456,6 +470,7 @@ extern "C" int nrhip_proposal_density_fwd(const nrhip_proposal* p, const nrhip_r
              "proposal_density: features_per_level must be 1 (neurad_field.py:166), got %d", p->grid.n_features);
   NR_REQUIRE(p->table && p->decoder_weight && density && p->static_scale > 0.f, NRHIP_ERR_INVALID_ARG,
              "proposal_density_fwd: bad argument");
+  if (int e = validate_lookup_table("proposal_density_fwd", &p->grid, p->table)) return e;
   const int64_t n = rays->n_rays * rays->n_samples;
   if (n == 0) return NRHIP_OK;
   const GridDev gd = to_dev(p->grid);

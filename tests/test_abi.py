@@ -143,6 +143,27 @@ def _grid(L, F, lg):
     return g
 
 
+def test_lookups_check_the_table_on_the_host(lib):
+    """the forward lookups fetch entries with vector loads of up to 16 bytes: a table off the 16-byte grid is refused, and so is
+    an fp32 table with one feature per level and 2-entry levels (its corners are read as aligned 4-entry blocks, which would
+    reach past the last level); fp16 storage reads aligned pairs and passes"""
+    from neurad_studio_amd import _lib
+
+    one, off = ctypes.c_void_p(0x1000), ctypes.c_void_p(0x1004)  # validation fails before anything is dereferenced
+    with pytest.raises(_lib.NeuradHipError, match="hashgrid_fwd: the table must be 16-byte aligned"):
+        _lib.call("nrhip_hashgrid_fwd", ctypes.byref(_grid(3, 1, 8)), off, one, 4, one, None)
+    with pytest.raises(_lib.NeuradHipError, match="hashgrid_fwd: an fp32 table with 1 feature per level needs log2_table_size >= 2"):
+        _lib.call("nrhip_hashgrid_fwd", ctypes.byref(_grid(3, 1, 1)), one, one, 4, one, None)
+    r = _lib.Rays()
+    r.n_rays, r.n_samples = 3, 5
+    r.origins = r.directions = r.pixel_area = r.starts = r.ends = 0x1000
+    with pytest.raises(_lib.NeuradHipError, match="encode_fwd: the table must be 16-byte aligned"):
+        _lib.call("nrhip_encode_fwd", ctypes.byref(_grid(3, 2, 8)), off, 1.0, ctypes.byref(r), one, None)
+    with pytest.raises(_lib.NeuradHipError, match="encode_fwd: an fp32 table with 1 feature"):
+        _lib.call("nrhip_encode_fwd", ctypes.byref(_grid(3, 1, 1)), one, 1.0, ctypes.byref(r), one, None)
+    assert _lib.call("nrhip_hashgrid_fwd", ctypes.byref(_grid(3, 1, 1)), one, one, 0, one, None) is None  # n = 0: nothing is read
+
+
 def test_table_gradient_workspace_query_is_host_logic(lib):
     """nrhip_encode_bwd_binned_workspace needs no GPU: one record slot per corner term ({entry, F values}, 8 per sample and level) --
     at F = 1 per x-pair of corner terms ({entry | xm, 2 values}, 4 per sample and level; the scalings here stay below every
