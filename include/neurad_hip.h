@@ -1142,7 +1142,7 @@ int nrhip_median_depth_packed(const float* weights, const float* t_starts, const
  * Shapes: the (L, F, hidden width) of every `PerSample, Static, F32` row of csrc/render_variants.h with a two-layer
  * geometry MLP L*F -> H -> out with biases (only row 0 of the last layer is read), fp32 and fp16 tables; anything
  * else is NRHIP_ERR_UNSUPPORTED (compose nrhip_encode_fwd, nrhip_mlp_fwd, nrhip_mlp_bwd and nrhip_encode_bwd_rays
- * instead).  The static scene only: a sample inside an actor's box would need that box's gradient rotated to the world.
+ * instead).  The static scene only: nrhip_field_normals_actors (below) rotates an in-box sample's gradient to the world.
  * Numerics.  One thread per sample; products are fp32 VALU fma chains (no MFMA, no fp16 pairs).  Position, cells, offsets
  * and the encoding row are nrhip_field_fwd's bits.  geo sums the same products as nrhip_field_fwd's sdf_or_raw from the
  * same encoding bits in another order (fma chains here, the matrix cores there): the two agree within
@@ -1171,6 +1171,47 @@ int nrhip_field_normals(const nrhip_field* f, const nrhip_rays* rays, const floa
 int nrhip_field_normals_packed(const nrhip_field* f, const nrhip_packed_rays* rays, const float* weights /*[M] or NULL*/,
                                float* geo /*[M] or NULL*/, float* gradient /*[M,3] or NULL*/,
                                float* normals /*[M,3] or NULL*/, float* ray_normals /*[R,3] or NULL*/, void* stream);
+
+/* ---- surface normals in a scene with dynamic actors (csrc/normals.hip; additive) -----------------------------------------
+ * The same quantity where the scene has actors.  cand_count [R], cand_actor [R,K], cand_w2b [R,K,12] are one candidate list
+ * per RAY, K = actors->max_candidates: what nrhip_actor_prepare / nrhip_actor_prepare_edited write (for packed samples: on
+ * the ray's line).  ray_flip [R] = +-1 (the training x flip) or NULL.
+ * Definition.  A sample whose gaussian mean x lies in no box: g = d geo / d x exactly as nrhip_field_normals defines it, and
+ * geo / gradient / normals have that kernel's bits.  A sample inside a box takes its encoding row from the actor's grid
+ * (neurad_encoding.py:173-187), so geo is the geometry MLP on the row nrhip_actor_encode writes, and the chain is
+ *   p = W x + t (the ray's world2box row of that actor, after the eval-time edit if one was prepared), p.x *= f,
+ *   ScaledSceneContraction(inf) of (p, std) with the ACTOR scale (std is the sample's own, not transformed),
+ *   the actor's La x F grid with its own scalings and rescale weights, zero columns from La * F on, the same MLP;
+ *   g_world = W^T diag(f, 1, 1) g_box,   g_box = d geo / d p through offsets, rescale weights and the contraction of mean
+ *   and std, with the subgradients above.  The static table is not gathered for such a sample.
+ * Winner only.  Where several boxes contain a sample the forward uses the highest actor index (nrhip_actor_encode), and the
+ * normal is the derivative of that value: the winner's chain.  (The reference's autograd also hands gradient to the
+ * overwritten duplicates, an artefact of index_put's backward and not a derivative of the output; this deviates on purpose.)
+ * Outputs: geo, gradient, normals, ray_normals as nrhip_field_normals (order of additions, G, zero-weight skipping, S == 0 /
+ * M == 0 / R == 0 included), and two more, optional and per sample: hit [N] int32 = the winning actor or -1, bit for bit
+ * nrhip_actor_encode's; box_position [N,3] = the fp32 box-frame position after the flip at which the kernel differentiated,
+ * left untouched where hit < 0.  Asking for either makes every sample evaluated, as a per-sample output does.
+ * Host-side checks, in this order: field as nrhip_field_normals (NULL: INVALID_ARG; shape: UNSUPPORTED); every output NULL
+ * (hit and box_position included): INVALID_ARG; NULL actors descriptor, one of its arrays or a candidate pointer:
+ * INVALID_ARG; an actor grid with another F or storage type than the static grid, or more levels: UNSUPPORTED; then the
+ * rays: R == 0 is a no-op that reads no device pointer.
+ * Shapes: the (L, F, hidden width) of every `Composite, Actors, F32` row of csrc/render_variants.h, fp32 and fp16 tables.
+ * Error bound for an in-box sample, against the float64 chain on the fp32 primal -- the kernel's own box_position and hit
+ * and the fp32 cand_w2b row:
+ *   |g - g_ref| <= 2^-24 |g_ref| + NRHIP_NORMALS_ACTORS_C(La, F, H) 2^-24 A,     A = |W|^T A_box,
+ * A_box the absolute-value chain of nrhip_field_normals on the actor grid.  The constant is NRHIP_NORMALS_C's count with the
+ * actor grid's La levels, plus 1 for the flip and 5 for a row of the W^T product (3 products, 2 sums).                     */
+#define NRHIP_NORMALS_ACTORS_C(La, F, H) (NRHIP_NORMALS_C(La, F, H) + 6)
+int nrhip_field_normals_actors(const nrhip_field* f, const nrhip_actors* actors, const nrhip_rays* rays,
+                               const int32_t* cand_count, const int32_t* cand_actor, const float* cand_w2b,
+                               const float* ray_flip /*[R] or NULL*/, const float* weights /*[R,weight_stride] or NULL*/,
+                               int32_t weight_stride, float* geo, float* gradient, float* normals, float* ray_normals,
+                               int32_t* hit /*[N] or NULL*/, float* box_position /*[N,3] or NULL*/, void* stream);
+int nrhip_field_normals_packed_actors(const nrhip_field* f, const nrhip_actors* actors, const nrhip_packed_rays* rays,
+                                      const int32_t* cand_count, const int32_t* cand_actor, const float* cand_w2b,
+                                      const float* ray_flip /*[R] or NULL*/, const float* weights /*[M] or NULL*/,
+                                      float* geo, float* gradient, float* normals, float* ray_normals,
+                                      int32_t* hit /*[M] or NULL*/, float* box_position /*[M,3] or NULL*/, void* stream);
 
 /* ---- camera image evaluation (csrc/image_eval.hip): PSNR and SSIM of NeuRADModel.get_image_metrics_and_images
  *      (models/neurad.py:265-266,585-586: torchmetrics' PeakSignalNoiseRatio(data_range=1.0) and

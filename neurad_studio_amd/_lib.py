@@ -138,6 +138,10 @@ def normals_c(num_levels: int, n_features: int, hidden_dim: int) -> int:  # NRHI
     return hidden_dim + num_levels + n_features + 240
 
 
+def normals_actors_c(actor_levels: int, n_features: int, hidden_dim: int) -> int:  # NRHIP_NORMALS_ACTORS_C
+    return normals_c(actor_levels, n_features, hidden_dim) + 6
+
+
 P, I32, I64, F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> argtypes : exactly the prototypes of include/neurad_hip.h (tests/test_abi.py cross-checks this
@@ -309,6 +313,10 @@ PROTOTYPES = {
     "nrhip_median_depth_packed": [P, P, P, P, I64, I64, C.POINTER(F32), I32, P, P, P],
     "nrhip_field_normals": [C.POINTER(Field), C.POINTER(Rays), P, I32, P, P, P, P, P],
     "nrhip_field_normals_packed": [C.POINTER(Field), C.POINTER(PackedRays), P, P, P, P, P, P],
+    "nrhip_field_normals_actors": [C.POINTER(Field), C.POINTER(Actors), C.POINTER(Rays), P, P, P, P, P, I32, P, P, P, P, P, P,
+                                   P],
+    "nrhip_field_normals_packed_actors": [C.POINTER(Field), C.POINTER(Actors), C.POINTER(PackedRays), P, P, P, P, P, P, P, P,
+                                          P, P, P, P],
     "nrhip_image_metrics_workspace": [I32, I32, I32, C.POINTER(I64)],
     "nrhip_image_metrics": [P, P, I32, I32, I32, F32, P, P, I64, P, P],
     "nrhip_image_psnr": [P, P, I64, F32, P, P, P],

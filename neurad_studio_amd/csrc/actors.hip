@@ -5,23 +5,9 @@
 // The per-sample geometry (find_hit, sample_hits) and the pair kernels are written once over both sample layouts: dense
 // [R,S] rows, and the occupancy march's packed samples with their ray named by ray_of [M] (nrhip_actor_find_packed,
 // nrhip_actor_pair_positions_fwd_packed / _bwd_packed) -- the same arithmetic, so the layouts agree bit for bit.
-#include "common.h"
+#include "actors_dev.h"  // ActorsDev, ActorHit, find_hit, to_dev(nrhip_actors): shared with normals.hip
 
 namespace nrhip {
-
-struct ActorsDev {
-  int A, Tn;
-  const float* ts;
-  const float* pos;
-  const float* rot6;
-  const uint8_t* present;
-  const float* bounds;
-  GridDev grid;
-  const void* const* tables;
-  float scale;
-  const float* flip;  // [R] +-1 per ray (training-mode x flip, neurad_encoding.py:212-219) or NULL
-  int K;              // row length of the per-ray candidate lists (nrhip_actors.max_candidates; == A: no ray overflows)
-};
 
 // Eval-time actor edit (DynamicActors.edit_boxes2world, model_components/dynamic_actors.py:181-249, the flatten=False branch the
 // hash encoding reads): the viewer's sliders and the actor-shift FID evaluation (pipelines/ad_pipeline.py:476-480) move /
@@ -132,51 +118,6 @@ __global__ __launch_bounds__(256) void actor_prepare_kernel(ActorsDev a, RaysDev
     count += __popcll(m);
   }
   if (lane == 0) cand_count[ray] = min(count, a.K);
-}
-
-// shared per-sample part: which actor (if any) contains the sample; box-frame position/direction
-struct ActorHit {
-  int actor;  // -1: none
-  float px, py, pz, std, dx, dy, dz;
-};
-
-// RD: RaysDev (row i = ray * S + s) or PackedRaysDev (row i = packed sample index, its ray from ray_of): one body, so the two
-// layouts agree bit for bit on every sample (common.h: ray_sample_ray_of_row / ray_sample_interval_of_row)
-template <class RD>
-__device__ __forceinline__ ActorHit find_hit(const ActorsDev& a, const RD& r, const int64_t* ray_of, int64_t i,
-                                             const int32_t* cand_count, const int32_t* cand_actor,
-                                             const float* cand_w2b) {
-  ActorHit h;
-  h.actor = -1;
-  const int64_t ray = ray_sample_ray_of_row(r, ray_of, i);
-  const int n = cand_count[ray];
-  h.dx = r.d[3 * ray], h.dy = r.d[3 * ray + 1], h.dz = r.d[3 * ray + 2];
-  if (n == 0) return h;
-  const int64_t iv = ray_sample_interval_of_row(r, ray, i);
-  const SamplePos g = sample_gaussian(r.o[3 * ray], r.o[3 * ray + 1], r.o[3 * ray + 2], h.dx, h.dy, h.dz, r.area[ray],
-                                      r.starts[iv], r.ends[iv]);
-  h.std = g.std;
-  const float* wsel = nullptr;
-  for (int c = 0; c < n; ++c) {  // ascending actor index; the LAST hit wins (neurad_encoding.py:184-185 on CPU)
-    const float* w = cand_w2b + (ray * a.K + c) * 12;
-    const int act = cand_actor[ray * a.K + c];
-    float bx, by, bz;
-    if (box_contains(w, a.bounds + 3 * act, g.x, g.y, g.z, bx, by, bz)) {
-      h.actor = act, h.px = bx, h.py = by, h.pz = bz, wsel = w;
-    }
-  }
-  if (h.actor >= 0) {
-    float ddx = wsel[0] * h.dx + wsel[1] * h.dy + wsel[2] * h.dz;
-    float ddy = wsel[4] * h.dx + wsel[5] * h.dy + wsel[6] * h.dz;
-    float ddz = wsel[8] * h.dx + wsel[9] * h.dy + wsel[10] * h.dz;
-    const float nn = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz) + 1e-7f;  // neurad_encoding.py:207
-    h.dx = ddx / nn, h.dy = ddy / nn, h.dz = ddz / nn;
-    if (a.flip) {
-      const float f = a.flip[ray];
-      h.px *= f, h.dx *= f;
-    }
-  }
-  return h;
 }
 
 template <int F, bool HALF>
@@ -290,21 +231,6 @@ __global__ __launch_bounds__(256) void actor_find_packed_kernel(ActorsDev a, Pac
   const ActorHit h = find_hit(a, r, ray_of, i, cand_count, cand_actor, cand_w2b);
   hit[i] = h.actor;
   if (dirs) dirs[3 * i] = h.dx, dirs[3 * i + 1] = h.dy, dirs[3 * i + 2] = h.dz;
-}
-
-static int to_dev(const nrhip_actors* a, ActorsDev& d) {
-  NR_REQUIRE(a, NRHIP_ERR_INVALID_ARG, "actors descriptor is NULL");
-  NR_REQUIRE(a->n_actors >= 1 && a->n_times >= 1, NRHIP_ERR_INVALID_ARG, "actors: need >= 1 actor and timestamp");
-  NR_REQUIRE(a->timestamps && a->positions && a->rotations_6d && a->present && a->bounds, NRHIP_ERR_INVALID_ARG,
-             "actors descriptor has a NULL pointer");
-  d.A = a->n_actors, d.Tn = a->n_times;
-  d.K = a->max_candidates > 0 ? a->max_candidates : NRHIP_DEFAULT_ACTOR_CANDIDATES;
-  d.ts = a->timestamps, d.pos = a->positions, d.rot6 = a->rotations_6d, d.present = a->present, d.bounds = a->bounds;
-  d.grid = to_dev(a->grid);
-  d.tables = a->tables;
-  d.scale = a->actor_scale;
-  d.flip = nullptr;
-  return NRHIP_OK;
 }
 
 }  // namespace nrhip

@@ -21,21 +21,48 @@
 // atomics, nothing allocated, no host synchronisation: every output element has one writer and the launch can be captured.
 // A ray's row depends on its own samples and on G alone.  One kernel body for dense ([R,S] with a row stride) and packed
 // (segments) samples through the ray_sample_* accessors of common.h.
-#include "common.h"
+#include "actors_dev.h"
 #include "render_variants.h"
+#include <type_traits>
 
 namespace nrhip {
 namespace {
 
+// What a lane of the actor form walks instead of the static table when its sample lies in a box: that actor's table, the
+// actor grid (La <= L levels; its scalings are zero from La on, so those levels add nothing) and the actor scale.
+struct BoxWalk {
+  bool in;
+  const void* table;
+  float scale;
+};
+
+// (The actor form's zero scratch rests on this barrier and on how one compiler version treats it: after a compiler upgrade
+//  re-check the table of profiles/LEDGER.md with -Rpass-analysis=kernel-resource-usage.)
+template <class T>
+__device__ __forceinline__ T pin_uniform(T v) {  // a wave-uniform value, held in a scalar register from here on
+  asm volatile("" : "+s"(v));
+  return v;
+}
+
 // d geo / d mean of one sample and geo itself.  w0 [H, L*F], b0 [H], w1 [H] = row 0 of the last layer, b1 its bias: all read
-// at wave-uniform addresses.
-template <int L, int F, int H, bool HALF>
-__device__ __forceinline__ void normals_of_sample(const GridDev& grid, const void* __restrict__ table, float scale,
+// at wave-uniform addresses.  ACT: the lane's table, scalings, table size and scale are selected per lane by bw.in (the
+// static form ignores bw); gs is then the box-frame position with the sample's own std, and g the box-frame gradient.
+template <int L, int F, int H, bool HALF, bool ACT>
+__device__ __forceinline__ void normals_of_sample(const GridDev& grid, const void* __restrict__ table_, float scale_,
                                                   const float* __restrict__ w0, const float* __restrict__ b0,
                                                   const float* __restrict__ w1, const float* __restrict__ b1,
-                                                  const SamplePos& gs, float& geo, float (&g)[3]) {
+                                                  const SamplePos& gs, const GridDev& agrid, const BoxWalk& bw, float& geo,
+                                                  float (&g)[3]) {
   constexpr int LF = L * F;
-  const uint32_t mask = (1u << grid.log2T) - 1u;
+  const bool box = ACT && bw.in;
+  // (the actor grid's members are pinned in scalar registers before the select: left alone, the compiler selects between
+  //  the two ADDRESSES in the kernel arguments and loads once, for which it copies every argument to scratch)
+  const int log2T = box ? pin_uniform(agrid.log2T) : grid.log2T;
+  const void* table = box ? bw.table : table_;
+  const float scale = box ? bw.scale : scale_;
+  const int La = box ? pin_uniform(agrid.L) : L;  // (levels from La on are not gathered: F.pad's zero columns)
+  auto scal = [&](int l) { return box ? pin_uniform(agrid.scal[l]) : grid.scal[l]; };
+  const uint32_t mask = (1u << log2T) - 1u;
   const SamplePos p = contract_gaussian(gs.x, gs.y, gs.z, gs.std, scale);
   float enc[LF], Dx[LF], Dy[LF], Dz[LF];
   // the gathers of LG levels are in flight together (64 result registers; 32 at F = 2, where 16 levels' index registers
@@ -50,16 +77,23 @@ __device__ __forceinline__ void normals_of_sample(const GridDev& grid, const voi
 #pragma unroll
     for (int i = 0; i < LG; ++i) {
       if (l0 + i >= L) break;
-      c[i] = hash_corners(p.x, p.y, p.z, grid.scal[l0 + i], mask);
+      c[i] = hash_corners(p.x, p.y, p.z, scal(l0 + i), mask);
+      if (ACT && l0 + i >= La) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) Entry<F, HALF>::load(table, ((uint32_t)(l0 + i) << grid.log2T) + c[i].idx[k], f[i][k]);
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+          for (int q = 0; q < F; ++q) f[i][k][q] = 0.f;
+        continue;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) Entry<F, HALF>::load(table, ((uint32_t)(l0 + i) << log2T) + c[i].idx[k], f[i][k]);
     }
 #pragma unroll
     for (int i = 0; i < LG; ++i) {
       if (l0 + i >= L) break;
       const int l = l0 + i;
       const float ox = c[i].ox, oy = c[i].oy, oz = c[i].oz, mx = 1.f - ox, my = 1.f - oy, mz = 1.f - oz;
-      const float rw = rescale_weight(grid.scal[l], p.std);
+      const float rw = rescale_weight(scal(l), p.std);
 #pragma unroll
       for (int q = 0; q < F; ++q) {
         const float(&v)[8][F] = f[i];
@@ -102,7 +136,7 @@ __device__ __forceinline__ void normals_of_sample(const GridDev& grid, const voi
   float gx = 0.f, gy = 0.f, gz = 0.f, gstd = 0.f;
 #pragma unroll
   for (int l = 0; l < L; ++l) {
-    const float sc = grid.scal[l];
+    const float sc = scal(l);
     float dx = 0.f, dy = 0.f, dz = 0.f, dv = 0.f;
 #pragma unroll
     for (int q = 0; q < F; ++q) {
@@ -137,20 +171,38 @@ __device__ __forceinline__ int64_t weight_index(const PackedRaysDev& r, int64_t 
   return ray_sample_row(r, ray, s);
 }
 
+// The actor form's extra arguments: the per-RAY candidate lists of nrhip_actor_prepare (a.K entries a row), the actors
+// (a.flip: the per-ray x flip or NULL) and the two optional per-sample outputs.  The static form carries none of it.
+struct NoActors {};
+struct ActorArgs {
+  ActorsDev a;
+  const int32_t* cand_count;
+  const int32_t* cand_actor;
+  const float* cand_w2b;
+  int32_t* hit;   // [N] or NULL
+  float* boxpos;  // [N,3] or NULL
+};
+
+__device__ __forceinline__ bool actor_outputs(const NoActors&) { return false; }
+__device__ __forceinline__ bool actor_outputs(const ActorArgs& a) { return a.hit || a.boxpos; }
+
 // L, F, H: a `PerSample, Static, F32` row of render_variants.h; HALF: fp16 table; Rays: RaysDev or PackedRaysDev.
 // sign: +1 (SDF: the normal points towards free space) or -1 (density mode).  weights (optional) with its row stride (dense),
 // geo / grad / nrm / ray_nrm: optional outputs.  G: lanes per ray, a power of two <= 64.
-template <int L, int F, int H, bool HALF, class Rays>
+// Act: NoActors (the static form) or ActorArgs -- the actor form, an instantiation of its own (the (L, F, H) of a
+// `Composite, Actors, F32` row of render_variants.h), so the static kernels keep their registers.
+template <int L, int F, int H, bool HALF, class Rays, class Act>
 __global__ __launch_bounds__(256) void field_normals_kernel(
     GridDev grid, const void* __restrict__ table, float scale, const float* __restrict__ w0, const float* __restrict__ b0,
     const float* __restrict__ w1, const float* __restrict__ b1, float sign, Rays r, const int32_t* __restrict__ order,
     const float* __restrict__ weights, int wstride, int G, float* __restrict__ geo, float* __restrict__ grad,
-    float* __restrict__ nrm, float* __restrict__ ray_nrm) {
+    float* __restrict__ nrm, float* __restrict__ ray_nrm, Act act) {
+  constexpr bool ACT = !std::is_same<Act, NoActors>::value;
   const int lane = threadIdx.x & 63;
   const int sub = lane & (G - 1);
   const int64_t slot = ((int64_t)blockIdx.x * 256 + threadIdx.x) / G;
   const bool live_ray = slot < r.R;
-  const bool per_sample = geo || grad || nrm;
+  const bool per_sample = geo || grad || nrm || actor_outputs(act);
   float acc[3] = {0.f, 0.f, 0.f};
   int64_t ray = slot;
   if (live_ray) {
@@ -162,6 +214,8 @@ __global__ __launch_bounds__(256) void field_normals_kernel(
     const float dx_ = r.d[3 * ray], dy_ = r.d[3 * ray + 1], dz_ = r.d[3 * ray + 2];
     const float area = r.area[ray];
     const int n = ray_sample_count(r, ray);
+    int ncand = 0;
+    if constexpr (ACT) ncand = act.cand_count[ray];
     for (int s = sub; s < n; s += G) {
       float w = 0.f;
       if (weights) {
@@ -171,13 +225,39 @@ __global__ __launch_bounds__(256) void field_normals_kernel(
       const int64_t ti = ray_sample_interval(r, ray, s);
       const SamplePos gs = sample_gaussian(ox_, oy_, oz_, dx_, dy_, dz_, area, r.starts[ti], r.ends[ti]);
       float v, g[3];
-      normals_of_sample<L, F, H, HALF>(grid, table, scale, w0, b0, w1, b1, gs, v, g);
+      int hit_actor = -1;
+      float bp[3] = {0.f, 0.f, 0.f};
+      if constexpr (ACT) {
+        // actors.hip's hit test on the ray's candidates; an in-box lane walks its actor's table at the box-frame position
+        // (the sample's own std), and its box-frame gradient goes back through the flip and W^T
+        ActorHit h;
+        h.actor = -1, h.dx = dx_, h.dy = dy_, h.dz = dz_;
+        const float* wsel = ncand ? find_hit_core(act.a, ray, ncand, gs, act.cand_actor, act.cand_w2b, h) : nullptr;
+        const bool in_box = h.actor >= 0;
+        SamplePos q = gs;
+        if (in_box) q.x = h.px, q.y = h.py, q.z = h.pz;
+        const BoxWalk bw{in_box, in_box ? act.a.tables[h.actor] : nullptr, act.a.scale};
+        normals_of_sample<L, F, H, HALF, true>(grid, table, scale, w0, b0, w1, b1, q, act.a.grid, bw, v, g);
+        if (in_box) {
+          const float bx = act.a.flip ? g[0] * act.a.flip[ray] : g[0], by = g[1], bz = g[2];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) g[c] = wsel[c] * bx + wsel[4 + c] * by + wsel[8 + c] * bz;
+          bp[0] = h.px, bp[1] = h.py, bp[2] = h.pz;
+        }
+        hit_actor = h.actor;
+      } else {
+        normals_of_sample<L, F, H, HALF, false>(grid, table, scale, w0, b0, w1, b1, gs, grid, BoxWalk{}, v, g);
+      }
       const float len = fmaxf(sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]), 1e-12f);
       const float nx = sign * g[0] / len, ny = sign * g[1] / len, nz = sign * g[2] / len;
       const int64_t i = ray_sample_row(r, ray, s);
       if (geo) geo[i] = v;
       if (grad) grad[3 * i] = g[0], grad[3 * i + 1] = g[1], grad[3 * i + 2] = g[2];
       if (nrm) nrm[3 * i] = nx, nrm[3 * i + 1] = ny, nrm[3 * i + 2] = nz;
+      if constexpr (ACT) {
+        if (act.hit) act.hit[i] = hit_actor;
+        if (act.boxpos && hit_actor >= 0) act.boxpos[3 * i] = bp[0], act.boxpos[3 * i + 1] = bp[1], act.boxpos[3 * i + 2] = bp[2];
+      }
       if (w != 0.f) acc[0] += w * nx, acc[1] += w * ny, acc[2] += w * nz;
     }
   }
@@ -192,6 +272,7 @@ __global__ __launch_bounds__(256) void field_normals_kernel(
 
 struct NormalsLaunch {
   const nrhip_field* f;
+  const ActorArgs* act;  // NULL: the static form
   const int32_t* order;
   const float* weights;
   int wstride, G;
@@ -203,15 +284,28 @@ template <int L, int F, int H, bool HALF, class Rays>
 void launch_normals(const NormalsLaunch& a, const Rays& rd) {
   const nrhip_mlp& m = a.f->geo;
   const int blocks = grid_for(rd.R * a.G, 256);
-  field_normals_kernel<L, F, H, HALF, Rays><<<blocks, 256, 0, a.st>>>(
+  field_normals_kernel<L, F, H, HALF, Rays, NoActors><<<blocks, 256, 0, a.st>>>(
       to_dev(a.f->grid), a.f->table, a.f->static_scale, m.weight[0], m.bias[0], m.weight[1], m.bias[1],
-      a.f->use_sdf ? 1.f : -1.f, rd, a.order, a.weights, a.wstride, a.G, a.geo, a.grad, a.nrm, a.ray_nrm);
+      a.f->use_sdf ? 1.f : -1.f, rd, a.order, a.weights, a.wstride, a.G, a.geo, a.grad, a.nrm, a.ray_nrm, NoActors{});
+}
+
+template <int L, int F, int H, bool HALF, class Rays>
+void launch_normals_actors(const NormalsLaunch& a, const Rays& rd) {
+  const nrhip_mlp& m = a.f->geo;
+  const int blocks = grid_for(rd.R * a.G, 256);
+  field_normals_kernel<L, F, H, HALF, Rays, ActorArgs><<<blocks, 256, 0, a.st>>>(
+      to_dev(a.f->grid), a.f->table, a.f->static_scale, m.weight[0], m.bias[0], m.weight[1], m.bias[1],
+      a.f->use_sdf ? 1.f : -1.f, rd, a.order, a.weights, a.wstride, a.G, a.geo, a.grad, a.nrm, a.ray_nrm, *a.act);
 }
 
 // The instantiations: the (L, F, H) of every `PerSample, Static, F32` row of render_variants.h, fp32 and fp16 tables, both
 // sample layouts.  The other rows of the table select the empty specialisation.
 constexpr bool normals_row(Out out, Src src, Prod prod) {
   return out == Out::PerSample && src == Src::Static && prod == Prod::F32;
+}
+// ... and the actor form: the (L, F, H) of every `Composite, Actors, F32` row (the shapes the fused eval render covers)
+constexpr bool normals_actors_row(Out out, Src src, Prod prod) {
+  return out == Out::Composite && src == Src::Actors && prod == Prod::F32;
 }
 template <int L, int F, int H, bool ROW>
 struct NormalsRow {
@@ -227,6 +321,28 @@ struct NormalsRow<L, F, H, true> {
   }
 };
 
+template <int L, int F, int H, bool ROW>
+struct NormalsActorsRow {
+  template <class Rays>
+  static void go(const NormalsLaunch&, const Rays&) {}
+};
+template <int L, int F, int H>
+struct NormalsActorsRow<L, F, H, true> {
+  template <class Rays>
+  static void go(const NormalsLaunch& a, const Rays& rd) {
+    if (a.f->grid.param_dtype == 1) launch_normals_actors<L, F, H, true, Rays>(a, rd);
+    else launch_normals_actors<L, F, H, false, Rays>(a, rd);
+  }
+};
+
+bool normals_actors_shape(int L, int F, int H) {
+#define X(L_, F_, H_, O_, S_, P_) \
+  if (normals_actors_row(Out::O_, Src::S_, Prod::P_) && L == L_ && F == F_ && H == H_) return true;
+  NRHIP_RENDER_VARIANTS(X)
+#undef X
+  return false;
+}
+
 bool normals_shape(int L, int F, int H) {
 #define X(L_, F_, H_, O_, S_, P_) \
   if (normals_row(Out::O_, Src::S_, Prod::P_) && L == L_ && F == F_ && H == H_) return true;
@@ -238,8 +354,15 @@ bool normals_shape(int L, int F, int H) {
 template <class Rays>
 int dispatch_normals(const char* who, const NormalsLaunch& a, const Rays& rd) {
   const int L = a.f->grid.num_levels, F = a.f->grid.n_features, H = a.f->geo.hidden_dim;
+#define X(L_, F_, H_, O_, S_, P_)                                                                       \
+  if (a.act && normals_actors_row(Out::O_, Src::S_, Prod::P_) && L == L_ && F == F_ && H == H_) {       \
+    NormalsActorsRow<L_, F_, H_, normals_actors_row(Out::O_, Src::S_, Prod::P_)>::go(a, rd);            \
+    return check_launch(who);                                                                           \
+  }
+  NRHIP_RENDER_VARIANTS(X)
+#undef X
 #define X(L_, F_, H_, O_, S_, P_)                                                            \
-  if (normals_row(Out::O_, Src::S_, Prod::P_) && L == L_ && F == F_ && H == H_) {            \
+  if (!a.act && normals_row(Out::O_, Src::S_, Prod::P_) && L == L_ && F == F_ && H == H_) {            \
     NormalsRow<L_, F_, H_, normals_row(Out::O_, Src::S_, Prod::P_)>::go(a, rd);              \
     return check_launch(who);                                                                \
   }
@@ -249,22 +372,46 @@ int dispatch_normals(const char* who, const NormalsLaunch& a, const Rays& rd) {
   return NRHIP_ERR_UNSUPPORTED;
 }
 
-// what both entry points check of the field and of the outputs, before any count is looked at
+// what every entry point checks of the field and of the outputs, before any count is looked at.  actors: the actor form
+// (shapes: the `Composite, Actors, F32` rows; extra: whether one of its own outputs, hit / box_position, is asked for)
 int validate_normals(const char* who, const nrhip_field* f, const float* geo, const float* grad, const float* nrm,
-                     const float* ray_nrm) {
+                     const float* ray_nrm, bool actors = false, bool extra = false) {
   NR_REQUIRE(f, NRHIP_ERR_INVALID_ARG, "%s: field descriptor is NULL", who);
   if (int e = validate_grid(&f->grid)) return e;
   NR_REQUIRE(f->table && f->static_scale > 0.f, NRHIP_ERR_INVALID_ARG, "%s: NULL table or non-positive scale", who);
   const nrhip_mlp& m = f->geo;
   const int L = f->grid.num_levels, F = f->grid.n_features;
-  NR_REQUIRE(m.num_layers == 2 && m.in_dim == L * F && m.out_dim >= 1 && normals_shape(L, F, m.hidden_dim),
+  NR_REQUIRE(m.num_layers == 2 && m.in_dim == L * F && m.out_dim >= 1 &&
+                 (actors ? normals_actors_shape(L, F, m.hidden_dim) : normals_shape(L, F, m.hidden_dim)),
              NRHIP_ERR_UNSUPPORTED,
-             "%s: no instantiation for L=%d F=%d and a geometry MLP %d -> %d -> %d of %d layers (the `PerSample, Static, "
-             "F32` rows of csrc/render_variants.h, 2 layers); compose the operators instead",
-             who, L, F, m.in_dim, m.hidden_dim, m.out_dim, m.num_layers);
+             "%s: no instantiation for L=%d F=%d and a geometry MLP %d -> %d -> %d of %d layers (the `%s, F32` rows of "
+             "csrc/render_variants.h, 2 layers); compose the operators instead",
+             who, L, F, m.in_dim, m.hidden_dim, m.out_dim, m.num_layers, actors ? "Composite, Actors" : "PerSample, Static");
   NR_REQUIRE(m.weight[0] && m.weight[1], NRHIP_ERR_INVALID_ARG, "%s: a geometry weight is NULL", who);
   NR_REQUIRE(m.bias[0] && m.bias[1], NRHIP_ERR_UNSUPPORTED, "%s: the geometry MLP has a layer without bias; compose the operators instead", who);
-  NR_REQUIRE(geo || grad || nrm || ray_nrm, NRHIP_ERR_INVALID_ARG, "%s: every output is NULL", who);
+  NR_REQUIRE(geo || grad || nrm || ray_nrm || extra, NRHIP_ERR_INVALID_ARG, "%s: every output is NULL", who);
+  return NRHIP_OK;
+}
+
+// the actor form's own checks, after validate_normals: descriptors and candidate pointers, then the actor grid against the
+// static one (the condition of the fused eval render: the same F and storage type, La <= L)
+int validate_normals_actors(const char* who, const nrhip_field* f, const nrhip_actors* actors, const int32_t* cand_count,
+                            const int32_t* cand_actor, const float* cand_w2b, const float* ray_flip, int32_t* hit,
+                            float* boxpos, ActorArgs& act) {
+  if (int e = to_dev(actors, act.a)) return e;
+  NR_REQUIRE(cand_count && cand_actor && cand_w2b, NRHIP_ERR_INVALID_ARG, "%s: a candidate list is NULL", who);
+  if (int e = validate_grid(&actors->grid)) return e;
+  NR_REQUIRE(actors->tables && actors->actor_scale > 0.f, NRHIP_ERR_INVALID_ARG, "%s: NULL actor tables or non-positive actor scale", who);
+  NR_REQUIRE(actors->grid.n_features == f->grid.n_features && actors->grid.param_dtype == f->grid.param_dtype &&
+                 actors->grid.num_levels <= f->grid.num_levels,
+             NRHIP_ERR_UNSUPPORTED,
+             "%s: the actor grid (L=%d F=%d dtype %d) must share the static grid's F=%d and storage type %d with at most its "
+             "L=%d levels; compose the operators instead",
+             who, actors->grid.num_levels, actors->grid.n_features, actors->grid.param_dtype, f->grid.n_features,
+             f->grid.param_dtype, f->grid.num_levels);
+  act.a.flip = ray_flip;
+  act.cand_count = cand_count, act.cand_actor = cand_actor, act.cand_w2b = cand_w2b;
+  act.hit = hit, act.boxpos = boxpos;
   return NRHIP_OK;
 }
 
@@ -279,11 +426,10 @@ int lanes_per_ray(int64_t samples_per_ray) {  // the power of two >= the count, 
 
 using namespace nrhip;
 
-extern "C" int nrhip_field_normals(const nrhip_field* f, const nrhip_rays* rays, const float* weights,
-                                   int32_t weight_stride, float* geo, float* gradient, float* normals, float* ray_normals,
-                                   void* stream) {
-  const char* who = "field_normals";
-  if (int e = validate_normals(who, f, geo, gradient, normals, ray_normals)) return e;
+// the dense and the packed entry body, once for the static form (act == NULL) and the actor form
+static int normals_dense(const char* who, const nrhip_field* f, const ActorArgs* act, const nrhip_rays* rays,
+                         const float* weights, int32_t weight_stride, float* geo, float* gradient, float* normals,
+                         float* ray_normals, void* stream) {
   if (int e = validate_rays(rays)) return e;
   const int64_t R = rays->n_rays;
   const int S = rays->n_samples;
@@ -298,15 +444,14 @@ extern "C" int nrhip_field_normals(const nrhip_field* f, const nrhip_rays* rays,
       return check_launch(who);
     return NRHIP_OK;
   }
-  const NormalsLaunch a{f,   rays->order, weights, weight_stride ? weight_stride : S, lanes_per_ray(S),
-                        geo, gradient,    normals, ray_normals,                       st};
+  const NormalsLaunch a{f,   act,      rays->order, weights,     weight_stride ? weight_stride : S, lanes_per_ray(S),
+                        geo, gradient, normals,     ray_normals, st};
   return dispatch_normals(who, a, to_dev(*rays));
 }
 
-extern "C" int nrhip_field_normals_packed(const nrhip_field* f, const nrhip_packed_rays* rays, const float* weights,
-                                          float* geo, float* gradient, float* normals, float* ray_normals, void* stream) {
-  const char* who = "field_normals_packed";
-  if (int e = validate_normals(who, f, geo, gradient, normals, ray_normals)) return e;
+static int normals_packed(const char* who, const nrhip_field* f, const ActorArgs* act, const nrhip_packed_rays* rays,
+                          const float* weights, float* geo, float* gradient, float* normals, float* ray_normals,
+                          void* stream) {
   if (int e = validate_packed_rays(who, rays, true)) return e;
   const int64_t R = rays->n_rays, M = rays->n_samples;
   NR_REQUIRE(M == 0 || R > 0, NRHIP_ERR_INVALID_ARG, "%s: samples without rays", who);
@@ -319,6 +464,48 @@ extern "C" int nrhip_field_normals_packed(const nrhip_field* f, const nrhip_pack
     return NRHIP_OK;
   }
   // the dense rule on the mean count (both are shapes: no device read)
-  const NormalsLaunch a{f, rays->order, weights, 0, lanes_per_ray((M + R - 1) / R), geo, gradient, normals, ray_normals, st};
+  const NormalsLaunch a{f,   act,      rays->order, weights,     0, lanes_per_ray((M + R - 1) / R),
+                        geo, gradient, normals,     ray_normals, st};
   return dispatch_normals(who, a, to_dev(*rays));
+}
+
+extern "C" int nrhip_field_normals(const nrhip_field* f, const nrhip_rays* rays, const float* weights,
+                                   int32_t weight_stride, float* geo, float* gradient, float* normals, float* ray_normals,
+                                   void* stream) {
+  const char* who = "field_normals";
+  if (int e = validate_normals(who, f, geo, gradient, normals, ray_normals)) return e;
+  return normals_dense(who, f, nullptr, rays, weights, weight_stride, geo, gradient, normals, ray_normals, stream);
+}
+
+extern "C" int nrhip_field_normals_packed(const nrhip_field* f, const nrhip_packed_rays* rays, const float* weights,
+                                          float* geo, float* gradient, float* normals, float* ray_normals, void* stream) {
+  const char* who = "field_normals_packed";
+  if (int e = validate_normals(who, f, geo, gradient, normals, ray_normals)) return e;
+  return normals_packed(who, f, nullptr, rays, weights, geo, gradient, normals, ray_normals, stream);
+}
+
+extern "C" int nrhip_field_normals_actors(const nrhip_field* f, const nrhip_actors* actors, const nrhip_rays* rays,
+                                          const int32_t* cand_count, const int32_t* cand_actor, const float* cand_w2b,
+                                          const float* ray_flip, const float* weights, int32_t weight_stride, float* geo,
+                                          float* gradient, float* normals, float* ray_normals, int32_t* hit,
+                                          float* box_position, void* stream) {
+  const char* who = "field_normals_actors";
+  ActorArgs act;
+  if (int e = validate_normals(who, f, geo, gradient, normals, ray_normals, true, hit || box_position)) return e;
+  if (int e = validate_normals_actors(who, f, actors, cand_count, cand_actor, cand_w2b, ray_flip, hit, box_position, act))
+    return e;
+  return normals_dense(who, f, &act, rays, weights, weight_stride, geo, gradient, normals, ray_normals, stream);
+}
+
+extern "C" int nrhip_field_normals_packed_actors(const nrhip_field* f, const nrhip_actors* actors,
+                                                 const nrhip_packed_rays* rays, const int32_t* cand_count,
+                                                 const int32_t* cand_actor, const float* cand_w2b, const float* ray_flip,
+                                                 const float* weights, float* geo, float* gradient, float* normals,
+                                                 float* ray_normals, int32_t* hit, float* box_position, void* stream) {
+  const char* who = "field_normals_packed_actors";
+  ActorArgs act;
+  if (int e = validate_normals(who, f, geo, gradient, normals, ray_normals, true, hit || box_position)) return e;
+  if (int e = validate_normals_actors(who, f, actors, cand_count, cand_actor, cand_w2b, ray_flip, hit, box_position, act))
+    return e;
+  return normals_packed(who, f, &act, rays, weights, geo, gradient, normals, ray_normals, stream);
 }

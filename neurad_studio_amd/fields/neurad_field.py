@@ -427,37 +427,61 @@ class NeuRADField(nn.Module):
         return ov.to(torch.int32), rows, pdirs, idx
 
     # ---- Field.forward (neurad_field.py:128-152) ------------------------------------------------
-    def _check_normals(self, what: str) -> None:
-        """what the normals do not cover, refused by name (``what``: the flag that asked for them)"""
-        if self.hashgrid.has_actors():
-            raise NotImplementedError(f"{what} with dynamic actors: a sample inside an actor's box needs the box-frame "
-                                      "gradient rotated to the world, which is not implemented; normals cover the static "
-                                      "scene only")
+    def _check_normals(self, what: str, times: Optional[Tensor] = None) -> None:
+        """what the normals do not cover, refused by name (``what``: the flag that asked for them; ``times``: the rays'
+        times, which a field with dynamic actors needs -- the boxes are where they are at the ray's time)"""
+        hg = self.hashgrid
+        if hg.has_actors():
+            if times is None:
+                raise NotImplementedError(f"{what} with dynamic actors needs the rays' times: a sample inside an actor's box "
+                                          "takes the box-frame gradient rotated to the world, and the box is placed at the "
+                                          "ray's time (ray samples / bundles with `times`, or normals(..., times=...))")
+            if hg.training and hg.config.actor.flip_prob > 1e-7:
+                raise NotImplementedError(f"{what} with dynamic actors in training mode with actor.flip_prob > 0: the x flip "
+                                          "is drawn inside the forward and cannot be shared with the normals; the "
+                                          "reference renders normals outside training only (eval() the field)")
         if self.config.num_multisamples != 1:
             raise NotImplementedError(f"{what} with num_multisamples != 1: the normals are taken at the one gaussian mean "
                                       "of a sample")
 
     def normals_fused(self) -> bool:
-        """Does the fused normals kernel (csrc/normals.hip) cover this field?  The static scene of a fused configuration whose
-        geometry MLP has its biases; else ``ops.field_normals_operators`` composes the result from the operator kernels."""
-        return (not self.hashgrid.has_actors() and self.fused_supported()
-                and all(l.bias is not None for l in self.mlp_geo.layers))
+        """Does the fused normals kernel (csrc/normals.hip) cover this field?  A fused configuration whose geometry MLP has
+        its biases: the static scene, or a scene with dynamic actors of the shapes the fused eval render covers
+        (``fused_supported(with_actors=True)``: the actor grids share the static grid's features per level and storage type
+        with at most its levels); else ``ops.field_normals_operators`` composes the result from the operator kernels."""
+        return self.fused_supported(with_actors=True) and all(l.bias is not None for l in self.mlp_geo.layers)
 
     @torch.no_grad()
-    def normals(self, origins, directions, pixel_area, starts, ends, weights: Optional[Tensor] = None, want=None) -> dict:
+    def normals(self, origins, directions, pixel_area, starts, ends, weights: Optional[Tensor] = None, want=None,
+                times: Optional[Tensor] = None, actor_cand=None) -> dict:
         """``ops.field_normals`` for this field (per-ray origins / directions [R,3], pixel_area [R], starts / ends [R,S]): the
-        fused kernel where ``normals_fused()``, else the operator composition.  Nothing carries a gradient."""
-        self._check_normals("normals")
-        fn = ops.field_normals if self.normals_fused() else ops.field_normals_operators
-        return fn(self.field_spec(), origins.detach(), directions.detach(), pixel_area.detach().reshape(-1), starts.detach(),
-                  ends.detach(), weights=None if weights is None else weights.detach(), want=want)
+        fused kernel where ``normals_fused()``, else the operator composition.  Nothing carries a gradient.  A field with
+        dynamic actors needs ``times`` [R]; ``actor_cand``: the rays' candidate lists when the caller has them already
+        (they depend on the ray's line and time only), else they are computed here, with the eval-time actor edit.  A
+        sample inside a box then gets the normal of that actor's surface, rotated to the world (``want`` may name ``hit``
+        and ``box_position``)."""
+        self._check_normals("normals", times)
+        o, d, a = origins.detach(), directions.detach(), pixel_area.detach().reshape(-1)
+        starts, ends = starts.detach(), ends.detach()
+        weights = None if weights is None else weights.detach()
+        if not self.hashgrid.has_actors():
+            fn = ops.field_normals if self.normals_fused() else ops.field_normals_operators
+            return fn(self.field_spec(), o, d, a, starts, ends, weights=weights, want=want)
+        times = times.detach().reshape(-1)
+        actors = self._actor_cand(actor_cand, o, d, times, (a, starts, ends) if starts.shape[-1] else None)
+        if self.normals_fused():
+            return ops.field_normals(self.field_spec(), o, d, a, starts, ends, weights=weights, want=want, actors=actors)
+        return ops.field_normals_operators(self.field_spec(), o, d, a, starts, ends, weights=weights, want=want,
+                                           actors=actors, times=times, edit=self.hashgrid.actor_edit())
 
     def forward(self, ray_samples: RaySamples, compute_normals: bool = False) -> Dict[FieldHeadNames, Tensor]:
         """``compute_normals``: also NORMALS and GRADIENT, [R,S,3] (packed samples: [M,3]): GRADIENT = d geo_out / d position
         at the sample's gaussian mean (geo_out: the SDF, or the pre-exp logit in density mode), NORMALS = GRADIENT / max(|.|,
         1e-12) for an SDF -- towards free space -- and its negative in density mode (fields/base_field.py:80-101).  Both are
         returned DETACHED: no gradient flows through either head (an eikonal term would need the double backward).  The other
-        heads are what the call without the flag returns, bit for bit.  Refused with dynamic actors and num_multisamples != 1."""
+        heads are what the call without the flag returns, bit for bit.  With dynamic actors the ray samples' ``times`` place
+        the boxes (eval mode honours the actor edit); refused without them, in training mode with actor.flip_prob > 0, and
+        with num_multisamples != 1."""
         fr = ray_samples.frustums  # this package's RaySamples or the reference's (cameras/rays.py:142-187)
         if fr.starts.dim() == 2:
             # packed samples [M,1] with their own origins [M,3] (VolumetricSampler): M rays of one sample each through the
@@ -472,9 +496,10 @@ class NeuRADField(nn.Module):
         starts, ends = fr.starts[..., 0], fr.ends[..., 0]
         R, S = starts.shape
         if compute_normals:
-            self._check_normals("compute_normals=True")
+            times = sample_times(ray_samples) if self.hashgrid.has_actors() else None
+            self._check_normals("compute_normals=True", times)
             out = self.forward(ray_samples)
-            nrm = self.normals(o, d, a, starts, ends, want=("gradient", "normals"))
+            nrm = self.normals(o, d, a, starts, ends, want=("gradient", "normals"), times=times)
             out[FieldHeadNames.NORMALS], out[FieldHeadNames.GRADIENT] = nrm["normals"], nrm["gradient"]
             return out
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())

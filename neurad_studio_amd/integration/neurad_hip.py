@@ -129,8 +129,9 @@ class NeuRADHipModelConfig(NeuRADModelConfig):
     normals: bool = False
     """Eval outputs also carry ``normals`` [R,3] (csrc/normals.hip): the weighted sum of the non-sky samples' unit normals of
     the geometry head (the SDF's gradient, towards free space; its negative in density mode), normalised as the
-    reference's NormalsRenderer does; one more launch per eval chunk.  Only the fused eval route produces the key, and only
-    for a static scene (dynamic actors are refused by name).  False: no key, no launch."""
+    reference's NormalsRenderer does; one more launch per eval chunk.  Only the fused eval route produces the key.  With
+    dynamic actors a sample inside a box contributes that actor's normal, rotated to the world, at the ray's time (the
+    bundle's ``times``; the render's candidate lists are shared).  False: no key, no launch."""
     fused_image_eval: bool = False
     """Camera image metrics on the device (csrc/image_eval.hip, model_components/image_metrics.py): the image branch of
     get_image_metrics_and_images (models/neurad.py:568-587) takes ``psnr`` and ``ssim`` from one launch sequence and reads both

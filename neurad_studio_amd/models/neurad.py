@@ -56,7 +56,9 @@ class FusedEvalMixin:
     """True: the outputs also carry ``normals`` [R,3] (csrc/normals.hip): the weighted sum of the non-sky samples' unit
     normals of the geometry head, from the weights the fused render kernel hands out, normalised as NormalsRenderer does
     (/ (|.| + 1e-10)); one more launch per chunk, samples of weight zero cost nothing.  Like ``median_depth`` only this
-    fused eval route produces the key.  Refused for a field with dynamic actors or num_multisamples != 1."""
+    fused eval route produces the key.  A field with dynamic actors needs the bundle's ``times`` (a sample inside a box
+    contributes that actor's normal, rotated to the world; the candidate lists of the render are shared); refused without
+    them and for num_multisamples != 1."""
     reproduce_late_binding_quirk: bool = True
     """models/neurad.py:248 builds density_fns with a late-binding closure, so BOTH proposal rounds evaluate
     proposal_fields[1]; the fused sampler has to be told the same."""
@@ -69,7 +71,7 @@ class FusedEvalMixin:
         cfg = self.config
         sky = cfg.sampling.sky_distance
         if self.normals:
-            self.field._check_normals("normals=True")
+            self.field._check_normals("normals=True", getattr(ray_bundle, "times", None))
         self._scale_pixel_area(ray_bundle)
         _clamp_far_default_near(ray_bundle, sky)
         o, d = ray_bundle.origins.contiguous(), ray_bundle.directions.contiguous()
@@ -114,7 +116,8 @@ class FusedEvalMixin:
             nff["median_depth"] = ops.median_depth(out[3][:, :-1], starts[:, :-1], ends[:, :-1])
         if self.normals:  # over the non-sky samples too; NormalsRenderer's normalisation of the weighted sum
             n = self.field.normals(o, d, ray_bundle.pixel_area, starts[:, :-1], ends[:, :-1], weights=out[3][:, :-1],
-                                   want=("ray_normals",))["ray_normals"]
+                                   want=("ray_normals",), times=times if field_actors else None,
+                                   actor_cand=cand if field_actors else None)["ray_normals"]
             nff["normals"] = n / (torch.linalg.norm(n, dim=-1, keepdim=True) + 1e-10)
         for i, (pw, prs) in enumerate(zip(prop_weights, prop_ray_samples)):
             nff[f"prop_depth_{i}"] = self.renderer_depth(pw, prs)

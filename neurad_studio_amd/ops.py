@@ -1644,14 +1644,17 @@ def field_fwd_train_packed(fs: FieldSpec, origins, directions, pixel_area, t_sta
 
 # ---- surface normals from the geometry head (csrc/normals.hip; the contract: include/neurad_hip.h at nrhip_field_normals) ----
 NORMALS_OUTPUTS = ("geo", "gradient", "normals", "ray_normals")
+NORMALS_ACTOR_OUTPUTS = ("hit", "box_position")  # with ``actors`` only: whose normal a sample got, and where in that box
 normals_c = _lib.normals_c  # NRHIP_NORMALS_C(L, F, H): the constant of the stated error bound
+normals_actors_c = _lib.normals_actors_c  # NRHIP_NORMALS_ACTORS_C(La, F, H): the same for a sample inside a box
 
 
-def _normals_want(who: str, want, weights) -> Tuple[str, ...]:
+def _normals_want(who: str, want, weights, actors=None) -> Tuple[str, ...]:
     want = tuple(want) if want is not None else ("gradient", "normals") + (("ray_normals",) if weights is not None else ())
-    bad = [k for k in want if k not in NORMALS_OUTPUTS]
+    names = NORMALS_OUTPUTS + (NORMALS_ACTOR_OUTPUTS if actors is not None else ())
+    bad = [k for k in want if k not in names]
     if bad or not want:
-        raise ValueError(f"{who}: want must name some of {NORMALS_OUTPUTS}, got {want}")
+        raise ValueError(f"{who}: want must name some of {names}, got {want}")
     if "ray_normals" in want and weights is None:
         raise ValueError(f"{who}: ray_normals needs weights")
     return want
@@ -1659,20 +1662,44 @@ def _normals_want(who: str, want, weights) -> Tuple[str, ...]:
 
 def _normals_outputs(want, n: int, r: int, device) -> dict:
     mk = lambda *s: torch.empty(s, device=device, dtype=torch.float32)  # noqa: E731
-    shapes = {"geo": (n,), "gradient": (n, 3), "normals": (n, 3), "ray_normals": (r, 3)}
-    return {k: mk(*shapes[k]) for k in NORMALS_OUTPUTS if k in want}
+    shapes = {"geo": (n,), "gradient": (n, 3), "normals": (n, 3), "ray_normals": (r, 3), "box_position": (n, 3)}
+    out = {k: mk(*shapes[k]) for k in NORMALS_OUTPUTS + NORMALS_ACTOR_OUTPUTS[1:] if k in want}
+    if "hit" in want:
+        out["hit"] = torch.empty((n,), device=device, dtype=torch.int32)
+    return out
+
+
+def _normals_actor_args(who: str, actors, ray_flip, R: int):
+    """``actors`` = (ActorSpec, cand), cand one candidate list per RAY (``actor_prepare`` / ``actor_prepare_line``), and the
+    optional per-ray x flip -> (nrhip_actors, cand_count, cand_actor, cand_w2b, ray_flip, what keeps them alive)"""
+    spec, cand = actors
+    a, keep = spec.c_actors()
+    cnt, act, w2b = _c_ray_candidates(who, cand, R, a.max_candidates)
+    flip = _opt(ray_flip, "ray_flip")
+    if flip is not None and flip.reshape(-1).shape[0] != R:
+        raise ValueError(f"{who}: ray_flip must have one entry per ray ({R})")
+    return a, cnt, act, w2b, flip, keep
 
 
 def field_normals(fs: FieldSpec, origins, directions, pixel_area, starts, ends, weights: Optional[Tensor] = None,
-                  want=None, order: Optional[Tensor] = None) -> dict:
+                  want=None, order: Optional[Tensor] = None, actors=None, ray_flip: Optional[Tensor] = None) -> dict:
     """Normals of the geometry head at the samples' gaussian means, one kernel (nrhip_field_normals): ``geo`` [R,S] (the SDF
     or the pre-exp logit), ``gradient`` [R,S,3] = d geo / d position, ``normals`` [R,S,3] = +-gradient / max(|gradient|,
     1e-12) (+ for an SDF: towards free space; - in density mode) and, with ``weights`` [R,S] (a strided view is read in
     place), ``ray_normals`` [R,3] = sum_s w_s normals_s (not normalised; samples of weight zero are skipped).  ``want``
     names the outputs (default: gradient and normals, and ray_normals when weights are given) -> dict.  starts / ends as
     ``field_fwd`` (views into bin edges are read in place); ``order``: locality hint.  No gradient flows through any
-    output.  Shapes the kernel is not instantiated for raise; ``field_normals_operators`` composes the same result."""
-    want = _normals_want("field_normals", want, weights)
+    output.  Shapes the kernel is not instantiated for raise; ``field_normals_operators`` composes the same result.
+
+    ``actors`` = (ActorSpec, cand) with cand one candidate list per RAY (``actor_prepare``): a scene with dynamic actors
+    (nrhip_field_normals_actors).  A sample inside a box is differentiated through that actor's grid in the box frame and
+    its gradient rotated to the world, g_world = W^T diag(f, 1, 1) g_box, of several boxes the highest actor index; a sample
+    outside every box has the static call's bits.  ``ray_flip`` [R]: +-1 per ray (the training x flip).  ``want`` may then
+    also name ``hit`` [R,S] int32 (the winning actor or -1) and ``box_position`` [R,S,3] (the box-frame position after the
+    flip; untouched where hit < 0).  Without ``actors`` the call is the static one."""
+    if actors is None and ray_flip is not None:
+        raise ValueError("field_normals: ray_flip without actors")
+    want = _normals_want("field_normals", want, weights, actors)
     r, keep = _c_rays(origins, directions, pixel_area, starts, ends, order)
     f, keep2 = fs.c_field()
     R, S = r.n_rays, r.n_samples
@@ -1685,36 +1712,64 @@ def field_normals(fs: FieldSpec, origins, directions, pixel_area, starts, ends, 
         w = weights if (S <= 1 or weights.stride(1) == 1) and (R <= 1 or weights.stride(0) >= S) else weights.contiguous()
         wstride = w.stride(0) if R > 1 and S > 0 else max(S, 1)
     out = _normals_outputs(want, R * S, R, keep[0].device)
-    if any(v.numel() for v in out.values()):  # (an empty batch has nothing to write, and no address to write it to)
+    if not any(v.numel() for v in out.values()):  # (an empty batch has nothing to write, and no address to write it to)
+        pass
+    elif actors is None:
         launch("nrhip_field_normals", f, r, w, int(wstride), out.get("geo"), out.get("gradient"), out.get("normals"),
                out.get("ray_normals"))
+    else:
+        a, cnt, act, w2b, flip, keep3 = _normals_actor_args("field_normals", actors, ray_flip, R)
+        launch("nrhip_field_normals_actors", f, a, r, cnt, act, w2b, flip, w, int(wstride), out.get("geo"),
+               out.get("gradient"), out.get("normals"), out.get("ray_normals"), out.get("hit"), out.get("box_position"))
     return {k: (v if k == "ray_normals" else v.view(R, S, *v.shape[1:])) for k, v in out.items()}
 
 
 def field_normals_packed(fs: FieldSpec, origins, directions, pixel_area, t_starts, t_ends, segments,
-                         weights: Optional[Tensor] = None, want=None, order: Optional[Tensor] = None) -> dict:
+                         weights: Optional[Tensor] = None, want=None, order: Optional[Tensor] = None, actors=None,
+                         ray_flip: Optional[Tensor] = None) -> dict:
     """``field_normals`` on the march's packed samples (nrhip_field_normals_packed): per-RAY origins / directions [R,3] and
     pixel_area [R], per-sample t_starts / t_ends [M], segments int64 [R+1], weights [M] -> ``geo`` [M], ``gradient`` [M,3],
-    ``normals`` [M,3] at the packed sample index, ``ray_normals`` [R,3] (zeros for a ray without samples)."""
-    want = _normals_want("field_normals_packed", want, weights)
+    ``normals`` [M,3] at the packed sample index, ``ray_normals`` [R,3] (zeros for a ray without samples).  ``actors`` /
+    ``ray_flip`` as ``field_normals`` (cand: ``actor_prepare_line``; nrhip_field_normals_packed_actors), with ``hit`` [M] and
+    ``box_position`` [M,3]."""
+    if actors is None and ray_flip is not None:
+        raise ValueError("field_normals_packed: ray_flip without actors")
+    want = _normals_want("field_normals_packed", want, weights, actors)
     r, keep = _c_packed_rays("field_normals_packed", origins, directions, pixel_area, t_starts, t_ends, segments, order)
     f, keep2 = fs.c_field()
     R, M = r.n_rays, r.n_samples
     w = None if weights is None else _flat(weights, "weights", M)
     out = _normals_outputs(want, M, R, keep[0].device)
-    if any(v.numel() for v in out.values()):
+    if not any(v.numel() for v in out.values()):
+        pass
+    elif actors is None:
         launch("nrhip_field_normals_packed", f, r, w if M else None, out.get("geo"), out.get("gradient"), out.get("normals"),
                out.get("ray_normals"))
+    else:
+        a, cnt, act, w2b, flip, keep3 = _normals_actor_args("field_normals_packed", actors, ray_flip, R)
+        launch("nrhip_field_normals_packed_actors", f, a, r, cnt, act, w2b, flip, w if M else None, out.get("geo"),
+               out.get("gradient"), out.get("normals"), out.get("ray_normals"), out.get("hit"), out.get("box_position"))
     return out
 
 
 def field_normals_operators(fs: FieldSpec, origins, directions, pixel_area, starts, ends, weights: Optional[Tensor] = None,
-                            want=None) -> dict:
+                            want=None, actors=None, times: Optional[Tensor] = None, ray_flip: Optional[Tensor] = None,
+                            edit: Optional[dict] = None) -> dict:
     """The result of ``field_normals`` composed from four operator kernels, for any grid and geometry MLP: encode_fwd ->
     mlp_fwd(save_hidden) -> mlp_bwd of a unit cotangent on column 0 -> encode_bwd_rays on [N,1] rays (the origin gradient
     of a one-sample ray is the gradient at its position).  Two [N, L*F] round trips and the MLP's weight gradients, which
-    are dropped: the route for shapes the fused kernel does not cover and its timing baseline.  Same outputs and shapes."""
-    want = _normals_want("field_normals_operators", want, weights)
+    are dropped: the route for shapes the fused kernel does not cover and its timing baseline.  Same outputs and shapes.
+
+    ``actors`` = (ActorSpec, cand) as ``field_normals``, with the rays' ``times`` [R] (the pair kernels place the boxes
+    themselves): actor_encode splices the in-box rows over the static ones and names the winners; the winners' (sample,
+    actor) pairs go through actor_pair_positions -> the actor grids' lookup and input gradient (hashgrid_multi_*) -> the
+    rescale weights' std term -> actor_pair_positions_bwd with ray gradients on [N,1] rays, whose origin gradient is W^T
+    diag(f, 1, 1) g_box; the static rows of in-box samples get a zero cotangent.  No new kernel.  The pair kernels know
+    nothing of an eval-time actor ``edit``: with one the composition is refused by name."""
+    want = _normals_want("field_normals_operators", want, weights, actors)
+    if "box_position" in want:
+        raise NotImplementedError("field_normals_operators: box_position is the fused kernel's output (the composition hands "
+                                  "the pairs their contracted position only)")
     o, d, a = _ray_constants(origins, directions, pixel_area)
     starts, ends = _chk(starts, "starts"), _chk(ends, "ends")
     R, S = starts.shape
@@ -1722,12 +1777,44 @@ def field_normals_operators(fs: FieldSpec, origins, directions, pixel_area, star
     per = lambda t: t.repeat_interleave(S, dim=0) if S != 1 else t  # noqa: E731  (ray constants per sample)
     o1, d1, a1, s1, e1 = per(o), per(d), per(a), starts.reshape(n, 1), ends.reshape(n, 1)
     enc = encode_fwd(fs.grid, fs.table, fs.static_scale, o1, d1, a1, s1, e1)
+    hit = None
+    if actors is not None:
+        if times is None:
+            raise ValueError("field_normals_operators: actors need the rays' times")
+        if edit is not None:
+            raise NotImplementedError("field_normals_operators with dynamic actors and an eval-time actor edit: the pair "
+                                      "position kernels place the boxes from the trajectories and know nothing of the edit")
+        spec, cand = actors
+        _, hit = actor_encode(spec, cand, o, d, a, starts, ends, enc, ray_flip)  # rows spliced in place
     y, hidden = mlp_fwd(enc, fs.geo_w, fs.geo_b, save_hidden=True)
     cot = torch.zeros_like(y)
     cot[:, 0] = 1.0
     g_enc, _, _ = mlp_bwd(enc, hidden, cot, fs.geo_w, fs.geo_b)
-    g, _ = encode_bwd_rays(fs.grid, fs.table, fs.static_scale, o1, d1, a1, s1, e1, g_enc)
+    if hit is None or not bool((hit >= 0).any()):
+        g, _ = encode_bwd_rays(fs.grid, fs.table, fs.static_scale, o1, d1, a1, s1, e1, g_enc)
+    else:
+        inside = hit >= 0
+        g, _ = encode_bwd_rays(fs.grid, fs.table, fs.static_scale, o1, d1, a1, s1, e1,
+                               torch.where(inside[:, None], torch.zeros_like(g_enc), g_enc))
+        idx = inside.nonzero()[:, 0]           # the winners' pairs, in sample order
+        act = hit[idx].contiguous()
+        t1 = per(_chk(times.reshape(-1), "times"))
+        f1 = None if ray_flip is None else per(_chk(ray_flip.reshape(-1), "ray_flip"))
+        x01, cstd = actor_pair_positions(spec, o1, d1, a1, s1, e1, t1, idx, act, f1)
+        ag_, La, F = spec.grid, spec.grid.num_levels, spec.grid.features_per_level
+        raw = hashgrid_multi_fwd(ag_, spec.tables, act, x01).view(-1, La, F)
+        sc = ag_.scalings.to(x01.device)[None, :]
+        a2 = sc * 2 * cstd[:, None]
+        w = 1 / a2.clamp_min(1.0)                                  # the rescale weight and its derivative in cstd,
+        ge = g_enc[idx, : La * F].view(-1, La, F)                  # which clamp_min passes at equality
+        g_cstd = -((ge * raw).sum(-1) * torch.where(a2 >= 1, 2 * sc * w * w, torch.zeros_like(w))).sum(-1)
+        g_x01 = hashgrid_multi_bwd_input(ag_, spec.tables, act, x01, (ge * w[..., None]).reshape(-1, La * F).contiguous())
+        g_act = actor_pair_positions_bwd(spec, o1, d1, a1, s1, e1, t1, idx, act, f1, g_x01, g_cstd.contiguous(),
+                                         ray_grads=True)[2]
+        g = torch.where(inside[:, None], g_act, g)
     out = {}
+    if "hit" in want:
+        out["hit"] = hit.view(R, S)
     if "geo" in want:
         out["geo"] = y[:, 0].reshape(R, S)
     if "gradient" in want:
